@@ -622,6 +622,16 @@ def dry_run(a):
         dist.destroy_process_group()
 
 
+def write_outputs(out_dir, arrays):
+    """`--dump-outputs`: each array as out_dir/<name>.npy, floating point as float32, integers (token ids) as float64 (exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        v = v.detach().cpu()
+        v = v.to(torch.float32) if v.is_floating_point() else v.to(torch.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
+
+
 def _split_merge_path():
     """Which way the decode step merges its attention splits on this box (acai_decode_merge_in_launch): a silent change of path is a 3 % change
     of the headline."""
@@ -650,6 +660,8 @@ def main():
     ap.add_argument("--no-mae", action="store_true")
     ap.add_argument("--grad-comm-dtype", default="fp32", choices=["fp32", "bf16"], help="what the gradient buckets travel as at N > 1 (dist.GradAllReduce comm_dtype)")
     ap.add_argument("--leg-timeout", type=float, default=420.0, help="seconds the secondary legs may take before the line is printed without them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step left for a caller of "
+                    "the decode path (rank 0: token ids, log-probs, last logits) as DIR/<name>.npy, so that two builds can be compared output for output")
     ap.add_argument("--dry-run", action="store_true", help="control flow only, on the CPU over gloo: argument parsing, rank / leg selection, the collectives "
                     "around the timed regions and the JSON line's shape, with stand-in numbers (no kernel runs; `dry_run: true` marks the line)")
     a = ap.parse_args()
@@ -729,6 +741,12 @@ def main():
         run_steps(a.steps)
         _barrier_sync(dist)
         dt = time.perf_counter() - t0
+        # (outside the timed region) the device-side decode state as the last timed step left it, copied before the 256-step window below
+        # moves it on: what a caller of the decode path reads (sequences and log-probs up to the current position, that step's logits)
+        dump = None
+        if a.dump_outputs and rank == 0:
+            t = 1 + pos
+            dump = dict(seqs=eng.seqs[:eng.B, :t].clone(), logprobs=eng.logprobs[:eng.B, :t].clone(), logits=eng.ws["logits"][:eng.B].clone())
         # the same region over 256 steps (0.2 s): the driver's --steps 20 times 14 ms, this side field says what a longer window gives
         dt256 = None
         if a.steps != 256:
@@ -743,6 +761,8 @@ def main():
         dt256 = _max_over_ranks(dt256, dist, dev)
     tokens = world * a.batch * a.steps
     assert int(eng.step[0].item()) == 1 + pos  # every replay advanced the device-side position
+    if dump is not None:
+        write_outputs(a.dump_outputs, dump)
 
     roof = None
     S = lens[0]

@@ -771,3 +771,29 @@ def test_benchmarked_decode_shape_bf16_vs_oracle(dev):
             assert float(margin[first - 1]) <= 0.13, (b, first, float(margin[first - 1]))
         assert first >= 8, (b, first)
         assert md(lps[b, 1:first], olps[0, 1:first]) < 0.07
+
+
+def test_bench_dump_outputs_of_the_timed_decode(dev, tmp_path):
+    """`bench.py --dump-outputs DIR` (headline only): the decode state the last timed step left - ids and log-probs up to the current position,
+    that step's logits - as float .npy files; `--steps` sets the timed steps, and two runs with the same arguments write the same arrays."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--legs", "", "--no-cpu-baseline",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        runs.append({n: np.load(out / f"{n}.npy") for n in ("seqs", "logprobs", "logits")})
+    seqs, lps, logits = runs[0]["seqs"], runs[0]["logprobs"], runs[0]["logits"]
+    assert seqs.dtype == np.float64 and lps.dtype == np.float32 and logits.dtype == np.float32
+    assert seqs.shape == (8, 1 + 2 + 3) and lps.shape == seqs.shape and logits.shape == (8, 227)
+    assert (seqs == np.round(seqs)).all() and seqs.min() >= 0 and seqs.max() < 227
+    assert np.isfinite(lps).all() and np.isfinite(logits).all()
+    for n in ("seqs", "logprobs", "logits"):
+        assert np.array_equal(runs[1][n], runs[0][n]), n
