@@ -218,16 +218,20 @@ class GradAllReduce:
 
 
 # ---- self-check of the data-parallel step on the REAL path (HIP autograd Functions + GradAllReduce + FusedAdamW) ---------------------------
-def dp_parity_check(golden_dir, vocab_path, device, group=None):
+def dp_parity_check(golden_dir, vocab_path, device, group=None, scheduled_sampling=False):
     """Every rank trains the tiny MAE and the tiny teacher-forced ViTOMR of tests/golden/{mae_small,tf_small}.pt on ITS ragged shard of a
     global batch (global-count loss scaling, bucketed gradient all-reduce, `no_sync` accumulation for the teacher-forced step, fused AdamW)
     and, beside it, the single-process step on the whole global batch; returns the largest |difference| of gradients (relative to the
     tensor's largest gradient) and of the AdamW-updated parameters (relative to lr, on the elements whose gradient is not ~0: AdamW's
     normalised update turns rounding noise on a ~0 gradient into a +-lr move on either side) - fp32: ~1e-5.  Called by `bench.py --gpus N` (field `dp_parity_max_abs_diff`)
-    and by the 2-rank GPU test; needs an initialised process group (or none: world size 1)."""
+    and by the 2-rank GPU test; needs an initialised process group (or none: world size 1).
+
+    scheduled_sampling (off by default; tools/dp_parity.py --scheduled-sampling): one more leg, ScheduledSamplingViTOMR.forward_train at
+    tf_prob 0.4 with per-item injected draws - the decoder's parameters get their second gradient contribution written in place (autograd_path
+    _PGRAD / _TGRAD) while the hooks hand their bucket views to the all-reduce."""
     import os
 
-    from .models.models import MAE, FineTuneOMREncoder, MAELoss, OMRCELoss, OMRDecoder, TeacherForcedViTOMR
+    from .models.models import MAE, FineTuneOMREncoder, MAELoss, OMRCELoss, OMRDecoder, ScheduledSamplingViTOMR, TeacherForcedViTOMR
     from .optim import FusedAdamW
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -281,12 +285,12 @@ def dp_parity_check(golden_dir, vocab_path, device, group=None):
     fx = torch.load(os.path.join(golden_dir, "tf_small.pt"), map_location="cpu", weights_only=False)
     cfg = fx["cfg"]
 
-    def build_tf():
+    def build_tf(cls=TeacherForcedViTOMR):
         enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"], hidden_dim=cfg["enc_dim"],
                                  num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"], transformer_dropout=0.0)
         dec = OMRDecoder(cfg["max_len"], vocab_path, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"], num_heads=cfg["dec_heads"],
                          mlp_dim=cfg["dec_mlp"], transformer_dropout=0.0)
-        m = TeacherForcedViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"], transition_head_dropout=0.0)
+        m = cls(enc, None, dec, transition_head_dim=cfg["head_dim"], transition_head_dropout=0.0)
         m.load_state_dict(fx["state_dict"])
         return m.to(dev).train()
 
@@ -312,6 +316,32 @@ def dp_parity_check(golden_dir, vocab_path, device, group=None):
             loss.backward()
     ddp.finish()
     compare(dp, ref)
+
+    if scheduled_sampling:
+        # ---- scheduled sampling at tf_prob 0.4: every item carries its own draws (uniform (L,), exponential (L, V)); a batch takes their
+        # first T positions, so an item sees the same draws in its shard as in the global batch
+        g = torch.Generator().manual_seed(7)
+        its = [(fx["imgs"][i % 3].to(dev), fx["lmx"][(2 * i) % 3].to(dev)) for i in range(2 * world + 1)]
+        draws = [(torch.rand(cfg["max_len"], generator=g), torch.empty(cfg["max_len"], 227).exponential_(generator=g)) for _ in its]
+
+        def noise_of(sel):
+            T = max(its[i][1].numel() for i in sel) - 1
+            return dict(uniform=torch.stack([draws[i][0][:T] for i in sel]).to(dev), exponential=torch.stack([draws[i][1][:T] for i in sel]).to(dev))
+
+        ref, dp = build_tf(ScheduledSamplingViTOMR), build_tf(ScheduledSamplingViTOMR)
+        everything = list(range(len(its)))
+        pred, tgt = ref.forward_train(its, 0.4, 0.5, False, noise=noise_of(everything))
+        ce(pred, tgt).backward()
+        ddp = GradAllReduce(dp, bucket_mb=0.01, group=group)
+        ddp.zero_grad()
+        sel = shard_by_cost([it[0].shape[-1] * it[0].shape[-2] + 64 * it[1].numel() for it in its], world)[rank]
+        pred, tgt = dp.forward_train([its[i] for i in sel], 0.4, 0.5, False, noise=noise_of(sel))
+        (ce(pred, tgt) * global_mean_scale(float((tgt != ref.decoder.pad_idx).sum().item()), group=group, device=dev)).backward()
+        ddp.finish()
+        compare(dp, ref)
+        for m in (ref, dp):
+            FusedAdamW(m.parameters(), lr=1e-3, betas=(0.9, 0.95), weight_decay=0.05).step()
+        compare_params(dp, ref, 1e-3)
     t = torch.tensor([worst], dtype=torch.float64, device=dev)
     if dist.is_initialized() and world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)

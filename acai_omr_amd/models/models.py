@@ -745,12 +745,35 @@ class OMRCELoss(nn.Module):
         return autograd_path.ce_loss(pred, target_seqs, self.pad_idx, self.label_smoothing)
 
 
+def _gumbel_softmax(logits, tau, hard, exponential=None):
+    """F.gumbel_softmax (torch/nn/functional.py) restated with its exponential draw injectable, in the logits' dtype: -log of the draw, the
+    shifted logits and the softmax output are rounded to that dtype as CPU autocast rounds them (bf16 logits), the softmax itself runs in
+    fp32.  hard: the straight-through form y_hard - y_soft.detach() + y_soft."""
+    dt = logits.dtype
+    with torch.autocast(logits.device.type, enabled=False):
+        e = torch.empty_like(logits).exponential_() if exponential is None else exponential.to(device=logits.device, dtype=dt)
+        g = (-e.float().log()).to(dt) if dt != torch.float32 else -e.log()
+        z = (logits + g) / tau
+        y = z.float().softmax(-1).to(dt)
+        if hard:
+            y_hard = torch.zeros_like(y).scatter_(-1, y.argmax(-1, keepdim=True), 1.0)
+            y = y_hard - y.detach() + y
+    return y
+
+
 class ScheduledSamplingViTOMR(TeacherForcedViTOMR):
-    def sample_and_mix_seqs(self, teacher_forcing_prob, tf_input_seqs, tf_pred_logits, sample_tau, use_hard_sampling, device):
+    def sample_and_mix_seqs(self, teacher_forcing_prob, tf_input_seqs, tf_pred_logits, sample_tau, use_hard_sampling, device, noise=None):
         """Mix gold embeddings with expected embeddings of a Gumbel-softmax sample of the first pass (M:801-817).
-        Tiny (B,T,227)x(227,E) work; stays in PyTorch-ROCm as SURVEY section 2.2 allows."""
+        Tiny (B,T,227)x(227,E) work; stays in PyTorch-ROCm as SURVEY section 2.2 allows.
+
+        noise (extension, like MAE.forward(noises=)): the two raw draws {"uniform": (B, T) fp32, "exponential": (B, T, V)} in place of
+        torch.rand (M:803) and the exponential_ inside F.gumbel_softmax; None draws them from torch's generator.  The sample mask and the
+        Gumbel noise are derived from them here, as the reference derives them.  Under autocast the Gumbel-softmax keeps the reference's
+        rounding points (CPU autocast, the oracle's "bf16" convention): the draw, the Gumbel sum and the softmax output in the logits' dtype
+        (bf16), softmax arithmetic in fp32 - CUDA autocast would run log and softmax in fp32 and return fp32."""
         from ..train import autograd_path as AP
-        sample_mask = torch.rand(tf_input_seqs.shape, device=device) < (1 - teacher_forcing_prob)
+        u = noise["uniform"].to(device) if noise is not None else torch.rand(tf_input_seqs.shape, device=device)
+        sample_mask = u < (1 - teacher_forcing_prob)
         dec = self.decoder
         W = dec.vocab_embedding.weight
         B, T = tf_input_seqs.shape
@@ -759,13 +782,14 @@ class ScheduledSamplingViTOMR(TeacherForcedViTOMR):
         table = torch.cat([W, W[dec.pad_idx:dec.pad_idx + 1].detach()], 0)
         idx = torch.where(tok == dec.pad_idx, torch.full_like(tok, W.shape[0]), tok).to(torch.int32).contiguous()
         gold = AP.GatherRowsFn.apply(table, idx, None).view(B, T, -1)
-        distr = F.gumbel_softmax(tf_pred_logits.float(), tau=sample_tau, hard=use_hard_sampling)
+        distr = _gumbel_softmax(tf_pred_logits, sample_tau, use_hard_sampling, None if noise is None else noise["exponential"])
         # (B, T, V) x (V, E) (M:809) on the path's own GEMM kernels, forward and both gradients (round 2 left it to ATen / hipBLASLt)
         expected = AP.MatmulKNFn.apply(distr.reshape(B * T, -1), W, AP._prec(), _wc(dec)).view(B, T, -1).to(gold.dtype)
         expected = torch.cat([gold[:, 0:1, :], expected], dim=1)[:, :-1]
         return torch.where(sample_mask.unsqueeze(-1), expected, gold)
 
-    def forward_train(self, x, teacher_forcing_prob: float, sample_tau: float, use_hard_sampling: bool):
+    def forward_train(self, x, teacher_forcing_prob: float, sample_tau: float, use_hard_sampling: bool, noise=None):
+        """noise: the draws of sample_and_mix_seqs (extension; None = torch's generator)."""
         imgs, lmx_seqs = zip(*x)
         img_latent, latent_attention_mask = self.encoder(imgs)
         img_latent = self.transition_head(img_latent)
@@ -774,7 +798,8 @@ class ScheduledSamplingViTOMR(TeacherForcedViTOMR):
         from ..train.autograd_path import shared_cross_kv
         with shared_cross_kv():   # both passes attend to the same latent: its packed form and cross K/V projections are computed once
             tf_pred_logits = self.decoder(tf_input_seqs, img_latent, lmx_attention_mask, latent_attention_mask)
-            mixed = self.sample_and_mix_seqs(teacher_forcing_prob, tf_input_seqs, tf_pred_logits, sample_tau, use_hard_sampling, device)
+            mixed = self.sample_and_mix_seqs(teacher_forcing_prob, tf_input_seqs, tf_pred_logits, sample_tau, use_hard_sampling, device,
+                                             noise=noise)
             pred = self.decoder(mixed, img_latent, lmx_attention_mask, latent_attention_mask, token_idxs_input=False)
         return pred, target_seqs
 

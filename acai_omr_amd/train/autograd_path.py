@@ -572,12 +572,13 @@ class GeluFn(Function):
 
 class MatmulKNFn(Function):
     """y[M,N] = a[M,K] @ W[K,N] with W stored [K][N] (an embedding matrix used as a linear map: the expected embedding of scheduled sampling,
-    models.py:809).  Under autocast the operands are bf16 and so is y (what `@` does there); dA = dy W^T and dW = a^T dy on the same kernels."""
+    models.py:809).  Under autocast the operands are bf16 (a may arrive as bf16 already) and so is y (what `@` does there); dA = dy W^T and
+    dW = a^T dy on the same kernels."""
 
     @staticmethod
     def forward(ctx, a32, W, prec, wc):
         bf = prec == "bf16"
-        ac = ops.cast_bf16(a32.contiguous()) if bf else a32.contiguous()
+        ac = ops.cast_bf16(a32.contiguous()) if (bf and a32.dtype != torch.bfloat16) else a32.contiguous()
         Wc = wc.w(W, prec)
         ctx.save_for_backward(ac, Wc)
         ctx.bf = bf

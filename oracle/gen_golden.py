@@ -5,6 +5,9 @@ Run in the build container only (needs /root/reference, read-only):
     cd /root/reference && PYTHONDONTWRITEBYTECODE=1 PYTHONPATH=/root/reference:/root/repo \
         python /root/repo/oracle/gen_golden.py
 
+Append `--only PREFIX` to write only the fixtures whose name starts with PREFIX (`--only tf_ss`: the
+scheduled-sampling fixtures, which read their base fixtures from tests/golden/).
+
 cwd must be /root/reference because the reference opens "lmx_vocab.txt" cwd-relative
 (tests/test_kv_caching.py:8).  Nothing of the reference's source travels: a fixture holds
 seeded weights (state_dict tensors), inputs and the reference's outputs.  While generating,
@@ -20,7 +23,7 @@ from torch.amp import autocast
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from acai_omr.models.models import (MAE, FineTuneOMREncoder, GRPOViTOMR, MAELoss, OMRCELoss, OMRDecoder, OMREncoder,  # noqa: E402
-                                    Encoder, TeacherForcedViTOMR, batchify_and_split_lmx_seqs)
+                                    Encoder, ScheduledSamplingViTOMR, TeacherForcedViTOMR, batchify_and_split_lmx_seqs)
 from oracle import vitomr_oracle as O  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
@@ -35,14 +38,13 @@ def maxdiff(a, b):
     return float((a.float() - b.float()).abs().max())
 
 
-def build_vitomr(cfg, dropout_zero=False):
+def build_vitomr(cfg, dropout_zero=False, cls=TeacherForcedViTOMR):
     enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"],
                              hidden_dim=cfg["enc_dim"], num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"],
                              transformer_dropout=0.0 if dropout_zero else 0.05)
     dec = OMRDecoder(cfg["max_len"], VOCAB, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"],
                      num_heads=cfg["dec_heads"], mlp_dim=cfg["dec_mlp"], transformer_dropout=0.0 if dropout_zero else 0.1)
-    return TeacherForcedViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"],
-                               transition_head_dropout=0.0 if dropout_zero else 0.05)
+    return cls(enc, None, dec, transition_head_dim=cfg["head_dim"], transition_head_dropout=0.0 if dropout_zero else 0.05)
 
 
 def run_reference_greedy(vitomr, imgs, cfg, use_autocast, cache_dtype):
@@ -341,30 +343,132 @@ def gen_ce_label_smoothing(name, seed):
     torch.save(fx, os.path.join(OUT, name + ".pt"))
 
 
-def main():
+SS_GRAD_NAMES = ["decoder.vocab_embedding.weight", "decoder.unembed.weight", "decoder.pos_embedding",
+                 "decoder.decoder_blocks.layers.0.multihead_attn.in_proj_weight", "decoder.decoder_blocks.layers.1.norm1.weight",
+                 "transition_head.0.weight", "encoder.fine_tune_blocks.layers.0.linear1.weight"]
+
+
+def gen_scheduled_sampling(name, base, tf_prob, tau, hard, use_autocast, seed):
+    """ScheduledSamplingViTOMR.forward_train (M:798-834) + OMRCELoss + backward on the weights, images and LMX sequences of the teacher-forced
+    fixture `base` (referenced by name, not copied), dropout 0.  The step's two random draws - torch.rand for the sample mask (M:803) and the
+    exponential_ inside F.gumbel_softmax (M:808) - are captured while the reference runs and stored, so that the oracle and the HIP path can be
+    fed the same draws.  use_autocast: forward and loss under autocast("cpu", bfloat16), backward outside (omr_teacher_force_train.py:115-120)."""
+    bfx = torch.load(os.path.join(OUT, base + ".pt"), map_location="cpu", weights_only=False)
+    cfg, sd = bfx["cfg"], bfx["state_dict"]
+    vitomr = build_vitomr(cfg, dropout_zero=True, cls=ScheduledSamplingViTOMR)
+    vitomr.load_state_dict(sd)
+    vitomr.train()
+    batch = list(zip(bfx["imgs"], bfx["lmx"]))
+    uni, expo = [], []
+    rand, exponential_ = torch.rand, torch.Tensor.exponential_
+
+    def rec_rand(*a, **k):
+        out = rand(*a, **k)
+        uni.append(out.detach().clone())
+        return out
+
+    def rec_exponential_(self, *a, **k):
+        out = exponential_(self, *a, **k)
+        expo.append(out.detach().clone())
+        return out
+
+    torch.manual_seed(seed)
+    torch.rand, torch.Tensor.exponential_ = rec_rand, rec_exponential_
+    try:
+        with autocast(device_type="cpu", dtype=torch.bfloat16, enabled=use_autocast):
+            pred, tgt = vitomr.forward_train(batch, tf_prob, tau, hard)
+            loss = OMRCELoss(vitomr.decoder.pad_idx)(pred, tgt)
+    finally:
+        torch.rand, torch.Tensor.exponential_ = rand, exponential_
+    assert len(uni) == 1 and len(expo) == 1, (len(uni), len(expo))
+    loss.backward()
+    noise = dict(uniform=uni[0], exponential=expo[0])
+    # one gold position past <bos> whose draw is moved onto the threshold itself, fp32(1 - tf_prob): `uniform < 1 - tf_prob` (M:803) keeps it
+    # gold, as the draw the reference made did - the step is unchanged, and a `<=` would sample there
+    inp0 = batchify_and_split_lmx_seqs(tuple(bfx["lmx"]), 1, "cpu")[0]
+    thr = torch.tensor(1 - tf_prob, dtype=torch.float32)
+    cand = ((noise["uniform"] >= thr) & (inp0 != 1)).nonzero().tolist()
+    b, t = [bt for bt in cand if bt[1] > 0][0]
+    noise["uniform"][b, t] = thr
+    B, T = tgt.shape
+    assert noise["uniform"].shape == (B, T) and noise["uniform"].dtype == torch.float32
+    assert noise["exponential"].shape == (B, T, 227) and noise["exponential"].dtype == (torch.bfloat16 if use_autocast else torch.float32)
+    # the mask must mix: sampled AND gold positions among the valid tokens past <bos> (else the fixture degenerates to teacher forcing)
+    inp = batchify_and_split_lmx_seqs(tuple(bfx["lmx"]), 1, "cpu")[0]
+    sampled = noise["uniform"] < (1 - tf_prob)
+    live = inp != 1
+    live[:, 0] = False
+    assert bool((sampled & live).any()) and bool((~sampled & live).any())
+    params = dict(vitomr.named_parameters())
+    grads = {n: params[n].grad.detach().float().clone() for n in SS_GRAD_NAMES}
+    if not hard:   # <pad> row: reached through distr @ W (M:809); hard: dW only reaches the drawn one-hot rows
+        assert float(grads["decoder.vocab_embedding.weight"][1].abs().max()) > 0
+    prec = "bf16" if use_autocast else "fp32"
+    fx = dict(base=base, tf_prob=tf_prob, tau=tau, hard=hard, prec=prec, noise=noise, threshold_draw=(b, t), pred=pred.detach().float(), target=tgt,
+              loss=loss.detach().float(), grads=grads, n_sampled=int((sampled & live).sum()), n_gold=int((~sampled & live).sum()))
+
+    sdg = {k: v.clone().requires_grad_(v.is_floating_point()) for k, v in sd.items()}
+    opred, otgt = O.scheduled_sampling_forward(batch, sdg, cfg["enc_heads"], cfg["dec_heads"], cfg["P"], prec, tf_prob, tau, hard, noise)
+    oloss = O.ce_loss(opred, otgt)
+    oloss.backward()
+    assert torch.equal(otgt, tgt)
+    valid = tgt != 1
+    dp = maxdiff(opred[valid], pred[valid])
+    dl = abs(float(oloss) - float(loss))
+    print(f"[{name}] sampled {fx['n_sampled']} gold {fx['n_gold']}  pred max|d| = {dp:.3e} loss {float(loss):.6f} d = {dl:.3e}")
+    if use_autocast:
+        # the CPU-autocast restatement: same rounding points, another accumulation order (bars of the config-3 GPU tests)
+        assert dp < 0.05 * max(1.0, float(pred.float().abs().max())) and dl < 2e-3 * max(1.0, abs(float(loss)))
+    else:
+        assert dp < 1e-4 and dl < 1e-5
+    for n in SS_GRAD_NAMES:
+        g, og = grads[n], sdg[n].grad
+        dg = maxdiff(og, g)
+        rel = dg / max(1e-30, float(g.abs().max()))
+        cos = float(torch.nn.functional.cosine_similarity(og.double().flatten(), g.double().flatten(), dim=0))
+        print(f"[{name}]   grad {n}: max|d| = {dg:.3e}  rel {rel:.3e}  cos {cos:.7f}  (|g|max {float(g.abs().max()):.3e})")
+        if use_autocast:
+            assert rel < 2e-2 and cos > 0.9999, (n, rel, cos)
+        else:
+            assert dg < 1e-4 * max(1.0, float(g.abs().max())), n
+    torch.save(fx, os.path.join(OUT, name + ".pt"))
+
+
+def main(only=None):
+    """only: a fixture-name prefix; the generators of other fixtures are skipped (their inputs are still drawn, in order)."""
     os.makedirs(OUT, exist_ok=True)
+
+    def want(name):
+        return only is None or name.startswith(only)
+
     g = torch.Generator().manual_seed(1234)
     small = dict(P=4, pe_h=6, pe_w=10, ft_depth=1, enc_layers=2, enc_dim=32, enc_heads=2, enc_mlp=64, head_dim=64,
                  dec_layers=2, dec_dim=48, dec_heads=4, dec_mlp=96, max_len=24, gen_len=12, lmx_lens=[5, 9, 3])
     imgs_small = [torch.rand(1, 8, 16, generator=g), torch.rand(1, 24, 40, generator=g), torch.rand(1, 12, 20, generator=g)]
-    gen_vitomr("vitomr_small", small, imgs_small, seed=11)
-    gen_teacher_forced("tf_small", dict(small, ft_depth=2), imgs_small, seed=12)
+    if want("vitomr_small"):
+        gen_vitomr("vitomr_small", small, imgs_small, seed=11)
+    if want("tf_small"):
+        gen_teacher_forced("tf_small", dict(small, ft_depth=2), imgs_small, seed=12)
 
     # real head dims (d_h = 64) and 16x16 patches at toy depth
     dh64 = dict(P=16, pe_h=4, pe_w=8, ft_depth=2, enc_layers=2, enc_dim=128, enc_heads=2, enc_mlp=256, head_dim=256,
                 dec_layers=2, dec_dim=128, dec_heads=2, dec_mlp=256, max_len=24, gen_len=10, lmx_lens=[7, 4])
     imgs_dh64 = [torch.rand(1, 32, 64, generator=g), torch.rand(1, 64, 128, generator=g)]
-    gen_vitomr("vitomr_dh64", dh64, imgs_dh64, seed=21)
-    gen_teacher_forced("tf_dh64", dh64, imgs_dh64, seed=22)
+    if want("vitomr_dh64"):
+        gen_vitomr("vitomr_dh64", dh64, imgs_dh64, seed=21)
+    if want("tf_dh64"):
+        gen_teacher_forced("tf_dh64", dh64, imgs_dh64, seed=22)
 
     # odd head count (tests/test_vitomr.py:12 convention, num_heads=1): torch slow path even in eval (SURVEY Q12)
     odd = dict(small, enc_heads=1, dec_heads=1, enc_dim=10, enc_mlp=1, dec_dim=12, dec_mlp=5, head_dim=7, ft_depth=2)
-    gen_vitomr("vitomr_odd", odd, imgs_small, seed=31)
+    if want("vitomr_odd"):
+        gen_vitomr("vitomr_odd", odd, imgs_small, seed=31)
 
     mae_cfg = dict(mask_ratio=0.75, P=4, pe_h=6, pe_w=10, enc_dim=32, dec_dim=16,
                    enc_kwargs=dict(num_layers=2, num_heads=2, mlp_dim=64), dec_kwargs=dict(num_layers=2, num_heads=2, mlp_dim=32))
     tg = [torch.rand(1, 8, 16, generator=g), torch.rand(1, 24, 40, generator=g), torch.rand(1, 12, 20, generator=g)]
-    gen_mae("mae_small", mae_cfg, imgs_small, tg, seed=41)
+    if want("mae_small"):
+        gen_mae("mae_small", mae_cfg, imgs_small, tg, seed=41)
 
     # the reference's own debug checkpoint (debug_pretrained_mae.pth: hidden 10, 2+2 layers, 1 head, mlp 1)
     dbg = torch.load("debug_pretrained_mae.pth")
@@ -372,23 +476,42 @@ def main():
                    enc_kwargs=dict(num_layers=2, num_heads=1, mlp_dim=1), dec_kwargs=dict(num_layers=2, num_heads=1, mlp_dim=1))
     dimgs = [torch.rand(1, 32, 64, generator=g), torch.rand(1, 48, 32, generator=g)]
     # keep the fixture small: store only the PE rows these images touch
-    gen_mae("mae_debug_ckpt", dbg_cfg, dimgs, dimgs, seed=51, sd_override=dbg)
+    if want("mae_debug_ckpt"):
+        gen_mae("mae_debug_ckpt", dbg_cfg, dimgs, dimgs, seed=51, sd_override=dbg)
 
-    gen_encoder_variants("omr_encoder_interp", seed=61)
+    if want("omr_encoder_interp"):
+        gen_encoder_variants("omr_encoder_interp", seed=61)
 
     # ---- round 2 additions (own generators: the fixtures above stay bit-identical) ----------------------------------------
     # GRPO rollout policy (M:988-1049): 2 memories x 3 rollouts on the small decoder (d_h = 12), 2 x 4 at d_h = 64
-    gen_grpo("grpo_small", small, seed=71, lat_lens=[9, 5], group=3, top_k=5, temperature=1.2, max_actions=10)
-    gen_grpo("grpo_dh64", dh64, seed=72, lat_lens=[24, 40], group=4, top_k=8, temperature=0.9, max_actions=9)
+    if want("grpo_small"):
+        gen_grpo("grpo_small", small, seed=71, lat_lens=[9, 5], group=3, top_k=5, temperature=1.2, max_actions=10)
+    if want("grpo_dh64"):
+        gen_grpo("grpo_dh64", dh64, seed=72, lat_lens=[24, 40], group=4, top_k=8, temperature=0.9, max_actions=9)
     # teacher-forced TRAIN step whose images exceed the PE grid: batchify interpolates in every mode (M:304-332) and the
     # gradient reaches pos_embedding through the bilinear interpolation (full fine-tune: pos_embedding trainable, M:667-677)
     g2 = torch.Generator().manual_seed(4321)
     interp = dict(small, ft_depth=2, lmx_lens=[5, 9, 3])
     imgs_interp = [torch.rand(1, 8, 16, generator=g2), torch.rand(1, 28, 44, generator=g2), torch.rand(1, 12, 48, generator=g2)]
-    gen_teacher_forced("tf_interp", interp, imgs_interp, seed=81)
-    gen_ce_label_smoothing("ce_label_smoothing", seed=91)
+    if want("tf_interp"):
+        gen_teacher_forced("tf_interp", interp, imgs_interp, seed=81)
+    if want("ce_label_smoothing"):
+        gen_ce_label_smoothing("ce_label_smoothing", seed=91)
+
+    # ---- scheduled sampling at 0 < tf_prob < 1 (M:798-834) with its draws captured: each fixture names its base teacher-forced fixture
+    if want("tf_ss_small"):
+        gen_scheduled_sampling("tf_ss_small", "tf_small", 0.7, 0.5, False, use_autocast=False, seed=101)
+    if want("tf_ss_small_hard"):
+        gen_scheduled_sampling("tf_ss_small_hard", "tf_small", 0.3, 0.5, True, use_autocast=False, seed=102)
+    if want("tf_ss_dh64"):
+        gen_scheduled_sampling("tf_ss_dh64", "tf_dh64", 0.7, 0.5, False, use_autocast=False, seed=103)
+    if want("tf_ss_small_bf16"):
+        gen_scheduled_sampling("tf_ss_small_bf16", "tf_small", 0.7, 0.5, False, use_autocast=True, seed=104)
     print("golden vectors written to", OUT)
 
 
 if __name__ == "__main__":
-    main()
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", default=None, help="fixture-name prefix, e.g. tf_ss: write only those fixtures")
+    main(ap.parse_args().only)

@@ -574,3 +574,60 @@ def rollout_generate(mem, lens_s, sd, num_heads, prec, max_actions, top_k, tempe
     if return_logits:
         return out + (torch.stack(all_logits, 1),)
     return out
+
+
+# ---- scheduled sampling (reference acai_omr/models/models.py:798-834) ---------------------------------------------------------------------
+def gumbel_softmax(logits, tau, hard, exponential, prec):
+    """F.gumbel_softmax (torch/nn/functional.py) with its exponential draw given: y_soft = softmax((logits - log(exponential)) / tau); hard:
+    the straight-through y_hard - y_soft.detach() + y_soft (M:808).  Under "bf16" the logits are bf16 values and CPU autocast leaves
+    gumbel_softmax in bf16: the draw, -log of it, the shifted logits, the softmax output and the straight-through sums are each rounded to
+    bf16 (softmax arithmetic in fp32)."""
+    e = exponential.to(logits.dtype)
+    if prec == "bf16":
+        z = rbf16(rbf16(logits + rbf16(-torch.log(rbf16(e)))) / tau)
+        y = rbf16(torch.softmax(z, dim=-1))
+    else:
+        y = torch.softmax((logits - torch.log(e)) / tau, dim=-1)
+    if hard:
+        y_hard = torch.zeros_like(y).scatter(-1, y.argmax(dim=-1, keepdim=True), 1.0)
+        y = _r(_r(y_hard - y.detach(), prec) + y, prec)
+    return y
+
+
+def sample_and_mix_seqs(tf_prob, tf_input_seqs, tf_pred_logits, tau, hard, noise, sd, prec, pad_idx=1, prefix="decoder."):
+    """ScheduledSamplingViTOMR.sample_and_mix_seqs (M:801-817) with the draws given: noise = {"uniform": (B, T), "exponential": (B, T, V)},
+    what torch.rand (M:803) and the exponential_ inside F.gumbel_softmax (M:808) drew.  tf_input_seqs (B, T) ids, tf_pred_logits (B, T, V).
+    Returns the mixed input embeddings (B, T, E).
+
+    - gold embeddings (M:805): nn.Embedding(padding_idx=<pad>) (M:403-404) - the <pad> row is read but receives no gradient;
+    - expected embeddings (M:809): distr @ W, so every row of W - <pad>'s too - gets a gradient; under autocast a bf16 matmul (bf16 operands,
+      fp32 accumulation, bf16 result) that torch.cat with the fp32 gold stem promotes back to fp32 exactly;
+    - right shift (M:812-814): the gold <bos> embedding in front, the last expected row dropped;
+    - mask (M:802-803): uniform < 1 - tf_prob, True = take the expected embedding."""
+    W = sd[prefix + "vocab_embedding.weight"]
+    sample_mask = noise["uniform"] < (1 - tf_prob)
+    gold = torch.where((tf_input_seqs == pad_idx).unsqueeze(-1), W[pad_idx].detach(), W[tf_input_seqs])
+    distr = gumbel_softmax(tf_pred_logits, tau, hard, noise["exponential"], prec)
+    if prec == "bf16":
+        expected = rbf16(rbf16(distr) @ (W if WEIGHTS_PREROUNDED else rbf16(W)))
+    else:
+        expected = distr @ W
+    expected = torch.cat([gold[:, 0:1, :], expected.to(gold.dtype)], dim=1)[:, :-1]
+    return torch.where(sample_mask.unsqueeze(-1), expected, gold)
+
+
+def scheduled_sampling_forward(batch, sd, enc_heads, dec_heads, P, prec, tf_prob, tau, hard, noise, enc_kind="omr_ft", pad_idx=1):
+    """ScheduledSamplingViTOMR.forward_train (M:819-834) with injected draws (see sample_and_mix_seqs): a teacher-forced first pass, the
+    mixed embeddings, a second decoder pass on them (token_idxs_input=False) over the same memory.  Plain torch, differentiable, in the
+    dtype of sd (float64 state dicts give a float64 reference under prec "fp32").  Returns padded pred (B, T, V), target (B, T)."""
+    imgs, lmx = zip(*batch)
+    lat, lens_s = encoder_forward(list(imgs), sd, "encoder.", P, enc_heads, enc_kind, prec)
+    mem = transition_head(lat, sd, prec)
+    inp, tgt, pad_mask = batchify_and_split_lmx_seqs(lmx, pad_idx)
+    B, T = inp.shape
+    lens_t = [T] * B
+    keep = [~pad_mask[i] for i in range(B)]
+    logits = decoder_forward_tf(inp.reshape(-1), mem, lens_t, lens_s, sd, dec_heads, prec, tgt_pad_keep=keep).reshape(B, T, -1)
+    mixed = sample_and_mix_seqs(tf_prob, inp, logits, tau, hard, noise, sd, prec, pad_idx)
+    pred = decoder_forward_tf(mixed.reshape(B * T, -1), mem, lens_t, lens_s, sd, dec_heads, prec, token_idxs_input=False, tgt_pad_keep=keep)
+    return pred.reshape(B, T, -1), tgt

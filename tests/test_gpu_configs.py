@@ -178,6 +178,54 @@ def test_config3_teacher_forced_bf16_step_at_size_vs_oracle(dev):
         assert r < 2e-2 and c > 0.9999, (n, r, c)            # measured 3e-3 ... 5e-3, cosine 0.999996
 
 
+def test_config3_scheduled_sampling_bf16_step_at_size_vs_oracle(dev):
+    """Config 3's step as the reference trains it for 35 of its 40 fine-tune epochs and as bench.py's tf_step times it: the FULL-SIZE
+    ScheduledSamplingViTOMR.forward_train at tf_prob = 0.7, tau = 0.5 (soft) under autocast(bf16), one 256 x 1024 system, T = 371, with
+    injected draws - so the expected-embedding branch carries gradient: MatmulKNFn's dW and d(distr) at E = 1024, V = 227, and the second
+    contributions of every decoder parameter.  Against autograd through the oracle's bf16 scheduled_sampling_forward on the same weights and
+    draws, with the bars and gradient names of test_config3_teacher_forced_bf16_step_at_size_vs_oracle plus the embedding table.  The bf16
+    target is the CPU-autocast restatement (Gumbel-softmax rounded to bf16 where CPU autocast rounds it), not CUDA autocast's fp32 softmax."""
+    import oracle.vitomr_oracle as O
+    from acai_omr_amd.config import ENCODER_FINE_TUNE_DEPTH, MAX_LMX_SEQ_LEN, NUM_DECODER_LAYERS, PATCH_SIZE, PE_MAX_HEIGHT, PE_MAX_WIDTH
+    from acai_omr_amd.models.models import FineTuneOMREncoder, OMRCELoss, OMRDecoder, ScheduledSamplingViTOMR
+    _threads()
+    torch.manual_seed(4)
+    enc = FineTuneOMREncoder(PATCH_SIZE, PE_MAX_HEIGHT, PE_MAX_WIDTH, ENCODER_FINE_TUNE_DEPTH, transformer_dropout=0.0)
+    dec = OMRDecoder(MAX_LMX_SEQ_LEN, VOCAB, num_layers=NUM_DECODER_LAYERS, transformer_dropout=0.0)
+    m = ScheduledSamplingViTOMR(enc, None, dec, transition_head_dropout=0.0)
+    _perturb(m, unembed_scale=3.0)
+    g = torch.Generator().manual_seed(6)
+    imgs = [torch.rand(1, 256, 1024, generator=g)]
+    lmx = [torch.cat([torch.tensor([0]), torch.randint(3, 227, (370,), generator=g), torch.tensor([2])])]
+    T = 371
+    noise = dict(uniform=torch.rand(1, T, generator=g), exponential=torch.empty(1, T, 227, dtype=torch.bfloat16).exponential_(generator=g))
+    names = ("decoder.unembed.weight", "decoder.decoder_blocks.layers.0.multihead_attn.in_proj_weight", "decoder.decoder_blocks.layers.11.linear2.weight",
+             "transition_head.0.weight", "encoder.fine_tune_blocks.layers.11.linear1.weight", "encoder.fine_tune_blocks.layers.0.self_attn.in_proj_weight",
+             "decoder.vocab_embedding.weight")
+    sd = {k: v.detach().clone().requires_grad_(k in names) for k, v in m.state_dict().items()}
+    pred_o, tgt_o = O.scheduled_sampling_forward(list(zip(imgs, lmx)), sd, 12, 16, PATCH_SIZE, "bf16", 0.7, 0.5, False, noise)
+    loss_o = O.ce_loss(pred_o, tgt_o, 1)
+    loss_o.backward()
+    m = m.to(dev).train()
+    batch = [(im.to(dev), sq.to(dev)) for im, sq in zip(imgs, lmx)]
+    with autocast(device_type="cuda", dtype=torch.bfloat16):
+        pred, tgt = m.forward_train(batch, 0.7, 0.5, False, noise=noise)
+        loss = OMRCELoss(m.decoder.pad_idx)(pred, tgt)
+    loss.backward()
+    assert torch.equal(tgt.cpu(), tgt_o) and pred.shape == (1, T, 227)
+    assert 0 < int((noise["uniform"][0, 1:] < 0.3).sum()) < T - 1
+    valid = tgt_o != 1
+    e_pred = md(pred.float().cpu()[valid], pred_o.detach()[valid])
+    print(f"config3 scheduled sampling at size: loss {float(loss):.5f} oracle {float(loss_o):.5f}  logits max|d| {e_pred:.3e} "
+          f"(|logit| max {float(pred_o.abs().max()):.2f})")
+    assert abs(float(loss) - float(loss_o)) < 2e-3 * max(1.0, abs(float(loss_o)))     # measured 1.2e-4 (loss 6.66)
+    assert e_pred < 0.05 * max(1.0, float(pred_o.abs().max()))                        # measured 5.1e-2 (|logit| max 5.6)
+    params = dict(m.named_parameters())
+    for n in names:
+        r, c = relerr(params[n].grad, sd[n].grad), cosine(params[n].grad, sd[n].grad)
+        print(f"  grad {n}: rel max err {r:.3e} cosine {c:.6f}")
+        assert r < 2e-2 and c > 0.9999, (n, r, c)            # measured 3.9e-3 ... 5.7e-3, cosine >= 0.999983 (CPU oracle ~10 s)
+
 # ---- configs 2 and 3 at their BATCH sizes: a size-independent property instead of the (too slow) CPU oracle ---------------------------------
 def _grads(model, names):
     ps = dict(model.named_parameters())
@@ -734,6 +782,26 @@ def test_data_parallel_step_on_the_hip_path_two_ranks(dev):
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
     assert out["world"] == 2 and out["dp_parity_max_abs_diff"] < 1e-4, out
+
+
+def test_data_parallel_scheduled_sampling_step_two_ranks(dev):
+    """The same two-rank check with its scheduled-sampling leg (tools/dp_parity.py --scheduled-sampling): forward_train at tf_prob = 0.4 with
+    per-item injected draws, sharded over two gloo ranks on this card, == the single-process global-batch step.  The decoder's parameters
+    get their second gradient contribution written in place (autograd_path._PGRAD) while GradAllReduce's hooks hand bucket views to the
+    all-reduce."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    port = 29500 + os.getpid() % 200
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+                        "--master-port", str(port), os.path.join(root, "tools", "dp_parity.py"), "--backend", "gloo", "--scheduled-sampling"],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
+    out = json.loads(line)
+    assert out["world"] == 2 and out["scheduled_sampling"] and out["dp_parity_max_abs_diff"] < 1e-4, out
 
 
 def test_benchmarked_decode_shape_bf16_vs_oracle(dev):

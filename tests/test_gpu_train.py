@@ -424,6 +424,125 @@ def test_scheduled_sampling_forward_train(dev):
     assert torch.equal(m2.forward_eval(batch)[1].cpu(), fx["target"])
 
 
+def _ss_model(dev, cfg, sd):
+    from acai_omr_amd.models.models import FineTuneOMREncoder, OMRDecoder, ScheduledSamplingViTOMR
+    enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"], hidden_dim=cfg["enc_dim"],
+                             num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"], transformer_dropout=0.0)
+    dec = OMRDecoder(cfg["max_len"], VOCAB, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"], num_heads=cfg["dec_heads"], mlp_dim=cfg["dec_mlp"],
+                     transformer_dropout=0.0)
+    m = ScheduledSamplingViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"], transition_head_dropout=0.0)
+    m.load_state_dict(sd)
+    return m.to(dev).train()
+
+
+@pytest.mark.parametrize("fuse", [True, False], ids=["fused", "plain"])
+@pytest.mark.parametrize("name", ["tf_ss_small", "tf_ss_small_hard", "tf_ss_dh64", "tf_ss_small_bf16"])
+def test_scheduled_sampling_train_step_vs_reference(dev, name, fuse):
+    """ScheduledSamplingViTOMR.forward_train (models.py:798-834) at 0 < tf_prob < 1 against the imported reference's step
+    (tests/golden/tf_ss_*.pt, oracle/gen_golden.py): the reference's own draws go in through `noise=`, so pred, loss and the gradients -
+    the whole embedding table's (the <pad> row gets a gradient from distr @ W only), the cross attention's K / V rows (shared by the two
+    passes), the decoder's positional table, a LayerNorm, the head and the encoder - must be the reference's.  Both with the second-contribution
+    fusions on (autograd_path.PGRAD_FUSE / _KV_GRAD_FUSE) and off: each form must meet the reference's bars by itself.
+
+    fp32 fixtures: the bars of test_teacher_forced_train_step_vs_reference.  tf_ss_small_bf16: autocast(bf16) forward + loss, backward outside;
+    the target is the reference under CPU autocast (the project's bf16 convention: Gumbel noise, shifted logits and softmax output rounded to
+    bf16, a bf16 distr @ W) - not CUDA autocast, which would run the softmax in fp32 - held to the config-3 bars."""
+    from torch.amp import autocast
+    from acai_omr_amd.models.models import OMRCELoss
+    from acai_omr_amd.train import autograd_path as AP
+    fx = load_golden(name)
+    base = load_golden(fx["base"])
+    m = _ss_model(dev, base["cfg"], base["state_dict"])
+    batch = list(zip(base["imgs"], base["lmx"]))
+    bf = fx["prec"] == "bf16"
+    AP.PGRAD_FUSE, AP._KV_GRAD_FUSE = fuse, fuse
+    try:
+        with autocast(device_type="cuda", dtype=torch.bfloat16, enabled=bf):
+            pred, tgt = m.forward_train(batch, fx["tf_prob"], fx["tau"], fx["hard"], noise=fx["noise"])
+            loss = OMRCELoss(m.decoder.pad_idx)(pred, tgt)
+        loss.backward()
+    finally:
+        AP.PGRAD_FUSE, AP._KV_GRAD_FUSE = True, True
+    assert torch.equal(tgt.cpu(), fx["target"])
+    valid = fx["target"] != 1
+    e_pred, e_loss = md(pred.float().cpu()[valid], fx["pred"][valid]), abs(float(loss) - float(fx["loss"]))
+    params = dict(m.named_parameters())
+    print(f"{name} {'fused' if fuse else 'plain'}: pred max|d| {e_pred:.3e}  loss d {e_loss:.3e}")
+    if not bf:
+        assert e_pred < 1e-3                                                     # measured <= 1.1e-6
+        assert e_loss < 1e-4                                                     # measured <= 1e-6
+        for n, gref in fx["grads"].items():
+            e = md(params[n].grad, gref)
+            print(f"  grad {n}: max|d| {e:.3e} (|g|max {float(gref.abs().max()):.3e})")
+            assert e < 3e-4 * max(1.0, float(gref.abs().max())), n              # measured <= 1.4e-7
+            # these gradients are ~1e-2: the absolute bar above is ~2 % of them; held to their own scale as well
+            assert e < 1e-3 * float(gref.abs().max()), n                        # measured <= 1e-6 relative
+        if not fx["hard"]:   # the <pad> row (~1e-5): only distr @ W reaches it
+            gp, rp = params["decoder.vocab_embedding.weight"].grad[1], fx["grads"]["decoder.vocab_embedding.weight"][1]
+            assert float(rp.abs().max()) > 0 and md(gp, rp) < 1e-3 * float(rp.abs().max())
+    else:
+        assert e_pred < 0.05 * max(1.0, float(fx["pred"].abs().max()))         # measured 1.2e-2
+        assert e_loss < 2e-3 * max(1.0, abs(float(fx["loss"])))                 # measured 2.1e-4 (loss 5.33)
+        for n, gref in fx["grads"].items():
+            g = params[n].grad.detach().double().cpu().flatten()
+            r = md(params[n].grad, gref) / float(gref.abs().max())
+            c = float(g @ gref.double().flatten() / (g.norm() * gref.double().norm()))
+            print(f"  grad {n}: rel max err {r:.3e} cosine {c:.7f}")
+            assert r < 2e-2 and c > 0.9999, (n, r, c)                           # measured <= 8.2e-3, cosine >= 0.999985
+
+
+def _kn_case(BT, E, dt, seed):
+    """distr (BT, 227): rows of a softmax (what MatmulKNFn multiplies), W (227, E), dy (BT, E); bf16 operands rounded before the reference."""
+    g = torch.Generator().manual_seed(seed)
+    a = torch.softmax(3.0 * torch.randn(BT, 227, generator=g), dim=-1)
+    W = torch.randn(227, E, generator=g) * 0.05
+    dy = torch.randn(BT, E, generator=g) * 1e-3
+    if dt == torch.bfloat16:
+        a, W, dy = (t.to(dt).float() for t in (a, W, dy))
+    return a, W, dy
+
+
+def _rel(got, ref, absref):
+    """max |got - ref| over the largest sum of |products| (the scale a summation-order error lives on)."""
+    return float((got.double().cpu() - ref).abs().max() / absref.abs().max())
+
+
+@pytest.mark.parametrize("BT,E", [(30, 48), (513, 128), (8208, 1024), (30, 1024), (8208, 48), (8195, 1024)])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_matmul_kn_gemms_vs_float64(dev, BT, E, dtype):
+    """The three GEMMs autograd_path.MatmulKNFn issues for scheduled sampling's distr @ W (models.py:809) at the vocabulary's width (V = 227)
+    against float64: forward gemm(trans_w) with K = 227, d(distr) gemm_nt with K = E, dW gemm(trans_a, trans_w) with K = B*T rows - the
+    split-K reduction into a slice of the zeroed arena (ops._ZEROS), which test_gemm_transposed_variants (K <= 256) never reaches; 8208 / 8195
+    rows end inside a K block.  dW is then called again at another shape: both results right, and the first one unchanged by the second
+    (no stale or shared arena slice)."""
+    from acai_omr_amd import ops
+    tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
+    a, W, dy = _kn_case(BT, E, tdt, BT * 7 + E)
+    ad, Wd, dyd = (t.to(dev).to(tdt).contiguous() for t in (a, W, dy))
+    A, Wr, D = a.double(), W.double(), dy.double()
+    # forward: y[BT, E] = a @ W, W stored [K = 227][N = E]
+    y = ops.gemm(ad, Wd, trans_w=True, out_dtype=tdt)
+    ry = _rel(y.float(), A @ Wr, A @ Wr.abs())
+    # d(distr)[BT, 227] = dy @ W^T
+    da = ops.gemm_nt(dyd, Wd, out_dtype=torch.float32)
+    rda = _rel(da, D @ Wr.t(), D.abs() @ Wr.abs().t())
+    # dW[227, E] = a^T dy, K = BT
+    dW = ops.gemm(ad, dyd, trans_a=True, trans_w=True, out_dtype=torch.float32)
+    ref_dW = A.t() @ D
+    rdw = _rel(dW, ref_dW, A.t() @ D.abs())
+    first = dW.clone()
+    a2, _, dy2 = _kn_case(BT // 2 + 77, E, tdt, BT + E)
+    dW2 = ops.gemm(a2.to(dev).to(tdt), dy2.to(dev).to(tdt), trans_a=True, trans_w=True, out_dtype=torch.float32)
+    rdw2 = _rel(dW2, a2.double().t() @ dy2.double(), a2.double().t() @ dy2.double().abs())
+    torch.cuda.synchronize()
+    print(f"BT {BT} E {E} {dtype}: fwd {ry:.2e}  d(distr) {rda:.2e}  dW {rdw:.2e}  dW again {rdw2:.2e}")
+    assert ry < (8e-3 if dtype == "bf16" else 3e-5), ry       # bf16: the output is rounded to bf16 (measured <= 3.6e-3); fp32 <= 1e-6
+    assert rda < 3e-5, rda                                    # measured <= 3.5e-7
+    assert rdw < 3e-5 and rdw2 < 3e-5, (rdw, rdw2)            # measured <= 5.6e-7
+    assert torch.equal(dW, first)
+    assert dW.data_ptr() != dW2.data_ptr()
+
+
 def test_twice_used_parameters_accumulate_in_place(dev):
     """Scheduled sampling with 0 < teacher_forcing_prob < 1: both decoder passes carry gradient, so every decoder parameter (and the encoder's,
     through the two passes' cross attention) gets two contributions in one backward.  The second contribution is accumulated by the
