@@ -30,6 +30,17 @@ Precision modes (`prec`):
 
 Reference citations are `acai_omr/models/models.py` (M:) and
 `acai_omr/models/kv_caching.py` (K:) line numbers.
+
+Train-mode dropout (`drop=`, default None: eval, no dropout anywhere): a hook
+`drop(site, kind, **geometry)` called at every dropout site torch's layers have,
+in their execution order; `site` is the module path of the nn.Dropout (or of the
+nn.MultiheadAttention whose probabilities are dropped) in the model's state dict.
+  kind "add":  geometry lens (the packed rows' sequence lengths), cols; returns
+               None (no dropout) or a (sum lens, cols) multiplier - keep / (1 - p);
+  kind "attn": geometry lens_q, lens_k, heads; returns None or a function
+               (sequence i, head h) -> (lens_q[i], lens_k[i]) multiplier of the
+               softmax probabilities in front of P V (the lse stays undropped).
+Decoder sites also get pass_ (0, or 1 for scheduled sampling's second pass).
 """
 import math
 
@@ -83,29 +94,42 @@ def layer_norm(x, w, b, eps):
     return (x - mean) / torch.sqrt(var + eps) * w + b
 
 
-def sdpa(q, k, v, keep_mask, prec):
+def sdpa(q, k, v, keep_mask, prec, drop_mult=None):
     """softmax(q k^T / sqrt(d)) v for ONE head. q (Lq,d) k,v (Lk,d); keep_mask bool
-    (Lq,Lk) True = attend, or None."""
+    (Lq,Lk) True = attend, or None; drop_mult: (Lq,Lk) dropout multiplier of the
+    probabilities (F.multi_head_attention_forward: dropout after softmax, before P V)."""
     d = q.shape[-1]
     s = (q @ k.t()) * (1.0 / math.sqrt(d))
     if keep_mask is not None:
         s = s.masked_fill(~keep_mask, NEG_INF)
     p = torch.softmax(s, dim=-1)
+    if drop_mult is not None:
+        p = p * drop_mult.to(p.dtype)
     return _r(p @ v, prec)
 
 
+def dropout(x, drop, site, lens, prec, **geom):
+    """nn.Dropout at `site` on packed rows x (sum lens, C) through the `drop` hook (identity when there is none or it returns None).
+    Under "bf16" a bf16 activation stays bf16 (x is a bf16 value: the product is rounded back)."""
+    if drop is None:
+        return x
+    m = drop(site, "add", lens=list(lens), cols=x.shape[1], **geom)
+    return x if m is None else _r(x * m.to(x.dtype), prec)
+
+
 def mha_packed(xq, xkv, lens_q, lens_k, in_w, in_b, out_w, out_b, num_heads, causal, prec,
-               key_keep=None):
+               key_keep=None, drop=None, site=None, **geom):
     """nn.MultiheadAttention on packed streams: xq (sum Lq, E), xkv (sum Lk, E).
     Each sequence attends only inside itself (== key padding mask on a padded batch).
     key_keep: optional list of bool (Lk_i,) per sequence, True = key may be attended
-    (tgt_key_padding_mask restated)."""
+    (tgt_key_padding_mask restated).  drop / site: attention-probability dropout (module docstring)."""
     E = xq.shape[-1]
     dh = E // num_heads
     q = linear(xq, in_w[:E], in_b[:E], prec)
     kv = linear(xkv, in_w[E:], in_b[E:], prec)
     k, v = kv[:, :E], kv[:, E:]
     out = torch.empty_like(q)
+    dm = drop(site, "attn", lens_q=list(lens_q), lens_k=list(lens_k), heads=num_heads, **geom) if drop is not None else None
     oq = ok = 0
     for i, (lq, lk) in enumerate(zip(lens_q, lens_k)):
         keep = None
@@ -116,7 +140,8 @@ def mha_packed(xq, xkv, lens_q, lens_k, in_w, in_b, out_w, out_b, num_heads, cau
             keep = kk if keep is None else (keep & kk)
         for h in range(num_heads):
             sl = slice(h * dh, (h + 1) * dh)
-            out[oq:oq + lq, sl] = sdpa(q[oq:oq + lq, sl], k[ok:ok + lk, sl], v[ok:ok + lk, sl], keep, prec)
+            out[oq:oq + lq, sl] = sdpa(q[oq:oq + lq, sl], k[ok:ok + lk, sl], v[ok:ok + lk, sl], keep, prec,
+                                       None if dm is None else dm(i, h))
         oq += lq
         ok += lk
     return linear(out, out_w, out_b, prec)
@@ -174,37 +199,49 @@ def pe_slice(pe, hp, wp, allow_interp):
 # ----------------------------------------------------------------------------
 # transformer stacks (post-LN, M:30-34 / torch transformer.py:952-956)
 # ----------------------------------------------------------------------------
-def encoder_layer(x, lens, sd, p, num_heads, prec):
+def encoder_layer(x, lens, sd, p, num_heads, prec, drop=None):
+    """nn.TransformerEncoderLayer, post-LN; dropout sites (torch transformer.py _sa_block / _ff_block): the attention probabilities,
+    dropout1 after the out-projection, dropout after the activation, dropout2 after linear2."""
     a = mha_packed(x, x, lens, lens, sd[p + "self_attn.in_proj_weight"], sd[p + "self_attn.in_proj_bias"],
-                   sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"], num_heads, False, prec)
+                   sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"], num_heads, False, prec,
+                   drop=drop, site=p + "self_attn")
+    a = dropout(a, drop, p + "dropout1", lens, prec)
     x = layer_norm(x + a, sd[p + "norm1.weight"], sd[p + "norm1.bias"], 1e-5)
     h = gelu(linear(x, sd[p + "linear1.weight"], sd[p + "linear1.bias"], prec), prec)
+    h = dropout(h, drop, p + "dropout", lens, prec)
     h = linear(h, sd[p + "linear2.weight"], sd[p + "linear2.bias"], prec)
+    h = dropout(h, drop, p + "dropout2", lens, prec)
     return layer_norm(x + h, sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-5)
 
 
-def encoder_stack(x, lens, sd, prefix, num_heads, prec):
+def encoder_stack(x, lens, sd, prefix, num_heads, prec, drop=None):
     """nn.TransformerEncoder: layers.{i}.* then optional final norm (eps 1e-6, M:33)."""
     i = 0
     while f"{prefix}layers.{i}.norm1.weight" in sd:
-        x = encoder_layer(x, lens, sd, f"{prefix}layers.{i}.", num_heads, prec)
+        x = encoder_layer(x, lens, sd, f"{prefix}layers.{i}.", num_heads, prec, drop)
         i += 1
     if prefix + "norm.weight" in sd:
         x = layer_norm(x, sd[prefix + "norm.weight"], sd[prefix + "norm.bias"], 1e-6)
     return x
 
 
-def decoder_layer_tf(x, mem, lens_t, lens_s, sd, p, num_heads, prec, tgt_keep):
-    """nn.TransformerDecoderLayer teacher-forced (torch transformer.py:1144-1153)."""
+def decoder_layer_tf(x, mem, lens_t, lens_s, sd, p, num_heads, prec, tgt_keep, drop=None, pass_=0):
+    """nn.TransformerDecoderLayer teacher-forced (torch transformer.py:1144-1153).  Dropout sites: self-attention probabilities, dropout1,
+    cross-attention probabilities, dropout2, dropout after the activation, dropout3."""
     a = mha_packed(x, x, lens_t, lens_t, sd[p + "self_attn.in_proj_weight"], sd[p + "self_attn.in_proj_bias"],
                    sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"], num_heads, True, prec,
-                   key_keep=tgt_keep)
+                   key_keep=tgt_keep, drop=drop, site=p + "self_attn", pass_=pass_)
+    a = dropout(a, drop, p + "dropout1", lens_t, prec, pass_=pass_)
     x = layer_norm(x + a, sd[p + "norm1.weight"], sd[p + "norm1.bias"], 1e-5)
     c = mha_packed(x, mem, lens_t, lens_s, sd[p + "multihead_attn.in_proj_weight"], sd[p + "multihead_attn.in_proj_bias"],
-                   sd[p + "multihead_attn.out_proj.weight"], sd[p + "multihead_attn.out_proj.bias"], num_heads, False, prec)
+                   sd[p + "multihead_attn.out_proj.weight"], sd[p + "multihead_attn.out_proj.bias"], num_heads, False, prec,
+                   drop=drop, site=p + "multihead_attn", pass_=pass_)
+    c = dropout(c, drop, p + "dropout2", lens_t, prec, pass_=pass_)
     x = layer_norm(x + c, sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-5)
     h = gelu(linear(x, sd[p + "linear1.weight"], sd[p + "linear1.bias"], prec), prec)
+    h = dropout(h, drop, p + "dropout", lens_t, prec, pass_=pass_)
     h = linear(h, sd[p + "linear2.weight"], sd[p + "linear2.bias"], prec)
+    h = dropout(h, drop, p + "dropout3", lens_t, prec, pass_=pass_)
     return layer_norm(x + h, sd[p + "norm3.weight"], sd[p + "norm3.bias"], 1e-5)
 
 
@@ -227,16 +264,16 @@ def encoder_embed(imgs, sd, prefix, P, allow_interp, prec):
     return x, lens
 
 
-def encoder_forward(imgs, sd, prefix, P, num_heads, kind="omr_ft", prec="fp32"):
+def encoder_forward(imgs, sd, prefix, P, num_heads, kind="omr_ft", prec="fp32", drop=None):
     """kind: "base" (Encoder, encoder_blocks), "omr" (OMREncoder, interpolation allowed),
     "omr_ft" (FineTuneOMREncoder: frozen_blocks then fine_tune_blocks).  Returns packed latent, lens."""
     x, lens = encoder_embed(imgs, sd, prefix, P, allow_interp=(kind != "base"), prec=prec)
     if kind == "omr_ft":
         if f"{prefix}frozen_blocks.layers.0.norm1.weight" in sd:
-            x = encoder_stack(x, lens, sd, prefix + "frozen_blocks.", num_heads, prec)
-        x = encoder_stack(x, lens, sd, prefix + "fine_tune_blocks.", num_heads, prec)
+            x = encoder_stack(x, lens, sd, prefix + "frozen_blocks.", num_heads, prec, drop)
+        x = encoder_stack(x, lens, sd, prefix + "fine_tune_blocks.", num_heads, prec, drop)
     else:
-        x = encoder_stack(x, lens, sd, prefix + "encoder_blocks.", num_heads, prec)
+        x = encoder_stack(x, lens, sd, prefix + "encoder_blocks.", num_heads, prec, drop)
     return x, lens
 
 
@@ -251,9 +288,10 @@ def encoder_forward_padded(imgs, sd, prefix, P, num_heads, kind="omr_ft", prec="
     return out, mask
 
 
-def transition_head(x, sd, prec, prefix="transition_head."):
-    """Linear, GELU, Dropout(eval: identity), Linear (M:655-660)."""
+def transition_head(x, sd, prec, prefix="transition_head.", drop=None, lens=None):
+    """Linear, GELU, Dropout (`drop`; none = eval: identity), Linear (M:655-660).  lens: the packed rows' sequence lengths (for the hook)."""
     h = gelu(linear(x, sd[prefix + "0.weight"], sd[prefix + "0.bias"], prec), prec)
+    h = dropout(h, drop, prefix + "2", [x.shape[0]] if lens is None else lens, prec)
     return linear(h, sd[prefix + "3.weight"], sd[prefix + "3.bias"], prec)
 
 
@@ -261,7 +299,7 @@ def transition_head(x, sd, prec, prefix="transition_head."):
 # A6/A7: OMRDecoder teacher-forced + KV-cached decode (M:378-528, K:5-302)
 # ----------------------------------------------------------------------------
 def decoder_forward_tf(inputs, mem, lens_t, lens_s, sd, num_heads, prec, prefix="decoder.",
-                       token_idxs_input=True, tgt_pad_keep=None):
+                       token_idxs_input=True, tgt_pad_keep=None, drop=None, pass_=0):
     """OMRDecoder.forward on packed streams (M:445-483).  inputs: packed token ids (sum T,)
     or packed embeddings (sum T, E).  Positions restart at 0 for each sequence (M:465-466).
     tgt_pad_keep: list of bool (T_i,) True = not <pad> (tgt_key_padding_mask inverted)."""
@@ -273,7 +311,7 @@ def decoder_forward_tf(inputs, mem, lens_t, lens_s, sd, num_heads, prec, prefix=
     x = x + sd[prefix + "pos_embedding"][pos]
     i = 0
     while f"{prefix}decoder_blocks.layers.{i}.norm1.weight" in sd:
-        x = decoder_layer_tf(x, mem, lens_t, lens_s, sd, f"{prefix}decoder_blocks.layers.{i}.", num_heads, prec, tgt_pad_keep)
+        x = decoder_layer_tf(x, mem, lens_t, lens_s, sd, f"{prefix}decoder_blocks.layers.{i}.", num_heads, prec, tgt_pad_keep, drop, pass_)
         i += 1
     x = layer_norm(x, sd[prefix + "decoder_blocks.norm.weight"], sd[prefix + "decoder_blocks.norm.bias"], 1e-6)
     return linear(x, sd[prefix + "unembed.weight"], sd[prefix + "unembed.bias"], prec)
@@ -425,17 +463,17 @@ def batchify_and_split_lmx_seqs(lmx_seqs, pad_idx):
     return inp, tgt, inp == pad_idx
 
 
-def teacher_forced_forward(batch, sd, enc_heads, dec_heads, P, prec, enc_kind="omr_ft", pad_idx=1):
-    """TeacherForcedViTOMR.forward (M:722-736).  Returns padded pred (B, T, V), target (B, T)."""
+def teacher_forced_forward(batch, sd, enc_heads, dec_heads, P, prec, enc_kind="omr_ft", pad_idx=1, drop=None):
+    """TeacherForcedViTOMR.forward (M:722-736).  Returns padded pred (B, T, V), target (B, T).  drop: train-mode dropout hook."""
     imgs, lmx = zip(*batch)
-    lat, lens_s = encoder_forward(list(imgs), sd, "encoder.", P, enc_heads, enc_kind, prec)
-    mem = transition_head(lat, sd, prec)
+    lat, lens_s = encoder_forward(list(imgs), sd, "encoder.", P, enc_heads, enc_kind, prec, drop)
+    mem = transition_head(lat, sd, prec, drop=drop, lens=lens_s)
     inp, tgt, pad_mask = batchify_and_split_lmx_seqs(lmx, pad_idx)
     B, T = inp.shape
     # the reference runs every row at the padded length T with <pad> keys masked
     lens_t = [T] * B
     keep = [~pad_mask[i] for i in range(B)]
-    pred = decoder_forward_tf(inp.reshape(-1), mem, lens_t, lens_s, sd, dec_heads, prec, tgt_pad_keep=keep)
+    pred = decoder_forward_tf(inp.reshape(-1), mem, lens_t, lens_s, sd, dec_heads, prec, tgt_pad_keep=keep, drop=drop)
     return pred.reshape(B, T, -1), tgt
 
 
@@ -616,18 +654,19 @@ def sample_and_mix_seqs(tf_prob, tf_input_seqs, tf_pred_logits, tau, hard, noise
     return torch.where(sample_mask.unsqueeze(-1), expected, gold)
 
 
-def scheduled_sampling_forward(batch, sd, enc_heads, dec_heads, P, prec, tf_prob, tau, hard, noise, enc_kind="omr_ft", pad_idx=1):
+def scheduled_sampling_forward(batch, sd, enc_heads, dec_heads, P, prec, tf_prob, tau, hard, noise, enc_kind="omr_ft", pad_idx=1, drop=None):
     """ScheduledSamplingViTOMR.forward_train (M:819-834) with injected draws (see sample_and_mix_seqs): a teacher-forced first pass, the
     mixed embeddings, a second decoder pass on them (token_idxs_input=False) over the same memory.  Plain torch, differentiable, in the
     dtype of sd (float64 state dicts give a float64 reference under prec "fp32").  Returns padded pred (B, T, V), target (B, T)."""
     imgs, lmx = zip(*batch)
-    lat, lens_s = encoder_forward(list(imgs), sd, "encoder.", P, enc_heads, enc_kind, prec)
-    mem = transition_head(lat, sd, prec)
+    lat, lens_s = encoder_forward(list(imgs), sd, "encoder.", P, enc_heads, enc_kind, prec, drop)
+    mem = transition_head(lat, sd, prec, drop=drop, lens=lens_s)
     inp, tgt, pad_mask = batchify_and_split_lmx_seqs(lmx, pad_idx)
     B, T = inp.shape
     lens_t = [T] * B
     keep = [~pad_mask[i] for i in range(B)]
-    logits = decoder_forward_tf(inp.reshape(-1), mem, lens_t, lens_s, sd, dec_heads, prec, tgt_pad_keep=keep).reshape(B, T, -1)
+    logits = decoder_forward_tf(inp.reshape(-1), mem, lens_t, lens_s, sd, dec_heads, prec, tgt_pad_keep=keep, drop=drop).reshape(B, T, -1)
     mixed = sample_and_mix_seqs(tf_prob, inp, logits, tau, hard, noise, sd, prec, pad_idx)
-    pred = decoder_forward_tf(mixed.reshape(B * T, -1), mem, lens_t, lens_s, sd, dec_heads, prec, token_idxs_input=False, tgt_pad_keep=keep)
+    pred = decoder_forward_tf(mixed.reshape(B * T, -1), mem, lens_t, lens_s, sd, dec_heads, prec, token_idxs_input=False, tgt_pad_keep=keep,
+                              drop=drop, pass_=1)
     return pred.reshape(B, T, -1), tgt
