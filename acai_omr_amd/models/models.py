@@ -394,15 +394,20 @@ class OMRDecoder(nn.Module):
         x32, xb = ops.layernorm(x32, nrm.weight.detach(), nrm.bias.detach(), nrm.eps, want_bf16=bf)
         return EG.linear(x32, xb, self.unembed.weight, self.unembed.bias, prec, wc, out_dtype=torch.float32)
 
-    def forward(self, input_seqs, img_latent, lmx_attention_mask, latent_attention_mask, token_idxs_input=True, checkpoint_grads=False):
+    def forward(self, input_seqs, img_latent, lmx_attention_mask, latent_attention_mask, token_idxs_input=True, checkpoint_grads=False,
+                memory_group_size=None):
         """Teacher-forced logits (B, L_lmxmax, V) (M:445-483).  <pad> positions (lmx_attention_mask True) are not computed
-        and come back as zeros (the reference leaves unspecified values there; OMRCELoss ignores them)."""
+        and come back as zeros (the reference leaves unspecified values there; OMRCELoss ignores them).
+        memory_group_size = G (extension, GRPO): img_latent / latent_attention_mask hold one memory per IMAGE and input_seqs G rows per image
+        (rows b*G .. b*G+G-1 attend to memory b) - the same logits as over expand_img_latent_for_rollout's copies, without making them."""
         T = input_seqs.shape[1]
         if T > self.max_lmx_seq_len:
             raise ValueError(f"{T} long lmx sequence length is too long for max sequence length of {self.max_lmx_seq_len}")
-        if _training_path_needed(self) or (torch.is_grad_enabled() and (img_latent.requires_grad or (not token_idxs_input and input_seqs.requires_grad))):
+        if memory_group_size is not None or _training_path_needed(self) or (
+                torch.is_grad_enabled() and (img_latent.requires_grad or (not token_idxs_input and input_seqs.requires_grad))):
             from ..train import autograd_path
-            return autograd_path.decoder_forward(self, input_seqs, img_latent, lmx_attention_mask, latent_attention_mask, token_idxs_input, checkpoint_grads)
+            return autograd_path.decoder_forward(self, input_seqs, img_latent, lmx_attention_mask, latent_attention_mask, token_idxs_input, checkpoint_grads,
+                                                 memory_group_size)
         dev = self.pos_embedding.device
         B = input_seqs.shape[0]
         lens_t = [T] * B if lmx_attention_mask is None else (~lmx_attention_mask).sum(dim=1).tolist()

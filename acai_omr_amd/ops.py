@@ -547,6 +547,35 @@ def ce_loss(logits, target, ignore_index, count, want_grad, label_smoothing=0.0)
     return loss[0], dl
 
 
+
+def grpo_objective_fwd(logits, rollouts, mask, old_lp, adv, clip_lo, clip_hi, num_groups, logv):
+    """GRPO objective and entropy bonus in one pass (acai_grpo_objective_fwd).  logits [R, T, V] fp32 / bf16, rollouts [R, >T] int64, mask [R, T]
+    (True = masked), old_lp [R, >T] fp32, adv [R] fp32.  Returns (out [2] = (objective, bonus), stats, rowstat): the workspaces the backward reads."""
+    R, T, V = logits.shape
+    _chk(logits, "logits"), _chk(rollouts, "rollouts", torch.int64), _chk(old_lp, "old_lp", torch.float32), _chk(adv, "adv", torch.float32)
+    assert logits.is_contiguous() and logits.data_ptr() % 16 == 0, "logits: contiguous and 16-byte aligned"
+    assert rollouts.shape[0] == R and rollouts.shape[1] > T and old_lp.shape[0] == R and old_lp.shape[1] > T and adv.numel() == R and adv.is_contiguous()
+    assert mask.shape == (R, T) and mask.is_contiguous() and mask.dtype in (torch.bool, torch.uint8)
+    stats = torch.empty(R * T, 4, dtype=torch.float32, device=logits.device)
+    rowstat = torch.empty(R, 4, dtype=torch.float32, device=logits.device)
+    out = torch.empty(2, dtype=torch.float32, device=logits.device)
+    _lib.check(_lib.lib().acai_grpo_objective_fwd(logits.data_ptr(), _dt(logits), rollouts.data_ptr(), _ld(rollouts), old_lp.data_ptr(), _ld(old_lp),
+                                                  mask.data_ptr(), adv.data_ptr(), R, T, V, float(clip_lo), float(clip_hi), int(num_groups), float(logv),
+                                                  stats.data_ptr(), rowstat.data_ptr(), out.data_ptr(), _st(logits)), "acai_grpo_objective_fwd")
+    return out, stats, rowstat
+
+
+def grpo_objective_bwd(logits, rollouts, mask, stats, rowstat, grad_out, num_groups, logv):
+    """dlogits (logits' dtype) of grad_out[0] * objective + grad_out[1] * bonus; grad_out is a [2] fp32 device tensor (read on the device)."""
+    R, T, V = logits.shape
+    _chk(grad_out, "grad_out", torch.float32)
+    assert grad_out.numel() == 2 and grad_out.is_contiguous()
+    dl = torch.empty_like(logits, memory_format=torch.contiguous_format)
+    _lib.check(_lib.lib().acai_grpo_objective_bwd(logits.data_ptr(), _dt(logits), rollouts.data_ptr(), _ld(rollouts), mask.data_ptr(), stats.data_ptr(),
+                                                  rowstat.data_ptr(), grad_out.data_ptr(), R, T, V, int(num_groups), float(logv), dl.data_ptr(),
+                                                  _st(logits)), "acai_grpo_objective_bwd")
+    return dl
+
 for _name, _fn in list(globals().items()):
     if callable(_fn) and not _name.startswith("_") and getattr(_fn, "__module__", None) == __name__ and not isinstance(_fn, type):
         globals()[_name] = _on_operand_device(_fn)

@@ -408,19 +408,19 @@ class CrossAttnFn(Function):
     """Packed cross attention: q [Mq, E], kv [Mk, 2E] -> [Mq, E]."""
 
     @staticmethod
-    def forward(ctx, q, kv, cu_q, cu_k, H, dh, max_q, max_k, dropout_p=0.0, pre=False):
+    def forward(ctx, q, kv, cu_q, cu_k, H, dh, max_q, max_k, dropout_p=0.0, pre=False, kv_shared=False):
         E = H * dh
         lse = torch.empty(H * q.shape[0], dtype=torch.float32, device=q.device)
         seed = _next_seed() if dropout_p > 0 else 0
         out = ops.attn_varlen(q, kv[:, :E], kv[:, E:], cu_q, cu_k, H, dh, max_q, lse=lse, dropout_p=dropout_p, seed=seed, q_prescaled=pre)
         ctx.save_for_backward(q, kv, out, lse, cu_q, cu_k)
-        ctx.cfg = (H, dh, max_q, max_k, dropout_p, seed, pre)
+        ctx.cfg = (H, dh, max_q, max_k, dropout_p, seed, pre, kv_shared)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, kv, out, lse, cu_q, cu_k = ctx.saved_tensors
-        H, dh, max_q, max_k, dropout_p, seed, pre = ctx.cfg
+        H, dh, max_q, max_k, dropout_p, seed, pre, kv_shared = ctx.cfg
         E = H * dh
         dq = torch.empty_like(q)
         # Two passes over ONE projected memory (scheduled sampling: decoder_forward shares `kv` between them): the pass whose backward runs second adds
@@ -428,16 +428,19 @@ class CrossAttnFn(Function):
         # after both nodes ran) and returns no gradient of its own - instead of autograd summing two [keys, 2E] tensors per layer (12 x ~150 us per
         # teacher-forced step).  Scoped to the current backward pass, as the in-place parameter gradients are.
         # (the kernel's accumulate form exists for bf16 with 16-byte aligned rows and head slices only - the condition of its vector path)
-        fusable = _KV_GRAD_FUSE and kv.dtype == torch.bfloat16 and dh % 8 == 0 and kv.stride(0) % 8 == 0 and q.stride(0) % 8 == 0 and kv.stride(1) == 1
+        # Only a kv that a shared_cross_kv context made is looked up or recorded: a kv recomputed inside a checkpointed segment is freed before the
+        # next layer's recomputation, which may get the same memory (same data_ptr / shape / stride) - and must not add into this layer's dK / dV.
+        fusable = (kv_shared and _KV_GRAD_FUSE and kv.dtype == torch.bfloat16 and dh % 8 == 0 and kv.stride(0) % 8 == 0 and q.stride(0) % 8 == 0
+                   and kv.stride(1) == 1)
         prev = _tgrad_prev(kv) if fusable else None
         dkv = prev if prev is not None else torch.empty_like(kv)
         ops.attn_varlen_bwd(q, kv[:, :E], kv[:, E:], out, dout.contiguous().to(q.dtype), lse, cu_q, cu_k, H, dh, max_q, max_k, False,
                             dq, dkv[:, :E], dkv[:, E:], dropout_p=dropout_p, seed=seed, q_prescaled=pre, accumulate_dkv=prev is not None)
         if prev is not None:
-            return dq, None, None, None, None, None, None, None, None, None
+            return dq, None, None, None, None, None, None, None, None, None, None
         if fusable:
             _tgrad_note(kv, dkv)
-        return dq, dkv, None, None, None, None, None, None, None, None
+        return dq, dkv, None, None, None, None, None, None, None, None, None
 
 
 class CrossAttnBlockFn(Function):
@@ -446,7 +449,7 @@ class CrossAttnBlockFn(Function):
     neither its accumulation add nor the bf16 -> fp32 copy in front of it (two launches per decoder layer and pass on the 8208-row stream)."""
 
     @staticmethod
-    def forward(ctx, x32, kv, Win, bin_, Wo, bo, cu_q, cu_k, H, max_q, max_k, prec, wc, attn_mod):
+    def forward(ctx, x32, kv, Win, bin_, Wo, bo, cu_q, cu_k, H, max_q, max_k, prec, wc, attn_mod, kv_shared=False):
         bf = prec == "bf16"
         cdt = torch.bfloat16 if bf else torch.float32
         E = x32.shape[1]
@@ -459,13 +462,13 @@ class CrossAttnBlockFn(Function):
         attn = ops.attn_varlen(q, kv[:, :E], kv[:, E:], cu_q, cu_k, H, dh, max_q, lse=lse, q_prescaled=pre)
         y = ops.gemm_nt(attn, wc.w(Wo, prec), wc.b(bo, prec), residual=x32, out_dtype=torch.float32, round_bf16=bf)
         ctx.save_for_backward(x, q, kv, attn, lse, cu_q, cu_k, Win, bin_, Wo, bo)
-        ctx.cfg = (H, dh, max_q, max_k, prec, wc, pre, attn_mod)
+        ctx.cfg = (H, dh, max_q, max_k, prec, wc, pre, attn_mod, kv_shared)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, q, kv, attn, lse, cu_q, cu_k, Win, bin_, Wo, bo = ctx.saved_tensors
-        H, dh, max_q, max_k, prec, wc, pre, attn_mod = ctx.cfg
+        H, dh, max_q, max_k, prec, wc, pre, attn_mod, kv_shared = ctx.cfg
         bf = prec == "bf16"
         E = H * dh
         dy = dy.contiguous()
@@ -473,8 +476,8 @@ class CrossAttnBlockFn(Function):
         dattn = ops.gemm_nt(dyc, wc.wt(Wo, prec), out_dtype=attn.dtype, round_bf16=bf)
         dWo, dbo = _wbgrad(Wo, bo, dyc, attn, cs, ctx.needs_input_grad[4], ctx.needs_input_grad[5])
         dq = torch.empty_like(q)
-        # (the second pass over a shared projected memory adds its dK / dV in the kernel's epilogue: see CrossAttnFn.backward)
-        fusable = _KV_GRAD_FUSE and kv.dtype == torch.bfloat16 and dh % 8 == 0 and kv.stride(0) % 8 == 0 and q.stride(0) % 8 == 0 and kv.stride(1) == 1
+        # (the second pass over a shared projected memory adds its dK / dV in the kernel's epilogue: see CrossAttnFn.backward, also for kv_shared)
+        fusable = kv_shared and _KV_GRAD_FUSE and kv.dtype == torch.bfloat16 and dh % 8 == 0 and kv.stride(0) % 8 == 0 and q.stride(0) % 8 == 0 and kv.stride(1) == 1
         prev = _tgrad_prev(kv) if fusable else None
         dkv = prev if prev is not None else torch.empty_like(kv)
         ops.attn_varlen_bwd(q, kv[:, :E], kv[:, E:], attn, dattn, lse, cu_q, cu_k, H, dh, max_q, max_k, False, dq, dkv[:, :E], dkv[:, E:], q_prescaled=pre,
@@ -486,7 +489,7 @@ class CrossAttnBlockFn(Function):
         if ctx.needs_input_grad[0]:
             dx = ops.gemm_nt(dq, sl.wt(Win, prec), residual=dy.float() if dy.dtype != torch.float32 else dy, out_dtype=torch.float32, round_bf16=bf)
         dWin, dbin = _rows_param_grads(Win, bin_, 0, E, dq, x, None, ctx.needs_input_grad[2], ctx.needs_input_grad[3])
-        return dx, (None if prev is not None else dkv), dWin, dbin, dWo, dbo, None, None, None, None, None, None, None, None
+        return dx, (None if prev is not None else dkv), dWin, dbin, dWo, dbo, None, None, None, None, None, None, None, None, None
 
 
 class DropoutAddFn(Function):
@@ -1008,6 +1011,30 @@ def ce_loss(pred, target_seqs, pad_idx, label_smoothing=0.0):
     return CeLossFn.apply(lg, tg, pad_idx, count, float(label_smoothing))
 
 
+class GrpoObjectiveFn(Function):
+    """(objective, entropy bonus) of omr_grpo_train.py:240-283 from one pass over the theta logits (acai_grpo_objective_fwd / _bwd).  The backward
+    hands both incoming gradients to the kernel as a device tensor: no host sync."""
+
+    @staticmethod
+    def forward(ctx, logits, rollouts, mask, old_lp, adv, epsilon, num_groups):
+        V = logits.shape[-1]
+        logv = float(torch.log(torch.tensor(V)))   # (the reference's fp32 torch.log(torch.tensor(vocab_size)), omr_grpo_train.py:282)
+        lg = logits if logits.is_contiguous() and logits.data_ptr() % 16 == 0 else logits.contiguous().clone()
+        ro, m = rollouts.contiguous(), mask.contiguous()
+        out, stats, rowstat = ops.grpo_objective_fwd(lg, ro, m, old_lp.float().contiguous(), adv.float().contiguous(), 1 - epsilon, 1 + epsilon,
+                                                     num_groups, logv)
+        ctx.save_for_backward(lg, ro, m, stats, rowstat)
+        ctx.cfg = (num_groups, logv)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_obj, g_bonus):
+        lg, ro, m, stats, rowstat = ctx.saved_tensors
+        num_groups, logv = ctx.cfg
+        z = torch.zeros((), dtype=torch.float32, device=lg.device)
+        g = torch.stack([z if g_obj is None else g_obj.float(), z if g_bonus is None else g_bonus.float()])
+        return ops.grpo_objective_bwd(lg, ro, m, stats, rowstat, g, num_groups, logv), None, None, None, None, None, None
+
 # ---- teacher-forced decoder (models.py:445-483) ---------------------------------------------------------------------------------
 _KV_SHARE = None   # set by shared_cross_kv(): {id(img_latent): {"mem": (mem32, lens_s, memc), "kv": {layer: kv}}}
 
@@ -1029,8 +1056,24 @@ class shared_cross_kv:
         return False
 
 
-def decoder_forward(dec, input_seqs, img_latent, lmx_attention_mask, latent_attention_mask, token_idxs_input=True, checkpoint_grads=False):
-    """checkpoint_grads (reference: models.py:470-478, `checkpoint_sequential` with one segment per decoder layer, used by the GRPO loop): each
+def group_cu(lens_t, lens_s, group_size):
+    """Cross-attention layout of a group-shared memory (decoder_forward's memory_group_size): the G = group_size consecutive rollouts of image b
+    (rows b*G .. b*G+G-1 of the packed token stream) attend to image b's memory as ONE query sequence - cross attention has no causal mask, so
+    concatenating them changes nothing but the summation order of dK / dV.  Returns (query lengths per image, key lengths per image) for
+    cu_from_lens: query lengths are the group totals, i.e. every G-th entry of the rollouts' cu_seqlens."""
+    G = int(group_size)
+    if G < 1 or len(lens_t) != G * len(lens_s):
+        raise ValueError(f"{len(lens_t)} token sequences are not group_size={G} rollouts of each of {len(lens_s)} memories")
+    return [sum(lens_t[b * G:(b + 1) * G]) for b in range(len(lens_s))], list(lens_s)
+
+
+def decoder_forward(dec, input_seqs, img_latent, lmx_attention_mask, latent_attention_mask, token_idxs_input=True, checkpoint_grads=False,
+                    memory_group_size=None):
+    """memory_group_size = G (extension, the GRPO policy update): img_latent / latent_attention_mask are per IMAGE ([B, S, D]) and input_seqs holds
+    B*G rows, image b's rollouts at rows b*G .. b*G+G-1.  The result equals the pass over expand_img_latent_for_rollout's G copies up to summation
+    order; the memory's K / V projection runs over B*S rows instead of B*G*S, and the attention backward sums dK / dV over the group (group_cu).
+
+    checkpoint_grads (reference: models.py:470-478, `checkpoint_sequential` with one segment per decoder layer, used by the GRPO loop): each
     layer's activations are dropped after the forward and recomputed in the backward (torch.utils.checkpoint, non-reentrant; the dropout seeds
     come from torch's CPU generator, whose state the checkpoint restores for the recomputation).  Same logits and gradients; the cross K / V
     projection of a layer is part of its checkpointed segment unless it is shared between two passes (then it is computed once, outside)."""
@@ -1056,6 +1099,11 @@ def decoder_forward(dec, input_seqs, img_latent, lmx_attention_mask, latent_atte
         idx = ops.h2d(torch.cat([torch.arange(b * T, b * T + l, dtype=torch.int32) for b, l in enumerate(lens_t)]), dev)
         x32 = GatherRowsFn.apply(input_seqs.reshape(B * T, E).float(), idx, pos)
     cu_t, cu_s = EG.cu_from_lens(lens_t, dev), EG.cu_from_lens(lens_s, dev)
+    if memory_group_size is not None:
+        lens_q, _ = group_cu(lens_t, lens_s, memory_group_size)
+        cu_x, mx = EG.cu_from_lens(lens_q, dev), max(lens_q)
+    else:
+        cu_x, mx = cu_t, max(lens_t)
     memc = memc_shared if memc_shared is not None else (CastBf16Fn.apply(mem32) if bf else mem32)
     if share is not None:
         share["mem"] = (mem32, lens_s, memc)
@@ -1070,11 +1118,12 @@ def decoder_forward(dec, input_seqs, img_latent, lmx_attention_mask, latent_atte
         # (the fused parameters go in whole: LinearFn takes its rows through the _SliceCache and writes their gradient into the full-size tensor)
         kv = kv_shared if kv_shared is not None else LinearFn.apply(memc, ca.in_proj_weight, ca.in_proj_bias, None, prec, _SliceCache(wc, ca, E, 3 * E), False)
         if _FUSED_MLP and _p_of(ca, tr) <= 0.0 and _p_of(ly.dropout2, tr) <= 0.0 and ca.in_proj_bias is not None and ca.out_proj.bias is not None:
-            y = CrossAttnBlockFn.apply(x32, kv, ca.in_proj_weight, ca.in_proj_bias, ca.out_proj.weight, ca.out_proj.bias, cu_t, cu_s, H, mt, ms, prec, wc, ca)
+            y = CrossAttnBlockFn.apply(x32, kv, ca.in_proj_weight, ca.in_proj_bias, ca.out_proj.weight, ca.out_proj.bias, cu_x, cu_s, H, mx, ms, prec, wc, ca,
+                                       kv_shared is not None)
         else:
             xc = CastBf16Fn.apply(x32) if bf else x32
             q = LinearFn.apply(xc, ca.in_proj_weight, ca.in_proj_bias, None, prec, _SliceCache(wc, ca, 0, E), False, (E, ops.QSCALE(dh)) if pre else None)
-            a = CrossAttnFn.apply(q, kv, cu_t, cu_s, H, dh, mt, ms, _p_of(ca, tr), pre)
+            a = CrossAttnFn.apply(q, kv, cu_x, cu_s, H, dh, mx, ms, _p_of(ca, tr), pre, kv_shared is not None)
             y = _proj_residual(a, ca.out_proj.weight, ca.out_proj.bias, x32, _p_of(ly.dropout2, tr), prec, wc)
         x32 = LayerNormFn.apply(y, ly.norm2.weight, ly.norm2.bias, ly.norm2.eps)
         y = _mlp(x32, ly.linear1, ly.linear2, _p_of(ly.dropout, tr), _p_of(ly.dropout3, tr), prec, wc)

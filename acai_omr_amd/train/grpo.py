@@ -1,0 +1,296 @@
+"""The GRPO policy-update step (acai_omr/train/omr_grpo_train.py:120-376, the configs of acai_omr/utils/utils.py:17-105): objective, entropy
+bonus, teacher-forced policy forward / backward and the optimizer step that consume rollouts and their rewards.
+
+Same names and argument orders as the reference, so code written for omr_grpo_train.py ports.  What differs:
+  * the objective and the entropy bonus come from ONE fused HIP pass over the theta logits (acai_grpo_objective_fwd / _bwd); there is no CPU
+    path, as elsewhere in the package.  An entropy term with p_c == 0 counts 0 where the reference gives NaN (only -inf logits produce it);
+  * the policy forward runs on the UNEXPANDED image memory (OMRDecoder.forward(memory_group_size=G)): the reference's
+    expand_img_latent_for_rollout copies it G times, and every layer projects each copy;
+  * rewards: the edit-distance terms (calc_edit_costs / reward_rollouts: TEDn through olimpic_app) are not ported - grpo_update takes a
+    `reward_fn` that returns the (B, G) raw rewards.  The tensor-only reward helpers are here."""
+from dataclasses import dataclass
+
+import torch
+
+from .. import ops
+from . import autograd_path as AP
+
+
+# ---- configs (utils.py:17-105) ----------------------------------------------------------------------------------------------------------
+@dataclass
+class RolloutConfig:
+    group_size: int
+    max_actions: int
+    top_k: int
+    temperature: float
+
+
+@dataclass
+class RewardComponents:
+    tedn_scores: torch.Tensor | float
+    wellformedness_scores: torch.Tensor | float
+    f1_scores: torch.Tensor | float
+    repeat_penalty: torch.Tensor | float
+    len_penalty: torch.Tensor | float
+
+    def __add__(self, other):
+        return RewardComponents(*(a + b for a, b in zip(self._vals(), other._vals())))
+
+    def __truediv__(self, divisor):
+        return RewardComponents(*(a / divisor for a in self._vals()))
+
+    def _vals(self):
+        return (self.tedn_scores, self.wellformedness_scores, self.f1_scores, self.repeat_penalty, self.len_penalty)
+
+    def avg_over_rollouts(self):
+        return RewardComponents(*(a.mean().item() for a in self._vals()))
+
+    def to_dict(self):
+        return {"tedn_scores": self.tedn_scores, "wellformedness_scores": self.wellformedness_scores, "f1_scores": self.f1_scores,
+                "repeat_penalty": self.repeat_penalty, "len_penalty": self.len_penalty}
+
+
+@dataclass
+class RewardConfig:
+    lambda_tedn: float
+    lambda_well_formed: float
+    lambda_f1: float
+    lambda_repeat: float
+    lambda_len: float
+    alpha_tedn: float
+    alpha_well_formed: float
+    gamma: float
+    delta: int
+    tau: int
+
+
+@dataclass
+class LossConfig:
+    entropy_beta: float
+    lambda_ce: float
+
+
+@dataclass
+class UpdateConfig:
+    epsilon: float
+    update_epochs: int
+    max_grad_norm: float
+
+
+@dataclass
+class GRPOConfig:
+    rollout_config: RolloutConfig
+    reward_config: RewardConfig
+    loss_config: LossConfig
+    update_config: UpdateConfig
+    mini_validation_freq: int
+    checkpoint_freq: int
+
+    def get_configs(self):
+        return self.rollout_config, self.reward_config, self.loss_config, self.update_config
+
+
+class StepCounter:
+    def __init__(self):
+        self.global_step = 0
+
+
+# the reference's initial values (omr_grpo_train.py:30-72)
+LR = 1e-6
+ADAMW_BETAS = (0.9, 0.95)
+ADAMW_WEIGHT_DECAY = 0.0
+TRAIN_BATCH_SIZE = 16
+INITIAL_ROLLOUT_CONFIG = RolloutConfig(group_size=8, max_actions=768, top_k=50, temperature=1.1)
+INITIAL_REWARD_CONFIG = RewardConfig(lambda_tedn=7, lambda_well_formed=1.5, lambda_f1=2.5, lambda_repeat=2, lambda_len=2, alpha_tedn=0.01,
+                                     alpha_well_formed=0.25, gamma=3, delta=5, tau=50)
+INITIAL_LOSS_CONFIG = LossConfig(entropy_beta=0.05, lambda_ce=0.1)
+INITIAL_UPDATE_CONFIG = UpdateConfig(epsilon=0.2, update_epochs=2, max_grad_norm=1.0)
+
+
+# ---- rewards (tensor-only helpers, omr_grpo_train.py:121-226) ------------------------------------------------------------------------------
+def expand_target_lmx_seqs(target_lmx_seqs, group_size, pad_idx, device):
+    """(B) ragged targets -> (B*G, Lmax) padded with pad_idx, each target repeated for its group's rollouts."""
+    L = max(int(t.shape[0]) for t in target_lmx_seqs)
+    out = torch.full((len(target_lmx_seqs), L), pad_idx, dtype=target_lmx_seqs[0].dtype, device=device)
+    for i, t in enumerate(target_lmx_seqs):
+        out[i, :t.shape[0]] = t.to(device)
+    return out.unsqueeze(1).expand(-1, group_size, -1).flatten(start_dim=0, end_dim=1)
+
+
+def calc_tedn_scores(edit_costs, alpha_t=0.01):
+    return torch.exp(-alpha_t * edit_costs)
+
+
+def calc_wellformedness(catastrophic_errors, minor_errors, gamma=3.0, alpha_w=0.2):
+    return torch.exp(-alpha_w * minor_errors).masked_fill(catastrophic_errors, -gamma)
+
+
+def calc_token_f1(rollouts, target_lmx_seqs, pad_idx):
+    num_predictions = (rollouts != pad_idx).sum(dim=-1)
+    num_targets = (target_lmx_seqs != pad_idx).sum(dim=-1)
+    n = min(rollouts.shape[-1], target_lmx_seqs.shape[-1])
+    preds, targets = rollouts[:, :n], target_lmx_seqs[:, :n]
+    true_positives = ((preds == targets) & (targets != pad_idx)).sum(dim=-1)
+    precision = true_positives / (num_predictions + 1e-8)
+    recall = true_positives / (num_targets + 1e-8)
+    return 2 * precision * recall / (precision + recall + 1e-8)
+
+
+def calc_n_gram_penalty(rollouts, n, pad_idx):
+    """Share of non-overlapping n-grams equal to the one before them (n-grams holding <pad> left out)."""
+    n_grams = rollouts.unfold(dimension=-1, size=n, step=n)
+    prev_n_grams, next_n_grams = n_grams[:, :-1, :], n_grams[:, 1:, :]
+    pad_mask = torch.any(next_n_grams == pad_idx, dim=-1)
+    repeats = torch.all(prev_n_grams == next_n_grams, dim=-1) & ~pad_mask
+    return repeats.sum(dim=-1) / ((~pad_mask).sum(dim=-1) + 1e-8)
+
+
+def calc_repeat_penalty(rollouts, pad_idx, n_values=(1, 2, 3, 4)):
+    total = 0
+    for n in n_values:
+        total += calc_n_gram_penalty(rollouts, n, pad_idx)
+    return total / len(n_values)
+
+
+def calc_len_penalty(rollout_mask, target_lmx_seqs, pad_idx, delta=10, tau=100):
+    len_diffs = torch.abs(rollout_mask.sum(dim=-1) - (target_lmx_seqs != pad_idx).sum(dim=-1))
+    len_diffs = len_diffs.masked_fill(len_diffs < delta, 0)
+    penalty = torch.exp((torch.log(torch.tensor(2)) / tau) * len_diffs) - 1
+    return torch.clip(penalty, max=1.0)
+
+
+def calc_group_rewards(reward_config: RewardConfig, reward_components: RewardComponents, num_groups, group_size):
+    c, rc = reward_components, reward_config
+    rewards = (rc.lambda_tedn * c.tedn_scores + rc.lambda_well_formed * c.wellformedness_scores + rc.lambda_f1 * c.f1_scores
+               - rc.lambda_repeat * c.repeat_penalty - rc.lambda_len * c.len_penalty)
+    return rewards.view(num_groups, group_size)
+
+
+# ---- objective and entropy (omr_grpo_train.py:240-283) through the fused op -------------------------------------------------------------
+def calc_grpo_objective_and_entropy_bonus(theta_logits, rollouts, rollout_attention_mask, old_policy_log_probs, advantages, epsilon, num_groups):
+    """(calc_grpo_objective(...), calc_entropy_bonus(theta_logits, rollout_attention_mask, V)) from one kernel pass over the logits."""
+    return AP.GrpoObjectiveFn.apply(theta_logits, rollouts, rollout_attention_mask, old_policy_log_probs, advantages, float(epsilon), int(num_groups))
+
+
+def calc_grpo_objective(theta_logits, rollouts, rollout_attention_mask, old_policy_log_probs, advantages, epsilon, num_groups):
+    return calc_grpo_objective_and_entropy_bonus(theta_logits, rollouts, rollout_attention_mask, old_policy_log_probs, advantages, epsilon,
+                                                 num_groups)[0]
+
+
+def calc_policy_theta_entropy(theta_logits, rollout_attention_mask):
+    """Per-rollout mean entropy (R,), the fused op's per-rollout statistic, without a gradient (calc_entropy_bonus is the differentiable form)."""
+    R, T, V = theta_logits.shape
+    dev = theta_logits.device
+    lg = theta_logits.detach().contiguous()
+    if lg.data_ptr() % 16:
+        lg = lg.clone()
+    # (zero actions / advantages: the entropy half of the pass does not read them)
+    _, _, rowstat = ops.grpo_objective_fwd(lg, torch.zeros(R, T + 1, dtype=torch.int64, device=dev), rollout_attention_mask.contiguous(),
+                                           torch.zeros(R, T + 1, device=dev), torch.zeros(R, device=dev), 0.8, 1.2, 1, float(torch.log(torch.tensor(V))))
+    return rowstat[:, 1].clone()
+
+
+def calc_entropy_bonus(theta_logits, rollout_attention_mask, vocab_size):
+    R, T, V = theta_logits.shape
+    assert V == vocab_size, "calc_entropy_bonus: vocab_size must be the logits' last dimension"
+    dev = theta_logits.device
+    rollouts = torch.zeros(R, T + 1, dtype=torch.int64, device=dev)
+    return calc_grpo_objective_and_entropy_bonus(theta_logits, rollouts, rollout_attention_mask, torch.zeros(R, T + 1, device=dev),
+                                                 torch.zeros(R, device=dev), 0.2, 1)[1]
+
+
+def calc_teacher_forced_ce_loss(policy_theta, unexpanded_img_latent, unexpanded_latent_attention_mask, unexpanded_target_lmx_seqs, ce_loss_fn):
+    logits, target_seqs = policy_theta.forward_teacher_forced(unexpanded_img_latent, unexpanded_latent_attention_mask, unexpanded_target_lmx_seqs,
+                                                              checkpoint_grads=True)
+    return ce_loss_fn(logits, target_seqs)
+
+
+# ---- the update step (omr_grpo_train.py:308-376) ---------------------------------------------------------------------------------------
+def _rollouts_grouped(old_policy, img_latent, latent_attention_mask, group_size, rollout_config, uniforms):
+    """cached_forward_rollout_policy(expand_img_latent_for_rollout(...), group_size=G) without making the G copies: the cached decode reads
+    one memory per image already (group_size), so the per-image latent goes in as it is."""
+    from .. import engine as EG
+    blocks = old_policy.decoder.decoder_blocks
+    mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
+    blocks.prepare_caches_packed(mem32, None, lens, group_size=group_size)
+    eng = blocks.engine(old_policy.decoder.pos_embedding.device)
+    seqs, lps, _ = eng.sample(rollout_config.max_actions, rollout_config.top_k, rollout_config.temperature, uniforms=uniforms)
+    return old_policy.mask_and_clip_seqs(seqs.clone(), lps.clone())
+
+
+def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOConfig, ce_loss_fn, device, logger=None, counter=None, *, reward_fn,
+                uniforms=None):
+    """One GRPO minibatch update.  batch: list of (image, target_lmx_seq, target_musicxml_str).  reward_fn(rollouts, rollout_mask, target_lmx_seqs,
+    batch) -> (B, G) raw rewards, or (rewards, RewardComponents).  uniforms (R, max_actions): the rollout draws (cached_forward_rollout_policy).
+    Returns (avg loss over update epochs, avg CE loss, avg raw reward, avg reward components or None)."""
+    rollout_config, reward_config, loss_config, update_config = grpo_config.get_configs()
+    dev_type = torch.device(device).type
+    pad_idx = old_policy.decoder.pad_idx
+    unexpanded_imgs, unexpanded_target_lmx_seqs, _ = zip(*batch)
+    unexpanded_imgs = [img.to(device, non_blocking=True) for img in unexpanded_imgs]
+    unexpanded_target_lmx_seqs = [t.to(device, non_blocking=True) for t in unexpanded_target_lmx_seqs]
+    group_size = rollout_config.group_size
+    num_groups = len(batch)
+
+    with torch.no_grad(), torch.autocast(device_type=dev_type, dtype=torch.bfloat16):
+        unexpanded_img_latent, unexpanded_latent_attention_mask = old_policy.encoder(unexpanded_imgs)
+        unexpanded_img_latent = old_policy.transition_head(unexpanded_img_latent)
+        rollouts, old_policy_log_probs, rollout_mask = _rollouts_grouped(old_policy, unexpanded_img_latent, unexpanded_latent_attention_mask,
+                                                                         group_size, rollout_config, uniforms)
+
+    target_lmx_seqs = expand_target_lmx_seqs(unexpanded_target_lmx_seqs, group_size, pad_idx, device)
+    got = reward_fn(rollouts, rollout_mask, target_lmx_seqs, batch)
+    raw_group_rewards, reward_components = got if isinstance(got, tuple) else (got, None)
+    raw_group_rewards = raw_group_rewards.to(device).float().view(num_groups, group_size)
+    if logger is not None:
+        logger.log_raw_reward_stats(raw_group_rewards, counter.global_step)
+        if reward_components is not None:
+            logger.log_raw_reward_components(reward_components, counter.global_step)
+    group_advantages = (raw_group_rewards - raw_group_rewards.mean(dim=-1, keepdim=True)) / (raw_group_rewards.std(dim=-1, keepdim=True) + 1e-8)
+    advantages = group_advantages.view(-1)
+    if logger is not None:
+        logger.log_group_advantages(group_advantages, counter.global_step)
+    right_shifted_rollouts, rollout_attention_mask = old_policy.prepare_rollouts_for_policy_theta(rollouts, rollout_mask)
+    unexpanded_img_latent = unexpanded_img_latent.float()   # (the decoder's fp32 memory stream; B*S rows, not B*G*S)
+
+    batch_overall_loss = 0.0
+    batch_ce_loss = 0.0
+    update_epochs = update_config.update_epochs
+    with torch.autocast(device_type=dev_type, dtype=torch.bfloat16):
+        for _ in range(update_epochs):
+            # both decoder passes of the epoch read the same per-image memory: each layer projects it once (shared_cross_kv)
+            with AP.shared_cross_kv():
+                theta_logits = policy_theta.decoder(right_shifted_rollouts, unexpanded_img_latent, rollout_attention_mask, unexpanded_latent_attention_mask,
+                                                    checkpoint_grads=True, memory_group_size=group_size)
+                grpo_objective, entropy_bonus = calc_grpo_objective_and_entropy_bonus(theta_logits, rollouts, rollout_attention_mask,
+                                                                                      old_policy_log_probs, advantages, update_config.epsilon, num_groups)
+                if loss_config.lambda_ce:
+                    ce_loss = calc_teacher_forced_ce_loss(policy_theta, unexpanded_img_latent, unexpanded_latent_attention_mask,
+                                                          unexpanded_target_lmx_seqs, ce_loss_fn)
+                else:
+                    # quirk kept: no CE term at lambda_ce == 0 (the reference's `ce_loss = 0` then crashes on `.item()`; here it counts 0)
+                    ce_loss = torch.zeros((), device=theta_logits.device)
+            if logger is not None:
+                logger.log_raw_objective_components(grpo_objective, entropy_bonus, ce_loss, counter.global_step)
+            loss = -(grpo_objective + loss_config.entropy_beta * entropy_bonus - loss_config.lambda_ce * ce_loss)
+            batch_overall_loss += loss.item()   # (the reference's two syncs per epoch, nothing more)
+            batch_ce_loss += ce_loss.item()
+            if logger is not None:
+                logger.log_overall_loss(loss, counter.global_step)
+            loss.backward()
+            # quirk kept: max_norm is the literal 1.0 of omr_grpo_train.py:367 - UpdateConfig.max_grad_norm is not read
+            torch.nn.utils.clip_grad_norm_(policy_theta.parameters(), max_norm=1.0)
+            optimizer.step()
+            optimizer.zero_grad()
+            if counter is not None:
+                counter.global_step += 1
+
+    avg_components = reward_components.avg_over_rollouts() if reward_components is not None else None
+    return batch_overall_loss / update_epochs, batch_ce_loss / update_epochs, raw_group_rewards.mean().item(), avg_components
+
+
+def refresh_old_policy(old_policy, policy_theta):
+    """The reference loop's refresh before each minibatch (omr_grpo_train.py:425-426): encoder and transition head are frozen, so only the decoder
+    parameters are copied.  load_state_dict writes in place, which the decode engine's weight copies notice (parameter versions)."""
+    old_policy.decoder.load_state_dict({k: v.clone() for k, v in policy_theta.decoder.state_dict().items()})
+

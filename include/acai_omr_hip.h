@@ -191,6 +191,22 @@ int acai_mae_loss(const float *pred, const float *target, const unsigned char *m
 int acai_ce_loss(const float *logits, int ld, const int64_t *target, int ignore_index, float inv_count, float label_smoothing, float *loss,
                  float *dlogits, int rows, int V, void *stream);
 
+/* GRPO objective and entropy bonus (acai_omr/train/omr_grpo_train.py:240-283: calc_grpo_objective, calc_policy_theta_entropy /
+ * calc_entropy_bonus; grpo_update calls both on the same theta logits, :354-355) in one pass over logits [R][T][V] (contiguous, dtype
+ * ACAI_F32 / ACAI_BF16, 16-byte aligned, V <= 1024).  Position (r, t) counts when mask[r*T + t] == 0 (rollout_attention_mask, uint8); its action
+ * is rollouts[r*ld_roll + t + 1] (int64), its old log-probability old_lp[r*ld_old + t + 1]; adv[R] are the advantages.  clip_lo / clip_hi =
+ * 1 -/+ epsilon, logv = log(V) as the reference rounds it (fp32).  out[0] = objective = sum_r (sum_t min(ratio A, clip(ratio) A) / len_r) /
+ * num_groups, out[1] = bonus = mean_r (sum_t H / len_r) / logv.  stats [R*T][4] and rowstat [R][4] (fp32, 16-byte aligned) are workspaces the
+ * backward reads.  Deterministic: fixed-order reductions, no atomics.  Entropy terms with p_c == 0 count 0 (the reference gives NaN for -inf logits).
+ * _bwd: dlogits (logits' dtype, zero at masked positions) of grad_out[0] * objective + grad_out[1] * bonus, grad_out = 2 floats in DEVICE memory
+ * (no host sync); autograd's tie and band rules for the min / clip (grpo.hip). */
+int acai_grpo_objective_fwd(const void *logits, int dtype, const int64_t *rollouts, int ld_roll, const float *old_lp, int ld_old,
+                            const unsigned char *mask, const float *adv, int R, int T, int V, float clip_lo, float clip_hi, int num_groups,
+                            float logv, float *stats, float *rowstat, float *out, void *stream);
+int acai_grpo_objective_bwd(const void *logits, int dtype, const int64_t *rollouts, int ld_roll, const unsigned char *mask, const float *stats,
+                            const float *rowstat, const float *grad_out, int R, int T, int V, int num_groups, float logv, void *dlogits,
+                            void *stream);
+
 /* Fused multi-tensor AdamW: one launch steps every parameter tensor (reference: torch.optim.AdamW in acai_omr/train/pre_train.py:105 and
  * omr_teacher_force_train.py:207 over the param groups of acai_omr/models/models.py:761-781; the cosine/warm-up schedule of
  * acai_omr/utils/utils.py:204-222 only changes `lr`).  All tables live in DEVICE memory.  tensors[i]: fp32 parameter, gradient and the two
