@@ -173,6 +173,27 @@ __device__ __forceinline__ void skm_row_stats(const float4 (&v)[NV], int K, int 
     rstd = 1.0f / sqrtf(wave_sum(qq) / (float)K + eps);
 }
 
+// LayerNorm statistics of a row are taken of x - p, p = the row's first element: the pre-LN residual stream may carry an offset large
+// against its spread, which one-pass E[x^2] - mean^2 (and a mean rounded at |mean|'s ulp) would turn into a relative variance error of
+// ~2^-24 mean^2 / var (offset / spread 3000: the variance off by 100 %).  x - p is exact (Sterbenz) for values within a factor 2 of p.
+// p comes from a scalar load of the wave-uniform row address, waited for on its own counter, so it adds no wait on the vector loads.
+__device__ __forceinline__ float skm_pivot(const float *row) {
+    const unsigned long long u = reinterpret_cast<unsigned long long>(row);
+    const unsigned long long r = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(u >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((unsigned)u);
+    float p;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(p) : "s"(r));
+    return p;
+}
+
+template <int NV>
+__device__ __forceinline__ void skm_shift(float4 (&v)[NV], int K, int lane, float p) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        if (j * 256 + lane * 4 < K) {
+            v[j].x -= p; v[j].y -= p; v[j].z -= p; v[j].w -= p;
+        }
+}
+
 // NV = float4 registers per lane for one fp32 activation row (K <= 256 * NV); NW = waves per workgroup = K slices
 // (NW = K/256 puts a slice's 8 weight fragments per lane in flight at once: one HBM round trip per workgroup)
 template <bool XBF16, int NV, int NW>
@@ -273,8 +294,12 @@ __global__ __launch_bounds__(64 * NW) void skinny_mfma_kernel(SkinnyArgs a) {
                 request_weights();   // behind this wave's activation rows
                 request_epilogue();
                 if (a.ln_w) {
-                    // both rows' sum and sum of squares ride the same 6 cross-lane steps (4 independent chains); one-pass variance
-                    // E[x^2] - mean^2 is accurate to ~1e-6 relative for O(1) activations and this path rounds to bf16 right after
+                    // both rows' sum and sum of squares ride the same 6 cross-lane steps (4 independent chains).  Shifted one-pass
+                    // variance: the sums run over x - p with p = the row's first element, so a common offset of the row (the pre-LN
+                    // residual stream) does not cancel catastrophically in E[x^2] - mean^2; the rows stay shifted until normalised
+                    const float p0 = skm_pivot(xr0), p1 = skm_pivot(xr1);
+                    skm_shift<NV>(v0, K, lane, p0);
+                    skm_shift<NV>(v1, K, lane, p1);
                     float t0 = 0.f, u0 = 0.f, t1 = 0.f, u1 = 0.f;
 #pragma unroll
                     for (int j = 0; j < NV; ++j)
@@ -295,10 +320,10 @@ __global__ __launch_bounds__(64 * NW) void skinny_mfma_kernel(SkinnyArgs a) {
                     const float m0 = t0 * invK, m1 = t1 * invK;
                     const float s0 = 1.0f / sqrtf(fmaxf(u0 * invK - m0 * m0, 0.f) + a.ln_eps), s1 = 1.0f / sqrtf(fmaxf(u1 * invK - m1 * m1, 0.f) + a.ln_eps);
                     if (lane == 0 && a.stats_out && blockIdx.x == 0) {
-                        a.stats_out[(bt + b0) * 2] = m0;
+                        a.stats_out[(bt + b0) * 2] = p0 + m0;
                         a.stats_out[(bt + b0) * 2 + 1] = s0;
                         if (two) {
-                            a.stats_out[(bt + b0 + NW) * 2] = m1;
+                            a.stats_out[(bt + b0 + NW) * 2] = p1 + m1;
                             a.stats_out[(bt + b0 + NW) * 2 + 1] = s1;
                         }
                     }
@@ -328,9 +353,11 @@ __global__ __launch_bounds__(64 * NW) void skinny_mfma_kernel(SkinnyArgs a) {
                     if (j * 256 + lane * 4 < K) v[j] = *reinterpret_cast<const float4 *>(xr + j * 256 + lane * 4);
                 float mean = 0.f, rstd = 1.f;
                 if (a.ln_w) {
+                    const float p = skm_pivot(xr);   // (as above: the statistics of x - p, the row stays shifted)
+                    skm_shift<NV>(v, K, lane, p);
                     skm_row_stats<NV>(v, K, lane, a.ln_eps, mean, rstd);
                     if (lane == 0 && a.stats_out && blockIdx.x == 0) {
-                        a.stats_out[(bt + b) * 2] = mean;
+                        a.stats_out[(bt + b) * 2] = p + mean;
                         a.stats_out[(bt + b) * 2 + 1] = rstd;
                     }
                 }
@@ -504,10 +531,14 @@ __global__ __launch_bounds__(64 * NW) void skinny_chain_kernel(SkinnyArgs a) {
                     lb2[j] = *reinterpret_cast<const float4 *>(a.ln2_b + j * 256 + lane * 4);
                 }
             }
+            __builtin_amdgcn_sched_barrier(0);   // (without it hipcc hoisted the weight requests above the activation rows: -4 % tokens/s)
             if (first) request_weights();   // behind this wave's activation rows: loads return in issue order
             __builtin_amdgcn_sched_barrier(0);   // every load above is in flight before anything is waited for (hipcc otherwise sinks the LN / weight loads below the statistics)
             if constexpr (HAS_LN) {
-                // both rows' sum and sum of squares ride the same 6 cross-lane steps; one-pass variance (as skinny_mfma_kernel)
+                // both rows' sum and sum of squares ride the same 6 cross-lane steps; shifted one-pass variance (as skinny_mfma_kernel)
+                const float p0 = skm_pivot(pa - lane * 4), p1 = skm_pivot(pb - lane * 4);
+                skm_shift<4>(va, K, lane, p0);
+                skm_shift<4>(vb, K, lane, p1);
                 float t0 = 0.f, u0 = 0.f, t1 = 0.f, u1 = 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -525,11 +556,11 @@ __global__ __launch_bounds__(64 * NW) void skinny_chain_kernel(SkinnyArgs a) {
                 const float s0 = 1.0f / sqrtf(fmaxf(u0 * invK - m0 * m0, 0.f) + a.ln_eps), s1 = 1.0f / sqrtf(fmaxf(u1 * invK - m1 * m1, 0.f) + a.ln_eps);
                 if (lane == 0 && a.stats_out && blockIdx.x == 0) {
                     if (oka) {
-                        a.stats_out[(bt + ra) * 2] = m0;
+                        a.stats_out[(bt + ra) * 2] = p0 + m0;
                         a.stats_out[(bt + ra) * 2 + 1] = s0;
                     }
                     if (okb) {
-                        a.stats_out[(bt + rb) * 2] = m1;
+                        a.stats_out[(bt + rb) * 2] = p1 + m1;
                         a.stats_out[(bt + rb) * 2 + 1] = s1;
                     }
                 }
@@ -644,6 +675,7 @@ static inline bool skinny_mfma_ok(const SkinnyArgs &a) {
 
 template <typename TW>
 int launch_skinny(const SkinnyArgs &a, hipStream_t st) {
+    if (a.x_bf16 && (a.ln_w || a.stats_out)) return acai_set_err(-1, "skinny_gemm: LayerNorm on load needs fp32 activations");
     if constexpr (sizeof(TW) == 2) {
         if (skinny_mfma_ok(a)) {
             const int rows = a.B < 16 ? ((a.B + 3) & ~3) : 16;

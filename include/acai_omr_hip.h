@@ -316,7 +316,8 @@ int acai_skinny_gemm(const float *x, int ldx, const void *W, int ldw, const floa
 
 /* acai_skinny_gemm with the fusions the decode step uses (bf16 weights, K % 256 == 0): x may be bf16 (x_dtype), y may be bf16;
  * ln_w/ln_b: x := LayerNorm(x) on load (norm1/2/3 of the post-LN layer, K:208,220,222), its per-row (mean, rstd) optionally
- * published to stats_out[B][2]; rln_w/rln_b/rstats: residual := LayerNorm(residual) from published statistics. */
+ * published to stats_out[B][2] (fp32 x only: refused for bf16 x); rln_w/rln_b/rstats: residual := LayerNorm(residual) from published
+ * statistics. */
 int acai_skinny_gemm_ex(const void *x, int ldx, int x_dtype, const void *W, int ldw, const float *bias, const float *residual, int ldr,
                         void *y, int ldy, int y_dtype, int B, int N, int K, int dtype, int flags, const float *ln_w, const float *ln_b,
                         float ln_eps, float *stats_out, const float *rln_w, const float *rln_b, const float *rstats, void *stream);

@@ -54,8 +54,8 @@ NEG_INF = float("-inf")
 # precision helpers
 # ----------------------------------------------------------------------------
 def rbf16(x):
-    """Round-to-nearest-even to bf16, kept in an fp32 container."""
-    return x.to(torch.bfloat16).to(torch.float32)
+    """Round-to-nearest-even to bf16, kept in an fp32 container (a float64 input stays float64)."""
+    return x.to(torch.bfloat16).to(torch.float64 if x.dtype == torch.float64 else torch.float32)
 
 
 def _r(x, prec):
@@ -344,8 +344,9 @@ class DecodeState:
             self.k_cross.append(ks)
             self.v_cross.append(vs)
         self.t = 0
-        self.k_self = [torch.zeros(self.B, H, t_cap, dh) for _ in range(self.L)]
-        self.v_self = [torch.zeros(self.B, H, t_cap, dh) for _ in range(self.L)]
+        # the self caches take the memory's dtype: a float64 run stays float64 end to end
+        self.k_self = [torch.zeros(self.B, H, t_cap, dh, dtype=mem.dtype) for _ in range(self.L)]
+        self.v_self = [torch.zeros(self.B, H, t_cap, dh, dtype=mem.dtype) for _ in range(self.L)]
 
     def _grow(self):
         for c in (self.k_self, self.v_self):
