@@ -1,7 +1,12 @@
 """Benchmark of the hot path on MI355X (BASELINE.json metric: LMX tokens/sec (greedy decode) + MAE images/sec, 512x2048 input).
 
-    python bench.py --gpus 1 --steps 256 --warmup 32
+    python bench.py --gpus 1 --steps 256 --warmup 32            (headline only)
+    python bench.py --gpus 1 --steps 256 --warmup 32 --full     (headline + every leg, baseline and roofline figure below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up, one prefill, warm-up, the timed steps, `--dump-outputs` and the JSON line.  The
+fields below that take runs of their own (`prefill_ms`, `value_steps256`, `roofline`, `cpu_baseline`, the legs) are measured with `--full`
+only and are None in a plain line.
 
 Headline (`value`): full-size ViTOMR (FineTuneOMREncoder ViT-B/16 + 12-layer d=1024 OMRDecoder, random init, seed 0), batch of 8 synthetic
 512x2048 system images per GPU (4096 patches each), reference inference plumbing (encoder fp32, transition head + decode in bf16 with a bf16
@@ -9,7 +14,7 @@ KV cache).  A "step" is one greedy decode step of the whole batch (8 tokens per 
 weights) are resident in HBM before the timed region.  Multi-GPU: images are independent -> each rank decodes its own batch (weak scaling, no
 data-path collective).
 
-Further legs in the same JSON line (each a dict; an exception in a leg is reported in it and never costs the headline):
+Further legs in the same JSON line with `--full` (each a dict; an exception in a leg is reported in it and never costs the headline):
   end_to_end     inference() TIMED AS CALLED on the headline batch (8 x 512x2048): encoder + head + prefill + 288 generated tokens      (N = 1)
   latency_b1     BASELINE config 1 on the GPU: inference() on ONE 256x1024 image, 256 generated tokens, ms/token, with the CPU oracle's
                  run of the same call beside it                                                                                    (N = 1)
@@ -559,9 +564,9 @@ def dry_run(a):
         import torch.distributed as dist
         dist.init_process_group("gloo")
     dev = torch.device("cpu")
-    legs = set((a.legs.split(",") if a.legs is not None else (["e2e", "b1", "mae", "tf", "ragged"] if world == 1 else ["mae", "config5"])))
+    legs = set((a.legs.split(",") if a.legs is not None else (["e2e", "b1", "mae", "tf", "ragged"] if world == 1 else ["mae", "config5"])) if a.full else [])
     legs.discard("")
-    if a.legs is None:
+    if a.full and a.legs is None:
         assert legs == ({"e2e", "b1", "mae", "tf", "ragged"} if world == 1 else {"mae", "config5"}), legs   # what the driver's N = 1, 2, 4, 8 runs select
     if a.no_mae:
         legs.discard("mae")
@@ -656,7 +661,9 @@ def main():
     ap.add_argument("--mae-batch", type=int, default=32)
     ap.add_argument("--mae-steps", type=int, default=5)
     ap.add_argument("--mae-dtype", default="bf16", choices=["fp32", "bf16"])
-    ap.add_argument("--legs", default=None, help="comma list of e2e,b1,mae,tf,ragged,config5 (default: e2e,b1,mae,tf,ragged at N = 1; mae,config5 at N > 1)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure the timed prefill, the 256-step window, the roofline kernel timing, "
+                    "the CPU baselines and the secondary legs (a plain run measures the headline only)")
+    ap.add_argument("--legs", default=None, help="with --full: comma list of e2e,b1,mae,tf,ragged,config5 (default: e2e,b1,mae,tf,ragged at N = 1; mae,config5 at N > 1)")
     ap.add_argument("--no-mae", action="store_true")
     ap.add_argument("--grad-comm-dtype", default="fp32", choices=["fp32", "bf16"], help="what the gradient buckets travel as at N > 1 (dist.GradAllReduce comm_dtype)")
     ap.add_argument("--leg-timeout", type=float, default=420.0, help="seconds the secondary legs may take before the line is printed without them")
@@ -665,6 +672,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="control flow only, on the CPU over gloo: argument parsing, rank / leg selection, the collectives "
                     "around the timed regions and the JSON line's shape, with stand-in numbers (no kernel runs; `dry_run: true` marks the line)")
     a = ap.parse_args()
+    if a.legs and not a.full:
+        ap.error("--legs selects among the legs of a --full run; add --full")
     if a.dry_run:
         return dry_run(a)
 
@@ -681,7 +690,7 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
         else:
             dist.init_process_group(backend)
-    legs = set((a.legs.split(",") if a.legs is not None else (["e2e", "b1", "mae", "tf", "ragged"] if world == 1 else ["mae", "config5"])))
+    legs = set((a.legs.split(",") if a.legs is not None else (["e2e", "b1", "mae", "tf", "ragged"] if world == 1 else ["mae", "config5"])) if a.full else [])
     legs.discard("")
     if a.no_mae:
         legs.discard("mae")
@@ -692,7 +701,7 @@ def main():
     g = torch.Generator().manual_seed(1000 + rank)
     imgs = [torch.rand(1, a.height, a.width, generator=g).to(dev) for _ in range(a.batch)]
 
-    # ---- prefill (timed once, reported separately) ----------------------------------------------------------------------
+    # ---- prefill (with --full: timed once more, warm, and reported separately) ---------------------------------------------
     with torch.no_grad():
         def prefill():
             with autocast(device_type="cuda", dtype=torch.bfloat16, enabled=a.encoder_dtype == "bf16"):
@@ -701,12 +710,14 @@ def main():
                 mem = vitomr.transition_head.forward_packed(lat32)
             vitomr.decoder.decoder_blocks.prepare_caches_packed(None, mem, lens)
             return lens
-        prefill()  # warm-up (code-object loads, allocator)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
         lens = prefill()
-        torch.cuda.synchronize()
-        prefill_s = time.perf_counter() - t0
+        prefill_s = None
+        if a.full:   # timed warm: the first call loaded the code objects and settled the allocator
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lens = prefill()
+            torch.cuda.synchronize()
+            prefill_s = time.perf_counter() - t0
 
     eng = vitomr.decoder.decoder_blocks.engine(dev)
     cap = eng.Tmax - 2   # decode steps one armed sequence can take before the 1536-token self-attention cache is full
@@ -749,7 +760,7 @@ def main():
             dump = dict(seqs=eng.seqs[:eng.B, :t].clone(), logprobs=eng.logprobs[:eng.B, :t].clone(), logits=eng.ws["logits"][:eng.B].clone())
         # the same region over 256 steps (0.2 s): the driver's --steps 20 times 14 ms, this side field says what a longer window gives
         dt256 = None
-        if a.steps != 256:
+        if a.full and a.steps != 256:
             _barrier_sync(dist)
             t1 = time.perf_counter()
             run_steps(256)
@@ -766,7 +777,7 @@ def main():
 
     roof = None
     S = lens[0]
-    if rank == 0:
+    if rank == 0 and a.full:
         t_mid = min(a.warmup + a.steps // 2, cap // 2) if a.warmup + a.steps <= cap else cap // 2
         # algorithmic bytes: weights once per step + per sequence 12*2*(S + t)*1024*2 B
         w_bytes = decode_weight_bytes(vitomr.decoder)
@@ -792,7 +803,7 @@ def main():
                                            "self-attention + embed / argmax", us_per_step=chain_s * 1e6, weight_bytes=w_bytes,
                                       achieved_GBs=w_bytes / chain_s / 1e9, frac=w_bytes / chain_s / 1e9 / HBM_PEAK_GBS))
     del eng
-    want_cpu = world == 1 and not a.no_cpu_baseline and rank == 0
+    want_cpu = a.full and world == 1 and not a.no_cpu_baseline and rank == 0
     cpu = cpu_baseline_decode(vitomr, lens, a.cpu_steps) if want_cpu else None
     del vitomr
     torch.cuda.empty_cache()
@@ -832,9 +843,9 @@ def main():
                    config=dict(workload=f"vitomr_greedy_decode batch {a.batch}/GPU of {a.height}x{a.width} images ({S} patches), decode steps {a.warmup + 1}..{a.warmup + a.steps}" + ("" if a.warmup + a.steps <= cap else f" (re-armed every {cap} steps)"),
                                batch_per_gpu=a.batch, memory_len=S, decoder="12 x d1024 h16 mlp4096, V=227", hipgraph=use_graph,
                                split_merge=_split_merge_path()),
-                   prefill_ms=prefill_s * 1e3, prefill_encoder_dtype=a.encoder_dtype, roofline=roof, cpu_baseline=cpu, mae=mae_res, tf_step=tf_res,
-                   ragged_decode=rag_res, config5=c5_res, dist=dinfo,
-                   value_steps256=(tokens / dt if a.steps == 256 else world * a.batch * 256 / dt256))
+                   prefill_ms=None if prefill_s is None else prefill_s * 1e3, prefill_encoder_dtype=a.encoder_dtype, roofline=roof, cpu_baseline=cpu,
+                   mae=mae_res, tf_step=tf_res, ragged_decode=rag_res, config5=c5_res, dist=dinfo,
+                   value_steps256=(None if not a.full else tokens / dt if a.steps == 256 else world * a.batch * 256 / dt256))
         if timed_out:
             out["legs_timed_out"] = f"secondary legs did not finish within {a.leg_timeout} s; fields still None were not measured"
         # decode-only (`value`) and end to end.  `end_to_end` = a TIMED call of inference() on the same batch shape (encoder + head +

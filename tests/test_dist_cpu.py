@@ -304,14 +304,15 @@ def test_parameter_without_gradient_on_every_rank_keeps_none(tmp_path):
 
 
 def test_bench_dry_run_two_ranks():
-    """`bench.py --gpus 2 --dry-run` under torch.distributed.run (gloo, CPU): the launcher contract, the leg selection at N > 1 and the JSON
-    line's keys, incl. config 5's shard deal - what the driver's first multi-GPU run exercises around the kernels."""
+    """`bench.py --gpus 2 --dry-run --full` under torch.distributed.run (gloo, CPU): the launcher contract, the leg selection at N > 1 and the
+    JSON line's keys, incl. config 5's shard deal - what the driver's first multi-GPU run exercises around the kernels.  Without `--full` the
+    line carries the headline alone."""
     import json
     import subprocess
     port = 33500 + os.getpid() % 2000
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-                        str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--dry-run"],
+                        str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--dry-run", "--full"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -331,21 +332,29 @@ def test_bench_dry_run_two_ranks():
     for leg in ("mae", "tf_step"):
         assert "allreduce_exposed_ms" in c5[leg] and "grad_bytes_on_wire" in c5[leg] and c5[leg]["grad_comm_dtype"] == "fp32"
     # and the single-process form selects the single-GPU legs
-    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "3"], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "3", "--full"], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
     assert r1.returncode == 0, r1.stderr[-2000:]
     d1 = json.loads([ln for ln in r1.stdout.splitlines() if ln.startswith("{")][0])
     assert d1["n_gpus"] == 1 and d1["config5"] is None and d1["end_to_end"] is not None and d1["latency_b1"] is not None and d1["tf_step"] is not None
+    # a plain run selects no leg; --legs without --full is refused
+    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "3"], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+    assert r2.returncode == 0, r2.stderr[-2000:]
+    d2 = json.loads([ln for ln in r2.stdout.splitlines() if ln.startswith("{")][0])
+    assert d2["n_gpus"] == 1 and d2["steps"] == 3 and d2["ms_per_step"] > 0 and d2["value"] > 0
+    assert all(d2[k] is None for k in ("roofline", "cpu_baseline", "mae", "tf_step", "ragged_decode", "config5", "end_to_end", "latency_b1", "value_steps256"))
+    r3 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--legs", "mae"], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+    assert r3.returncode == 2 and "--full" in r3.stderr, r3.stderr[-2000:]
 
 
 def test_bench_dry_run_eight_ranks_selects_the_multi_gpu_legs():
-    """The driver's N = 8 launch, rehearsed on the CPU (8 gloo ranks): default legs = mae + config5 (asserted inside --dry-run), the config-5 keys
+    """The driver's N = 8 launch with --full, rehearsed on the CPU (8 gloo ranks): default legs = mae + config5 (asserted inside --dry-run), the config-5 keys
     the scaling record will be read from, the bf16 bucket option on the command line, 8 device entries."""
     import json
     import subprocess
     port = 37500 + os.getpid() % 2000
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port",
-                        str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--dry-run", "--grad-comm-dtype", "bf16"],
+                        str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--dry-run", "--full", "--grad-comm-dtype", "bf16"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

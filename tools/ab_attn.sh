@@ -23,4 +23,4 @@ for v in ${ACAI_AB_PMC_VARIANTS:-main}; do
 done
 python3 $R/tools/pmc_attn_summary.py $O > $O/pmc_summary.txt 2>&1; cat $O/pmc_summary.txt
 rm -f $(find $O -name "*kernel_trace.csv")
-cd $R && timeout -k 10 300 python3 bench.py --legs mae,tf --no-cpu-baseline > $O/bench_legs.log 2>&1; tail -1 $O/bench_legs.log | python3 -c "import sys, json; d = json.loads(sys.stdin.readline()); print('mae', d.get('mae'), 'tf', d.get('tf_step'))" || tail -5 $O/bench_legs.log
+cd $R && timeout -k 10 300 python3 bench.py --full --legs mae,tf --no-cpu-baseline > $O/bench_legs.log 2>&1; tail -1 $O/bench_legs.log | python3 -c "import sys, json; d = json.loads(sys.stdin.readline()); print('mae', d.get('mae'), 'tf', d.get('tf_step'))" || tail -5 $O/bench_legs.log
