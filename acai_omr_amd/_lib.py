@@ -47,6 +47,11 @@ class AcaiDecoder(Structure):
             "step", "finished", "x", "xn", "qkv", "attn", "proj", "hid", "logits", "partial", "tickets", "stats")]
 
 
+class AcaiBeam(Structure):
+    _fields_ = [("K", c_int32), ("pitch", c_int32), ("rows", c_int32), ("pad_", c_int32)] + [
+        (n, c_void_p) for n in ("anc", "tok", "lp", "cum", "len")]
+
+
 _SIGNATURES = {
     "acai_version": (c_int, []),
     "acai_last_error": (c_char_p, []),
@@ -102,6 +107,7 @@ _SIGNATURES = {
     "acai_decode_embed": (c_int, [POINTER(AcaiDecoder), c_void_p]),
     "acai_decode_step": (c_int, [POINTER(AcaiDecoder), c_void_p]),
     "acai_decode_sample_step": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_float, c_void_p]),
+    "acai_decode_beam_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiBeam), c_void_p]),
     "acai_decode_logits": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_void_p]),
     "acai_decode_hidden": (c_int, [POINTER(AcaiDecoder), c_void_p, c_void_p]),
     "acai_decode_merge_in_launch": (c_int, [c_int, c_int]),

@@ -765,13 +765,19 @@ struct DAttnArgs {
     float *out;              // nsplit == 1: the workgroup writes softmax(qK^T)V itself to out[b, h*dh + d] (no combine launch)
     int ldo, round_out;
     unsigned *tickets;       // [B*H] arrival counters (zero between launches): the LAST workgroup of a (b, h) merges the splits
+    // beam search (ANC instantiation only): key p of row b lives in cache row anc[b][p] of the parity copy (step[0] & 1) of the ancestor table
+    const int32_t *anc;      // [2][rows][anc_pitch]
+    int anc_pitch;
+    long long anc_bstride;   // elements between the two parity copies (rows * anc_pitch)
 };
 
 // LPK = lanes per key = dhp * sizeof(TC) / 16.  RAGGED = cross attention over the ragged encoder memory (the dominant
 // HBM stream of a decode step); !RAGGED = self attention over the [B][H][Tmax][dhp] cache.  Two instantiations so that
-// rocprof reports them as separate kernels.
-template <typename TC, int LPK, bool RAGGED, int U = 2>
+// rocprof reports them as separate kernels.  ANC (self attention of a beam step, !RAGGED only): the cache rows are read through the
+// ancestor table - key p of row b from k_self[anc[b][p]][h][p][:] - staged in LDS (dynamic shared memory, chunk ints) before the key loop.
+template <typename TC, int LPK, bool RAGGED, int U = 2, bool ANC = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
+    static_assert(!(ANC && RAGGED), "the ancestor table indexes the self-attention cache");
     constexpr int EPC = 16 / sizeof(TC), KPW = 64 / LPK;
     __shared__ float red[4][2 + 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -783,6 +789,10 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
         len = a.seq_len[b];
         hstride = len * a.dhp;
         base = (size_t)a.seq_off[b] + (size_t)h * hstride;
+    } else if constexpr (ANC) {
+        len = a.step[1] + 1;
+        hstride = a.Tmax * a.dhp;
+        base = (size_t)h * hstride;   // + anc[b][p] * H * hstride per key
     } else {
         len = a.step[1] + 1;
         hstride = a.Tmax * a.dhp;
@@ -802,6 +812,18 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
     }
     const TC *Kp = reinterpret_cast<const TC *>(a.kc) + base;
     const TC *Vp = reinterpret_cast<const TC *>(a.vc) + base;
+    [[maybe_unused]] int32_t *anc_s = nullptr;
+    if constexpr (ANC) {
+        extern __shared__ int32_t anc_dyn[];
+        anc_s = anc_dyn;
+        const int32_t *ar = a.anc + (size_t)(a.step[0] & 1) * a.anc_bstride + (size_t)b * a.anc_pitch;
+        for (int p = c0 + tid; p < c1; p += 256) anc_s[p - c0] = ar[p];
+        __syncthreads();
+    }
+    auto key_off = [&](int key) -> size_t {
+        if constexpr (ANC) return (size_t)anc_s[key - c0] * a.H * hstride + (size_t)key * a.dhp;
+        else return (size_t)key * a.dhp;
+    };
 
     float qf[EPC];
 #pragma unroll
@@ -823,8 +845,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
             kn[u] = vn[u] = make_uint4(0, 0, 0, 0);
             if (key < c1) {
                 // every K/V byte is read exactly once per step: non-temporal loads (streaming cache policy)
-                kn[u] = ld_nt16(Kp + (size_t)key * a.dhp + kq * EPC);
-                vn[u] = ld_nt16(Vp + (size_t)key * a.dhp + kq * EPC);
+                kn[u] = ld_nt16(Kp + key_off(key) + kq * EPC);
+                vn[u] = ld_nt16(Vp + key_off(key) + kq * EPC);
             }
         }
     };
@@ -1223,6 +1245,32 @@ __global__ __launch_bounds__(256) void embed_kernel(const float *emb, const floa
 
 __global__ void set_step_kernel(int32_t *step, int t) { step[0] = t; }
 
+// One wave over a logit row: the row maximum `best` at its first index `bi` (torch.argmax on CPU) and sum_i exp(lg[i] - best), returned
+// wave-uniform.  The greedy step and the beam step share it, so that a beam of width 1 reproduces greedy's log-probabilities bit for bit.
+__device__ __forceinline__ float row_argmax_sumexp(const float *lg, int V, int lane, float &best, int &bi) {
+    best = -INFINITY;
+    bi = 0x7fffffff;
+    for (int i = lane; i < V; i += 64) {
+        const float v = lg[i];
+        if (v > best) {  // strided scan keeps the lowest index per lane on ties
+            best = v;
+            bi = i;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {  // argmax, first index on ties (torch.argmax on CPU)
+        const float ov = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bi, o);
+        if (ov > best || (ov == best && oi < bi)) {
+            best = ov;
+            bi = oi;
+        }
+    }
+    float se = 0.f;
+    for (int i = lane; i < V; i += 64) se += expf(lg[i] - best);
+    return wave_sum(se);
+}
+
 // cached_get_next_token (M:579-581) + loop bookkeeping (M:606-611).  One workgroup, wave w takes rows w, w+4, ...
 // With `emb`: the wave that chose row b's token also writes the NEXT step's input x[b] = vocab_embedding[token] + pos_embedding[t + 1]
 // (quirk Q1: the token at index t is embedded with position t + 1, M:576), so a token step needs no embed launch of its own.
@@ -1236,27 +1284,9 @@ __global__ __launch_bounds__(1024) void argmax_logprob_kernel(const float *logit
     const int nw = blockDim.x >> 6;
     for (int b = wave; b < B; b += nw) {
         const float *lg = logits + (size_t)b * V;
-        float best = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int i = lane; i < V; i += 64) {
-            const float v = lg[i];
-            if (v > best) {  // strided scan keeps the lowest index per lane on ties
-                best = v;
-                bi = i;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {  // argmax, first index on ties (torch.argmax on CPU)
-            const float ov = __shfl_xor(best, o);
-            const int oi = __shfl_xor(bi, o);
-            if (ov > best || (ov == best && oi < bi)) {
-                best = ov;
-                bi = oi;
-            }
-        }
-        float se = 0.f;
-        for (int i = lane; i < V; i += 64) se += expf(lg[i] - best);
-        se = wave_sum(se);
+        float best;
+        int bi;
+        const float se = row_argmax_sumexp(lg, V, lane, best, bi);
         float lp = -logf(se);  // logit[argmax] - logsumexp
         if (round_lp) lp = round_bf16(lp);
         if (bookkeeping) {
@@ -1383,6 +1413,155 @@ __global__ __launch_bounds__(64) void sample_bookkeeping_kernel(int B, int32_t *
 
 __global__ void advance_cache_kernel(int32_t *step) { step[1] = step[1] + 1; }
 
+// ---- beam search (an extension: the reference decodes greedily) ------------------------------------------------------------------------
+constexpr int BEAM_MAX = 16;
+
+struct BeamArgs {
+    const float *logits;
+    int V, K, E, Tmax, pitch, eos, pad, round_lp;
+    const int32_t *step;
+    int32_t *finished;
+    const float *emb, *pos;
+    float *x;
+    int32_t *anc;
+    int64_t *tok;
+    float *lp;
+    long long bstride;   // elements between the two parity copies of the lineage
+    float *cum;
+    int32_t *len;
+};
+
+// One workgroup per image (rows r0 .. r0 + K - 1), step t = step[0]; lineage copy (t & 1) is read, copy (t + 1) & 1 written.
+//   1. the K rows' (cum, finished, len) into LDS (this workgroup is their only writer);
+//   2. wave w builds the candidates of rows w, w + 4, ...: a live row its K best tokens by raw logit in K rounds of a wave-wide arg-max (lower
+//      index first on ties, sample_logprob_kernel's pattern), score cum + lp with greedy's row max / sum of exponentials; a finished row the
+//      single candidate (itself + <pad>, lp 0, score cum); a row at cum = -inf none.  Candidate c = parent * K + rank;
+//   3. thread c ranks its candidate against all K*K (score descending, then c ascending = parent slot, then rank): rank j < K -> slot j;
+//   4. wave w fills new slots w, w + 4, ...: the parent's lineage up to position t - 1 plus (slot, token, lp) at t, cum, finished, len and the
+//      next step's input emb[token] + pos[t + 1].
+__global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
+    __shared__ float cs[BEAM_MAX * BEAM_MAX], clp[BEAM_MAX * BEAM_MAX];
+    __shared__ int ctok[BEAM_MAX * BEAM_MAX];
+    __shared__ float pcum[BEAM_MAX];
+    __shared__ int pfin[BEAM_MAX], plen[BEAM_MAX], sel[BEAM_MAX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = a.K, NC = K * K, r0 = blockIdx.x * K;
+    const int t = a.step[0];
+    const size_t cur = (size_t)(t & 1) * a.bstride, nxt = (size_t)((t + 1) & 1) * a.bstride;
+    if (tid < K) {
+        pcum[tid] = a.cum[r0 + tid];
+        pfin[tid] = a.finished[r0 + tid];
+        plen[tid] = a.len[r0 + tid];
+        sel[tid] = -1;
+    }
+    if (tid < NC) cs[tid] = -INFINITY;
+    __syncthreads();
+    const int kv = min(K, a.V);
+    for (int k = wave; k < K; k += 4) {
+        const float c0 = pcum[k];
+        if (c0 == -INFINITY) continue;
+        if (pfin[k]) {
+            if (lane == 0) {
+                cs[k * K] = c0;
+                ctok[k * K] = a.pad;
+                clp[k * K] = 0.f;
+            }
+            continue;
+        }
+        const float *lg = a.logits + (size_t)(r0 + k) * a.V;
+        float best;
+        int bi;
+        const float lse = logf(row_argmax_sumexp(lg, a.V, lane, best, bi));
+        float v[8];   // lane owns vocabulary entries lane, lane + 64, ... (V <= 512)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (lane + 64 * j < a.V) ? lg[lane + 64 * j] : -INFINITY;
+        for (int r = 0; r < kv; ++r) {
+            float bv = -INFINITY;
+            int bj = 0x7fffffff;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (v[j] > bv) {
+                    bv = v[j];
+                    bj = lane + 64 * j;
+                }
+            if (bv == -INFINITY) bj = 0x7fffffff;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o);
+                const int oi = __shfl_xor(bj, o);
+                if (ov > bv || (ov == bv && oi < bj)) {
+                    bv = ov;
+                    bj = oi;
+                }
+            }
+            if ((bj & 63) == lane) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (bj == lane + 64 * j) v[j] = -INFINITY;
+            }
+            if (lane == 0 && bj < a.V) {
+                const float l = -(lse - (bv - best));   // = (logit - max) - lse; -lse exactly for the arg-max (greedy's -logf(se))
+                cs[k * K + r] = c0 + l;
+                ctok[k * K + r] = bj;
+                clp[k * K + r] = l;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < NC) {
+        const float sc = cs[tid];
+        if (sc > -INFINITY) {
+            int rank = 0;
+            for (int c = 0; c < NC; ++c) {
+                const float o = cs[c];
+                rank += (o > sc || (o == sc && c < tid)) ? 1 : 0;
+            }
+            if (rank < K) sel[rank] = tid;
+        }
+    }
+    __syncthreads();
+    for (int j = wave; j < K; j += 4) {
+        const int c = sel[j], row = r0 + j;
+        int par = j, tk = a.pad, fin = 1, ln = 0;
+        float l = 0.f, sc = -INFINITY;
+        if (c >= 0) {   // (no candidate: a dead slot - it keeps its own lineage, extended by <pad>)
+            par = c / K;
+            tk = ctok[c];
+            l = clp[c];
+            sc = cs[c];
+            if (pfin[par]) {
+                ln = plen[par];
+            } else if (tk == a.eos) {
+                ln = t;
+            } else {
+                fin = 0;
+            }
+        }
+        const size_t src = cur + (size_t)(r0 + par) * a.pitch, dst = nxt + (size_t)row * a.pitch;
+        const int tc = min(t, a.pitch);
+        for (int p = lane; p < tc; p += 64) {
+            a.anc[dst + p] = a.anc[src + p];
+            a.tok[dst + p] = a.tok[src + p];
+            a.lp[dst + p] = a.lp[src + p];
+        }
+        if (lane == 0) {
+            if (t < a.pitch) {
+                a.anc[dst + t] = row;   // the next step writes this row's K/V at position t
+                a.tok[dst + t] = tk;
+                a.lp[dst + t] = a.round_lp ? round_bf16(l) : l;
+            }
+            a.cum[row] = sc;
+            a.finished[row] = fin;
+            a.len[row] = ln;
+        }
+        if (t + 1 < a.Tmax)   // next step's input (see argmax_logprob_kernel)
+            for (int i = lane * 4; i < a.E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(a.emb + (size_t)tk * a.E + i), pv = *reinterpret_cast<const float4 *>(a.pos + (size_t)(t + 1) * a.E + i);
+                *reinterpret_cast<float4 *>(a.x + (size_t)row * a.E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+    }
+}
+
 // rollout groups: B rows = B / group images x group rows (bf16, dhp = 64; needs the in-launch merge or a single split)
 inline int launch_dattn_group(const DAttnArgs &a, int B, int group, hipStream_t st) {
     const int gtm = cdiv(group, 16);
@@ -1401,6 +1580,7 @@ int launch_dattn(const DAttnArgs &a, int B, hipStream_t st) {
         if (a.seq_off && L == 8 && dattn_u == 4) hipLaunchKernelGGL((decode_attn_kernel<TC, 8, true, 4>), grid, dim3(256), 0, st, a);  \
         else if (a.seq_off && L == 8 && dattn_u == 3) hipLaunchKernelGGL((decode_attn_kernel<TC, 8, true, 3>), grid, dim3(256), 0, st, a);  \
         else if (a.seq_off) hipLaunchKernelGGL((decode_attn_kernel<TC, L, true>), grid, dim3(256), 0, st, a);  \
+        else if (a.anc) hipLaunchKernelGGL((decode_attn_kernel<TC, L, false, 2, true>), grid, dim3(256), sizeof(int32_t) * a.chunk, st, a); \
         else hipLaunchKernelGGL((decode_attn_kernel<TC, L, false>), grid, dim3(256), 0, st, a);           \
         break;
     switch (lpk) {
@@ -1483,7 +1663,8 @@ int check_decoder(const AcaiDecoder *d) {
 }
 
 template <typename TW>
-int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, bool do_embed = true, bool do_unembed = true) {
+int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, bool do_embed = true, bool do_unembed = true,
+                const AcaiBeam *beam = nullptr) {
     const int B = d->B, E = d->E, H = d->H, F = d->F;
     const int rnd = (d->flags & ACAI_GEMM_ROUND_BF16) ? ACAI_GEMM_ROUND_BF16 : 0;
     const float sc = 1.4426950408889634f / sqrtf((float)d->dh);
@@ -1512,6 +1693,9 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
             a.seq_off = d->cross_off; a.seq_len = d->cross_len; a.chunk = d->cross_chunk; a.nsplit = d->cross_nsplit;
         } else {
             a.step = d->step; a.chunk = d->self_chunk; a.nsplit = d->self_nsplit;
+            if (beam) {   // beam step: keys through the ancestor table (decode_attn_kernel's ANC instantiation)
+                a.anc = beam->anc; a.anc_pitch = beam->pitch; a.anc_bstride = (long long)beam->rows * beam->pitch;
+            }
         }
         // rollout groups (bf16, d_h padded to 64): one K/V stream per image through the matrix-core kernel; otherwise the rows simply alias
         // the stored K/V through the per-row kernel (ACAI_DECODE_GROUP_KERNEL=0 forces that form: A/B aid)
@@ -1766,6 +1950,33 @@ extern "C" int acai_decode_sample_step(const AcaiDecoder *d, const float *unifor
                        chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax);
     hipLaunchKernelGGL(sample_bookkeeping_kernel, dim3(1), dim3(64), 0, st, d->B, d->step, d->finished);
     ACAI_LAUNCH_CHECK("sample_logprob");
+    return 0;
+}
+
+extern "C" int acai_decode_beam_step(const AcaiDecoder *d, const AcaiBeam *bs, void *stream) {
+    int rc = check_decoder(d);
+    if (rc) return rc;
+    ACAI_CHECK_ARG(d->emb && d->pos && d->unembed_w && d->logits, "acai_decode_beam_step: decoder has no embedding / unembed");
+    ACAI_CHECK_ARG(d->seqs && d->logprobs && d->finished && d->max_len > 1, "acai_decode_beam_step: null sequence state");
+    ACAI_CHECK_ARG(bs && bs->anc && bs->tok && bs->lp && bs->cum && bs->len, "acai_decode_beam_step: null beam state");
+    ACAI_CHECK_ARG(bs->K >= 1 && bs->K <= BEAM_MAX && d->B % bs->K == 0 && bs->rows >= d->B && bs->pitch >= d->max_len && d->V <= 512 &&
+                       d->E % 4 == 0 && d->self_chunk <= 16384,
+                   "acai_decode_beam_step: needs 1 <= K <= 16 dividing B, rows >= B, pitch >= max_len, vocabulary <= 512, E %% 4 == 0, "
+                   "self_chunk <= 16384 (K=%d B=%d rows=%d pitch=%d V=%d E=%d)", bs->K, d->B, bs->rows, bs->pitch, d->V, d->E);
+    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_beam_step: x does not hold this step's input embedding - call acai_decode_embed after arming "
+                                   "the sequence state and after every acai_decode_logits / acai_decode_hidden");
+    hipStream_t st = (hipStream_t)stream;
+    rc = d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, nullptr, st, false, true, bs) : decode_core<float>(d, nullptr, st, false, true, bs);
+    if (rc) return rc;
+    BeamArgs a{};
+    a.logits = d->logits; a.V = d->V; a.K = bs->K; a.E = d->E; a.Tmax = d->Tmax; a.pitch = bs->pitch; a.eos = d->eos; a.pad = d->pad;
+    a.round_lp = (d->flags & ACAI_GEMM_ROUND_BF16) ? 1 : 0;
+    a.step = d->step; a.finished = d->finished; a.emb = d->emb; a.pos = d->pos; a.x = d->x;
+    a.anc = bs->anc; a.tok = bs->tok; a.lp = bs->lp; a.bstride = (long long)bs->rows * bs->pitch; a.cum = bs->cum; a.len = bs->len;
+    hipLaunchKernelGGL(beam_select_kernel, dim3(d->B / bs->K), dim3(256), 0, st, a);
+    ACAI_LAUNCH_CHECK("beam_select");
+    hipLaunchKernelGGL(sample_bookkeeping_kernel, dim3(1), dim3(64), 0, st, d->B, d->step, d->finished);
+    ACAI_LAUNCH_CHECK("beam_bookkeeping");
     return 0;
 }
 

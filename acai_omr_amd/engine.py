@@ -260,6 +260,9 @@ class DecodeEngine:
         self.group = 1          # decode rows per stored cross K/V (GRPO rollout groups)
         self._sampler = None    # (top_k, temperature) while a sampling rollout runs, else greedy
         self.uniforms = None    # (Bmax, Tmax) uniforms of the sampling step, allocated on first use
+        self._beam = None       # beam width K while a beam search runs
+        self.beam_anc = None    # beam-search lineage [2][Bmax][Tmax] (anc / tok / lp) and per-row cum / len, allocated on first use
+        self._beam_done = 0
         self.cache_len = 0
         self._desc = None
         self._keep = None
@@ -451,6 +454,68 @@ class DecodeEngine:
             if fin:
                 return
 
+    # ---- beam search (an extension: the reference decodes greedily) ----------------------------------------------------------------------
+    def beam(self, max_len, beam_width, length_penalty=1.0, poll=16, use_graph=True):
+        """Beam search over the B / K images prepared with group_size = K (rows i*K .. i*K+K-1 are the beam slots of image i): up to
+        max_len-1 steps of acai_decode_beam_step, then per image the slot with the highest cum / len^length_penalty (ties: lower slot).
+        Returns seqs (B/K, max_len) int64 and log_probs (B/K, max_len) fp32 of the chosen hypotheses and their cumulative log-probs cum (B/K,)."""
+        K = int(beam_width)
+        if max_len > self.Tmax:
+            raise RuntimeError(f"{max_len} decoding steps is too long for max sequence length of {self.Tmax}")
+        if not 1 <= K <= 16:
+            raise ValueError(f"beam_width must be in [1, 16], got {K}")
+        if self.group != K or self.B % K:
+            raise ValueError(f"beam width {K} needs the memories prepared with group_size={K} (prepared: {self.group})")
+        if self.beam_anc is None:
+            z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.device)  # noqa: E731
+            self.beam_anc = z(2, self.Bmax, self.Tmax, dt=torch.int32)
+            self.beam_tok = z(2, self.Bmax, self.Tmax, dt=torch.int64)
+            self.beam_lp = z(2, self.Bmax, self.Tmax, dt=torch.float32)
+            self.beam_cum = z(self.Bmax, dt=torch.float32)
+            self.beam_len = z(self.Bmax, dt=torch.int32)
+            d = _lib.AcaiBeam()
+            d.pitch, d.rows = self.Tmax, self.Bmax
+            d.anc, d.tok, d.lp = self.beam_anc.data_ptr(), self.beam_tok.data_ptr(), self.beam_lp.data_ptr()
+            d.cum, d.len = self.beam_cum.data_ptr(), self.beam_len.data_ptr()
+            self._beam_desc = d
+        self._beam_desc.K = K
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        self._beam = K
+        try:
+            with torch.cuda.stream(self.stream):
+                _, _, done = self._greedy_on_stream(max_len, poll, use_graph, None)
+                self._beam_done = done
+                seqs, lps, cum, _ = self.beam_slots(max_len)
+                n = self.B // K
+                ln = self.beam_len[:self.B].view(n, K)
+                ln = torch.where(ln == 0, torch.full_like(ln, max_len - 1), ln).to(torch.float32)
+                c = cum.view(n, K)
+                score = torch.where(c == float("-inf"), c, c / ln.pow(float(length_penalty)))
+                rows = torch.arange(n, device=self.device) * K + torch.argmax(score, dim=1)   # first maximum: the lower slot on ties
+                out = seqs.index_select(0, rows), lps.index_select(0, rows), cum.index_select(0, rows)
+        finally:
+            self._beam = None
+        cur.wait_stream(self.stream)
+        return out
+
+    def beam_slots(self, max_len):
+        """Every slot of the last beam search as it ended: tokens (B, max_len), per-token log-probs, cum (B,) and len (B,) (0 = unfinished).
+        The lineage copy written last is (1 + steps run) & 1."""
+        par, B = (1 + self._beam_done) & 1, self.B
+        return self.beam_tok[par, :B, :max_len], self.beam_lp[par, :B, :max_len], self.beam_cum[:B], self.beam_len[:B]
+
+    def _arm_beam(self, B):
+        K, own = self._beam, self.omr
+        self.beam_anc[:, :B] = torch.arange(B, dtype=torch.int32, device=self.device).view(1, B, 1)   # every position: the row's own cache row
+        self.beam_tok[:, :B].fill_(own.pad_idx)
+        self.beam_tok[:, :B, 0] = own.bos_idx
+        self.beam_lp[:, :B].zero_()
+        c = self.beam_cum[:B].view(B // K, K)
+        c.fill_(float("-inf"))
+        c[:, 0] = 0.0                 # one live hypothesis per image: step 1 does not produce K copies of it
+        self.beam_len[:B].zero_()
+
     def arm(self, B):
         own = self.omr
         self.seqs[:B].fill_(own.pad_idx)
@@ -459,6 +524,8 @@ class DecodeEngine:
         self.finished.zero_()
         self.reset_self_cache()
         self.step.copy_(torch.tensor([1, 0], dtype=torch.int32))
+        if self._beam is not None:
+            self._arm_beam(B)
         # input of the first step (<bos> at position 1, quirk Q1); each step's argmax / sampling kernel writes the next step's input
         _lib.check(_lib.lib().acai_decode_embed(ctypes.byref(self._desc), ops._st()), "acai_decode_embed")
         self._x_valid = True
@@ -466,9 +533,12 @@ class DecodeEngine:
     STEPS_PER_GRAPH = 8   # a graph replay costs ~10-15 us of launch latency: amortise it over several decode steps
 
     def _step(self, st):
-        """One decode step on the current stream: greedy, or (self._sampler = (top_k, temperature)) a sampling step."""
+        """One decode step on the current stream: greedy, a sampling step (self._sampler = (top_k, temperature)) or a beam-search step
+        (self._beam = K)."""
         smp = self._sampler
-        if smp is None:
+        if self._beam is not None:
+            _lib.check(_lib.lib().acai_decode_beam_step(ctypes.byref(self._desc), ctypes.byref(self._beam_desc), st), "acai_decode_beam_step")
+        elif smp is None:
             _lib.check(_lib.lib().acai_decode_step(ctypes.byref(self._desc), st), "acai_decode_step")
         else:
             _lib.check(_lib.lib().acai_decode_sample_step(ctypes.byref(self._desc), self.uniforms.data_ptr(), int(smp[0]), float(smp[1]), st),
@@ -477,7 +547,8 @@ class DecodeEngine:
     def ensure_graph(self, nsteps=1):
         """hipGraph of `nsteps` consecutive decode steps for the current (B, cross split) configuration.  Must run on self.stream."""
         B = self.B
-        key = (B, self.cross_nsplit, getattr(self, "cross_chunk", self.CROSS_CHUNK), nsteps, self._sampler, self.group)
+        mode = ("beam", self._beam) if self._beam is not None else self._sampler
+        key = (B, self.cross_nsplit, getattr(self, "cross_chunk", self.CROSS_CHUNK), nsteps, mode, self.group)
         g = self.graphs.get(key)
         if g is None:
             st = ops._st()

@@ -531,6 +531,35 @@ class ViTOMR(nn.Module):
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._greedy_packed(mem32, None, lens, max_len)
 
+    def _beam_packed(self, mem32, memb, lens, beam_width, max_len, length_penalty):
+        blocks = self.decoder.decoder_blocks
+        if not isinstance(blocks, CachedTransformerDecoder):
+            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
+        K = int(beam_width)
+        if not 1 <= K <= 16:
+            raise ValueError(f"beam_width must be in [1, 16], got {beam_width}")
+        if len(lens) * K > blocks.max_batch_size:
+            raise ValueError(f"{len(lens)} images x beam width {K} = {len(lens) * K} decode rows exceed the cache's max batch size of "
+                             f"{blocks.max_batch_size}")
+        blocks.prepare_caches_packed(mem32, memb, lens, group_size=K)
+        eng = blocks.engine(self.decoder.pos_embedding.device)
+        seqs, lps, _ = eng.beam(max_len, K, length_penalty)
+        return self.mask_and_clip_seqs(seqs, lps)
+
+    def cached_beam_generate(self, img_latent, latent_attention_mask=None, beam_width=4, max_len=1536, length_penalty=1.0):
+        """Beam-search decode with KV caching (an extension: the reference decodes greedily) -> seqs (B,T') int64, log_probs (B,T') fp32 per
+        token, mask (B,T') bool, as cached_greedy_generate.  Each image keeps beam_width hypotheses; a step extends each live one by its
+        beam_width best tokens, keeps the beam_width best by cumulative log-probability, and a hypothesis ends at <eos>.  The result per image
+        is the hypothesis with the highest cum / len^length_penalty (len: tokens after <bos>, <eos> included).  beam_width = 1 is greedy,
+        bit for bit.  The K hypotheses of an image share its cross K/V; a selection moves no self K/V, only an ancestor table."""
+        blocks = self.decoder.decoder_blocks
+        if not isinstance(blocks, CachedTransformerDecoder):
+            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
+        if not 1 <= int(beam_width) <= 16:
+            raise ValueError(f"beam_width must be in [1, 16], got {beam_width}")
+        mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
+        return self._beam_packed(mem32, None, lens, beam_width, max_len, length_penalty)
+
     def streamed_cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, flush_interval=25):
         """Generator of {"type", "payload"} events (M:625-647); single image only."""
         if img_latent.shape[0] != 1:

@@ -296,6 +296,35 @@ int acai_decode_step(const AcaiDecoder *dec, void *stream);
  * softmax(top_k(logits)) (models.py:1006-1019).  The draw is the inverse CDF of uniforms[b * max_len + t] over the kept logits in
  * descending order (ties: lower index first), 1 <= top_k <= 64: torch.multinomial's random stream is replaced by caller-supplied uniforms. */
 int acai_decode_sample_step(const AcaiDecoder *d, const float *uniforms, int top_k, float temperature, void *stream);
+
+/* Beam-search state (an extension: the reference decodes greedily only).  Decode row i*K + k is beam slot k of image i; the rows of an
+ * image are one cross-attention group (dec->cross_group = K).  All buffers are device memory, armed by the caller:
+ *   anc/tok/lp: two parity copies [2][rows][pitch] of the lineage of every row, copy (t & 1) valid before step t = step[0]; anc[r][p] =
+ *               the cache row holding row r's self K/V at position p (armed: r), tok / lp = the row's tokens and per-token log-probs
+ *               (armed: <bos> at 0, <pad> after; 0).  A step reads copy (t & 1) and writes copy (t + 1) & 1: the parity is taken on the
+ *               device from step[0], so graphs of any step count may be mixed.
+ *   cum:        [B] fp32 cumulative log-probability (armed: 0 for slot 0, -inf for slots 1..K-1).
+ *   len:        [B] int32 generated length (tokens after <bos>, <eos> included) once the row finished, 0 while it runs (armed: 0). */
+typedef struct {
+    int32_t K;         /* beam width, 1..16; dec->B % K == 0 */
+    int32_t pitch;     /* positions per lineage row, >= dec->max_len */
+    int32_t rows;      /* rows per parity copy, >= dec->B */
+    int32_t pad_;
+    int32_t *anc;
+    int64_t *tok;
+    float *lp;
+    float *cum;
+    int32_t *len;
+} AcaiBeam;
+/* One BEAM-SEARCH decode step t = step[0] for every row: the greedy step's layers with the self attention read through the ancestor table
+ * (the K/V caches are never moved), then per image: every live row (cum > -inf, not finished) proposes its K best tokens by raw logit
+ * (lower index first on ties) with score cum + lp, lp = (logit - max) - log(sum exp(logit - max)) in fp32 (the greedy step's reduction);
+ * a finished row proposes itself extended by <pad> (lp 0, score unchanged); the K best candidates by score (ties: lower parent slot, then
+ * lower rank) become slots 0..K-1 with their parent's lineage plus the new token; a chosen <eos> finishes the row (len = t).  Writes cum,
+ * len, finished[] and the unfinished count finished[B], the next step's input x, and advances step[0] / step[1].  Slots left without a
+ * candidate get cum = -inf and count as finished.  Same checks and the same x contract as acai_decode_sample_step (dec->x must hold the
+ * step's input: acai_decode_embed after arming); V <= 512, E % 4 == 0, self_chunk <= 16384. */
+int acai_decode_beam_step(const AcaiDecoder *d, const AcaiBeam *bs, void *stream);
 /* The same without the token bookkeeping: logits for caller-supplied tokens/time_step (OMRDecoder.cached_generate). */
 int acai_decode_logits(const AcaiDecoder *dec, const int64_t *tokens, int time_step, void *stream);
 
