@@ -52,6 +52,10 @@ class AcaiBeam(Structure):
         (n, c_void_p) for n in ("anc", "tok", "lp", "cum", "len")]
 
 
+class AcaiSlots(Structure):
+    _fields_ = [(n, c_void_p) for n in ("t", "first", "cap")] + [("rows", c_int32), ("pad_", c_int32)]
+
+
 _SIGNATURES = {
     "acai_version": (c_int, []),
     "acai_last_error": (c_char_p, []),
@@ -108,6 +112,8 @@ _SIGNATURES = {
     "acai_decode_step": (c_int, [POINTER(AcaiDecoder), c_void_p]),
     "acai_decode_sample_step": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_float, c_void_p]),
     "acai_decode_beam_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiBeam), c_void_p]),
+    "acai_decode_slot_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p]),
+    "acai_decode_slot_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p, c_int, c_void_p]),
     "acai_decode_logits": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_void_p]),
     "acai_decode_hidden": (c_int, [POINTER(AcaiDecoder), c_void_p, c_void_p]),
     "acai_decode_merge_in_launch": (c_int, [c_int, c_int]),

@@ -757,7 +757,7 @@ struct DAttnArgs {
     const float *q;   // [B, ldq] fp32, head h at column h*dh
     const void *kc, *vc;
     const int64_t *seq_off;  // per-sequence element offset (ragged cross K/V) or null
-    const int32_t *seq_len;  // per-sequence length (cross) or null
+    const int32_t *seq_len;  // per-sequence length (cross) or null; SLOT (with seq_off null): per-row key count
     const int32_t *step;     // self-attention: length = step[1] + 1, layout [B][H][Tmax][dhp]
     float *partial;          // [B][H][nsplit][dhp + 2]
     int ldq, H, dh, dhp, Tmax, chunk, nsplit;
@@ -765,8 +765,13 @@ struct DAttnArgs {
     float *out;              // nsplit == 1: the workgroup writes softmax(qK^T)V itself to out[b, h*dh + d] (no combine launch)
     int ldo, round_out;
     unsigned *tickets;       // [B*H] arrival counters (zero between launches): the LAST workgroup of a (b, h) merges the splits
-    // beam search (ANC instantiation only): key p of row b lives in cache row anc[b][p] of the parity copy (step[0] & 1) of the ancestor table
-    const int32_t *anc;      // [2][rows][anc_pitch]
+    // beam search (ANC instantiation only): key p of row b lives in cache row anc[b][p] of the parity copy (step[0] & 1) of the ancestor table.
+    // Continuous batching (SLOT instantiation only): row b has seq_len[b] keys, key j at ring position (slot_first[b] + j) % Tmax.  The two
+    // share a slot so that the struct - and with it every existing kernel's argument offsets - stays as it was.
+    union {
+        const int32_t *anc;  // [2][rows][anc_pitch]
+        const int32_t *slot_first;
+    };
     int anc_pitch;
     long long anc_bstride;   // elements between the two parity copies (rows * anc_pitch)
 };
@@ -775,9 +780,12 @@ struct DAttnArgs {
 // HBM stream of a decode step); !RAGGED = self attention over the [B][H][Tmax][dhp] cache.  Two instantiations so that
 // rocprof reports them as separate kernels.  ANC (self attention of a beam step, !RAGGED only): the cache rows are read through the
 // ancestor table - key p of row b from k_self[anc[b][p]][h][p][:] - staged in LDS (dynamic shared memory, chunk ints) before the key loop.
-template <typename TC, int LPK, bool RAGGED, int U = 2, bool ANC = false>
+// SLOT (self attention of a continuous-batching step, !RAGGED only): the cache is a ring of Tmax positions shared by the rows' write index
+// step[1]; row b has its own length seq_len[b] and its key j sits at position (slot_first[b] + j) % Tmax of its own cache row.
+template <typename TC, int LPK, bool RAGGED, int U = 2, bool ANC = false, bool SLOT = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
     static_assert(!(ANC && RAGGED), "the ancestor table indexes the self-attention cache");
+    static_assert(!(SLOT && (RAGGED || ANC)), "the ring indexes the self-attention cache of the row itself");
     constexpr int EPC = 16 / sizeof(TC), KPW = 64 / LPK;
     __shared__ float red[4][2 + 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -793,6 +801,10 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
         len = a.step[1] + 1;
         hstride = a.Tmax * a.dhp;
         base = (size_t)h * hstride;   // + anc[b][p] * H * hstride per key
+    } else if constexpr (SLOT) {
+        len = a.seq_len[b];
+        hstride = a.Tmax * a.dhp;
+        base = ((size_t)b * a.H + h) * hstride;
     } else {
         len = a.step[1] + 1;
         hstride = a.Tmax * a.dhp;
@@ -820,9 +832,14 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
         for (int p = c0 + tid; p < c1; p += 256) anc_s[p - c0] = ar[p];
         __syncthreads();
     }
+    [[maybe_unused]] int ring0 = 0;
+    if constexpr (SLOT) ring0 = a.slot_first[b];
     auto key_off = [&](int key) -> size_t {
         if constexpr (ANC) return (size_t)anc_s[key - c0] * a.H * hstride + (size_t)key * a.dhp;
-        else return (size_t)key * a.dhp;
+        else if constexpr (SLOT) {
+            const int p = ring0 + key;   // ring0 < Tmax, key < seq_len[b] <= Tmax
+            return (size_t)(p >= a.Tmax ? p - a.Tmax : p) * a.dhp;
+        } else return (size_t)key * a.dhp;
     };
 
     float qf[EPC];
@@ -1413,6 +1430,76 @@ __global__ __launch_bounds__(64) void sample_bookkeeping_kernel(int B, int32_t *
 
 __global__ void advance_cache_kernel(int32_t *step) { step[1] = step[1] + 1; }
 
+// ---- continuous batching (slot mode; an extension: the reference decodes one static batch) --------------------------------------------
+// The greedy token of every unfinished row at its OWN local time t = slot_t[b] (argmax_logprob_kernel's reduction, so a row decodes as it
+// would in a greedy batch): seqs / logprobs at index t, then either the row finishes (<eos>, or t has reached its cap - 1) and from then on
+// writes nothing, or t advances and the wave writes the row's next input emb[token] + pos[t + 1] (quirk Q1).  Thread 0 publishes the
+// unfinished count finished[B] and advances the shared ring write index step[1] modulo Tmax.  step[0] is not used in slot mode.
+__global__ __launch_bounds__(1024) void slot_argmax_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                          int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap, int eos,
+                                                          int round_lp, const float *emb, const float *pos, float *x, int E, int Tmax) {
+    __shared__ int unfinished[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int cnt = 0;
+    const int nw = blockDim.x >> 6;
+    for (int b = wave; b < B; b += nw) {
+        if (finished[b]) continue;   // wave-uniform: a finished or idle row writes nothing
+        const int t = slot_t[b];
+        const float *lg = logits + (size_t)b * V;
+        float best;
+        int bi;
+        const float se = row_argmax_sumexp(lg, V, lane, best, bi);
+        float lp = -logf(se);
+        if (round_lp) lp = round_bf16(lp);
+        const bool fin = bi == eos || t >= slot_cap[b] - 1;
+        if (lane == 0) {
+            seqs[(size_t)b * max_len + t] = bi;
+            logprobs[(size_t)b * max_len + t] = lp;
+            if (fin) finished[b] = 1;
+            else slot_t[b] = t + 1;
+        }
+        if (!fin) {   // t + 1 <= cap - 1 < max_len <= Tmax
+            cnt += 1;
+            for (int i = lane * 4; i < E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)bi * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+        }
+    }
+    if (lane == 0) unfinished[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < nw; ++w) tot += unfinished[w];
+        finished[B] = tot;
+        const int nxt = step[1] + 1;
+        step[1] = nxt >= Tmax ? 0 : nxt;
+    }
+}
+
+// Arms row rows[i] (one workgroup each) for a new sequence: <bos> then <pad>, log-probs 0, unfinished, local time 1 starting at the current
+// ring write index step[1], cap rows[n + i] (clamped to [2, max_len]) and the first input emb[<bos>] + pos[1].  Rows outside [0, B) are
+// ignored.
+__global__ __launch_bounds__(256) void slot_arm_kernel(const int32_t *rows, int n, int B, int max_len, int64_t *seqs, float *logprobs,
+                                                       int32_t *finished, int32_t *slot_t, int32_t *slot_first, int32_t *slot_cap,
+                                                       const int32_t *step, int bos, int pad, const float *emb,
+                                                       const float *pos, float *x, int E) {
+    const int r = rows[blockIdx.x];
+    if (r < 0 || r >= B) return;
+    const int cap = min(max(rows[n + blockIdx.x], 2), max_len);
+    for (int p = threadIdx.x; p < max_len; p += 256) {
+        seqs[(size_t)r * max_len + p] = p == 0 ? bos : pad;
+        logprobs[(size_t)r * max_len + p] = 0.f;
+    }
+    for (int i = threadIdx.x; i < E; i += 256) x[(size_t)r * E + i] = emb[(size_t)bos * E + i] + pos[(size_t)E + i];
+    if (threadIdx.x == 0) {
+        finished[r] = 0;
+        slot_t[r] = 1;
+        slot_first[r] = step[1];
+        slot_cap[r] = cap;
+    }
+}
+
 // ---- beam search (an extension: the reference decodes greedily) ------------------------------------------------------------------------
 constexpr int BEAM_MAX = 16;
 
@@ -1580,6 +1667,7 @@ int launch_dattn(const DAttnArgs &a, int B, hipStream_t st) {
         if (a.seq_off && L == 8 && dattn_u == 4) hipLaunchKernelGGL((decode_attn_kernel<TC, 8, true, 4>), grid, dim3(256), 0, st, a);  \
         else if (a.seq_off && L == 8 && dattn_u == 3) hipLaunchKernelGGL((decode_attn_kernel<TC, 8, true, 3>), grid, dim3(256), 0, st, a);  \
         else if (a.seq_off) hipLaunchKernelGGL((decode_attn_kernel<TC, L, true>), grid, dim3(256), 0, st, a);  \
+        else if (a.seq_len) hipLaunchKernelGGL((decode_attn_kernel<TC, L, false, 2, false, true>), grid, dim3(256), 0, st, a);             \
         else if (a.anc) hipLaunchKernelGGL((decode_attn_kernel<TC, L, false, 2, true>), grid, dim3(256), sizeof(int32_t) * a.chunk, st, a); \
         else hipLaunchKernelGGL((decode_attn_kernel<TC, L, false>), grid, dim3(256), 0, st, a);           \
         break;
@@ -1664,7 +1752,7 @@ int check_decoder(const AcaiDecoder *d) {
 
 template <typename TW>
 int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, bool do_embed = true, bool do_unembed = true,
-                const AcaiBeam *beam = nullptr) {
+                const AcaiBeam *beam = nullptr, const AcaiSlots *slots = nullptr) {
     const int B = d->B, E = d->E, H = d->H, F = d->F;
     const int rnd = (d->flags & ACAI_GEMM_ROUND_BF16) ? ACAI_GEMM_ROUND_BF16 : 0;
     const float sc = 1.4426950408889634f / sqrtf((float)d->dh);
@@ -1695,6 +1783,9 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
             a.step = d->step; a.chunk = d->self_chunk; a.nsplit = d->self_nsplit;
             if (beam) {   // beam step: keys through the ancestor table (decode_attn_kernel's ANC instantiation)
                 a.anc = beam->anc; a.anc_pitch = beam->pitch; a.anc_bstride = (long long)beam->rows * beam->pitch;
+            }
+            if (slots) {   // slot step: per-row lengths over the ring (decode_attn_kernel's SLOT instantiation)
+                a.seq_len = slots->t; a.slot_first = slots->first;
             }
         }
         // rollout groups (bf16, d_h padded to 64): one K/V stream per image through the matrix-core kernel; otherwise the rows simply alias
@@ -1977,6 +2068,48 @@ extern "C" int acai_decode_beam_step(const AcaiDecoder *d, const AcaiBeam *bs, v
     ACAI_LAUNCH_CHECK("beam_select");
     hipLaunchKernelGGL(sample_bookkeeping_kernel, dim3(1), dim3(64), 0, st, d->B, d->step, d->finished);
     ACAI_LAUNCH_CHECK("beam_bookkeeping");
+    return 0;
+}
+
+static int check_slots(const AcaiDecoder *d, const AcaiSlots *sl, const char *fn) {
+    int rc = check_decoder(d);
+    if (rc) return rc;
+    ACAI_CHECK_ARG(d->emb && d->pos && d->unembed_w && d->logits, "%s: decoder has no embedding / unembed", fn);
+    ACAI_CHECK_ARG(d->seqs && d->logprobs && d->finished && d->max_len > 1 && d->max_len <= d->Tmax, "%s: null sequence state or max_len "
+                   "outside [2, Tmax] (max_len=%d Tmax=%d)", fn, d->max_len, d->Tmax);
+    ACAI_CHECK_ARG(sl && sl->t && sl->first && sl->cap && sl->rows >= d->B, "%s: null slot state or rows < B", fn);
+    ACAI_CHECK_ARG(d->cross_group == 1 && d->E % 4 == 0, "%s: needs cross_group == 1 and E %% 4 == 0 (cross_group=%d E=%d)", fn,
+                   d->cross_group, d->E);
+    return 0;
+}
+
+extern "C" int acai_decode_slot_arm(const AcaiDecoder *d, const AcaiSlots *sl, const int32_t *rows, int n, void *stream) {
+    int rc = check_slots(d, sl, "acai_decode_slot_arm");
+    if (rc) return rc;
+    ACAI_CHECK_ARG(n >= 0 && (n == 0 || rows), "acai_decode_slot_arm: bad row list (n=%d)", n);
+    if (n > 0) {
+        hipLaunchKernelGGL(slot_arm_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, rows, n, d->B, d->max_len, d->seqs, d->logprobs,
+                           d->finished, sl->t, sl->first, sl->cap, (const int32_t *)d->step, d->bos, d->pad,
+                           (const float *)d->emb, (const float *)d->pos, d->x, d->E);
+        ACAI_LAUNCH_CHECK("slot_arm");
+    }
+    x_valid_set(d, true);   // every armed row's x holds its first input; the caller keeps every other row finished or chained
+    return 0;
+}
+
+extern "C" int acai_decode_slot_step(const AcaiDecoder *d, const AcaiSlots *sl, void *stream) {
+    int rc = check_slots(d, sl, "acai_decode_slot_step");
+    if (rc) return rc;
+    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_slot_step: x does not hold this step's input embedding - call acai_decode_slot_arm after "
+                                   "setting up the slot state and after every acai_decode_logits / acai_decode_hidden");
+    hipStream_t st = (hipStream_t)stream;
+    rc = d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, nullptr, st, false, true, nullptr, sl)
+                               : decode_core<float>(d, nullptr, st, false, true, nullptr, sl);
+    if (rc) return rc;
+    hipLaunchKernelGGL(slot_argmax_kernel, dim3(1), dim3(d->B > 8 ? 1024 : (d->B > 4 ? 512 : 256)), 0, st, d->logits, d->V, d->B, d->seqs,
+                       d->logprobs, d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos,
+                       (d->flags & ACAI_GEMM_ROUND_BF16) ? 1 : 0, (const float *)d->emb, (const float *)d->pos, d->x, d->E, d->Tmax);
+    ACAI_LAUNCH_CHECK("slot_argmax");
     return 0;
 }
 

@@ -18,6 +18,7 @@ import weakref
 import torch
 
 from . import _lib, ops
+from .scheduler import SlotScheduler
 
 
 class WeightCache:
@@ -263,6 +264,9 @@ class DecodeEngine:
         self._beam = None       # beam width K while a beam search runs
         self.beam_anc = None    # beam-search lineage [2][Bmax][Tmax] (anc / tok / lp) and per-row cum / len, allocated on first use
         self._beam_done = 0
+        self._slot_mode = False  # True while a continuous-batching run steps the engine (acai_decode_slot_step)
+        self.slot_t = None      # slot state [Bmax] x 3 (local time, ring start, cap), allocated on first use
+        self.slot_steps = 0     # decode steps of the last continuous-batching run (the ring index wrapped slot_steps // Tmax times)
         self.cache_len = 0
         self._desc = None
         self._keep = None
@@ -274,6 +278,7 @@ class DecodeEngine:
         offsets alias it, instead of the reference's group_size materialised copies."""
         G = int(group_size)
         B = len(lens) * G
+        self._slot_mode = False
         if B > self.Bmax:
             raise ValueError(f"The current cache has been setup with a max batch size of {self.Bmax}, but found new key tensors with batch size {B}!")
         E, H, dhp, dev = self.E, self.H, self.dhp, self.device
@@ -517,6 +522,9 @@ class DecodeEngine:
         self.beam_len[:B].zero_()
 
     def arm(self, B):
+        if self._slot_mode:
+            self._slot_reset()
+            return
         own = self.omr
         self.seqs[:B].fill_(own.pad_idx)
         self.seqs[:B, 0] = own.bos_idx
@@ -536,7 +544,9 @@ class DecodeEngine:
         """One decode step on the current stream: greedy, a sampling step (self._sampler = (top_k, temperature)) or a beam-search step
         (self._beam = K)."""
         smp = self._sampler
-        if self._beam is not None:
+        if self._slot_mode:
+            _lib.check(_lib.lib().acai_decode_slot_step(ctypes.byref(self._desc), ctypes.byref(self._slot_desc), st), "acai_decode_slot_step")
+        elif self._beam is not None:
             _lib.check(_lib.lib().acai_decode_beam_step(ctypes.byref(self._desc), ctypes.byref(self._beam_desc), st), "acai_decode_beam_step")
         elif smp is None:
             _lib.check(_lib.lib().acai_decode_step(ctypes.byref(self._desc), st), "acai_decode_step")
@@ -547,7 +557,7 @@ class DecodeEngine:
     def ensure_graph(self, nsteps=1):
         """hipGraph of `nsteps` consecutive decode steps for the current (B, cross split) configuration.  Must run on self.stream."""
         B = self.B
-        mode = ("beam", self._beam) if self._beam is not None else self._sampler
+        mode = ("slot",) if self._slot_mode else ("beam", self._beam) if self._beam is not None else self._sampler
         key = (B, self.cross_nsplit, getattr(self, "cross_chunk", self.CROSS_CHUNK), nsteps, mode, self.group)
         g = self.graphs.get(key)
         if g is None:
@@ -607,3 +617,143 @@ class DecodeEngine:
             if int(self.finished[B].item()) == 0:  # device -> host sync once per `poll` tokens
                 break
         return self.seqs[:B, :max_len], self.logprobs[:B, :max_len], done
+
+    # ---- continuous batching (an extension: the reference decodes one static batch) ----------------------------------------------------
+    def continuous(self, mem32, memb, lens, caps, slots, poll=16, use_graph=True):
+        """Greedy decode of len(lens) images through `slots` decode rows that are refilled as they finish.  mem32 / memb: the images'
+        packed memories (M, E) fp32 / bf16 copy, lens their lengths, caps[i] image i's cap (its row ends after token index caps[i] - 1, or
+        at <eos>).  A generator: yields each image's index once its tokens and per-token log-probs are in `cont_seqs` / `cont_lps`
+        (N, max(caps)), in completion order.  Every image decodes exactly as it would alone in a greedy batch; only the step schedule is
+        shared.  Slot s owns a cross K/V region of max(lens) rows; an idle slot has cross length 1 and stays finished."""
+        N, S, dev, own = len(lens), int(slots), self.device, self.omr
+        caps = [int(c) for c in caps]
+        if max(caps) > self.Tmax:
+            raise RuntimeError(f"{max(caps)} decoding steps is too long for max sequence length of {self.Tmax}")
+        if not 1 <= S <= self.Bmax:
+            raise ValueError(f"slots must be in [1, {self.Bmax}] (the cache's max batch size), got {slots}")
+        if len(caps) != N:
+            raise ValueError(f"{len(caps)} caps for {N} images")
+        mem = memb if self.bf else mem32
+        if mem is None:
+            mem = ops.cast_bf16(mem32)
+        W = max(caps)
+        self.cont_seqs = torch.full((N, W), own.pad_idx, dtype=torch.int64, device=dev)
+        self.cont_seqs[:, 0] = own.bos_idx
+        self.cont_lps = torch.zeros(N, W, dtype=torch.float32, device=dev)
+        sched = SlotScheduler(caps, S)
+        offs = [0]
+        for l in lens:
+            offs.append(offs[-1] + l)
+        cur = torch.cuda.current_stream(dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self._slot_setup(max(lens), S)
+            lens_dev = ops.h2d(torch.tensor(lens, dtype=torch.int32), dev)
+            self._slot_mode = True
+            self.arm(S)
+            if use_graph:   # capture (and warm up) before the loop, then reset: the warm-up launch advances the device state
+                self.ensure_graph(1)
+                self.ensure_graph(self.STEPS_PER_GRAPH)
+                self.arm(S)
+        self.slot_steps = 0
+        harvested = torch.cuda.Event()
+        try:
+            if sched.skipped:
+                harvested.record(self.stream)
+                cur.wait_event(harvested)
+                yield from sched.skipped
+            with torch.cuda.stream(self.stream):
+                self._slot_refill(sched.admit(), mem, offs, lens_dev, caps)
+                n = sched.chunk(poll)
+                self.launch_steps(n, use_graph)
+            while n > 0:
+                with torch.cuda.stream(self.stream):
+                    fin = self.finished[:S].tolist()   # device -> host sync once per poll
+                    self.slot_steps += n
+                    freed = sched.advance(n, fin)
+                    for s, i in freed:   # harvest: device-side copies of the finished rows, before the refill re-arms them
+                        c = caps[i]
+                        self.cont_seqs[i, :c].copy_(self.seqs[s, :c])
+                        self.cont_lps[i, :c].copy_(self.logprobs[s, :c])
+                    harvested.record(self.stream)
+                    self._slot_refill(sched.admit(), mem, offs, lens_dev, caps)
+                    for s in sched.idle():
+                        if s not in self._parked:   # queue drained: the slot goes idle on a 1-key cross length
+                            self.cross_len[s:s + 1].fill_(1)
+                            self._parked.add(s)
+                    n = sched.chunk(poll)
+                    self.launch_steps(n, use_graph)   # the next steps run while the caller reads this poll's images
+                if freed:
+                    cur.wait_event(harvested)
+                    for _, i in freed:
+                        yield i
+        finally:
+            self._slot_mode = False
+            cur.wait_stream(self.stream)
+
+    def _slot_setup(self, Scap, S):
+        """Slot mode for S rows over regions of Scap memory rows: the cross K/V layout, the cross split picked once for [Scap] * S (so that
+        the captured graphs stay valid across refills), the slot state and the descriptors."""
+        H, dhp, dev = self.H, self.dhp, self.device
+        region = Scap * H * dhp
+        if S * region > self.cross_cap:
+            self.cross_cap = S * region
+            self.k_cross = [torch.zeros(S * region, dtype=self.cdt, device=dev) for _ in range(self.L)]
+            self.v_cross = [torch.zeros(S * region, dtype=self.cdt, device=dev) for _ in range(self.L)]
+            self.graphs.clear()
+        self.slot_off = torch.arange(S, dtype=torch.int64, device=dev) * region
+        self.cross_off[:S] = self.slot_off
+        self.cross_len[:S].fill_(1)
+        self.B, self.lens, self.group = S, [Scap] * S, 1
+        self.cross_chunk = self.pick_cross_chunk(self.lens, H)
+        self.cross_nsplit = max(1, -(-Scap // self.cross_chunk))
+        need = S * H * max(self.cross_nsplit, self.self_nsplit) * (dhp + 2)
+        if self.partial is None or self.partial.numel() < need:
+            self.partial = torch.empty(self.Bmax * H * max(self.cross_nsplit, self.self_nsplit) * (dhp + 2), dtype=torch.float32, device=dev)
+            self.graphs.clear()
+        if self.slot_t is None:
+            self.slot_t, self.slot_first, self.slot_cap = (torch.zeros(self.Bmax, dtype=torch.int32, device=dev) for _ in range(3))
+            d = _lib.AcaiSlots()
+            d.t, d.first, d.cap, d.rows = self.slot_t.data_ptr(), self.slot_first.data_ptr(), self.slot_cap.data_ptr(), self.Bmax
+            self._slot_desc = d
+        self._row_seq = torch.zeros(Scap, dtype=torch.int32, device=dev)    # prefill of one image: every row is memory 0 ...
+        self._row_pos = torch.arange(Scap, dtype=torch.int32, device=dev)   # ... at its own position
+        E, prec = self.E, self.prec
+        self._cross_w = [(self.wc.w(ly.multihead_attn.in_proj_weight, prec)[E:], self.wc.b(ly.multihead_attn.in_proj_bias, prec)[E:])
+                         for ly in self.blocks.layers]
+        self._build_desc()
+
+    def _slot_reset(self):
+        """Every slot idle: finished, cross length 1, local time 1 at ring start 0; ring write index 0 (step[0] is unused in slot mode)."""
+        S = self.B
+        self.step.copy_(torch.tensor([1, 0], dtype=torch.int32))
+        self.finished.zero_()
+        self.finished[:S].fill_(1)
+        self.slot_t.fill_(1)
+        self.slot_first.zero_()
+        self.slot_cap.fill_(2)
+        self.cross_len[:S].fill_(1)
+        self._parked = set(range(S))
+        self.cache_len = 0
+        _lib.check(_lib.lib().acai_decode_slot_arm(ctypes.byref(self._desc), ctypes.byref(self._slot_desc), None, 0, ops._st()),
+                   "acai_decode_slot_arm")
+        self._x_valid = True
+
+    def _slot_refill(self, admitted, mem, offs, lens_dev, caps):
+        """Prefill each admitted image's cross K/V into its slot's region (one prefill per image and layer, so that an image's K/V does not
+        depend on which images were admitted with it), set the slot's cross length and arm the slots."""
+        if not admitted:
+            return
+        H, dh, dhp = self.H, self.dh, self.dhp
+        for s, i in admitted:
+            l = offs[i + 1] - offs[i]
+            for li, (w, b) in enumerate(self._cross_w):
+                ops.cross_kv_prefill(mem[offs[i]:offs[i + 1]], w, b, self._row_seq[:l], self._row_pos[:l], self.slot_off[s:s + 1],
+                                     lens_dev[i:i + 1], self.k_cross[li], self.v_cross[li], H, dh, dhp, round_bf16=self.bf)
+            self.cross_len[s:s + 1].copy_(lens_dev[i:i + 1])
+            self._parked.discard(s)
+        rows = torch.tensor([[s for s, _ in admitted], [caps[i] for _, i in admitted]], dtype=torch.int32)
+        rows = ops.h2d(rows, self.device)
+        _lib.check(_lib.lib().acai_decode_slot_arm(ctypes.byref(self._desc), ctypes.byref(self._slot_desc), rows.data_ptr(), len(admitted),
+                                                   ops._st()), "acai_decode_slot_arm")
+        self._keep_rows = rows   # (the arm kernel reads it asynchronously)

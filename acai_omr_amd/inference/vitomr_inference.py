@@ -46,6 +46,50 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
             return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len)
 
 
+def _encode_chunks(vitomr, imgs, device):
+    """Encoder (fp32, outside autocast) and transition head (inside autocast) over chunks of at most max_batch_size images; the packed
+    memories of all chunks, concatenated, and their lengths."""
+    chunk = vitomr.decoder.decoder_blocks.max_batch_size if hasattr(vitomr.decoder.decoder_blocks, "max_batch_size") else len(imgs)
+    mems, lens = [], []
+    for c0 in range(0, len(imgs), chunk):
+        lat32, _, ln = _encode(vitomr, imgs[c0:c0 + chunk])
+        with autocast(device_type=device, dtype=torch.bfloat16):
+            mems.append(vitomr.transition_head.forward_packed(lat32))
+        lens += ln
+    return (mems[0] if len(mems) == 1 else torch.cat(mems)), lens
+
+
+def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None):
+    """Continuous-batching greedy inference (an extension) as a generator: yields (index, seqs (1,T'), log_probs (1,T'), mask (1,T')) for
+    each image as soon as it finishes, in completion order; each is what inference(vitomr, [imgs[index]]) returns.  max_inference_len: one
+    cap or a list of per-image caps; slots: decode rows (default: the cache's max batch size)."""
+    vitomr.eval()
+    imgs = list(imgs)
+    with torch.no_grad():
+        mem, lens = _encode_chunks(vitomr, imgs, device)
+        bf = mem.dtype == torch.bfloat16
+        with autocast(device_type=device, dtype=torch.bfloat16):
+            run = vitomr._continuous_packed_iter(None if bf else mem, mem if bf else None, lens, max_inference_len, slots)
+
+    def images():
+        with torch.no_grad():
+            yield from run
+    return images()
+
+
+def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None):
+    """inference() over a list of any length through continuous batching (an extension): `slots` decode rows work through the images in
+    input order and a finished row is refilled with the next image at once.  Returns exactly what inference(vitomr, imgs, ...) returns
+    (seqs (N,T'), log_probs (N,T'), mask (N,T'), clipped to the longest row); max_inference_len may be a list of per-image caps."""
+    vitomr.eval()
+    imgs = list(imgs)
+    with torch.no_grad():
+        mem, lens = _encode_chunks(vitomr, imgs, device)
+        bf = mem.dtype == torch.bfloat16
+        with autocast(device_type=device, dtype=torch.bfloat16):
+            return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots)
+
+
 def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25):
     vitomr.eval()
     with torch.no_grad():

@@ -482,6 +482,16 @@ class _TransitionHead(nn.Sequential):
         return y.view(*shp[:-1], y.shape[-1])
 
 
+def _continuous_caps(max_len, n):
+    """max_len of the continuous-batching entry points: one cap for all n images or n per-image caps."""
+    if isinstance(max_len, int) or (torch.is_tensor(max_len) and max_len.dim() == 0):
+        return [int(max_len)] * n
+    caps = [int(c) for c in max_len]
+    if len(caps) != n:
+        raise ValueError(f"max_len holds {len(caps)} per-image caps for {n} images")
+    return caps
+
+
 class ViTOMR(nn.Module):
     def __init__(self, encoder, transition_head, decoder):
         super().__init__()
@@ -559,6 +569,58 @@ class ViTOMR(nn.Module):
             raise ValueError(f"beam_width must be in [1, 16], got {beam_width}")
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._beam_packed(mem32, None, lens, beam_width, max_len, length_penalty)
+
+    def _continuous_run(self, mem32, memb, lens, max_len, slots, poll, use_graph):
+        """(engine, caps, generator of finished image indices) of a continuous-batching run; argument errors are raised here, at the call."""
+        blocks = self.decoder.decoder_blocks
+        if not isinstance(blocks, CachedTransformerDecoder):
+            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
+        caps = _continuous_caps(max_len, len(lens))
+        S = blocks.max_batch_size if slots is None else int(slots)
+        if not 1 <= S <= blocks.max_batch_size:
+            raise ValueError(f"slots must be in [1, {blocks.max_batch_size}] (the cache's max batch size), got {slots}")
+        eng = blocks.engine((mem32 if mem32 is not None else memb).device)
+        if max(caps) > eng.Tmax:
+            raise RuntimeError(f"{max(caps)} decoding steps is too long for max sequence length of {eng.Tmax}")
+        return eng, caps, eng.continuous(mem32, memb, lens, caps, S, poll=poll, use_graph=use_graph)
+
+    def _continuous_packed_iter(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True):
+        """Continuous-batching greedy decode of packed memories: yields (index, seqs (1,T'), log_probs (1,T'), mask (1,T')) per image in
+        completion order, each what _greedy_packed of that image alone at its cap returns."""
+        eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph)
+
+        def images():
+            for i in run:
+                yield (i,) + self._mask_and_clip_capped(eng.cont_seqs[i:i + 1, :caps[i]], eng.cont_lps[i:i + 1, :caps[i]], [caps[i]])
+        return images()
+
+    def _mask_and_clip_capped(self, seqs, lps, caps):
+        """mask_and_clip_seqs with per-row caps: positions at or past a row's cap are never part of it."""
+        seq_mask = self.create_inference_mask(seqs)
+        if min(caps) < seqs.shape[1]:
+            seq_mask &= torch.arange(seqs.shape[1], device=seqs.device) < torch.tensor(caps, device=seqs.device).unsqueeze(1)
+        seqs = seqs.masked_fill(~seq_mask, self.decoder.pad_idx)
+        lps = lps.masked_fill(~seq_mask, 0.0)
+        n = int(seq_mask.sum(dim=-1).max())
+        return seqs[:, :n], lps[:, :n], seq_mask[:, :n]
+
+    def _continuous_packed(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True):
+        eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph)
+        for _ in run:
+            pass
+        return self._mask_and_clip_capped(eng.cont_seqs, eng.cont_lps, caps)
+
+    def cached_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None):
+        """Continuous-batching greedy decode (an extension: the reference decodes one static batch) -> seqs (N,T') int64, log_probs (N,T')
+        fp32, mask (N,T') bool, as cached_greedy_generate on the same batch.  `slots` decode rows (default: the cache's max batch size)
+        work through the N images in input order; a row that finishes (<eos> or its cap) is refilled with the next image while the others
+        go on, so N may exceed the max batch size.  max_len: one cap for every image, or a sequence of N per-image caps (positions at or
+        past an image's cap are masked)."""
+        blocks = self.decoder.decoder_blocks
+        if not isinstance(blocks, CachedTransformerDecoder):
+            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
+        mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
+        return self._continuous_packed(mem32, None, lens, max_len, slots)
 
     def streamed_cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, flush_interval=25):
         """Generator of {"type", "payload"} events (M:625-647); single image only."""

@@ -325,6 +325,40 @@ typedef struct {
  * candidate get cum = -inf and count as finished.  Same checks and the same x contract as acai_decode_sample_step (dec->x must hold the
  * step's input: acai_decode_embed after arming); V <= 512, E % 4 == 0, self_chunk <= 16384. */
 int acai_decode_beam_step(const AcaiDecoder *d, const AcaiBeam *bs, void *stream);
+
+/* Continuous-batching state (slot mode; an extension: the reference decodes one static batch).  Each decode row is a SLOT that decodes one
+ * image at a time; when it finishes, the caller harvests it and re-arms the row for the next queued image while the other rows go on.
+ * The self-attention cache of every row is a ring of Tmax positions: every step writes its self K/V at the shared ring write index step[1]
+ * (the same skinny kernels as the greedy step), and the step advances step[1] modulo Tmax.  A row armed when the index was w reads its key
+ * j at ring position (w + j) % Tmax.  A row ends by t = cap - 1 <= max_len - 1 <= Tmax - 1, so its window never overwrites its own keys.
+ * step[0] is not used in slot mode.  All buffers are device memory:
+ *   t:     [rows] int32 local time of each row: the index its next token is written at (armed: 1);
+ *   first: [rows] int32 ring index of the row's key 0 (armed: step[1] at arming, read on the device);
+ *   cap:   [rows] int32 per-row cap: the row finishes after writing index cap - 1 (armed: 2 <= cap <= max_len).
+ * Idle rows (nothing to decode) are kept finished: finished[b] = 1 makes the step write nothing for them.  To keep their cross attention
+ * cheap the caller gives them cross_len[b] = 1 inside their own cross K/V region; nothing an idle row computes reaches seqs / logprobs. */
+typedef struct {
+    int32_t *t;
+    int32_t *first;
+    int32_t *cap;
+    int32_t rows;      /* entries of t / first / cap, >= dec->B */
+    int32_t pad_;
+} AcaiSlots;
+/* One SLOT-MODE greedy step for every row: the greedy step's layers with the self attention of row b over its own t[b] keys on the ring,
+ * then for every unfinished row the greedy token and log-prob (the greedy step's reduction) written at seqs[b][t[b]] / logprobs[b][t[b]];
+ * a row that emits <eos> or reaches t[b] = cap[b] - 1 is marked finished and writes nothing after that; an unfinished row advances t[b]
+ * and gets its next input x[b] = vocab_embedding[token] + pos_embedding[t[b] + 1] (quirk Q1).  Writes the unfinished count finished[B]
+ * and advances step[1] modulo Tmax.  Needs cross_group == 1, E % 4 == 0, 2 <= max_len <= Tmax, and the same x contract as
+ * acai_decode_step: x must hold the input of every unfinished row (acai_decode_slot_arm sets it; acai_decode_logits / acai_decode_hidden
+ * clear it). */
+int acai_decode_slot_step(const AcaiDecoder *d, const AcaiSlots *sl, void *stream);
+/* Arms n rows for new sequences (n >= 0).  rows: device int32 [2][n] - rows[i] the decode row, rows[n + i] its cap (clamped to
+ * [2, max_len]).  The caller has already set the row's cross_len and prefilled its cross K/V region (e.g. acai_cross_kv_prefill at the
+ * row's cross_off), ordered before the next step.  Per row: seqs = <bos> then <pad>, logprobs = 0, finished = 0,
+ * t = 1, first = step[1] (read on the device, so arming is stream-ordered after the steps before it), cap, and x = vocab_embedding[<bos>] +
+ * pos_embedding[1].  Rows outside [0, B) are ignored.  Marks x valid for acai_decode_slot_step: the caller keeps every row it did not arm
+ * either finished or chained from the previous slot step. */
+int acai_decode_slot_arm(const AcaiDecoder *d, const AcaiSlots *sl, const int32_t *rows, int n, void *stream);
 /* The same without the token bookkeeping: logits for caller-supplied tokens/time_step (OMRDecoder.cached_generate). */
 int acai_decode_logits(const AcaiDecoder *dec, const int64_t *tokens, int time_step, void *stream);
 
