@@ -1762,16 +1762,35 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
         ACAI_LAUNCH_CHECK("embed");
     }
 
+    // Fused path (bf16, MFMA skinny GEMM): the residual stream is kept PRE-LayerNorm (z) and every consumer applies the
+    // LayerNorm on load, so a layer is 6 GEMV + 2 attention (+2 combine) launches instead of 17.
+    SkinnyArgs probe{};
+    probe.x = d->x; probe.W = d->layers[0].self_in_w; probe.K = E; probe.ldw = E; probe.ldx = E;
+    const bool fused = sizeof(TW) == 2 && d->stats && rnd && skinny_mfma_ok(probe) && (F % 256 == 0) && F <= SKM_MAXK;
+    bool hid_bf16 = false, hid_in_bf16 = false;
+    // every GEMV of the step: y = x . W^T + bias (+ res); kvl: append the self K/V; lnw / lnb: LayerNorm (eps) of x on load, its row
+    // statistics published to stats_out; rlnw / rlnb / rstats: LayerNorm of res from published statistics; ln2w / ln2b: a second
+    // LayerNorm (eps 1e-6) after the first (unembed).  The LayerNorm operands are only passed on the fused path.
     auto skinny = [&](const float *x, int ldx, const void *W, const float *bias, const float *res, float *y, int ldy, int N, int K,
-                      int flags, const AcaiDecLayer *kvl) -> int {
+                      int flags, const AcaiDecLayer *kvl, const float *lnw = nullptr, const float *lnb = nullptr, float *stats_out = nullptr,
+                      const float *rlnw = nullptr, const float *rlnb = nullptr, const float *rstats = nullptr, float eps = 1e-5f,
+                      const float *ln2w = nullptr, const float *ln2b = nullptr) -> int {
         SkinnyArgs s{};
         s.x = x; s.W = W; s.bias = bias; s.residual = res; s.y = y;
         s.ldx = ldx; s.ldw = K; s.ldr = E; s.ldy = ldy; s.B = B; s.N = N; s.K = K; s.flags = flags;
+        s.ln_w = lnw; s.ln_b = lnb; s.ln_eps = eps; s.stats_out = stats_out; s.rln_w = rlnw; s.rln_b = rlnb; s.rstats = rstats;
+        s.ln2_w = ln2w; s.ln2_b = ln2b; s.ln2_eps = 1e-6f;
+        s.y_bf16 = hid_bf16 && (flags & ACAI_GEMM_ROUND_BF16);
+        s.x_bf16 = hid_in_bf16 && (flags & ACAI_GEMM_ROUND_BF16);
         if (kvl) {
             s.k_cache = kvl->k_self; s.v_cache = kvl->v_self; s.step = d->step;
             s.E = E; s.H = H; s.dh = d->dh; s.dhp = d->dhp; s.Tmax = d->Tmax;
         }
         return launch_skinny<TW>(s, st);
+    };
+    auto unembed = [&](const float *x, const float *lnw, const float *lnb, float eps, const float *ln2w, const float *ln2b) -> int {
+        return skinny(x, E, d->unembed_w, d->unembed_b, nullptr, d->logits, d->V, d->V, E, rnd, nullptr, lnw, lnb, nullptr, nullptr, nullptr,
+                      nullptr, eps, ln2w, ln2b);
     };
     auto attend = [&](const float *q, int ldq, const void *kc, const void *vc, bool cross) -> int {
         DAttnArgs a{};
@@ -1807,44 +1826,23 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
         return 0;
     };
 
-    // Fused path (bf16, MFMA skinny GEMM): the residual stream is kept PRE-LayerNorm (z) and every consumer applies the
-    // LayerNorm on load, so a layer is 6 GEMV + 2 attention (+2 combine) launches instead of 17.
-    SkinnyArgs probe{};
-    probe.x = d->x; probe.W = d->layers[0].self_in_w; probe.K = E; probe.ldw = E; probe.ldx = E;
-    const bool fused = sizeof(TW) == 2 && d->stats && rnd && skinny_mfma_ok(probe) && (F % 256 == 0) && F <= SKM_MAXK;
-    bool hid_bf16 = false, hid_in_bf16 = false;
-    auto skinny_ln = [&](const float *x, int ldx, const void *W, const float *bias, float *y, int ldy, int N, int K, int flags,
-                         const AcaiDecLayer *kvl, const float *lnw, const float *lnb, float *stats_out, const float *res,
-                         const float *rlnw, const float *rlnb, const float *rstats) -> int {
-        SkinnyArgs s{};
-        s.x = x; s.W = W; s.bias = bias; s.residual = res; s.y = y;
-        s.ldx = ldx; s.ldw = K; s.ldr = E; s.ldy = ldy; s.B = B; s.N = N; s.K = K; s.flags = flags;
-        s.ln_w = lnw; s.ln_b = lnb; s.ln_eps = 1e-5f; s.stats_out = stats_out; s.rln_w = rlnw; s.rln_b = rlnb; s.rstats = rstats;
-        s.y_bf16 = hid_bf16 && (flags & ACAI_GEMM_ROUND_BF16);
-        s.x_bf16 = hid_in_bf16 && (flags & ACAI_GEMM_ROUND_BF16);
-        if (kvl) {
-            s.k_cache = kvl->k_self; s.v_cache = kvl->v_self; s.step = d->step;
-            s.E = E; s.H = H; s.dh = d->dh; s.dhp = d->dhp; s.Tmax = d->Tmax;
-        }
-        return launch_skinny<TW>(s, st);
-    };
     if (fused) {
         float *st0 = d->stats, *st1 = d->stats + 2 * B, *st2 = d->stats + 4 * B;
         float *zin = d->x, *z1 = d->proj, *z2 = d->xn;
         const float *lnw = nullptr, *lnb = nullptr;  // LayerNorm still to be applied to zin (norm3 of the previous layer)
         for (int l = 0; l < d->L; ++l) {
             const AcaiDecLayer *ly = d->layers + l;
-            if ((rc = skinny_ln(zin, E, ly->self_in_w, ly->self_in_b, d->qkv, 3 * E, 3 * E, E, rnd, ly, lnw, lnb, st0, nullptr, nullptr, nullptr, nullptr))) return rc;
+            if ((rc = skinny(zin, E, ly->self_in_w, ly->self_in_b, nullptr, d->qkv, 3 * E, 3 * E, E, rnd, ly, lnw, lnb, st0))) return rc;
             if ((rc = attend(d->qkv, 3 * E, ly->k_self, ly->v_self, false))) return rc;
-            if ((rc = skinny_ln(d->attn, E, ly->self_out_w, ly->self_out_b, z1, E, E, E, rnd, nullptr, nullptr, nullptr, nullptr, zin, lnw, lnb, st0))) return rc;
-            if ((rc = skinny_ln(z1, E, ly->cross_q_w, ly->cross_q_b, d->qkv, 3 * E, E, E, rnd, nullptr, ly->n1_w, ly->n1_b, st1, nullptr, nullptr, nullptr, nullptr))) return rc;
+            if ((rc = skinny(d->attn, E, ly->self_out_w, ly->self_out_b, zin, z1, E, E, E, rnd, nullptr, nullptr, nullptr, nullptr, lnw, lnb, st0))) return rc;
+            if ((rc = skinny(z1, E, ly->cross_q_w, ly->cross_q_b, nullptr, d->qkv, 3 * E, E, E, rnd, nullptr, ly->n1_w, ly->n1_b, st1))) return rc;
             if ((rc = attend(d->qkv, 3 * E, ly->k_cross, ly->v_cross, true))) return rc;
-            if ((rc = skinny_ln(d->attn, E, ly->cross_out_w, ly->cross_out_b, z2, E, E, E, rnd, nullptr, nullptr, nullptr, nullptr, z1, ly->n1_w, ly->n1_b, st1))) return rc;
+            if ((rc = skinny(d->attn, E, ly->cross_out_w, ly->cross_out_b, z1, z2, E, E, E, rnd, nullptr, nullptr, nullptr, nullptr, ly->n1_w, ly->n1_b, st1))) return rc;
             hid_bf16 = true;   // linear1 -> GELU output is bf16 under autocast anyway: store it as such (half the x bytes of linear2)
-            if ((rc = skinny_ln(z2, E, ly->lin1_w, ly->lin1_b, d->hid, F, F, E, rnd | ACAI_GEMM_GELU, nullptr, ly->n2_w, ly->n2_b, st2, nullptr, nullptr, nullptr, nullptr))) return rc;
+            if ((rc = skinny(z2, E, ly->lin1_w, ly->lin1_b, nullptr, d->hid, F, F, E, rnd | ACAI_GEMM_GELU, nullptr, ly->n2_w, ly->n2_b, st2))) return rc;
             hid_bf16 = false;
             hid_in_bf16 = true;
-            if ((rc = skinny_ln(d->hid, F, ly->lin2_w, ly->lin2_b, zin, E, E, F, rnd, nullptr, nullptr, nullptr, nullptr, z2, ly->n2_w, ly->n2_b, st2))) return rc;
+            if ((rc = skinny(d->hid, F, ly->lin2_w, ly->lin2_b, z2, zin, E, E, F, rnd, nullptr, nullptr, nullptr, nullptr, ly->n2_w, ly->n2_b, st2))) return rc;
             hid_in_bf16 = false;
             lnw = ly->n3_w;
             lnb = ly->n3_b;
@@ -1852,22 +1850,9 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
         // x = norm3(z3) of the last layer, then the stack's final norm (eps 1e-6): both fused into the unembed GEMV's load when the chain
         // kernel takes it (E = 1024) - no stand-alone LayerNorm launch is left in a token step
         static const bool no_chain2 = getenv("ACAI_SKINNY_CHAIN") && atoi(getenv("ACAI_SKINNY_CHAIN")) == 0;
-        if (do_unembed && d->fn_w && E == 1024 && !no_chain2 && lnw) {
-            SkinnyArgs s{};
-            s.x = zin; s.W = d->unembed_w; s.bias = d->unembed_b; s.y = d->logits;
-            s.ldx = E; s.ldw = E; s.ldy = d->V; s.B = B; s.N = d->V; s.K = E; s.flags = rnd;
-            s.ln_w = lnw; s.ln_b = lnb; s.ln_eps = 1e-5f;
-            s.ln2_w = d->fn_w; s.ln2_b = d->fn_b; s.ln2_eps = 1e-6f;
-            return launch_skinny<TW>(s, st);
-        }
+        if (do_unembed && d->fn_w && E == 1024 && !no_chain2 && lnw) return unembed(zin, lnw, lnb, 1e-5f, d->fn_w, d->fn_b);
         if ((rc = acai_layernorm_fwd(zin, lnw, lnb, 1e-5f, d->proj, nullptr, B, E, st))) return rc;
-        if (do_unembed && d->fn_w) {
-            SkinnyArgs s{};
-            s.x = d->proj; s.W = d->unembed_w; s.bias = d->unembed_b; s.y = d->logits;
-            s.ldx = E; s.ldw = E; s.ldy = d->V; s.B = B; s.N = d->V; s.K = E; s.flags = rnd;
-            s.ln_w = d->fn_w; s.ln_b = d->fn_b; s.ln_eps = 1e-6f;
-            return launch_skinny<TW>(s, st);
-        }
+        if (do_unembed && d->fn_w) return unembed(d->proj, d->fn_w, d->fn_b, 1e-6f, nullptr, nullptr);
         if (d->fn_w) {
             if ((rc = acai_layernorm_fwd(d->proj, d->fn_w, d->fn_b, 1e-6f, d->xn, nullptr, B, E, st))) return rc;
         } else {
@@ -1899,13 +1884,14 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
         if (e != hipSuccess) return acai_set_err((int)e, "hipMemcpyAsync: %s", hipGetErrorString(e));
     }
     }
-    if (do_unembed) {
-        SkinnyArgs s{};
-        s.x = d->xn; s.W = d->unembed_w; s.bias = d->unembed_b; s.y = d->logits;
-        s.ldx = E; s.ldw = E; s.ldy = d->V; s.B = B; s.N = d->V; s.K = E; s.flags = rnd;
-        if ((rc = launch_skinny<TW>(s, st))) return rc;
-    }
-    return 0;
+    return do_unembed ? unembed(d->xn, nullptr, nullptr, 1e-5f, nullptr, nullptr) : 0;
+}
+
+// decode_core in the descriptor's weight dtype
+int decode(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, bool do_embed = true, bool do_unembed = true,
+           const AcaiBeam *beam = nullptr, const AcaiSlots *slots = nullptr) {
+    return d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, tokens, st, do_embed, do_unembed, beam, slots)
+                                 : decode_core<float>(d, tokens, st, do_embed, do_unembed, beam, slots);
 }
 
 }  // namespace
@@ -1984,7 +1970,7 @@ extern "C" int acai_decode_hidden(const AcaiDecoder *d, const float *x_in, void 
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemcpyAsync(d->x, x_in, sizeof(float) * (size_t)d->B * d->E, hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return acai_set_err((int)e, "hipMemcpyAsync: %s", hipGetErrorString(e));
-    rc = d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, nullptr, st, false, false) : decode_core<float>(d, nullptr, st, false, false);
+    rc = decode(d, nullptr, st, false, false);
     if (rc) return rc;
     hipLaunchKernelGGL(advance_cache_kernel, dim3(1), dim3(1), 0, st, d->step);
     ACAI_LAUNCH_CHECK("advance_cache");
@@ -2005,17 +1991,32 @@ extern "C" int acai_decode_embed(const AcaiDecoder *d, void *stream) {
     return 0;
 }
 
-extern "C" int acai_decode_step(const AcaiDecoder *d, void *stream) {
+// The descriptor and the embedding / unembed operands of every entry point that produces logits.
+static int check_unembed(const AcaiDecoder *d, const char *fn) {
     int rc = check_decoder(d);
     if (rc) return rc;
-    ACAI_CHECK_ARG(d->emb && d->pos && d->unembed_w && d->logits, "acai_decode_step: decoder has no embedding / unembed");
-    ACAI_CHECK_ARG(d->seqs && d->logprobs && d->finished && d->max_len > 1, "acai_decode_step: null sequence state");
-    hipStream_t st = (hipStream_t)stream;
+    ACAI_CHECK_ARG(d->emb && d->pos && d->unembed_w && d->logits, "%s: decoder has no embedding / unembed", fn);
+    return 0;
+}
+
+// Prologue of the chained greedy / sampling / beam steps: the operands, the sequence state and, for a chained step, that x holds this
+// step's input (written by the previous step's argmax / sampling / beam-select kernel, or by acai_decode_embed after arming).
+static int check_step(const AcaiDecoder *d, const char *fn, bool chained) {
+    int rc = check_unembed(d, fn);
+    if (rc) return rc;
+    ACAI_CHECK_ARG(d->seqs && d->logprobs && d->finished && d->max_len > 1, "%s: null sequence state", fn);
+    ACAI_CHECK_ARG(!chained || x_valid_get(d), "%s: x does not hold this step's input embedding - call acai_decode_embed after arming the "
+                                               "sequence state and after every acai_decode_logits / acai_decode_hidden", fn);
+    return 0;
+}
+
+extern "C" int acai_decode_step(const AcaiDecoder *d, void *stream) {
     // the step's input x was written by the previous step's argmax (or by acai_decode_embed after arming) when E allows 16-byte rows
-    const bool chained = (d->E % 4 == 0);
-    ACAI_CHECK_ARG(!chained || x_valid_get(d), "acai_decode_step: x does not hold this step's input embedding - call acai_decode_embed after arming the "
-                                               "sequence state and after every acai_decode_logits / acai_decode_hidden");
-    rc = d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, nullptr, st, !chained) : decode_core<float>(d, nullptr, st, !chained);
+    const bool chained = d && d->E % 4 == 0;
+    int rc = check_step(d, "acai_decode_step", chained);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, !chained);
     if (rc) return rc;
     hipLaunchKernelGGL(argmax_logprob_kernel, dim3(1), dim3(d->B > 8 ? 1024 : (d->B > 4 ? 512 : 256)), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
                        d->finished, d->eos, (d->flags & ACAI_GEMM_ROUND_BF16) ? 1 : 0, 1, chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax);
@@ -2024,17 +2025,13 @@ extern "C" int acai_decode_step(const AcaiDecoder *d, void *stream) {
 }
 
 extern "C" int acai_decode_sample_step(const AcaiDecoder *d, const float *uniforms, int top_k, float temperature, void *stream) {
-    int rc = check_decoder(d);
+    const bool chained = d && d->E % 4 == 0;
+    int rc = check_step(d, "acai_decode_sample_step", chained);
     if (rc) return rc;
-    ACAI_CHECK_ARG(d->emb && d->pos && d->unembed_w && d->logits, "acai_decode_sample_step: decoder has no embedding / unembed");
-    ACAI_CHECK_ARG(d->seqs && d->logprobs && d->finished && d->max_len > 1, "acai_decode_sample_step: null sequence state");
     ACAI_CHECK_ARG(uniforms && top_k >= 1 && top_k <= 64 && temperature > 0.f && d->V <= 512,
                    "acai_decode_sample_step: needs uniforms, 1 <= top_k <= 64, temperature > 0, vocabulary <= 512 (top_k=%d V=%d)", top_k, d->V);
     hipStream_t st = (hipStream_t)stream;
-    const bool chained = (d->E % 4 == 0);
-    ACAI_CHECK_ARG(!chained || x_valid_get(d), "acai_decode_sample_step: x does not hold this step's input embedding - call acai_decode_embed after arming "
-                                               "the sequence state and after every acai_decode_logits / acai_decode_hidden");
-    rc = d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, nullptr, st, !chained) : decode_core<float>(d, nullptr, st, !chained);
+    rc = decode(d, nullptr, st, !chained);
     if (rc) return rc;
     hipLaunchKernelGGL(sample_logprob_kernel, dim3(cdiv(d->B, 4)), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
                        d->finished, d->eos, (d->flags & ACAI_GEMM_ROUND_BF16) ? 1 : 0, uniforms, top_k, 1.0f / temperature,
@@ -2045,19 +2042,15 @@ extern "C" int acai_decode_sample_step(const AcaiDecoder *d, const float *unifor
 }
 
 extern "C" int acai_decode_beam_step(const AcaiDecoder *d, const AcaiBeam *bs, void *stream) {
-    int rc = check_decoder(d);
+    int rc = check_step(d, "acai_decode_beam_step", true);
     if (rc) return rc;
-    ACAI_CHECK_ARG(d->emb && d->pos && d->unembed_w && d->logits, "acai_decode_beam_step: decoder has no embedding / unembed");
-    ACAI_CHECK_ARG(d->seqs && d->logprobs && d->finished && d->max_len > 1, "acai_decode_beam_step: null sequence state");
     ACAI_CHECK_ARG(bs && bs->anc && bs->tok && bs->lp && bs->cum && bs->len, "acai_decode_beam_step: null beam state");
     ACAI_CHECK_ARG(bs->K >= 1 && bs->K <= BEAM_MAX && d->B % bs->K == 0 && bs->rows >= d->B && bs->pitch >= d->max_len && d->V <= 512 &&
                        d->E % 4 == 0 && d->self_chunk <= 16384,
                    "acai_decode_beam_step: needs 1 <= K <= 16 dividing B, rows >= B, pitch >= max_len, vocabulary <= 512, E %% 4 == 0, "
                    "self_chunk <= 16384 (K=%d B=%d rows=%d pitch=%d V=%d E=%d)", bs->K, d->B, bs->rows, bs->pitch, d->V, d->E);
-    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_beam_step: x does not hold this step's input embedding - call acai_decode_embed after arming "
-                                   "the sequence state and after every acai_decode_logits / acai_decode_hidden");
     hipStream_t st = (hipStream_t)stream;
-    rc = d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, nullptr, st, false, true, bs) : decode_core<float>(d, nullptr, st, false, true, bs);
+    rc = decode(d, nullptr, st, false, true, bs);
     if (rc) return rc;
     BeamArgs a{};
     a.logits = d->logits; a.V = d->V; a.K = bs->K; a.E = d->E; a.Tmax = d->Tmax; a.pitch = bs->pitch; a.eos = d->eos; a.pad = d->pad;
@@ -2072,9 +2065,8 @@ extern "C" int acai_decode_beam_step(const AcaiDecoder *d, const AcaiBeam *bs, v
 }
 
 static int check_slots(const AcaiDecoder *d, const AcaiSlots *sl, const char *fn) {
-    int rc = check_decoder(d);
+    int rc = check_unembed(d, fn);
     if (rc) return rc;
-    ACAI_CHECK_ARG(d->emb && d->pos && d->unembed_w && d->logits, "%s: decoder has no embedding / unembed", fn);
     ACAI_CHECK_ARG(d->seqs && d->logprobs && d->finished && d->max_len > 1 && d->max_len <= d->Tmax, "%s: null sequence state or max_len "
                    "outside [2, Tmax] (max_len=%d Tmax=%d)", fn, d->max_len, d->Tmax);
     ACAI_CHECK_ARG(sl && sl->t && sl->first && sl->cap && sl->rows >= d->B, "%s: null slot state or rows < B", fn);
@@ -2103,8 +2095,7 @@ extern "C" int acai_decode_slot_step(const AcaiDecoder *d, const AcaiSlots *sl, 
     ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_slot_step: x does not hold this step's input embedding - call acai_decode_slot_arm after "
                                    "setting up the slot state and after every acai_decode_logits / acai_decode_hidden");
     hipStream_t st = (hipStream_t)stream;
-    rc = d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, nullptr, st, false, true, nullptr, sl)
-                               : decode_core<float>(d, nullptr, st, false, true, nullptr, sl);
+    rc = decode(d, nullptr, st, false, true, nullptr, sl);
     if (rc) return rc;
     hipLaunchKernelGGL(slot_argmax_kernel, dim3(1), dim3(d->B > 8 ? 1024 : (d->B > 4 ? 512 : 256)), 0, st, d->logits, d->V, d->B, d->seqs,
                        d->logprobs, d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos,
@@ -2114,13 +2105,12 @@ extern "C" int acai_decode_slot_step(const AcaiDecoder *d, const AcaiSlots *sl, 
 }
 
 extern "C" int acai_decode_logits(const AcaiDecoder *d, const int64_t *tokens, int time_step, void *stream) {
-    int rc = check_decoder(d);
+    int rc = check_unembed(d, "acai_decode_logits");
     if (rc) return rc;
-    ACAI_CHECK_ARG(d->emb && d->pos && d->unembed_w && d->logits, "acai_decode_logits: decoder has no embedding / unembed");
     ACAI_CHECK_ARG(tokens && time_step >= 0 && time_step < d->Tmax, "acai_decode_logits: bad tokens / time_step %d", time_step);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(set_step_kernel, dim3(1), dim3(1), 0, st, d->step, time_step);
-    rc = d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, tokens, st) : decode_core<float>(d, tokens, st);
+    rc = decode(d, tokens, st);
     if (rc) return rc;
     hipLaunchKernelGGL(advance_cache_kernel, dim3(1), dim3(1), 0, st, d->step);
     ACAI_LAUNCH_CHECK("advance_cache");

@@ -10,6 +10,7 @@ their forward is never called).  This file turns those parameters into kernel la
 Precision ("fp32" | "bf16") follows the reference plumbing: fp32 = outside autocast; bf16 = what
 torch.autocast(bfloat16) does to linear / SDPA (bf16 operands and outputs, fp32 accumulate, fp32 residual + LayerNorm).
 """
+import contextlib
 import ctypes
 import os
 
@@ -259,12 +260,12 @@ class DecodeEngine:
         self.B = 0
         self.lens = None
         self.group = 1          # decode rows per stored cross K/V (GRPO rollout groups)
-        self._sampler = None    # (top_k, temperature) while a sampling rollout runs, else greedy
+        # what a decode step does: ("greedy",), ("sample", top_k, temperature), ("beam", K) or ("slot",) (continuous batching); a run sets
+        # it and restores greedy when it ends
+        self._mode = ("greedy",)
         self.uniforms = None    # (Bmax, Tmax) uniforms of the sampling step, allocated on first use
-        self._beam = None       # beam width K while a beam search runs
         self.beam_anc = None    # beam-search lineage [2][Bmax][Tmax] (anc / tok / lp) and per-row cum / len, allocated on first use
         self._beam_done = 0
-        self._slot_mode = False  # True while a continuous-batching run steps the engine (acai_decode_slot_step)
         self.slot_t = None      # slot state [Bmax] x 3 (local time, ring start, cap), allocated on first use
         self.slot_steps = 0     # decode steps of the last continuous-batching run (the ring index wrapped slot_steps // Tmax times)
         self.cache_len = 0
@@ -278,16 +279,11 @@ class DecodeEngine:
         offsets alias it, instead of the reference's group_size materialised copies."""
         G = int(group_size)
         B = len(lens) * G
-        self._slot_mode = False
+        self._mode = ("greedy",)
         if B > self.Bmax:
             raise ValueError(f"The current cache has been setup with a max batch size of {self.Bmax}, but found new key tensors with batch size {B}!")
         E, H, dhp, dev = self.E, self.H, self.dhp, self.device
-        total = sum(lens) * H * dhp
-        if total > self.cross_cap:
-            self.cross_cap = total
-            self.k_cross = [torch.zeros(total, dtype=self.cdt, device=dev) for _ in range(self.L)]
-            self.v_cross = [torch.zeros(total, dtype=self.cdt, device=dev) for _ in range(self.L)]
-            self.graphs.clear()  # pointers changed
+        self._size_cross(sum(lens) * H * dhp, B, lens, G)
         offs, o = [], 0
         for l in lens:
             offs.append(o)
@@ -308,14 +304,24 @@ class DecodeEngine:
             ops.cross_kv_prefill(mem, w, b, row_seq, row_pos, pre_off, pre_len, self.k_cross[i], self.v_cross[i],
                                  H, self.dh, dhp, round_bf16=self.bf)
         self.B, self.lens, self.group = B, [l for l in lens for _ in range(G)], G
-        self.cross_chunk = self.pick_cross_chunk(lens, H) if G == 1 else self.CROSS_CHUNK
-        self.cross_nsplit = max(1, -(-max(lens) // self.cross_chunk))
-        need = B * H * max(self.cross_nsplit, self.self_nsplit) * (dhp + 2)
-        if self.partial is None or self.partial.numel() < need:
-            self.partial = torch.empty(self.Bmax * H * max(self.cross_nsplit, self.self_nsplit) * (dhp + 2), dtype=torch.float32, device=dev)
-            self.graphs.clear()
         self.reset_self_cache()
         self._build_desc()
+
+    def _size_cross(self, total, B, lens, group=1):
+        """Cross K/V buffers of at least `total` elements per layer, the cross split (keys per workgroup, splits) of memories of lengths
+        `lens` shared by `group` rows each, and `partial` for B rows at that split.  A reallocation drops the captured graphs."""
+        H, dhp, dev = self.H, self.dhp, self.device
+        if total > self.cross_cap:
+            self.cross_cap = total
+            self.k_cross = [torch.zeros(total, dtype=self.cdt, device=dev) for _ in range(self.L)]
+            self.v_cross = [torch.zeros(total, dtype=self.cdt, device=dev) for _ in range(self.L)]
+            self.graphs.clear()  # pointers changed
+        self.cross_chunk = self.pick_cross_chunk(lens, H) if group == 1 else self.CROSS_CHUNK
+        self.cross_nsplit = max(1, -(-max(lens) // self.cross_chunk))
+        nsplit = max(self.cross_nsplit, self.self_nsplit)
+        if self.partial is None or self.partial.numel() < B * H * nsplit * (dhp + 2):
+            self.partial = torch.empty(self.Bmax * H * nsplit * (dhp + 2), dtype=torch.float32, device=dev)
+            self.graphs.clear()
 
     def reset_self_cache(self):
         """KVCache.reset (kv_caching.py:47-51): position back to 0 (stale entries are never read: length is step[1]+1)."""
@@ -349,7 +355,7 @@ class DecodeEngine:
         d.flags = _lib.GEMM_ROUND_BF16 if self.bf else 0
         d.max_len = self.Tmax
         d.cross_group = self.group
-        d.self_chunk, d.cross_chunk, d.self_nsplit, d.cross_nsplit = self.SELF_CHUNK, getattr(self, "cross_chunk", self.CROSS_CHUNK), self.self_nsplit, self.cross_nsplit
+        d.self_chunk, d.cross_chunk, d.self_nsplit, d.cross_nsplit = self.SELF_CHUNK, self.cross_chunk, self.self_nsplit, self.cross_nsplit
         d.layers = ctypes.cast(layers, ctypes.POINTER(_lib.AcaiDecLayer))
         top = {}
         if nrm is not None:
@@ -397,43 +403,42 @@ class DecodeEngine:
         self.cache_len += 1
         return self.ws["logits"][:self.B]
 
-    # ---- ViTOMR.cached_greedy_generate (models.py:600-615) ----------------------------------------------------------
-    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None):
-        """Runs up to max_len-1 greedy steps; returns views seqs (B,max_len) int64 and logprobs (B,max_len) fp32.
-        Early exit when every row has produced <eos> (checked every `poll` steps; overshoot is masked later)."""
-        B, own = self.B, self.omr
+    @contextlib.contextmanager
+    def _run(self, max_len, mode):
+        """Frame of a greedy / sampling / beam run of up to max_len-1 steps: the body runs on self.stream in `mode`; the caller's stream
+        waits for it.  The mode goes back to greedy however the body ends."""
         if max_len > self.Tmax:
             raise RuntimeError(f"{max_len} decoding steps is too long for max sequence length of {self.Tmax}")
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            out = self._greedy_on_stream(max_len, poll, use_graph, on_chunk)
+        self._mode = mode
+        try:
+            with torch.cuda.stream(self.stream):
+                yield
+        finally:
+            self._mode = ("greedy",)
         cur.wait_stream(self.stream)
-        return out
+
+    # ---- ViTOMR.cached_greedy_generate (models.py:600-615) ----------------------------------------------------------
+    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None):
+        """Runs up to max_len-1 greedy steps; returns views seqs (B,max_len) int64 and logprobs (B,max_len) fp32.
+        Early exit when every row has produced <eos> (checked every `poll` steps; overshoot is masked later)."""
+        with self._run(max_len, ("greedy",)):
+            return self._decode_loop(max_len, poll, use_graph, on_chunk)
 
     # ---- GRPOViTOMR.cached_forward_rollout_policy (models.py:988-1049) ---------------------------------------------------------
     def sample(self, max_actions, top_k, temperature, uniforms=None, poll=16, use_graph=True):
         """Up to max_actions-1 sampling steps (top-k, temperature, inverse-CDF draw from `uniforms` (B, max_actions) in [0,1) - drawn from
         torch's generator when None).  Returns views seqs (B, max_actions), logprobs (B, max_actions) and the number of steps run."""
-        if max_actions > self.Tmax:
-            raise RuntimeError(f"{max_actions} decoding steps is too long for max sequence length of {self.Tmax}")
-        B = self.B
-        if self.uniforms is None:
-            self.uniforms = torch.zeros(self.Bmax, self.Tmax, dtype=torch.float32, device=self.device)
-        if uniforms is None:
-            uniforms = torch.rand(B, max_actions, device=self.device)
-        assert uniforms.shape == (B, max_actions)
-        self.uniforms[:B, :max_actions] = uniforms.to(device=self.device, dtype=torch.float32)
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        self._sampler = (int(top_k), float(temperature))
-        try:
-            with torch.cuda.stream(self.stream):
-                out = self._greedy_on_stream(max_actions, poll, use_graph, None)
-        finally:
-            self._sampler = None
-        cur.wait_stream(self.stream)
-        return out
+        with self._run(max_actions, ("sample", int(top_k), float(temperature))):
+            B = self.B
+            if self.uniforms is None:
+                self.uniforms = torch.zeros(self.Bmax, self.Tmax, dtype=torch.float32, device=self.device)
+            if uniforms is None:
+                uniforms = torch.rand(B, max_actions, device=self.device)
+            assert uniforms.shape == (B, max_actions)
+            self.uniforms[:B, :max_actions] = uniforms.to(device=self.device, dtype=torch.float32)
+            return self._decode_loop(max_actions, poll, use_graph)
 
     def greedy_chunks(self, max_len, chunk):
         """Generator over the greedy loop in chunks of `chunk` tokens (streamed inference): yields (tokens_done, all_finished)
@@ -443,9 +448,7 @@ class DecodeEngine:
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            self.arm(self.B)
-            self.ensure_graph(1)
-            self.arm(self.B)
+            self._arm_and_capture(self.B)
         done, total = 0, max_len - 1
         while done < total:
             n = min(chunk, total - done)
@@ -465,44 +468,31 @@ class DecodeEngine:
         max_len-1 steps of acai_decode_beam_step, then per image the slot with the highest cum / len^length_penalty (ties: lower slot).
         Returns seqs (B/K, max_len) int64 and log_probs (B/K, max_len) fp32 of the chosen hypotheses and their cumulative log-probs cum (B/K,)."""
         K = int(beam_width)
-        if max_len > self.Tmax:
-            raise RuntimeError(f"{max_len} decoding steps is too long for max sequence length of {self.Tmax}")
-        if not 1 <= K <= 16:
-            raise ValueError(f"beam_width must be in [1, 16], got {K}")
-        if self.group != K or self.B % K:
-            raise ValueError(f"beam width {K} needs the memories prepared with group_size={K} (prepared: {self.group})")
-        if self.beam_anc is None:
-            z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.device)  # noqa: E731
-            self.beam_anc = z(2, self.Bmax, self.Tmax, dt=torch.int32)
-            self.beam_tok = z(2, self.Bmax, self.Tmax, dt=torch.int64)
-            self.beam_lp = z(2, self.Bmax, self.Tmax, dt=torch.float32)
-            self.beam_cum = z(self.Bmax, dt=torch.float32)
-            self.beam_len = z(self.Bmax, dt=torch.int32)
-            d = _lib.AcaiBeam()
-            d.pitch, d.rows = self.Tmax, self.Bmax
-            d.anc, d.tok, d.lp = self.beam_anc.data_ptr(), self.beam_tok.data_ptr(), self.beam_lp.data_ptr()
-            d.cum, d.len = self.beam_cum.data_ptr(), self.beam_len.data_ptr()
-            self._beam_desc = d
-        self._beam_desc.K = K
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        self._beam = K
-        try:
-            with torch.cuda.stream(self.stream):
-                _, _, done = self._greedy_on_stream(max_len, poll, use_graph, None)
-                self._beam_done = done
-                seqs, lps, cum, _ = self.beam_slots(max_len)
-                n = self.B // K
-                ln = self.beam_len[:self.B].view(n, K)
-                ln = torch.where(ln == 0, torch.full_like(ln, max_len - 1), ln).to(torch.float32)
-                c = cum.view(n, K)
-                score = torch.where(c == float("-inf"), c, c / ln.pow(float(length_penalty)))
-                rows = torch.arange(n, device=self.device) * K + torch.argmax(score, dim=1)   # first maximum: the lower slot on ties
-                out = seqs.index_select(0, rows), lps.index_select(0, rows), cum.index_select(0, rows)
-        finally:
-            self._beam = None
-        cur.wait_stream(self.stream)
-        return out
+        with self._run(max_len, ("beam", K)):
+            if self.group != K or self.B % K:
+                raise ValueError(f"beam width {K} needs the memories prepared with group_size={K} (prepared: {self.group})")
+            if self.beam_anc is None:
+                z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.device)  # noqa: E731
+                self.beam_anc = z(2, self.Bmax, self.Tmax, dt=torch.int32)
+                self.beam_tok = z(2, self.Bmax, self.Tmax, dt=torch.int64)
+                self.beam_lp = z(2, self.Bmax, self.Tmax, dt=torch.float32)
+                self.beam_cum = z(self.Bmax, dt=torch.float32)
+                self.beam_len = z(self.Bmax, dt=torch.int32)
+                d = _lib.AcaiBeam()
+                d.pitch, d.rows = self.Tmax, self.Bmax
+                d.anc, d.tok, d.lp = self.beam_anc.data_ptr(), self.beam_tok.data_ptr(), self.beam_lp.data_ptr()
+                d.cum, d.len = self.beam_cum.data_ptr(), self.beam_len.data_ptr()
+                self._beam_desc = d
+            self._beam_desc.K = K
+            _, _, self._beam_done = self._decode_loop(max_len, poll, use_graph)
+            seqs, lps, cum, _ = self.beam_slots(max_len)
+            n = self.B // K
+            ln = self.beam_len[:self.B].view(n, K)
+            ln = torch.where(ln == 0, torch.full_like(ln, max_len - 1), ln).to(torch.float32)
+            c = cum.view(n, K)
+            score = torch.where(c == float("-inf"), c, c / ln.pow(float(length_penalty)))
+            rows = torch.arange(n, device=self.device) * K + torch.argmax(score, dim=1)   # first maximum: the lower slot on ties
+            return seqs.index_select(0, rows), lps.index_select(0, rows), cum.index_select(0, rows)
 
     def beam_slots(self, max_len):
         """Every slot of the last beam search as it ended: tokens (B, max_len), per-token log-probs, cum (B,) and len (B,) (0 = unfinished).
@@ -511,7 +501,7 @@ class DecodeEngine:
         return self.beam_tok[par, :B, :max_len], self.beam_lp[par, :B, :max_len], self.beam_cum[:B], self.beam_len[:B]
 
     def _arm_beam(self, B):
-        K, own = self._beam, self.omr
+        K, own = self._mode[1], self.omr
         self.beam_anc[:, :B] = torch.arange(B, dtype=torch.int32, device=self.device).view(1, B, 1)   # every position: the row's own cache row
         self.beam_tok[:, :B].fill_(own.pad_idx)
         self.beam_tok[:, :B, 0] = own.bos_idx
@@ -522,7 +512,7 @@ class DecodeEngine:
         self.beam_len[:B].zero_()
 
     def arm(self, B):
-        if self._slot_mode:
+        if self._mode[0] == "slot":
             self._slot_reset()
             return
         own = self.omr
@@ -532,7 +522,7 @@ class DecodeEngine:
         self.finished.zero_()
         self.reset_self_cache()
         self.step.copy_(torch.tensor([1, 0], dtype=torch.int32))
-        if self._beam is not None:
+        if self._mode[0] == "beam":
             self._arm_beam(B)
         # input of the first step (<bos> at position 1, quirk Q1); each step's argmax / sampling kernel writes the next step's input
         _lib.check(_lib.lib().acai_decode_embed(ctypes.byref(self._desc), ops._st()), "acai_decode_embed")
@@ -541,24 +531,21 @@ class DecodeEngine:
     STEPS_PER_GRAPH = 8   # a graph replay costs ~10-15 us of launch latency: amortise it over several decode steps
 
     def _step(self, st):
-        """One decode step on the current stream: greedy, a sampling step (self._sampler = (top_k, temperature)) or a beam-search step
-        (self._beam = K)."""
-        smp = self._sampler
-        if self._slot_mode:
-            _lib.check(_lib.lib().acai_decode_slot_step(ctypes.byref(self._desc), ctypes.byref(self._slot_desc), st), "acai_decode_slot_step")
-        elif self._beam is not None:
-            _lib.check(_lib.lib().acai_decode_beam_step(ctypes.byref(self._desc), ctypes.byref(self._beam_desc), st), "acai_decode_beam_step")
-        elif smp is None:
-            _lib.check(_lib.lib().acai_decode_step(ctypes.byref(self._desc), st), "acai_decode_step")
+        """One decode step of the current mode on the current stream."""
+        mode, L, d = self._mode, _lib.lib(), ctypes.byref(self._desc)
+        if mode[0] == "greedy":
+            _lib.check(L.acai_decode_step(d, st), "acai_decode_step")
+        elif mode[0] == "sample":
+            _lib.check(L.acai_decode_sample_step(d, self.uniforms.data_ptr(), mode[1], mode[2], st), "acai_decode_sample_step")
+        elif mode[0] == "beam":
+            _lib.check(L.acai_decode_beam_step(d, ctypes.byref(self._beam_desc), st), "acai_decode_beam_step")
         else:
-            _lib.check(_lib.lib().acai_decode_sample_step(ctypes.byref(self._desc), self.uniforms.data_ptr(), int(smp[0]), float(smp[1]), st),
-                       "acai_decode_sample_step")
+            _lib.check(L.acai_decode_slot_step(d, ctypes.byref(self._slot_desc), st), "acai_decode_slot_step")
 
     def ensure_graph(self, nsteps=1):
         """hipGraph of `nsteps` consecutive decode steps for the current (B, cross split) configuration.  Must run on self.stream."""
         B = self.B
-        mode = ("slot",) if self._slot_mode else ("beam", self._beam) if self._beam is not None else self._sampler
-        key = (B, self.cross_nsplit, getattr(self, "cross_chunk", self.CROSS_CHUNK), nsteps, mode, self.group)
+        key = (B, self.cross_nsplit, self.cross_chunk, nsteps, self._mode, self.group)
         g = self.graphs.get(key)
         if g is None:
             st = ops._st()
@@ -598,13 +585,18 @@ class DecodeEngine:
             self.ensure_graph(1).launch()
             n -= 1
 
-    def _greedy_on_stream(self, max_len, poll, use_graph, on_chunk):
-        B = self.B
+    def _arm_and_capture(self, B, use_graph=True):
+        """Arm B rows; with graphs, capture (and warm up) the 1- and STEPS_PER_GRAPH-step graphs first, then re-arm: the warm-up launch
+        advances the device state."""
         self.arm(B)
-        if use_graph:   # capture (and warm up) before the loop, then re-arm: the warm-up launch advances the device state
+        if use_graph:
             self.ensure_graph(1)
             self.ensure_graph(self.STEPS_PER_GRAPH)
             self.arm(B)
+
+    def _decode_loop(self, max_len, poll, use_graph, on_chunk=None):
+        B = self.B
+        self._arm_and_capture(B, use_graph)
         done = 0
         total = max_len - 1
         while done < total:
@@ -622,17 +614,22 @@ class DecodeEngine:
     def continuous(self, mem32, memb, lens, caps, slots, poll=16, use_graph=True):
         """Greedy decode of len(lens) images through `slots` decode rows that are refilled as they finish.  mem32 / memb: the images'
         packed memories (M, E) fp32 / bf16 copy, lens their lengths, caps[i] image i's cap (its row ends after token index caps[i] - 1, or
-        at <eos>).  A generator: yields each image's index once its tokens and per-token log-probs are in `cont_seqs` / `cont_lps`
-        (N, max(caps)), in completion order.  Every image decodes exactly as it would alone in a greedy batch; only the step schedule is
-        shared.  Slot s owns a cross K/V region of max(lens) rows; an idle slot has cross length 1 and stays finished."""
-        N, S, dev, own = len(lens), int(slots), self.device, self.omr
+        at <eos>).  Checks the arguments at the call, then returns a generator that yields each image's index once its tokens and
+        per-token log-probs are in `cont_seqs` / `cont_lps` (N, max(caps)), in completion order.  Every image decodes exactly as it would
+        alone in a greedy batch; only the step schedule is shared.  Slot s owns a cross K/V region of max(lens) rows; an idle slot has
+        cross length 1 and stays finished."""
+        S = int(slots)
         caps = [int(c) for c in caps]
         if max(caps) > self.Tmax:
             raise RuntimeError(f"{max(caps)} decoding steps is too long for max sequence length of {self.Tmax}")
         if not 1 <= S <= self.Bmax:
             raise ValueError(f"slots must be in [1, {self.Bmax}] (the cache's max batch size), got {slots}")
-        if len(caps) != N:
-            raise ValueError(f"{len(caps)} caps for {N} images")
+        if len(caps) != len(lens):
+            raise ValueError(f"{len(caps)} caps for {len(lens)} images")
+        return self._continuous(mem32, memb, lens, caps, S, poll, use_graph)
+
+    def _continuous(self, mem32, memb, lens, caps, S, poll, use_graph):
+        N, dev, own = len(lens), self.device, self.omr
         mem = memb if self.bf else mem32
         if mem is None:
             mem = ops.cast_bf16(mem32)
@@ -646,18 +643,14 @@ class DecodeEngine:
             offs.append(offs[-1] + l)
         cur = torch.cuda.current_stream(dev)
         self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self._slot_setup(max(lens), S)
-            lens_dev = ops.h2d(torch.tensor(lens, dtype=torch.int32), dev)
-            self._slot_mode = True
-            self.arm(S)
-            if use_graph:   # capture (and warm up) before the loop, then reset: the warm-up launch advances the device state
-                self.ensure_graph(1)
-                self.ensure_graph(self.STEPS_PER_GRAPH)
-                self.arm(S)
         self.slot_steps = 0
         harvested = torch.cuda.Event()
         try:
+            with torch.cuda.stream(self.stream):
+                self._slot_setup(max(lens), S)
+                lens_dev = ops.h2d(torch.tensor(lens, dtype=torch.int32), dev)
+                self._mode = ("slot",)
+                self._arm_and_capture(S, use_graph)
             if sched.skipped:
                 harvested.record(self.stream)
                 cur.wait_event(harvested)
@@ -688,7 +681,7 @@ class DecodeEngine:
                     for _, i in freed:
                         yield i
         finally:
-            self._slot_mode = False
+            self._mode = ("greedy",)
             cur.wait_stream(self.stream)
 
     def _slot_setup(self, Scap, S):
@@ -696,21 +689,11 @@ class DecodeEngine:
         the captured graphs stay valid across refills), the slot state and the descriptors."""
         H, dhp, dev = self.H, self.dhp, self.device
         region = Scap * H * dhp
-        if S * region > self.cross_cap:
-            self.cross_cap = S * region
-            self.k_cross = [torch.zeros(S * region, dtype=self.cdt, device=dev) for _ in range(self.L)]
-            self.v_cross = [torch.zeros(S * region, dtype=self.cdt, device=dev) for _ in range(self.L)]
-            self.graphs.clear()
+        self._size_cross(S * region, S, [Scap] * S)
         self.slot_off = torch.arange(S, dtype=torch.int64, device=dev) * region
         self.cross_off[:S] = self.slot_off
         self.cross_len[:S].fill_(1)
         self.B, self.lens, self.group = S, [Scap] * S, 1
-        self.cross_chunk = self.pick_cross_chunk(self.lens, H)
-        self.cross_nsplit = max(1, -(-Scap // self.cross_chunk))
-        need = S * H * max(self.cross_nsplit, self.self_nsplit) * (dhp + 2)
-        if self.partial is None or self.partial.numel() < need:
-            self.partial = torch.empty(self.Bmax * H * max(self.cross_nsplit, self.self_nsplit) * (dhp + 2), dtype=torch.float32, device=dev)
-            self.graphs.clear()
         if self.slot_t is None:
             self.slot_t, self.slot_first, self.slot_cap = (torch.zeros(self.Bmax, dtype=torch.int32, device=dev) for _ in range(3))
             d = _lib.AcaiSlots()

@@ -431,18 +431,20 @@ class OMRDecoder(nn.Module):
         return self.forward(input_seqs, img_latent, None, latent_attention_mask)
 
     # ---- KV-cached path ------------------------------------------------------------------------------------------------
-    def prepare_caches(self, encoder_memory):
+    def _cached_blocks(self):
+        """decoder_blocks, which the KV-cached inference pathway needs to be a CachedTransformerDecoder."""
         if not isinstance(self.decoder_blocks, CachedTransformerDecoder):
             raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
-        self.decoder_blocks.prepare_caches(encoder_memory)
+        return self.decoder_blocks
+
+    def prepare_caches(self, encoder_memory):
+        self._cached_blocks().prepare_caches(encoder_memory)
 
     def cached_generate(self, token_t: torch.Tensor, time_step: int, latent_attention_mask=None):
         """Logits (B,1,V) for the token after `token_t` (B,1); pos_embedding is indexed with `time_step` literally."""
         if time_step >= self.max_lmx_seq_len:
             raise RuntimeError(f"{time_step + 1} decoding steps is too long for max sequence length of {self.max_lmx_seq_len}")
-        if not isinstance(self.decoder_blocks, CachedTransformerDecoder):
-            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
-        blocks = self.decoder_blocks
+        blocks = self._cached_blocks()
         blocks._materialise(latent_attention_mask)
         eng = blocks.engine(self.pos_embedding.device)
         logits = eng.logits_step(token_t, time_step)
@@ -527,9 +529,7 @@ class ViTOMR(nn.Module):
         return idx, lp
 
     def _greedy_packed(self, mem32, memb, lens, max_len, on_chunk=None):
-        blocks = self.decoder.decoder_blocks
-        if not isinstance(blocks, CachedTransformerDecoder):
-            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
+        blocks = self.decoder._cached_blocks()
         blocks.prepare_caches_packed(mem32, memb, lens)
         eng = blocks.engine(self.decoder.pos_embedding.device)
         seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk)
@@ -542,9 +542,7 @@ class ViTOMR(nn.Module):
         return self._greedy_packed(mem32, None, lens, max_len)
 
     def _beam_packed(self, mem32, memb, lens, beam_width, max_len, length_penalty):
-        blocks = self.decoder.decoder_blocks
-        if not isinstance(blocks, CachedTransformerDecoder):
-            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
+        blocks = self.decoder._cached_blocks()
         K = int(beam_width)
         if not 1 <= K <= 16:
             raise ValueError(f"beam_width must be in [1, 16], got {beam_width}")
@@ -562,26 +560,15 @@ class ViTOMR(nn.Module):
         beam_width best tokens, keeps the beam_width best by cumulative log-probability, and a hypothesis ends at <eos>.  The result per image
         is the hypothesis with the highest cum / len^length_penalty (len: tokens after <bos>, <eos> included).  beam_width = 1 is greedy,
         bit for bit.  The K hypotheses of an image share its cross K/V; a selection moves no self K/V, only an ancestor table."""
-        blocks = self.decoder.decoder_blocks
-        if not isinstance(blocks, CachedTransformerDecoder):
-            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
-        if not 1 <= int(beam_width) <= 16:
-            raise ValueError(f"beam_width must be in [1, 16], got {beam_width}")
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._beam_packed(mem32, None, lens, beam_width, max_len, length_penalty)
 
     def _continuous_run(self, mem32, memb, lens, max_len, slots, poll, use_graph):
         """(engine, caps, generator of finished image indices) of a continuous-batching run; argument errors are raised here, at the call."""
-        blocks = self.decoder.decoder_blocks
-        if not isinstance(blocks, CachedTransformerDecoder):
-            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
+        blocks = self.decoder._cached_blocks()
         caps = _continuous_caps(max_len, len(lens))
-        S = blocks.max_batch_size if slots is None else int(slots)
-        if not 1 <= S <= blocks.max_batch_size:
-            raise ValueError(f"slots must be in [1, {blocks.max_batch_size}] (the cache's max batch size), got {slots}")
         eng = blocks.engine((mem32 if mem32 is not None else memb).device)
-        if max(caps) > eng.Tmax:
-            raise RuntimeError(f"{max(caps)} decoding steps is too long for max sequence length of {eng.Tmax}")
+        S = blocks.max_batch_size if slots is None else slots
         return eng, caps, eng.continuous(mem32, memb, lens, caps, S, poll=poll, use_graph=use_graph)
 
     def _continuous_packed_iter(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True):
@@ -616,9 +603,6 @@ class ViTOMR(nn.Module):
         work through the N images in input order; a row that finishes (<eos> or its cap) is refilled with the next image while the others
         go on, so N may exceed the max batch size.  max_len: one cap for every image, or a sequence of N per-image caps (positions at or
         past an image's cap are masked)."""
-        blocks = self.decoder.decoder_blocks
-        if not isinstance(blocks, CachedTransformerDecoder):
-            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._continuous_packed(mem32, None, lens, max_len, slots)
 
@@ -627,9 +611,7 @@ class ViTOMR(nn.Module):
         if img_latent.shape[0] != 1:
             raise ValueError("Streamed generation only supports single image batches")
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
-        blocks = self.decoder.decoder_blocks
-        if not isinstance(blocks, CachedTransformerDecoder):
-            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
+        blocks = self.decoder._cached_blocks()
         blocks.prepare_caches_packed(mem32, None, lens)
         eng = blocks.engine(self.decoder.pos_embedding.device)
         # replay the decode graph flush_interval tokens at a time; after each chunk hand out the freshly written tokens
@@ -742,9 +724,7 @@ class GRPOViTOMR(ViTOMR):
         are inverse-CDF samples from `uniforms` (R, max_actions) in [0, 1), taken from torch's generator when None (so torch.manual_seed makes
         a rollout reproducible).  group_size (extension): img_latent rows r*group_size .. are the copies expand_img_latent_for_rollout made of
         one image; their cross K/V is then projected and stored once per image instead of once per rollout."""
-        blocks = self.decoder.decoder_blocks
-        if not isinstance(blocks, CachedTransformerDecoder):
-            raise RuntimeError("Trying to use cached inference pathway with an uncached TransformerDecoder instance")
+        blocks = self.decoder._cached_blocks()
         G = 1 if group_size is None else int(group_size)
         if img_latent.shape[0] % G:
             raise ValueError(f"{img_latent.shape[0]} rollout rows are not a multiple of group_size {G}")

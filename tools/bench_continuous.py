@@ -42,7 +42,7 @@ def step_time(eng, rows, slot, steps=64, repeats=5):
     cur = torch.cuda.current_stream()
     eng.stream.wait_stream(cur)
     with torch.cuda.stream(eng.stream):
-        eng._slot_mode = slot
+        eng._mode = ("slot",) if slot else ("greedy",)
         eng.arm(rows)
         eng.ensure_graph(eng.STEPS_PER_GRAPH)
         rl = torch.tensor([list(range(rows)), [eng.Tmax] * rows], dtype=torch.int32).to(eng.device)
@@ -59,7 +59,7 @@ def step_time(eng, rows, slot, steps=64, repeats=5):
             e1.synchronize()
             if r:
                 res.append(e0.elapsed_time(e1) / steps)
-        eng._slot_mode = False
+        eng._mode = ("greedy",)
     cur.wait_stream(eng.stream)
     return res
 
