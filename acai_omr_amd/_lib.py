@@ -13,15 +13,16 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
 SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "decode.hip", "resize.hip"]
 
-ACAI_F32, ACAI_BF16 = 0, 1
+ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
+DEC_CROSS_FP8 = 256   # AcaiDecoder.flags: e4m3fn cross K/V with per-row scales (AcaiDecLayer.k_cross_scale / v_cross_scale)
 
 
 class AcaiDecLayer(Structure):
     _fields_ = [(n, c_void_p) for n in (
         "self_in_w", "self_in_b", "self_out_w", "self_out_b", "cross_q_w", "cross_q_b", "cross_out_w", "cross_out_b",
         "lin1_w", "lin1_b", "lin2_w", "lin2_b", "n1_w", "n1_b", "n2_w", "n2_b", "n3_w", "n3_b",
-        "k_self", "v_self", "k_cross", "v_cross")]
+        "k_self", "v_self", "k_cross", "v_cross", "k_cross_scale", "v_cross_scale")]
 
 
 class AcaiAdamWTensor(Structure):
@@ -108,6 +109,9 @@ _SIGNATURES = {
                                     c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "acai_decode_attn": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "acai_decode_attn_fp8": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "acai_cross_kv_quantize_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "acai_decode_embed": (c_int, [POINTER(AcaiDecoder), c_void_p]),
     "acai_decode_step": (c_int, [POINTER(AcaiDecoder), c_void_p]),
     "acai_decode_sample_step": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_float, c_void_p]),

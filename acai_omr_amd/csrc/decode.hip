@@ -774,6 +774,13 @@ struct DAttnArgs {
     };
     int anc_pitch;
     long long anc_bstride;   // elements between the two parity copies (rows * anc_pitch)
+    // FP8 memory cache (fp8e4m3_t instantiation only): one fp32 power-of-two scale per K row and per V row, at the row's element offset / dhp
+    const float *k_scale, *v_scale;
+};
+
+// Element type of an FP8 (OCP e4m3fn) cross K/V cache: a stored value is q * 2^e, 2^e the row's scale (acai_cross_kv_quantize_fp8)
+struct fp8e4m3_t {
+    uint8_t bits;
 };
 
 // LPK = lanes per key = dhp * sizeof(TC) / 16.  RAGGED = cross attention over the ragged encoder memory (the dominant
@@ -782,10 +789,15 @@ struct DAttnArgs {
 // ancestor table - key p of row b from k_self[anc[b][p]][h][p][:] - staged in LDS (dynamic shared memory, chunk ints) before the key loop.
 // SLOT (self attention of a continuous-batching step, !RAGGED only): the cache is a ring of Tmax positions shared by the rows' write index
 // step[1]; row b has its own length seq_len[b] and its key j sits at position (slot_first[b] + j) % Tmax of its own cache row.
+// TC = fp8e4m3_t (RAGGED only): the FP8 memory cache.  16 elements per 16-byte load, so LPK = dhp / 16 (4 lanes per key at d_h 64); the
+// key's K and V scales are requested with its bytes and fold in outside the element loops: s = (q . k8) sk scale_log2e, acc += (p sv) v8,
+// l += p.
 template <typename TC, int LPK, bool RAGGED, int U = 2, bool ANC = false, bool SLOT = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
     static_assert(!(ANC && RAGGED), "the ancestor table indexes the self-attention cache");
     static_assert(!(SLOT && (RAGGED || ANC)), "the ring indexes the self-attention cache of the row itself");
+    constexpr bool F8 = sizeof(TC) == 1;
+    static_assert(!F8 || RAGGED, "FP8 storage is the cross K/V's only");
     constexpr int EPC = 16 / sizeof(TC), KPW = 64 / LPK;
     __shared__ float red[4][2 + 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -824,6 +836,12 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
     }
     const TC *Kp = reinterpret_cast<const TC *>(a.kc) + base;
     const TC *Vp = reinterpret_cast<const TC *>(a.vc) + base;
+    [[maybe_unused]] const float *Ks = nullptr, *Vs = nullptr;
+    if constexpr (F8) {   // the scale of key s sits at row (base / dhp) + s
+        const size_t row0 = base >> __builtin_ctz(a.dhp);
+        Ks = a.k_scale + row0;
+        Vs = a.v_scale + row0;
+    }
     [[maybe_unused]] int32_t *anc_s = nullptr;
     if constexpr (ANC) {
         extern __shared__ int32_t anc_dyn[];
@@ -855,32 +873,58 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
     // software pipeline: the U key groups of iteration i+1 are requested before iteration i is computed (a wave that computes has no load
     // in flight otherwise: PMC showed the VALU busy a third of the time and the waves waiting on memory for half of it)
     uint4 kn[U], vn[U];
+    [[maybe_unused]] float ksn[U], vsn[U];
     auto request = [&](int key0) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int key = key0 + u * 4 * KPW;
             kn[u] = vn[u] = make_uint4(0, 0, 0, 0);
+            if constexpr (F8) ksn[u] = vsn[u] = 0.f;
             if (key < c1) {
                 // every K/V byte is read exactly once per step: non-temporal loads (streaming cache policy)
                 kn[u] = ld_nt16(Kp + key_off(key) + kq * EPC);
                 vn[u] = ld_nt16(Vp + key_off(key) + kq * EPC);
+                if constexpr (F8) {
+                    ksn[u] = __builtin_nontemporal_load(Ks + key);
+                    vsn[u] = __builtin_nontemporal_load(Vs + key);
+                }
             }
         }
     };
     request(c0 + wave * KPW + kg);
     for (int key0 = c0 + wave * KPW + kg; key0 < c1; key0 += 4 * KPW * U) {
         uint4 kk[U], vv[U];
+        [[maybe_unused]] float ks[U], vs[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             kk[u] = kn[u];
             vv[u] = vn[u];
+            if constexpr (F8) {
+                ks[u] = ksn[u];
+                vs[u] = vsn[u];
+            }
         }
         if (key0 + 4 * KPW * U < c1) request(key0 + 4 * KPW * U);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int key = key0 + u * 4 * KPW;
             float kf[EPC], vf[EPC];
-            if constexpr (sizeof(TC) == 2) {
+            if constexpr (F8) {   // v_cvt_pk_f32_fp8: two e4m3 bytes (word 0 or 1 of the dword) -> two floats
+                const uint32_t kw[4] = {kk[u].x, kk[u].y, kk[u].z, kk[u].w}, vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const auto k0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)kw[e], false), k1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)kw[e], true);
+                    const auto v0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)vw[e], false), v1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)vw[e], true);
+                    kf[4 * e] = k0[0];
+                    kf[4 * e + 1] = k0[1];
+                    kf[4 * e + 2] = k1[0];
+                    kf[4 * e + 3] = k1[1];
+                    vf[4 * e] = v0[0];
+                    vf[4 * e + 1] = v0[1];
+                    vf[4 * e + 2] = v1[0];
+                    vf[4 * e + 3] = v1[1];
+                }
+            } else if constexpr (sizeof(TC) == 2) {
                 const uint32_t kw[4] = {kk[u].x, kk[u].y, kk[u].z, kk[u].w}, vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -903,12 +947,15 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
 #pragma unroll
             for (int o = 1; o < LPK; o <<= 1) s += __shfl_xor(s, o);
             if (key < c1) {  // uniform inside a lane group
+                if constexpr (F8) s *= ks[u];
                 s *= a.scale_log2e;
                 const float mn = fmaxf(m, s), al = fast_exp2(m - mn), p = fast_exp2(s - mn);
                 m = mn;
                 l = l * al + p;
+                float pv = p;
+                if constexpr (F8) pv *= vs[u];
 #pragma unroll
-                for (int e = 0; e < EPC; ++e) acc[e] = acc[e] * al + p * vf[e];
+                for (int e = 0; e < EPC; ++e) acc[e] = acc[e] * al + pv * vf[e];
             }
         }
     }
@@ -1657,6 +1704,20 @@ inline int launch_dattn_group(const DAttnArgs &a, int B, int group, hipStream_t 
     return 0;
 }
 
+// FP8 memory cache: the RAGGED form only (static and streamed greedy, and the slots' cross attention), dhp 16 / 32 / 64
+inline int launch_dattn_fp8(const DAttnArgs &a, int B, hipStream_t st) {
+    if (!a.seq_off || !a.k_scale || !a.v_scale) return acai_set_err(-1, "decode_attn: the FP8 cache form needs ragged offsets and K / V scales");
+    dim3 grid(a.nsplit, a.H, B);
+    switch (a.dhp) {
+        case 16: hipLaunchKernelGGL((decode_attn_kernel<fp8e4m3_t, 1, true>), grid, dim3(256), 0, st, a); break;
+        case 32: hipLaunchKernelGGL((decode_attn_kernel<fp8e4m3_t, 2, true>), grid, dim3(256), 0, st, a); break;
+        case 64: hipLaunchKernelGGL((decode_attn_kernel<fp8e4m3_t, 4, true>), grid, dim3(256), 0, st, a); break;
+        default: return acai_set_err(-1, "decode_attn: FP8 cache dhp=%d unsupported (16, 32 or 64)", a.dhp);
+    }
+    ACAI_LAUNCH_CHECK("decode_attn_fp8");
+    return 0;
+}
+
 template <typename TC>
 int launch_dattn(const DAttnArgs &a, int B, hipStream_t st) {
     const int lpk = a.dhp * (int)sizeof(TC) / 16;
@@ -1719,6 +1780,30 @@ bool dattn_merge_validated(int dhp) {
     return cached[idx] == 1;
 }
 
+// The residency rule for the FP8 form (decode_attn_kernel<fp8e4m3_t, dhp / 16, RAGGED>); its launches, like the bf16 form's, put two
+// workgroups on a CU at the headline shape.
+inline bool dattn_merge_validated_fp8(int dhp) {
+    static int cached[3] = {-1, -1, -1};   // dhp 16, 32, 64
+    static const int force = getenv("ACAI_DATTN_MERGE") ? atoi(getenv("ACAI_DATTN_MERGE")) : -1;
+    if (force >= 0) return force != 0;
+    const int idx = dhp == 16 ? 0 : dhp == 32 ? 1 : dhp == 64 ? 2 : -1;
+    if (idx < 0) return false;
+    if (cached[idx] < 0) {
+        const void *k = idx == 0 ? reinterpret_cast<const void *>(&decode_attn_kernel<fp8e4m3_t, 1, true>)
+                      : idx == 1 ? reinterpret_cast<const void *>(&decode_attn_kernel<fp8e4m3_t, 2, true>)
+                                 : reinterpret_cast<const void *>(&decode_attn_kernel<fp8e4m3_t, 4, true>);
+        int n = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 256, 0);
+        if (getenv("ACAI_DATTN_MERGE_DEBUG"))
+            fprintf(stderr, "decode_attn_kernel<fp8 e4m3 cache, dhp %d>: hipOccupancyMaxActiveBlocksPerMultiprocessor = %d (err %d)\n", dhp, n, (int)e);
+        // this form carries 16 elements per lane (94-104 VGPRs on gfx950 / ROCm 7.2, 4-5 waves per SIMD), so the API reports fewer
+        // resident workgroups than the bf16 form's 7; the hand-off was validated with the launch at two workgroups per CU
+        // (tests/test_gpu_fp8_memory.py with the merge in the launch, tools/bench_fp8_memory.py): any residency of at least 2 is that regime
+        cached[idx] = (e == hipSuccess && n >= 2 && n <= 8) ? 1 : 0;
+    }
+    return cached[idx] == 1;
+}
+
 // Host-side record of "d->x holds the chained step's input embedding" per decoder state (keyed by the x buffer): acai_decode_embed sets it,
 // acai_decode_step / acai_decode_sample_step require it (they no longer embed by themselves: their input is what the previous step's argmax
 // kernel wrote) and keep it, acai_decode_logits / acai_decode_hidden clear it (they overwrite x).  A C-ABI caller that mixes the stepwise and
@@ -1742,6 +1827,11 @@ int check_decoder(const AcaiDecoder *d) {
                        d->dhp * (d->dtype == ACAI_BF16 ? 2 : 4) >= 16,
                    "decoder: bad dims B=%d L=%d E=%d H=%d dh=%d dhp=%d", d->B, d->L, d->E, d->H, d->dh, d->dhp);
     ACAI_CHECK_ARG(d->dtype == ACAI_F32 || d->dtype == ACAI_BF16, "decoder: bad dtype");
+    if (d->flags & ACAI_DEC_CROSS_FP8) {
+        ACAI_CHECK_ARG(d->dtype == ACAI_BF16 && d->cross_group == 1, "decoder: an FP8 cross K/V needs the bf16 decoder and cross_group 1");
+        for (int l = 0; l < d->L; ++l)
+            ACAI_CHECK_ARG(d->layers[l].k_cross_scale && d->layers[l].v_cross_scale, "decoder: FP8 cross K/V of layer %d without scales", l);
+    }
     ACAI_CHECK_ARG(d->self_chunk > 0 && d->cross_chunk > 0 && d->self_nsplit > 0 && d->cross_nsplit > 0 &&
                        (long)d->self_chunk * d->self_nsplit >= d->Tmax,
                    "decoder: attention split does not cover the cache");
@@ -1792,10 +1882,27 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
         return skinny(x, E, d->unembed_w, d->unembed_b, nullptr, d->logits, d->V, d->V, E, rnd, nullptr, lnw, lnb, nullptr, nullptr, nullptr,
                       nullptr, eps, ln2w, ln2b);
     };
-    auto attend = [&](const float *q, int ldq, const void *kc, const void *vc, bool cross) -> int {
+    // FP8 memory cache (ACAI_DEC_CROSS_FP8): the cross attention reads e4m3 rows of dhp8 = max(dhp, 16) elements and their scales
+    const bool cross_f8 = (d->flags & ACAI_DEC_CROSS_FP8) != 0;
+    auto attend = [&](const float *q, int ldq, const void *kc, const void *vc, bool cross, const AcaiDecLayer *ly = nullptr) -> int {
         DAttnArgs a{};
         a.q = q; a.kc = kc; a.vc = vc; a.ldq = ldq; a.H = H; a.dh = d->dh; a.dhp = d->dhp; a.Tmax = d->Tmax;
         a.partial = d->partial; a.scale_log2e = sc;
+        if (cross && cross_f8) {
+            a.seq_off = d->cross_off; a.seq_len = d->cross_len; a.chunk = d->cross_chunk; a.nsplit = d->cross_nsplit;
+            a.dhp = d->dhp < 16 ? 16 : d->dhp;
+            a.k_scale = ly->k_cross_scale; a.v_scale = ly->v_cross_scale;
+            if (a.nsplit == 1 || (d->tickets && dattn_merge_validated_fp8(a.dhp))) {
+                a.out = d->attn; a.ldo = E; a.round_out = rnd ? 1 : 0;
+                if (a.nsplit > 1) a.tickets = d->tickets;
+                return launch_dattn_fp8(a, B, st);
+            }
+            int r = launch_dattn_fp8(a, B, st);
+            if (r) return r;
+            hipLaunchKernelGGL(attn_combine_kernel, dim3(H, B), dim3(64), 0, st, d->partial, d->attn, E, H, d->dh, a.dhp, a.nsplit, rnd ? 1 : 0);
+            ACAI_LAUNCH_CHECK("attn_combine");
+            return 0;
+        }
         if (cross) {
             a.seq_off = d->cross_off; a.seq_len = d->cross_len; a.chunk = d->cross_chunk; a.nsplit = d->cross_nsplit;
         } else {
@@ -1836,7 +1943,7 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
             if ((rc = attend(d->qkv, 3 * E, ly->k_self, ly->v_self, false))) return rc;
             if ((rc = skinny(d->attn, E, ly->self_out_w, ly->self_out_b, zin, z1, E, E, E, rnd, nullptr, nullptr, nullptr, nullptr, lnw, lnb, st0))) return rc;
             if ((rc = skinny(z1, E, ly->cross_q_w, ly->cross_q_b, nullptr, d->qkv, 3 * E, E, E, rnd, nullptr, ly->n1_w, ly->n1_b, st1))) return rc;
-            if ((rc = attend(d->qkv, 3 * E, ly->k_cross, ly->v_cross, true))) return rc;
+            if ((rc = attend(d->qkv, 3 * E, ly->k_cross, ly->v_cross, true, ly))) return rc;
             if ((rc = skinny(d->attn, E, ly->cross_out_w, ly->cross_out_b, z1, z2, E, E, E, rnd, nullptr, nullptr, nullptr, nullptr, ly->n1_w, ly->n1_b, st1))) return rc;
             hid_bf16 = true;   // linear1 -> GELU output is bf16 under autocast anyway: store it as such (half the x bytes of linear2)
             if ((rc = skinny(z2, E, ly->lin1_w, ly->lin1_b, nullptr, d->hid, F, F, E, rnd | ACAI_GEMM_GELU, nullptr, ly->n2_w, ly->n2_b, st2))) return rc;
@@ -1869,7 +1976,7 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
         if ((rc = acai_layernorm_fwd(d->proj, ly->n1_w, ly->n1_b, 1e-5f, d->x, nullptr, B, E, st))) return rc;
         // cross attention (K:212-220)
         if ((rc = skinny(d->x, E, ly->cross_q_w, ly->cross_q_b, nullptr, d->qkv, 3 * E, E, E, rnd, nullptr))) return rc;
-        if ((rc = attend(d->qkv, 3 * E, ly->k_cross, ly->v_cross, true))) return rc;
+        if ((rc = attend(d->qkv, 3 * E, ly->k_cross, ly->v_cross, true, ly))) return rc;
         if ((rc = skinny(d->attn, E, ly->cross_out_w, ly->cross_out_b, d->x, d->proj, E, E, E, rnd, nullptr))) return rc;
         if ((rc = acai_layernorm_fwd(d->proj, ly->n2_w, ly->n2_b, 1e-5f, d->x, nullptr, B, E, st))) return rc;
         // feed forward (K:222)
@@ -1894,7 +2001,75 @@ int decode(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, bool do_
                                  : decode_core<float>(d, tokens, st, do_embed, do_unembed, beam, slots);
 }
 
+// ---- FP8 memory cache: bf16 cross K/V rows -> e4m3fn rows + one power-of-two scale per row -------------------------------------------
+// Row r (elements r*dhp .. r*dhp + dhp - 1 of the ragged head-major layout) is owned by a group of LPR = dhp / 16 lanes, 16 elements each
+// (32 bytes of bf16 in, 16 bytes of e4m3 out).  amax over the group by shuffles; scale 2^e with e the smallest integer such that
+// amax 2^-e <= 448 (frexp: amax = m 2^k, m in [0.5, 1): e = k - 9 + (m > 0.875)), e >= -126 so that 2^e and 2^-e are normal floats; an
+// all-zero row gets e = 0.  q = RNE(x 2^-e) by v_cvt_pk_fp8_f32 (OCP e4m3fn on gfx950): both steps are exact but for that one rounding, so
+// the format restates bit for bit as torch's `(x.float() * 2^-e).to(torch.float8_e4m3fn)`.
+__device__ __forceinline__ float pow2i(int e) { return __int_as_float((e + 127) << 23); }   // -126 <= e <= 127
+
+template <int LPR>
+__device__ __forceinline__ void quantize_row_part(const bf16_t *in, uint8_t *out, float *scale, int part) {
+    const uint4 w0 = *reinterpret_cast<const uint4 *>(in), w1 = *reinterpret_cast<const uint4 *>(in + 8);
+    const uint32_t w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+    float x[16], amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        x[2 * i] = __uint_as_float(w[i] << 16);
+        x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        amax = fmaxf(amax, fmaxf(fabsf(x[2 * i]), fabsf(x[2 * i + 1])));
+    }
+#pragma unroll
+    for (int o = 1; o < LPR; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    int k = 0;
+    const float m = frexpf(amax, &k);
+    const int e = amax > 0.f ? max(k - 9 + (m > 0.875f ? 1 : 0), -126) : 0;
+    const float inv = pow2i(-e);
+    uint32_t q[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int v = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * i] * inv, x[4 * i + 1] * inv, 0, false);
+        v = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * i + 2] * inv, x[4 * i + 3] * inv, v, true);
+        q[i] = (uint32_t)v;
+    }
+    *reinterpret_cast<uint4 *>(out) = make_uint4(q[0], q[1], q[2], q[3]);
+    if (part == 0) *scale = pow2i(e);
+}
+
+template <int LPR>
+__global__ __launch_bounds__(256) void cross_kv_quantize_fp8_kernel(const bf16_t *kin, const bf16_t *vin, uint8_t *k8, uint8_t *v8, float *ks,
+                                                                    float *vs, long long row0, long long nrows) {
+    constexpr int DHP = 16 * LPR;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long r = g / LPR;
+    const int part = (int)(g % LPR);
+    if (r >= nrows) return;   // the lanes of a row exit together (LPR divides 64): the shuffles stay inside live groups
+    const size_t row = (size_t)(row0 + r), e0 = row * DHP + part * 16;
+    quantize_row_part<LPR>(kin + e0, k8 + e0, ks + row, part);
+    quantize_row_part<LPR>(vin + e0, v8 + e0, vs + row, part);
+}
+
 }  // namespace
+
+extern "C" int acai_cross_kv_quantize_fp8(const void *k_in, const void *v_in, void *k_out, void *v_out, float *k_scale, float *v_scale,
+                                          int64_t row0, int64_t nrows, int dhp, void *stream) {
+    ACAI_CHECK_ARG(k_in && v_in && k_out && v_out && k_scale && v_scale, "acai_cross_kv_quantize_fp8: null operand");
+    ACAI_CHECK_ARG(row0 >= 0 && nrows >= 0 && (dhp == 16 || dhp == 32 || dhp == 64), "acai_cross_kv_quantize_fp8: bad dims row0=%lld nrows=%lld dhp=%d",
+                   (long long)row0, (long long)nrows, dhp);
+    ACAI_CHECK_ARG(aligned16(k_in) && aligned16(v_in) && aligned16(k_out) && aligned16(v_out), "acai_cross_kv_quantize_fp8: operands must be 16-byte aligned");
+    if (nrows == 0) return 0;
+    const int lpr = dhp / 16;
+    const dim3 grid((unsigned)((nrows * lpr + 255) / 256));
+    hipStream_t st = (hipStream_t)stream;
+    auto kin = (const bf16_t *)k_in, vin = (const bf16_t *)v_in;
+    auto k8 = (uint8_t *)k_out, v8 = (uint8_t *)v_out;
+    if (lpr == 1) hipLaunchKernelGGL(cross_kv_quantize_fp8_kernel<1>, grid, dim3(256), 0, st, kin, vin, k8, v8, k_scale, v_scale, (long long)row0, (long long)nrows);
+    else if (lpr == 2) hipLaunchKernelGGL(cross_kv_quantize_fp8_kernel<2>, grid, dim3(256), 0, st, kin, vin, k8, v8, k_scale, v_scale, (long long)row0, (long long)nrows);
+    else hipLaunchKernelGGL(cross_kv_quantize_fp8_kernel<4>, grid, dim3(256), 0, st, kin, vin, k8, v8, k_scale, v_scale, (long long)row0, (long long)nrows);
+    ACAI_LAUNCH_CHECK("cross_kv_quantize_fp8");
+    return 0;
+}
 
 // Stand-alone entry points for the module-level API (CachedMultiheadAttention.cached_forward K:123-140,
 // F.linear on (B,1,E) K:193,215): the same kernels acai_decode_step chains.
@@ -1949,6 +2124,28 @@ extern "C" int acai_decode_attn(const float *q, int ldq, const void *kc, const v
     return 0;
 }
 
+extern "C" int acai_decode_attn_fp8(const float *q, int ldq, const void *kc, const void *vc, const float *k_scale, const float *v_scale,
+                                    const int64_t *seq_off, const int32_t *seq_len, float *partial, float *out, int ldo, int B, int H, int dh,
+                                    int dhp, int chunk, int nsplit, int round_out, uint32_t *tickets, void *stream) {
+    ACAI_CHECK_ARG(q && kc && vc && k_scale && v_scale && seq_off && seq_len && partial, "acai_decode_attn_fp8: null operand");
+    ACAI_CHECK_ARG(B > 0 && H > 0 && dh > 0 && dhp >= dh && (dhp == 16 || dhp == 32 || dhp == 64) && chunk > 0 && nsplit > 0,
+                   "acai_decode_attn_fp8: bad dims");
+    DAttnArgs a{};
+    a.q = q; a.kc = kc; a.vc = vc; a.k_scale = k_scale; a.v_scale = v_scale; a.seq_off = seq_off; a.seq_len = seq_len; a.partial = partial;
+    a.ldq = ldq; a.H = H; a.dh = dh; a.dhp = dhp; a.chunk = chunk; a.nsplit = nsplit;
+    a.scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+    hipStream_t st = (hipStream_t)stream;
+    if (tickets && out) {
+        a.out = out; a.ldo = ldo; a.round_out = round_out; a.tickets = tickets;
+        return launch_dattn_fp8(a, B, st);
+    }
+    int rc = launch_dattn_fp8(a, B, st);
+    if (rc || !out) return rc;
+    hipLaunchKernelGGL(attn_combine_kernel, dim3(H, B), dim3(64), 0, st, partial, out, ldo, H, dh, dhp, nsplit, round_out);
+    ACAI_LAUNCH_CHECK("attn_combine");
+    return 0;
+}
+
 // Diagnostic: from now on every MFMA skinny launch (up to cap_launches, 1024 workgroups each) writes s_memrealtime stamps of its stages
 // into buf[launch][workgroup][8]; buf = NULL switches it off and rewinds the slot counter.  Not part of the product path.
 extern "C" int acai_debug_stamps(void *buf, int cap_launches) {
@@ -1959,6 +2156,10 @@ extern "C" int acai_debug_stamps(void *buf, int cap_launches) {
 }
 
 extern "C" int acai_decode_merge_in_launch(int dtype, int dhp) {
+    if (dtype == ACAI_FP8_E4M3) {
+        ACAI_CHECK_ARG(dhp == 16 || dhp == 32 || dhp == 64, "acai_decode_merge_in_launch: bad FP8 dhp");
+        return dattn_merge_validated_fp8(dhp) ? 1 : 0;
+    }
     ACAI_CHECK_ARG((dtype == ACAI_BF16 || dtype == ACAI_F32) && dhp > 0 && dhp <= 64 && (dhp & (dhp - 1)) == 0, "acai_decode_merge_in_launch: bad dtype / dhp");
     return dtype == ACAI_BF16 ? (dattn_merge_validated<bf16_t>(dhp) ? 1 : 0) : (dattn_merge_validated<float>(dhp) ? 1 : 0);
 }

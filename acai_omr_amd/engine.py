@@ -198,6 +198,14 @@ class DecodeEngine:
     # +2.8 % tokens/s over 512 on the same box; 256 and 2048 are slower.  ACAI_CROSS_CHUNK overrides (A/B aid).
     CROSS_CHUNK = int(os.environ.get("ACAI_CROSS_CHUNK", "1024"))
     CROSS_SLOTS = 512   # cross-attention workgroups resident at once (two per CU on 256 CUs)
+    # the same for an FP8 memory cache (68-byte key rows instead of 128): ACAI_CROSS_CHUNK_FP8 pins it (A/B aid)
+    CROSS_CHUNK_FP8 = 1024
+
+    @classmethod
+    def pick_cross_chunk_fp8(cls, lens, H):
+        if "ACAI_CROSS_CHUNK_FP8" in os.environ:
+            return int(os.environ["ACAI_CROSS_CHUNK_FP8"])
+        return cls.CROSS_CHUNK_FP8
 
     @classmethod
     def pick_cross_chunk(cls, lens, H):
@@ -215,7 +223,7 @@ class DecodeEngine:
                 best, best_cost = c, cost
         return best
 
-    def __init__(self, blocks, omr, max_batch_size, max_len, prec, device):
+    def __init__(self, blocks, omr, max_batch_size, max_len, prec, device, memory_fp8=False):
         self.blocks = blocks        # CachedTransformerDecoder mirror (layers, norm): parameters are read from it
         self.omr = omr              # OMRDecoder mirror (embedding, positions, unembed) or None
         self.prec = prec
@@ -232,6 +240,14 @@ class DecodeEngine:
         while dhp < self.dh:
             dhp *= 2
         self.dhp = dhp
+        # FP8 memory cache (bf16 engines only): the cross K/V is e4m3fn with one fp32 scale per row, rows of cdhp = max(dhp, 16) elements;
+        # every layer's prefill goes through one reused bf16 region (k_stage / v_stage) and is then quantised into the layer's buffers
+        self.cross_fp8 = bool(memory_fp8)
+        if self.cross_fp8 and not self.bf:
+            raise TypeError("an FP8 memory cache needs cache_dtype=torch.bfloat16")
+        self.cdhp = max(dhp, 16) if self.cross_fp8 else dhp
+        self.k_cross_scale = self.v_cross_scale = None
+        self.k_stage = self.v_stage = None
         self.F = blocks.layers[0].linear1.out_features
         self.V = omr.vocab_size if omr is not None else 1
         self.wc = WeightCache()
@@ -282,7 +298,10 @@ class DecodeEngine:
         self._mode = ("greedy",)
         if B > self.Bmax:
             raise ValueError(f"The current cache has been setup with a max batch size of {self.Bmax}, but found new key tensors with batch size {B}!")
-        E, H, dhp, dev = self.E, self.H, self.dhp, self.device
+        if G > 1 and self.cross_fp8:
+            raise ValueError("an FP8 memory cache does not support grouped cross K/V (group_size > 1: beam search, grouped GRPO rollouts); "
+                             "use memory_cache_dtype=None")
+        E, H, dhp, dev = self.E, self.H, self.cdhp, self.device
         self._size_cross(sum(lens) * H * dhp, B, lens, G)
         offs, o = [], 0
         for l in lens:
@@ -301,8 +320,13 @@ class DecodeEngine:
             ca = layer.multihead_attn
             w = self.wc.w(ca.in_proj_weight, self.prec)[E:]
             b = self.wc.b(ca.in_proj_bias, self.prec)[E:]
-            ops.cross_kv_prefill(mem, w, b, row_seq, row_pos, pre_off, pre_len, self.k_cross[i], self.v_cross[i],
-                                 H, self.dh, dhp, round_bf16=self.bf)
+            if self.cross_fp8:
+                ops.cross_kv_prefill(mem, w, b, row_seq, row_pos, pre_off, pre_len, self.k_stage, self.v_stage, H, self.dh, dhp, round_bf16=True)
+                ops.cross_kv_quantize_fp8(self.k_stage, self.v_stage, self.k_cross[i], self.v_cross[i], self.k_cross_scale[i],
+                                          self.v_cross_scale[i], 0, sum(lens) * H, dhp)
+            else:
+                ops.cross_kv_prefill(mem, w, b, row_seq, row_pos, pre_off, pre_len, self.k_cross[i], self.v_cross[i],
+                                     H, self.dh, dhp, round_bf16=self.bf)
         self.B, self.lens, self.group = B, [l for l in lens for _ in range(G)], G
         self.reset_self_cache()
         self._build_desc()
@@ -310,18 +334,45 @@ class DecodeEngine:
     def _size_cross(self, total, B, lens, group=1):
         """Cross K/V buffers of at least `total` elements per layer, the cross split (keys per workgroup, splits) of memories of lengths
         `lens` shared by `group` rows each, and `partial` for B rows at that split.  A reallocation drops the captured graphs."""
-        H, dhp, dev = self.H, self.dhp, self.device
+        H, dhp, dev = self.H, self.cdhp, self.device
         if total > self.cross_cap:
             self.cross_cap = total
-            self.k_cross = [torch.zeros(total, dtype=self.cdt, device=dev) for _ in range(self.L)]
-            self.v_cross = [torch.zeros(total, dtype=self.cdt, device=dev) for _ in range(self.L)]
+            if self.cross_fp8:
+                self.k_cross = self.v_cross = self.k_cross_scale = self.v_cross_scale = self.k_stage = self.v_stage = None   # (peak memory)
+                self.k_cross = [torch.zeros(total, dtype=torch.float8_e4m3fn, device=dev) for _ in range(self.L)]
+                self.v_cross = [torch.zeros(total, dtype=torch.float8_e4m3fn, device=dev) for _ in range(self.L)]
+                self.k_cross_scale = [torch.zeros(total // dhp, dtype=torch.float32, device=dev) for _ in range(self.L)]
+                self.v_cross_scale = [torch.zeros(total // dhp, dtype=torch.float32, device=dev) for _ in range(self.L)]
+                self.k_stage = torch.zeros(total, dtype=torch.bfloat16, device=dev)
+                self.v_stage = torch.zeros(total, dtype=torch.bfloat16, device=dev)
+            else:
+                self.k_cross = [torch.zeros(total, dtype=self.cdt, device=dev) for _ in range(self.L)]
+                self.v_cross = [torch.zeros(total, dtype=self.cdt, device=dev) for _ in range(self.L)]
             self.graphs.clear()  # pointers changed
-        self.cross_chunk = self.pick_cross_chunk(lens, H) if group == 1 else self.CROSS_CHUNK
+        if self.cross_fp8:
+            self.cross_chunk = self.pick_cross_chunk_fp8(lens, H)
+        else:
+            self.cross_chunk = self.pick_cross_chunk(lens, H) if group == 1 else self.CROSS_CHUNK
         self.cross_nsplit = max(1, -(-max(lens) // self.cross_chunk))
         nsplit = max(self.cross_nsplit, self.self_nsplit)
         if self.partial is None or self.partial.numel() < B * H * nsplit * (dhp + 2):
             self.partial = torch.empty(self.Bmax * H * nsplit * (dhp + 2), dtype=torch.float32, device=dev)
             self.graphs.clear()
+
+    def cross_kv_bytes(self):
+        """Bytes of the cross K/V allocation over all layers (values and, for an FP8 memory cache, the per-row scales; not the staging)."""
+        ts = list(self.k_cross or []) + list(self.v_cross or []) + list(self.k_cross_scale or []) + list(self.v_cross_scale or [])
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def cross_kv_values(self, layer):
+        """Layer `layer`'s cross K and V as the decode step reads them, fp32, flat in the stored layout (an FP8 cache: dequantised)."""
+        k, v = self.k_cross[layer], self.v_cross[layer]
+        if not self.cross_fp8:
+            return k.float(), v.float()
+        from .fp8 import dequantize_rows
+        d = self.cdhp
+        return (dequantize_rows(k.view(-1, d), self.k_cross_scale[layer]).view(-1),
+                dequantize_rows(v.view(-1, d), self.v_cross_scale[layer]).view(-1))
 
     def reset_self_cache(self):
         """KVCache.reset (kv_caching.py:47-51): position back to 0 (stale entries are never read: length is step[1]+1)."""
@@ -344,6 +395,8 @@ class DecodeEngine:
                      n1_w=ly.norm1.weight.detach(), n1_b=ly.norm1.bias.detach(), n2_w=ly.norm2.weight.detach(), n2_b=ly.norm2.bias.detach(),
                      n3_w=ly.norm3.weight.detach(), n3_b=ly.norm3.bias.detach(),
                      k_self=self.k_self[i], v_self=self.v_self[i], k_cross=self.k_cross[i], v_cross=self.v_cross[i])
+            if self.cross_fp8:
+                t.update(k_cross_scale=self.k_cross_scale[i], v_cross_scale=self.v_cross_scale[i])
             for k, v in t.items():
                 assert v.is_contiguous() or k.startswith("cross_q"), k
                 setattr(layers[i], k, P(v))
@@ -352,7 +405,7 @@ class DecodeEngine:
         d = _lib.AcaiDecoder()
         d.B, d.E, d.H, d.dh, d.dhp, d.F, d.V, d.L, d.Tmax = self.B, E, self.H, self.dh, self.dhp, self.F, self.V, self.L, self.Tmax
         d.dtype = _lib.ACAI_BF16 if self.bf else _lib.ACAI_F32
-        d.flags = _lib.GEMM_ROUND_BF16 if self.bf else 0
+        d.flags = (_lib.GEMM_ROUND_BF16 if self.bf else 0) | (_lib.DEC_CROSS_FP8 if self.cross_fp8 else 0)
         d.max_len = self.Tmax
         d.cross_group = self.group
         d.self_chunk, d.cross_chunk, d.self_nsplit, d.cross_nsplit = self.SELF_CHUNK, self.cross_chunk, self.self_nsplit, self.cross_nsplit
@@ -687,10 +740,11 @@ class DecodeEngine:
     def _slot_setup(self, Scap, S):
         """Slot mode for S rows over regions of Scap memory rows: the cross K/V layout, the cross split picked once for [Scap] * S (so that
         the captured graphs stay valid across refills), the slot state and the descriptors."""
-        H, dhp, dev = self.H, self.dhp, self.device
+        H, dhp, dev = self.H, self.cdhp, self.device
         region = Scap * H * dhp
         self._size_cross(S * region, S, [Scap] * S)
         self.slot_off = torch.arange(S, dtype=torch.int64, device=dev) * region
+        self._slot_row0 = [s * (region // dhp) for s in range(S)]
         self.cross_off[:S] = self.slot_off
         self.cross_len[:S].fill_(1)
         self.B, self.lens, self.group = S, [Scap] * S, 1
@@ -727,12 +781,18 @@ class DecodeEngine:
         depend on which images were admitted with it), set the slot's cross length and arm the slots."""
         if not admitted:
             return
-        H, dh, dhp = self.H, self.dh, self.dhp
+        H, dh, dhp = self.H, self.dh, self.cdhp
         for s, i in admitted:
             l = offs[i + 1] - offs[i]
             for li, (w, b) in enumerate(self._cross_w):
-                ops.cross_kv_prefill(mem[offs[i]:offs[i + 1]], w, b, self._row_seq[:l], self._row_pos[:l], self.slot_off[s:s + 1],
-                                     lens_dev[i:i + 1], self.k_cross[li], self.v_cross[li], H, dh, dhp, round_bf16=self.bf)
+                if self.cross_fp8:   # through the staging region at the slot's offset, then quantised into the slot's rows
+                    ops.cross_kv_prefill(mem[offs[i]:offs[i + 1]], w, b, self._row_seq[:l], self._row_pos[:l], self.slot_off[s:s + 1],
+                                         lens_dev[i:i + 1], self.k_stage, self.v_stage, H, dh, dhp, round_bf16=True)
+                    ops.cross_kv_quantize_fp8(self.k_stage, self.v_stage, self.k_cross[li], self.v_cross[li], self.k_cross_scale[li],
+                                              self.v_cross_scale[li], self._slot_row0[s], l * H, dhp)
+                else:
+                    ops.cross_kv_prefill(mem[offs[i]:offs[i + 1]], w, b, self._row_seq[:l], self._row_pos[:l], self.slot_off[s:s + 1],
+                                         lens_dev[i:i + 1], self.k_cross[li], self.v_cross[li], H, dh, dhp, round_bf16=self.bf)
             self.cross_len[s:s + 1].copy_(lens_dev[i:i + 1])
             self._parked.discard(s)
         rows = torch.tensor([[s for s, _ in admitted], [caps[i] for _, i in admitted]], dtype=torch.int32)

@@ -15,13 +15,14 @@ from ..models.models import FineTuneOMREncoder, OMRDecoder, ScheduledSamplingViT
 logger = logging.getLogger(__name__)
 
 
-def set_up_omr_inference(lmx_vocab_path=LMX_VOCAB_PATH, max_batch_size=32, cache_dtype=torch.bfloat16, device="cuda"):
+def set_up_omr_inference(lmx_vocab_path=LMX_VOCAB_PATH, max_batch_size=32, cache_dtype=torch.bfloat16, device="cuda", memory_cache_dtype=None):
     """Model construction of omr_teacher_force_train.set_up_omr_inference (:265-284) + the cached-decoder swap of
-    vitomr_inference.__main__ (:98).  The torchvision image transform is host preprocessing and out of scope."""
+    vitomr_inference.__main__ (:98).  The torchvision image transform is host preprocessing and out of scope.  memory_cache_dtype
+    (extension): torch.float8_e4m3fn keeps the decoder's cross-attention K/V in FP8 (OMRDecoder.to_cached_version)."""
     encoder = FineTuneOMREncoder(PATCH_SIZE, PE_MAX_HEIGHT, PE_MAX_WIDTH, ENCODER_FINE_TUNE_DEPTH)
     decoder = OMRDecoder(MAX_LMX_SEQ_LEN, lmx_vocab_path, num_layers=NUM_DECODER_LAYERS)
     vitomr = ScheduledSamplingViTOMR(encoder, None, decoder)
-    vitomr.decoder = vitomr.decoder.to_cached_version(max_batch_size, cache_dtype)
+    vitomr.decoder = vitomr.decoder.to_cached_version(max_batch_size, cache_dtype, memory_cache_dtype)
     return vitomr.to(device), device
 
 

@@ -8,6 +8,12 @@ fused, hipGraph-capturable step of `engine.DecodeEngine`.  There is no CPU path:
 
 Precision follows the cache dtype, as in the reference plumbing (vitomr_inference.py:94): a bfloat16 cache means
 "what autocast(bfloat16) computes" (bf16 operands/outputs, fp32 accumulate), a float cache means plain fp32.
+
+memory_cache_dtype (an extension, opt-in): torch.float8_e4m3fn with cache_dtype=torch.bfloat16 stores the cross-attention K/V that the
+decode engine prefills from the encoder memory in FP8 (e4m3fn values, one power-of-two fp32 scale per row: acai_omr_amd/fp8.py); the
+self-attention caches stay bf16.  It applies to the engine path (prepare_caches / cached_generate and every inference entry point built on
+it); the module-level `CachedTransformerDecoderLayer.cached_forward` / `MemoryCache` API-parity path keeps the cache dtype.  Grouped cross
+K/V (group_size > 1: beam search, grouped GRPO rollouts) is not supported with it and raises ValueError.
 """
 import torch
 import torch.nn.functional as F
@@ -23,6 +29,16 @@ def _prec_of(dtype):
     if dtype in (torch.float32, torch.float):
         return "fp32"
     raise TypeError(f"cache dtype {dtype} is not supported by the MI355X backend (float32 or bfloat16)")
+
+
+def _memory_fp8(cache_dtype, memory_cache_dtype):
+    """True for an FP8 memory cache; None or cache_dtype itself mean the cache dtype.  Anything else raises TypeError."""
+    if memory_cache_dtype is None or memory_cache_dtype == cache_dtype:
+        return False
+    if memory_cache_dtype == torch.float8_e4m3fn and cache_dtype == torch.bfloat16:
+        return True
+    raise TypeError(f"memory_cache_dtype {memory_cache_dtype} with cache_dtype {cache_dtype} is not supported by the MI355X backend "
+                    "(None, the cache dtype, or torch.float8_e4m3fn with cache_dtype=torch.bfloat16)")
 
 
 def _pad_pow2(dh, es):
@@ -189,8 +205,9 @@ class CachedTransformerDecoder(nn.TransformerDecoder):
     prepare_caches(memory) then cached_generate(embedding_t, mask) once per token, starting with <bos>."""
 
     def __init__(self, decoder_layer: CachedTransformerDecoderLayer, num_layers: int, max_batch_size: int, max_decoder_seq_len: int,
-                 cache_dtype, norm: nn.Module = None):
+                 cache_dtype, norm: nn.Module = None, memory_cache_dtype=None):
         assert isinstance(decoder_layer, CachedTransformerDecoderLayer), "Can't use uncached TransformerDecoderLayer in a cached TransformerDecoder"
+        memory_fp8 = _memory_fp8(cache_dtype, memory_cache_dtype)
         super().__init__(decoder_layer, num_layers, norm)
         self.self_attn_caches = nn.ModuleList([KVCache(max_batch_size, max_decoder_seq_len, layer.num_heads, layer.head_dim, dtype=cache_dtype)
                                                for layer in self.layers])
@@ -198,6 +215,8 @@ class CachedTransformerDecoder(nn.TransformerDecoder):
         self.max_batch_size = max_batch_size
         self.max_decoder_seq_len = max_decoder_seq_len
         self.cache_dtype = cache_dtype
+        self.memory_cache_dtype = memory_cache_dtype
+        self.__dict__["_memory_fp8"] = memory_fp8
         self.__dict__["_engine"] = None
         self.__dict__["_pending"] = None
         self.__dict__["_omr"] = None  # set by OMRDecoder so that the fused step can embed / unembed
@@ -214,7 +233,8 @@ class CachedTransformerDecoder(nn.TransformerDecoder):
     def engine(self, device):
         eng = self.__dict__["_engine"]
         if eng is None or eng.device != torch.device(device):
-            eng = DecodeEngine(self, self.__dict__["_omr"], self.max_batch_size, self.max_decoder_seq_len, _prec_of(self.cache_dtype), torch.device(device))
+            eng = DecodeEngine(self, self.__dict__["_omr"], self.max_batch_size, self.max_decoder_seq_len, _prec_of(self.cache_dtype), torch.device(device),
+                               memory_fp8=self.__dict__.get("_memory_fp8", False))
             self.__dict__["_engine"] = eng
         return eng
 

@@ -21,7 +21,7 @@ from torch import nn
 from .. import engine as EG
 from .. import ops
 from ..config import LMX_BOS_TOKEN, LMX_EOS_TOKEN, LMX_PAD_TOKEN, InferenceEvent
-from .kv_caching import CachedTransformerDecoder, CachedTransformerDecoderLayer, _wc
+from .kv_caching import CachedTransformerDecoder, CachedTransformerDecoderLayer, _memory_fp8, _wc
 
 NUM_CHANNELS = 1  # grayscale sheet music
 
@@ -319,8 +319,11 @@ class OMRDecoder(nn.Module):
     """Autoregressive LMX decoder (M:378-528): embedding + learned positions + post-LN decoder blocks + unembed."""
 
     def __init__(self, max_lmx_seq_len, lmx_vocab_path, num_layers=10, hidden_dim=1024, num_heads=16, mlp_dim=4096, transformer_dropout=0.1,
-                 use_caching=False, max_batch_size=None, cache_dtype=None):
+                 use_caching=False, max_batch_size=None, cache_dtype=None, memory_cache_dtype=None):
+        """memory_cache_dtype (extension, opt-in; cached decoder only): torch.float8_e4m3fn with cache_dtype=torch.bfloat16 keeps the decode
+        engine's cross-attention K/V in FP8 (see models/kv_caching.py); None = the cache dtype."""
         super().__init__()
+        _memory_fp8(cache_dtype, memory_cache_dtype)   # TypeError for an unsupported combination, cached or not
         self.max_lmx_seq_len = max_lmx_seq_len
         self.lmx_vocab_path = lmx_vocab_path
         self.num_layers = num_layers
@@ -344,16 +347,18 @@ class OMRDecoder(nn.Module):
         if use_caching:
             self.decoder_blocks = CachedTransformerDecoder(decoder_layer=CachedTransformerDecoderLayer(**lkw), num_layers=num_layers,
                                                            max_batch_size=max_batch_size, max_decoder_seq_len=max_lmx_seq_len,
-                                                           cache_dtype=cache_dtype, norm=nn.LayerNorm(self.hidden_dim, eps=1e-6))
+                                                           cache_dtype=cache_dtype, norm=nn.LayerNorm(self.hidden_dim, eps=1e-6),
+                                                           memory_cache_dtype=memory_cache_dtype)
             self.decoder_blocks.__dict__["_omr"] = self
         else:
             self.decoder_blocks = nn.TransformerDecoder(decoder_layer=nn.TransformerDecoderLayer(**lkw), num_layers=num_layers,
                                                         norm=nn.LayerNorm(self.hidden_dim, eps=1e-6))
         self.unembed = nn.Linear(self.hidden_dim, self.vocab_size)
 
-    def to_cached_version(self, max_batch_size, cache_dtype):
+    def to_cached_version(self, max_batch_size, cache_dtype, memory_cache_dtype=None):
         return OMRDecoder(self.max_lmx_seq_len, self.lmx_vocab_path, self.num_layers, self.hidden_dim, self.num_heads, self.mlp_dim,
-                          self.transformer_dropout, use_caching=True, max_batch_size=max_batch_size, cache_dtype=cache_dtype)
+                          self.transformer_dropout, use_caching=True, max_batch_size=max_batch_size, cache_dtype=cache_dtype,
+                          memory_cache_dtype=memory_cache_dtype)
 
     # ---- teacher-forced / uncached batch paths -----------------------------------------------------------------------------
     def forward_packed(self, inputs, lens_t, mem32, memb, lens_s, token_idxs_input=True, prec=None):

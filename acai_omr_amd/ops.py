@@ -299,6 +299,22 @@ def cross_kv_prefill(mem, w_kv, b_kv, row_seq, row_pos, seq_off, seq_len, k_out,
                                                 M, E, H, dh, dhp, _dt(mem), GEMM_ROUND_BF16 if round_bf16 else 0, _st()), "acai_cross_kv_prefill")
 
 
+def cross_kv_quantize_fp8(k_in, v_in, k_out, v_out, k_scale, v_scale, row0, nrows, dhp):
+    """FP8 memory cache prefill: rows row0 .. row0+nrows-1 (dhp elements each) of the bf16 cross K/V k_in / v_in -> e4m3fn rows of k_out /
+    v_out and their fp32 power-of-two scales k_scale[row] / v_scale[row] (the format of acai_omr_amd.fp8.quantize_rows)."""
+    for t, n in ((k_in, "k_in"), (v_in, "v_in")):
+        _chk(t, n, torch.bfloat16)
+    for t, n in ((k_out, "k_out"), (v_out, "v_out")):
+        _chk(t, n, torch.float8_e4m3fn)
+    for t, n in ((k_scale, "k_scale"), (v_scale, "v_scale")):
+        _chk(t, n, torch.float32)
+    end = (int(row0) + int(nrows)) * dhp
+    assert all(t.is_contiguous() and t.numel() >= end for t in (k_in, v_in, k_out, v_out)), "row range beyond a K/V buffer"
+    assert k_scale.numel() >= end // dhp and v_scale.numel() >= end // dhp, "row range beyond a scale buffer"
+    _lib.check(_lib.lib().acai_cross_kv_quantize_fp8(k_in.data_ptr(), v_in.data_ptr(), k_out.data_ptr(), v_out.data_ptr(), k_scale.data_ptr(),
+                                                     v_scale.data_ptr(), int(row0), int(nrows), int(dhp), _st()), "acai_cross_kv_quantize_fp8")
+
+
 def skinny_gemm(x, w, bias=None, residual=None, gelu=False, round_bf16=False, out=None):
     """x [B,K] fp32, w [N,K] fp32 or bf16 -> y [B,N] fp32."""
     _chk(x, "x", torch.float32), _chk(w, "w")
@@ -330,17 +346,27 @@ def skinny_gemm_ex(x, w, bias=None, residual=None, gelu=False, round_bf16=False,
     return out
 
 
-def decode_attn(q, kc, vc, seq_off, seq_len, H, dh, dhp, max_len, round_out=False, chunk=256, fused_merge=False):
-    """q [B, H*dh] fp32 (row stride free); kc/vc flat caches addressed by seq_off / seq_len (see header)."""
+def decode_attn(q, kc, vc, seq_off, seq_len, H, dh, dhp, max_len, round_out=False, chunk=256, fused_merge=False, k_scale=None, v_scale=None):
+    """q [B, H*dh] fp32 (row stride free); kc/vc flat caches addressed by seq_off / seq_len (see header).  kc / vc in torch.float8_e4m3fn:
+    the FP8 cache form (acai_decode_attn_fp8), with k_scale / v_scale the fp32 per-row scales (row = element offset / dhp)."""
     _chk(q, "q", torch.float32)
     B = q.shape[0]
     nsplit = max(1, -(-int(max_len) // chunk))
     partial = torch.empty(B * H * nsplit * (dhp + 2), dtype=torch.float32, device=q.device)
     out = torch.empty(B, H * dh, dtype=torch.float32, device=q.device)
     tickets = torch.zeros(B * H, dtype=torch.int32, device=q.device) if fused_merge else None
-    _lib.check(_lib.lib().acai_decode_attn(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), seq_off.data_ptr(), seq_len.data_ptr(),
-                                           partial.data_ptr(), out.data_ptr(), out.stride(0), B, H, dh, dhp, chunk, nsplit, _dt(kc),
-                                           1 if round_out else 0, tickets.data_ptr() if tickets is not None else None, _st()), "acai_decode_attn")
+    tk = tickets.data_ptr() if tickets is not None else None
+    if kc.dtype == torch.float8_e4m3fn:
+        assert vc.dtype == kc.dtype and k_scale is not None and v_scale is not None
+        _chk(k_scale, "k_scale", torch.float32), _chk(v_scale, "v_scale", torch.float32)
+        _lib.check(_lib.lib().acai_decode_attn_fp8(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+                                                   seq_off.data_ptr(), seq_len.data_ptr(), partial.data_ptr(), out.data_ptr(), out.stride(0), B, H,
+                                                   dh, dhp, chunk, nsplit, 1 if round_out else 0, tk, _st()), "acai_decode_attn_fp8")
+    else:
+        assert k_scale is None and v_scale is None, "per-row scales belong to an FP8 cache"
+        _lib.check(_lib.lib().acai_decode_attn(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), seq_off.data_ptr(), seq_len.data_ptr(),
+                                               partial.data_ptr(), out.data_ptr(), out.stride(0), B, H, dh, dhp, chunk, nsplit, _dt(kc),
+                                               1 if round_out else 0, tk, _st()), "acai_decode_attn")
     if tickets is not None:
         assert int(tickets.abs().sum().item()) == 0, "arrival counters must re-arm to zero"
     return out

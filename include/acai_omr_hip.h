@@ -11,7 +11,8 @@
  * positive = hipError_t; acai_last_error() gives a message.  No C++ exception crosses the ABI.
  *
  * dtypes: ACAI_F32 = fp32 storage + exact-fp32 MFMA (v_mfma_f32_32x32x2_f32);
- *         ACAI_BF16 = bf16 storage + bf16 MFMA with fp32 accumulate.
+ *         ACAI_BF16 = bf16 storage + bf16 MFMA with fp32 accumulate;
+ *         ACAI_FP8_E4M3 = OCP e4m3fn storage with one fp32 power-of-two scale per row (the decode cross K/V of an FP8 memory cache only).
  * The residual stream, LayerNorm, softmax statistics, biases and logits are always fp32.
  */
 #ifndef ACAI_OMR_HIP_H
@@ -26,6 +27,7 @@ extern "C" {
 #define ACAI_ABI_VERSION 1
 #define ACAI_F32 0
 #define ACAI_BF16 1
+#define ACAI_FP8_E4M3 2
 
 /* gemm epilogue flags */
 #define ACAI_GEMM_GELU 1       /* exact-erf GELU after bias (M:31 activation="gelu", M:657 nn.GELU) */
@@ -250,8 +252,15 @@ typedef struct {
     const void *lin2_w;      const float *lin2_b;      /* linear2 [E,F] */
     const float *n1_w, *n1_b, *n2_w, *n2_b, *n3_w, *n3_b;
     void *k_self, *v_self;              /* KVCache (K:35-41) as [Bmax][H][Tmax][dhp] */
-    const void *k_cross, *v_cross;      /* acai_cross_kv_prefill output */
+    const void *k_cross, *v_cross;      /* acai_cross_kv_prefill output (bf16 / fp32), or acai_cross_kv_quantize_fp8 output (ACAI_DEC_CROSS_FP8) */
+    const float *k_cross_scale, *v_cross_scale;  /* ACAI_DEC_CROSS_FP8: per-row scales of k_cross / v_cross, else unused */
 } AcaiDecLayer;
+
+/* AcaiDecoder.flags: besides ACAI_GEMM_ROUND_BF16, ACAI_DEC_CROSS_FP8 = the cross K/V of every layer is e4m3fn with per-row scales
+ * (bf16 decoder, cross_group 1).  Its rows are dhp8 = max(dhp, 16) elements (element offset cross_off[b] + (h*S_b + s)*dhp8, scale at
+ * that offset / dhp8), and `partial` must hold B*H*cross_nsplit*(dhp8+2) floats.  The self-attention caches keep `dtype`. */
+#define ACAI_DEC_CROSS_FP8 256
+
 
 typedef struct {
     int32_t B, E, H, dh, dhp, F, V, L, Tmax, dtype, flags, max_len;
@@ -394,6 +403,18 @@ int acai_skinny_gemm_ex(const void *x, int ldx, int x_dtype, const void *W, int 
 int acai_decode_attn(const float *q, int ldq, const void *kc, const void *vc, const int64_t *seq_off, const int32_t *seq_len,
                      float *partial, float *out, int ldo, int B, int H, int dh, int dhp, int chunk, int nsplit, int dtype,
                      int round_out, uint32_t *tickets, void *stream);
+/* The same over an FP8 (ACAI_FP8_E4M3) cache: element (b, h, s, d) is kc[seq_off[b] + (h*seq_len[b] + s)*dhp + d] * k_scale[row], row =
+ * (seq_off[b] + (h*seq_len[b] + s)*dhp) / dhp (likewise V); dhp 16, 32 or 64. */
+int acai_decode_attn_fp8(const float *q, int ldq, const void *kc, const void *vc, const float *k_scale, const float *v_scale,
+                         const int64_t *seq_off, const int32_t *seq_len, float *partial, float *out, int ldo, int B, int H, int dh,
+                         int dhp, int chunk, int nsplit, int round_out, uint32_t *tickets, void *stream);
+
+/* FP8 memory cache prefill: rows row0 .. row0+nrows-1 (dhp = 16, 32 or 64 elements each, at element offset row*dhp) of the bf16 cross K/V
+ * written by acai_cross_kv_prefill -> the same rows of k_out / v_out in OCP e4m3fn, and k_scale[row] / v_scale[row].  The scale is 2^e,
+ * e the smallest integer with amax(row) 2^-e <= 448 (at least -126; 0 for an all-zero row); q = round-to-nearest-even(x 2^-e).
+ * All four row buffers 16-byte aligned. */
+int acai_cross_kv_quantize_fp8(const void *k_in, const void *v_in, void *k_out, void *v_out, float *k_scale, float *v_scale,
+                               int64_t row0, int64_t nrows, int dhp, void *stream);
 
 /* hipGraph helpers (capture on `stream`, replay). */
 int acai_graph_begin(void *stream);
