@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int6
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "decode.hip", "resize.hip"]
+SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "decode.hip", "resize.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -98,6 +98,7 @@ _SIGNATURES = {
                                         c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "acai_grpo_objective_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                         c_void_p, c_void_p]),
+    "acai_edit_distance": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "acai_debug_stamps": (c_int, [c_void_p, c_int]),
     "acai_debug_lds_dma_oob": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "acai_pe_interp_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),

@@ -602,6 +602,56 @@ def grpo_objective_bwd(logits, rollouts, mask, stats, rowstat, grad_out, num_gro
                                                   _st(logits)), "acai_grpo_objective_bwd")
     return dl
 
+
+EDIT_DISTANCE_MAX_LEN = 4096
+
+
+def _seq_rows(t, lens, name):
+    """(rows with stride == width, int32 lengths) of one side of edit_distance; lens may be a bool prefix mask of t's shape (summed on the device,
+    not validated: no host sync)."""
+    _chk(t, name, torch.int64)
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected (rows, tokens), got {tuple(t.shape)}")
+    if t.shape[1] > EDIT_DISTANCE_MAX_LEN:
+        raise ValueError(f"{name}: rows of {t.shape[1]} tokens; edit_distance takes at most {EDIT_DISTANCE_MAX_LEN}")
+    _chk(lens, name + "_len")
+    if lens.dtype == torch.bool:
+        if lens.shape != t.shape:
+            raise ValueError(f"{name}_len: a mask must have {name}'s shape {tuple(t.shape)}, got {tuple(lens.shape)}")
+        lens = lens.sum(dim=-1, dtype=torch.int32)
+    elif lens.dtype != torch.int32:
+        raise TypeError(f"{name}_len: expected int32 lengths or a bool mask, got {lens.dtype}")
+    if lens.shape != (t.shape[0],):
+        raise ValueError(f"{name}_len: expected {t.shape[0]} lengths, got {tuple(lens.shape)}")
+    return (t if t.is_contiguous() else t.contiguous()), lens.contiguous()
+
+
+def edit_distance(pred, pred_len, tgt, tgt_len, group=1, out=None):
+    """Unit-cost Levenshtein distance of each pred[r, :pred_len[r]] to tgt[r // group, :tgt_len[r // group]] (acai_edit_distance): int32 (R,).
+    pred (R, Lp) and tgt (R // group, Lt) int64, Lp, Lt <= 4096 (ValueError beyond); the lengths are int32 vectors or bool prefix masks of the
+    padded shapes, read on the device (no host sync; positions past a length are never read).  With int32 lengths and `out` given, the call is one
+    kernel launch and nothing else, so it can be captured in a Graph."""
+    pred, pred_len = _seq_rows(pred, pred_len, "pred")
+    tgt, tgt_len = _seq_rows(tgt, tgt_len, "tgt")
+    R, group = pred.shape[0], int(group)
+    if group < 1 or tgt.shape[0] * group != R:
+        raise ValueError(f"edit_distance: {R} pred rows against {tgt.shape[0]} tgt rows with group {group}")
+    if out is None:
+        out = torch.empty(R, dtype=torch.int32, device=pred.device)
+    else:
+        _chk(out, "out", torch.int32)
+        if out.shape != (R,):
+            raise ValueError(f"out: expected ({R},), got {tuple(out.shape)}")
+    for t in (pred_len, tgt, tgt_len, out):
+        if t.device != pred.device:
+            raise RuntimeError(f"edit_distance: operands on different devices ({pred.device} and {t.device})")
+    if R == 0:
+        return out
+    _lib.check(_lib.lib().acai_edit_distance(pred.data_ptr(), pred.shape[1], pred_len.data_ptr(), tgt.data_ptr(), tgt.shape[1], tgt_len.data_ptr(),
+                                             R, group, out.data_ptr(), _st(pred)), "acai_edit_distance")
+    return out
+
+
 for _name, _fn in list(globals().items()):
     if callable(_fn) and not _name.startswith("_") and getattr(_fn, "__module__", None) == __name__ and not isinstance(_fn, type):
         globals()[_name] = _on_operand_device(_fn)

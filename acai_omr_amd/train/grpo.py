@@ -6,8 +6,11 @@ Same names and argument orders as the reference, so code written for omr_grpo_tr
     path, as elsewhere in the package.  An entropy term with p_c == 0 counts 0 where the reference gives NaN (only -inf logits produce it);
   * the policy forward runs on the UNEXPANDED image memory (OMRDecoder.forward(memory_group_size=G)): the reference's
     expand_img_latent_for_rollout copies it G times, and every layer projects each copy;
-  * rewards: the edit-distance terms (calc_edit_costs / reward_rollouts: TEDn through olimpic_app) are not ported - grpo_update takes a
-    `reward_fn` that returns the (B, G) raw rewards.  The tensor-only reward helpers are here."""
+  * rewards: grpo_update takes a `reward_fn` that returns the (B, G) raw rewards.  The tensor-only reward helpers are here, and so is a
+    reward that runs from the package alone: the TOKEN-level edit cost (calc_token_edit_costs: Levenshtein distance over LMX tokens, one HIP
+    launch on the rollouts where they lie, acai_edit_distance) stands in for the reference's tree edit cost in token_reward_rollouts /
+    make_token_reward_fn.  Still not ported: calc_edit_costs itself (TEDn on MusicXML trees through olimpic_app) and the well-formedness
+    counts, which need the LMX delinearizer."""
 from dataclasses import dataclass
 
 import torch
@@ -164,6 +167,39 @@ def calc_group_rewards(reward_config: RewardConfig, reward_components: RewardCom
     rewards = (rc.lambda_tedn * c.tedn_scores + rc.lambda_well_formed * c.wellformedness_scores + rc.lambda_f1 * c.f1_scores
                - rc.lambda_repeat * c.repeat_penalty - rc.lambda_len * c.len_penalty)
     return rewards.view(num_groups, group_size)
+
+
+# ---- a reward without the external tree-edit tool: token-level edit costs on the device ------------------------------------------------------
+def calc_token_edit_costs(rollouts, rollout_mask, target_lmx_seqs, pad_idx, group_size=1):
+    """Levenshtein distance over LMX tokens of each rollout (its rollout_mask positions, <bos> / <eos> included as they stand) to its target
+    (the non-pad entries, counted as calc_len_penalty counts them: targets are padded on the right), as float (R,).  target_lmx_seqs is either
+    the expanded (R, L) tensor grpo_update hands to reward_fn (group_size=1) or the unexpanded (B, L) one with group_size=G."""
+    target_lens = (target_lmx_seqs != pad_idx).sum(dim=-1, dtype=torch.int32)
+    return ops.edit_distance(rollouts, rollout_mask, target_lmx_seqs, target_lens, group=group_size).float()
+
+
+def token_reward_rollouts(reward_config: RewardConfig, rollouts, rollout_mask, target_lmx_seqs, num_groups, group_size, pad_idx):
+    """reward_rollouts (omr_grpo_train.py:227-237) with the token-level edit cost in the place of the tree edit cost:
+    tedn_scores = calc_tedn_scores(calc_token_edit_costs(...), alpha_tedn).  wellformedness_scores is a zeros tensor: the catastrophic / minor
+    error counts come from delinearizing the LMX string, and the delinearizer is not part of this package.  The other three components are the
+    reference's.  target_lmx_seqs: the expanded (B*G, L) targets.  Returns (raw_group_rewards (B, G), RewardComponents)."""
+    token_edit_costs = calc_token_edit_costs(rollouts, rollout_mask, target_lmx_seqs, pad_idx)
+    tedn_scores = calc_tedn_scores(token_edit_costs, alpha_t=reward_config.alpha_tedn)
+    wellformedness_scores = torch.zeros_like(tedn_scores)
+    f1_scores = calc_token_f1(rollouts, target_lmx_seqs, pad_idx)
+    repeat_penalty = calc_repeat_penalty(rollouts, pad_idx)
+    len_penalty = calc_len_penalty(rollout_mask, target_lmx_seqs, pad_idx, delta=reward_config.delta, tau=reward_config.tau)
+    reward_components = RewardComponents(tedn_scores, wellformedness_scores, f1_scores, repeat_penalty, len_penalty)
+    raw_group_rewards = calc_group_rewards(reward_config, reward_components, num_groups, group_size)
+    return raw_group_rewards, reward_components
+
+
+def make_token_reward_fn(reward_config: RewardConfig, pad_idx):
+    """A `reward_fn` for grpo_update built from token_reward_rollouts: the group shape is read off the batch and the expanded targets."""
+    def reward_fn(rollouts, rollout_mask, target_lmx_seqs, batch):
+        num_groups = len(batch)
+        return token_reward_rollouts(reward_config, rollouts, rollout_mask, target_lmx_seqs, num_groups, rollouts.shape[0] // num_groups, pad_idx)
+    return reward_fn
 
 
 # ---- objective and entropy (omr_grpo_train.py:240-283) through the fused op -------------------------------------------------------------

@@ -14,6 +14,7 @@ from dataclasses import dataclass
 import torch
 
 from ..config import LMX_BOS_TOKEN, LMX_EOS_TOKEN, MASK_RATIO, PATCH_SIZE, PE_MAX_HEIGHT, PE_MAX_WIDTH
+from ..config import MAX_LMX_SEQ_LEN
 from ..optim import FusedAdamW
 from ..utils import cosine_anneal_with_warmup
 
@@ -240,6 +241,27 @@ def fine_tune_validation(vitomr, dataloader, loss_fn, device):
             pred, target_seqs = vitomr.forward_eval(_on_device(batch, device))
             losses.append(loss_fn(pred, target_seqs).detach())
     return _mean_of(losses)
+
+
+def ser_validation(vitomr, dataloader, device, max_inference_len=MAX_LMX_SEQ_LEN, beam_width=1):
+    """Corpus symbol error rate of the decoded validation set (utils.symbol_error_rate): `inference()` per batch (greedy, or beam search with
+    beam_width > 1), token edit distances and target lengths accumulated on the device, one read at the end.  Targets are the batches' LMX
+    rows as the dataset yields them, so <bos> / <eos> count on both sides.  NaN when the loader holds no target tokens."""
+    from .. import ops
+    from ..inference.vitomr_inference import inference
+    from ..utils import _pad_targets
+    vitomr.eval()
+    dev_type = torch.device(device).type
+    dist_sum = torch.zeros((), dtype=torch.int64, device=device)
+    len_sum = torch.zeros((), dtype=torch.int64, device=device)
+    for batch in dataloader:
+        imgs, targets = zip(*[(ex[0], ex[1]) for ex in batch])
+        seqs, _, seq_mask = inference(vitomr, [img.to(device) for img in imgs], dev_type, max_inference_len=max_inference_len, beam_width=beam_width)
+        tgt, target_lens = _pad_targets(list(targets), None, seqs.device)
+        dist_sum += ops.edit_distance(seqs, seq_mask, tgt, target_lens).sum()
+        len_sum += target_lens.sum()
+    total = torch.stack([dist_sum, len_sum]).tolist()
+    return total[0] / total[1] if total[1] else float("nan")
 
 
 def save_omr_training_state(path, vitomr, optimizer, scheduler):

@@ -19,6 +19,36 @@ def stringify_lmx_seq(lmx_seq, idxs_to_tokens):
     return " ".join(toks[1:])
 
 
+def _pad_targets(target_lmx_seqs, pad_idx, device):
+    """(padded int64 (N, L) targets on `device`, int32 (N,) lengths) from a list of 1-D tensors, or from a padded tensor and its pad_idx."""
+    if isinstance(target_lmx_seqs, torch.Tensor):
+        if pad_idx is None:
+            raise ValueError("symbol_error_rate: a padded target tensor needs pad_idx")
+        tgt = target_lmx_seqs.to(device=device, dtype=torch.int64)
+        return tgt, (tgt != pad_idx).sum(dim=-1, dtype=torch.int32)
+    lens = [int(t.shape[0]) for t in target_lmx_seqs]
+    tgt = torch.zeros(len(lens), max(lens + [1]), dtype=torch.int64, device=device)
+    for i, t in enumerate(target_lmx_seqs):
+        tgt[i, :lens[i]] = t.to(device)
+    return tgt, torch.tensor(lens, dtype=torch.int32).to(device)
+
+
+def symbol_error_rate(seqs, seq_mask, target_lmx_seqs, pad_idx=None):
+    """Symbol error rate of decoded rows: Levenshtein distance over LMX tokens (ops.edit_distance, on the device) summed over the rows, divided
+    by the summed target lengths.  seqs / seq_mask (N, T): what inference(), continuous_inference() and beam search return.  Targets: a list of
+    N 1-D tensors, or a right-padded (N, L) tensor with its pad_idx (a row's length is its count of non-pad entries).
+    What is compared: seqs[i] at its seq_mask positions against target i, BOTH AS GIVEN - <bos> / <eos> count as symbols where present, so the
+    caller strips them from both sides or from neither.  Returns (ser as a Python float - the one host sync, at the end; NaN when every target
+    is empty -, distances int32 (N,), target_lens int32 (N,)); a zero-length target row contributes its row's length to the distances."""
+    from . import ops
+    tgt, target_lens = _pad_targets(target_lmx_seqs, pad_idx, seqs.device)
+    if tgt.shape[0] != seqs.shape[0]:
+        raise ValueError(f"symbol_error_rate: {seqs.shape[0]} decoded rows against {tgt.shape[0]} targets")
+    distances = ops.edit_distance(seqs, seq_mask, tgt, target_lens)
+    total = torch.stack([distances.sum(), target_lens.sum()]).tolist()
+    return (total[0] / total[1] if total[1] else float("nan")), distances, target_lens
+
+
 def stepwise_cosine_anneal_with_warmup(optimizer, warmup_steps, total_epochs, final_lr, num_steps_per_epoch):
     """Linear warm-up from 0.5 % of the base LR, then cosine annealing to final_lr, stepped per minibatch (utils.py:204-208)."""
     warmup = LinearLR(optimizer, start_factor=5e-3, end_factor=1.0, total_iters=warmup_steps)

@@ -209,6 +209,17 @@ int acai_grpo_objective_bwd(const void *logits, int dtype, const int64_t *rollou
                             const float *rowstat, const float *grad_out, int R, int T, int V, int num_groups, float logv, void *dlogits,
                             void *stream);
 
+/* Batched unit-cost Levenshtein distance (insert, delete, substitute cost 1 each) between ragged token rows in device memory (seqdist.hip): the
+ * token-level edit cost of the GRPO reward and the numerator of the symbol error rate.  pred [R][ld_pred] and tgt [R / group][ld_tgt] are int64
+ * rows (row stride = width = ld), pred_len [R] and tgt_len [R / group] int32.  Pair r compares pred[r][0 .. pred_len[r]) with
+ * tgt[r / group][0 .. tgt_len[r / group]): `group` consecutive rows of pred share one target row (G rollouts of one image), R % group == 0.
+ * out [R] int32 receives the distances.  The lengths are read ON THE DEVICE and clamped to [0, ld] there: no host synchronisation, no allocation,
+ * one kernel launch, capturable in a hipGraph.  Either length may be 0 (the distance is then the other length); positions past a row's length are
+ * never read.  ld_pred, ld_tgt <= 4096; a larger one is refused (-1).  Token ids are compared by their low 32 bits: exact for ids in [0, 2^31),
+ * no vocabulary size is assumed.  Integer arithmetic without atomics: results are the same on every run. */
+int acai_edit_distance(const int64_t *pred, int ld_pred, const int32_t *pred_len, const int64_t *tgt, int ld_tgt, const int32_t *tgt_len, int R,
+                       int group, int32_t *out, void *stream);
+
 /* Fused multi-tensor AdamW: one launch steps every parameter tensor (reference: torch.optim.AdamW in acai_omr/train/pre_train.py:105 and
  * omr_teacher_force_train.py:207 over the param groups of acai_omr/models/models.py:761-781; the cosine/warm-up schedule of
  * acai_omr/utils/utils.py:204-222 only changes `lr`).  All tables live in DEVICE memory.  tensors[i]: fp32 parameter, gradient and the two
