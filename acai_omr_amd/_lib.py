@@ -118,6 +118,8 @@ _SIGNATURES = {
     "acai_decode_sample_step": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_float, c_void_p]),
     "acai_decode_beam_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiBeam), c_void_p]),
     "acai_decode_slot_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p]),
+    "acai_decode_slot_sample_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p, c_int, c_void_p, c_int, c_float,
+                                             c_void_p]),
     "acai_decode_slot_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p, c_int, c_void_p]),
     "acai_decode_logits": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_void_p]),
     "acai_decode_hidden": (c_int, [POINTER(AcaiDecoder), c_void_p, c_void_p]),

@@ -1388,17 +1388,10 @@ __global__ __launch_bounds__(1024) void argmax_logprob_kernel(const float *logit
 // log_softmax(top_k_logits), M:1017).  torch.multinomial's Philox stream is not reproducible here; the draw is the inverse CDF of a caller
 // supplied uniform u[b][t] over the kept logits in descending order (ties: lower vocabulary index first), so a step is a pure function of
 // (logits, u) that the oracle restates.  One wave per row: k rounds of a wave-wide arg-max build the sorted top-k (k <= 64).
-__global__ __launch_bounds__(256) void sample_logprob_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
-                                                             const int32_t *step, int32_t *finished, int eos, int round_lp,
-                                                             const float *uniforms, int top_k, float inv_temperature, const float *emb,
-                                                             const float *pos, float *xnext, int E, int Tmax) {
-    __shared__ float sv[4][64];
-    __shared__ int si[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x * 4 + wave;
-    if (b >= B) return;
-    const int t = step[0];
-    const float *lg = logits + (size_t)b * V;
+// The per-row part, shared by the static and the slot sampler so that a sequence draws the same tokens in either: wave-wide, `sv` / `si` are
+// the wave's own 64 LDS entries.  Returns the drawn token; lp = log_softmax(kept)[drawn] (not rounded).
+__device__ __forceinline__ int topk_draw_row(const float *lg, int V, int lane, float *sv, int *si, int top_k, float inv_temperature, float u,
+                                             float &lp) {
     // lane owns vocabulary entries lane, lane + 64, ... (V <= 512)
     float v[8];
 #pragma unroll
@@ -1429,13 +1422,13 @@ __global__ __launch_bounds__(256) void sample_logprob_kernel(const float *logits
                 if (bi == lane + 64 * j) v[j] = -INFINITY;
         }
         if (lane == 0) {
-            sv[wave][r] = best;
-            si[wave][r] = bi;
+            sv[r] = best;
+            si[r] = bi;
         }
     }
     // same wave wrote and reads: LDS operations of a wave complete in order
     const bool in = lane < k;
-    const float x = in ? sv[wave][lane] : -INFINITY, m = sv[wave][0];
+    const float x = in ? sv[lane] : -INFINITY, m = sv[0];
     const float pT = in ? expf((x - m) * inv_temperature) : 0.f;   // softmax(top_k_logits / temperature), unnormalised
     const float p1 = in ? expf(x - m) : 0.f;                       // softmax(top_k_logits), unnormalised
     const float sumT = wave_sum(pT), sum1 = wave_sum(p1);
@@ -1445,11 +1438,26 @@ __global__ __launch_bounds__(256) void sample_logprob_kernel(const float *logits
         const float up = __shfl_up(cdf, o);
         if (lane >= o) cdf += up;
     }
-    const float target = uniforms[(size_t)b * max_len + t] * sumT;
+    const float target = u * sumT;
     const unsigned long long hit = __ballot(in && cdf > target);
     const int r = hit ? __builtin_ctzll(hit) : k - 1;              // rounding at the top of the CDF: last kept entry
-    const int tok = si[wave][r];
-    float lp = (sv[wave][r] - m) - logf(sum1);
+    lp = (sv[r] - m) - logf(sum1);
+    return si[r];
+}
+
+__global__ __launch_bounds__(256) void sample_logprob_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                             const int32_t *step, int32_t *finished, int eos, int round_lp,
+                                                             const float *uniforms, int top_k, float inv_temperature, const float *emb,
+                                                             const float *pos, float *xnext, int E, int Tmax) {
+    __shared__ float sv[4][64];
+    __shared__ int si[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + wave;
+    if (b >= B) return;
+    const int t = step[0];
+    float lp;
+    const int tok = topk_draw_row(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
+                                  uniforms[(size_t)b * max_len + t], lp);
     if (round_lp) lp = round_bf16(lp);
     if (lane == 0) {
         seqs[(size_t)b * max_len + t] = tok;
@@ -1521,6 +1529,64 @@ __global__ __launch_bounds__(1024) void slot_argmax_kernel(const float *logits, 
         finished[B] = tot;
         const int nxt = step[1] + 1;
         step[1] = nxt >= Tmax ? 0 : nxt;
+    }
+}
+
+// The sampling form of slot_argmax_kernel: the token of every unfinished row is topk_draw_row's at the row's local time t = slot_t[b], with
+// the uniform uniforms[urow[b]][t] of the sequence the slot decodes (urow is set when the slot is armed), so a sequence draws what it draws
+// alone in sample_logprob_kernel whichever slot and step it runs in.  One wave per row over gridDim.x workgroups of four (the k rounds of
+// a row are a serial chain: one workgroup for every row would put them end to end).  With more than one workgroup the unfinished count and
+// the ring index are written by the workgroup that arrives last at `ticket` (zero between launches, re-armed here): every workgroup
+// publishes its rows' flags with agent-scope atomic stores before it takes its ticket, and the last one reads all flags the same way.
+__global__ __launch_bounds__(256) void slot_sample_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                          int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap, int eos,
+                                                          int round_lp, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k,
+                                                          float inv_temperature, const float *emb, const float *pos, float *x, int E, int Tmax,
+                                                          unsigned *ticket) {
+    __shared__ float sv[4][64];
+    __shared__ int si[4][64];
+    __shared__ int is_last;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
+        if (finished[b]) continue;   // wave-uniform: a finished or idle row writes nothing
+        const int t = slot_t[b];
+        float lp;
+        const int tok = topk_draw_row(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
+                                      uniforms[(size_t)urow[b] * ld_uniforms + t], lp);
+        if (round_lp) lp = round_bf16(lp);
+        const bool fin = tok == eos || t >= slot_cap[b] - 1;
+        if (lane == 0) {
+            seqs[(size_t)b * max_len + t] = tok;
+            logprobs[(size_t)b * max_len + t] = lp;
+            if (fin) __hip_atomic_store(finished + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else slot_t[b] = t + 1;
+        }
+        if (!fin)   // t + 1 <= cap - 1 < max_len <= Tmax
+            for (int i = lane * 4; i < E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+    }
+    if (gridDim.x > 1) {
+        __threadfence();   // this thread's flag stores are visible device-wide before the workgroup's ticket
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned n = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            is_last = n == gridDim.x - 1;
+            if (is_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (gridDim.x > 1 && !is_last) return;
+    if (wave == 0) {
+        int cnt = 0;
+        for (int b = lane; b < B; b += 64) cnt += __hip_atomic_load(finished + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 1;
+        cnt = (int)wave_sum((float)cnt);
+        if (lane == 0) {
+            finished[B] = cnt;
+            const int nxt = step[1] + 1;
+            step[1] = nxt >= Tmax ? 0 : nxt;
+        }
     }
 }
 
@@ -2302,6 +2368,30 @@ extern "C" int acai_decode_slot_step(const AcaiDecoder *d, const AcaiSlots *sl, 
                        d->logprobs, d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos,
                        (d->flags & ACAI_GEMM_ROUND_BF16) ? 1 : 0, (const float *)d->emb, (const float *)d->pos, d->x, d->E, d->Tmax);
     ACAI_LAUNCH_CHECK("slot_argmax");
+    return 0;
+}
+
+extern "C" int acai_decode_slot_sample_step(const AcaiDecoder *d, const AcaiSlots *sl, const float *uniforms, int ld_uniforms,
+                                            const int32_t *urow, int top_k, float temperature, void *stream) {
+    int rc = check_slots(d, sl, "acai_decode_slot_sample_step");
+    if (rc) return rc;
+    ACAI_CHECK_ARG(uniforms, "acai_decode_slot_sample_step: null uniforms");
+    ACAI_CHECK_ARG(urow, "acai_decode_slot_sample_step: null urow");
+    ACAI_CHECK_ARG(ld_uniforms >= d->max_len, "acai_decode_slot_sample_step: ld_uniforms %d is below max_len %d", ld_uniforms, d->max_len);
+    ACAI_CHECK_ARG(top_k >= 1 && top_k <= 64, "acai_decode_slot_sample_step: top_k %d outside [1, 64]", top_k);
+    ACAI_CHECK_ARG(temperature > 0.f, "acai_decode_slot_sample_step: temperature must be > 0 (got %g)", (double)temperature);
+    ACAI_CHECK_ARG(d->V <= 512, "acai_decode_slot_sample_step: vocabulary %d above 512", d->V);
+    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_slot_sample_step: x does not hold this step's input embedding - call acai_decode_slot_arm "
+                                   "after setting up the slot state and after every acai_decode_logits / acai_decode_hidden");
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, false, true, nullptr, sl);
+    if (rc) return rc;
+    // one wave per row; without arrival counters (d->tickets) one workgroup takes every row and closes the step itself
+    hipLaunchKernelGGL(slot_sample_kernel, dim3(d->tickets ? cdiv(d->B, 4) : 1), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs,
+                       d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos, (d->flags & ACAI_GEMM_ROUND_BF16) ? 1 : 0,
+                       uniforms, ld_uniforms, urow, top_k, 1.0f / temperature, (const float *)d->emb, (const float *)d->pos, d->x, d->E, d->Tmax,
+                       (unsigned *)d->tickets);
+    ACAI_LAUNCH_CHECK("slot_sample");
     return 0;
 }
 

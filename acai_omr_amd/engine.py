@@ -276,14 +276,17 @@ class DecodeEngine:
         self.B = 0
         self.lens = None
         self.group = 1          # decode rows per stored cross K/V (GRPO rollout groups)
-        # what a decode step does: ("greedy",), ("sample", top_k, temperature), ("beam", K) or ("slot",) (continuous batching); a run sets
-        # it and restores greedy when it ends
+        # what a decode step does: ("greedy",), ("sample", top_k, temperature), ("beam", K), ("slot",) (continuous batching) or
+        # ("slot_sample", top_k, temperature) (continuous batching, sampled); a run sets it and restores greedy when it ends
         self._mode = ("greedy",)
         self.uniforms = None    # (Bmax, Tmax) uniforms of the sampling step, allocated on first use
         self.beam_anc = None    # beam-search lineage [2][Bmax][Tmax] (anc / tok / lp) and per-row cum / len, allocated on first use
         self._beam_done = 0
         self.slot_t = None      # slot state [Bmax] x 3 (local time, ring start, cap), allocated on first use
         self.slot_steps = 0     # decode steps of the last continuous-batching run (the ring index wrapped slot_steps // Tmax times)
+        self.slot_busy = 0      # busy slots summed over those steps (mean occupancy = slot_busy / slot_steps)
+        self.slot_urow = None   # sampled slot mode: [Bmax] int32 uniforms row of the sequence in each slot, and the (rows, Tmax) table
+        self.slot_uniforms = None
         self.cache_len = 0
         self._desc = None
         self._keep = None
@@ -565,7 +568,7 @@ class DecodeEngine:
         self.beam_len[:B].zero_()
 
     def arm(self, B):
-        if self._mode[0] == "slot":
+        if self._mode[0] in ("slot", "slot_sample"):
             self._slot_reset()
             return
         own = self.omr
@@ -592,6 +595,9 @@ class DecodeEngine:
             _lib.check(L.acai_decode_sample_step(d, self.uniforms.data_ptr(), mode[1], mode[2], st), "acai_decode_sample_step")
         elif mode[0] == "beam":
             _lib.check(L.acai_decode_beam_step(d, ctypes.byref(self._beam_desc), st), "acai_decode_beam_step")
+        elif mode[0] == "slot_sample":
+            _lib.check(L.acai_decode_slot_sample_step(d, ctypes.byref(self._slot_desc), self.slot_uniforms.data_ptr(), self.Tmax,
+                                                      self.slot_urow.data_ptr(), mode[1], mode[2], st), "acai_decode_slot_sample_step")
         else:
             _lib.check(L.acai_decode_slot_step(d, ctypes.byref(self._slot_desc), st), "acai_decode_slot_step")
 
@@ -664,25 +670,45 @@ class DecodeEngine:
         return self.seqs[:B, :max_len], self.logprobs[:B, :max_len], done
 
     # ---- continuous batching (an extension: the reference decodes one static batch) ----------------------------------------------------
-    def continuous(self, mem32, memb, lens, caps, slots, poll=16, use_graph=True):
-        """Greedy decode of len(lens) images through `slots` decode rows that are refilled as they finish.  mem32 / memb: the images'
-        packed memories (M, E) fp32 / bf16 copy, lens their lengths, caps[i] image i's cap (its row ends after token index caps[i] - 1, or
-        at <eos>).  Checks the arguments at the call, then returns a generator that yields each image's index once its tokens and
-        per-token log-probs are in `cont_seqs` / `cont_lps` (N, max(caps)), in completion order.  Every image decodes exactly as it would
-        alone in a greedy batch; only the step schedule is shared.  Slot s owns a cross K/V region of max(lens) rows; an idle slot has
-        cross length 1 and stays finished."""
+    def continuous(self, mem32, memb, lens, caps, slots, poll=16, use_graph=True, sample=None, uniforms=None, group=1):
+        """Decode of len(lens) images through `slots` decode rows that are refilled as they finish: greedy, or with sample=(top_k,
+        temperature) sampled as DecodeEngine.sample samples.  mem32 / memb: the images' packed memories (M, E) fp32 / bf16 copy, lens
+        their lengths, caps[i] image i's cap (its row ends after token index caps[i] - 1, or at <eos>).  Checks the arguments at the call,
+        then returns a generator that yields each image's index once its tokens and per-token log-probs are in `cont_seqs` / `cont_lps`
+        (N, max(caps)), in completion order.  Every image decodes exactly as it would alone in a greedy (sampled: a sampling) batch; only
+        the step schedule is shared.  Slot s owns a cross K/V region of max(lens) rows; an idle slot has cross length 1 and stays finished.
+        Sampled runs: sequence i draws token index t from uniforms[i, t] (`uniforms` (N, max(caps)) in [0, 1); from torch's generator on
+        the device when None), whichever slot and step it runs in; the mode is ("slot_sample", top_k, temperature), with graphs of its own.
+        group = G > 1 (sampled runs only): every memory is queued G times - sequences m*G .. m*G+G-1 decode memory m, caps and uniforms
+        are per sequence (N = len(lens) * G), and each admission prefills its own slot region."""
         S = int(slots)
         caps = [int(c) for c in caps]
         if max(caps) > self.Tmax:
             raise RuntimeError(f"{max(caps)} decoding steps is too long for max sequence length of {self.Tmax}")
         if not 1 <= S <= self.Bmax:
             raise ValueError(f"slots must be in [1, {self.Bmax}] (the cache's max batch size), got {slots}")
-        if len(caps) != len(lens):
-            raise ValueError(f"{len(caps)} caps for {len(lens)} images")
-        return self._continuous(mem32, memb, lens, caps, S, poll, use_graph)
+        G = int(group)
+        if G < 1 or (G > 1 and sample is None):
+            raise ValueError(f"group must be >= 1, and above 1 only in a sampled run (got {group})")
+        if len(caps) != len(lens) * G:
+            raise ValueError(f"{len(caps)} caps for {len(lens) * G} images")
+        mode = ("slot",)
+        if sample is not None:
+            top_k, temperature = int(sample[0]), float(sample[1])
+            if not 1 <= top_k <= 64 or not temperature > 0:
+                raise ValueError(f"sample=(top_k, temperature) needs 1 <= top_k <= 64 and temperature > 0, got {tuple(sample)}")
+            mode = ("slot_sample", top_k, temperature)
+            if uniforms is None:
+                uniforms = torch.rand(len(caps), max(caps), device=self.device)
+            if tuple(uniforms.shape) != (len(caps), max(caps)):
+                raise ValueError(f"uniforms must be (N, max(caps)) = ({len(caps)}, {max(caps)}), got {tuple(uniforms.shape)}")
+        elif uniforms is not None:
+            raise ValueError("uniforms are the draws of a sampled run: pass sample=(top_k, temperature) with them")
+        return self._continuous(mem32, memb, lens, caps, S, poll, use_graph, mode, uniforms, G)
 
-    def _continuous(self, mem32, memb, lens, caps, S, poll, use_graph):
-        N, dev, own = len(lens), self.device, self.omr
+    def _continuous(self, mem32, memb, lens, caps, S, poll, use_graph, mode=("slot",), uniforms=None, G=1):
+        N, dev, own = len(caps), self.device, self.omr
+        self._slot_group = G
         mem = memb if self.bf else mem32
         if mem is None:
             mem = ops.cast_bf16(mem32)
@@ -696,13 +722,15 @@ class DecodeEngine:
             offs.append(offs[-1] + l)
         cur = torch.cuda.current_stream(dev)
         self.stream.wait_stream(cur)
-        self.slot_steps = 0
+        self.slot_steps = self.slot_busy = 0
         harvested = torch.cuda.Event()
         try:
             with torch.cuda.stream(self.stream):
                 self._slot_setup(max(lens), S)
                 lens_dev = ops.h2d(torch.tensor(lens, dtype=torch.int32), dev)
-                self._mode = ("slot",)
+                if uniforms is not None:
+                    self._slot_uniforms(uniforms)
+                self._mode = mode
                 self._arm_and_capture(S, use_graph)
             if sched.skipped:
                 harvested.record(self.stream)
@@ -716,6 +744,7 @@ class DecodeEngine:
                 with torch.cuda.stream(self.stream):
                     fin = self.finished[:S].tolist()   # device -> host sync once per poll
                     self.slot_steps += n
+                    self.slot_busy += n * sum(i is not None for i in sched.image)
                     freed = sched.advance(n, fin)
                     for s, i in freed:   # harvest: device-side copies of the finished rows, before the refill re-arms them
                         c = caps[i]
@@ -760,6 +789,18 @@ class DecodeEngine:
                          for ly in self.blocks.layers]
         self._build_desc()
 
+    def _slot_uniforms(self, uniforms):
+        """The run's draws in the (rows, Tmax) table the sampled slot step reads, and the per-slot row index.  The table only grows; a
+        reallocation drops the sampled slot graphs (they hold its address), never the greedy ones."""
+        N, W = uniforms.shape
+        if self.slot_uniforms is None or self.slot_uniforms.shape[0] < N:
+            self.slot_uniforms = torch.zeros(N, self.Tmax, dtype=torch.float32, device=self.device)
+            for key in [k for k in self.graphs if k[4][0] == "slot_sample"]:
+                del self.graphs[key]
+        if self.slot_urow is None:
+            self.slot_urow = torch.zeros(self.Bmax, dtype=torch.int32, device=self.device)
+        self.slot_uniforms[:N, :W] = uniforms.to(device=self.device, dtype=torch.float32)
+
     def _slot_reset(self):
         """Every slot idle: finished, cross length 1, local time 1 at ring start 0; ring write index 0 (step[0] is unused in slot mode)."""
         S = self.B
@@ -782,7 +823,8 @@ class DecodeEngine:
         if not admitted:
             return
         H, dh, dhp = self.H, self.dh, self.cdhp
-        for s, i in admitted:
+        for s, seq in admitted:
+            i = seq // self._slot_group   # the memory this sequence decodes
             l = offs[i + 1] - offs[i]
             for li, (w, b) in enumerate(self._cross_w):
                 if self.cross_fp8:   # through the staging region at the slot's offset, then quantised into the slot's rows
@@ -795,8 +837,14 @@ class DecodeEngine:
                                          lens_dev[i:i + 1], self.k_cross[li], self.v_cross[li], H, dh, dhp, round_bf16=self.bf)
             self.cross_len[s:s + 1].copy_(lens_dev[i:i + 1])
             self._parked.discard(s)
-        rows = torch.tensor([[s for s, _ in admitted], [caps[i] for _, i in admitted]], dtype=torch.int32)
-        rows = ops.h2d(rows, self.device)
+        table = [[s for s, _ in admitted], [caps[i] for _, i in admitted]]
+        sampled = self._mode[0] == "slot_sample"
+        if sampled:
+            table.append([i for _, i in admitted])   # the slot's uniforms row: the sequence's own, whichever slot it lands in
+        rows = ops.h2d(torch.tensor(table, dtype=torch.int32), self.device)
+        if sampled:
+            for j, (s, _) in enumerate(admitted):
+                self.slot_urow[s:s + 1].copy_(rows[2, j:j + 1])
         _lib.check(_lib.lib().acai_decode_slot_arm(ctypes.byref(self._desc), ctypes.byref(self._slot_desc), rows.data_ptr(), len(admitted),
                                                    ops._st()), "acai_decode_slot_arm")
         self._keep_rows = rows   # (the arm kernel reads it asynchronously)

@@ -568,13 +568,14 @@ class ViTOMR(nn.Module):
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._beam_packed(mem32, None, lens, beam_width, max_len, length_penalty)
 
-    def _continuous_run(self, mem32, memb, lens, max_len, slots, poll, use_graph):
-        """(engine, caps, generator of finished image indices) of a continuous-batching run; argument errors are raised here, at the call."""
+    def _continuous_run(self, mem32, memb, lens, max_len, slots, poll, use_graph, **sampling):
+        """(engine, caps, generator of finished image indices) of a continuous-batching run; argument errors are raised here, at the call.
+        sampling: DecodeEngine.continuous's sample / uniforms / group."""
         blocks = self.decoder._cached_blocks()
-        caps = _continuous_caps(max_len, len(lens))
+        caps = _continuous_caps(max_len, len(lens) * sampling.get("group", 1))
         eng = blocks.engine((mem32 if mem32 is not None else memb).device)
         S = blocks.max_batch_size if slots is None else slots
-        return eng, caps, eng.continuous(mem32, memb, lens, caps, S, poll=poll, use_graph=use_graph)
+        return eng, caps, eng.continuous(mem32, memb, lens, caps, S, poll=poll, use_graph=use_graph, **sampling)
 
     def _continuous_packed_iter(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True):
         """Continuous-batching greedy decode of packed memories: yields (index, seqs (1,T'), log_probs (1,T'), mask (1,T')) per image in
@@ -596,8 +597,8 @@ class ViTOMR(nn.Module):
         n = int(seq_mask.sum(dim=-1).max())
         return seqs[:, :n], lps[:, :n], seq_mask[:, :n]
 
-    def _continuous_packed(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True):
-        eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph)
+    def _continuous_packed(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True, **sampling):
+        eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph, **sampling)
         for _ in run:
             pass
         return self._mask_and_clip_capped(eng.cont_seqs, eng.cont_lps, caps)
@@ -740,6 +741,24 @@ class GRPOViTOMR(ViTOMR):
         eng = blocks.engine(self.decoder.pos_embedding.device)
         seqs, lps, _ = eng.sample(max_actions, top_k, temperature, uniforms=uniforms)
         return self.mask_and_clip_seqs(seqs.clone(), lps.clone())
+
+    def cached_continuous_rollout_policy(self, img_latent, latent_attention_mask, max_actions=768, top_k=50, temperature=1.2, slots=None,
+                                         group_size=1, uniforms=None):
+        """Sampling rollouts through continuous batching (an extension: the reference samples one static batch) -> the triple of
+        cached_forward_rollout_policy, in input order, same dtypes and clipping.  `slots` decode rows (default: the cache's max batch size)
+        work through the rollouts; a row that draws <eos> or reaches its cap is refilled with the next queued rollout while the others go
+        on, so the number of rollouts may exceed the max batch size and a long rollout does not hold the finished ones' rows.  Rollout r draws
+        token index t from uniforms[r, t] (`uniforms` (R, max cap) in [0, 1); torch's generator when None) exactly as it would alone in
+        cached_forward_rollout_policy, whichever row and step it runs in.  max_actions: one cap, or a sequence of R per-rollout caps.
+
+        group_size = G > 1: img_latent holds the UNEXPANDED images and each is queued G times (rollouts i*G .. i*G+G-1 of the result, uniforms
+        rows likewise).  Every admission prefills its own row's region, so an image's cross K/V projection is repeated G times - unlike
+        cached_forward_rollout_policy(group_size=G), which stores it once per image."""
+        G = int(group_size)
+        if G < 1:
+            raise ValueError(f"group_size must be >= 1, got {group_size}")
+        mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
+        return self._continuous_packed(mem32, None, lens, max_actions, slots, sample=(top_k, temperature), uniforms=uniforms, group=G)
 
 
 class TeacherForcedViTOMR(ViTOMR):

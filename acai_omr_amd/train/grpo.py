@@ -10,7 +10,10 @@ Same names and argument orders as the reference, so code written for omr_grpo_tr
     reward that runs from the package alone: the TOKEN-level edit cost (calc_token_edit_costs: Levenshtein distance over LMX tokens, one HIP
     launch on the rollouts where they lie, acai_edit_distance) stands in for the reference's tree edit cost in token_reward_rollouts /
     make_token_reward_fn.  Still not ported: calc_edit_costs itself (TEDn on MusicXML trees through olimpic_app) and the well-formedness
-    counts, which need the LMX delinearizer."""
+    counts, which need the LMX delinearizer;
+  * rollouts may go through continuously refilled decode rows instead of one static batch (grpo_update(rollout_slots=...), and always in
+    validation_loop): the same draws per rollout, no B * G <= max batch size limit, and a rollout that never draws <eos> does not hold the
+    finished ones' rows to max_actions."""
 from dataclasses import dataclass
 
 import torch
@@ -254,11 +257,20 @@ def _rollouts_grouped(old_policy, img_latent, latent_attention_mask, group_size,
     return old_policy.mask_and_clip_seqs(seqs.clone(), lps.clone())
 
 
+def _rollouts_continuous(old_policy, img_latent, latent_attention_mask, group_size, rollout_config, uniforms, slots):
+    """The same rollouts through `slots` continuously refilled decode rows (GRPOViTOMR.cached_continuous_rollout_policy): B * G may exceed
+    the cache's max batch size, at the price of one cross K/V projection per rollout instead of one per image."""
+    return old_policy.cached_continuous_rollout_policy(img_latent, latent_attention_mask, rollout_config.max_actions, rollout_config.top_k,
+                                                       rollout_config.temperature, slots=slots, group_size=group_size, uniforms=uniforms)
+
+
 def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOConfig, ce_loss_fn, device, logger=None, counter=None, *, reward_fn,
-                uniforms=None):
+                uniforms=None, rollout_slots=None):
     """One GRPO minibatch update.  batch: list of (image, target_lmx_seq, target_musicxml_str).  reward_fn(rollouts, rollout_mask, target_lmx_seqs,
     batch) -> (B, G) raw rewards, or (rewards, RewardComponents).  uniforms (R, max_actions): the rollout draws (cached_forward_rollout_policy).
-    Returns (avg loss over update epochs, avg CE loss, avg raw reward, avg reward components or None)."""
+    rollout_slots: None = one static batch of B * G rollout rows (B * G <= the cache's max batch size); an integer = that many decode rows
+    refilled as rollouts finish, for any B * G.  Returns (avg loss over update epochs, avg CE loss, avg raw reward, avg reward components
+    or None)."""
     rollout_config, reward_config, loss_config, update_config = grpo_config.get_configs()
     dev_type = torch.device(device).type
     pad_idx = old_policy.decoder.pad_idx
@@ -271,8 +283,12 @@ def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOCon
     with torch.no_grad(), torch.autocast(device_type=dev_type, dtype=torch.bfloat16):
         unexpanded_img_latent, unexpanded_latent_attention_mask = old_policy.encoder(unexpanded_imgs)
         unexpanded_img_latent = old_policy.transition_head(unexpanded_img_latent)
-        rollouts, old_policy_log_probs, rollout_mask = _rollouts_grouped(old_policy, unexpanded_img_latent, unexpanded_latent_attention_mask,
-                                                                         group_size, rollout_config, uniforms)
+        if rollout_slots is None:
+            rollouts, old_policy_log_probs, rollout_mask = _rollouts_grouped(old_policy, unexpanded_img_latent, unexpanded_latent_attention_mask,
+                                                                             group_size, rollout_config, uniforms)
+        else:
+            rollouts, old_policy_log_probs, rollout_mask = _rollouts_continuous(old_policy, unexpanded_img_latent, unexpanded_latent_attention_mask,
+                                                                                group_size, rollout_config, uniforms, int(rollout_slots))
 
     target_lmx_seqs = expand_target_lmx_seqs(unexpanded_target_lmx_seqs, group_size, pad_idx, device)
     got = reward_fn(rollouts, rollout_mask, target_lmx_seqs, batch)
@@ -323,6 +339,48 @@ def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOCon
 
     avg_components = reward_components.avg_over_rollouts() if reward_components is not None else None
     return batch_overall_loss / update_epochs, batch_ce_loss / update_epochs, raw_group_rewards.mean().item(), avg_components
+
+
+# ---- validation (omr_grpo_train.py:456-492) -----------------------------------------------------------------------------------------------
+def validation_loop(dataloader, policy_theta, reward_config, rollout_config, ce_loss_fn, pad_idx, device, *, reward_fn=None, slots=None,
+                    uniforms_fn=None, autocast_dtype=torch.bfloat16):
+    """Mini or full validation, depending on the dataloader: one sampled rollout per image (group size 1) at rollout_config's max_actions /
+    top_k / temperature, scored by reward_fn, and the teacher-forced CE loss of each batch.  Returns (mean raw reward, mean RewardComponents,
+    mean CE loss), each a mean over batches of per-batch means, as the reference computes them.
+
+    The reference calls `policy_theta.forward_rollout_policy` here, a method it does not define (as in batch_policy_inference); the cached
+    policy is what it means.  The rollouts go through cached_continuous_rollout_policy with `slots` decode rows (default: the cache's max
+    batch size): a dataloader batch may be larger than the cache, and a rollout that never draws <eos> does not hold the others' rows to
+    max_actions.  reward_fn: as grpo_update's (default make_token_reward_fn(reward_config, pad_idx): the token-level edit cost in the place
+    of the reference's tree edit cost).  uniforms_fn(batch_index, R, max_actions) -> (R, max_actions) uniforms fixes the draws (default:
+    torch's generator).  autocast_dtype: the reference validates under bf16 autocast; None runs without autocast."""
+    if reward_fn is None:
+        reward_fn = make_token_reward_fn(reward_config, pad_idx)
+    dev_type = torch.device(device).type
+    num_batches = len(dataloader)
+    validation_reward = 0
+    validation_reward_components = RewardComponents(0, 0, 0, 0, 0)
+    validation_ce_loss = 0
+    group_size = 1
+    with torch.no_grad(), torch.autocast(device_type=dev_type, dtype=autocast_dtype or torch.bfloat16, enabled=autocast_dtype is not None):
+        for i, batch in enumerate(dataloader):
+            imgs, target_lmx_seqs, _ = zip(*batch)
+            imgs = [img.to(device, non_blocking=True) for img in imgs]
+            target_lmx_seqs = [t.to(device, non_blocking=True) for t in target_lmx_seqs]
+            img_latent, latent_attention_mask = policy_theta.encoder(imgs)
+            img_latent = policy_theta.transition_head(img_latent)
+            uniforms = uniforms_fn(i, len(imgs), rollout_config.max_actions) if uniforms_fn is not None else None
+            rollouts, _, rollout_mask = policy_theta.cached_continuous_rollout_policy(
+                img_latent, latent_attention_mask, rollout_config.max_actions, rollout_config.top_k, rollout_config.temperature, slots=slots,
+                group_size=group_size, uniforms=uniforms)
+            padded_targets = expand_target_lmx_seqs(target_lmx_seqs, group_size, pad_idx, device)
+            got = reward_fn(rollouts, rollout_mask, padded_targets, batch)
+            raw_rewards, reward_components = got if isinstance(got, tuple) else (got, None)
+            validation_reward += raw_rewards.float().mean().item()
+            if reward_components is not None:
+                validation_reward_components += reward_components.avg_over_rollouts()
+            validation_ce_loss += calc_teacher_forced_ce_loss(policy_theta, img_latent, latent_attention_mask, target_lmx_seqs, ce_loss_fn).item()
+    return validation_reward / num_batches, validation_reward_components / num_batches, validation_ce_loss / num_batches
 
 
 def refresh_old_policy(old_policy, policy_theta):

@@ -372,6 +372,18 @@ typedef struct {
  * acai_decode_step: x must hold the input of every unfinished row (acai_decode_slot_arm sets it; acai_decode_logits / acai_decode_hidden
  * clear it). */
 int acai_decode_slot_step(const AcaiDecoder *d, const AcaiSlots *sl, void *stream);
+/* One SLOT-MODE SAMPLING step: acai_decode_slot_step with acai_decode_sample_step's token choice.  The layers, the ring self attention,
+ * idle rows, finished[] / finished[B], t[] / cap[] and the next input are the greedy slot step's; for every unfinished row b at its LOCAL time
+ * t[b] the step keeps the top_k largest logits (ties: lower index first), draws by inverse CDF over softmax(kept / temperature) in
+ * descending order with u = uniforms[urow[b] * ld_uniforms + t[b]] and records log_softmax(kept)[drawn] (no temperature) at
+ * logprobs[b][t[b]].  uniforms: device fp32 table in [0, 1), ld_uniforms >= max_len floats per row; urow: device int32 [B], the table row
+ * of the sequence slot b decodes (the caller writes it when it arms the slot, ordered before the step; rows of idle slots are not read).
+ * The per-row arithmetic is the static sampler's own, so a sequence draws what it draws alone through acai_decode_sample_step with its
+ * table row.  Same checks and x contract as acai_decode_slot_step, plus 1 <= top_k <= 64, temperature > 0, V <= 512.  With dec->tickets
+ * the token choice runs one wave per row over ceil(B / 4) workgroups and uses tickets[0] (zero before, zero after) to close the step;
+ * without, one workgroup takes all rows.  Enqueues kernels only (capturable). */
+int acai_decode_slot_sample_step(const AcaiDecoder *d, const AcaiSlots *sl, const float *uniforms, int ld_uniforms, const int32_t *urow,
+                                 int top_k, float temperature, void *stream);
 /* Arms n rows for new sequences (n >= 0).  rows: device int32 [2][n] - rows[i] the decode row, rows[n + i] its cap (clamped to
  * [2, max_len]).  The caller has already set the row's cross_len and prefilled its cross K/V region (e.g. acai_cross_kv_prefill at the
  * row's cross_off), ordered before the next step.  Per row: seqs = <bos> then <pad>, logprobs = 0, finished = 0,
