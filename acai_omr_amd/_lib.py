@@ -7,11 +7,11 @@ without a GPU); the built .so is git-ignored but travels to the GPU box with the
 import ctypes
 import os
 import subprocess
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p, c_size_t
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p, c_size_t
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "decode.hip", "resize.hip"]
+SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "decode.hip", "resize.hip", "augment.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -57,6 +57,17 @@ class AcaiSlots(Structure):
     _fields_ = [(n, c_void_p) for n in ("t", "first", "cap")] + [("rows", c_int32), ("pad_", c_int32)]
 
 
+AUG_MAX_TAPS, AUG_MEAN_PARTS = 32, 128
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_BRIGHTNESS_FIRST = 1, 2, 4   # AcaiAugImage.jitter
+
+
+class AcaiAugImage(Structure):
+    _fields_ = [("src", c_void_p), ("buf", c_void_p * 2), ("noise", c_void_p), ("out", c_void_p), ("partials", c_void_p),
+                ("rot_cos", c_double), ("rot_sin", c_double), ("persp", c_double * 8)] + [
+        (n, c_int32) for n in ("H", "W", "apply", "jitter", "ktaps", "row0")] + [
+        (n, c_float) for n in ("noise_sigma", "fb", "fc", "pad_")] + [("w", c_float * AUG_MAX_TAPS)]
+
+
 _SIGNATURES = {
     "acai_version": (c_int, []),
     "acai_last_error": (c_char_p, []),
@@ -73,6 +84,9 @@ _SIGNATURES = {
     "acai_resize_bicubic_aa": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "acai_resize_to_patches": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_int, c_void_p]),
+    "acai_augment_blur_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "acai_augment_warp": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "acai_augment_jitter_out": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "acai_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "acai_attn_varlen_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_uint32, c_int, c_void_p]),

@@ -250,6 +250,60 @@ def resize_to_patches(img, size, P, out, row0, crop=None, clamp01=False):
     return n
 
 
+# ---- camera augmentation (csrc/augment.hip) ---------------------------------------------------------------------------------------------
+def augment_table(entries, device):
+    """A list of `_lib.AcaiAugImage` -> the read-only descriptor table in device memory (a uint8 tensor): the one upload of a call."""
+    import ctypes
+    if not entries:
+        raise ValueError("augment_table: no images")
+    arr = (_lib.AcaiAugImage * len(entries))(*entries)
+    host = torch.frombuffer(memoryview(arr).cast("B"), dtype=torch.uint8)
+    assert host.numel() == len(entries) * ctypes.sizeof(_lib.AcaiAugImage)
+    return host.to(device)
+
+
+def _aug_chk(table, n_images, max_h, max_w, slots):
+    import ctypes
+    _chk(table, "table", torch.uint8)
+    if table.dim() != 1 or not table.is_contiguous() or table.numel() != int(n_images) * ctypes.sizeof(_lib.AcaiAugImage):
+        raise ValueError(f"table: expected {n_images} AcaiAugImage descriptors ({ctypes.sizeof(_lib.AcaiAugImage)} bytes each) in one contiguous uint8 tensor")
+    if not (0 < int(n_images) <= 65535 and 0 < int(max_h) <= 65535 and int(max_w) > 0):
+        raise ValueError(f"augment: {n_images} images of at most {max_h} x {max_w}: images and rows are grid dimensions (1 .. 65535)")
+    if len(set(slots)) != len(slots) or any(s not in (-1, 0, 1) for s in slots) or any(s < 0 for s in slots[1:]):
+        raise ValueError(f"augment: slots {slots}: the input is -1 (the source), 0 or 1, every other slot 0 or 1, all different")
+
+
+def augment_blur_noise(table, n_images, max_h, max_w, in_slot, tmp_slot, out_slot, do_blur=True, do_noise=True):
+    """GaussianBlur (separable, reflect padding) and GaussianNoise + clamp over every applied image of the descriptor table:
+    in_slot -> tmp_slot -> out_slot; without blur the noise pass alone, in_slot -> out_slot."""
+    _aug_chk(table, n_images, max_h, max_w, (in_slot, tmp_slot, out_slot) if do_blur else (in_slot, out_slot))
+    _lib.check(_lib.lib().acai_augment_blur_noise(table.data_ptr(), int(n_images), int(max_h), int(max_w), int(in_slot), int(tmp_slot), int(out_slot),
+                                                  int(bool(do_blur)), int(bool(do_noise)), _st(table)), "acai_augment_blur_noise")
+
+
+def augment_warp(table, n_images, max_h, max_w, in_slot, out_slot, perspective):
+    """RandomRotation (perspective=False) or RandomPerspective (True) of every applied image: bilinear, zero fill, in_slot -> out_slot."""
+    _aug_chk(table, n_images, max_h, max_w, (in_slot, out_slot))
+    _lib.check(_lib.lib().acai_augment_warp(table.data_ptr(), int(n_images), int(max_h), int(max_w), int(in_slot), int(out_slot), int(bool(perspective)),
+                                            _st(table)), "acai_augment_warp")
+
+
+def augment_jitter_out(table, n_images, max_h, max_w, in_slot, do_jitter=True, patches=None, patch_size=0):
+    """ColorJitter (brightness / contrast with the order-fixed image mean) and the output stage: every image goes to its descriptor's `out`,
+    or, with `patches` [rows, P*P] (fp32 / bf16), to its nn.Unfold(P, P) rows from its descriptor's row0.  Images that are not applied are
+    copied from their source."""
+    _aug_chk(table, n_images, max_h, max_w, (in_slot,))
+    ld = P = dt = 0
+    if patches is not None:
+        _chk(patches, "patches")
+        P = int(patch_size)
+        if P <= 0 or patches.dim() != 2 or patches.shape[1] != P * P:
+            raise ValueError(f"patches: expected [rows, {P * P}] for patch size {P}, got {tuple(patches.shape)}")
+        ld, dt = _ld(patches), _dt(patches)
+    _lib.check(_lib.lib().acai_augment_jitter_out(table.data_ptr(), int(n_images), int(max_h), int(max_w), int(in_slot), int(bool(do_jitter)), _p(patches),
+                                                  ld, P, dt, _st(table)), "acai_augment_jitter_out")
+
+
 def gather_rows(table, idx, add=None, out=None):
     _chk(table, "table", torch.float32), _chk(idx, "idx", torch.int32)
     assert table.dim() == 2 and table.is_contiguous() and idx.dim() == 1 and idx.is_contiguous()

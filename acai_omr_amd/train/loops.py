@@ -41,6 +41,14 @@ def _on_device(batch, device):
     return [(x.to(device, non_blocking=True), y.to(device, non_blocking=True)) for x, y in batch]
 
 
+def _augmented(batch, augment):
+    """The batch with `augment` (a callable over a LIST of images, e.g. `augment.CameraAugment`: one call per batch) applied to the first
+    element of every pair - the MAE input or the fine-tune image; the second - the clean MAE target or the LMX row - passes through."""
+    if augment is None:
+        return batch
+    return [(a, y) for a, (_, y) in zip(augment([x for x, _ in batch]), batch)]
+
+
 def _mean_of(losses):
     """Average of the per-batch fp32 losses, summed in double in batch order (what `epoch_loss += loss.item()` accumulates)."""
     if not losses:
@@ -79,8 +87,10 @@ def _dp_mean_of(ddp, losses, device):
     return sum(v.cpu().tolist()) / len(losses)
 
 
-def pretrain_epoch(mae, dataloader, loss_fn, optimizer, scheduler, device, ddp=None):
+def pretrain_epoch(mae, dataloader, loss_fn, optimizer, scheduler, device, ddp=None, augment=None):
     """`pre_train.train_loop`: every batch is a full step; the scheduler moves once, after the last batch.
+    augment (optional, `augment.CameraAugment` or any callable over a list of images): applied on the device to the INPUT of every
+    (input, target) pair, the target stays clean (`PreTrainWrapper` with `transform=camera_augment`, pre_train.py:194).
     ddp (`dist.GradAllReduce` over `mae`, optional): `dataloader` yields this rank's shard of each global batch; the step is then the
     single-process global-batch step (global-count loss scaling, bucketed gradient SUM all-reduce overlapped with backward)."""
     mae.train()
@@ -88,7 +98,7 @@ def pretrain_epoch(mae, dataloader, loss_fn, optimizer, scheduler, device, ddp=N
     if ddp is not None:
         ddp.zero_grad()
     for batch in dataloader:
-        pred, loss_mask, target = mae(_on_device(batch, device))
+        pred, loss_mask, target = mae(_augmented(_on_device(batch, device), augment))
         loss = loss_fn(pred, loss_mask, target)
         if ddp is not None:
             loss = loss * _dp_scale(ddp, loss_mask.sum().item(), device)
@@ -184,10 +194,11 @@ def set_up_fine_tune_optimizer(vitomr, num_train_batches, epochs=FINE_TUNE["epoc
 
 
 def fine_tune_epoch(vitomr, dataloader, loss_fn, optimizer, scheduler, device, grad_accumulation_steps, tf_config, tf_scheduler, writer=None,
-                    counter=None, ddp=None):
+                    counter=None, ddp=None, augment=None):
     """`omr_teacher_force_train.train_loop`: bf16 autocast forward_train + CE per batch, gradients accumulate (losses are NOT divided by the
     accumulation count, as in the reference), optimizer / LR scheduler / TF scheduler / counter move every `grad_accumulation_steps` batches
     and on the last batch.
+    augment (optional, as in `pretrain_epoch`): applied on the device to the image of every (image, LMX row) example.
     ddp (`dist.GradAllReduce` over `vitomr`, optional): every batch is this rank's shard of a global micro-batch; micro-batches accumulate
     locally (`no_sync`) and the gradients are all-reduced once, by the backward of the micro-batch that precedes the optimizer step."""
     import contextlib
@@ -200,7 +211,7 @@ def fine_tune_epoch(vitomr, dataloader, loss_fn, optimizer, scheduler, device, g
     for i, batch in enumerate(dataloader):
         stepping = (i + 1) % grad_accumulation_steps == 0 or i + 1 == n
         with torch.autocast(device_type=dev_type, dtype=torch.bfloat16):
-            pred, target_seqs = vitomr.forward_train(_on_device(batch, device), tf_config.tf_prob, tf_config.tau, tf_config.use_hard_sampling)
+            pred, target_seqs = vitomr.forward_train(_augmented(_on_device(batch, device), augment), tf_config.tf_prob, tf_config.tau, tf_config.use_hard_sampling)
             loss = loss_fn(pred, target_seqs)
         if ddp is not None:
             loss = loss * _dp_scale(ddp, (target_seqs != loss_fn.pad_idx).sum().item(), device)

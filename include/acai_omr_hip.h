@@ -439,6 +439,53 @@ int acai_decode_attn_fp8(const float *q, int ldq, const void *kc, const void *vc
 int acai_cross_kv_quantize_fp8(const void *k_in, const void *v_in, void *k_out, void *v_out, float *k_scale, float *v_scale,
                                int64_t row0, int64_t nrows, int dhp, void *stream);
 
+/* ---- camera augmentation of the training input pipeline -------------------------------------------------------------------------------
+ * `v2.RandomApply([GaussianBlur(15, sigma), GaussianNoise(sigma), RandomRotation(degrees, BILINEAR), RandomPerspective(scale, p=1),
+ * ColorJitter(brightness, saturation, contrast, hue=0)], p=AUGMENTATION_P)` and the GrandStaff pair (perspective + jitter) of
+ * acai_omr/train/pre_train.py:178-190, omr_teacher_force_train.py:320-331, omr_grpo_train.py:530-541, on one-channel fp32 images in [0, 1].
+ * The three entry points below are batched over a RAGGED list of images through a read-only table of AcaiAugImage in device memory: one
+ * launch covers every image (grid z = image, blocks beyond an image's H x W leave at once), so the launches of a call do not grow with the
+ * number of images.  Slots: -1 = the image's `src`, 0 / 1 = its two H x W scratch buffers `buf`; a stage reads one slot and writes another.
+ * An image whose `apply` is 0 is skipped by every stage and copied from `src`, bit for bit, by the last one.  All random draws are made
+ * by the caller and arrive in the table. */
+#define ACAI_AUG_MAX_TAPS 32
+#define ACAI_AUG_MEAN_PARTS 128
+#define ACAI_AUG_BRIGHTNESS 1       /* AcaiAugImage.jitter: brightness is applied */
+#define ACAI_AUG_CONTRAST 2         /* contrast is applied */
+#define ACAI_AUG_BRIGHTNESS_FIRST 4 /* brightness before contrast (the only observable part of ColorJitter's random order) */
+typedef struct AcaiAugImage {
+    const float *src;    /* H x W input, never written */
+    float *buf[2];       /* H x W scratch each */
+    const float *noise;  /* H x W standard-normal draws (NULL: no noise and no clamp for this image) */
+    float *out;          /* H x W result of the image form (NULL in the patch form) */
+    double *partials;    /* ACAI_AUG_MEAN_PARTS partial sums of the contrast mean */
+    double rot_cos, rot_sin; /* cos / sin of the rotation angle */
+    double persp[8];     /* perspective coefficients c0 .. c7 */
+    int32_t H, W, apply, jitter;
+    int32_t ktaps, row0; /* blur taps (odd, <= ACAI_AUG_MAX_TAPS; 1 with w[0] = 1 is the identity); first patch row of the patch form */
+    float noise_sigma, fb, fc, pad_;
+    float w[ACAI_AUG_MAX_TAPS]; /* blur weights, softmax(-(x / sigma)^2) over linspace(-lim, lim, ktaps) */
+} AcaiAugImage;
+
+/* GaussianBlur + GaussianNoise: separable convolution with `w` over the image reflect-padded by ktaps / 2 (F.pad(mode="reflect"): H and W
+ * must exceed ktaps / 2), rows first (in_slot -> tmp_slot), then columns (tmp_slot -> out_slot), and with do_noise
+ * clamp(blurred + noise_sigma * noise, 0, 1) in the column pass.  do_blur = 0: the column pass alone, in_slot -> out_slot (ktaps must be 1). */
+int acai_augment_blur_noise(const AcaiAugImage *table, int n_images, int max_h, int max_w, int in_slot, int tmp_slot, int out_slot,
+                            int do_blur, int do_noise, void *stream);
+/* RandomRotation (perspective = 0) or RandomPerspective (perspective = 1), in_slot -> out_slot: F.grid_sample(bilinear, zeros,
+ * align_corners=False) of the image and of an all-ones mask, multiplied (torchvision's fill path with fill = 0).  Output pixel (x, y) samples
+ *   rotation:    (cos xc - sin yc + W/2 - 0.5, sin xc + cos yc + H/2 - 0.5), xc = x + 0.5 - W/2, yc = y + 0.5 - H/2
+ *   perspective: ((c0 X + c1 Y + c2) / d - 0.5, (c3 X + c4 Y + c5) / d - 0.5), X = x + 0.5, Y = y + 0.5, d = c6 X + c7 Y + 1
+ * with the coordinates evaluated in fp64 and the interpolation in fp32. */
+int acai_augment_warp(const AcaiAugImage *table, int n_images, int max_h, int max_w, int in_slot, int out_slot, int perspective, void *stream);
+/* ColorJitter on one channel + the output stage: brightness clamp(v fb, 0, 1), contrast clamp(fc v + (1 - fc) mean, 0, 1) with the mean
+ * of the whole image as it is when contrast is applied (partial sums in a fixed order, no atomics: bit-reproducible), in the order
+ * `jitter` gives; saturation does nothing on one channel.  do_jitter = 0: output only.  patches == NULL: every image is written to its `out`;
+ * otherwise its nn.Unfold(P, stride P) rows go to rows row0 .. of `patches` [rows][ld >= P*P] in out_dtype (fp32 / bf16) as
+ * acai_resize_to_patches orders them (H and W multiples of P). */
+int acai_augment_jitter_out(const AcaiAugImage *table, int n_images, int max_h, int max_w, int in_slot, int do_jitter, void *patches,
+                            int ld, int P, int out_dtype, void *stream);
+
 /* hipGraph helpers (capture on `stream`, replay). */
 int acai_graph_begin(void *stream);
 int acai_graph_end(void *stream, void **graph_exec_out);
