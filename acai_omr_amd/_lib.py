@@ -57,6 +57,10 @@ class AcaiSlots(Structure):
     _fields_ = [(n, c_void_p) for n in ("t", "first", "cap")] + [("rows", c_int32), ("pad_", c_int32)]
 
 
+class AcaiSpec(Structure):
+    _fields_ = [(n, c_int32) for n in ("D", "ngram", "pitch", "rows")] + [(n, c_void_p) for n in ("t", "cap", "steps", "tab", "next", "drafts")]
+
+
 AUG_MAX_TAPS, AUG_MEAN_PARTS = 32, 128
 AUG_BRIGHTNESS, AUG_CONTRAST, AUG_BRIGHTNESS_FIRST = 1, 2, 4   # AcaiAugImage.jitter
 
@@ -135,6 +139,8 @@ _SIGNATURES = {
     "acai_decode_slot_sample_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p, c_int, c_void_p, c_int, c_float,
                                              c_void_p]),
     "acai_decode_slot_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p, c_int, c_void_p]),
+    "acai_decode_spec_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), c_void_p]),
+    "acai_decode_spec_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), c_void_p]),
     "acai_decode_logits": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_void_p]),
     "acai_decode_hidden": (c_int, [POINTER(AcaiDecoder), c_void_p, c_void_p]),
     "acai_decode_merge_in_launch": (c_int, [c_int, c_int]),

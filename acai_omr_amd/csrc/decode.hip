@@ -768,12 +768,16 @@ struct DAttnArgs {
     // beam search (ANC instantiation only): key p of row b lives in cache row anc[b][p] of the parity copy (step[0] & 1) of the ancestor table.
     // Continuous batching (SLOT instantiation only): row b has seq_len[b] keys, key j at ring position (slot_first[b] + j) % Tmax.  The two
     // share a slot so that the struct - and with it every existing kernel's argument offsets - stays as it was.
+    // Speculative greedy decoding (SPEC instantiation only): the R = anc_bstride rows of image b / R share the image's key table
+    // spec_tab[b / R][anc_pitch]; entry p = 8 * (cache position) + (row of the image) holds key p; row b attends over seq_len[b / R] + b % R
+    // keys.  It rides the same slot, and anc_pitch / anc_bstride / seq_len, for the same reason.
     union {
         const int32_t *anc;  // [2][rows][anc_pitch]
         const int32_t *slot_first;
+        const int32_t *spec_tab;
     };
     int anc_pitch;
-    long long anc_bstride;   // elements between the two parity copies (rows * anc_pitch)
+    long long anc_bstride;   // elements between the two parity copies (rows * anc_pitch); SPEC: rows per image
     // FP8 memory cache (fp8e4m3_t instantiation only): one fp32 power-of-two scale per K row and per V row, at the row's element offset / dhp
     const float *k_scale, *v_scale;
 };
@@ -792,10 +796,15 @@ struct fp8e4m3_t {
 // TC = fp8e4m3_t (RAGGED only): the FP8 memory cache.  16 elements per 16-byte load, so LPK = dhp / 16 (4 lanes per key at d_h 64); the
 // key's K and V scales are requested with its bytes and fold in outside the element loops: s = (q . k8) sk scale_log2e, acc += (p sv) v8,
 // l += p.
-template <typename TC, int LPK, bool RAGGED, int U = 2, bool ANC = false, bool SLOT = false>
+// SPEC (self attention of a speculative verify step, !RAGGED only): the R rows of an image verify consecutive tokens of ONE sequence.  Row j
+// of image i attends over keys 0 .. t[i] - 1 + j; key p is found through the image's table entry (cache row of the image, cache position),
+// staged in LDS like the ancestor table.  The key loop runs over the logical index p exactly as the plain form's, so a row's sums are
+// ordered as the greedy step orders them.  Every index formed from a table entry is clamped into the image's rows and the cache.
+template <typename TC, int LPK, bool RAGGED, int U = 2, bool ANC = false, bool SLOT = false, bool SPEC = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
     static_assert(!(ANC && RAGGED), "the ancestor table indexes the self-attention cache");
     static_assert(!(SLOT && (RAGGED || ANC)), "the ring indexes the self-attention cache of the row itself");
+    static_assert(!(SPEC && (RAGGED || ANC || SLOT)), "the key table indexes the self-attention cache of the image's rows");
     constexpr bool F8 = sizeof(TC) == 1;
     static_assert(!F8 || RAGGED, "FP8 storage is the cross K/V's only");
     constexpr int EPC = 16 / sizeof(TC), KPW = 64 / LPK;
@@ -817,6 +826,11 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
         len = a.seq_len[b];
         hstride = a.Tmax * a.dhp;
         base = ((size_t)b * a.H + h) * hstride;
+    } else if constexpr (SPEC) {
+        const int R = (int)a.anc_bstride, img = b / R;
+        len = max(1, min(a.seq_len[img] + (b - img * R), min(a.anc_pitch, a.chunk * a.nsplit)));
+        hstride = a.Tmax * a.dhp;
+        base = ((size_t)img * R * a.H + h) * hstride;   // + (row of the image) * H * hstride per key
     } else {
         len = a.step[1] + 1;
         hstride = a.Tmax * a.dhp;
@@ -850,10 +864,22 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
         for (int p = c0 + tid; p < c1; p += 256) anc_s[p - c0] = ar[p];
         __syncthreads();
     }
+    if constexpr (SPEC) {
+        extern __shared__ int32_t anc_dyn[];
+        anc_s = anc_dyn;
+        const int32_t *tr = a.spec_tab + (size_t)(b / (int)a.anc_bstride) * a.anc_pitch;
+        for (int p = c0 + tid; p < c1; p += 256) anc_s[p - c0] = tr[p];
+        __syncthreads();
+    }
     [[maybe_unused]] int ring0 = 0;
     if constexpr (SLOT) ring0 = a.slot_first[b];
     auto key_off = [&](int key) -> size_t {
         if constexpr (ANC) return (size_t)anc_s[key - c0] * a.H * hstride + (size_t)key * a.dhp;
+        else if constexpr (SPEC) {
+            const unsigned e = (unsigned)anc_s[key - c0];
+            const int r = min((int)(e & 7u), (int)a.anc_bstride - 1), pos = min((int)(e >> 3), a.Tmax - 1);
+            return (size_t)r * a.H * hstride + (size_t)pos * a.dhp;
+        }
         else if constexpr (SLOT) {
             const int p = ring0 + key;   // ring0 < Tmax, key < seq_len[b] <= Tmax
             return (size_t)(p >= a.Tmax ? p - a.Tmax : p) * a.dhp;
@@ -1613,6 +1639,136 @@ __global__ __launch_bounds__(256) void slot_arm_kernel(const int32_t *rows, int 
     }
 }
 
+// ---- speculative greedy decoding (an extension: the reference emits one token per step) -------------------------------------------------
+// An image owns R = D + 1 consecutive decode rows.  Before a verify step, next[i][0] is the image's last emitted token (index t - 1) and
+// next[i][1..D] the draft tokens for indices t .. t + D - 1 (-1 = none); row j consumed next[i][j] at position t + j (quirk Q1) and its
+// logits predict index t + j.  One workgroup closes the step (and, with arm set, opens the run):
+//   1. wave w: the greedy token and log-prob of rows w, w + nw, ... (argmax_logprob_kernel's reduction) into LDS;
+//   2. wave w: images w, w + nw, ...: accept - g_0, then g_j while draft j equals g_{j-1} - written at t .. t + n, cut at the first <eos>
+//      and at cap - 1; t, finished[i], steps[i];
+//   3. the same wave drafts the next step: from the injected table drafts[i][index] when given, else by prompt lookup - for m = ngram .. 1
+//      the most recent earlier occurrence of the sequence's last m tokens, the first m that has one proposes the up to D tokens after it -
+//      and writes next[i][], the table entries of indices t - 1 .. t - 1 + D (row j at the NEXT write index) and every row's input x;
+//   4. thread 0: the unfinished count finished[B] and the shared write index step[1].
+// Every loop is bounded by cap <= max_len or by B.
+struct SpecArgs {
+    const float *logits;
+    int V, B, R, E, Tmax, ld, eos, pad, round_lp, ngram, arm, pitch;
+    int64_t *seqs;
+    float *logprobs;
+    int32_t *step, *finished;
+    const float *emb, *pos;
+    float *x;
+    int32_t *t, *steps, *tab, *next;
+    const int32_t *cap, *drafts;
+};
+
+__global__ __launch_bounds__(1024) void spec_accept_kernel(SpecArgs a) {
+    extern __shared__ int spec_dyn[];   // [B] greedy tokens, [B] their log-probs
+    __shared__ int unfinished[16];
+    int *g_tok = spec_dyn;
+    float *g_lp = reinterpret_cast<float *>(spec_dyn + a.B);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int R = a.R, nimg = a.B / R;
+    if (!a.arm)
+        for (int b = wave; b < a.B; b += nw) {
+            float best;
+            int bi;
+            const float se = row_argmax_sumexp(a.logits + (size_t)b * a.V, a.V, lane, best, bi);
+            float lp = -logf(se);
+            if (a.round_lp) lp = round_bf16(lp);
+            if (lane == 0) {
+                g_tok[b] = bi;
+                g_lp[b] = lp;
+            }
+        }
+    __syncthreads();
+    const int wnext = min(a.step[1] + (a.arm ? 0 : 1), a.Tmax - 1);   // the cache position the next step's rows write
+    int cnt = 0;
+    for (int img = wave; img < nimg; img += nw) {
+        int64_t *sq = a.seqs + (size_t)img * a.ld;
+        float *lq = a.logprobs + (size_t)img * a.ld;
+        int32_t *nx = a.next + (size_t)img * 8;
+        const int cap = min(a.cap[img], min(a.ld, a.pitch));
+        int t = a.t[img], fin = a.finished[img];
+        if (t < 1 || t >= cap) fin = 1;   // (an armed, unfinished image has 1 <= t <= cap - 1)
+        if (!a.arm && !fin) {
+            int n = 0;
+            for (int j = 0; j < R; ++j) {   // wave-uniform
+                if (j > 0 && nx[j] != g_tok[img * R + j - 1]) break;   // draft j was wrong (or none): row j saw another sequence
+                if (t + j >= cap) break;
+                const int tok = g_tok[img * R + j];
+                if (lane == 0) {
+                    sq[t + j] = tok;
+                    lq[t + j] = g_lp[img * R + j];
+                }
+                n = j + 1;
+                if (tok == a.eos) {
+                    fin = 1;
+                    break;
+                }
+            }
+            t += n;
+            if (t >= cap) fin = 1;
+            if (lane == 0) {
+                a.t[img] = t;
+                a.steps[img] += 1;
+            }
+            __threadfence();   // lane 0's tokens are read back by every lane of this wave below
+        }
+        if (lane == 0) a.finished[img] = fin;
+        if (fin) continue;
+        cnt += 1;
+        // the next step's inputs: lane j < R holds the token row j consumes (index t - 1 + j), -1 = none
+        int mine = -1;
+        if (a.drafts) {
+            const int idx = t - 1 + lane;
+            if (lane >= 1 && lane < R && t + lane < cap) {   // (a row whose prediction index would reach cap is idle)
+                const int v = a.drafts[(size_t)img * a.pitch + idx];
+                mine = (v >= 0 && v < a.V) ? v : -1;
+            }
+        } else {
+            int e_found = -1;
+            for (int m = min(a.ngram, t - 1); m >= 1 && e_found < 0; --m)
+                for (int base = t - 1; base >= m; base -= 64) {   // candidate ends e (exclusive) from the most recent down
+                    const int e = base - lane;
+                    bool ok = e >= m;
+                    if (ok)
+                        for (int i = 0; i < m; ++i)
+                            if (sq[e - m + i] != sq[t - m + i]) {
+                                ok = false;
+                                break;
+                            }
+                    const unsigned long long hit = __ballot(ok);
+                    if (hit) {
+                        e_found = base - __builtin_ctzll(hit);
+                        break;
+                    }
+                }
+            if (e_found >= 0 && lane >= 1 && lane < R && e_found + lane - 1 < t && t + lane < cap) mine = (int)sq[e_found + lane - 1];
+        }
+        if (lane == 0) mine = (int)sq[t - 1];
+        if (lane < R) {
+            nx[lane] = mine;
+            const int idx = t - 1 + lane;
+            if (idx < a.pitch) a.tab[(size_t)img * a.pitch + idx] = wnext * 8 + lane;
+        }
+        for (int j = 0; j < R; ++j) {
+            const int tk = __shfl(mine, j), tok = tk < 0 ? a.pad : tk, p = min(t + j, a.Tmax - 1);
+            float *xr = a.x + (size_t)(img * R + j) * a.E;
+            for (int i = lane; i < a.E; i += 64) xr[i] = a.emb[(size_t)tok * a.E + i] + a.pos[(size_t)p * a.E + i];
+        }
+    }
+    if (lane == 0) unfinished[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < nw; ++w) tot += unfinished[w];
+        a.finished[a.B] = tot;
+        if (!a.arm) a.step[1] = min(a.step[1] + 1, a.Tmax - 1);
+    }
+}
+
 // ---- beam search (an extension: the reference decodes greedily) ------------------------------------------------------------------------
 constexpr int BEAM_MAX = 16;
 
@@ -1807,6 +1963,24 @@ int launch_dattn(const DAttnArgs &a, int B, hipStream_t st) {
     return 0;
 }
 
+// self attention of a speculative verify step (decode_attn_kernel's SPEC instantiation): the key table is staged in LDS, chunk ints
+template <typename TC>
+int launch_dattn_spec(const DAttnArgs &a, int B, hipStream_t st) {
+    const int lpk = a.dhp * (int)sizeof(TC) / 16;
+    dim3 grid(a.nsplit, a.H, B);
+    const size_t lds = sizeof(int32_t) * a.chunk;
+    switch (lpk) {
+        case 1: hipLaunchKernelGGL((decode_attn_kernel<TC, 1, false, 2, false, false, true>), grid, dim3(256), lds, st, a); break;
+        case 2: hipLaunchKernelGGL((decode_attn_kernel<TC, 2, false, 2, false, false, true>), grid, dim3(256), lds, st, a); break;
+        case 4: hipLaunchKernelGGL((decode_attn_kernel<TC, 4, false, 2, false, false, true>), grid, dim3(256), lds, st, a); break;
+        case 8: hipLaunchKernelGGL((decode_attn_kernel<TC, 8, false, 2, false, false, true>), grid, dim3(256), lds, st, a); break;
+        case 16: hipLaunchKernelGGL((decode_attn_kernel<TC, 16, false, 2, false, false, true>), grid, dim3(256), lds, st, a); break;
+        default: return acai_set_err(-1, "decode_attn: dhp=%d unsupported", a.dhp);
+    }
+    ACAI_LAUNCH_CHECK("decode_attn_spec");
+    return 0;
+}
+
 // The in-launch merge of the split partials (decode_attn_kernel: write-through stores, one agent-scope ticket per (sequence, head), the last
 // arriver loads every partial) is a hand-off MEASURED on gfx950 / ROCm 7.2 with this kernel at TWO resident workgroups per CU - not an
 // architectural guarantee (MI355X_MICROARCH.md, "Valid forms").  If a toolchain change moves the kernel's register count so that the residency
@@ -1908,7 +2082,7 @@ int check_decoder(const AcaiDecoder *d) {
 
 template <typename TW>
 int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, bool do_embed = true, bool do_unembed = true,
-                const AcaiBeam *beam = nullptr, const AcaiSlots *slots = nullptr) {
+                const AcaiBeam *beam = nullptr, const AcaiSlots *slots = nullptr, const AcaiSpec *spec = nullptr) {
     const int B = d->B, E = d->E, H = d->H, F = d->F;
     const int rnd = (d->flags & ACAI_GEMM_ROUND_BF16) ? ACAI_GEMM_ROUND_BF16 : 0;
     const float sc = 1.4426950408889634f / sqrtf((float)d->dh);
@@ -1979,20 +2153,26 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
             if (slots) {   // slot step: per-row lengths over the ring (decode_attn_kernel's SLOT instantiation)
                 a.seq_len = slots->t; a.slot_first = slots->first;
             }
+            if (spec) {   // verify step: keys through the image's table, t + j of them for row j (decode_attn_kernel's SPEC instantiation)
+                a.seq_len = spec->t; a.spec_tab = spec->tab; a.anc_pitch = spec->pitch; a.anc_bstride = spec->D + 1;
+            }
         }
+        const bool spec_self = spec && !cross;
+        auto per_row = [&]() { return spec_self ? launch_dattn_spec<TW>(a, B, st) : launch_dattn<TW>(a, B, st); };
         // rollout groups (bf16, d_h padded to 64): one K/V stream per image through the matrix-core kernel; otherwise the rows simply alias
         // the stored K/V through the per-row kernel (ACAI_DECODE_GROUP_KERNEL=0 forces that form: A/B aid)
         static const bool no_group = getenv("ACAI_DECODE_GROUP_KERNEL") && atoi(getenv("ACAI_DECODE_GROUP_KERNEL")) == 0;
-        const int group = (!no_group && sizeof(TW) == 2 && d->dhp == 64 && cross && d->cross_group > 1 && B % d->cross_group == 0) ? d->cross_group : 1;
+        // (a verify step keeps the per-row kernel: the matrix-core form orders a row's sums differently from the greedy step's)
+        const int group = (!no_group && !spec && sizeof(TW) == 2 && d->dhp == 64 && cross && d->cross_group > 1 && B % d->cross_group == 0) ? d->cross_group : 1;
         if (a.nsplit == 1) {
             a.out = d->attn; a.ldo = E; a.round_out = rnd ? 1 : 0;
-            return group > 1 ? launch_dattn_group(a, B, group, st) : launch_dattn<TW>(a, B, st);
+            return group > 1 ? launch_dattn_group(a, B, group, st) : per_row();
         }
         if (d->tickets && (group > 1 || dattn_merge_validated<TW>(d->dhp))) {
             a.out = d->attn; a.ldo = E; a.round_out = rnd ? 1 : 0; a.tickets = d->tickets;
-            return group > 1 ? launch_dattn_group(a, B, group, st) : launch_dattn<TW>(a, B, st);
+            return group > 1 ? launch_dattn_group(a, B, group, st) : per_row();
         }
-        int r = launch_dattn<TW>(a, B, st);
+        int r = per_row();
         if (r) return r;
         hipLaunchKernelGGL(attn_combine_kernel, dim3(H, B), dim3(64), 0, st, d->partial, d->attn, E, H, d->dh, d->dhp, a.nsplit, rnd ? 1 : 0);
         ACAI_LAUNCH_CHECK("attn_combine");
@@ -2062,9 +2242,9 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
 
 // decode_core in the descriptor's weight dtype
 int decode(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, bool do_embed = true, bool do_unembed = true,
-           const AcaiBeam *beam = nullptr, const AcaiSlots *slots = nullptr) {
-    return d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, tokens, st, do_embed, do_unembed, beam, slots)
-                                 : decode_core<float>(d, tokens, st, do_embed, do_unembed, beam, slots);
+           const AcaiBeam *beam = nullptr, const AcaiSlots *slots = nullptr, const AcaiSpec *spec = nullptr) {
+    return d->dtype == ACAI_BF16 ? decode_core<bf16_t>(d, tokens, st, do_embed, do_unembed, beam, slots, spec)
+                                 : decode_core<float>(d, tokens, st, do_embed, do_unembed, beam, slots, spec);
 }
 
 // ---- FP8 memory cache: bf16 cross K/V rows -> e4m3fn rows + one power-of-two scale per row -------------------------------------------
@@ -2393,6 +2573,56 @@ extern "C" int acai_decode_slot_sample_step(const AcaiDecoder *d, const AcaiSlot
                        (unsigned *)d->tickets);
     ACAI_LAUNCH_CHECK("slot_sample");
     return 0;
+}
+
+// Prologue of the speculative entry points: the operands, the sequence state, the row layout (R = D + 1 rows per image sharing its cross
+// K/V) and the speculative state.
+static int check_spec(const AcaiDecoder *d, const AcaiSpec *sp, const char *fn) {
+    int rc = check_unembed(d, fn);
+    if (rc) return rc;
+    ACAI_CHECK_ARG(d->seqs && d->logprobs && d->finished && d->max_len > 1 && d->max_len <= d->Tmax, "%s: null sequence state or max_len "
+                   "outside [2, Tmax] (max_len=%d Tmax=%d)", fn, d->max_len, d->Tmax);
+    ACAI_CHECK_ARG(sp && sp->t && sp->cap && sp->steps && sp->tab && sp->next, "%s: null speculative state", fn);
+    ACAI_CHECK_ARG(sp->D >= 1 && sp->D <= 7, "%s: draft length %d outside [1, 7]", fn, sp->D);
+    ACAI_CHECK_ARG(d->B % (sp->D + 1) == 0 && d->cross_group == sp->D + 1, "%s: needs B %% (D + 1) == 0 and cross_group == D + 1 (B=%d D=%d "
+                   "cross_group=%d)", fn, d->B, sp->D, d->cross_group);
+    ACAI_CHECK_ARG(!(d->flags & ACAI_DEC_CROSS_FP8), "%s: an FP8 cross K/V is not supported", fn);
+    ACAI_CHECK_ARG(sp->rows >= d->B / (sp->D + 1) && sp->pitch >= d->max_len && sp->pitch <= d->Tmax, "%s: needs rows >= B / (D + 1) and "
+                   "max_len <= pitch <= Tmax (rows=%d pitch=%d)", fn, sp->rows, sp->pitch);
+    ACAI_CHECK_ARG(sp->drafts || (sp->ngram >= 1 && sp->ngram <= 8), "%s: without a drafts table ngram must be in [1, 8] (got %d)", fn, sp->ngram);
+    ACAI_CHECK_ARG(d->self_chunk <= 16384, "%s: self_chunk %d above 16384", fn, d->self_chunk);
+    return 0;
+}
+
+static int launch_spec_accept(const AcaiDecoder *d, const AcaiSpec *sp, int arm, hipStream_t st) {
+    SpecArgs a{};
+    a.logits = d->logits; a.V = d->V; a.B = d->B; a.R = sp->D + 1; a.E = d->E; a.Tmax = d->Tmax; a.ld = d->max_len; a.eos = d->eos; a.pad = d->pad;
+    a.round_lp = (d->flags & ACAI_GEMM_ROUND_BF16) ? 1 : 0; a.ngram = sp->ngram; a.arm = arm; a.pitch = sp->pitch;
+    a.seqs = d->seqs; a.logprobs = d->logprobs; a.step = d->step; a.finished = d->finished; a.emb = d->emb; a.pos = d->pos; a.x = d->x;
+    a.t = sp->t; a.steps = sp->steps; a.tab = sp->tab; a.next = sp->next; a.cap = sp->cap; a.drafts = sp->drafts;
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(d->B > 8 ? 1024 : (d->B > 4 ? 512 : 256)), sizeof(int) * 2 * (size_t)d->B, st, a);
+    ACAI_LAUNCH_CHECK("spec_accept");
+    return 0;
+}
+
+extern "C" int acai_decode_spec_arm(const AcaiDecoder *d, const AcaiSpec *sp, void *stream) {
+    int rc = check_spec(d, sp, "acai_decode_spec_arm");
+    if (rc) return rc;
+    rc = launch_spec_accept(d, sp, 1, (hipStream_t)stream);
+    if (rc) return rc;
+    x_valid_set(d, true);
+    return 0;
+}
+
+extern "C" int acai_decode_spec_step(const AcaiDecoder *d, const AcaiSpec *sp, void *stream) {
+    int rc = check_spec(d, sp, "acai_decode_spec_step");
+    if (rc) return rc;
+    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_spec_step: x does not hold this step's input embedding - call acai_decode_spec_arm after "
+                                   "setting up the speculative state and after every acai_decode_logits / acai_decode_hidden");
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, false, true, nullptr, nullptr, sp);
+    if (rc) return rc;
+    return launch_spec_accept(d, sp, 0, st);
 }
 
 extern "C" int acai_decode_logits(const AcaiDecoder *d, const int64_t *tokens, int time_step, void *stream) {

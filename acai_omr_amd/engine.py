@@ -276,8 +276,9 @@ class DecodeEngine:
         self.B = 0
         self.lens = None
         self.group = 1          # decode rows per stored cross K/V (GRPO rollout groups)
-        # what a decode step does: ("greedy",), ("sample", top_k, temperature), ("beam", K), ("slot",) (continuous batching) or
-        # ("slot_sample", top_k, temperature) (continuous batching, sampled); a run sets it and restores greedy when it ends
+        # what a decode step does: ("greedy",), ("sample", top_k, temperature), ("beam", K), ("slot",) (continuous batching),
+        # ("slot_sample", top_k, temperature) (continuous batching, sampled) or ("spec", D, ngram) (speculative greedy; ngram 0 = drafts from
+        # the injected table); a run sets it and restores greedy when it ends
         self._mode = ("greedy",)
         self.uniforms = None    # (Bmax, Tmax) uniforms of the sampling step, allocated on first use
         self.beam_anc = None    # beam-search lineage [2][Bmax][Tmax] (anc / tok / lp) and per-row cum / len, allocated on first use
@@ -287,15 +288,19 @@ class DecodeEngine:
         self.slot_busy = 0      # busy slots summed over those steps (mean occupancy = slot_busy / slot_steps)
         self.slot_urow = None   # sampled slot mode: [Bmax] int32 uniforms row of the sequence in each slot, and the (rows, Tmax) table
         self.slot_uniforms = None
+        self.spec_t = None      # speculative decoding: per-image state (t, cap, steps, key table, next inputs, injected drafts), allocated on first use
+        self._per_row_cross = False
         self.cache_len = 0
         self._desc = None
         self._keep = None
 
     # ---- cross K/V prefill (MemoryCache.cache_memory_keys_and_vals, kv_caching.py:235-253) -----------------------------
-    def prepare(self, mem32, memb, lens, group_size=1):
+    def prepare(self, mem32, memb, lens, group_size=1, per_row_cross=False):
         """mem32 / memb: packed memory (M, E) fp32 / bf16 copy; lens: per-memory lengths.  group_size > 1: every memory serves `group_size`
         consecutive decode rows (the rollouts of one image, models.py:883-891) - its cross K/V is projected and stored ONCE and the rows'
-        offsets alias it, instead of the reference's group_size materialised copies."""
+        offsets alias it, instead of the reference's group_size materialised copies.  per_row_cross (speculative decoding): the rows of a
+        group go through the per-row cross-attention kernel at the split an ungrouped batch of these memories gets, so that every row's
+        arithmetic is the plain greedy step's."""
         G = int(group_size)
         B = len(lens) * G
         self._mode = ("greedy",)
@@ -305,7 +310,8 @@ class DecodeEngine:
             raise ValueError("an FP8 memory cache does not support grouped cross K/V (group_size > 1: beam search, grouped GRPO rollouts); "
                              "use memory_cache_dtype=None")
         E, H, dhp, dev = self.E, self.H, self.cdhp, self.device
-        self._size_cross(sum(lens) * H * dhp, B, lens, G)
+        self._size_cross(sum(lens) * H * dhp, B, lens, 1 if per_row_cross else G)
+        self._per_row_cross = bool(per_row_cross)
         offs, o = [], 0
         for l in lens:
             offs.append(o)
@@ -550,6 +556,65 @@ class DecodeEngine:
             rows = torch.arange(n, device=self.device) * K + torch.argmax(score, dim=1)   # first maximum: the lower slot on ties
             return seqs.index_select(0, rows), lps.index_select(0, rows), cum.index_select(0, rows)
 
+    # ---- speculative greedy decoding (an extension: the reference emits one token per step) ------------------------------------------------
+    def speculative(self, max_len, draft_len, ngram=3, drafts=None, poll=16, use_graph=True, on_chunk=None):
+        """Greedy decoding that emits up to draft_len + 1 tokens per step, over the B / R images prepared with group_size = R = draft_len + 1
+        and per_row_cross=True (rows i*R .. i*R+R-1 verify consecutive tokens of image i): up to max_len-1 steps of acai_decode_spec_step.
+        Drafts come from the sequence's own earlier n-grams (suffixes of up to `ngram` tokens), or from `drafts` (B/R, max_len) int - the
+        token proposed for each index, negative = none - when given.  Returns views seqs (B/R, max_len) int64 and logprobs (B/R, max_len)
+        fp32, bitwise what greedy() writes up to each image's first <eos> (nothing is written after it), and steps (B/R,) int32, the
+        verify steps each image took.  Not combinable with beam search, sampling, slot mode or an FP8 memory cache."""
+        D = int(draft_len)
+        R = D + 1
+        if not 1 <= D <= 7:
+            raise ValueError(f"draft_len must be in [1, 7], got {draft_len}")
+        if drafts is None and not 1 <= int(ngram) <= 8:
+            raise ValueError(f"ngram must be in [1, 8], got {ngram}")
+        if self.cross_fp8:
+            raise ValueError("speculative decoding does not support an FP8 memory cache; use memory_cache_dtype=None")
+        if self.group != R or self.B % R or not self._per_row_cross:
+            raise ValueError(f"draft_len {D} needs the memories prepared with group_size={R}, per_row_cross=True (prepared: group_size="
+                             f"{self.group}, per_row_cross={self._per_row_cross})")
+        n = self.B // R
+        if drafts is not None and tuple(drafts.shape) != (n, max_len):
+            raise ValueError(f"drafts must be (images, max_len) = ({n}, {max_len}), got {tuple(drafts.shape)}")
+        with self._run(max_len, ("spec", D, 0 if drafts is not None else int(ngram))):
+            if self.spec_t is None:
+                z = lambda *s: torch.zeros(*s, dtype=torch.int32, device=self.device)  # noqa: E731
+                self.spec_t, self.spec_cap, self.spec_steps = z(self.Bmax), z(self.Bmax), z(self.Bmax)
+                self.spec_tab, self.spec_next, self.spec_drafts = z(self.Bmax, self.Tmax), z(self.Bmax, 8), z(self.Bmax, self.Tmax)
+                d = _lib.AcaiSpec()
+                d.pitch, d.rows = self.Tmax, self.Bmax
+                d.t, d.cap, d.steps = self.spec_t.data_ptr(), self.spec_cap.data_ptr(), self.spec_steps.data_ptr()
+                d.tab, d.next = self.spec_tab.data_ptr(), self.spec_next.data_ptr()
+                self._spec_desc = d
+            self._spec_desc.D, self._spec_desc.ngram = D, self._mode[2]
+            self._spec_desc.drafts = None if drafts is None else self.spec_drafts.data_ptr()
+            if drafts is not None:
+                self.spec_drafts[:n].fill_(-1)
+                self.spec_drafts[:n, :max_len] = drafts.to(device=self.device, dtype=torch.int32)
+            self._spec_cap = int(max_len)
+            self._decode_loop(max_len, poll, use_graph, on_chunk)
+            return self.seqs[:n, :max_len], self.logprobs[:n, :max_len], self.spec_steps[:n]
+
+    def _arm_spec(self, B):
+        """Device-side state of a speculative run over B rows = B / R images: image i's tokens in row i of seqs / logprobs, t = 1, the key
+        table cleared; acai_decode_spec_arm drafts the first step and writes every row's input."""
+        n, own = B // (self._mode[1] + 1), self.omr
+        self.seqs[:n].fill_(own.pad_idx)
+        self.seqs[:n, 0] = own.bos_idx
+        self.logprobs[:n].zero_()
+        self.finished.zero_()
+        self.reset_self_cache()
+        self.step.copy_(torch.tensor([1, 0], dtype=torch.int32))
+        self.spec_t.fill_(1)
+        self.spec_cap.fill_(self._spec_cap)
+        self.spec_steps.zero_()
+        self.spec_tab.zero_()
+        self.spec_next.fill_(-1)
+        _lib.check(_lib.lib().acai_decode_spec_arm(ctypes.byref(self._desc), ctypes.byref(self._spec_desc), ops._st()), "acai_decode_spec_arm")
+        self._x_valid = True
+
     def beam_slots(self, max_len):
         """Every slot of the last beam search as it ended: tokens (B, max_len), per-token log-probs, cum (B,) and len (B,) (0 = unfinished).
         The lineage copy written last is (1 + steps run) & 1."""
@@ -570,6 +635,9 @@ class DecodeEngine:
     def arm(self, B):
         if self._mode[0] in ("slot", "slot_sample"):
             self._slot_reset()
+            return
+        if self._mode[0] == "spec":
+            self._arm_spec(B)
             return
         own = self.omr
         self.seqs[:B].fill_(own.pad_idx)
@@ -595,6 +663,8 @@ class DecodeEngine:
             _lib.check(L.acai_decode_sample_step(d, self.uniforms.data_ptr(), mode[1], mode[2], st), "acai_decode_sample_step")
         elif mode[0] == "beam":
             _lib.check(L.acai_decode_beam_step(d, ctypes.byref(self._beam_desc), st), "acai_decode_beam_step")
+        elif mode[0] == "spec":
+            _lib.check(L.acai_decode_spec_step(d, ctypes.byref(self._spec_desc), st), "acai_decode_spec_step")
         elif mode[0] == "slot_sample":
             _lib.check(L.acai_decode_slot_sample_step(d, ctypes.byref(self._slot_desc), self.slot_uniforms.data_ptr(), self.Tmax,
                                                       self.slot_urow.data_ptr(), mode[1], mode[2], st), "acai_decode_slot_sample_step")

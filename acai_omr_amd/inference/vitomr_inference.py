@@ -32,16 +32,23 @@ def _encode(vitomr, img):
         return vitomr.encoder.forward_packed(img)
 
 
-def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1, length_penalty=1.0):
+def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1, length_penalty=1.0, speculative=0, ngram=3):
     """img: one (1,H,W) tensor or a list of them -> (seqs int64 (B,T'), log_probs fp32 (B,T'), seq_mask bool (B,T')).
     beam_width > 1 (extension): beam search with that many hypotheses per image, scored by cum / len^length_penalty
-    (ViTOMR.cached_beam_generate); beam_width = 1 is the reference's greedy decode."""
+    (ViTOMR.cached_beam_generate); beam_width = 1 is the reference's greedy decode.
+    speculative = D in 1..7 (extension, default 0 = off): greedy decoding that verifies up to D n-gram draft tokens per step
+    (ViTOMR.cached_speculative_generate) - the same result in fewer steps where the output repeats itself; needs images * (D + 1) <= the
+    cache's max batch size, and cannot be combined with beam_width > 1 or an FP8 memory cache (ValueError)."""
+    if speculative and beam_width != 1:
+        raise ValueError("speculative decoding cannot be combined with beam search (beam_width > 1)")
     vitomr.eval()
     with torch.no_grad():
         lat32, _, lens = _encode(vitomr, img)
         with autocast(device_type=device, dtype=torch.bfloat16):
             mem = vitomr.transition_head.forward_packed(lat32)
             bf = mem.dtype == torch.bfloat16
+            if speculative:
+                return vitomr._speculative_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, speculative, ngram)
             if beam_width != 1:
                 return vitomr._beam_packed(None if bf else mem, mem if bf else None, lens, beam_width, max_inference_len, length_penalty)
             return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len)

@@ -568,6 +568,32 @@ class ViTOMR(nn.Module):
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._beam_packed(mem32, None, lens, beam_width, max_len, length_penalty)
 
+    def _speculative_packed(self, mem32, memb, lens, max_len, draft_len, ngram=3, drafts=None, poll=16, use_graph=True):
+        blocks = self.decoder._cached_blocks()
+        D = int(draft_len)
+        if not 1 <= D <= 7:
+            raise ValueError(f"draft_len must be in [1, 7], got {draft_len}")
+        if len(lens) * (D + 1) > blocks.max_batch_size:
+            raise ValueError(f"{len(lens)} images x (draft_len {D} + 1) = {len(lens) * (D + 1)} decode rows exceed the cache's max batch size "
+                             f"of {blocks.max_batch_size}")
+        if blocks.__dict__.get("_memory_fp8", False):
+            raise ValueError("speculative decoding does not support an FP8 memory cache; use memory_cache_dtype=None")
+        blocks.prepare_caches_packed(mem32, memb, lens, group_size=D + 1, per_row_cross=True)
+        eng = blocks.engine(self.decoder.pos_embedding.device)
+        seqs, lps, _ = eng.speculative(max_len, D, ngram=ngram, drafts=drafts, poll=poll, use_graph=use_graph)
+        return self.mask_and_clip_seqs(seqs.clone(), lps.clone())
+
+    def cached_speculative_generate(self, img_latent, latent_attention_mask=None, max_len=1536, draft_len=4, ngram=3, drafts=None):
+        """Speculative greedy decode with KV caching (an extension: the reference emits one token per step) -> seqs (B,T') int64, log_probs
+        (B,T') fp32, mask (B,T') bool: bitwise what cached_greedy_generate returns for the same arguments, in fewer decode steps when drafts
+        are accepted.  Each image owns draft_len + 1 decode rows (so B * (draft_len + 1) <= max batch size, 1 <= draft_len <= 7): one step
+        verifies up to draft_len draft tokens and emits the accepted ones plus one.  Drafts are looked up in the sequence's own earlier
+        n-grams (suffixes of up to `ngram` tokens, 1..8) or taken from `drafts` (B, max_len) - the token proposed for each index, negative =
+        none.  An image that ends early idles until the batch does.  Beam search, sampling, continuous batching (slot mode) and an FP8
+        memory cache cannot be combined with it (ValueError): out of scope here."""
+        mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
+        return self._speculative_packed(mem32, None, lens, max_len, draft_len, ngram, drafts)
+
     def _continuous_run(self, mem32, memb, lens, max_len, slots, poll, use_graph, **sampling):
         """(engine, caps, generator of finished image indices) of a continuous-batching run; argument errors are raised here, at the call.
         sampling: DecodeEngine.continuous's sample / uniforms / group."""

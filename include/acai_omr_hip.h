@@ -391,6 +391,48 @@ int acai_decode_slot_sample_step(const AcaiDecoder *d, const AcaiSlots *sl, cons
  * pos_embedding[1].  Rows outside [0, B) are ignored.  Marks x valid for acai_decode_slot_step: the caller keeps every row it did not arm
  * either finished or chained from the previous slot step. */
 int acai_decode_slot_arm(const AcaiDecoder *d, const AcaiSlots *sl, const int32_t *rows, int n, void *stream);
+/* Speculative greedy decoding state (draft and verify; an extension: the reference emits one token per step).  An image owns R = D + 1
+ * consecutive decode rows that share its cross K/V (dec->cross_group = R, dec->B = images * R).  With t the image's next index to write,
+ * row j of a verify step consumes the token at index t - 1 + j - row 0 the last emitted token, rows 1..D the draft tokens - at
+ * pos_embedding[t + j] (quirk Q1) and predicts index t + j.  Every row appends its self K/V at the shared write index step[1] of its own
+ * cache row; key p of the image is found through tab[i][p] = 8 * (cache position) + (row of the image), so nothing is moved when drafts
+ * are accepted or dropped.  step[0] is not used.  The image's tokens and log-probs land in row i (not i * R) of dec->seqs / dec->logprobs,
+ * its flag in finished[i], the count of unfinished images in finished[B].  All buffers are device memory:
+ *   t:      [rows] int32 next index to write (armed: 1);
+ *   cap:    [rows] int32 the run's max_len for the image: it finishes at <eos> or once index cap - 1 is written (2 <= cap <= max_len);
+ *   steps:  [rows] int32 verify steps the image took part in (armed: 0);
+ *   tab:    [rows][pitch] int32 key table (armed: 0; acai_decode_spec_arm and every step set entries t - 1 .. t - 1 + D);
+ *   next:   [rows][8] int32 the tokens the next step's rows consume: [0] the last emitted token, [1..D] the drafts, -1 = none;
+ *   drafts: NULL, or [rows][pitch] int32: drafts[i][p] is the token proposed for index p (outside [0, V): none) and replaces the lookup.
+ * The caller arms seqs (<bos> then <pad>), logprobs (0), finished (0), step = {1, 0}, t, cap, steps and tab, then calls
+ * acai_decode_spec_arm once. */
+typedef struct {
+    int32_t D;         /* draft tokens per step, 1..7 */
+    int32_t ngram;     /* longest suffix the prompt-lookup drafter matches, 1..8 (unused with drafts) */
+    int32_t pitch;     /* entries per image of tab / drafts: max_len <= pitch <= Tmax */
+    int32_t rows;      /* images the arrays hold, >= dec->B / (D + 1) */
+    int32_t *t;
+    int32_t *cap;
+    int32_t *steps;
+    int32_t *tab;
+    int32_t *next;
+    const int32_t *drafts;
+} AcaiSpec;
+/* Opens a speculative run on the armed state: drafts the first step (t = 1), sets the table entries and every row's input x, writes
+ * finished[B].  Marks x valid for acai_decode_spec_step. */
+int acai_decode_spec_arm(const AcaiDecoder *d, const AcaiSpec *sp, void *stream);
+/* One VERIFY step for every image: the greedy step's layers on all B rows (the same GEMV kernels; self attention of row j over the image's
+ * t + j keys through tab; cross attention by the per-row kernel, the rows aliasing the image's K/V, so that a row's arithmetic is the plain
+ * greedy step's), then one launch per step: g_j = the greedy token and log-prob of row j (the greedy step's reduction); n = the number of
+ * leading drafts with draft_j == g_{j-1}; g_0 .. g_n and their log-probs are written at indices t .. t + n, cut at the first <eos> and at
+ * cap - 1; t, finished[] and finished[B] are updated; the next step is drafted - from drafts when given, else for m = ngram .. 1 the most
+ * recent earlier occurrence of the sequence's last m tokens, the first m with a match proposing the up to D tokens that followed it - and
+ * next, tab and x are written; step[1] advances.  A row whose draft is none, or whose index would reach cap, is idle: what it computes is
+ * never read and every index it forms is clamped.  The emitted tokens and log-probs are those of acai_decode_step run token by token.
+ * Needs 1 <= D <= 7, B % (D + 1) == 0, cross_group == D + 1, no FP8 cross K/V, max_len <= pitch <= Tmax, rows >= B / (D + 1), ngram in
+ * [1, 8] unless drafts is given, self_chunk <= 16384, and x valid (acai_decode_spec_arm; acai_decode_logits / acai_decode_hidden clear it).
+ * A run takes at most max_len - 1 steps, so step[1] stays below Tmax.  Enqueues kernels only (capturable). */
+int acai_decode_spec_step(const AcaiDecoder *d, const AcaiSpec *sp, void *stream);
 /* The same without the token bookkeeping: logits for caller-supplied tokens/time_step (OMRDecoder.cached_generate). */
 int acai_decode_logits(const AcaiDecoder *dec, const int64_t *tokens, int time_step, void *stream);
 
