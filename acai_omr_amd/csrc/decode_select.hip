@@ -1,0 +1,693 @@
+// Token selection of a decode step (see decode.hip): embedding, greedy / sampled / slot / speculative / beam selection and their
+// bookkeeping, each with the host helper that launches it from the decoder descriptor.
+#include "decode_internal.h"
+
+namespace {
+
+// x[b,:] = vocab_embedding[token_b] + pos_embedding[t]; token from `tokens` or seqs[b, t-1] (quirk Q1: M:576)
+__global__ __launch_bounds__(256) void embed_kernel(const float *emb, const float *pos, const int64_t *tokens, const int64_t *seqs,
+                                                    const int32_t *step, int max_len, float *x, int E) {
+    const int b = blockIdx.x, t = step[0];
+    const int64_t tok = tokens ? tokens[b] : seqs[(size_t)b * max_len + t - 1];
+    for (int i = threadIdx.x; i < E; i += 256) x[(size_t)b * E + i] = emb[(size_t)tok * E + i] + pos[(size_t)t * E + i];
+}
+
+__global__ void set_step_kernel(int32_t *step, int t) { step[0] = t; }
+
+// One wave over a logit row: the row maximum `best` at its first index `bi` (torch.argmax on CPU) and sum_i exp(lg[i] - best), returned
+// wave-uniform.  The greedy step and the beam step share it, so that a beam of width 1 reproduces greedy's log-probabilities bit for bit.
+__device__ __forceinline__ float row_argmax_sumexp(const float *lg, int V, int lane, float &best, int &bi) {
+    best = -INFINITY;
+    bi = 0x7fffffff;
+    for (int i = lane; i < V; i += 64) {
+        const float v = lg[i];
+        if (v > best) {  // strided scan keeps the lowest index per lane on ties
+            best = v;
+            bi = i;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {  // argmax, first index on ties (torch.argmax on CPU)
+        const float ov = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bi, o);
+        if (ov > best || (ov == best && oi < bi)) {
+            best = ov;
+            bi = oi;
+        }
+    }
+    float se = 0.f;
+    for (int i = lane; i < V; i += 64) se += expf(lg[i] - best);
+    return wave_sum(se);
+}
+
+// cached_get_next_token (M:579-581) + loop bookkeeping (M:606-611).  One workgroup, wave w takes rows w, w+4, ...
+// With `emb`: the wave that chose row b's token also writes the NEXT step's input x[b] = vocab_embedding[token] + pos_embedding[t + 1]
+// (quirk Q1: the token at index t is embedded with position t + 1, M:576), so a token step needs no embed launch of its own.
+__global__ __launch_bounds__(1024) void argmax_logprob_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs,
+                                                             int max_len, int32_t *step, int32_t *finished, int eos, int round_lp,
+                                                             int bookkeeping, const float *emb, const float *pos, float *x, int E, int Tmax) {
+    __shared__ int unfinished[16];   // up to 16 waves: one row per wave for the usual batch sizes (the rows of a wave run back to back)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = step[0];
+    int cnt = 0;
+    const int nw = blockDim.x >> 6;
+    for (int b = wave; b < B; b += nw) {
+        const float *lg = logits + (size_t)b * V;
+        float best;
+        int bi;
+        const float se = row_argmax_sumexp(lg, V, lane, best, bi);
+        float lp = -logf(se);  // logit[argmax] - logsumexp
+        if (round_lp) lp = round_bf16(lp);
+        if (bookkeeping) {
+            int fin = finished[b];
+            if (bi == eos) fin = 1;
+            if (lane == 0) {
+                seqs[(size_t)b * max_len + t] = bi;
+                logprobs[(size_t)b * max_len + t] = lp;
+                finished[b] = fin;
+            }
+            cnt += fin ? 0 : 1;
+            if (emb && t + 1 < Tmax)
+                for (int i = lane * 4; i < E; i += 256) {
+                    const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)bi * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+                    *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+                }
+        } else if (lane == 0) {
+            seqs[b] = bi;
+            logprobs[b] = lp;
+        }
+    }
+    if (lane == 0) unfinished[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < nw; ++w) tot += unfinished[w];
+        if (bookkeeping) finished[B] = tot;
+        step[0] = t + 1;
+        step[1] = step[1] + 1;
+    }
+}
+
+// GRPOViTOMR.cached_forward_rollout_policy (M:988-1049), one sampling step: top-k filter, softmax with temperature over the kept logits,
+// draw from that distribution, log-prob of the drawn token under the UN-tempered softmax of the kept logits (the reference takes
+// log_softmax(top_k_logits), M:1017).  torch.multinomial's Philox stream is not reproducible here; the draw is the inverse CDF of a caller
+// supplied uniform u[b][t] over the kept logits in descending order (ties: lower vocabulary index first), so a step is a pure function of
+// (logits, u) that the oracle restates.  One wave per row: k rounds of a wave-wide arg-max build the sorted top-k (k <= 64).
+// The per-row part, shared by the static and the slot sampler so that a sequence draws the same tokens in either: wave-wide, `sv` / `si` are
+// the wave's own 64 LDS entries.  Returns the drawn token; lp = log_softmax(kept)[drawn] (not rounded).
+__device__ __forceinline__ int topk_draw_row(const float *lg, int V, int lane, float *sv, int *si, int top_k, float inv_temperature, float u,
+                                             float &lp) {
+    // lane owns vocabulary entries lane, lane + 64, ... (V <= 512)
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (lane + 64 * j < V) ? lg[lane + 64 * j] : -INFINITY;
+    const int k = min(top_k, V);
+    for (int r = 0; r < k; ++r) {
+        float best = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (v[j] > best) {   // ascending j = ascending index: first maximum wins
+                best = v[j];
+                bi = lane + 64 * j;
+            }
+        if (best == -INFINITY) bi = 0x7fffffff;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(best, o);
+            const int oi = __shfl_xor(bi, o);
+            if (ov > best || (ov == best && oi < bi)) {
+                best = ov;
+                bi = oi;
+            }
+        }
+        if ((bi & 63) == lane) {   // owner removes the winner
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (bi == lane + 64 * j) v[j] = -INFINITY;
+        }
+        if (lane == 0) {
+            sv[r] = best;
+            si[r] = bi;
+        }
+    }
+    // same wave wrote and reads: LDS operations of a wave complete in order
+    const bool in = lane < k;
+    const float x = in ? sv[lane] : -INFINITY, m = sv[0];
+    const float pT = in ? expf((x - m) * inv_temperature) : 0.f;   // softmax(top_k_logits / temperature), unnormalised
+    const float p1 = in ? expf(x - m) : 0.f;                       // softmax(top_k_logits), unnormalised
+    const float sumT = wave_sum(pT), sum1 = wave_sum(p1);
+    float cdf = pT;                                                // inclusive prefix sum over the lanes
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(cdf, o);
+        if (lane >= o) cdf += up;
+    }
+    const float target = u * sumT;
+    const unsigned long long hit = __ballot(in && cdf > target);
+    const int r = hit ? __builtin_ctzll(hit) : k - 1;              // rounding at the top of the CDF: last kept entry
+    lp = (sv[r] - m) - logf(sum1);
+    return si[r];
+}
+
+__global__ __launch_bounds__(256) void sample_logprob_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                             const int32_t *step, int32_t *finished, int eos, int round_lp,
+                                                             const float *uniforms, int top_k, float inv_temperature, const float *emb,
+                                                             const float *pos, float *xnext, int E, int Tmax) {
+    __shared__ float sv[4][64];
+    __shared__ int si[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + wave;
+    if (b >= B) return;
+    const int t = step[0];
+    float lp;
+    const int tok = topk_draw_row(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
+                                  uniforms[(size_t)b * max_len + t], lp);
+    if (round_lp) lp = round_bf16(lp);
+    if (lane == 0) {
+        seqs[(size_t)b * max_len + t] = tok;
+        logprobs[(size_t)b * max_len + t] = lp;
+        if (tok == eos) finished[b] = 1;
+    }
+    if (emb && t + 1 < Tmax)   // next step's input (see argmax_logprob_kernel)
+        for (int i = lane * 4; i < E; i += 256) {
+            const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+            *reinterpret_cast<float4 *>(xnext + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+        }
+}
+
+// loop bookkeeping after a sampling step: unfinished count, advance position and cache length
+__global__ __launch_bounds__(64) void sample_bookkeeping_kernel(int B, int32_t *step, int32_t *finished) {
+    int cnt = 0;
+    for (int b = threadIdx.x; b < B; b += 64) cnt += finished[b] ? 0 : 1;
+    cnt = (int)wave_sum((float)cnt);
+    if (threadIdx.x == 0) {
+        finished[B] = cnt;
+        step[0] = step[0] + 1;
+        step[1] = step[1] + 1;
+    }
+}
+
+__global__ void advance_cache_kernel(int32_t *step) { step[1] = step[1] + 1; }
+
+// ---- continuous batching (slot mode; an extension: the reference decodes one static batch) --------------------------------------------
+// The greedy token of every unfinished row at its OWN local time t = slot_t[b] (argmax_logprob_kernel's reduction, so a row decodes as it
+// would in a greedy batch): seqs / logprobs at index t, then either the row finishes (<eos>, or t has reached its cap - 1) and from then on
+// writes nothing, or t advances and the wave writes the row's next input emb[token] + pos[t + 1] (quirk Q1).  Thread 0 publishes the
+// unfinished count finished[B] and advances the shared ring write index step[1] modulo Tmax.  step[0] is not used in slot mode.
+__global__ __launch_bounds__(1024) void slot_argmax_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                          int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap, int eos,
+                                                          int round_lp, const float *emb, const float *pos, float *x, int E, int Tmax) {
+    __shared__ int unfinished[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int cnt = 0;
+    const int nw = blockDim.x >> 6;
+    for (int b = wave; b < B; b += nw) {
+        if (finished[b]) continue;   // wave-uniform: a finished or idle row writes nothing
+        const int t = slot_t[b];
+        const float *lg = logits + (size_t)b * V;
+        float best;
+        int bi;
+        const float se = row_argmax_sumexp(lg, V, lane, best, bi);
+        float lp = -logf(se);
+        if (round_lp) lp = round_bf16(lp);
+        const bool fin = bi == eos || t >= slot_cap[b] - 1;
+        if (lane == 0) {
+            seqs[(size_t)b * max_len + t] = bi;
+            logprobs[(size_t)b * max_len + t] = lp;
+            if (fin) finished[b] = 1;
+            else slot_t[b] = t + 1;
+        }
+        if (!fin) {   // t + 1 <= cap - 1 < max_len <= Tmax
+            cnt += 1;
+            for (int i = lane * 4; i < E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)bi * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+        }
+    }
+    if (lane == 0) unfinished[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < nw; ++w) tot += unfinished[w];
+        finished[B] = tot;
+        const int nxt = step[1] + 1;
+        step[1] = nxt >= Tmax ? 0 : nxt;
+    }
+}
+
+// The sampling form of slot_argmax_kernel: the token of every unfinished row is topk_draw_row's at the row's local time t = slot_t[b], with
+// the uniform uniforms[urow[b]][t] of the sequence the slot decodes (urow is set when the slot is armed), so a sequence draws what it draws
+// alone in sample_logprob_kernel whichever slot and step it runs in.  One wave per row over gridDim.x workgroups of four (the k rounds of
+// a row are a serial chain: one workgroup for every row would put them end to end).  With more than one workgroup the unfinished count and
+// the ring index are written by the workgroup that arrives last at `ticket` (zero between launches, re-armed here): every workgroup
+// publishes its rows' flags with agent-scope atomic stores before it takes its ticket, and the last one reads all flags the same way.
+__global__ __launch_bounds__(256) void slot_sample_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                          int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap, int eos,
+                                                          int round_lp, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k,
+                                                          float inv_temperature, const float *emb, const float *pos, float *x, int E, int Tmax,
+                                                          unsigned *ticket) {
+    __shared__ float sv[4][64];
+    __shared__ int si[4][64];
+    __shared__ int is_last;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
+        if (finished[b]) continue;   // wave-uniform: a finished or idle row writes nothing
+        const int t = slot_t[b];
+        float lp;
+        const int tok = topk_draw_row(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
+                                      uniforms[(size_t)urow[b] * ld_uniforms + t], lp);
+        if (round_lp) lp = round_bf16(lp);
+        const bool fin = tok == eos || t >= slot_cap[b] - 1;
+        if (lane == 0) {
+            seqs[(size_t)b * max_len + t] = tok;
+            logprobs[(size_t)b * max_len + t] = lp;
+            if (fin) __hip_atomic_store(finished + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else slot_t[b] = t + 1;
+        }
+        if (!fin)   // t + 1 <= cap - 1 < max_len <= Tmax
+            for (int i = lane * 4; i < E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+    }
+    if (gridDim.x > 1) {
+        __threadfence();   // this thread's flag stores are visible device-wide before the workgroup's ticket
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned n = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            is_last = n == gridDim.x - 1;
+            if (is_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (gridDim.x > 1 && !is_last) return;
+    if (wave == 0) {
+        int cnt = 0;
+        for (int b = lane; b < B; b += 64) cnt += __hip_atomic_load(finished + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 1;
+        cnt = (int)wave_sum((float)cnt);
+        if (lane == 0) {
+            finished[B] = cnt;
+            const int nxt = step[1] + 1;
+            step[1] = nxt >= Tmax ? 0 : nxt;
+        }
+    }
+}
+
+// Arms row rows[i] (one workgroup each) for a new sequence: <bos> then <pad>, log-probs 0, unfinished, local time 1 starting at the current
+// ring write index step[1], cap rows[n + i] (clamped to [2, max_len]) and the first input emb[<bos>] + pos[1].  Rows outside [0, B) are
+// ignored.
+__global__ __launch_bounds__(256) void slot_arm_kernel(const int32_t *rows, int n, int B, int max_len, int64_t *seqs, float *logprobs,
+                                                       int32_t *finished, int32_t *slot_t, int32_t *slot_first, int32_t *slot_cap,
+                                                       const int32_t *step, int bos, int pad, const float *emb,
+                                                       const float *pos, float *x, int E) {
+    const int r = rows[blockIdx.x];
+    if (r < 0 || r >= B) return;
+    const int cap = min(max(rows[n + blockIdx.x], 2), max_len);
+    for (int p = threadIdx.x; p < max_len; p += 256) {
+        seqs[(size_t)r * max_len + p] = p == 0 ? bos : pad;
+        logprobs[(size_t)r * max_len + p] = 0.f;
+    }
+    for (int i = threadIdx.x; i < E; i += 256) x[(size_t)r * E + i] = emb[(size_t)bos * E + i] + pos[(size_t)E + i];
+    if (threadIdx.x == 0) {
+        finished[r] = 0;
+        slot_t[r] = 1;
+        slot_first[r] = step[1];
+        slot_cap[r] = cap;
+    }
+}
+
+// ---- speculative greedy decoding (an extension: the reference emits one token per step) -------------------------------------------------
+// An image owns R = D + 1 consecutive decode rows.  Before a verify step, next[i][0] is the image's last emitted token (index t - 1) and
+// next[i][1..D] the draft tokens for indices t .. t + D - 1 (-1 = none); row j consumed next[i][j] at position t + j (quirk Q1) and its
+// logits predict index t + j.  One workgroup closes the step (and, with arm set, opens the run):
+//   1. wave w: the greedy token and log-prob of rows w, w + nw, ... (argmax_logprob_kernel's reduction) into LDS;
+//   2. wave w: images w, w + nw, ...: accept - g_0, then g_j while draft j equals g_{j-1} - written at t .. t + n, cut at the first <eos>
+//      and at cap - 1; t, finished[i], steps[i];
+//   3. the same wave drafts the next step: from the injected table drafts[i][index] when given, else by prompt lookup - for m = ngram .. 1
+//      the most recent earlier occurrence of the sequence's last m tokens, the first m that has one proposes the up to D tokens after it -
+//      and writes next[i][], the table entries of indices t - 1 .. t - 1 + D (row j at the NEXT write index) and every row's input x;
+//   4. thread 0: the unfinished count finished[B] and the shared write index step[1].
+// Every loop is bounded by cap <= max_len or by B.
+struct SpecArgs {
+    const float *logits;
+    int V, B, R, E, Tmax, ld, eos, pad, round_lp, ngram, arm, pitch;
+    int64_t *seqs;
+    float *logprobs;
+    int32_t *step, *finished;
+    const float *emb, *pos;
+    float *x;
+    int32_t *t, *steps, *tab, *next;
+    const int32_t *cap, *drafts;
+};
+
+__global__ __launch_bounds__(1024) void spec_accept_kernel(SpecArgs a) {
+    extern __shared__ int spec_dyn[];   // [B] greedy tokens, [B] their log-probs
+    __shared__ int unfinished[16];
+    int *g_tok = spec_dyn;
+    float *g_lp = reinterpret_cast<float *>(spec_dyn + a.B);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int R = a.R, nimg = a.B / R;
+    if (!a.arm)
+        for (int b = wave; b < a.B; b += nw) {
+            float best;
+            int bi;
+            const float se = row_argmax_sumexp(a.logits + (size_t)b * a.V, a.V, lane, best, bi);
+            float lp = -logf(se);
+            if (a.round_lp) lp = round_bf16(lp);
+            if (lane == 0) {
+                g_tok[b] = bi;
+                g_lp[b] = lp;
+            }
+        }
+    __syncthreads();
+    const int wnext = min(a.step[1] + (a.arm ? 0 : 1), a.Tmax - 1);   // the cache position the next step's rows write
+    int cnt = 0;
+    for (int img = wave; img < nimg; img += nw) {
+        int64_t *sq = a.seqs + (size_t)img * a.ld;
+        float *lq = a.logprobs + (size_t)img * a.ld;
+        int32_t *nx = a.next + (size_t)img * 8;
+        const int cap = min(a.cap[img], min(a.ld, a.pitch));
+        int t = a.t[img], fin = a.finished[img];
+        if (t < 1 || t >= cap) fin = 1;   // (an armed, unfinished image has 1 <= t <= cap - 1)
+        if (!a.arm && !fin) {
+            int n = 0;
+            for (int j = 0; j < R; ++j) {   // wave-uniform
+                if (j > 0 && nx[j] != g_tok[img * R + j - 1]) break;   // draft j was wrong (or none): row j saw another sequence
+                if (t + j >= cap) break;
+                const int tok = g_tok[img * R + j];
+                if (lane == 0) {
+                    sq[t + j] = tok;
+                    lq[t + j] = g_lp[img * R + j];
+                }
+                n = j + 1;
+                if (tok == a.eos) {
+                    fin = 1;
+                    break;
+                }
+            }
+            t += n;
+            if (t >= cap) fin = 1;
+            if (lane == 0) {
+                a.t[img] = t;
+                a.steps[img] += 1;
+            }
+            __threadfence();   // lane 0's tokens are read back by every lane of this wave below
+        }
+        if (lane == 0) a.finished[img] = fin;
+        if (fin) continue;
+        cnt += 1;
+        // the next step's inputs: lane j < R holds the token row j consumes (index t - 1 + j), -1 = none
+        int mine = -1;
+        if (a.drafts) {
+            const int idx = t - 1 + lane;
+            if (lane >= 1 && lane < R && t + lane < cap) {   // (a row whose prediction index would reach cap is idle)
+                const int v = a.drafts[(size_t)img * a.pitch + idx];
+                mine = (v >= 0 && v < a.V) ? v : -1;
+            }
+        } else {
+            int e_found = -1;
+            for (int m = min(a.ngram, t - 1); m >= 1 && e_found < 0; --m)
+                for (int base = t - 1; base >= m; base -= 64) {   // candidate ends e (exclusive) from the most recent down
+                    const int e = base - lane;
+                    bool ok = e >= m;
+                    if (ok)
+                        for (int i = 0; i < m; ++i)
+                            if (sq[e - m + i] != sq[t - m + i]) {
+                                ok = false;
+                                break;
+                            }
+                    const unsigned long long hit = __ballot(ok);
+                    if (hit) {
+                        e_found = base - __builtin_ctzll(hit);
+                        break;
+                    }
+                }
+            if (e_found >= 0 && lane >= 1 && lane < R && e_found + lane - 1 < t && t + lane < cap) mine = (int)sq[e_found + lane - 1];
+        }
+        if (lane == 0) mine = (int)sq[t - 1];
+        if (lane < R) {
+            nx[lane] = mine;
+            const int idx = t - 1 + lane;
+            if (idx < a.pitch) a.tab[(size_t)img * a.pitch + idx] = wnext * 8 + lane;
+        }
+        for (int j = 0; j < R; ++j) {
+            const int tk = __shfl(mine, j), tok = tk < 0 ? a.pad : tk, p = min(t + j, a.Tmax - 1);
+            float *xr = a.x + (size_t)(img * R + j) * a.E;
+            for (int i = lane; i < a.E; i += 64) xr[i] = a.emb[(size_t)tok * a.E + i] + a.pos[(size_t)p * a.E + i];
+        }
+    }
+    if (lane == 0) unfinished[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < nw; ++w) tot += unfinished[w];
+        a.finished[a.B] = tot;
+        if (!a.arm) a.step[1] = min(a.step[1] + 1, a.Tmax - 1);
+    }
+}
+
+// ---- beam search (an extension: the reference decodes greedily) ------------------------------------------------------------------------
+
+struct BeamArgs {
+    const float *logits;
+    int V, K, E, Tmax, pitch, eos, pad, round_lp;
+    const int32_t *step;
+    int32_t *finished;
+    const float *emb, *pos;
+    float *x;
+    int32_t *anc;
+    int64_t *tok;
+    float *lp;
+    long long bstride;   // elements between the two parity copies of the lineage
+    float *cum;
+    int32_t *len;
+};
+
+// One workgroup per image (rows r0 .. r0 + K - 1), step t = step[0]; lineage copy (t & 1) is read, copy (t + 1) & 1 written.
+//   1. the K rows' (cum, finished, len) into LDS (this workgroup is their only writer);
+//   2. wave w builds the candidates of rows w, w + 4, ...: a live row its K best tokens by raw logit in K rounds of a wave-wide arg-max (lower
+//      index first on ties, sample_logprob_kernel's pattern), score cum + lp with greedy's row max / sum of exponentials; a finished row the
+//      single candidate (itself + <pad>, lp 0, score cum); a row at cum = -inf none.  Candidate c = parent * K + rank;
+//   3. thread c ranks its candidate against all K*K (score descending, then c ascending = parent slot, then rank): rank j < K -> slot j;
+//   4. wave w fills new slots w, w + 4, ...: the parent's lineage up to position t - 1 plus (slot, token, lp) at t, cum, finished, len and the
+//      next step's input emb[token] + pos[t + 1].
+__global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
+    __shared__ float cs[BEAM_MAX * BEAM_MAX], clp[BEAM_MAX * BEAM_MAX];
+    __shared__ int ctok[BEAM_MAX * BEAM_MAX];
+    __shared__ float pcum[BEAM_MAX];
+    __shared__ int pfin[BEAM_MAX], plen[BEAM_MAX], sel[BEAM_MAX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = a.K, NC = K * K, r0 = blockIdx.x * K;
+    const int t = a.step[0];
+    const size_t cur = (size_t)(t & 1) * a.bstride, nxt = (size_t)((t + 1) & 1) * a.bstride;
+    if (tid < K) {
+        pcum[tid] = a.cum[r0 + tid];
+        pfin[tid] = a.finished[r0 + tid];
+        plen[tid] = a.len[r0 + tid];
+        sel[tid] = -1;
+    }
+    if (tid < NC) cs[tid] = -INFINITY;
+    __syncthreads();
+    const int kv = min(K, a.V);
+    for (int k = wave; k < K; k += 4) {
+        const float c0 = pcum[k];
+        if (c0 == -INFINITY) continue;
+        if (pfin[k]) {
+            if (lane == 0) {
+                cs[k * K] = c0;
+                ctok[k * K] = a.pad;
+                clp[k * K] = 0.f;
+            }
+            continue;
+        }
+        const float *lg = a.logits + (size_t)(r0 + k) * a.V;
+        float best;
+        int bi;
+        const float lse = logf(row_argmax_sumexp(lg, a.V, lane, best, bi));
+        float v[8];   // lane owns vocabulary entries lane, lane + 64, ... (V <= 512)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (lane + 64 * j < a.V) ? lg[lane + 64 * j] : -INFINITY;
+        for (int r = 0; r < kv; ++r) {
+            float bv = -INFINITY;
+            int bj = 0x7fffffff;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (v[j] > bv) {
+                    bv = v[j];
+                    bj = lane + 64 * j;
+                }
+            if (bv == -INFINITY) bj = 0x7fffffff;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o);
+                const int oi = __shfl_xor(bj, o);
+                if (ov > bv || (ov == bv && oi < bj)) {
+                    bv = ov;
+                    bj = oi;
+                }
+            }
+            if ((bj & 63) == lane) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (bj == lane + 64 * j) v[j] = -INFINITY;
+            }
+            if (lane == 0 && bj < a.V) {
+                const float l = -(lse - (bv - best));   // = (logit - max) - lse; -lse exactly for the arg-max (greedy's -logf(se))
+                cs[k * K + r] = c0 + l;
+                ctok[k * K + r] = bj;
+                clp[k * K + r] = l;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < NC) {
+        const float sc = cs[tid];
+        if (sc > -INFINITY) {
+            int rank = 0;
+            for (int c = 0; c < NC; ++c) {
+                const float o = cs[c];
+                rank += (o > sc || (o == sc && c < tid)) ? 1 : 0;
+            }
+            if (rank < K) sel[rank] = tid;
+        }
+    }
+    __syncthreads();
+    for (int j = wave; j < K; j += 4) {
+        const int c = sel[j], row = r0 + j;
+        int par = j, tk = a.pad, fin = 1, ln = 0;
+        float l = 0.f, sc = -INFINITY;
+        if (c >= 0) {   // (no candidate: a dead slot - it keeps its own lineage, extended by <pad>)
+            par = c / K;
+            tk = ctok[c];
+            l = clp[c];
+            sc = cs[c];
+            if (pfin[par]) {
+                ln = plen[par];
+            } else if (tk == a.eos) {
+                ln = t;
+            } else {
+                fin = 0;
+            }
+        }
+        const size_t src = cur + (size_t)(r0 + par) * a.pitch, dst = nxt + (size_t)row * a.pitch;
+        const int tc = min(t, a.pitch);
+        for (int p = lane; p < tc; p += 64) {
+            a.anc[dst + p] = a.anc[src + p];
+            a.tok[dst + p] = a.tok[src + p];
+            a.lp[dst + p] = a.lp[src + p];
+        }
+        if (lane == 0) {
+            if (t < a.pitch) {
+                a.anc[dst + t] = row;   // the next step writes this row's K/V at position t
+                a.tok[dst + t] = tk;
+                a.lp[dst + t] = a.round_lp ? round_bf16(l) : l;
+            }
+            a.cum[row] = sc;
+            a.finished[row] = fin;
+            a.len[row] = ln;
+        }
+        if (t + 1 < a.Tmax)   // next step's input (see argmax_logprob_kernel)
+            for (int i = lane * 4; i < a.E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(a.emb + (size_t)tk * a.E + i), pv = *reinterpret_cast<const float4 *>(a.pos + (size_t)(t + 1) * a.E + i);
+                *reinterpret_cast<float4 *>(a.x + (size_t)row * a.E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+    }
+}
+
+}  // namespace
+
+static int round_lp(const AcaiDecoder *d) { return (d->flags & ACAI_GEMM_ROUND_BF16) ? 1 : 0; }
+// one workgroup closes the step, one wave per row for the usual batch sizes
+static dim3 row_waves(const AcaiDecoder *d) { return dim3(d->B > 8 ? 1024 : (d->B > 4 ? 512 : 256)); }
+
+int launch_embed(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st) {
+    hipLaunchKernelGGL(embed_kernel, dim3(d->B), dim3(256), 0, st, (const float *)d->emb, (const float *)d->pos, tokens, (const int64_t *)d->seqs,
+                       (const int32_t *)d->step, d->max_len, d->x, d->E);
+    ACAI_LAUNCH_CHECK("embed");
+    return 0;
+}
+
+int launch_set_step(const AcaiDecoder *d, int t, hipStream_t st) {
+    hipLaunchKernelGGL(set_step_kernel, dim3(1), dim3(1), 0, st, d->step, t);
+    ACAI_LAUNCH_CHECK("set_step");
+    return 0;
+}
+
+int launch_advance_cache(const AcaiDecoder *d, hipStream_t st) {
+    hipLaunchKernelGGL(advance_cache_kernel, dim3(1), dim3(1), 0, st, d->step);
+    ACAI_LAUNCH_CHECK("advance_cache");
+    return 0;
+}
+
+// `chained`: the kernel also writes the next step's input x
+int launch_argmax_logprob(const AcaiDecoder *d, bool chained, hipStream_t st) {
+    hipLaunchKernelGGL(argmax_logprob_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
+                       d->finished, d->eos, round_lp(d), 1, chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax);
+    ACAI_LAUNCH_CHECK("argmax_logprob");
+    return 0;
+}
+
+// the sampling kernel, then the loop bookkeeping
+int launch_sample_logprob(const AcaiDecoder *d, const float *uniforms, int top_k, float temperature, bool chained, hipStream_t st) {
+    hipLaunchKernelGGL(sample_logprob_kernel, dim3(cdiv(d->B, 4)), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
+                       d->finished, d->eos, round_lp(d), uniforms, top_k, 1.0f / temperature,
+                       chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax);
+    hipLaunchKernelGGL(sample_bookkeeping_kernel, dim3(1), dim3(64), 0, st, d->B, d->step, d->finished);
+    ACAI_LAUNCH_CHECK("sample_logprob");
+    return 0;
+}
+
+// the beam selection, then the loop bookkeeping
+int launch_beam_select(const AcaiDecoder *d, const AcaiBeam *bs, hipStream_t st) {
+    BeamArgs a{};
+    a.logits = d->logits; a.V = d->V; a.K = bs->K; a.E = d->E; a.Tmax = d->Tmax; a.pitch = bs->pitch; a.eos = d->eos; a.pad = d->pad;
+    a.round_lp = round_lp(d);
+    a.step = d->step; a.finished = d->finished; a.emb = d->emb; a.pos = d->pos; a.x = d->x;
+    a.anc = bs->anc; a.tok = bs->tok; a.lp = bs->lp; a.bstride = (long long)bs->rows * bs->pitch; a.cum = bs->cum; a.len = bs->len;
+    hipLaunchKernelGGL(beam_select_kernel, dim3(d->B / bs->K), dim3(256), 0, st, a);
+    ACAI_LAUNCH_CHECK("beam_select");
+    hipLaunchKernelGGL(sample_bookkeeping_kernel, dim3(1), dim3(64), 0, st, d->B, d->step, d->finished);
+    ACAI_LAUNCH_CHECK("beam_bookkeeping");
+    return 0;
+}
+
+int launch_slot_arm(const AcaiDecoder *d, const AcaiSlots *sl, const int32_t *rows, int n, hipStream_t st) {
+    hipLaunchKernelGGL(slot_arm_kernel, dim3(n), dim3(256), 0, st, rows, n, d->B, d->max_len, d->seqs, d->logprobs,
+                       d->finished, sl->t, sl->first, sl->cap, (const int32_t *)d->step, d->bos, d->pad,
+                       (const float *)d->emb, (const float *)d->pos, d->x, d->E);
+    ACAI_LAUNCH_CHECK("slot_arm");
+    return 0;
+}
+
+int launch_slot_argmax(const AcaiDecoder *d, const AcaiSlots *sl, hipStream_t st) {
+    hipLaunchKernelGGL(slot_argmax_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs,
+                       d->logprobs, d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos,
+                       round_lp(d), (const float *)d->emb, (const float *)d->pos, d->x, d->E, d->Tmax);
+    ACAI_LAUNCH_CHECK("slot_argmax");
+    return 0;
+}
+
+int launch_slot_sample(const AcaiDecoder *d, const AcaiSlots *sl, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k,
+                       float temperature, hipStream_t st) {
+    // one wave per row; without arrival counters (d->tickets) one workgroup takes every row and closes the step itself
+    hipLaunchKernelGGL(slot_sample_kernel, dim3(d->tickets ? cdiv(d->B, 4) : 1), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs,
+                       d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos, round_lp(d),
+                       uniforms, ld_uniforms, urow, top_k, 1.0f / temperature, (const float *)d->emb, (const float *)d->pos, d->x, d->E, d->Tmax,
+                       (unsigned *)d->tickets);
+    ACAI_LAUNCH_CHECK("slot_sample");
+    return 0;
+}
+
+// arm != 0 opens a run (no logits are read), arm == 0 closes a verify step
+int launch_spec_accept(const AcaiDecoder *d, const AcaiSpec *sp, int arm, hipStream_t st) {
+    SpecArgs a{};
+    a.logits = d->logits; a.V = d->V; a.B = d->B; a.R = sp->D + 1; a.E = d->E; a.Tmax = d->Tmax; a.ld = d->max_len; a.eos = d->eos; a.pad = d->pad;
+    a.round_lp = round_lp(d); a.ngram = sp->ngram; a.arm = arm; a.pitch = sp->pitch;
+    a.seqs = d->seqs; a.logprobs = d->logprobs; a.step = d->step; a.finished = d->finished; a.emb = d->emb; a.pos = d->pos; a.x = d->x;
+    a.t = sp->t; a.steps = sp->steps; a.tab = sp->tab; a.next = sp->next; a.cap = sp->cap; a.drafts = sp->drafts;
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(1), row_waves(d), sizeof(int) * 2 * (size_t)d->B, st, a);
+    ACAI_LAUNCH_CHECK("spec_accept");
+    return 0;
+}

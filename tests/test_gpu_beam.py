@@ -20,53 +20,10 @@ import torch
 from torch.amp import autocast
 
 from beam_reference import beam_generate
-from conftest import VOCAB, load_golden
+from conftest import load_golden
+from decode_support import build_vitomr, _decoder, dev, _same, _vit
 
 pytestmark = pytest.mark.gpu
-
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from acai_omr_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
-def build_vitomr(cfg, sd, dev, cache_dtype, max_batch=8):
-    from acai_omr_amd.models.models import FineTuneOMREncoder, OMRDecoder, TeacherForcedViTOMR
-    enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"], hidden_dim=cfg["enc_dim"],
-                             num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"])
-    dec = OMRDecoder(cfg["max_len"], VOCAB, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"], num_heads=cfg["dec_heads"], mlp_dim=cfg["dec_mlp"])
-    m = TeacherForcedViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"])
-    m.load_state_dict(sd)
-    if cache_dtype is not None:
-        cached = m.decoder.to_cached_version(max_batch, cache_dtype)
-        cached.load_state_dict(m.decoder.state_dict())
-        m.decoder = cached
-    return m.to(dev).eval()
-
-
-def _decoder(T, L=2, E=1024, H=16, Fd=4096, seed=5, scale=4.0):
-    """Random-init OMRDecoder with perturbed norms and the unembed scaled up (well separated decisions)."""
-    from acai_omr_amd.models.models import OMRDecoder
-    torch.manual_seed(seed)
-    dec = OMRDecoder(T, VOCAB, num_layers=L, hidden_dim=E, num_heads=H, mlp_dim=Fd)
-    with torch.no_grad():
-        for n, p in dec.named_parameters():
-            if "norm" in n:
-                p.add_(0.1 * torch.randn_like(p))
-        dec.unembed.weight.mul_(scale)
-    return dec
-
-
-def _vit(dec, max_batch, cdt, dev):
-    from acai_omr_amd.models.models import ViTOMR
-    c = dec.to_cached_version(max_batch, cdt)
-    c.load_state_dict(dec.state_dict())
-    return ViTOMR(None, None, c.to(dev).eval())
 
 
 def _padded(mem, lens, dev):
@@ -86,19 +43,13 @@ def _sd64(dec):
     return {"decoder." + k: v.detach().double() for k, v in dec.state_dict().items()}
 
 
-def _same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert x.dtype == y.dtype and x.shape == y.shape and torch.equal(x, y)
-
-
 # ---- 1. beam width 1 is greedy, bit for bit ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["vitomr_small", "vitomr_dh64", "vitomr_odd"])
 @pytest.mark.parametrize("cdt", [torch.float32, torch.bfloat16])
 def test_width_one_is_greedy_bitwise(dev, name, cdt):
     fx = load_golden(name)
     cfg, ref = fx["cfg"], fx["ref_fp32"]
-    m = build_vitomr(cfg, fx["state_dict"], dev, cdt)
+    m = build_vitomr(cfg, fx["state_dict"], dev, cdt, max_batch=8)
     with torch.no_grad():
         lat, mask = m.encoder(fx["imgs"])
         with autocast(device_type="cuda", dtype=torch.bfloat16, enabled=cdt == torch.bfloat16):
@@ -290,7 +241,7 @@ def test_inference_entry_point_and_errors(dev):
     _same(out4, b4)
     _same(out1, g)
     assert torch.equal(out1[0].cpu(), fx["ref_bf16"]["seqs"])
-    un = build_vitomr(cfg, fx["state_dict"], dev, None)
+    un = build_vitomr(cfg, fx["state_dict"], dev, None, max_batch=8)
     with torch.no_grad():
         lat, mask = un.encoder(fx["imgs"])
         with pytest.raises(RuntimeError, match="uncached"):

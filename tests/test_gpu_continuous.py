@@ -20,72 +20,11 @@ import torch
 from torch.amp import autocast
 
 from conftest import load_golden
+from decode_support import build_vitomr, _decoder, dev, _md, _memory, _same, _vit
 
 pytestmark = pytest.mark.gpu
 
 FIXTURES = ["vitomr_small", "vitomr_dh64", "vitomr_dh64b", "vitomr_odd"]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from acai_omr_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
-def build_vitomr(cfg, sd, dev, cache_dtype, max_batch=8):
-    from acai_omr_amd.models.models import FineTuneOMREncoder, OMRDecoder, TeacherForcedViTOMR
-    from conftest import VOCAB
-    enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"], hidden_dim=cfg["enc_dim"],
-                             num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"])
-    dec = OMRDecoder(cfg["max_len"], VOCAB, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"], num_heads=cfg["dec_heads"], mlp_dim=cfg["dec_mlp"])
-    m = TeacherForcedViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"])
-    m.load_state_dict(sd)
-    if cache_dtype is not None:
-        cached = m.decoder.to_cached_version(max_batch, cache_dtype)
-        cached.load_state_dict(m.decoder.state_dict())
-        m.decoder = cached
-    return m.to(dev).eval()
-
-
-def _decoder(T, L=2, E=1024, H=16, Fd=4096, seed=5, scale=4.0):
-    """Random-init OMRDecoder with perturbed norms and the unembed scaled up (well separated decisions), as tests/test_gpu_beam.py."""
-    from acai_omr_amd.models.models import OMRDecoder
-    from conftest import VOCAB
-    torch.manual_seed(seed)
-    dec = OMRDecoder(T, VOCAB, num_layers=L, hidden_dim=E, num_heads=H, mlp_dim=Fd)
-    with torch.no_grad():
-        for n, p in dec.named_parameters():
-            if "norm" in n:
-                p.add_(0.1 * torch.randn_like(p))
-        dec.unembed.weight.mul_(scale)
-    return dec
-
-
-def _vit(dec, max_batch, cdt, dev):
-    from acai_omr_amd.models.models import ViTOMR
-    c = dec.to_cached_version(max_batch, cdt)
-    c.load_state_dict(dec.state_dict())
-    return ViTOMR(None, None, c.to(dev).eval())
-
-
-def _same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert x.dtype == y.dtype and x.shape == y.shape and torch.equal(x, y)
-
-
-def _md(a, b):
-    return float((a.cpu().double() - b.cpu().double()).abs().max())
-
-
-def _memory(m, imgs, bf16):
-    with torch.no_grad():
-        lat, mask = m.encoder(imgs)
-        with autocast(device_type="cuda", dtype=torch.bfloat16, enabled=bf16):
-            return m.transition_head(lat), mask
 
 
 # ---- 1. fixtures, fp32 -------------------------------------------------------------------------------------------------------------------
@@ -94,7 +33,7 @@ def test_fp32_fixtures_vs_reference(dev, name):
     fx = load_golden(name)
     cfg, ref = fx["cfg"], fx["ref_fp32"]
     N, T = len(fx["imgs"]), cfg["gen_len"]
-    m = build_vitomr(cfg, fx["state_dict"], dev, torch.float32)
+    m = build_vitomr(cfg, fx["state_dict"], dev, torch.float32, max_batch=8)
     mem, mask = _memory(m, fx["imgs"], False)
     for slots in sorted({1, 2, N, N + 3}):   # N + 3: idle slots from the start
         with torch.no_grad():
@@ -134,7 +73,7 @@ def test_bf16_continuous_inference_vs_inference_and_reference(dev, name):
     fx = load_golden(name)
     cfg, ref = fx["cfg"], fx["ref_bf16"]
     T = cfg["gen_len"]
-    m = build_vitomr(cfg, fx["state_dict"], dev, torch.bfloat16)
+    m = build_vitomr(cfg, fx["state_dict"], dev, torch.bfloat16, max_batch=8)
     seqs, lps, smask = continuous_inference(m, fx["imgs"], "cuda", max_inference_len=T, slots=2)
     g = inference(m, fx["imgs"], "cuda", max_inference_len=T)
     assert torch.equal(seqs, g[0]) and torch.equal(smask, g[2])
@@ -281,7 +220,7 @@ def test_errors_and_c_abi_checks(dev):
     fx = load_golden("vitomr_dh64b")
     cfg = fx["cfg"]
     T = cfg["gen_len"]
-    m = build_vitomr(cfg, fx["state_dict"], dev, torch.float32)
+    m = build_vitomr(cfg, fx["state_dict"], dev, torch.float32, max_batch=8)
     mem, mask = _memory(m, fx["imgs"], False)
     with torch.no_grad():
         for s in (0, 9):
@@ -309,7 +248,7 @@ def test_errors_and_c_abi_checks(dev):
         finally:
             eng._desc.cross_group = 1
         torch.cuda.synchronize()
-    un = build_vitomr(cfg, fx["state_dict"], dev, None)
+    un = build_vitomr(cfg, fx["state_dict"], dev, None, max_batch=8)
     with torch.no_grad():
         lat, mask = un.encoder(fx["imgs"])
         with pytest.raises(RuntimeError, match="uncached"):

@@ -22,51 +22,13 @@ import pytest
 import torch
 from torch.amp import autocast
 
-from conftest import VOCAB, load_golden
+from conftest import load_golden
+from decode_support import build_vitomr, _decoder, dev, _md, _memory, _models, ref_objective_and_bonus, _reward_fn, _same, _vit, _vocab
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from acai_omr_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
 # ---- the set-up of tests/test_gpu_continuous.py -------------------------------------------------------------------------------------------
-def _decoder(T, L=2, E=1024, H=16, Fd=4096, seed=5, scale=4.0):
-    """Random-init OMRDecoder with perturbed norms and the unembed scaled up (well separated decisions), as tests/test_gpu_beam.py."""
-    from acai_omr_amd.models.models import OMRDecoder
-    torch.manual_seed(seed)
-    dec = OMRDecoder(T, VOCAB, num_layers=L, hidden_dim=E, num_heads=H, mlp_dim=Fd)
-    with torch.no_grad():
-        for n, p in dec.named_parameters():
-            if "norm" in n:
-                p.add_(0.1 * torch.randn_like(p))
-        dec.unembed.weight.mul_(scale)
-    return dec
-
-
-def _vit(dec, max_batch, cdt, dev, memory_cache_dtype=None):
-    from acai_omr_amd.models.models import ViTOMR
-    c = dec.to_cached_version(max_batch, cdt, memory_cache_dtype=memory_cache_dtype)
-    c.load_state_dict(dec.state_dict())
-    return ViTOMR(None, None, c.to(dev).eval())
-
-
-def _same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert x.dtype == y.dtype and x.shape == y.shape and torch.equal(x, y)
-
-
-def _md(a, b):
-    return float((a.cpu().double() - b.cpu().double()).abs().max())
-
-
 LENS = [256, 4096, 700, 1300, 3000, 512, 2048, 999, 4096, 300, 1500, 2600, 777, 3500, 1024, 2222]
 CAPS = [2, 8, 9, 16, 17, 96, 33, 50, 64, 5, 12, 24, 70, 96, 40, 3]
 OFFS = [sum(LENS[:i]) for i in range(len(LENS) + 1)]
@@ -260,31 +222,6 @@ def test_forms_agree_bitwise(dev):
 
 
 # ---- 5. isolation -------------------------------------------------------------------------------------------------------------------------
-def build_vitomr(cfg, sd, dev, cache_dtype, max_batch=8, grpo=False):
-    from acai_omr_amd.models.models import FineTuneOMREncoder, GRPOViTOMR, OMRDecoder, TeacherForcedViTOMR
-    enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"], hidden_dim=cfg["enc_dim"],
-                             num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"])
-    dec = OMRDecoder(cfg["max_len"], VOCAB, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"], num_heads=cfg["dec_heads"], mlp_dim=cfg["dec_mlp"],
-                     transformer_dropout=0.0)
-    m = TeacherForcedViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"])
-    m.load_state_dict(sd)
-    if grpo:
-        d = dec.to_cached_version(max_batch, cache_dtype) if cache_dtype is not None else dec
-        return GRPOViTOMR(m.encoder, m.transition_head, d, m.state_dict()).to(dev)
-    if cache_dtype is not None:
-        cached = m.decoder.to_cached_version(max_batch, cache_dtype)
-        cached.load_state_dict(m.decoder.state_dict())
-        m.decoder = cached
-    return m.to(dev).eval()
-
-
-def _memory(m, imgs, bf16):
-    with torch.no_grad():
-        lat, mask = m.encoder(imgs)
-        with autocast(device_type="cuda", dtype=torch.bfloat16, enabled=bf16):
-            return m.transition_head(lat), mask
-
-
 def test_sampled_slot_mode_leaves_other_modes_alone(dev):
     from acai_omr_amd import engine as EG
     from acai_omr_amd.inference.vitomr_inference import inference
@@ -295,7 +232,7 @@ def test_sampled_slot_mode_leaves_other_modes_alone(dev):
     caps = [T, T - 3, 5]
 
     def setup():
-        m = build_vitomr(cfg, fx["state_dict"], dev, torch.bfloat16, max_batch=16)
+        m = build_vitomr(cfg, fx["state_dict"], dev, torch.bfloat16, max_batch=16, transformer_dropout=0.0)
         mem, mask = _memory(m, fx["imgs"], True)
         return m, mem, mask
 
@@ -342,7 +279,7 @@ def test_cached_continuous_rollout_policy_vs_static(dev):
     fx = load_golden("vitomr_dh64b")
     cfg = fx["cfg"]
     N, T = len(fx["imgs"]), cfg["max_len"] - 2
-    big = build_vitomr(cfg, fx["state_dict"], dev, torch.float32, max_batch=16, grpo=True).eval()
+    big = build_vitomr(cfg, fx["state_dict"], dev, torch.float32, max_batch=16, grpo=True, transformer_dropout=0.0).eval()
     mem, mask = _memory(big, fx["imgs"], False)
     g = torch.Generator().manual_seed(21)
     U = torch.rand(N, T, generator=g).to(dev)
@@ -370,7 +307,7 @@ def test_cached_continuous_rollout_policy_vs_static(dev):
         assert torch.equal(got4[0], ref4[0]) and torch.equal(got4[2], ref4[2])
         assert _md(got4[1], ref4[1]) < 1e-4
         # more rollouts than the cache's max batch size
-        small = build_vitomr(cfg, fx["state_dict"], dev, torch.float32, max_batch=2, grpo=True).eval()
+        small = build_vitomr(cfg, fx["state_dict"], dev, torch.float32, max_batch=2, grpo=True, transformer_dropout=0.0).eval()
         with pytest.raises(ValueError, match="max batch size"):
             small.cached_forward_rollout_policy(mem, mask, T, 20, 1.1, uniforms=U)
         _same(ref, small.cached_continuous_rollout_policy(mem, mask, T, 20, 1.1, uniforms=U))
@@ -383,44 +320,6 @@ def test_cached_continuous_rollout_policy_vs_static(dev):
 
 
 # ---- 8. training surface ------------------------------------------------------------------------------------------------------------------
-def _vocab():
-    toks = [ln.strip() for ln in open(VOCAB) if ln.strip()]
-    return len(toks), toks.index("<pad>"), toks.index("<eos>")
-
-
-def ref_objective_and_bonus(logits, rollouts, mask, old_lp, adv, eps, num_groups):
-    """logits float64 [R, T, V] (requires_grad allowed); entropy terms with p == 0 count 0 (tests/test_gpu_grpo.py)."""
-    V = logits.shape[-1]
-    lsm = torch.log_softmax(logits, dim=-1)
-    lp = torch.gather(lsm, -1, rollouts[:, 1:logits.shape[1] + 1].unsqueeze(-1)).squeeze(-1)
-    ratios = torch.exp(lp - old_lp[:, 1:logits.shape[1] + 1].double())
-    a = adv.double().unsqueeze(1)
-    unclipped = (ratios * a).masked_fill(mask, 0)
-    clipped = (torch.clip(ratios, min=1 - eps, max=1 + eps) * a).masked_fill(mask, 0)
-    lens = (~mask).sum(dim=-1)
-    obj = (torch.minimum(unclipped, clipped).sum(-1) / lens).sum() / num_groups
-    p = torch.softmax(logits, dim=-1)
-    ent = torch.where(p > 0, -p * lsm, torch.zeros_like(p)).sum(-1).masked_fill(mask, 0)
-    bonus = (ent.sum(-1) / lens).mean() / float(torch.log(torch.tensor(V)))
-    return obj, bonus
-
-
-def _models(dev):
-    fx = load_golden("vitomr_dh64b")
-    cfg, sd = fx["cfg"], fx["state_dict"]
-    G = 3
-    old = build_vitomr(cfg, sd, dev, torch.bfloat16, max_batch=len(fx["imgs"]) * G, grpo=True).eval()
-    theta = build_vitomr(cfg, sd, dev, None, grpo=True).train()
-    return fx, old, theta, G, cfg
-
-
-def _reward_fn(rollouts, rollout_mask, target_lmx_seqs, batch):
-    from acai_omr_amd.train import grpo as G
-    _, pad, _ = _vocab()
-    r = G.calc_token_f1(rollouts, target_lmx_seqs.to(rollouts.device), pad) + 0.05 * rollout_mask.sum(-1).float()
-    return r.view(len(batch), -1)
-
-
 @pytest.mark.parametrize("lambda_ce", [0.1, 0.0])
 def test_grpo_update_with_rollout_slots_matches_a_reference_step(dev, lambda_ce):
     """test_grpo_update_matches_a_reference_step (tests/test_gpu_grpo.py) with rollout_slots set: the reference step is built on the
@@ -519,7 +418,7 @@ def test_validation_loop_vs_hand_rolled(dev):
     fx = load_golden("vitomr_dh64b")
     cfg = fx["cfg"]
     _, pad, _ = _vocab()
-    policy = build_vitomr(cfg, fx["state_dict"], dev, torch.float32, max_batch=4, grpo=True).eval()
+    policy = build_vitomr(cfg, fx["state_dict"], dev, torch.float32, max_batch=4, grpo=True, transformer_dropout=0.0).eval()
     g = torch.Generator().manual_seed(80)
     max_actions = cfg["max_len"] - 2
     imgs = fx["imgs"]

@@ -22,19 +22,11 @@ import torch
 import torch.nn.functional as F
 
 from conftest import VOCAB
+from decode_support import dev
 
 pytestmark = pytest.mark.gpu
 
 F64 = torch.float64
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from acai_omr_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 def ulp_bf16(a):
@@ -164,7 +156,7 @@ def _gemv(dev, B, N, K, *, xbf=False, ln=False, res=False, rln=None, gelu=False,
     return dict(err=float(err.max()), gap=gap, excess=excess, stats=st_err, y=y, stats_t=stats, xs=xs, lnw=lnw, lnb=lnb)
 
 
-# (form the launcher selects, cases).  The selection (decode.hip launch_skinny, bf16 weights, K % 256 == 0, 16-byte aligned operands):
+# (form the launcher selects, cases).  The selection (decode_gemv.hip launch_skinny, bf16 weights, K % 256 == 0, 16-byte aligned operands):
 #   fp32 x, K = 1024                  -> skinny_chain_kernel<false, LN, 4>        (LN = 1 with ln, 0 without)
 #   bf16 x, K = 4096, no ln           -> skinny_chain_kernel<true, 0, 16>
 #   fp32 x, K <= 1024 (not 1024)      -> skinny_mfma_kernel<false, 4, 4>

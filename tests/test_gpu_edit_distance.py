@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import VOCAB, load_golden
+from decode_support import _models
 from edit_distance_reference import edit_distance
 
 pytestmark = pytest.mark.gpu
@@ -268,34 +269,12 @@ def test_token_reward_rollouts_components(dev):
     assert torch.equal(got[0], rewards) and torch.equal(got[1].tedn_scores, comp.tedn_scores)
 
 
-def _policies(dev):
-    """The old / theta policy pair on the vitomr_dh64b fixture, three rollouts per image."""
-    from acai_omr_amd.models.models import FineTuneOMREncoder, GRPOViTOMR, OMRDecoder, TeacherForcedViTOMR
-    fx = load_golden("vitomr_dh64b")
-    cfg, sd = fx["cfg"], fx["state_dict"]
-
-    def tf():
-        enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"], hidden_dim=cfg["enc_dim"],
-                                 num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"])
-        dec = OMRDecoder(cfg["max_len"], VOCAB, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"], num_heads=cfg["dec_heads"],
-                         mlp_dim=cfg["dec_mlp"], transformer_dropout=0.0)
-        m = TeacherForcedViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"])
-        m.load_state_dict(sd)
-        return m, dec
-    G = 3
-    m_old, d_old = tf()
-    old = GRPOViTOMR(m_old.encoder, m_old.transition_head, d_old.to_cached_version(len(fx["imgs"]) * G, torch.bfloat16), m_old.state_dict()).to(dev).eval()
-    m_th, d_th = tf()
-    theta = GRPOViTOMR(m_th.encoder, m_th.transition_head, d_th, m_th.state_dict()).to(dev).train()
-    return fx, old, theta, G, cfg
-
-
 def test_grpo_update_with_the_token_reward(dev):
     """grpo_update runs on a reward from the package alone: the average reward it returns is the mean of token_reward_rollouts on the rollouts it
     drew, and the step moves the parameters."""
     from acai_omr_amd.models.models import OMRCELoss
     from acai_omr_amd.train import grpo as GR
-    fx, old, theta, Gs, cfg = _policies(dev)
+    fx, old, theta, Gs, cfg = _models(dev)
     _, pad = _vocab()
     g = torch.Generator().manual_seed(60)
     max_actions = cfg["max_len"] - 2

@@ -15,20 +15,12 @@ import torch
 from torch.amp import autocast
 
 from conftest import VOCAB, load_golden
+from decode_support import build_vitomr, dev
 
 pytestmark = pytest.mark.gpu
 
 F8 = torch.float8_e4m3fn
 F64 = torch.float64
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from acai_omr_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 def _small_decoder(E, H, L=2, T=32, seed=1):
@@ -176,19 +168,6 @@ def test_full_width_decoder_steps_fp8_memory(dev):
 
 
 # ---- 4. entry points ---------------------------------------------------------------------------------------------------------------------
-def _build(cfg, sd, dev, mdt, max_batch=8):
-    from acai_omr_amd.models.models import FineTuneOMREncoder, OMRDecoder, TeacherForcedViTOMR
-    enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"], hidden_dim=cfg["enc_dim"],
-                             num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"])
-    dec = OMRDecoder(cfg["max_len"], VOCAB, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"], num_heads=cfg["dec_heads"], mlp_dim=cfg["dec_mlp"])
-    m = TeacherForcedViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"])
-    m.load_state_dict(sd)
-    cached = m.decoder.to_cached_version(max_batch, torch.bfloat16, mdt)
-    cached.load_state_dict(m.decoder.state_dict())
-    m.decoder = cached
-    return m.to(dev).eval()
-
-
 def _rows_equal(a, b):
     return a.shape == b.shape and torch.equal(a, b)
 
@@ -201,7 +180,7 @@ def test_entry_points_agree_on_fp8_memory(dev, name):
     from acai_omr_amd.inference.vitomr_inference import continuous_inference, inference, streamed_inference
     fx = load_golden(name)
     cfg, sd, imgs, T = fx["cfg"], fx["state_dict"], fx["imgs"], fx["cfg"]["gen_len"]
-    m = _build(cfg, sd, dev, F8)
+    m = build_vitomr(cfg, sd, dev, torch.bfloat16, max_batch=8, memory_cache_dtype=F8)
     blocks = m.decoder.decoder_blocks
     seqs, lps, mask = inference(m, imgs, "cuda", max_inference_len=T)
     eng = blocks.engine(dev)
@@ -239,7 +218,7 @@ def test_entry_points_agree_on_fp8_memory(dev, name):
             assert torch.equal(cs[r, :n], si[0]) and torch.equal(cl[r, :n], li[0]), r
             assert bool((cs[r, n:] == m.decoder.pad_idx).all()), r
     # allocation: at most (dhp8 + 4) / (2 dhp) of the bf16 engine's, prepared on the same memories
-    mb, m8 = _build(cfg, sd, dev, None), _build(cfg, sd, dev, F8)
+    mb, m8 = (build_vitomr(cfg, sd, dev, torch.bfloat16, max_batch=8, memory_cache_dtype=mdt) for mdt in (None, F8))
     inference(mb, imgs, "cuda", max_inference_len=T)
     inference(m8, imgs, "cuda", max_inference_len=T)
     eb, eng = mb.decoder.decoder_blocks.engine(dev), m8.decoder.decoder_blocks.engine(dev)

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import VOCAB, load_golden
+from decode_support import _models, ref_objective_and_bonus, _reward_fn, _vocab
 
 pytestmark = pytest.mark.gpu
 
@@ -18,29 +19,6 @@ def dev():
     from acai_omr_amd import _lib
     _lib.lib()
     return "cuda"
-
-
-def _vocab():
-    toks = [ln.strip() for ln in open(VOCAB) if ln.strip()]
-    return len(toks), toks.index("<pad>"), toks.index("<eos>")
-
-
-# ---- float64 reference formulas (written from the issue's statement of omr_grpo_train.py:240-283) -----------------------------------------
-def ref_objective_and_bonus(logits, rollouts, mask, old_lp, adv, eps, num_groups):
-    """logits float64 [R, T, V] (requires_grad allowed); entropy terms with p == 0 count 0."""
-    V = logits.shape[-1]
-    lsm = torch.log_softmax(logits, dim=-1)
-    lp = torch.gather(lsm, -1, rollouts[:, 1:logits.shape[1] + 1].unsqueeze(-1)).squeeze(-1)
-    ratios = torch.exp(lp - old_lp[:, 1:logits.shape[1] + 1].double())
-    a = adv.double().unsqueeze(1)
-    unclipped = (ratios * a).masked_fill(mask, 0)
-    clipped = (torch.clip(ratios, min=1 - eps, max=1 + eps) * a).masked_fill(mask, 0)
-    lens = (~mask).sum(dim=-1)
-    obj = (torch.minimum(unclipped, clipped).sum(-1) / lens).sum() / num_groups
-    p = torch.softmax(logits, dim=-1)
-    ent = torch.where(p > 0, -p * lsm, torch.zeros_like(p)).sum(-1).masked_fill(mask, 0)
-    bonus = (ent.sum(-1) / lens).mean() / float(torch.log(torch.tensor(V)))
-    return obj, bonus
 
 
 def _fused(logits, rollouts, mask, old_lp, adv, eps, num_groups):
@@ -250,35 +228,6 @@ def test_decoder_memory_group_size_vs_float64_oracle(dev):
 
 
 # ---- the full step -------------------------------------------------------------------------------------------------------------------------
-def _models(dev):
-    from acai_omr_amd.models.models import FineTuneOMREncoder, GRPOViTOMR, OMRDecoder, TeacherForcedViTOMR
-    fx = load_golden("vitomr_dh64b")
-    cfg, sd = fx["cfg"], fx["state_dict"]
-
-    def tf():
-        enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"], hidden_dim=cfg["enc_dim"],
-                                 num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"])
-        dec = OMRDecoder(cfg["max_len"], VOCAB, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"], num_heads=cfg["dec_heads"], mlp_dim=cfg["dec_mlp"],
-                         transformer_dropout=0.0)
-        m = TeacherForcedViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"])
-        m.load_state_dict(sd)
-        return m, dec
-    G = 3
-    R = len(fx["imgs"]) * G
-    m_old, d_old = tf()
-    old = GRPOViTOMR(m_old.encoder, m_old.transition_head, d_old.to_cached_version(R, torch.bfloat16), m_old.state_dict()).to(dev).eval()
-    m_th, d_th = tf()
-    theta = GRPOViTOMR(m_th.encoder, m_th.transition_head, d_th, m_th.state_dict()).to(dev).train()
-    return fx, old, theta, G, cfg
-
-
-def _reward_fn(rollouts, rollout_mask, target_lmx_seqs, batch):
-    from acai_omr_amd.train import grpo as G
-    _, pad, _ = _vocab()
-    r = G.calc_token_f1(rollouts, target_lmx_seqs.to(rollouts.device), pad) + 0.05 * rollout_mask.sum(-1).float()
-    return r.view(len(batch), -1)
-
-
 @pytest.mark.parametrize("lambda_ce", [0.1, 0.0])
 def test_grpo_update_matches_a_reference_step(dev, lambda_ce):
     """One grpo_update (update_epochs = 1, plain SGD so that the parameter change IS the clipped gradient) against the same step built from

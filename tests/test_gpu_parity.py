@@ -528,7 +528,7 @@ def test_decode_is_deterministic_run_to_run(dev):
 
 
 def test_decode_split_merge_runs_in_launch_on_this_toolchain(dev):
-    """The headline decode step merges its attention splits inside the attention launches (decode.hip, last-arriver hand-off) only at the
+    """The headline decode step merges its attention splits inside the attention launches (decode_attn.hip, last-arriver hand-off) only at the
     workgroup residency it was validated at; otherwise it silently takes a separate combine launch (12 more launches per step: 0.712 against
     0.689 ms - round 4 shipped that way for a while because the check compared the occupancy API's answer with the wrong number).  On this
     pool's toolchain the validated path must be the one in use; a red test here after a ROCm upgrade means: re-run the determinism test and

@@ -19,47 +19,12 @@ from torch.amp import autocast
 
 import speculative_reference as SR
 from conftest import load_golden
+from decode_support import build_vitomr, dev, _memory, _same
 
 pytestmark = pytest.mark.gpu
 
 FIXTURES = ["vitomr_small", "vitomr_dh64", "vitomr_dh64b", "vitomr_odd"]
 DS = [1, 2, 4, 7]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from acai_omr_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
-def build_vitomr(cfg, sd, dev, cache_dtype, max_batch=24, memory_cache_dtype=None):
-    from acai_omr_amd.models.models import FineTuneOMREncoder, OMRDecoder, TeacherForcedViTOMR
-    from conftest import VOCAB
-    enc = FineTuneOMREncoder(cfg["P"], cfg["pe_h"], cfg["pe_w"], cfg["ft_depth"], num_layers=cfg["enc_layers"], hidden_dim=cfg["enc_dim"],
-                             num_heads=cfg["enc_heads"], mlp_dim=cfg["enc_mlp"])
-    dec = OMRDecoder(cfg["max_len"], VOCAB, num_layers=cfg["dec_layers"], hidden_dim=cfg["dec_dim"], num_heads=cfg["dec_heads"], mlp_dim=cfg["dec_mlp"])
-    m = TeacherForcedViTOMR(enc, None, dec, transition_head_dim=cfg["head_dim"])
-    m.load_state_dict(sd)
-    cached = m.decoder.to_cached_version(max_batch, cache_dtype, memory_cache_dtype)
-    cached.load_state_dict(m.decoder.state_dict())
-    m.decoder = cached
-    return m.to(dev).eval()
-
-
-def _same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert x.dtype == y.dtype and x.shape == y.shape and torch.equal(x, y)
-
-
-def _memory(m, imgs, bf16):
-    with torch.no_grad():
-        lat, mask = m.encoder(imgs)
-        with autocast(device_type="cuda", dtype=torch.bfloat16, enabled=bf16):
-            return m.transition_head(lat), mask
 
 
 def _tables(greedy, max_len, V):
@@ -102,7 +67,7 @@ def test_equals_greedy_and_step_counts(dev, name, cdt):
     cfg = fx["cfg"]
     T = cfg["gen_len"]
     bf = cdt == torch.bfloat16
-    m = build_vitomr(cfg, fx["state_dict"], dev, cdt)
+    m = build_vitomr(cfg, fx["state_dict"], dev, cdt, max_batch=24)
     V, eos = m.decoder.vocab_size, m.decoder.eos_idx
     mem_all, mask_all = _memory(m, fx["imgs"], bf)
     last = len(fx["imgs"]) - 1
@@ -177,7 +142,7 @@ def test_eos_and_max_len_inside_an_accepted_run(dev, cdt):
     fx = load_golden("vitomr_dh64b")
     cfg = fx["cfg"]
     bf = cdt == torch.bfloat16
-    m = build_vitomr(cfg, fx["state_dict"], dev, cdt)
+    m = build_vitomr(cfg, fx["state_dict"], dev, cdt, max_batch=24)
     V = m.decoder.vocab_size
     mem, mask = _memory(m, fx["imgs"], bf)
     Tfull = cfg["gen_len"]
@@ -195,7 +160,7 @@ def test_eos_and_max_len_inside_an_accepted_run(dev, cdt):
             _same(g, _spec(m, mem, mask, T, D)[0])
         # <eos> inside an accepted run: the token image 0 emits at index 6 becomes <eos> (images 1 and 2 emit it elsewhere or never), on a
         # fresh model - captured decode graphs hold the <eos> id they were captured with
-        m = build_vitomr(cfg, fx["state_dict"], dev, cdt)
+        m = build_vitomr(cfg, fx["state_dict"], dev, cdt, max_batch=24)
         old = m.decoder.eos_idx
         m.decoder.eos_idx = int(g0[0][0, 6])
         try:
@@ -220,7 +185,7 @@ def test_eos_and_max_len_inside_an_accepted_run(dev, cdt):
 def test_ngram_proposals_equal_the_restatement(dev, name):
     fx = load_golden(name)
     cfg = fx["cfg"]
-    m = build_vitomr(cfg, fx["state_dict"], dev, torch.float32)
+    m = build_vitomr(cfg, fx["state_dict"], dev, torch.float32, max_batch=24)
     mem, mask = _memory(m, fx["imgs"], False)
     T = cfg["max_len"]   # the longest run the cache allows: the toy decoders repeat themselves
     eng = m.decoder.decoder_blocks.engine(dev)
