@@ -2503,8 +2503,14 @@ extern "C" int acai_cross_kv_prefill(const void *mem, int ldm, const void *Wkv, 
                                      const int32_t *row_pos, const int64_t *seq_off, const int32_t *seq_len, void *k_out,
                                      void *v_out, int M, int E, int H, int dh, int dhp, int dtype, int flags, void *stream) {
     ACAI_CHECK_ARG(mem && Wkv && row_seq && row_pos && seq_off && seq_len && k_out && v_out, "acai_cross_kv_prefill: null operand");
+    // (the scatter epilogue divides by E and dh)
+    ACAI_CHECK_ARG(M >= 0 && E > 0 && H > 0 && dh > 0, "acai_cross_kv_prefill: bad shape M=%d E=%d H=%d dh=%d", M, E, H, dh);
     ACAI_CHECK_ARG(E == H * dh && dhp >= dh && ldm >= E && ldw >= E, "acai_cross_kv_prefill: bad dims E=%d H=%d dh=%d dhp=%d", E, H, dh, dhp);
     ACAI_CHECK_ARG(dtype == ACAI_F32 || dtype == ACAI_BF16, "acai_cross_kv_prefill: bad dtype");
+    // The scatter epilogue applies no flag: a bf16 cache is rounded by its store (ROUND_BF16 is a no-op there), an fp32 cache would silently
+    // stay unrounded, and there is no GELU form.
+    ACAI_CHECK_ARG((flags & ~ACAI_GEMM_ROUND_BF16) == 0, "acai_cross_kv_prefill: flag bits 0x%x (only ACAI_GEMM_ROUND_BF16 is accepted)", flags);
+    ACAI_CHECK_ARG(!(flags & ACAI_GEMM_ROUND_BF16) || dtype == ACAI_BF16, "acai_cross_kv_prefill: ACAI_GEMM_ROUND_BF16 needs a bf16 cache (fp32 output is not rounded)");
     if (M == 0) return 0;
     GemmArgs g{};
     g.A = mem; g.W = Wkv; g.bias = bkv; g.lda = ldm; g.ldw = ldw; g.M = M; g.N = 2 * E; g.K = E;

@@ -78,7 +78,13 @@ int acai_gemm_dw(const void *dY, int ldy, const void *X, int ldx, float *dW, int
 
 /* MemoryCache.cache_memory_keys_and_vals (K:235-253): KV = mem . W_kv^T + b_kv with W_kv = rows E..3E of the
  * cross-attention in_proj; written head-major and ragged for the decode kernels:
- * k_out[seq_off[b] + (h*len[b] + s)*dhp + d], same for v_out; row_seq/row_pos give (b, s) of each memory row. */
+ * k_out[seq_off[b] + (h*len[b] + s)*dhp + d], same for v_out; row_seq/row_pos give (b, s) of each memory row.
+ * The memory rows may come in any order (row_seq / row_pos need not be sorted; seq_off need not be monotonic), as long as each (b, s)
+ * occurs once.  Only the lanes d < dh are written: the pad lanes [dh, dhp) of every row, and whatever lies between the sequences' regions,
+ * keep their contents - the caller zeroes the buffers once (the engine allocates them with torch.zeros).
+ * M >= 0 (0: nothing is written), E = H * dh, H and dh > 0, dhp >= dh.  flags: 0 or ACAI_GEMM_ROUND_BF16, the latter only with
+ * dtype = ACAI_BF16, where the store rounds to bf16 anyway (the flag changes nothing); ACAI_GEMM_ROUND_BF16 with an fp32 cache,
+ * ACAI_GEMM_GELU and unknown bits are refused. */
 int acai_cross_kv_prefill(const void *mem, int ldm, const void *Wkv, int ldw, const float *bkv, const int32_t *row_seq,
                           const int32_t *row_pos, const int64_t *seq_off, const int32_t *seq_len, void *k_out, void *v_out,
                           int M, int E, int H, int dh, int dhp, int dtype, int flags, void *stream);

@@ -200,6 +200,32 @@ def test_attn_backward_workspace_query_matches_the_dispatch():
     assert q(4, 16, 32, 512, 400, 2048, 1600, 0, bf, 0.0, 1) == 0          # short key side
 
 
+def test_cross_kv_prefill_refuses_bad_shapes_and_flags():
+    """acai_cross_kv_prefill validates on the host before any launch: its scatter epilogue divides by E and dh and applies no flag, so
+    non-positive dims, ACAI_GEMM_GELU, unknown bits and ACAI_GEMM_ROUND_BF16 with an fp32 cache (which would stay unrounded) are errors.
+    M = 0 throughout (except the M < 0 case): a call that passed the checks returns 0 without touching the operands or a device."""
+    import ctypes
+    from acai_omr_amd import _lib
+    L = _lib.lib()
+    bf, f32, GELU, ROUND = _lib.ACAI_BF16, _lib.ACAI_F32, _lib.GEMM_GELU, _lib.GEMM_ROUND_BF16
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)
+
+    def call(M=0, E=8, H=2, dh=4, dhp=4, dtype=bf, flags=0, bias=p):
+        return L.acai_cross_kv_prefill(p, E, p, E, bias, p, p, p, p, p, p, M, E, H, dh, dhp, dtype, flags, None)
+
+    assert call() == 0 and call(bias=None) == 0 and call(dtype=f32) == 0 and call(dhp=8) == 0
+    assert call(flags=ROUND) == 0                                   # legal with a bf16 cache (a no-op: the store rounds)
+    for bad, word in ((dict(M=-1), "bad shape"), (dict(E=0, H=0, dh=4), "bad shape"), (dict(E=0, H=2, dh=0), "bad shape"),
+                      (dict(E=0, H=0, dh=0), "bad shape"), (dict(E=8, H=-2, dh=-4), "bad shape"), (dict(E=-8, H=2, dh=-4), "bad shape"),
+                      (dict(flags=GELU), "flag bits 0x1"), (dict(flags=GELU | ROUND), "flag bits 0x3"), (dict(flags=4), "flag bits 0x4"),
+                      (dict(flags=ROUND | 256), "flag bits 0x102"), (dict(flags=-1), "flag bits"),
+                      (dict(flags=ROUND, dtype=f32), "needs a bf16 cache")):
+        assert call(**bad) != 0, bad
+        assert word in L.acai_last_error().decode(), (bad, L.acai_last_error().decode())
+    assert call(E=8, H=2, dh=3) != 0 and call(dh=4, dhp=3) != 0 and call(dtype=2) != 0   # the checks that were there before
+
+
 def test_asm_checks_flag_what_they_are_for():
     """acai_omr_amd/_asmcheck.py runs inside _lib.build() and fails the build: (1) a register written by an inline-asm load the compiler cannot
     see, touched before the kernel's counted vmcnt wait (the miscompile gemm_nt_pp_kernel once hit); (2) more LDS operations behind the staged
