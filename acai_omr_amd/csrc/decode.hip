@@ -68,6 +68,13 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
     probe.x = d->x; probe.W = d->layers[0].self_in_w; probe.K = E; probe.ldw = E; probe.ldx = E;
     const bool fused = sizeof(TW) == 2 && d->stats && rnd && skinny_mfma_ok(probe) && (F % 256 == 0) && F <= SKM_MAXK;
     bool hid_bf16 = false, hid_in_bf16 = false;
+    // The per-row attention kernel, when it finishes its output inside its own launch, stores the (bf16-valued) rows as bf16 and the out /
+    // cross-out GEMV takes the bf16-activation chain form at K = 1024: half the bytes every workgroup of the GEMV stages.  attn_bf16 says
+    // what the last attend() left in d->attn.  ACAI_ATTN_BF16=0 keeps fp32 rows (A/B aid).
+    static const bool no_chain = getenv("ACAI_SKINNY_CHAIN") && atoi(getenv("ACAI_SKINNY_CHAIN")) == 0;
+    static const bool no_attn_bf16 = getenv("ACAI_ATTN_BF16") && atoi(getenv("ACAI_ATTN_BF16")) == 0;
+    const bool attn_bf16_ok = fused && E == 1024 && !no_chain && !no_attn_bf16;
+    bool attn_bf16 = false;
     // every GEMV of the step: y = x . W^T + bias (+ res); kvl: append the self K/V; lnw / lnb: LayerNorm (eps) of x on load, its row
     // statistics published to stats_out; rlnw / rlnb / rstats: LayerNorm of res from published statistics; ln2w / ln2b: a second
     // LayerNorm (eps 1e-6) after the first (unembed).  The LayerNorm operands are only passed on the fused path.
@@ -126,8 +133,11 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
         // the splits are merged by the launch itself (one split, or tickets at a validated residency), else by a separate combine launch
         // behind the per-row kernel
         const bool merge = a.nsplit > 1 && d->tickets && (group > 1 || dattn_merge_in_launch(f8 ? ACAI_FP8_E4M3 : DT<TW>::id, a.dhp));
+        attn_bf16 = false;
         if (a.nsplit == 1 || merge) {
             a.out = d->attn; a.ldo = E; a.round_out = rnd ? 1 : 0;
+            attn_bf16 = attn_bf16_ok && group == 1 && !f8;   // (the matrix-core and FP8 kernels and the combine launch keep fp32 rows)
+            a.out_bf16 = attn_bf16 ? 1 : 0;
             if (merge) a.tickets = d->tickets;
             return group > 1 ? launch_dattn_group(a, B, group, st) : per_row();
         }
@@ -143,10 +153,14 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
             const AcaiDecLayer *ly = d->layers + l;
             if ((rc = skinny(zin, E, ly->self_in_w, ly->self_in_b, nullptr, d->qkv, 3 * E, 3 * E, E, rnd, ly, lnw, lnb, st0))) return rc;
             if ((rc = attend(d->qkv, 3 * E, ly->k_self, ly->v_self, false))) return rc;
+            hid_in_bf16 = attn_bf16;
             if ((rc = skinny(d->attn, E, ly->self_out_w, ly->self_out_b, zin, z1, E, E, E, rnd, nullptr, nullptr, nullptr, nullptr, lnw, lnb, st0))) return rc;
+            hid_in_bf16 = false;
             if ((rc = skinny(z1, E, ly->cross_q_w, ly->cross_q_b, nullptr, d->qkv, 3 * E, E, E, rnd, nullptr, ly->n1_w, ly->n1_b, st1))) return rc;
             if ((rc = attend(d->qkv, 3 * E, ly->k_cross, ly->v_cross, true, ly))) return rc;
+            hid_in_bf16 = attn_bf16;
             if ((rc = skinny(d->attn, E, ly->cross_out_w, ly->cross_out_b, z1, z2, E, E, E, rnd, nullptr, nullptr, nullptr, nullptr, ly->n1_w, ly->n1_b, st1))) return rc;
+            hid_in_bf16 = false;
             hid_bf16 = true;   // linear1 -> GELU output is bf16 under autocast anyway: store it as such (half the x bytes of linear2)
             if ((rc = skinny(z2, E, ly->lin1_w, ly->lin1_b, nullptr, d->hid, F, F, E, rnd | ACAI_GEMM_GELU, nullptr, ly->n2_w, ly->n2_b, st2))) return rc;
             hid_bf16 = false;
@@ -158,8 +172,7 @@ int decode_core(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st, boo
         }
         // x = norm3(z3) of the last layer, then the stack's final norm (eps 1e-6): both fused into the unembed GEMV's load when the chain
         // kernel takes it (E = 1024) - no stand-alone LayerNorm launch is left in a token step
-        static const bool no_chain2 = getenv("ACAI_SKINNY_CHAIN") && atoi(getenv("ACAI_SKINNY_CHAIN")) == 0;
-        if (do_unembed && d->fn_w && E == 1024 && !no_chain2 && lnw) return unembed(zin, lnw, lnb, 1e-5f, d->fn_w, d->fn_b);
+        if (do_unembed && d->fn_w && E == 1024 && !no_chain && lnw) return unembed(zin, lnw, lnb, 1e-5f, d->fn_w, d->fn_b);
         if ((rc = acai_layernorm_fwd(zin, lnw, lnb, 1e-5f, d->proj, nullptr, B, E, st))) return rc;
         if (do_unembed && d->fn_w) return unembed(d->proj, d->fn_w, d->fn_b, 1e-6f, nullptr, nullptr);
         if (d->fn_w) {

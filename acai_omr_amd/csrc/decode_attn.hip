@@ -243,7 +243,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
         if (d < a.dh) {
             float o = v / lsum;
             if (a.round_out) o = round_bf16(o);
-            a.out[(size_t)b * a.ldo + h * a.dh + d] = o;
+            if (a.out_bf16) reinterpret_cast<bf16_t *>(a.out)[(size_t)b * a.ldo + h * a.dh + d] = f2bf(o);   // (exact: o is a bf16 value)
+            else a.out[(size_t)b * a.ldo + h * a.dh + d] = o;
         }
         return;
     }
@@ -309,7 +310,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
     if (d < a.dh) {
         float o = om / lm;
         if (a.round_out) o = round_bf16(o);
-        a.out[(size_t)b * a.ldo + h * a.dh + d] = o;
+        if (a.out_bf16) reinterpret_cast<bf16_t *>(a.out)[(size_t)b * a.ldo + h * a.dh + d] = f2bf(o);
+        else a.out[(size_t)b * a.ldo + h * a.dh + d] = o;
     }
 }
 

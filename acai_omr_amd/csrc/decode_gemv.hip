@@ -396,7 +396,7 @@ __global__ __launch_bounds__(64 * NW) void skinny_mfma_kernel(SkinnyArgs a) {
     }
 }
 
-// ---- the decode chain's GEMV at its two hot shapes (K = 256 * NW: K = 1024 fp32 activations, K = 4096 bf16 activations) ------------------
+// ---- the decode chain's GEMV at its hot shapes (K = 256 * NW: K = 1024 fp32 or bf16 activations, K = 4096 bf16 activations) --------------
 // Same arithmetic and fusions as skinny_mfma_kernel (bit-identical results), rebuilt around what in-kernel stamps showed on MI355X
 // (tools/stamp_decode.py): of a 5-7 us launch, 2.7-5.2 us passed before the activation image was complete and ~1 us in the epilogue, because
 //   * the compiler fetched the 200-byte argument struct in SIX dependent scalar-load stages (each a cold round trip after a kernel boundary):
@@ -441,11 +441,30 @@ __global__ __launch_bounds__(64 * NW) void skinny_chain_kernel(SkinnyArgs a) {
         for (int c = 0; c < 8; ++c) wf[c] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, woff + 64 * c, 0, 2);
     };
 
-    if constexpr (XBF16) {
+    if constexpr (XBF16 && NW == 4) {
+        // K = 1024, bf16 rows (the attention output as decode_attn_kernel stores it): the image is copied as it is, wave w takes rows w and
+        // w + 4 (then w + 8, w + 12 when the tile has more than 8 rows), a row = two coalesced 1 KB loads.  A wave without a row copies row 0
+        // again (same bytes to the same place) instead of branching around its loads.
+        auto copy = [&](int ra, int rb, bool first) {
+            const int ca = ra < nb ? ra : 0, cb = rb < nb ? rb : 0;
+            const bf16_t *pa = reinterpret_cast<const bf16_t *>(a.x) + (size_t)(bt + ca) * a.ldx + lane * 8;
+            const bf16_t *pb = reinterpret_cast<const bf16_t *>(a.x) + (size_t)(bt + cb) * a.ldx + lane * 8;
+            const uint4 a0 = *reinterpret_cast<const uint4 *>(pa), a1 = *reinterpret_cast<const uint4 *>(pa + 512),
+                        b0 = *reinterpret_cast<const uint4 *>(pb), b1 = *reinterpret_cast<const uint4 *>(pb + 512);
+            __builtin_amdgcn_sched_barrier(0);
+            if (first) request_weights();   // behind this wave's activation rows: loads return in issue order
+            __builtin_amdgcn_sched_barrier(0);
+            *reinterpret_cast<uint4 *>(xs + ca * PITCH + lane * 16) = a0;
+            *reinterpret_cast<uint4 *>(xs + ca * PITCH + lane * 16 + 1024) = a1;
+            *reinterpret_cast<uint4 *>(xs + cb * PITCH + lane * 16) = b0;
+            *reinterpret_cast<uint4 *>(xs + cb * PITCH + lane * 16 + 1024) = b1;
+        };
+        copy(wave, wave + 4, true);
+        if (nb > 8) copy(wave + 8, wave + 12, false);
+    } else if constexpr (XBF16) {
         // activation rows are bf16 already: the [nb][K] image is copied in half-row chunks (4 KB), wave w takes chunk w (and w + 16 when the
         // tile has more than 8 rows): every wave has 4 loads in flight, none idles.  A wave without a chunk copies chunk 0 again (same bytes
         // to the same place) instead of branching around its loads.
-        static_assert(!XBF16 || NW == 16, "bf16 activations: K = 4096");
         auto copy = [&](int ch, bool first) {
             const int c = ch < 2 * nb ? ch : 0;
             const bf16_t *xr = reinterpret_cast<const bf16_t *>(a.x) + (size_t)(bt + (c >> 1)) * a.ldx + (c & 1) * (K / 2) + lane * 8;
@@ -664,17 +683,19 @@ int launch_skinny(const SkinnyArgs &a, hipStream_t st) {
             static const bool no_chain = getenv("ACAI_SKINNY_CHAIN") && atoi(getenv("ACAI_SKINNY_CHAIN")) == 0;   // A/B aid
             const bool chain_ok = !no_chain && (size_t)a.N * a.ldw * 2 < 0xFFF00000u && (a.ldx % 8 == 0);   // (row statistics are only published with a LayerNorm on load, as in skinny_mfma_kernel)
             if (a.ln2_w && !(chain_ok && a.K == 1024 && !a.x_bf16 && a.ln_w)) return acai_set_err(-1, "skinny_gemm: the double LayerNorm needs the chain kernel (K = 1024, fp32 activations)");
-            if (chain_ok && ((a.K == 1024 && !a.x_bf16) || (a.K == 4096 && a.x_bf16 && !a.ln_w))) {
+            if (chain_ok && (a.K == 1024 || (a.K == 4096 && a.x_bf16))) {   // (bf16 activations never carry a LayerNorm on load: refused above)
                 static bool attr2[ACAI_MAX_DEV] = {};
                 if (acai_first_on_device(attr2)) {
                     hipFuncSetAttribute(reinterpret_cast<const void *>(skinny_chain_kernel<true, 0, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
                     hipFuncSetAttribute(reinterpret_cast<const void *>(skinny_chain_kernel<true, 0, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
                 }
                 const dim3 cgrid(cdiv(a.N, b.rows_per_block), cdiv(a.B, 16));
-                const int nw = a.x_bf16 ? 16 : 4;
+                const int nw = a.K == 4096 ? 16 : 4;
                 const size_t clds = (size_t)nw * 1024 + (size_t)rows * (a.K * 2 + 16);
                 static const bool wfirst = getenv("ACAI_LIN2_WFIRST") && atoi(getenv("ACAI_LIN2_WFIRST")) == 1;   // A/B aid
-                if (a.x_bf16 && wfirst)
+                if (a.x_bf16 && a.K == 1024)
+                    hipLaunchKernelGGL((skinny_chain_kernel<true, 0, 4>), cgrid, dim3(256), clds, st, b);
+                else if (a.x_bf16 && wfirst)
                     hipLaunchKernelGGL((skinny_chain_kernel<true, 0, 16, true>), cgrid, dim3(1024), clds, st, b);
                 else if (a.x_bf16)
                     hipLaunchKernelGGL((skinny_chain_kernel<true, 0, 16>), cgrid, dim3(1024), clds, st, b);

@@ -60,6 +60,9 @@ struct DAttnArgs {
     long long anc_bstride;   // elements between the two parity copies (rows * anc_pitch); SPEC: rows per image
     // FP8 memory cache (fp8e4m3_t instantiation only): one fp32 power-of-two scale per K row and per V row, at the row's element offset / dhp
     const float *k_scale, *v_scale;
+    // decode_attn_kernel only: out holds bf16 rows (ldo in bf16 elements) - the fused step's values are bf16-representable already (round_out),
+    // and the out / cross-out GEMV then stages half the bytes.  Appended, so that every other member keeps its offset.
+    int out_bf16;
 };
 
 // Element type of an FP8 (OCP e4m3fn) cross K/V cache: a stored value is q * 2^e, 2^e the row's scale (acai_cross_kv_quantize_fp8)

@@ -40,6 +40,7 @@ def run(name, N, K, xdt, ln, res, ydt=torch.float32, gelu=False):
 
 run("qkv (LN on load)", 3072, 1024, torch.float32, True, 0)
 run("out (res+rLN)", 1024, 1024, torch.float32, False, 2)
+run("out (bf16 x, res+rLN)", 1024, 1024, torch.bfloat16, False, 2)
 run("out (plain res)", 1024, 1024, torch.float32, False, 1)
 run("crossq (LN on load)", 1024, 1024, torch.float32, True, 0)
 run("lin1 (LN, gelu, bf16 out)", 4096, 1024, torch.float32, True, 0, torch.bfloat16, True)
