@@ -61,6 +61,10 @@ class AcaiSpec(Structure):
     _fields_ = [(n, c_int32) for n in ("D", "ngram", "pitch", "rows")] + [(n, c_void_p) for n in ("t", "cap", "steps", "tab", "next", "drafts")]
 
 
+class AcaiPrompt(Structure):
+    _fields_ = [("tok", c_void_p), ("len", c_void_p), ("pitch", c_int32), ("rows", c_int32)]
+
+
 AUG_MAX_TAPS, AUG_MEAN_PARTS = 32, 128
 AUG_BRIGHTNESS, AUG_CONTRAST, AUG_BRIGHTNESS_FIRST = 1, 2, 4   # AcaiAugImage.jitter
 
@@ -141,6 +145,9 @@ _SIGNATURES = {
     "acai_decode_slot_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p, c_int, c_void_p]),
     "acai_decode_spec_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), c_void_p]),
     "acai_decode_spec_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), c_void_p]),
+    "acai_decode_prompt_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiPrompt), c_void_p]),
+    "acai_decode_spec_prompt_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), POINTER(AcaiPrompt), c_void_p]),
+    "acai_decode_spec_prompt_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), POINTER(AcaiPrompt), c_void_p]),
     "acai_decode_logits": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_void_p]),
     "acai_decode_hidden": (c_int, [POINTER(AcaiDecoder), c_void_p, c_void_p]),
     "acai_decode_merge_in_launch": (c_int, [c_int, c_int]),

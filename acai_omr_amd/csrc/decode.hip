@@ -387,6 +387,47 @@ extern "C" int acai_decode_spec_step(const AcaiDecoder *d, const AcaiSpec *sp, v
     return launch_spec_accept(d, sp, 0, st);
 }
 
+static int check_prompt(const AcaiDecoder *d, const AcaiPrompt *pr, int rows, const char *fn) {
+    ACAI_CHECK_ARG(pr && pr->tok && pr->len, "%s: null prompt tables", fn);
+    ACAI_CHECK_ARG(pr->pitch >= d->max_len && pr->rows >= rows, "%s: needs prompt pitch >= max_len and rows >= %d (pitch=%d max_len=%d rows=%d)",
+                   fn, rows, pr->pitch, d->max_len, pr->rows);
+    return 0;
+}
+
+extern "C" int acai_decode_prompt_step(const AcaiDecoder *d, const AcaiPrompt *prompt, void *stream) {
+    const bool chained = d && d->E % 4 == 0;
+    int rc = check_step(d, "acai_decode_prompt_step", chained);
+    if (rc) return rc;
+    if ((rc = check_prompt(d, prompt, d->B, "acai_decode_prompt_step"))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, !chained);
+    if (rc) return rc;
+    return launch_prompt_logprob(d, prompt, chained, st);
+}
+
+extern "C" int acai_decode_spec_prompt_arm(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *prompt, void *stream) {
+    int rc = check_spec(d, sp, "acai_decode_spec_prompt_arm");
+    if (rc) return rc;
+    if ((rc = check_prompt(d, prompt, d->B / (sp->D + 1), "acai_decode_spec_prompt_arm"))) return rc;
+    rc = launch_spec_prompt_accept(d, sp, prompt, 1, (hipStream_t)stream);
+    if (rc) return rc;
+    x_valid_set(d, true);
+    return 0;
+}
+
+extern "C" int acai_decode_spec_prompt_step(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *prompt, void *stream) {
+    int rc = check_spec(d, sp, "acai_decode_spec_prompt_step");
+    if (rc) return rc;
+    if ((rc = check_prompt(d, prompt, d->B / (sp->D + 1), "acai_decode_spec_prompt_step"))) return rc;
+    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_spec_prompt_step: x does not hold this step's input embedding - call "
+                                   "acai_decode_spec_prompt_arm after setting up the speculative state and after every acai_decode_logits / "
+                                   "acai_decode_hidden");
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, false, true, nullptr, nullptr, sp);
+    if (rc) return rc;
+    return launch_spec_prompt_accept(d, sp, prompt, 0, st);
+}
+
 extern "C" int acai_decode_logits(const AcaiDecoder *d, const int64_t *tokens, int time_step, void *stream) {
     int rc = check_unembed(d, "acai_decode_logits");
     if (rc) return rc;

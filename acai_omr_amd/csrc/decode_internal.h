@@ -96,3 +96,5 @@ int launch_slot_argmax(const AcaiDecoder *d, const AcaiSlots *sl, hipStream_t st
 int launch_slot_sample(const AcaiDecoder *d, const AcaiSlots *sl, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k,
                        float temperature, hipStream_t st);
 int launch_spec_accept(const AcaiDecoder *d, const AcaiSpec *sp, int arm, hipStream_t st);
+int launch_prompt_logprob(const AcaiDecoder *d, const AcaiPrompt *pr, bool chained, hipStream_t st);
+int launch_spec_prompt_accept(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *pr, int arm, hipStream_t st);

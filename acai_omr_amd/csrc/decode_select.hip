@@ -88,6 +88,66 @@ __global__ __launch_bounds__(1024) void argmax_logprob_kernel(const float *logit
     }
 }
 
+// ---- prompted decoding (an extension: the reference starts every sequence from <bos> alone) -----------------------------------------------
+// The prompt length of table row `row`, clamped so that every index 1 .. len is a column of the table and of seqs.
+__device__ __forceinline__ int prompt_len(const int32_t *plen, int row, int ppitch, int max_len) {
+    return min(max(plen[row], 0), min(ppitch, max_len) - 1);
+}
+
+// The prompt's token of output index p of table row `row`, or -1 where the prompt gives none (p outside 1 .. len, an id outside [0, V)).
+__device__ __forceinline__ int prompt_token(const int32_t *ptok, int row, int ppitch, int p, int len, int V) {
+    if (p < 1 || p > len) return -1;
+    const int v = ptok[(size_t)row * ppitch + p];
+    return (v >= 0 && v < V) ? v : -1;
+}
+
+// argmax_logprob_kernel (with its bookkeeping) whose token at index t <= len[b] is the prompt's.  The log-prob of token k is
+// -(logf(se) - (logit[k] - max)): for the arg-max the inner difference is exactly 0 and the value is argmax_logprob_kernel's -logf(se) bit for
+// bit (beam_select_kernel's form).  A row inside its prompt (t < len[b]) counts as unfinished.
+__global__ __launch_bounds__(1024) void prompt_logprob_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                             int32_t *step, int32_t *finished, int eos, int round_lp, const int32_t *ptok,
+                                                             const int32_t *plen, int ppitch, const float *emb, const float *pos, float *x,
+                                                             int E, int Tmax) {
+    __shared__ int unfinished[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = step[0];
+    int cnt = 0;
+    const int nw = blockDim.x >> 6;
+    for (int b = wave; b < B; b += nw) {
+        const float *lg = logits + (size_t)b * V;
+        float best;
+        int bi;
+        const float se = row_argmax_sumexp(lg, V, lane, best, bi);
+        const int P = prompt_len(plen, b, ppitch, max_len);
+        const int forced = prompt_token(ptok, b, ppitch, t, P, V);
+        const int tok = forced >= 0 ? forced : bi;
+        float lp = -(logf(se) - (lg[tok] - best));
+        if (round_lp) lp = round_bf16(lp);
+        int fin = finished[b];
+        if (tok == eos) fin = 1;
+        if (lane == 0) {
+            seqs[(size_t)b * max_len + t] = tok;
+            logprobs[(size_t)b * max_len + t] = lp;
+            finished[b] = fin;
+        }
+        cnt += (fin && t >= P) ? 0 : 1;
+        if (emb && t + 1 < Tmax)   // next step's input (see argmax_logprob_kernel)
+            for (int i = lane * 4; i < E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+    }
+    if (lane == 0) unfinished[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < nw; ++w) tot += unfinished[w];
+        finished[B] = tot;
+        step[0] = t + 1;
+        step[1] = step[1] + 1;
+    }
+}
+
 // GRPOViTOMR.cached_forward_rollout_policy (M:988-1049), one sampling step: top-k filter, softmax with temperature over the kept logits,
 // draw from that distribution, log-prob of the drawn token under the UN-tempered softmax of the kept logits (the reference takes
 // log_softmax(top_k_logits), M:1017).  torch.multinomial's Philox stream is not reproducible here; the draw is the inverse CDF of a caller
@@ -342,7 +402,20 @@ struct SpecArgs {
     const int32_t *cap, *drafts;
 };
 
-__global__ __launch_bounds__(1024) void spec_accept_kernel(SpecArgs a) {
+// A prompted run (acai_decode_spec_prompt_step): the verify step with image i's prompt row i.  Row j at write index t emits the prompt's token
+// while t + j <= len[i], with prompt_logprob_kernel's log-prob, and while the new t <= len[i] the next step's drafts are the prompt's tokens
+// of indices <= len[i] (none beyond), so that they are all accepted.  The kernel is a template over its argument struct: the unprompted
+// instantiation compiles to what it was.
+struct SpecPromptArgs : SpecArgs {
+    const int32_t *ptok, *plen;
+    int ppitch;
+};
+template <typename A> struct spec_prompted { static constexpr bool value = false; };
+template <> struct spec_prompted<SpecPromptArgs> { static constexpr bool value = true; };
+
+template <typename A>
+__global__ __launch_bounds__(1024) void spec_accept_kernel(A a) {
+    constexpr bool PROMPT = spec_prompted<A>::value;
     extern __shared__ int spec_dyn[];   // [B] greedy tokens, [B] their log-probs
     __shared__ int unfinished[16];
     int *g_tok = spec_dyn;
@@ -355,13 +428,21 @@ __global__ __launch_bounds__(1024) void spec_accept_kernel(SpecArgs a) {
             int bi;
             const float se = row_argmax_sumexp(a.logits + (size_t)b * a.V, a.V, lane, best, bi);
             float lp = -logf(se);
+            if constexpr (PROMPT) {   // row b predicts index t + b % R of image b / R
+                const int img = b / R;
+                const int forced = prompt_token(a.ptok, img, a.ppitch, a.t[img] + b % R, prompt_len(a.plen, img, a.ppitch, a.ld), a.V);
+                if (forced >= 0) {
+                    lp = -(logf(se) - (a.logits[(size_t)b * a.V + forced] - best));
+                    bi = forced;
+                }
+            }
             if (a.round_lp) lp = round_bf16(lp);
             if (lane == 0) {
                 g_tok[b] = bi;
                 g_lp[b] = lp;
             }
         }
-    __syncthreads();
+    __syncthreads();   // (also orders the a.t reads above before the writes below)
     const int wnext = min(a.step[1] + (a.arm ? 0 : 1), a.Tmax - 1);   // the cache position the next step's rows write
     int cnt = 0;
     for (int img = wave; img < nimg; img += nw) {
@@ -400,7 +481,14 @@ __global__ __launch_bounds__(1024) void spec_accept_kernel(SpecArgs a) {
         cnt += 1;
         // the next step's inputs: lane j < R holds the token row j consumes (index t - 1 + j), -1 = none
         int mine = -1;
-        if (a.drafts) {
+        bool in_prompt = false;
+        if constexpr (PROMPT) {
+            const int P = prompt_len(a.plen, img, a.ppitch, a.ld);
+            in_prompt = t <= P;   // wave-uniform
+            if (in_prompt && lane >= 1 && lane < R && t + lane < cap) mine = prompt_token(a.ptok, img, a.ppitch, t - 1 + lane, P, a.V);
+        }
+        if (in_prompt) {
+        } else if (a.drafts) {
             const int idx = t - 1 + lane;
             if (lane >= 1 && lane < R && t + lane < cap) {   // (a row whose prediction index would reach cap is idle)
                 const int v = a.drafts[(size_t)img * a.pitch + idx];
@@ -629,6 +717,15 @@ int launch_argmax_logprob(const AcaiDecoder *d, bool chained, hipStream_t st) {
     return 0;
 }
 
+// the prompted form of launch_argmax_logprob
+int launch_prompt_logprob(const AcaiDecoder *d, const AcaiPrompt *pr, bool chained, hipStream_t st) {
+    hipLaunchKernelGGL(prompt_logprob_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
+                       d->finished, d->eos, round_lp(d), pr->tok, pr->len, pr->pitch, chained ? (const float *)d->emb : nullptr,
+                       (const float *)d->pos, d->x, d->E, d->Tmax);
+    ACAI_LAUNCH_CHECK("prompt_logprob");
+    return 0;
+}
+
 // the sampling kernel, then the loop bookkeeping
 int launch_sample_logprob(const AcaiDecoder *d, const float *uniforms, int top_k, float temperature, bool chained, hipStream_t st) {
     hipLaunchKernelGGL(sample_logprob_kernel, dim3(cdiv(d->B, 4)), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
@@ -687,7 +784,20 @@ int launch_spec_accept(const AcaiDecoder *d, const AcaiSpec *sp, int arm, hipStr
     a.round_lp = round_lp(d); a.ngram = sp->ngram; a.arm = arm; a.pitch = sp->pitch;
     a.seqs = d->seqs; a.logprobs = d->logprobs; a.step = d->step; a.finished = d->finished; a.emb = d->emb; a.pos = d->pos; a.x = d->x;
     a.t = sp->t; a.steps = sp->steps; a.tab = sp->tab; a.next = sp->next; a.cap = sp->cap; a.drafts = sp->drafts;
-    hipLaunchKernelGGL(spec_accept_kernel, dim3(1), row_waves(d), sizeof(int) * 2 * (size_t)d->B, st, a);
+    hipLaunchKernelGGL(spec_accept_kernel<SpecArgs>, dim3(1), row_waves(d), sizeof(int) * 2 * (size_t)d->B, st, a);
     ACAI_LAUNCH_CHECK("spec_accept");
+    return 0;
+}
+
+// launch_spec_accept with the prompt tables
+int launch_spec_prompt_accept(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *pr, int arm, hipStream_t st) {
+    SpecPromptArgs a{};
+    a.logits = d->logits; a.V = d->V; a.B = d->B; a.R = sp->D + 1; a.E = d->E; a.Tmax = d->Tmax; a.ld = d->max_len; a.eos = d->eos; a.pad = d->pad;
+    a.round_lp = round_lp(d); a.ngram = sp->ngram; a.arm = arm; a.pitch = sp->pitch;
+    a.seqs = d->seqs; a.logprobs = d->logprobs; a.step = d->step; a.finished = d->finished; a.emb = d->emb; a.pos = d->pos; a.x = d->x;
+    a.t = sp->t; a.steps = sp->steps; a.tab = sp->tab; a.next = sp->next; a.cap = sp->cap; a.drafts = sp->drafts;
+    a.ptok = pr->tok; a.plen = pr->len; a.ppitch = pr->pitch;
+    hipLaunchKernelGGL(spec_accept_kernel<SpecPromptArgs>, dim3(1), row_waves(d), sizeof(int) * 2 * (size_t)d->B, st, a);
+    ACAI_LAUNCH_CHECK("spec_prompt_accept");
     return 0;
 }

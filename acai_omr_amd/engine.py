@@ -277,8 +277,9 @@ class DecodeEngine:
         self.lens = None
         self.group = 1          # decode rows per stored cross K/V (GRPO rollout groups)
         # what a decode step does: ("greedy",), ("sample", top_k, temperature), ("beam", K), ("slot",) (continuous batching),
-        # ("slot_sample", top_k, temperature) (continuous batching, sampled) or ("spec", D, ngram) (speculative greedy; ngram 0 = drafts from
-        # the injected table); a run sets it and restores greedy when it ends
+        # ("slot_sample", top_k, temperature) (continuous batching, sampled), ("spec", D, ngram) (speculative greedy; ngram 0 = drafts from
+        # the injected table), ("prompt",) (greedy from given tokens) or ("spec", D, ngram, "prompt") (the two together); a run sets it and
+        # restores greedy when it ends
         self._mode = ("greedy",)
         self.uniforms = None    # (Bmax, Tmax) uniforms of the sampling step, allocated on first use
         self.beam_anc = None    # beam-search lineage [2][Bmax][Tmax] (anc / tok / lp) and per-row cum / len, allocated on first use
@@ -289,6 +290,7 @@ class DecodeEngine:
         self.slot_urow = None   # sampled slot mode: [Bmax] int32 uniforms row of the sequence in each slot, and the (rows, Tmax) table
         self.slot_uniforms = None
         self.spec_t = None      # speculative decoding: per-image state (t, cap, steps, key table, next inputs, injected drafts), allocated on first use
+        self.prompt_tok = None  # prompted decoding: (Bmax, Tmax) int32 tokens by output index and (Bmax,) int32 lengths, allocated on first use
         self._per_row_cross = False
         self.cache_len = 0
         self._desc = None
@@ -482,11 +484,41 @@ class DecodeEngine:
         cur.wait_stream(self.stream)
 
     # ---- ViTOMR.cached_greedy_generate (models.py:600-615) ----------------------------------------------------------
-    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None):
+    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None, prompt=None):
         """Runs up to max_len-1 greedy steps; returns views seqs (B,max_len) int64 and logprobs (B,max_len) fp32.
-        Early exit when every row has produced <eos> (checked every `poll` steps; overshoot is masked later)."""
-        with self._run(max_len, ("greedy",)):
+        Early exit when every row has produced <eos> (checked every `poll` steps; overshoot is masked later).
+        prompt (an extension; None = off): one token list / 1-D tensor per row, the row's tokens of indices 1 .. P (_set_prompt); the row
+        takes them whatever the model prefers, records the model's log-prob of each, and decodes greedily from index P + 1."""
+        if prompt is None:
+            with self._run(max_len, ("greedy",)):
+                return self._decode_loop(max_len, poll, use_graph, on_chunk)
+        with self._run(max_len, ("prompt",)):
+            self._set_prompt(prompt, self.B, max_len)
             return self._decode_loop(max_len, poll, use_graph, on_chunk)
+
+    # ---- prompted decoding (an extension: the reference starts every sequence from <bos> alone) -------------------------------------------
+    def _set_prompt(self, prompt, n, max_len):
+        """Fills the engine-owned prompt tables for n sequences: prompt[i] holds sequence i's tokens of output indices 1 .. P_i (0 <= P_i <=
+        max_len - 1; validated by the caller - ViTOMR._check_prefix).  The tables keep their address from call to call, so the captured
+        prompt-mode graphs stay valid; they are written on the current stream, before arming."""
+        if len(prompt) != n:
+            raise ValueError(f"prompt holds {len(prompt)} token lists for {n} sequences")
+        if self.prompt_tok is None:
+            self.prompt_tok = torch.zeros(self.Bmax, self.Tmax, dtype=torch.int32, device=self.device)
+            self.prompt_len = torch.zeros(self.Bmax, dtype=torch.int32, device=self.device)
+            d = _lib.AcaiPrompt()
+            d.tok, d.len, d.pitch, d.rows = self.prompt_tok.data_ptr(), self.prompt_len.data_ptr(), self.Tmax, self.Bmax
+            self._prompt_desc = d
+        tab = torch.zeros(n, self.Tmax, dtype=torch.int32)
+        lens = torch.zeros(n, dtype=torch.int32)
+        for i, p in enumerate(prompt):
+            p = torch.as_tensor(p).reshape(-1).to(device="cpu", dtype=torch.int32)
+            if p.numel() > max_len - 1:
+                raise ValueError(f"prompt {i} holds {p.numel()} tokens: more than max_len - 1 = {max_len - 1}")
+            tab[i, 1:1 + p.numel()] = p
+            lens[i] = p.numel()
+        self.prompt_tok[:n].copy_(ops.h2d(tab, self.device))
+        self.prompt_len[:n].copy_(ops.h2d(lens, self.device))
 
     # ---- GRPOViTOMR.cached_forward_rollout_policy (models.py:988-1049) ---------------------------------------------------------
     def sample(self, max_actions, top_k, temperature, uniforms=None, poll=16, use_graph=True):
@@ -502,27 +534,36 @@ class DecodeEngine:
             self.uniforms[:B, :max_actions] = uniforms.to(device=self.device, dtype=torch.float32)
             return self._decode_loop(max_actions, poll, use_graph)
 
-    def greedy_chunks(self, max_len, chunk):
+    def greedy_chunks(self, max_len, chunk, prompt=None):
         """Generator over the greedy loop in chunks of `chunk` tokens (streamed inference): yields (tokens_done, all_finished)
-        after each chunk; the decode graph is replayed on the engine's stream, the caller's stream waits for it."""
+        after each chunk; the decode graph is replayed on the engine's stream, the caller's stream waits for it.
+        prompt: as in greedy(); the mode is ("prompt",) while the generator runs and goes back to greedy when it ends or is closed."""
         if max_len > self.Tmax:
             raise RuntimeError(f"{max_len} decoding steps is too long for max sequence length of {self.Tmax}")
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self._arm_and_capture(self.B)
-        done, total = 0, max_len - 1
-        while done < total:
-            n = min(chunk, total - done)
+        if prompt is not None:
+            self._mode = ("prompt",)
+        try:
             with torch.cuda.stream(self.stream):
-                self.launch_steps(n)
-                fin = int(self.finished[self.B].item()) == 0
-            cur.wait_stream(self.stream)
-            done += n
-            self.cache_len = done
-            yield done, fin
-            if fin:
-                return
+                if prompt is not None:
+                    self._set_prompt(prompt, self.B, max_len)
+                self._arm_and_capture(self.B)
+            done, total = 0, max_len - 1
+            while done < total:
+                n = min(chunk, total - done)
+                with torch.cuda.stream(self.stream):
+                    self.launch_steps(n)
+                    fin = int(self.finished[self.B].item()) == 0
+                cur.wait_stream(self.stream)
+                done += n
+                self.cache_len = done
+                yield done, fin
+                if fin:
+                    return
+        finally:
+            if prompt is not None:
+                self._mode = ("greedy",)
 
     # ---- beam search (an extension: the reference decodes greedily) ----------------------------------------------------------------------
     def beam(self, max_len, beam_width, length_penalty=1.0, poll=16, use_graph=True):
@@ -557,13 +598,16 @@ class DecodeEngine:
             return seqs.index_select(0, rows), lps.index_select(0, rows), cum.index_select(0, rows)
 
     # ---- speculative greedy decoding (an extension: the reference emits one token per step) ------------------------------------------------
-    def speculative(self, max_len, draft_len, ngram=3, drafts=None, poll=16, use_graph=True, on_chunk=None):
+    def speculative(self, max_len, draft_len, ngram=3, drafts=None, poll=16, use_graph=True, on_chunk=None, prompt=None):
         """Greedy decoding that emits up to draft_len + 1 tokens per step, over the B / R images prepared with group_size = R = draft_len + 1
         and per_row_cross=True (rows i*R .. i*R+R-1 verify consecutive tokens of image i): up to max_len-1 steps of acai_decode_spec_step.
         Drafts come from the sequence's own earlier n-grams (suffixes of up to `ngram` tokens), or from `drafts` (B/R, max_len) int - the
         token proposed for each index, negative = none - when given.  Returns views seqs (B/R, max_len) int64 and logprobs (B/R, max_len)
         fp32, bitwise what greedy() writes up to each image's first <eos> (nothing is written after it), and steps (B/R,) int32, the
-        verify steps each image took.  Not combinable with beam search, sampling, slot mode or an FP8 memory cache."""
+        verify steps each image took.  Not combinable with beam search, sampling, slot mode or an FP8 memory cache.
+        prompt (None = off): one token list / 1-D tensor per image, as in greedy(): a step consumes up to draft_len + 1 prompt tokens (they
+        are their own drafts), so P prompt tokens and the first free token take ceil((P + 1) / (draft_len + 1)) steps; the result is
+        bitwise greedy(prompt=...)'s up to each image's first <eos>."""
         D = int(draft_len)
         R = D + 1
         if not 1 <= D <= 7:
@@ -578,7 +622,10 @@ class DecodeEngine:
         n = self.B // R
         if drafts is not None and tuple(drafts.shape) != (n, max_len):
             raise ValueError(f"drafts must be (images, max_len) = ({n}, {max_len}), got {tuple(drafts.shape)}")
-        with self._run(max_len, ("spec", D, 0 if drafts is not None else int(ngram))):
+        mode = ("spec", D, 0 if drafts is not None else int(ngram))
+        with self._run(max_len, mode if prompt is None else mode + ("prompt",)):
+            if prompt is not None:
+                self._set_prompt(prompt, n, max_len)
             if self.spec_t is None:
                 z = lambda *s: torch.zeros(*s, dtype=torch.int32, device=self.device)  # noqa: E731
                 self.spec_t, self.spec_cap, self.spec_steps = z(self.Bmax), z(self.Bmax), z(self.Bmax)
@@ -612,7 +659,11 @@ class DecodeEngine:
         self.spec_steps.zero_()
         self.spec_tab.zero_()
         self.spec_next.fill_(-1)
-        _lib.check(_lib.lib().acai_decode_spec_arm(ctypes.byref(self._desc), ctypes.byref(self._spec_desc), ops._st()), "acai_decode_spec_arm")
+        if len(self._mode) > 3:
+            _lib.check(_lib.lib().acai_decode_spec_prompt_arm(ctypes.byref(self._desc), ctypes.byref(self._spec_desc),
+                                                              ctypes.byref(self._prompt_desc), ops._st()), "acai_decode_spec_prompt_arm")
+        else:
+            _lib.check(_lib.lib().acai_decode_spec_arm(ctypes.byref(self._desc), ctypes.byref(self._spec_desc), ops._st()), "acai_decode_spec_arm")
         self._x_valid = True
 
     def beam_slots(self, max_len):
@@ -663,6 +714,11 @@ class DecodeEngine:
             _lib.check(L.acai_decode_sample_step(d, self.uniforms.data_ptr(), mode[1], mode[2], st), "acai_decode_sample_step")
         elif mode[0] == "beam":
             _lib.check(L.acai_decode_beam_step(d, ctypes.byref(self._beam_desc), st), "acai_decode_beam_step")
+        elif mode[0] == "prompt":
+            _lib.check(L.acai_decode_prompt_step(d, ctypes.byref(self._prompt_desc), st), "acai_decode_prompt_step")
+        elif mode[0] == "spec" and len(mode) > 3:
+            _lib.check(L.acai_decode_spec_prompt_step(d, ctypes.byref(self._spec_desc), ctypes.byref(self._prompt_desc), st),
+                       "acai_decode_spec_prompt_step")
         elif mode[0] == "spec":
             _lib.check(L.acai_decode_spec_step(d, ctypes.byref(self._spec_desc), st), "acai_decode_spec_step")
         elif mode[0] == "slot_sample":

@@ -32,15 +32,20 @@ def _encode(vitomr, img):
         return vitomr.encoder.forward_packed(img)
 
 
-def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1, length_penalty=1.0, speculative=0, ngram=3):
+def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1, length_penalty=1.0, speculative=0, ngram=3, prefix=None):
     """img: one (1,H,W) tensor or a list of them -> (seqs int64 (B,T'), log_probs fp32 (B,T'), seq_mask bool (B,T')).
     beam_width > 1 (extension): beam search with that many hypotheses per image, scored by cum / len^length_penalty
     (ViTOMR.cached_beam_generate); beam_width = 1 is the reference's greedy decode.
     speculative = D in 1..7 (extension, default 0 = off): greedy decoding that verifies up to D n-gram draft tokens per step
     (ViTOMR.cached_speculative_generate) - the same result in fewer steps where the output repeats itself; needs images * (D + 1) <= the
-    cache's max batch size, and cannot be combined with beam_width > 1 or an FP8 memory cache (ValueError)."""
+    cache's max batch size, and cannot be combined with beam_width > 1 or an FP8 memory cache (ValueError).
+    prefix (extension, default None = off): prompted decoding - one entry per image with the already known tokens of output indices
+    1 .. P_i (ViTOMR.cached_greedy_generate); works with greedy and speculative decoding, not with beam search (ValueError: out of scope
+    here)."""
     if speculative and beam_width != 1:
         raise ValueError("speculative decoding cannot be combined with beam search (beam_width > 1)")
+    if prefix is not None and beam_width != 1:
+        raise ValueError("prefix (prompted decoding) cannot be combined with beam search (beam_width > 1): out of scope here")
     vitomr.eval()
     with torch.no_grad():
         lat32, _, lens = _encode(vitomr, img)
@@ -48,10 +53,11 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
             mem = vitomr.transition_head.forward_packed(lat32)
             bf = mem.dtype == torch.bfloat16
             if speculative:
-                return vitomr._speculative_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, speculative, ngram)
+                return vitomr._speculative_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, speculative, ngram,
+                                                  prefix=prefix)
             if beam_width != 1:
                 return vitomr._beam_packed(None if bf else mem, mem if bf else None, lens, beam_width, max_inference_len, length_penalty)
-            return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len)
+            return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, prefix=prefix)
 
 
 def _encode_chunks(vitomr, imgs, device):
@@ -67,10 +73,12 @@ def _encode_chunks(vitomr, imgs, device):
     return (mems[0] if len(mems) == 1 else torch.cat(mems)), lens
 
 
-def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None):
+def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None):
     """Continuous-batching greedy inference (an extension) as a generator: yields (index, seqs (1,T'), log_probs (1,T'), mask (1,T')) for
     each image as soon as it finishes, in completion order; each is what inference(vitomr, [imgs[index]]) returns.  max_inference_len: one
-    cap or a list of per-image caps; slots: decode rows (default: the cache's max batch size)."""
+    cap or a list of per-image caps; slots: decode rows (default: the cache's max batch size).  prefix (prompted decoding, inference())
+    is not supported here: anything but None raises ValueError."""
+    vitomr._no_prefix(prefix, "continuous batching")
     vitomr.eval()
     imgs = list(imgs)
     with torch.no_grad():
@@ -85,10 +93,12 @@ def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=15
     return images()
 
 
-def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None):
+def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None):
     """inference() over a list of any length through continuous batching (an extension): `slots` decode rows work through the images in
     input order and a finished row is refilled with the next image at once.  Returns exactly what inference(vitomr, imgs, ...) returns
-    (seqs (N,T'), log_probs (N,T'), mask (N,T'), clipped to the longest row); max_inference_len may be a list of per-image caps."""
+    (seqs (N,T'), log_probs (N,T'), mask (N,T'), clipped to the longest row); max_inference_len may be a list of per-image caps.  prefix
+    (prompted decoding, inference()) is not supported here: anything but None raises ValueError."""
+    vitomr._no_prefix(prefix, "continuous batching")
     vitomr.eval()
     imgs = list(imgs)
     with torch.no_grad():
@@ -98,7 +108,9 @@ def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, s
             return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots)
 
 
-def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25):
+def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None):
+    """prefix (extension, default None = off): prompted decoding of the one image, as in inference(); the forced tokens arrive in the
+    STEP events like any others."""
     vitomr.eval()
     with torch.no_grad():
         yield {"type": InferenceEvent.ENCODING_START.value, "payload": None}
@@ -107,5 +119,5 @@ def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flus
             img_latent = vitomr.transition_head(img_latent)
             yield {"type": InferenceEvent.ENCODING_FINISH.value, "payload": None}
             for event in vitomr.streamed_cached_greedy_generate(img_latent, latent_attention_mask, max_len=max_inference_len,
-                                                                flush_interval=flush_interval):
+                                                                flush_interval=flush_interval, prefix=prefix):
                 yield event

@@ -533,18 +533,64 @@ class ViTOMR(nn.Module):
         lp = F.log_softmax(logits, dim=-1).gather(-1, idx.unsqueeze(1)).squeeze(1)
         return idx, lp
 
-    def _greedy_packed(self, mem32, memb, lens, max_len, on_chunk=None):
+    def _check_prefix(self, prefix, n, max_len):
+        """Prompted decoding (an extension): `prefix` as the entry points take it - None, or one entry per image, each a 1-D integer tensor
+        or list (possibly empty) holding the image's tokens of output indices 1 .. P_i; a single 1-D tensor stands for one image - checked
+        and returned as a list of n 1-D int64 CPU tensors (None stays None).  ValueError for a wrong count, an id outside [0, V), <bos> or
+        <pad>, an <eos> before the end of a prompt, or P_i > max_len - 1."""
+        if prefix is None:
+            return None
+        dec = self.decoder
+        if torch.is_tensor(prefix) and prefix.dim() == 1:
+            prefix = [prefix]
+        try:
+            rows = [torch.as_tensor(p) for p in prefix]
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"prefix must be a sequence of 1-D integer tensors or lists, one per image: {e}") from None
+        if len(rows) != n:
+            raise ValueError(f"prefix holds {len(rows)} entries for {n} images")
+        out = []
+        for i, r in enumerate(rows):
+            if r.numel() == 0:
+                out.append(torch.zeros(0, dtype=torch.int64))
+                continue
+            if r.dim() != 1 or r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool:
+                raise ValueError(f"prefix[{i}] must be a 1-D integer tensor or list, got shape {tuple(r.shape)} dtype {r.dtype}")
+            r = r.detach().to(device="cpu", dtype=torch.int64)
+            if r.numel() > max_len - 1:
+                raise ValueError(f"prefix[{i}] holds {r.numel()} tokens: more than max_len - 1 = {max_len - 1}")
+            if int(r.min()) < 0 or int(r.max()) >= dec.vocab_size:
+                raise ValueError(f"prefix[{i}] holds a token id outside [0, {dec.vocab_size})")
+            if bool(((r == dec.bos_idx) | (r == dec.pad_idx)).any()):
+                raise ValueError(f"prefix[{i}] holds <bos> or <pad>: a prompt starts after <bos> and has no padding")
+            if bool((r[:-1] == dec.eos_idx).any()):
+                raise ValueError(f"prefix[{i}] holds <eos> before its end: <eos> may only be a prompt's last token")
+            out.append(r)
+        return out
+
+    @staticmethod
+    def _no_prefix(prefix, what):
+        if prefix is not None:
+            raise ValueError(f"prefix (prompted decoding) cannot be combined with {what}: out of scope here")
+
+    def _greedy_packed(self, mem32, memb, lens, max_len, on_chunk=None, prefix=None):
         blocks = self.decoder._cached_blocks()
+        prompt = self._check_prefix(prefix, len(lens), max_len)
         blocks.prepare_caches_packed(mem32, memb, lens)
         eng = blocks.engine(self.decoder.pos_embedding.device)
-        seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk)
+        seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk) if prompt is None else eng.greedy(max_len, on_chunk=on_chunk, prompt=prompt)
         return self.mask_and_clip_seqs(seqs.clone(), lps.clone())
 
-    def cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536):
+    def cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, prefix=None):
         """Batched greedy decode with KV caching (M:600-615) -> seqs (B,T') int64, log_probs (B,T') fp32, mask (B,T') bool.
-        The whole loop runs as replays of one captured hipGraph; the host only polls an "all finished" counter."""
+        The whole loop runs as replays of one captured hipGraph; the host only polls an "all finished" counter.
+        prefix (an extension, default None = off): prompted decoding - one entry per image (a 1-D integer tensor or list, possibly empty;
+        a single 1-D tensor for one image) with the tokens of output indices 1 .. P_i <= max_len - 1 that are already known.  The row takes
+        them whatever the model would choose, log_probs holds the model's log-probability of each, and greedy decoding goes on from index
+        P_i + 1; a prompt-final <eos> ends the row.  Ids must lie in [0, V), never <bos> or <pad>, <eos> only last (ValueError).  Where
+        the prompt is the model's own greedy output the result is bitwise the unprompted one."""
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
-        return self._greedy_packed(mem32, None, lens, max_len)
+        return self._greedy_packed(mem32, None, lens, max_len, prefix=prefix)
 
     def _beam_packed(self, mem32, memb, lens, beam_width, max_len, length_penalty):
         blocks = self.decoder._cached_blocks()
@@ -559,17 +605,20 @@ class ViTOMR(nn.Module):
         seqs, lps, _ = eng.beam(max_len, K, length_penalty)
         return self.mask_and_clip_seqs(seqs, lps)
 
-    def cached_beam_generate(self, img_latent, latent_attention_mask=None, beam_width=4, max_len=1536, length_penalty=1.0):
+    def cached_beam_generate(self, img_latent, latent_attention_mask=None, beam_width=4, max_len=1536, length_penalty=1.0, prefix=None):
         """Beam-search decode with KV caching (an extension: the reference decodes greedily) -> seqs (B,T') int64, log_probs (B,T') fp32 per
         token, mask (B,T') bool, as cached_greedy_generate.  Each image keeps beam_width hypotheses; a step extends each live one by its
         beam_width best tokens, keeps the beam_width best by cumulative log-probability, and a hypothesis ends at <eos>.  The result per image
         is the hypothesis with the highest cum / len^length_penalty (len: tokens after <bos>, <eos> included).  beam_width = 1 is greedy,
-        bit for bit.  The K hypotheses of an image share its cross K/V; a selection moves no self K/V, only an ancestor table."""
+        bit for bit.  The K hypotheses of an image share its cross K/V; a selection moves no self K/V, only an ancestor table.
+        prefix (prompted decoding, cached_greedy_generate) is not supported here: anything but None raises ValueError."""
+        self._no_prefix(prefix, "beam search")
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._beam_packed(mem32, None, lens, beam_width, max_len, length_penalty)
 
-    def _speculative_packed(self, mem32, memb, lens, max_len, draft_len, ngram=3, drafts=None, poll=16, use_graph=True):
+    def _speculative_packed(self, mem32, memb, lens, max_len, draft_len, ngram=3, drafts=None, poll=16, use_graph=True, prefix=None):
         blocks = self.decoder._cached_blocks()
+        prompt = self._check_prefix(prefix, len(lens), max_len)
         D = int(draft_len)
         if not 1 <= D <= 7:
             raise ValueError(f"draft_len must be in [1, 7], got {draft_len}")
@@ -580,19 +629,21 @@ class ViTOMR(nn.Module):
             raise ValueError("speculative decoding does not support an FP8 memory cache; use memory_cache_dtype=None")
         blocks.prepare_caches_packed(mem32, memb, lens, group_size=D + 1, per_row_cross=True)
         eng = blocks.engine(self.decoder.pos_embedding.device)
-        seqs, lps, _ = eng.speculative(max_len, D, ngram=ngram, drafts=drafts, poll=poll, use_graph=use_graph)
+        kw = {} if prompt is None else {"prompt": prompt}
+        seqs, lps, _ = eng.speculative(max_len, D, ngram=ngram, drafts=drafts, poll=poll, use_graph=use_graph, **kw)
         return self.mask_and_clip_seqs(seqs.clone(), lps.clone())
 
-    def cached_speculative_generate(self, img_latent, latent_attention_mask=None, max_len=1536, draft_len=4, ngram=3, drafts=None):
+    def cached_speculative_generate(self, img_latent, latent_attention_mask=None, max_len=1536, draft_len=4, ngram=3, drafts=None, prefix=None):
         """Speculative greedy decode with KV caching (an extension: the reference emits one token per step) -> seqs (B,T') int64, log_probs
         (B,T') fp32, mask (B,T') bool: bitwise what cached_greedy_generate returns for the same arguments, in fewer decode steps when drafts
         are accepted.  Each image owns draft_len + 1 decode rows (so B * (draft_len + 1) <= max batch size, 1 <= draft_len <= 7): one step
         verifies up to draft_len draft tokens and emits the accepted ones plus one.  Drafts are looked up in the sequence's own earlier
         n-grams (suffixes of up to `ngram` tokens, 1..8) or taken from `drafts` (B, max_len) - the token proposed for each index, negative =
         none.  An image that ends early idles until the batch does.  Beam search, sampling, continuous batching (slot mode) and an FP8
-        memory cache cannot be combined with it (ValueError): out of scope here."""
+        memory cache cannot be combined with it (ValueError): out of scope here.
+        prefix: prompted decoding as in cached_greedy_generate, bitwise its result; the prompt is consumed draft_len + 1 tokens per step."""
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
-        return self._speculative_packed(mem32, None, lens, max_len, draft_len, ngram, drafts)
+        return self._speculative_packed(mem32, None, lens, max_len, draft_len, ngram, drafts, prefix=prefix)
 
     def _continuous_run(self, mem32, memb, lens, max_len, slots, poll, use_graph, **sampling):
         """(engine, caps, generator of finished image indices) of a continuous-batching run; argument errors are raised here, at the call.
@@ -629,26 +680,31 @@ class ViTOMR(nn.Module):
             pass
         return self._mask_and_clip_capped(eng.cont_seqs, eng.cont_lps, caps)
 
-    def cached_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None):
+    def cached_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None, prefix=None):
         """Continuous-batching greedy decode (an extension: the reference decodes one static batch) -> seqs (N,T') int64, log_probs (N,T')
         fp32, mask (N,T') bool, as cached_greedy_generate on the same batch.  `slots` decode rows (default: the cache's max batch size)
         work through the N images in input order; a row that finishes (<eos> or its cap) is refilled with the next image while the others
         go on, so N may exceed the max batch size.  max_len: one cap for every image, or a sequence of N per-image caps (positions at or
-        past an image's cap are masked)."""
+        past an image's cap are masked).  prefix (prompted decoding, cached_greedy_generate) is not supported here: anything but None
+        raises ValueError."""
+        self._no_prefix(prefix, "continuous batching")
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._continuous_packed(mem32, None, lens, max_len, slots)
 
-    def streamed_cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, flush_interval=25):
-        """Generator of {"type", "payload"} events (M:625-647); single image only."""
+    def streamed_cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, flush_interval=25, prefix=None):
+        """Generator of {"type", "payload"} events (M:625-647); single image only.
+        prefix: prompted decoding as in cached_greedy_generate; STEP events carry the forced tokens like any others."""
         if img_latent.shape[0] != 1:
             raise ValueError("Streamed generation only supports single image batches")
+        prompt = self._check_prefix(prefix, 1, max_len)
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         blocks = self.decoder._cached_blocks()
         blocks.prepare_caches_packed(mem32, None, lens)
         eng = blocks.engine(self.decoder.pos_embedding.device)
         # replay the decode graph flush_interval tokens at a time; after each chunk hand out the freshly written tokens
         # (the reference yields STEP at every t % flush_interval == 0 that did not finish the sequence - also at t == max_len - 1, M:641-645)
-        for t_done, finished in eng.greedy_chunks(max_len, flush_interval):
+        for t_done, finished in (eng.greedy_chunks(max_len, flush_interval) if prompt is None else
+                                 eng.greedy_chunks(max_len, flush_interval, prompt=prompt)):
             if finished:
                 break
             if t_done % flush_interval == 0:
@@ -747,7 +803,7 @@ class GRPOViTOMR(ViTOMR):
         return self.cached_forward_rollout_policy(img_latent, latent_attention_mask, max_actions, top_k, temperature)
 
     def cached_forward_rollout_policy(self, img_latent, latent_attention_mask, max_actions=768, top_k=50, temperature=1.2, group_size=None,
-                                      uniforms=None):
+                                      uniforms=None, prefix=None):
         """Sampling rollouts with KV caching (M:988-1049): per step keep the top_k logits, draw from softmax(kept / temperature), record
         log_softmax(kept)[drawn]; rows stop mattering after their first <eos>.  Returns rollouts (R, T') int64, rollout_log_probs (R, T') fp32,
         rollout_mask (R, T') bool with padding / zero log-probs outside the mask.
@@ -755,7 +811,9 @@ class GRPOViTOMR(ViTOMR):
         The whole loop is replayed hipGraphs of `acai_decode_sample_step`.  torch.multinomial's random stream cannot be reproduced: the draws
         are inverse-CDF samples from `uniforms` (R, max_actions) in [0, 1), taken from torch's generator when None (so torch.manual_seed makes
         a rollout reproducible).  group_size (extension): img_latent rows r*group_size .. are the copies expand_img_latent_for_rollout made of
-        one image; their cross K/V is then projected and stored once per image instead of once per rollout."""
+        one image; their cross K/V is then projected and stored once per image instead of once per rollout.  prefix (prompted decoding,
+        cached_greedy_generate) is not supported here: anything but None raises ValueError."""
+        self._no_prefix(prefix, "sampling")
         blocks = self.decoder._cached_blocks()
         G = 1 if group_size is None else int(group_size)
         if img_latent.shape[0] % G:

@@ -439,6 +439,41 @@ int acai_decode_spec_arm(const AcaiDecoder *d, const AcaiSpec *sp, void *stream)
  * [1, 8] unless drafts is given, self_chunk <= 16384, and x valid (acai_decode_spec_arm; acai_decode_logits / acai_decode_hidden clear it).
  * A run takes at most max_len - 1 steps, so step[1] stays below Tmax.  Enqueues kernels only (capturable). */
 int acai_decode_spec_step(const AcaiDecoder *d, const AcaiSpec *sp, void *stream);
+
+/* Prompted decoding (an extension: the reference starts every sequence from <bos> alone).  Sequence i is given the tokens of its output
+ * indices 1 .. len[i] (index 0 is always <bos>); from index len[i] + 1 on it decodes greedily.  Both tables are device memory and are read
+ * by every step (the caller fills them before the first step and keeps them until the last has run):
+ *   tok: [rows][pitch] int32, tok[i][p] the token of output index p for 1 <= p <= len[i]; column 0 and the columns past len[i] are not read.
+ *        The caller keeps the ids inside [0, V), never <bos> or <pad>, and <eos> only at index len[i]; an entry outside [0, V) is not
+ *        forced (the step is greedy at that index), so that no table content can make the step index out of bounds;
+ *   len: [rows] int32 prompt lengths, clamped on the device to [0, min(pitch, max_len) - 1]; 0 = plain greedy decoding of that row. */
+typedef struct {
+    const int32_t *tok;
+    const int32_t *len;
+    int32_t pitch;     /* entries per row of tok, >= dec->max_len */
+    int32_t rows;      /* rows of tok / len, >= dec->B (speculative entry points: >= dec->B / (D + 1), one row per image) */
+} AcaiPrompt;
+/* One PROMPTED greedy step t = *step for all B rows: acai_decode_step's layers and unembed, then one selection launch.  A row with
+ * t <= len[b] takes tok[b][t] whatever the model prefers; a row with t > len[b] takes the arg-max as acai_decode_step does.  Either way
+ * logprobs[b][t] = (logit[token] - max) - logf(sum_j expf(logit[j] - max)) with acai_decode_step's max / sum reduction, rounded to bf16
+ * where that step rounds: where the token is the arg-max the first term is exactly 0 and the value is bitwise acai_decode_step's.  The
+ * launch also writes seqs[b][t], the next step's input x[b] = vocab_embedding[token] + pos_embedding[t + 1] (quirk Q1), finished[b] (set
+ * by <eos>, forced or chosen), the unfinished count finished[B] - a row with t < len[b] always counts as unfinished - and advances step[0]
+ * / step[1].  Works for fp32 and bf16 decoders and with an FP8 cross K/V.  Same checks and the same x contract as acai_decode_step, plus
+ * non-null tok / len, pitch >= max_len and rows >= B.  Enqueues kernels only (capturable). */
+int acai_decode_prompt_step(const AcaiDecoder *d, const AcaiPrompt *prompt, void *stream);
+/* acai_decode_spec_arm for a prompted run (prompt row i belongs to image i): the drafts of the first step are the prompt's tokens of
+ * indices 1 .. min(D, len[i]) and none beyond; with len[i] = 0 they come from sp's usual source.  Same checks as acai_decode_spec_arm,
+ * plus non-null tok / len, prompt->pitch >= max_len and prompt->rows >= B / (D + 1). */
+int acai_decode_spec_prompt_arm(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *prompt, void *stream);
+/* One VERIFY step of a prompted speculative run: acai_decode_spec_step in which row j of an image at write index t, predicting index
+ * t + j, emits g_j = tok[i][t + j] while t + j <= len[i] (log-prob as in acai_decode_prompt_step) and its greedy token beyond.  Acceptance,
+ * the cut at <eos> and cap - 1, tab, next, x, steps and step[1] are acai_decode_spec_step's.  While the new write index t' <= len[i] the
+ * drafts of the next step are the prompt's tokens of indices t' .. min(t' + D - 1, len[i]) and none beyond - so a prompt's drafts are all
+ * accepted, and len[i] prompt tokens plus the first free token take ceil((len[i] + 1) / (D + 1)) steps; once t' > len[i] the drafts come
+ * from sp's usual source.  What is written equals acai_decode_prompt_step run token by token.  Same checks as acai_decode_spec_step and
+ * acai_decode_spec_prompt_arm. */
+int acai_decode_spec_prompt_step(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *prompt, void *stream);
 /* The same without the token bookkeeping: logits for caller-supplied tokens/time_step (OMRDecoder.cached_generate). */
 int acai_decode_logits(const AcaiDecoder *dec, const int64_t *tokens, int time_step, void *stream);
 
