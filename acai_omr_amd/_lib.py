@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip"]
+SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -63,6 +63,10 @@ class AcaiSpec(Structure):
 
 class AcaiPrompt(Structure):
     _fields_ = [("tok", c_void_p), ("len", c_void_p), ("pitch", c_int32), ("rows", c_int32)]
+
+
+class AcaiGrammar(Structure):
+    _fields_ = [("next", c_void_p), ("resync", c_void_p), ("state", c_void_p)] + [(n, c_int32) for n in ("states", "start", "rows", "pad_")]
 
 
 AUG_MAX_TAPS, AUG_MEAN_PARTS = 32, 128
@@ -148,6 +152,13 @@ _SIGNATURES = {
     "acai_decode_prompt_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiPrompt), c_void_p]),
     "acai_decode_spec_prompt_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), POINTER(AcaiPrompt), c_void_p]),
     "acai_decode_spec_prompt_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), POINTER(AcaiPrompt), c_void_p]),
+    "acai_decode_grammar_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiGrammar), c_void_p]),
+    "acai_decode_grammar_sample_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiGrammar), c_void_p, c_int, c_float, c_void_p]),
+    "acai_decode_slot_grammar_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), POINTER(AcaiGrammar), c_void_p]),
+    "acai_decode_slot_grammar_sample_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), POINTER(AcaiGrammar), c_void_p, c_int, c_void_p,
+                                                     c_int, c_float, c_void_p]),
+    "acai_grammar_scan": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                  c_void_p]),
     "acai_decode_logits": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_void_p]),
     "acai_decode_hidden": (c_int, [POINTER(AcaiDecoder), c_void_p, c_void_p]),
     "acai_decode_merge_in_launch": (c_int, [c_int, c_int]),

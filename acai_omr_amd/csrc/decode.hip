@@ -428,6 +428,70 @@ extern "C" int acai_decode_spec_prompt_step(const AcaiDecoder *d, const AcaiSpec
     return launch_spec_prompt_accept(d, sp, prompt, 0, st);
 }
 
+// Prologue of the grammar-constrained steps, after the counterpart's own checks.
+static int check_grammar(const AcaiDecoder *d, const AcaiGrammar *g, const char *fn) {
+    ACAI_CHECK_ARG(g && g->next && g->resync && g->state, "%s: null grammar tables or state", fn);
+    ACAI_CHECK_ARG(g->states >= 1 && g->states <= 32767, "%s: states %d outside [1, 32767]", fn, g->states);
+    ACAI_CHECK_ARG(g->start >= 0 && g->start < g->states, "%s: start %d outside [0, states = %d)", fn, g->start, g->states);
+    ACAI_CHECK_ARG(g->rows >= d->B, "%s: grammar rows %d below B = %d", fn, g->rows, d->B);
+    ACAI_CHECK_ARG(d->V <= 512, "%s: vocabulary %d above 512", fn, d->V);
+    return 0;
+}
+
+extern "C" int acai_decode_grammar_step(const AcaiDecoder *d, const AcaiGrammar *g, void *stream) {
+    const bool chained = d && d->E % 4 == 0;
+    int rc = check_step(d, "acai_decode_grammar_step", chained);
+    if (rc) return rc;
+    if ((rc = check_grammar(d, g, "acai_decode_grammar_step"))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, !chained);
+    if (rc) return rc;
+    return launch_grammar_argmax(d, g, chained, st);
+}
+
+extern "C" int acai_decode_grammar_sample_step(const AcaiDecoder *d, const AcaiGrammar *g, const float *uniforms, int top_k, float temperature,
+                                               void *stream) {
+    const bool chained = d && d->E % 4 == 0;
+    int rc = check_step(d, "acai_decode_grammar_sample_step", chained);
+    if (rc) return rc;
+    if ((rc = check_grammar(d, g, "acai_decode_grammar_sample_step"))) return rc;
+    ACAI_CHECK_ARG(uniforms && top_k >= 1 && top_k <= 64 && temperature > 0.f,
+                   "acai_decode_grammar_sample_step: needs uniforms, 1 <= top_k <= 64, temperature > 0 (top_k=%d)", top_k);
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, !chained);
+    if (rc) return rc;
+    return launch_grammar_sample(d, g, uniforms, top_k, temperature, chained, st);
+}
+
+extern "C" int acai_decode_slot_grammar_step(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *g, void *stream) {
+    int rc = check_slots(d, sl, "acai_decode_slot_grammar_step");
+    if (rc) return rc;
+    if ((rc = check_grammar(d, g, "acai_decode_slot_grammar_step"))) return rc;
+    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_slot_grammar_step: x does not hold this step's input embedding - call acai_decode_slot_arm "
+                                   "after setting up the slot state and after every acai_decode_logits / acai_decode_hidden");
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, false, true, nullptr, sl);
+    if (rc) return rc;
+    return launch_slot_grammar_argmax(d, sl, g, st);
+}
+
+extern "C" int acai_decode_slot_grammar_sample_step(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *g, const float *uniforms,
+                                                    int ld_uniforms, const int32_t *urow, int top_k, float temperature, void *stream) {
+    int rc = check_slots(d, sl, "acai_decode_slot_grammar_sample_step");
+    if (rc) return rc;
+    if ((rc = check_grammar(d, g, "acai_decode_slot_grammar_sample_step"))) return rc;
+    ACAI_CHECK_ARG(uniforms && urow, "acai_decode_slot_grammar_sample_step: null uniforms or urow");
+    ACAI_CHECK_ARG(ld_uniforms >= d->max_len, "acai_decode_slot_grammar_sample_step: ld_uniforms %d is below max_len %d", ld_uniforms, d->max_len);
+    ACAI_CHECK_ARG(top_k >= 1 && top_k <= 64, "acai_decode_slot_grammar_sample_step: top_k %d outside [1, 64]", top_k);
+    ACAI_CHECK_ARG(temperature > 0.f, "acai_decode_slot_grammar_sample_step: temperature must be > 0 (got %g)", (double)temperature);
+    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_slot_grammar_sample_step: x does not hold this step's input embedding - call "
+                                   "acai_decode_slot_arm after setting up the slot state and after every acai_decode_logits / acai_decode_hidden");
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, false, true, nullptr, sl);
+    if (rc) return rc;
+    return launch_slot_grammar_sample(d, sl, g, uniforms, ld_uniforms, urow, top_k, temperature, st);
+}
+
 extern "C" int acai_decode_logits(const AcaiDecoder *d, const int64_t *tokens, int time_step, void *stream) {
     int rc = check_unembed(d, "acai_decode_logits");
     if (rc) return rc;

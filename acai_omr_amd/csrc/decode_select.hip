@@ -1,4 +1,4 @@
-// Token selection of a decode step (see decode.hip): embedding, greedy / sampled / slot / speculative / beam selection and their
+// Token selection of a decode step (see decode.hip): embedding, greedy / sampled / slot / speculative / beam / grammar-constrained selection and their
 // bookkeeping, each with the host helper that launches it from the decoder descriptor.
 #include "decode_internal.h"
 
@@ -684,6 +684,288 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
     }
 }
 
+// ---- grammar-constrained decoding (an extension: the reference knows no grammar) -------------------------------------------------------------
+// The selection kernels above are left exactly as they are; the constrained forms below are their copies with three additions: the row's
+// table row (grammar_row), the masked reductions (row_argmax_sumexp_masked / topk_draw_row_masked: a token the state forbids counts as a -inf
+// logit) and the state update (grammar_advance).  With a table that allows every token each computes what its plain form computes, bit for
+// bit: a masked term is expf(-inf) = 0 exactly and the order of every reduction is the plain one's.
+struct GrammarArgs {   // AcaiGrammar as the kernels take it
+    const int16_t *next, *resync;
+    int32_t *state;
+    int states, start;
+};
+
+// Wave-uniform: the table row of decode row b's state (clamped to [0, states)), or null when that state allows no token - the row is then
+// unconstrained at this step (a defensive path: the builders refuse such tables).
+__device__ __forceinline__ const int16_t *grammar_row(const GrammarArgs &g, int b, int V, int lane) {
+    const int s = min(max(g.state[b], 0), g.states - 1);
+    const int16_t *row = g.next + (size_t)s * V;
+    bool any = false;
+    for (int i = lane; i < V; i += 64) any |= row[i] >= 0;
+    return __ballot(any) ? row : nullptr;
+}
+
+// The state after `tok` was emitted from the state of `row` (grammar_row's result): the table's, resync[tok] out of a dead state.  A token
+// outside [0, V) (no finite logit in the row) leads to start, so that no index leaves the tables.
+__device__ __forceinline__ int grammar_advance(const GrammarArgs &g, const int16_t *row, int tok, int V) {
+    if ((unsigned)tok >= (unsigned)V) return g.start;
+    return row ? row[tok] : g.resync[tok];
+}
+
+// row_argmax_sumexp over the tokens with allow[i] >= 0 (allow null: every token)
+__device__ __forceinline__ float row_argmax_sumexp_masked(const float *lg, int V, int lane, float &best, int &bi, const int16_t *allow) {
+    best = -INFINITY;
+    bi = 0x7fffffff;
+    for (int i = lane; i < V; i += 64) {
+        const float v = (allow && allow[i] < 0) ? -INFINITY : lg[i];
+        if (v > best) {
+            best = v;
+            bi = i;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bi, o);
+        if (ov > best || (ov == best && oi < bi)) {
+            best = ov;
+            bi = oi;
+        }
+    }
+    float se = 0.f;
+    for (int i = lane; i < V; i += 64) se += expf(((allow && allow[i] < 0) ? -INFINITY : lg[i]) - best);
+    return wave_sum(se);
+}
+
+// topk_draw_row over the tokens with allow[i] >= 0 (allow null: every token): with fewer than top_k of them the kept set is the allowed set -
+// the trailing rounds find none - and the rounding fallback of the draw is the last entry that holds a token.
+__device__ __forceinline__ int topk_draw_row_masked(const float *lg, int V, int lane, float *sv, int *si, int top_k, float inv_temperature,
+                                                    float u, float &lp, const int16_t *allow) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (lane + 64 * j < V && !(allow && allow[lane + 64 * j] < 0)) ? lg[lane + 64 * j] : -INFINITY;
+    const int k = min(top_k, V);
+    for (int r = 0; r < k; ++r) {
+        float best = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (v[j] > best) {
+                best = v[j];
+                bi = lane + 64 * j;
+            }
+        if (best == -INFINITY) bi = 0x7fffffff;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(best, o);
+            const int oi = __shfl_xor(bi, o);
+            if (ov > best || (ov == best && oi < bi)) {
+                best = ov;
+                bi = oi;
+            }
+        }
+        if ((bi & 63) == lane) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (bi == lane + 64 * j) v[j] = -INFINITY;
+        }
+        if (lane == 0) {
+            sv[r] = best;
+            si[r] = bi;
+        }
+    }
+    const bool in = lane < k;
+    const float x = in ? sv[lane] : -INFINITY, m = sv[0];
+    const float pT = in ? expf((x - m) * inv_temperature) : 0.f;
+    const float p1 = in ? expf(x - m) : 0.f;
+    const float sumT = wave_sum(pT), sum1 = wave_sum(p1);
+    float cdf = pT;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(cdf, o);
+        if (lane >= o) cdf += up;
+    }
+    const float target = u * sumT;
+    const unsigned long long hit = __ballot(in && cdf > target);
+    const int last = max(__popcll(__ballot(in && x > -INFINITY)), 1) - 1;
+    const int r = hit ? __builtin_ctzll(hit) : last;
+    lp = (sv[r] - m) - logf(sum1);
+    return si[r];
+}
+
+// argmax_logprob_kernel (with its bookkeeping) under the automaton: logprobs holds the log-softmax over the allowed tokens
+__global__ __launch_bounds__(1024) void grammar_argmax_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                             int32_t *step, int32_t *finished, int eos, int round_lp, const float *emb,
+                                                             const float *pos, float *x, int E, int Tmax, GrammarArgs g) {
+    __shared__ int unfinished[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = step[0];
+    int cnt = 0;
+    const int nw = blockDim.x >> 6;
+    for (int b = wave; b < B; b += nw) {
+        const float *lg = logits + (size_t)b * V;
+        float best;
+        int bi;
+        const int16_t *allow = grammar_row(g, b, V, lane);
+        const float se = row_argmax_sumexp_masked(lg, V, lane, best, bi, allow);
+        float lp = -logf(se);
+        if (round_lp) lp = round_bf16(lp);
+        int fin = finished[b];
+        if (bi == eos) fin = 1;
+        if (lane == 0) {
+            seqs[(size_t)b * max_len + t] = bi;
+            logprobs[(size_t)b * max_len + t] = lp;
+            finished[b] = fin;
+            g.state[b] = grammar_advance(g, allow, bi, V);
+        }
+        cnt += fin ? 0 : 1;
+        if (emb && t + 1 < Tmax)
+            for (int i = lane * 4; i < E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)bi * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+    }
+    if (lane == 0) unfinished[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < nw; ++w) tot += unfinished[w];
+        finished[B] = tot;
+        step[0] = t + 1;
+        step[1] = step[1] + 1;
+    }
+}
+
+// sample_logprob_kernel under the automaton
+__global__ __launch_bounds__(256) void grammar_sample_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                             const int32_t *step, int32_t *finished, int eos, int round_lp,
+                                                             const float *uniforms, int top_k, float inv_temperature, const float *emb,
+                                                             const float *pos, float *xnext, int E, int Tmax, GrammarArgs g) {
+    __shared__ float sv[4][64];
+    __shared__ int si[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + wave;
+    if (b >= B) return;
+    const int t = step[0];
+    float lp;
+    const int16_t *allow = grammar_row(g, b, V, lane);
+    const int tok = topk_draw_row_masked(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
+                                         uniforms[(size_t)b * max_len + t], lp, allow);
+    if (round_lp) lp = round_bf16(lp);
+    if (lane == 0) {
+        seqs[(size_t)b * max_len + t] = tok;
+        logprobs[(size_t)b * max_len + t] = lp;
+        if (tok == eos) finished[b] = 1;
+        g.state[b] = grammar_advance(g, allow, tok, V);
+    }
+    if (emb && t + 1 < Tmax)
+        for (int i = lane * 4; i < E; i += 256) {
+            const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+            *reinterpret_cast<float4 *>(xnext + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+        }
+}
+
+// slot_argmax_kernel under the automaton: a finished or idle row reads and writes no state
+__global__ __launch_bounds__(1024) void slot_grammar_argmax_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                                  int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap,
+                                                                  int eos, int round_lp, const float *emb, const float *pos, float *x, int E,
+                                                                  int Tmax, GrammarArgs g) {
+    __shared__ int unfinished[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int cnt = 0;
+    const int nw = blockDim.x >> 6;
+    for (int b = wave; b < B; b += nw) {
+        if (finished[b]) continue;   // wave-uniform
+        const int t = slot_t[b];
+        const float *lg = logits + (size_t)b * V;
+        float best;
+        int bi;
+        const int16_t *allow = grammar_row(g, b, V, lane);
+        const float se = row_argmax_sumexp_masked(lg, V, lane, best, bi, allow);
+        float lp = -logf(se);
+        if (round_lp) lp = round_bf16(lp);
+        const bool fin = bi == eos || t >= slot_cap[b] - 1;
+        if (lane == 0) {
+            seqs[(size_t)b * max_len + t] = bi;
+            logprobs[(size_t)b * max_len + t] = lp;
+            if (fin) finished[b] = 1;
+            else slot_t[b] = t + 1;
+            g.state[b] = grammar_advance(g, allow, bi, V);
+        }
+        if (!fin) {   // t + 1 <= cap - 1 < max_len <= Tmax
+            cnt += 1;
+            for (int i = lane * 4; i < E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)bi * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+        }
+    }
+    if (lane == 0) unfinished[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < nw; ++w) tot += unfinished[w];
+        finished[B] = tot;
+        const int nxt = step[1] + 1;
+        step[1] = nxt >= Tmax ? 0 : nxt;
+    }
+}
+
+// slot_sample_kernel under the automaton (the same ticket hand-off closes the step)
+__global__ __launch_bounds__(256) void slot_grammar_sample_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
+                                                                  int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap,
+                                                                  int eos, int round_lp, const float *uniforms, int ld_uniforms,
+                                                                  const int32_t *urow, int top_k, float inv_temperature, const float *emb,
+                                                                  const float *pos, float *x, int E, int Tmax, unsigned *ticket, GrammarArgs g) {
+    __shared__ float sv[4][64];
+    __shared__ int si[4][64];
+    __shared__ int is_last;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
+        if (finished[b]) continue;   // wave-uniform
+        const int t = slot_t[b];
+        float lp;
+        const int16_t *allow = grammar_row(g, b, V, lane);
+        const int tok = topk_draw_row_masked(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
+                                             uniforms[(size_t)urow[b] * ld_uniforms + t], lp, allow);
+        if (round_lp) lp = round_bf16(lp);
+        const bool fin = tok == eos || t >= slot_cap[b] - 1;
+        if (lane == 0) {
+            seqs[(size_t)b * max_len + t] = tok;
+            logprobs[(size_t)b * max_len + t] = lp;
+            if (fin) __hip_atomic_store(finished + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else slot_t[b] = t + 1;
+            g.state[b] = grammar_advance(g, allow, tok, V);
+        }
+        if (!fin)
+            for (int i = lane * 4; i < E; i += 256) {
+                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
+                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+            }
+    }
+    if (gridDim.x > 1) {
+        __threadfence();
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned n = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            is_last = n == gridDim.x - 1;
+            if (is_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (gridDim.x > 1 && !is_last) return;
+    if (wave == 0) {
+        int cnt = 0;
+        for (int b = lane; b < B; b += 64) cnt += __hip_atomic_load(finished + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 1;
+        cnt = (int)wave_sum((float)cnt);
+        if (lane == 0) {
+            finished[B] = cnt;
+            const int nxt = step[1] + 1;
+            step[1] = nxt >= Tmax ? 0 : nxt;
+        }
+    }
+}
+
 }  // namespace
 
 static int round_lp(const AcaiDecoder *d) { return (d->flags & ACAI_GEMM_ROUND_BF16) ? 1 : 0; }
@@ -714,6 +996,45 @@ int launch_argmax_logprob(const AcaiDecoder *d, bool chained, hipStream_t st) {
     hipLaunchKernelGGL(argmax_logprob_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
                        d->finished, d->eos, round_lp(d), 1, chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax);
     ACAI_LAUNCH_CHECK("argmax_logprob");
+    return 0;
+}
+
+static GrammarArgs grammar_args(const AcaiGrammar *gr) { return GrammarArgs{gr->next, gr->resync, gr->state, gr->states, gr->start}; }
+
+// the grammar-constrained forms of launch_argmax_logprob / launch_sample_logprob / launch_slot_argmax / launch_slot_sample
+int launch_grammar_argmax(const AcaiDecoder *d, const AcaiGrammar *gr, bool chained, hipStream_t st) {
+    hipLaunchKernelGGL(grammar_argmax_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
+                       d->finished, d->eos, round_lp(d), chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax,
+                       grammar_args(gr));
+    ACAI_LAUNCH_CHECK("grammar_argmax");
+    return 0;
+}
+
+int launch_grammar_sample(const AcaiDecoder *d, const AcaiGrammar *gr, const float *uniforms, int top_k, float temperature, bool chained,
+                          hipStream_t st) {
+    hipLaunchKernelGGL(grammar_sample_kernel, dim3(cdiv(d->B, 4)), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len,
+                       d->step, d->finished, d->eos, round_lp(d), uniforms, top_k, 1.0f / temperature,
+                       chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax, grammar_args(gr));
+    hipLaunchKernelGGL(sample_bookkeeping_kernel, dim3(1), dim3(64), 0, st, d->B, d->step, d->finished);
+    ACAI_LAUNCH_CHECK("grammar_sample");
+    return 0;
+}
+
+int launch_slot_grammar_argmax(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *gr, hipStream_t st) {
+    hipLaunchKernelGGL(slot_grammar_argmax_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
+                       d->finished, sl->t, (const int32_t *)sl->cap, d->eos, round_lp(d), (const float *)d->emb, (const float *)d->pos, d->x,
+                       d->E, d->Tmax, grammar_args(gr));
+    ACAI_LAUNCH_CHECK("slot_grammar_argmax");
+    return 0;
+}
+
+int launch_slot_grammar_sample(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *gr, const float *uniforms, int ld_uniforms,
+                               const int32_t *urow, int top_k, float temperature, hipStream_t st) {
+    hipLaunchKernelGGL(slot_grammar_sample_kernel, dim3(d->tickets ? cdiv(d->B, 4) : 1), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs,
+                       d->logprobs, d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos, round_lp(d), uniforms,
+                       ld_uniforms, urow, top_k, 1.0f / temperature, (const float *)d->emb, (const float *)d->pos, d->x, d->E, d->Tmax,
+                       (unsigned *)d->tickets, grammar_args(gr));
+    ACAI_LAUNCH_CHECK("slot_grammar_sample");
     return 0;
 }
 

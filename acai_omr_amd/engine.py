@@ -279,7 +279,8 @@ class DecodeEngine:
         # what a decode step does: ("greedy",), ("sample", top_k, temperature), ("beam", K), ("slot",) (continuous batching),
         # ("slot_sample", top_k, temperature) (continuous batching, sampled), ("spec", D, ngram) (speculative greedy; ngram 0 = drafts from
         # the injected table), ("prompt",) (greedy from given tokens) or ("spec", D, ngram, "prompt") (the two together); a run sets it and
-        # restores greedy when it ends
+        # restores greedy when it ends.  Grammar-constrained decoding: ("grammar",), ("grammar_sample", top_k, temperature), ("slot_grammar",),
+        # ("slot_grammar_sample", top_k, temperature) - the four forms above with the token choice masked by a token automaton
         self._mode = ("greedy",)
         self.uniforms = None    # (Bmax, Tmax) uniforms of the sampling step, allocated on first use
         self.beam_anc = None    # beam-search lineage [2][Bmax][Tmax] (anc / tok / lp) and per-row cum / len, allocated on first use
@@ -291,6 +292,7 @@ class DecodeEngine:
         self.slot_uniforms = None
         self.spec_t = None      # speculative decoding: per-image state (t, cap, steps, key table, next inputs, injected drafts), allocated on first use
         self.prompt_tok = None  # prompted decoding: (Bmax, Tmax) int32 tokens by output index and (Bmax,) int32 lengths, allocated on first use
+        self.gram_next = None   # grammar-constrained decoding: engine-owned copies of the automaton's tables and the rows' states (_set_grammar)
         self._per_row_cross = False
         self.cache_len = 0
         self._desc = None
@@ -484,11 +486,19 @@ class DecodeEngine:
         cur.wait_stream(self.stream)
 
     # ---- ViTOMR.cached_greedy_generate (models.py:600-615) ----------------------------------------------------------
-    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None, prompt=None):
+    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None, prompt=None, *, grammar=None):
         """Runs up to max_len-1 greedy steps; returns views seqs (B,max_len) int64 and logprobs (B,max_len) fp32.
         Early exit when every row has produced <eos> (checked every `poll` steps; overshoot is masked later).
         prompt (an extension; None = off): one token list / 1-D tensor per row, the row's tokens of indices 1 .. P (_set_prompt); the row
-        takes them whatever the model prefers, records the model's log-prob of each, and decodes greedily from index P + 1."""
+        takes them whatever the model prefers, records the model's log-prob of each, and decodes greedily from index P + 1.
+        grammar (an extension; None = off): a grammar.TokenAutomaton - every row takes the best token its automaton state allows and
+        logprobs holds the log-softmax over the allowed tokens (_set_grammar); not combinable with prompt."""
+        if grammar is not None:
+            if prompt is not None:
+                raise ValueError("grammar (constrained decoding) cannot be combined with prompt (prompted decoding): out of scope here")
+            with self._run(max_len, ("grammar",)):
+                self._set_grammar(grammar)
+                return self._decode_loop(max_len, poll, use_graph, on_chunk)
         if prompt is None:
             with self._run(max_len, ("greedy",)):
                 return self._decode_loop(max_len, poll, use_graph, on_chunk)
@@ -520,11 +530,57 @@ class DecodeEngine:
         self.prompt_tok[:n].copy_(ops.h2d(tab, self.device))
         self.prompt_len[:n].copy_(ops.h2d(lens, self.device))
 
+    # ---- grammar-constrained decoding (an extension: the reference knows no grammar) -----------------------------------------------------------
+    GRAMMAR_MODES = ("grammar", "grammar_sample", "slot_grammar", "slot_grammar_sample")
+
+    def _set_grammar(self, automaton):
+        """Copies a grammar.TokenAutomaton's tables into engine-owned device buffers that keep their address from run to run (_set_prompt's
+        pattern), so the captured grammar-mode graphs stay valid; written on the current stream, before arming.  A larger automaton
+        reallocates the table; that, or another number of states or start state (both are launch arguments), drops the grammar modes'
+        graphs.  The copy is skipped when `automaton` is the object of the previous run: an automaton is not edited in place."""
+        from .grammar import TokenAutomaton
+        if not isinstance(automaton, TokenAutomaton):
+            raise TypeError(f"grammar must be a grammar.TokenAutomaton, got {type(automaton).__name__}")
+        S, V = automaton.states, automaton.vocab_size
+        if V != self.V:
+            raise ValueError(f"the grammar is over {V} tokens, the decoder's vocabulary has {self.V}")
+        if self.V > 512:
+            raise ValueError(f"grammar-constrained decoding needs a vocabulary of at most 512 tokens, got {self.V}")
+        stale = False
+        if self.gram_next is None:
+            self.gram_resync = torch.zeros(V, dtype=torch.int16, device=self.device)
+            self.gram_state = torch.zeros(self.Bmax, dtype=torch.int32, device=self.device)
+            self._gram_desc = _lib.AcaiGrammar()
+            self._gram_src = None
+        if self.gram_next is None or self.gram_next.shape[0] < S:
+            self.gram_next = torch.zeros(S, V, dtype=torch.int16, device=self.device)
+            self._gram_src, stale = None, True
+        d = self._gram_desc
+        if (d.states, d.start) != (S, automaton.start):
+            stale = True
+        if stale:
+            for key in [k for k in self.graphs if k[4][0] in self.GRAMMAR_MODES]:
+                del self.graphs[key]
+        d.next, d.resync, d.state = self.gram_next.data_ptr(), self.gram_resync.data_ptr(), self.gram_state.data_ptr()
+        d.states, d.start, d.rows = S, automaton.start, self.Bmax
+        if self._gram_src is not automaton:
+            src_next, src_resync = automaton.next, automaton.resync
+            if not src_next.is_cuda:
+                src_next, src_resync = ops.h2d(src_next.contiguous(), self.device), ops.h2d(src_resync.contiguous(), self.device)
+            self.gram_next[:S].copy_(src_next)
+            self.gram_resync.copy_(src_resync)
+            self._gram_src = automaton
+
     # ---- GRPOViTOMR.cached_forward_rollout_policy (models.py:988-1049) ---------------------------------------------------------
-    def sample(self, max_actions, top_k, temperature, uniforms=None, poll=16, use_graph=True):
+    def sample(self, max_actions, top_k, temperature, uniforms=None, poll=16, use_graph=True, *, grammar=None):
         """Up to max_actions-1 sampling steps (top-k, temperature, inverse-CDF draw from `uniforms` (B, max_actions) in [0,1) - drawn from
-        torch's generator when None).  Returns views seqs (B, max_actions), logprobs (B, max_actions) and the number of steps run."""
-        with self._run(max_actions, ("sample", int(top_k), float(temperature))):
+        torch's generator when None).  Returns views seqs (B, max_actions), logprobs (B, max_actions) and the number of steps run.
+        grammar (None = off): a grammar.TokenAutomaton - the top-k, the draw and the recorded log_softmax(kept) run over the tokens the
+        row's automaton state allows."""
+        mode = ("sample" if grammar is None else "grammar_sample", int(top_k), float(temperature))
+        with self._run(max_actions, mode):
+            if grammar is not None:
+                self._set_grammar(grammar)
             B = self.B
             if self.uniforms is None:
                 self.uniforms = torch.zeros(self.Bmax, self.Tmax, dtype=torch.float32, device=self.device)
@@ -534,20 +590,27 @@ class DecodeEngine:
             self.uniforms[:B, :max_actions] = uniforms.to(device=self.device, dtype=torch.float32)
             return self._decode_loop(max_actions, poll, use_graph)
 
-    def greedy_chunks(self, max_len, chunk, prompt=None):
+    def greedy_chunks(self, max_len, chunk, prompt=None, *, grammar=None):
         """Generator over the greedy loop in chunks of `chunk` tokens (streamed inference): yields (tokens_done, all_finished)
         after each chunk; the decode graph is replayed on the engine's stream, the caller's stream waits for it.
-        prompt: as in greedy(); the mode is ("prompt",) while the generator runs and goes back to greedy when it ends or is closed."""
+        prompt / grammar: as in greedy(); the mode is ("prompt",) / ("grammar",) while the generator runs and goes back to greedy when it
+        ends or is closed."""
         if max_len > self.Tmax:
             raise RuntimeError(f"{max_len} decoding steps is too long for max sequence length of {self.Tmax}")
+        if grammar is not None and prompt is not None:
+            raise ValueError("grammar (constrained decoding) cannot be combined with prompt (prompted decoding): out of scope here")
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         if prompt is not None:
             self._mode = ("prompt",)
+        if grammar is not None:
+            self._mode = ("grammar",)
         try:
             with torch.cuda.stream(self.stream):
                 if prompt is not None:
                     self._set_prompt(prompt, self.B, max_len)
+                if grammar is not None:
+                    self._set_grammar(grammar)
                 self._arm_and_capture(self.B)
             done, total = 0, max_len - 1
             while done < total:
@@ -562,7 +625,7 @@ class DecodeEngine:
                 if fin:
                     return
         finally:
-            if prompt is not None:
+            if prompt is not None or grammar is not None:
                 self._mode = ("greedy",)
 
     # ---- beam search (an extension: the reference decodes greedily) ----------------------------------------------------------------------
@@ -684,7 +747,7 @@ class DecodeEngine:
         self.beam_len[:B].zero_()
 
     def arm(self, B):
-        if self._mode[0] in ("slot", "slot_sample"):
+        if self._mode[0] in ("slot", "slot_sample", "slot_grammar", "slot_grammar_sample"):
             self._slot_reset()
             return
         if self._mode[0] == "spec":
@@ -699,6 +762,8 @@ class DecodeEngine:
         self.step.copy_(torch.tensor([1, 0], dtype=torch.int32))
         if self._mode[0] == "beam":
             self._arm_beam(B)
+        if self._mode[0] in ("grammar", "grammar_sample"):
+            self.gram_state[:B].fill_(self._gram_desc.start)
         # input of the first step (<bos> at position 1, quirk Q1); each step's argmax / sampling kernel writes the next step's input
         _lib.check(_lib.lib().acai_decode_embed(ctypes.byref(self._desc), ops._st()), "acai_decode_embed")
         self._x_valid = True
@@ -721,6 +786,18 @@ class DecodeEngine:
                        "acai_decode_spec_prompt_step")
         elif mode[0] == "spec":
             _lib.check(L.acai_decode_spec_step(d, ctypes.byref(self._spec_desc), st), "acai_decode_spec_step")
+        elif mode[0] == "grammar":
+            _lib.check(L.acai_decode_grammar_step(d, ctypes.byref(self._gram_desc), st), "acai_decode_grammar_step")
+        elif mode[0] == "grammar_sample":
+            _lib.check(L.acai_decode_grammar_sample_step(d, ctypes.byref(self._gram_desc), self.uniforms.data_ptr(), mode[1], mode[2], st),
+                       "acai_decode_grammar_sample_step")
+        elif mode[0] == "slot_grammar":
+            _lib.check(L.acai_decode_slot_grammar_step(d, ctypes.byref(self._slot_desc), ctypes.byref(self._gram_desc), st),
+                       "acai_decode_slot_grammar_step")
+        elif mode[0] == "slot_grammar_sample":
+            _lib.check(L.acai_decode_slot_grammar_sample_step(d, ctypes.byref(self._slot_desc), ctypes.byref(self._gram_desc),
+                                                              self.slot_uniforms.data_ptr(), self.Tmax, self.slot_urow.data_ptr(), mode[1],
+                                                              mode[2], st), "acai_decode_slot_grammar_sample_step")
         elif mode[0] == "slot_sample":
             _lib.check(L.acai_decode_slot_sample_step(d, ctypes.byref(self._slot_desc), self.slot_uniforms.data_ptr(), self.Tmax,
                                                       self.slot_urow.data_ptr(), mode[1], mode[2], st), "acai_decode_slot_sample_step")
@@ -796,7 +873,7 @@ class DecodeEngine:
         return self.seqs[:B, :max_len], self.logprobs[:B, :max_len], done
 
     # ---- continuous batching (an extension: the reference decodes one static batch) ----------------------------------------------------
-    def continuous(self, mem32, memb, lens, caps, slots, poll=16, use_graph=True, sample=None, uniforms=None, group=1):
+    def continuous(self, mem32, memb, lens, caps, slots, poll=16, use_graph=True, sample=None, uniforms=None, group=1, *, grammar=None):
         """Decode of len(lens) images through `slots` decode rows that are refilled as they finish: greedy, or with sample=(top_k,
         temperature) sampled as DecodeEngine.sample samples.  mem32 / memb: the images' packed memories (M, E) fp32 / bf16 copy, lens
         their lengths, caps[i] image i's cap (its row ends after token index caps[i] - 1, or at <eos>).  Checks the arguments at the call,
@@ -806,7 +883,10 @@ class DecodeEngine:
         Sampled runs: sequence i draws token index t from uniforms[i, t] (`uniforms` (N, max(caps)) in [0, 1); from torch's generator on
         the device when None), whichever slot and step it runs in; the mode is ("slot_sample", top_k, temperature), with graphs of its own.
         group = G > 1 (sampled runs only): every memory is queued G times - sequences m*G .. m*G+G-1 decode memory m, caps and uniforms
-        are per sequence (N = len(lens) * G), and each admission prefills its own slot region."""
+        are per sequence (N = len(lens) * G), and each admission prefills its own slot region.
+        grammar (None = off): a grammar.TokenAutomaton constraining every sequence as DecodeEngine.greedy / sample(grammar=) constrain it;
+        a slot's automaton state is set to the start state when the slot is refilled.  Modes ("slot_grammar",) / ("slot_grammar_sample",
+        top_k, temperature)."""
         S = int(slots)
         caps = [int(c) for c in caps]
         if max(caps) > self.Tmax:
@@ -830,9 +910,14 @@ class DecodeEngine:
                 raise ValueError(f"uniforms must be (N, max(caps)) = ({len(caps)}, {max(caps)}), got {tuple(uniforms.shape)}")
         elif uniforms is not None:
             raise ValueError("uniforms are the draws of a sampled run: pass sample=(top_k, temperature) with them")
-        return self._continuous(mem32, memb, lens, caps, S, poll, use_graph, mode, uniforms, G)
+        if grammar is not None:
+            from .grammar import TokenAutomaton
+            if not isinstance(grammar, TokenAutomaton):
+                raise TypeError(f"grammar must be a grammar.TokenAutomaton, got {type(grammar).__name__}")
+            mode = ("slot_grammar",) if sample is None else ("slot_grammar_sample",) + mode[1:]
+        return self._continuous(mem32, memb, lens, caps, S, poll, use_graph, mode, uniforms, G, grammar)
 
-    def _continuous(self, mem32, memb, lens, caps, S, poll, use_graph, mode=("slot",), uniforms=None, G=1):
+    def _continuous(self, mem32, memb, lens, caps, S, poll, use_graph, mode=("slot",), uniforms=None, G=1, grammar=None):
         N, dev, own = len(caps), self.device, self.omr
         self._slot_group = G
         mem = memb if self.bf else mem32
@@ -856,6 +941,8 @@ class DecodeEngine:
                 lens_dev = ops.h2d(torch.tensor(lens, dtype=torch.int32), dev)
                 if uniforms is not None:
                     self._slot_uniforms(uniforms)
+                if grammar is not None:
+                    self._set_grammar(grammar)
                 self._mode = mode
                 self._arm_and_capture(S, use_graph)
             if sched.skipped:
@@ -917,11 +1004,11 @@ class DecodeEngine:
 
     def _slot_uniforms(self, uniforms):
         """The run's draws in the (rows, Tmax) table the sampled slot step reads, and the per-slot row index.  The table only grows; a
-        reallocation drops the sampled slot graphs (they hold its address), never the greedy ones."""
+        reallocation drops the sampled slot graphs (they hold its address; the grammar form's too), never the greedy ones."""
         N, W = uniforms.shape
         if self.slot_uniforms is None or self.slot_uniforms.shape[0] < N:
             self.slot_uniforms = torch.zeros(N, self.Tmax, dtype=torch.float32, device=self.device)
-            for key in [k for k in self.graphs if k[4][0] == "slot_sample"]:
+            for key in [k for k in self.graphs if k[4][0] in ("slot_sample", "slot_grammar_sample")]:
                 del self.graphs[key]
         if self.slot_urow is None:
             self.slot_urow = torch.zeros(self.Bmax, dtype=torch.int32, device=self.device)
@@ -964,7 +1051,10 @@ class DecodeEngine:
             self.cross_len[s:s + 1].copy_(lens_dev[i:i + 1])
             self._parked.discard(s)
         table = [[s for s, _ in admitted], [caps[i] for _, i in admitted]]
-        sampled = self._mode[0] == "slot_sample"
+        sampled = self._mode[0] in ("slot_sample", "slot_grammar_sample")
+        if self._mode[0] in ("slot_grammar", "slot_grammar_sample"):   # a refilled row starts in the automaton's start state; rows that stay
+            for s, _ in admitted:                                      # idle keep whatever their state holds (it is never read)
+                self.gram_state[s:s + 1].fill_(self._gram_desc.start)
         if sampled:
             table.append([i for _, i in admitted])   # the slot's uniforms row: the sequence's own, whichever slot it lands in
         rows = ops.h2d(torch.tensor(table, dtype=torch.int32), self.device)

@@ -32,7 +32,8 @@ def _encode(vitomr, img):
         return vitomr.encoder.forward_packed(img)
 
 
-def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1, length_penalty=1.0, speculative=0, ngram=3, prefix=None):
+def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1, length_penalty=1.0, speculative=0, ngram=3, prefix=None, *,
+              grammar=None):
     """img: one (1,H,W) tensor or a list of them -> (seqs int64 (B,T'), log_probs fp32 (B,T'), seq_mask bool (B,T')).
     beam_width > 1 (extension): beam search with that many hypotheses per image, scored by cum / len^length_penalty
     (ViTOMR.cached_beam_generate); beam_width = 1 is the reference's greedy decode.
@@ -41,7 +42,15 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
     cache's max batch size, and cannot be combined with beam_width > 1 or an FP8 memory cache (ValueError).
     prefix (extension, default None = off): prompted decoding - one entry per image with the already known tokens of output indices
     1 .. P_i (ViTOMR.cached_greedy_generate); works with greedy and speculative decoding, not with beam search (ValueError: out of scope
-    here)."""
+    here).
+    grammar (extension, default None = off): a grammar.TokenAutomaton - greedy decoding in which every token is one the automaton allows
+    after the tokens before it (ViTOMR.cached_greedy_generate); with beam_width > 1, speculative or prefix it raises ValueError (out of
+    scope here).  What a learned automaton does to the output of a trained checkpoint has not been measured."""
+    if grammar is not None:
+        for other, on in (("beam search (beam_width > 1)", beam_width != 1), ("speculative decoding (speculative)", bool(speculative)),
+                          ("prompted decoding (prefix)", prefix is not None)):
+            if on:
+                raise ValueError(f"grammar (constrained decoding) cannot be combined with {other}: out of scope here")
     if speculative and beam_width != 1:
         raise ValueError("speculative decoding cannot be combined with beam search (beam_width > 1)")
     if prefix is not None and beam_width != 1:
@@ -57,7 +66,7 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
                                                   prefix=prefix)
             if beam_width != 1:
                 return vitomr._beam_packed(None if bf else mem, mem if bf else None, lens, beam_width, max_inference_len, length_penalty)
-            return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, prefix=prefix)
+            return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, prefix=prefix, grammar=grammar)
 
 
 def _encode_chunks(vitomr, imgs, device):
@@ -73,11 +82,11 @@ def _encode_chunks(vitomr, imgs, device):
     return (mems[0] if len(mems) == 1 else torch.cat(mems)), lens
 
 
-def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None):
+def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None):
     """Continuous-batching greedy inference (an extension) as a generator: yields (index, seqs (1,T'), log_probs (1,T'), mask (1,T')) for
     each image as soon as it finishes, in completion order; each is what inference(vitomr, [imgs[index]]) returns.  max_inference_len: one
     cap or a list of per-image caps; slots: decode rows (default: the cache's max batch size).  prefix (prompted decoding, inference())
-    is not supported here: anything but None raises ValueError."""
+    is not supported here: anything but None raises ValueError.  grammar: constrained decoding as in inference()."""
     vitomr._no_prefix(prefix, "continuous batching")
     vitomr.eval()
     imgs = list(imgs)
@@ -85,7 +94,7 @@ def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=15
         mem, lens = _encode_chunks(vitomr, imgs, device)
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
-            run = vitomr._continuous_packed_iter(None if bf else mem, mem if bf else None, lens, max_inference_len, slots)
+            run = vitomr._continuous_packed_iter(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
 
     def images():
         with torch.no_grad():
@@ -93,11 +102,12 @@ def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=15
     return images()
 
 
-def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None):
+def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None):
     """inference() over a list of any length through continuous batching (an extension): `slots` decode rows work through the images in
     input order and a finished row is refilled with the next image at once.  Returns exactly what inference(vitomr, imgs, ...) returns
     (seqs (N,T'), log_probs (N,T'), mask (N,T'), clipped to the longest row); max_inference_len may be a list of per-image caps.  prefix
-    (prompted decoding, inference()) is not supported here: anything but None raises ValueError."""
+    (prompted decoding, inference()) is not supported here: anything but None raises ValueError.  grammar: constrained decoding as in
+    inference()."""
     vitomr._no_prefix(prefix, "continuous batching")
     vitomr.eval()
     imgs = list(imgs)
@@ -105,12 +115,12 @@ def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, s
         mem, lens = _encode_chunks(vitomr, imgs, device)
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
-            return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots)
+            return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
 
 
-def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None):
+def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None, *, grammar=None):
     """prefix (extension, default None = off): prompted decoding of the one image, as in inference(); the forced tokens arrive in the
-    STEP events like any others."""
+    STEP events like any others.  grammar (extension, default None = off): constrained decoding as in inference(), not with prefix."""
     vitomr.eval()
     with torch.no_grad():
         yield {"type": InferenceEvent.ENCODING_START.value, "payload": None}
@@ -119,5 +129,5 @@ def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flus
             img_latent = vitomr.transition_head(img_latent)
             yield {"type": InferenceEvent.ENCODING_FINISH.value, "payload": None}
             for event in vitomr.streamed_cached_greedy_generate(img_latent, latent_attention_mask, max_len=max_inference_len,
-                                                                flush_interval=flush_interval, prefix=prefix):
+                                                                flush_interval=flush_interval, prefix=prefix, grammar=grammar):
                 yield event

@@ -573,24 +573,43 @@ class ViTOMR(nn.Module):
         if prefix is not None:
             raise ValueError(f"prefix (prompted decoding) cannot be combined with {what}: out of scope here")
 
-    def _greedy_packed(self, mem32, memb, lens, max_len, on_chunk=None, prefix=None):
+    @staticmethod
+    def _check_grammar(grammar, prefix=None):
+        """Grammar-constrained decoding (an extension): `grammar` as the entry points take it - None, or a grammar.TokenAutomaton."""
+        if grammar is None:
+            return
+        from ..grammar import TokenAutomaton
+        if not isinstance(grammar, TokenAutomaton):
+            raise TypeError(f"grammar must be a grammar.TokenAutomaton, got {type(grammar).__name__}")
+        if prefix is not None:
+            raise ValueError("grammar (constrained decoding) cannot be combined with prefix (prompted decoding): out of scope here")
+
+    def _greedy_packed(self, mem32, memb, lens, max_len, on_chunk=None, prefix=None, grammar=None):
         blocks = self.decoder._cached_blocks()
+        self._check_grammar(grammar, prefix)
         prompt = self._check_prefix(prefix, len(lens), max_len)
         blocks.prepare_caches_packed(mem32, memb, lens)
         eng = blocks.engine(self.decoder.pos_embedding.device)
-        seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk) if prompt is None else eng.greedy(max_len, on_chunk=on_chunk, prompt=prompt)
+        if grammar is not None:
+            seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk, grammar=grammar)
+        else:
+            seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk) if prompt is None else eng.greedy(max_len, on_chunk=on_chunk, prompt=prompt)
         return self.mask_and_clip_seqs(seqs.clone(), lps.clone())
 
-    def cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, prefix=None):
+    def cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, prefix=None, *, grammar=None):
         """Batched greedy decode with KV caching (M:600-615) -> seqs (B,T') int64, log_probs (B,T') fp32, mask (B,T') bool.
         The whole loop runs as replays of one captured hipGraph; the host only polls an "all finished" counter.
         prefix (an extension, default None = off): prompted decoding - one entry per image (a 1-D integer tensor or list, possibly empty;
         a single 1-D tensor for one image) with the tokens of output indices 1 .. P_i <= max_len - 1 that are already known.  The row takes
         them whatever the model would choose, log_probs holds the model's log-probability of each, and greedy decoding goes on from index
         P_i + 1; a prompt-final <eos> ends the row.  Ids must lie in [0, V), never <bos> or <pad>, <eos> only last (ValueError).  Where
-        the prompt is the model's own greedy output the result is bitwise the unprompted one."""
+        the prompt is the model's own greedy output the result is bitwise the unprompted one.
+        grammar (an extension, default None = off): a grammar.TokenAutomaton - at every index a row takes the best token its automaton state
+        allows, log_probs holds the log-softmax over the allowed tokens (the policy actually run), and the state advances on the device
+        inside the replayed graph.  An automaton that allows everything gives the unconstrained result bit for bit.  Not combinable with
+        prefix (ValueError)."""
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
-        return self._greedy_packed(mem32, None, lens, max_len, prefix=prefix)
+        return self._greedy_packed(mem32, None, lens, max_len, prefix=prefix, grammar=grammar)
 
     def _beam_packed(self, mem32, memb, lens, beam_width, max_len, length_penalty):
         blocks = self.decoder._cached_blocks()
@@ -654,10 +673,11 @@ class ViTOMR(nn.Module):
         S = blocks.max_batch_size if slots is None else slots
         return eng, caps, eng.continuous(mem32, memb, lens, caps, S, poll=poll, use_graph=use_graph, **sampling)
 
-    def _continuous_packed_iter(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True):
+    def _continuous_packed_iter(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True, grammar=None):
         """Continuous-batching greedy decode of packed memories: yields (index, seqs (1,T'), log_probs (1,T'), mask (1,T')) per image in
         completion order, each what _greedy_packed of that image alone at its cap returns."""
-        eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph)
+        self._check_grammar(grammar)
+        eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph, grammar=grammar)
 
         def images():
             for i in run:
@@ -675,27 +695,31 @@ class ViTOMR(nn.Module):
         return seqs[:, :n], lps[:, :n], seq_mask[:, :n]
 
     def _continuous_packed(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True, **sampling):
+        self._check_grammar(sampling.get("grammar"))
         eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph, **sampling)
         for _ in run:
             pass
         return self._mask_and_clip_capped(eng.cont_seqs, eng.cont_lps, caps)
 
-    def cached_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None, prefix=None):
+    def cached_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None, prefix=None, *, grammar=None):
         """Continuous-batching greedy decode (an extension: the reference decodes one static batch) -> seqs (N,T') int64, log_probs (N,T')
         fp32, mask (N,T') bool, as cached_greedy_generate on the same batch.  `slots` decode rows (default: the cache's max batch size)
         work through the N images in input order; a row that finishes (<eos> or its cap) is refilled with the next image while the others
         go on, so N may exceed the max batch size.  max_len: one cap for every image, or a sequence of N per-image caps (positions at or
         past an image's cap are masked).  prefix (prompted decoding, cached_greedy_generate) is not supported here: anything but None
-        raises ValueError."""
+        raises ValueError.  grammar: constrained decoding as in cached_greedy_generate; every image gets what it gets there alone."""
         self._no_prefix(prefix, "continuous batching")
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
-        return self._continuous_packed(mem32, None, lens, max_len, slots)
+        return self._continuous_packed(mem32, None, lens, max_len, slots, grammar=grammar)
 
-    def streamed_cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, flush_interval=25, prefix=None):
+    def streamed_cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, flush_interval=25, prefix=None, *,
+                                        grammar=None):
         """Generator of {"type", "payload"} events (M:625-647); single image only.
-        prefix: prompted decoding as in cached_greedy_generate; STEP events carry the forced tokens like any others."""
+        prefix: prompted decoding as in cached_greedy_generate; STEP events carry the forced tokens like any others.
+        grammar: constrained decoding as in cached_greedy_generate (not with prefix)."""
         if img_latent.shape[0] != 1:
             raise ValueError("Streamed generation only supports single image batches")
+        self._check_grammar(grammar, prefix)
         prompt = self._check_prefix(prefix, 1, max_len)
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         blocks = self.decoder._cached_blocks()
@@ -703,7 +727,8 @@ class ViTOMR(nn.Module):
         eng = blocks.engine(self.decoder.pos_embedding.device)
         # replay the decode graph flush_interval tokens at a time; after each chunk hand out the freshly written tokens
         # (the reference yields STEP at every t % flush_interval == 0 that did not finish the sequence - also at t == max_len - 1, M:641-645)
-        for t_done, finished in (eng.greedy_chunks(max_len, flush_interval) if prompt is None else
+        kw = {} if grammar is None else {"grammar": grammar}
+        for t_done, finished in (eng.greedy_chunks(max_len, flush_interval, **kw) if prompt is None else
                                  eng.greedy_chunks(max_len, flush_interval, prompt=prompt)):
             if finished:
                 break
@@ -803,7 +828,7 @@ class GRPOViTOMR(ViTOMR):
         return self.cached_forward_rollout_policy(img_latent, latent_attention_mask, max_actions, top_k, temperature)
 
     def cached_forward_rollout_policy(self, img_latent, latent_attention_mask, max_actions=768, top_k=50, temperature=1.2, group_size=None,
-                                      uniforms=None, prefix=None):
+                                      uniforms=None, prefix=None, *, grammar=None):
         """Sampling rollouts with KV caching (M:988-1049): per step keep the top_k logits, draw from softmax(kept / temperature), record
         log_softmax(kept)[drawn]; rows stop mattering after their first <eos>.  Returns rollouts (R, T') int64, rollout_log_probs (R, T') fp32,
         rollout_mask (R, T') bool with padding / zero log-probs outside the mask.
@@ -812,8 +837,12 @@ class GRPOViTOMR(ViTOMR):
         are inverse-CDF samples from `uniforms` (R, max_actions) in [0, 1), taken from torch's generator when None (so torch.manual_seed makes
         a rollout reproducible).  group_size (extension): img_latent rows r*group_size .. are the copies expand_img_latent_for_rollout made of
         one image; their cross K/V is then projected and stored once per image instead of once per rollout.  prefix (prompted decoding,
-        cached_greedy_generate) is not supported here: anything but None raises ValueError."""
+        cached_greedy_generate) is not supported here: anything but None raises ValueError.  grammar (an extension, default None = off): a
+        grammar.TokenAutomaton - the top-k filter, the draw and the recorded log_softmax(kept) run over the tokens the rollout's automaton
+        state allows, so a rollout cannot hold a transition the automaton forbids; rollout_log_probs is then the log-probability under the
+        constrained policy, which is the old policy of the GRPO ratio."""
         self._no_prefix(prefix, "sampling")
+        self._check_grammar(grammar)
         blocks = self.decoder._cached_blocks()
         G = 1 if group_size is None else int(group_size)
         if img_latent.shape[0] % G:
@@ -823,7 +852,7 @@ class GRPOViTOMR(ViTOMR):
         mem32, lens = EG.unpad_rows(lat, msk)
         blocks.prepare_caches_packed(mem32, None, lens, group_size=G)
         eng = blocks.engine(self.decoder.pos_embedding.device)
-        seqs, lps, _ = eng.sample(max_actions, top_k, temperature, uniforms=uniforms)
+        seqs, lps, _ = eng.sample(max_actions, top_k, temperature, uniforms=uniforms, grammar=grammar)
         return self.mask_and_clip_seqs(seqs.clone(), lps.clone())
 
     def cached_continuous_rollout_policy(self, img_latent, latent_attention_mask, max_actions=768, top_k=50, temperature=1.2, slots=None,
@@ -837,12 +866,26 @@ class GRPOViTOMR(ViTOMR):
 
         group_size = G > 1: img_latent holds the UNEXPANDED images and each is queued G times (rollouts i*G .. i*G+G-1 of the result, uniforms
         rows likewise).  Every admission prefills its own row's region, so an image's cross K/V projection is repeated G times - unlike
-        cached_forward_rollout_policy(group_size=G), which stores it once per image."""
+        cached_forward_rollout_policy(group_size=G), which stores it once per image.  The grammar-constrained form is
+        cached_constrained_continuous_rollout_policy."""
+        return self._continuous_rollouts(img_latent, latent_attention_mask, max_actions, top_k, temperature, slots, group_size, uniforms, None)
+
+    def cached_constrained_continuous_rollout_policy(self, img_latent, latent_attention_mask, grammar, max_actions=768, top_k=50, temperature=1.2,
+                                                     slots=None, group_size=1, uniforms=None):
+        """cached_continuous_rollout_policy under a grammar.TokenAutomaton (an extension; a method of its own because that one's parameter
+        list is pinned): every rollout is constrained as in cached_forward_rollout_policy(grammar=) and draws what it draws there alone."""
+        self._check_grammar(grammar)
+        if grammar is None:
+            raise TypeError("grammar must be a grammar.TokenAutomaton, got None")
+        return self._continuous_rollouts(img_latent, latent_attention_mask, max_actions, top_k, temperature, slots, group_size, uniforms, grammar)
+
+    def _continuous_rollouts(self, img_latent, latent_attention_mask, max_actions, top_k, temperature, slots, group_size, uniforms, grammar):
         G = int(group_size)
         if G < 1:
             raise ValueError(f"group_size must be >= 1, got {group_size}")
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
-        return self._continuous_packed(mem32, None, lens, max_actions, slots, sample=(top_k, temperature), uniforms=uniforms, group=G)
+        kw = {} if grammar is None else {"grammar": grammar}
+        return self._continuous_packed(mem32, None, lens, max_actions, slots, sample=(top_k, temperature), uniforms=uniforms, group=G, **kw)
 
 
 class TeacherForcedViTOMR(ViTOMR):

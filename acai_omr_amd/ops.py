@@ -706,6 +706,40 @@ def edit_distance(pred, pred_len, tgt, tgt_len, group=1, out=None):
     return out
 
 
+def grammar_scan(rollouts, rollout_mask, automaton):
+    """(violations int32 (R,), complete bool (R,)) of the rows rollouts[r, :len_r] under a grammar.TokenAutomaton (acai_grammar_scan; the CPU
+    statement is automaton.violations).  rollouts (R, T) int64; rollout_mask: a bool prefix mask of that shape or int32 lengths (R,), read on
+    the device as edit_distance reads them (no host sync).  The automaton's tables are used where they lie when they are on rollouts'
+    device (automaton.to(device) once, outside the loop) and copied there otherwise.  CPU rollouts take automaton.violations itself."""
+    if not rollouts.is_cuda:
+        return automaton.violations(rollouts, rollout_mask)
+    _chk(rollouts, "rollouts", torch.int64)
+    if rollouts.dim() != 2:
+        raise ValueError(f"rollouts: expected (rows, tokens), got {tuple(rollouts.shape)}")
+    _chk(rollout_mask, "rollout_mask")
+    lens = rollout_mask
+    if lens.dtype == torch.bool:
+        if lens.shape != rollouts.shape:
+            raise ValueError(f"rollout_mask: a mask must have rollouts' shape {tuple(rollouts.shape)}, got {tuple(lens.shape)}")
+        lens = lens.sum(dim=-1, dtype=torch.int32)
+    elif lens.dtype != torch.int32:
+        raise TypeError(f"rollout_mask: expected a bool mask or int32 lengths, got {lens.dtype}")
+    if lens.shape != (rollouts.shape[0],) or lens.device != rollouts.device:
+        raise ValueError(f"rollout_mask: expected {rollouts.shape[0]} lengths on {rollouts.device}, got {tuple(lens.shape)} on {lens.device}")
+    rollouts, lens = rollouts.contiguous(), lens.contiguous()
+    nxt, rs = automaton.next.to(rollouts.device).contiguous(), automaton.resync.to(rollouts.device).contiguous()
+    if nxt.dtype != torch.int16 or rs.dtype != torch.int16 or nxt.dim() != 2 or rs.shape != (nxt.shape[1],):
+        raise TypeError("grammar_scan: the automaton's tables must be int16 [states][V] and [V]")
+    R = rollouts.shape[0]
+    viol = torch.empty(R, dtype=torch.int32, device=rollouts.device)
+    comp = torch.empty(R, dtype=torch.int32, device=rollouts.device)
+    if R:
+        _lib.check(_lib.lib().acai_grammar_scan(rollouts.data_ptr(), rollouts.shape[1], lens.data_ptr(), R, nxt.data_ptr(), rs.data_ptr(),
+                                                nxt.shape[0], automaton.start, nxt.shape[1], automaton.eos_idx, viol.data_ptr(), comp.data_ptr(),
+                                                _st(rollouts)), "acai_grammar_scan")
+    return viol, comp != 0
+
+
 for _name, _fn in list(globals().items()):
     if callable(_fn) and not _name.startswith("_") and getattr(_fn, "__module__", None) == __name__ and not isinstance(_fn, type):
         globals()[_name] = _on_operand_device(_fn)

@@ -9,8 +9,10 @@ Same names and argument orders as the reference, so code written for omr_grpo_tr
   * rewards: grpo_update takes a `reward_fn` that returns the (B, G) raw rewards.  The tensor-only reward helpers are here, and so is a
     reward that runs from the package alone: the TOKEN-level edit cost (calc_token_edit_costs: Levenshtein distance over LMX tokens, one HIP
     launch on the rollouts where they lie, acai_edit_distance) stands in for the reference's tree edit cost in token_reward_rollouts /
-    make_token_reward_fn.  Still not ported: calc_edit_costs itself (TEDn on MusicXML trees through olimpic_app) and the well-formedness
-    counts, which need the LMX delinearizer;
+    make_token_reward_fn.  Not ported: calc_edit_costs itself (TEDn on MusicXML trees through olimpic_app) and the delinearizer's
+    well-formedness counts.  With a token automaton (grammar.TokenAutomaton, `grammar=`) the well-formedness term is computed from the
+    automaton instead - violations and "ended with an allowed <eos>" from one scan launch over the rollouts (acai_grammar_scan) - and the
+    rollouts themselves can be constrained by it (grpo_update(grammar=), validation_loop(grammar=));
   * rollouts may go through continuously refilled decode rows instead of one static batch (grpo_update(rollout_slots=...), and always in
     validation_loop): the same draws per rollout, no B * G <= max batch size limit, and a rollout that never draws <eos> does not hold the
     finished ones' rows to max_actions."""
@@ -181,14 +183,29 @@ def calc_token_edit_costs(rollouts, rollout_mask, target_lmx_seqs, pad_idx, grou
     return ops.edit_distance(rollouts, rollout_mask, target_lmx_seqs, target_lens, group=group_size).float()
 
 
-def token_reward_rollouts(reward_config: RewardConfig, rollouts, rollout_mask, target_lmx_seqs, num_groups, group_size, pad_idx):
+def calc_grammar_wellformedness(rollouts, rollout_mask, grammar, gamma=3.0, alpha_w=0.2):
+    """calc_wellformedness from a token automaton: minor errors = the rollout's transitions the automaton forbids, catastrophic = the rollout
+    did not end with an allowed <eos> (ops.grammar_scan: one launch on the rollouts where they lie).  This stands in for the delinearizer's
+    verdict as the token edit cost stands in for TEDn: it says what the automaton knows - for one learned from a corpus, whether the rollout's
+    n-grams occur in that corpus - not whether the LMX delinearizes."""
+    violations, complete = ops.grammar_scan(rollouts, rollout_mask, grammar)
+    return calc_wellformedness(~complete, violations.float(), gamma=gamma, alpha_w=alpha_w)
+
+
+def token_reward_rollouts(reward_config: RewardConfig, rollouts, rollout_mask, target_lmx_seqs, num_groups, group_size, pad_idx, grammar=None):
     """reward_rollouts (omr_grpo_train.py:227-237) with the token-level edit cost in the place of the tree edit cost:
-    tedn_scores = calc_tedn_scores(calc_token_edit_costs(...), alpha_tedn).  wellformedness_scores is a zeros tensor: the catastrophic / minor
-    error counts come from delinearizing the LMX string, and the delinearizer is not part of this package.  The other three components are the
-    reference's.  target_lmx_seqs: the expanded (B*G, L) targets.  Returns (raw_group_rewards (B, G), RewardComponents)."""
+    tedn_scores = calc_tedn_scores(calc_token_edit_costs(...), alpha_tedn).  Without a grammar wellformedness_scores is a zeros tensor: the
+    catastrophic / minor error counts come from delinearizing the LMX string, and the delinearizer is not part of this package.  With
+    grammar (a grammar.TokenAutomaton) it is calc_grammar_wellformedness(rollouts, rollout_mask, grammar, gamma, alpha_well_formed): the
+    automaton's verdict in the delinearizer's place.  The other three components are the reference's.  target_lmx_seqs: the expanded
+    (B*G, L) targets.  Returns (raw_group_rewards (B, G), RewardComponents)."""
     token_edit_costs = calc_token_edit_costs(rollouts, rollout_mask, target_lmx_seqs, pad_idx)
     tedn_scores = calc_tedn_scores(token_edit_costs, alpha_t=reward_config.alpha_tedn)
-    wellformedness_scores = torch.zeros_like(tedn_scores)
+    if grammar is None:
+        wellformedness_scores = torch.zeros_like(tedn_scores)
+    else:
+        wellformedness_scores = calc_grammar_wellformedness(rollouts, rollout_mask, grammar, gamma=reward_config.gamma,
+                                                            alpha_w=reward_config.alpha_well_formed).to(tedn_scores.device)
     f1_scores = calc_token_f1(rollouts, target_lmx_seqs, pad_idx)
     repeat_penalty = calc_repeat_penalty(rollouts, pad_idx)
     len_penalty = calc_len_penalty(rollout_mask, target_lmx_seqs, pad_idx, delta=reward_config.delta, tau=reward_config.tau)
@@ -197,11 +214,13 @@ def token_reward_rollouts(reward_config: RewardConfig, rollouts, rollout_mask, t
     return raw_group_rewards, reward_components
 
 
-def make_token_reward_fn(reward_config: RewardConfig, pad_idx):
-    """A `reward_fn` for grpo_update built from token_reward_rollouts: the group shape is read off the batch and the expanded targets."""
+def make_token_reward_fn(reward_config: RewardConfig, pad_idx, grammar=None):
+    """A `reward_fn` for grpo_update built from token_reward_rollouts: the group shape is read off the batch and the expanded targets.
+    grammar: the token automaton of the well-formedness term (token_reward_rollouts); None leaves that term at zero."""
     def reward_fn(rollouts, rollout_mask, target_lmx_seqs, batch):
         num_groups = len(batch)
-        return token_reward_rollouts(reward_config, rollouts, rollout_mask, target_lmx_seqs, num_groups, rollouts.shape[0] // num_groups, pad_idx)
+        return token_reward_rollouts(reward_config, rollouts, rollout_mask, target_lmx_seqs, num_groups, rollouts.shape[0] // num_groups, pad_idx,
+                                     grammar=grammar)
     return reward_fn
 
 
@@ -245,7 +264,7 @@ def calc_teacher_forced_ce_loss(policy_theta, unexpanded_img_latent, unexpanded_
 
 
 # ---- the update step (omr_grpo_train.py:308-376) ---------------------------------------------------------------------------------------
-def _rollouts_grouped(old_policy, img_latent, latent_attention_mask, group_size, rollout_config, uniforms):
+def _rollouts_grouped(old_policy, img_latent, latent_attention_mask, group_size, rollout_config, uniforms, grammar=None):
     """cached_forward_rollout_policy(expand_img_latent_for_rollout(...), group_size=G) without making the G copies: the cached decode reads
     one memory per image already (group_size), so the per-image latent goes in as it is."""
     from .. import engine as EG
@@ -253,23 +272,29 @@ def _rollouts_grouped(old_policy, img_latent, latent_attention_mask, group_size,
     mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
     blocks.prepare_caches_packed(mem32, None, lens, group_size=group_size)
     eng = blocks.engine(old_policy.decoder.pos_embedding.device)
-    seqs, lps, _ = eng.sample(rollout_config.max_actions, rollout_config.top_k, rollout_config.temperature, uniforms=uniforms)
+    seqs, lps, _ = eng.sample(rollout_config.max_actions, rollout_config.top_k, rollout_config.temperature, uniforms=uniforms, grammar=grammar)
     return old_policy.mask_and_clip_seqs(seqs.clone(), lps.clone())
 
 
-def _rollouts_continuous(old_policy, img_latent, latent_attention_mask, group_size, rollout_config, uniforms, slots):
+def _rollouts_continuous(old_policy, img_latent, latent_attention_mask, group_size, rollout_config, uniforms, slots, grammar=None):
     """The same rollouts through `slots` continuously refilled decode rows (GRPOViTOMR.cached_continuous_rollout_policy): B * G may exceed
     the cache's max batch size, at the price of one cross K/V projection per rollout instead of one per image."""
+    if grammar is not None:
+        return old_policy.cached_constrained_continuous_rollout_policy(img_latent, latent_attention_mask, grammar, rollout_config.max_actions,
+                                                                       rollout_config.top_k, rollout_config.temperature, slots=slots,
+                                                                       group_size=group_size, uniforms=uniforms)
     return old_policy.cached_continuous_rollout_policy(img_latent, latent_attention_mask, rollout_config.max_actions, rollout_config.top_k,
                                                        rollout_config.temperature, slots=slots, group_size=group_size, uniforms=uniforms)
 
 
 def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOConfig, ce_loss_fn, device, logger=None, counter=None, *, reward_fn,
-                uniforms=None, rollout_slots=None):
+                uniforms=None, rollout_slots=None, grammar=None):
     """One GRPO minibatch update.  batch: list of (image, target_lmx_seq, target_musicxml_str).  reward_fn(rollouts, rollout_mask, target_lmx_seqs,
     batch) -> (B, G) raw rewards, or (rewards, RewardComponents).  uniforms (R, max_actions): the rollout draws (cached_forward_rollout_policy).
     rollout_slots: None = one static batch of B * G rollout rows (B * G <= the cache's max batch size); an integer = that many decode rows
-    refilled as rollouts finish, for any B * G.  Returns (avg loss over update epochs, avg CE loss, avg raw reward, avg reward components
+    refilled as rollouts finish, for any B * G.  grammar: a grammar.TokenAutomaton that constrains the rollouts
+    (cached_forward_rollout_policy(grammar=)): old_policy_log_probs are then the constrained policy's, while the theta logits of the ratio
+    stay unconstrained - pass the same automaton to make_token_reward_fn to reward what it checks.  Returns (avg loss over update epochs, avg CE loss, avg raw reward, avg reward components
     or None)."""
     rollout_config, reward_config, loss_config, update_config = grpo_config.get_configs()
     dev_type = torch.device(device).type
@@ -285,10 +310,10 @@ def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOCon
         unexpanded_img_latent = old_policy.transition_head(unexpanded_img_latent)
         if rollout_slots is None:
             rollouts, old_policy_log_probs, rollout_mask = _rollouts_grouped(old_policy, unexpanded_img_latent, unexpanded_latent_attention_mask,
-                                                                             group_size, rollout_config, uniforms)
+                                                                             group_size, rollout_config, uniforms, grammar)
         else:
             rollouts, old_policy_log_probs, rollout_mask = _rollouts_continuous(old_policy, unexpanded_img_latent, unexpanded_latent_attention_mask,
-                                                                                group_size, rollout_config, uniforms, int(rollout_slots))
+                                                                                group_size, rollout_config, uniforms, int(rollout_slots), grammar)
 
     target_lmx_seqs = expand_target_lmx_seqs(unexpanded_target_lmx_seqs, group_size, pad_idx, device)
     got = reward_fn(rollouts, rollout_mask, target_lmx_seqs, batch)
@@ -343,7 +368,7 @@ def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOCon
 
 # ---- validation (omr_grpo_train.py:456-492) -----------------------------------------------------------------------------------------------
 def validation_loop(dataloader, policy_theta, reward_config, rollout_config, ce_loss_fn, pad_idx, device, *, reward_fn=None, slots=None,
-                    uniforms_fn=None, autocast_dtype=torch.bfloat16):
+                    uniforms_fn=None, autocast_dtype=torch.bfloat16, grammar=None):
     """Mini or full validation, depending on the dataloader: one sampled rollout per image (group size 1) at rollout_config's max_actions /
     top_k / temperature, scored by reward_fn, and the teacher-forced CE loss of each batch.  Returns (mean raw reward, mean RewardComponents,
     mean CE loss), each a mean over batches of per-batch means, as the reference computes them.
@@ -353,9 +378,10 @@ def validation_loop(dataloader, policy_theta, reward_config, rollout_config, ce_
     batch size): a dataloader batch may be larger than the cache, and a rollout that never draws <eos> does not hold the others' rows to
     max_actions.  reward_fn: as grpo_update's (default make_token_reward_fn(reward_config, pad_idx): the token-level edit cost in the place
     of the reference's tree edit cost).  uniforms_fn(batch_index, R, max_actions) -> (R, max_actions) uniforms fixes the draws (default:
-    torch's generator).  autocast_dtype: the reference validates under bf16 autocast; None runs without autocast."""
+    torch's generator).  autocast_dtype: the reference validates under bf16 autocast; None runs without autocast.  grammar: a
+    grammar.TokenAutomaton that constrains the rollouts and, with the default reward_fn, scores their well-formedness."""
     if reward_fn is None:
-        reward_fn = make_token_reward_fn(reward_config, pad_idx)
+        reward_fn = make_token_reward_fn(reward_config, pad_idx, grammar=grammar)
     dev_type = torch.device(device).type
     num_batches = len(dataloader)
     validation_reward = 0
@@ -370,9 +396,14 @@ def validation_loop(dataloader, policy_theta, reward_config, rollout_config, ce_
             img_latent, latent_attention_mask = policy_theta.encoder(imgs)
             img_latent = policy_theta.transition_head(img_latent)
             uniforms = uniforms_fn(i, len(imgs), rollout_config.max_actions) if uniforms_fn is not None else None
-            rollouts, _, rollout_mask = policy_theta.cached_continuous_rollout_policy(
-                img_latent, latent_attention_mask, rollout_config.max_actions, rollout_config.top_k, rollout_config.temperature, slots=slots,
-                group_size=group_size, uniforms=uniforms)
+            if grammar is None:
+                rollouts, _, rollout_mask = policy_theta.cached_continuous_rollout_policy(
+                    img_latent, latent_attention_mask, rollout_config.max_actions, rollout_config.top_k, rollout_config.temperature, slots=slots,
+                    group_size=group_size, uniforms=uniforms)
+            else:
+                rollouts, _, rollout_mask = policy_theta.cached_constrained_continuous_rollout_policy(
+                    img_latent, latent_attention_mask, grammar, rollout_config.max_actions, rollout_config.top_k, rollout_config.temperature,
+                    slots=slots, group_size=group_size, uniforms=uniforms)
             padded_targets = expand_target_lmx_seqs(target_lmx_seqs, group_size, pad_idx, device)
             got = reward_fn(rollouts, rollout_mask, padded_targets, batch)
             raw_rewards, reward_components = got if isinstance(got, tuple) else (got, None)

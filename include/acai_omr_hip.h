@@ -474,6 +474,50 @@ int acai_decode_spec_prompt_arm(const AcaiDecoder *d, const AcaiSpec *sp, const 
  * from sp's usual source.  What is written equals acai_decode_prompt_step run token by token.  Same checks as acai_decode_spec_step and
  * acai_decode_spec_prompt_arm. */
 int acai_decode_spec_prompt_step(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *prompt, void *stream);
+/* Grammar-constrained decoding (an extension: the reference knows no grammar).  A token automaton is a table next[state][token]: an entry
+ * >= 0 is the state after emitting that token, an entry < 0 forbids the token in that state.  All arrays are device memory:
+ *   next:   [states][V] int16, every non-negative entry < states;
+ *   resync: [V] int16 in [0, states): the state taken after a token the table did not allow (here: out of a state that allows none);
+ *   state:  [rows] int32, the state of every decode row; the caller arms it to `start` before the first step (slot mode: when it arms the
+ *           slot), ordered before the step; the steps advance it.  A value outside [0, states) is clamped where it is read.
+ * There is no accept set: a row may end in state s exactly when next[s][<eos>] >= 0. */
+typedef struct {
+    const int16_t *next;
+    const int16_t *resync;
+    int32_t *state;
+    int32_t states;    /* 1 .. 32767 */
+    int32_t start;     /* the state after <bos>, in [0, states); also taken after a token outside [0, V) */
+    int32_t rows;      /* entries of state, >= dec->B */
+    int32_t pad_;
+} AcaiGrammar;
+/* One CONSTRAINED greedy step: acai_decode_step's layers and unembed, then one selection launch in which row b reads its state
+ * s = clamp(state[b], 0, states - 1) and the table row next[s][:]; a token i with next[s][i] < 0 counts as a -inf logit in the arg-max (first
+ * index on ties) and in the sum of exponentials, so logprobs[b][t] is the log-softmax over the ALLOWED tokens (the policy actually run) and
+ * state[b] = next[s][token].  If s allows no token the row is unconstrained at this step and state[b] = resync[token] (a defensive path).
+ * seqs, finished[], finished[B], step[], the bf16 rounding of the log-prob and the next input x are acai_decode_step's; a finished row goes on
+ * emitting (masked) tokens as it does there.  With a table that allows every token the step is acai_decode_step bit for bit.  Same checks
+ * and x contract as acai_decode_step, plus non-null next / resync / state, 1 <= states <= 32767, 0 <= start < states, rows >= B, V <= 512.
+ * Enqueues kernels only (capturable). */
+int acai_decode_grammar_step(const AcaiDecoder *d, const AcaiGrammar *g, void *stream);
+/* One CONSTRAINED sampling step: acai_decode_sample_step whose top-k rounds, draw and log_softmax(kept) run over the allowed tokens of the
+ * row's state only; with fewer than top_k allowed tokens the kept set is the allowed set (one allowed token is drawn with log-prob 0 whatever
+ * u is).  State handling and checks as acai_decode_grammar_step, plus acai_decode_sample_step's. */
+int acai_decode_grammar_sample_step(const AcaiDecoder *d, const AcaiGrammar *g, const float *uniforms, int top_k, float temperature, void *stream);
+/* The SLOT-MODE forms: acai_decode_slot_step / acai_decode_slot_sample_step with the constrained token choice.  A finished or idle row
+ * reads and writes neither its tokens nor its state; the caller sets state[b] = start when it arms slot b (before acai_decode_slot_arm's
+ * step).  Checks: the slot step's and acai_decode_grammar_step's. */
+int acai_decode_slot_grammar_step(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *g, void *stream);
+int acai_decode_slot_grammar_sample_step(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *g, const float *uniforms, int ld_uniforms,
+                                         const int32_t *urow, int top_k, float temperature, void *stream);
+/* Walks R finished token rows through a token automaton (grammar.hip): the inputs of the GRPO well-formedness reward.  tokens [R][ld] int64
+ * (row stride = ld), lens [R] int32, read ON THE DEVICE and clamped to [0, ld]; next [states][V] / resync [V] int16 as in AcaiGrammar.  Row r
+ * starts in s = start (index 0 is <bos> and is not checked); for p = 1 .. len - 1 with k = tokens[r][p]: k outside [0, V) is one violation
+ * and s = start; next[s][k] < 0 is one violation and s = resync[k]; otherwise s = next[s][k].  violations[r] (int32) receives the count,
+ * complete[r] (int32) is 1 iff len >= 2, the last token is `eos` and its transition was allowed.  Rows run in parallel, each is a serial
+ * chain; the table is staged in LDS when states * V * 2 bytes fit 156 KB (a bigram automaton at V = 227 is 103 KB) and read from global
+ * memory otherwise.  One launch, no host synchronisation, no allocation (capturable).  1 <= states <= 32767, 0 <= start < states, V >= 1. */
+int acai_grammar_scan(const int64_t *tokens, int ld, const int32_t *lens, int R, const int16_t *next, const int16_t *resync, int states, int start,
+                      int V, int eos, int32_t *violations, int32_t *complete, void *stream);
 /* The same without the token bookkeeping: logits for caller-supplied tokens/time_step (OMRDecoder.cached_generate). */
 int acai_decode_logits(const AcaiDecoder *dec, const int64_t *tokens, int time_step, void *stream);
 
