@@ -69,6 +69,49 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
             return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, prefix=prefix, grammar=grammar)
 
 
+def aligned_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, layers=None, head_weights=None, return_maps=False, **decode_kwargs):
+    """inference() plus token-to-image alignment (an extension) -> (seqs, log_probs, seq_mask, TokenAlignment).  The images are encoded once;
+    the decode is inference()'s own (decode_kwargs - beam_width, length_penalty, speculative, ngram, prefix, grammar - are passed on, and
+    its errors stay its errors); then one teacher-forced pass over the produced tokens on the same packed memory, with the decode's
+    positions, writes each token's cross-attention map over the image's patches and reduces it to a location
+    (ViTOMR.locate_tokens; the grids come from the image sizes).  layers / head_weights select and weight the decoder layers and heads
+    that are averaged (OMRDecoder.cross_attention_maps_packed; default all, uniform): which of them align best on trained checkpoints has
+    not been measured.  return_maps keeps the per-token maps in the result."""
+    unknown = set(decode_kwargs) - {"beam_width", "length_penalty", "speculative", "ngram", "prefix", "grammar"}
+    if unknown:
+        raise TypeError(f"aligned_inference() got unexpected decode arguments {sorted(unknown)}")
+    beam_width, speculative = decode_kwargs.get("beam_width", 1), decode_kwargs.get("speculative", 0)
+    prefix, grammar = decode_kwargs.get("prefix"), decode_kwargs.get("grammar")
+    if grammar is not None:
+        for other, on in (("beam search (beam_width > 1)", beam_width != 1), ("speculative decoding (speculative)", bool(speculative)),
+                          ("prompted decoding (prefix)", prefix is not None)):
+            if on:
+                raise ValueError(f"grammar (constrained decoding) cannot be combined with {other}: out of scope here")
+    if speculative and beam_width != 1:
+        raise ValueError("speculative decoding cannot be combined with beam search (beam_width > 1)")
+    if prefix is not None and beam_width != 1:
+        raise ValueError("prefix (prompted decoding) cannot be combined with beam search (beam_width > 1): out of scope here")
+    vitomr.decoder._alignment_selection(layers, head_weights)
+    vitomr.eval()
+    with torch.no_grad():
+        dims = list(img.dims) if hasattr(img, "dims") else [vitomr.encoder._grid(t) for t in img]
+        lat32, _, lens = _encode(vitomr, img)
+        with autocast(device_type=device, dtype=torch.bfloat16):
+            mem = vitomr.transition_head.forward_packed(lat32)
+            bf = mem.dtype == torch.bfloat16
+            mem32, memb = (None, mem) if bf else (mem, None)
+            if speculative:
+                seqs, lps, mask = vitomr._speculative_packed(mem32, memb, lens, max_inference_len, speculative, decode_kwargs.get("ngram", 3),
+                                                             prefix=prefix)
+            elif beam_width != 1:
+                seqs, lps, mask = vitomr._beam_packed(mem32, memb, lens, beam_width, max_inference_len, decode_kwargs.get("length_penalty", 1.0))
+            else:
+                seqs, lps, mask = vitomr._greedy_packed(mem32, memb, lens, max_inference_len, prefix=prefix, grammar=grammar)
+            grids = vitomr._check_grids(dims, lens)
+            align = vitomr._align_packed(mem32, memb, lens, seqs, mask, layers, head_weights, True, grids, vitomr.encoder.patch_size, return_maps)
+    return seqs, lps, mask, align
+
+
 def _encode_chunks(vitomr, imgs, device):
     """Encoder (fp32, outside autocast) and transition head (inside autocast) over chunks of at most max_batch_size images; the packed
     memories of all chunks, concatenated, and their lengths."""

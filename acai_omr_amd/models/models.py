@@ -361,26 +361,34 @@ class OMRDecoder(nn.Module):
                           memory_cache_dtype=memory_cache_dtype)
 
     # ---- teacher-forced / uncached batch paths -----------------------------------------------------------------------------
-    def forward_packed(self, inputs, lens_t, mem32, memb, lens_s, token_idxs_input=True, prec=None):
-        """Teacher-forced decoder on packed streams.  inputs: packed token ids (sum T,) int or packed embeddings (sum T, E);
-        positions restart at 0 in every sequence (M:465-466).  Returns packed logits (sum T, V) fp32."""
-        prec = prec or _autocast_prec()
+    def _embed_packed(self, inputs, lens_t, token_idxs_input, position_offset=0):
+        """Token + position embeddings of a packed stream (fp32); positions restart at position_offset in every sequence."""
+        dev = self.pos_embedding.device
+        pos_idx = torch.cat([torch.arange(t, dtype=torch.int32) for t in lens_t])
+        if position_offset:
+            pos_idx = pos_idx + int(position_offset)
+        x32 = ops.gather_rows(self.pos_embedding.detach(), pos_idx.to(dev))
+        if token_idxs_input:
+            return ops.gather_rows(self.vocab_embedding.weight.detach(), inputs.to(device=dev, dtype=torch.int32).contiguous(), add=x32)
+        return x32 + inputs.to(dev).float()
+
+    def _layers_packed(self, x32, lens_t, mem32, memb, lens_s, prec, maps=None):
+        """The decoder layers, final norm and unembed on a packed stream: forward_packed's body, shared with cross_attention_maps_packed.
+        maps (None = plain forward): {"weights": {layer index: [H] fp32 device tensor}, "out", "map_off", "logits"} - in those layers the
+        cross-attention also saves its log-sum-exp and ops.attn_probs_mean adds the layer's weighted head mean to maps["out"]; unless
+        maps["logits"], the pass ends after the last such layer's cross-attention and returns None."""
         bf = prec == "bf16"
         dev, E, H = self.pos_embedding.device, self.hidden_dim, self.num_heads
         wc = _wc(self)
-        pos_idx = torch.cat([torch.arange(t, dtype=torch.int32) for t in lens_t]).to(dev)
-        x32 = ops.gather_rows(self.pos_embedding.detach(), pos_idx)
-        if token_idxs_input:
-            x32 = ops.gather_rows(self.vocab_embedding.weight.detach(), inputs.to(device=dev, dtype=torch.int32).contiguous(), add=x32)
-        else:
-            x32 = x32 + inputs.to(dev).float()
         xb = ops.cast_bf16(x32) if bf else None
         cu_t, cu_s = EG.cu_from_lens(lens_t, dev), EG.cu_from_lens(lens_s, dev)
         mem = memb if bf else mem32
         if mem is None:
             mem = ops.cast_bf16(mem32)
         mt, dh = max(lens_t), E // H
-        for ly in self.decoder_blocks.layers:
+        picked = maps["weights"] if maps is not None else {}
+        lse, first = None, True
+        for i, ly in enumerate(self.decoder_blocks.layers):
             sa, ca = ly.self_attn, ly.multihead_attn
             qkv = EG.linear(x32, xb, sa.in_proj_weight, sa.in_proj_bias, prec, wc)
             a = ops.attn_varlen(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], cu_t, cu_t, H, dh, mt, causal=True)
@@ -389,7 +397,17 @@ class OMRDecoder(nn.Module):
             cdt = torch.bfloat16 if bf else torch.float32
             q = ops.gemm_nt(xb if bf else x32, wc.w(ca.in_proj_weight, prec)[:E], wc.b(ca.in_proj_bias, prec)[:E], out_dtype=cdt, round_bf16=bf)
             kv = ops.gemm_nt(mem, wc.w(ca.in_proj_weight, prec)[E:], wc.b(ca.in_proj_bias, prec)[E:], out_dtype=cdt, round_bf16=bf)
-            a = ops.attn_varlen(q, kv[:, :E], kv[:, E:], cu_t, cu_s, H, dh, mt)
+            if i in picked:
+                if lse is None:
+                    lse = torch.empty(H * q.shape[0], dtype=torch.float32, device=dev)
+                a = ops.attn_varlen(q, kv[:, :E], kv[:, E:], cu_t, cu_s, H, dh, mt, lse=lse)
+                ops.attn_probs_mean(q, kv[:, :E], cu_t, cu_s, H, dh, mt, max(lens_s), lse, picked[i], maps["map_off"], maps["out"],
+                                    accumulate=not first)
+                first = False
+                if i == max(picked) and not maps["logits"]:
+                    return None
+            else:
+                a = ops.attn_varlen(q, kv[:, :E], kv[:, E:], cu_t, cu_s, H, dh, mt)
             y = ops.gemm_nt(a, wc.w(ca.out_proj.weight, prec), wc.b(ca.out_proj.bias, prec), residual=x32, round_bf16=bf)
             x32, xb = ops.layernorm(y, ly.norm2.weight.detach(), ly.norm2.bias.detach(), ly.norm2.eps, want_bf16=bf)
             h = EG.linear(x32, xb, ly.linear1.weight, ly.linear1.bias, prec, wc, gelu=True)
@@ -398,6 +416,93 @@ class OMRDecoder(nn.Module):
         nrm = self.decoder_blocks.norm
         x32, xb = ops.layernorm(x32, nrm.weight.detach(), nrm.bias.detach(), nrm.eps, want_bf16=bf)
         return EG.linear(x32, xb, self.unembed.weight, self.unembed.bias, prec, wc, out_dtype=torch.float32)
+
+    def forward_packed(self, inputs, lens_t, mem32, memb, lens_s, token_idxs_input=True, prec=None):
+        """Teacher-forced decoder on packed streams.  inputs: packed token ids (sum T,) int or packed embeddings (sum T, E);
+        positions restart at 0 in every sequence (M:465-466).  Returns packed logits (sum T, V) fp32."""
+        prec = prec or _autocast_prec()
+        return self._layers_packed(self._embed_packed(inputs, lens_t, token_idxs_input), lens_t, mem32, memb, lens_s, prec)
+
+    def _alignment_selection(self, layers, head_weights):
+        """cross_attention_maps_packed's `layers` and `head_weights`, checked on the host: (sorted layer indices, float64 CPU weights
+        [len(layers), H] in that order, summing to 1 over everything).  ValueError for anything else."""
+        L, H = len(self.decoder_blocks.layers), self.num_heads
+        if layers is None:
+            idx = list(range(L))
+        else:
+            try:
+                raw = [int(i) for i in layers]
+            except (TypeError, ValueError):
+                raise ValueError(f"layers must be an iterable of layer indices, got {layers!r}") from None
+            if not raw:
+                raise ValueError("layers is empty: select at least one decoder layer")
+            idx = []
+            for i in raw:
+                if not -L <= i < L:
+                    raise ValueError(f"layer index {i} is out of range for a decoder of {L} layers")
+                idx.append(i + L if i < 0 else i)
+            if len(set(idx)) != len(idx):
+                raise ValueError(f"layers holds a layer more than once: {raw}")
+        n = len(idx)
+        if head_weights is None:
+            w = torch.full((n, H), 1.0 / (n * H), dtype=torch.float64)
+        else:
+            try:
+                w = torch.as_tensor(head_weights).detach().to(device="cpu", dtype=torch.float64)
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise ValueError(f"head_weights must be a [H] or [len(layers), H] tensor or nested list: {e}") from None
+            if w.dim() == 1 and w.shape[0] == H:
+                w = w.unsqueeze(0).expand(n, H)
+            elif w.dim() != 2 or tuple(w.shape) != (n, H):
+                raise ValueError(f"head_weights must have shape [{H}] or [{n}, {H}], got {tuple(w.shape)}")
+            if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                raise ValueError("head_weights must be finite and non-negative")
+            if not float(w.sum()) > 0:
+                raise ValueError("head_weights sum to zero")
+            w = w / w.sum()
+        order = sorted(range(n), key=lambda j: idx[j])
+        return [idx[j] for j in order], w[order].contiguous()
+
+    def cross_attention_maps_packed(self, tokens, lens_t, mem32, memb, lens_s, layers=None, head_weights=None, position_offset=0, prec=None,
+                                    return_logits=False):
+        """Token-to-image alignment (an extension): a teacher-forced pass over packed token ids `tokens` (sum T,) that also writes out, per
+        token, the cross-attention distribution over the image's patches - the weighted mean over the selected layers and heads.
+        Returns a list of (T_i, S_i) fp32 maps (views of one buffer), and with return_logits (maps, packed logits (sum T, V) fp32).
+
+        position_offset adds to every position index.  The KV-cached decode embeds the token at output index t-1 at position t (quirk Q1),
+        so with position_offset=1 row j of a decoded sequence's map is the attention the decode itself ran when it chose index j+1; 0 gives
+        the positions of forward_packed.  layers: iterable of layer indices, negative ones counted from the end, default all (ValueError
+        when empty, out of range or repeated).  head_weights: a [H] or [len(layers), H] tensor or nested list, in the order `layers` lists
+        them, non-negative with a positive sum, normalised so that all weights sum to 1; default uniform (ValueError for a wrong shape,
+        negative or non-finite entries, a zero sum).  Each map row sums to 1 up to rounding.  Without return_logits the pass ends after the
+        last selected layer's cross-attention.  Which layers and heads align best on trained checkpoints has not been measured: the
+        uniform default is a neutral choice, not a tuned one."""
+        out, offs, _, logits = self._cross_attention_maps_flat(tokens, lens_t, mem32, memb, lens_s, layers, head_weights, position_offset, prec,
+                                                               return_logits)
+        views = [out[o:o + int(t) * int(s)].view(int(t), int(s)) for o, t, s in zip(offs, lens_t, lens_s)]
+        return (views, logits) if return_logits else views
+
+    def _cross_attention_maps_flat(self, tokens, lens_t, mem32, memb, lens_s, layers, head_weights, position_offset, prec, return_logits):
+        """cross_attention_maps_packed's work: (flat fp32 map buffer, the images' element offsets as a list and as an int64 device tensor,
+        logits or None)."""
+        sel, w = self._alignment_selection(layers, head_weights)
+        lens_t, lens_s = [int(t) for t in lens_t], [int(s) for s in lens_s]
+        if len(lens_t) != len(lens_s) or not lens_t or min(lens_t) < 1 or min(lens_s) < 1:
+            raise ValueError(f"lens_t {lens_t} and lens_s {lens_s} must be equally many positive lengths")
+        position_offset = int(position_offset)
+        if position_offset < 0 or max(lens_t) + position_offset > self.max_lmx_seq_len:
+            raise ValueError(f"positions {position_offset} .. {max(lens_t) + position_offset - 1} lie outside the {self.max_lmx_seq_len} learned ones")
+        if int(tokens.numel()) != sum(lens_t):
+            raise ValueError(f"tokens holds {int(tokens.numel())} ids for lens_t summing to {sum(lens_t)}")
+        prec = prec or _autocast_prec()
+        dev = self.pos_embedding.device
+        offs, total = ops.attn_map_layout(lens_t, lens_s)
+        out = torch.empty(total, dtype=torch.float32, device=dev)
+        wdev = ops.h2d(w.to(torch.float32), dev)
+        map_off = ops.h2d(torch.tensor(offs, dtype=torch.int64), dev)
+        maps = {"weights": {l: wdev[j] for j, l in enumerate(sel)}, "out": out, "map_off": map_off, "logits": bool(return_logits)}
+        logits = self._layers_packed(self._embed_packed(tokens.reshape(-1), lens_t, True, position_offset), lens_t, mem32, memb, lens_s, prec, maps)
+        return out, offs, map_off, logits
 
     def forward(self, input_seqs, img_latent, lmx_attention_mask, latent_attention_mask, token_idxs_input=True, checkpoint_grads=False,
                 memory_group_size=None):
@@ -499,6 +604,22 @@ def _continuous_caps(max_len, n):
     return caps
 
 
+class TokenAlignment:
+    """Where on the page each output token came from (ViTOMR.locate_tokens; an extension).  For a batch of B sequences clipped to T' indices:
+    patch (B, T') int64 - the arg-max patch of the token's attention map, row-major in the image's patch grid, -1 where there is no map
+    (index 0, <bos>, and positions after the row's end); center_px / spread_px (B, T', 2) fp32 - centroid and standard deviation of the map
+    as (x, y) in pixels of the input tensor (patch units x patch_size), NaN where there is no map; peak (B, T') fp32 - the map's largest
+    probability, NaN where there is none; grids - the images' (h_p, w_p); maps - the list of (L_i - 1, S_i) maps, or None."""
+
+    __slots__ = ("patch", "center_px", "spread_px", "peak", "grids", "maps")
+
+    def __init__(self, patch, center_px, spread_px, peak, grids, maps=None):
+        self.patch, self.center_px, self.spread_px, self.peak, self.grids, self.maps = patch, center_px, spread_px, peak, grids, maps
+
+    def __repr__(self):
+        return f"TokenAlignment(patch={tuple(self.patch.shape)}, grids={self.grids}, maps={'yes' if self.maps is not None else None})"
+
+
 class ViTOMR(nn.Module):
     def __init__(self, encoder, transition_head, decoder):
         super().__init__()
@@ -518,6 +639,109 @@ class ViTOMR(nn.Module):
         seq_log_probs = seq_log_probs.masked_fill(~seq_mask, 0.0)
         n = int(seq_mask.sum(dim=-1).max())
         return seqs[:, :n], seq_log_probs[:, :n], seq_mask[:, :n]
+
+    # ---- token-to-image alignment (an extension) --------------------------------------------------------------------------
+    def _alignment_lengths(self, seqs, seq_mask):
+        """L_i of cross_attention_maps: tokens of row i up to and including its first <eos>, or up to the first masked position."""
+        if seqs.dim() != 2 or seqs.dtype.is_floating_point:
+            raise ValueError(f"seqs must be a (B, T) integer tensor, got shape {tuple(seqs.shape)} dtype {seqs.dtype}")
+        keep = self.create_inference_mask(seqs)
+        if seq_mask is not None:
+            if seq_mask.shape != seqs.shape:
+                raise ValueError(f"seq_mask {tuple(seq_mask.shape)} does not match seqs {tuple(seqs.shape)}")
+            keep = keep & (seq_mask.to(seqs.device).bool().int().cumprod(dim=-1) > 0)
+        return [int(l) for l in keep.sum(dim=-1).tolist()]
+
+    @staticmethod
+    def _check_grids(grids, lens_s):
+        """locate_tokens' `grids`: one (h_p, w_p) of positive ints per image with h_p * w_p patches (so S_i % w_p == 0).  ValueError."""
+        try:
+            out = [(int(h), int(w)) for h, w in grids]
+        except (TypeError, ValueError):
+            raise ValueError(f"grids must be a list of (h_p, w_p) pairs, one per image, got {grids!r}") from None
+        if len(out) != len(lens_s):
+            raise ValueError(f"grids holds {len(out)} entries for {len(lens_s)} images")
+        for i, ((h, w), s) in enumerate(zip(out, lens_s)):
+            if h < 1 or w < 1:
+                raise ValueError(f"grids[{i}] = {(h, w)}: both sides must be at least 1")
+            if h * w != s:
+                raise ValueError(f"grids[{i}] = {(h, w)} does not cover the image's {s} patches")
+        return out
+
+    def _align_packed(self, mem32, memb, lens_s, seqs, seq_mask, layers, head_weights, as_decoded, grids=None, patch_size=None, return_maps=True):
+        """The alignment pass on packed memories: the maps list of cross_attention_maps, and with grids a TokenAlignment."""
+        dec = self.decoder
+        dec._alignment_selection(layers, head_weights)   # argument errors before any work
+        Ls = self._alignment_lengths(seqs, seq_mask)
+        B, Tp = seqs.shape
+        if len(lens_s) != B:
+            raise ValueError(f"{B} sequences for {len(lens_s)} images")
+        dev = dec.pos_embedding.device
+        rows = [i for i, L in enumerate(Ls) if L >= 2]
+        empty = lambda i: torch.zeros(0, lens_s[i], dtype=torch.float32, device=dev)   # noqa: E731
+        maps = [None] * B
+        patch = torch.full((B, Tp), -1, dtype=torch.int64, device=dev)
+        loc_full = torch.full((B, Tp, 6), float("nan"), dtype=torch.float32, device=dev)
+        if rows:
+            lens_t = [Ls[i] - 1 for i in rows]
+            sub_s = [lens_s[i] for i in rows]
+            if len(rows) < B:   # rows without a map leave the batch: their memory rows are cut out
+                starts = [sum(lens_s[:i]) for i in rows]
+                cut = lambda m: None if m is None else torch.cat([m[o:o + s] for o, s in zip(starts, sub_s)]).contiguous()   # noqa: E731
+                mem32, memb = cut(mem32), cut(memb)
+            tokens = torch.cat([seqs[i, :Ls[i] - 1] for i in rows])
+            out, offs, map_off, _ = dec._cross_attention_maps_flat(tokens, lens_t, mem32, memb, sub_s, layers, head_weights, 1 if as_decoded else 0,
+                                                                   None, False)
+            for i, o, t, s in zip(rows, offs, lens_t, sub_s):
+                maps[i] = out[o:o + t * s].view(t, s)
+            if grids is not None:
+                cu_t, cu_s = EG.cu_from_lens(lens_t, dev), EG.cu_from_lens(sub_s, dev)
+                p, loc = ops.attn_map_locate(out, map_off, cu_t, cu_s, [grids[i][1] for i in rows], max(lens_t), sum(lens_t))
+                bi = torch.cat([torch.full((t,), i, dtype=torch.int64) for i, t in zip(rows, lens_t)]).to(dev)
+                ti = torch.cat([torch.arange(1, t + 1, dtype=torch.int64) for t in lens_t]).to(dev)
+                patch[bi, ti] = p.long()
+                loc_full[bi, ti] = loc
+        maps = [m if m is not None else empty(i) for i, m in enumerate(maps)]
+        if grids is None:
+            return maps
+        P = float(patch_size)
+        return TokenAlignment(patch, loc_full[..., 2:4] * P, loc_full[..., 4:6] * P, loc_full[..., 1].clone(), list(grids), maps if return_maps else None)
+
+    def cross_attention_maps(self, img_latent, latent_attention_mask, seqs, seq_mask=None, layers=None, head_weights=None, as_decoded=True):
+        """Token-to-image alignment (an extension): for decoded (or any) sequences `seqs` (B, T) over the memories img_latent (B, S_max, E) /
+        latent_attention_mask, a list of (L_i - 1, S_i) fp32 tensors - row j of image i is the distribution over the image's S_i patches
+        (row-major, Encoder) behind output index j + 1: the mean over the selected decoder layers and heads of the cross-attention
+        probabilities of a teacher-forced pass over input indices 0 .. L_i - 2.  L_i counts row i's tokens up to and including its first
+        <eos>, or up to the first position seq_mask (True = token) masks.  as_decoded (default): positions as the KV-cached decode uses
+        them (OMRDecoder.cross_attention_maps_packed, position_offset=1), so a map is the attention that decode itself ran; False: the
+        teacher-forced positions of OMRDecoder.forward.  layers / head_weights: see cross_attention_maps_packed - which of them align best
+        on trained checkpoints has not been measured.  Runs under the caller's autocast, as forward does, and reads the memory itself, not
+        the KV caches: any cache dtype (FP8 memory cache included) gives the same maps and engine state, graphs and caches stay untouched."""
+        self.decoder._alignment_selection(layers, head_weights)
+        self._alignment_lengths(seqs, seq_mask)
+        mem32, lens_s = EG.unpad_rows(img_latent.to(self.decoder.pos_embedding.device), latent_attention_mask)
+        with torch.no_grad():
+            return self._align_packed(mem32, None, lens_s, seqs, seq_mask, layers, head_weights, as_decoded)
+
+    def locate_tokens(self, img_latent, latent_attention_mask, seqs, seq_mask=None, layers=None, head_weights=None, as_decoded=True, grids=None,
+                      return_maps=False, patch_size=None):
+        """cross_attention_maps reduced to a location per token (an extension) -> TokenAlignment.  grids (required): the images' patch grids
+        [(h_p, w_p), ...] with h_p * w_p = S_i (ValueError otherwise); patch_size: pixels per patch side, default the encoder's.
+        return_maps keeps the maps in the result."""
+        if grids is None:
+            raise ValueError("grids is required: one (h_p, w_p) per image")
+        self.decoder._alignment_selection(layers, head_weights)
+        B, Lm = img_latent.shape[0], img_latent.shape[1]
+        lens_s = [Lm] * B if latent_attention_mask is None else [int(l) for l in (~latent_attention_mask).sum(dim=1).tolist()]
+        grids = self._check_grids(grids, lens_s)
+        if patch_size is None:
+            patch_size = getattr(self.encoder, "patch_size", None)
+        if patch_size is None or float(patch_size) <= 0:
+            raise ValueError("patch_size is needed (the model has no encoder to take it from) and must be positive")
+        self._alignment_lengths(seqs, seq_mask)
+        mem32, lens_s = EG.unpad_rows(img_latent.to(self.decoder.pos_embedding.device), latent_attention_mask)
+        with torch.no_grad():
+            return self._align_packed(mem32, None, lens_s, seqs, seq_mask, layers, head_weights, as_decoded, grids, patch_size, return_maps)
 
     def cached_set_up_inference(self, img_latent, max_len):
         self.decoder.prepare_caches(img_latent)

@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the current stream; every FL
 the HIP library.  Every wrapper checks device / dtype / contiguity on the host before the launch (a
 faulting kernel can take the whole node down) and raises RuntimeError on a non-zero return code.
 """
+import ctypes
 import functools
 
 import math
@@ -340,6 +341,50 @@ def attn_varlen(q, k, v, cu_q, cu_k, H, dh, max_q, causal=False, out=None, lse=N
                                                1 if q_prescaled else 0, _st()),
                "acai_attn_varlen_fwd")
     return out
+
+
+def attn_map_layout(lens_q, lens_k, guard=0):
+    """Element offsets of the dense [T_b][S_b] blocks of an attention map buffer laid out back to back (`guard` spare elements before,
+    between and after them) and the buffer's total length: (offsets list, total)."""
+    offs, o = [], int(guard)
+    for t, s in zip(lens_q, lens_k):
+        offs.append(o)
+        o += int(t) * int(s) + int(guard)
+    return offs, o
+
+
+def attn_probs_mean(q, k, cu_q, cu_k, H, dh, max_q, max_k, lse, head_w, map_off, out, accumulate=False):
+    """Weighted mean over heads of the attention probabilities (acai_attn_probs_mean): q [Mq, >=H*dh], k [Mk, >=H*dh] as attn_varlen takes
+    them, lse [H * Mq] fp32 as attn_varlen(lse=) wrote it for the same q and k, head_w [H] fp32, map_off [B] int64 element offsets into the
+    flat fp32 `out` (attn_map_layout), all on the GPU.  Image b's [T_b][S_b] block is overwritten, or added to with accumulate."""
+    for t, n in ((q, "q"), (k, "k")):
+        _chk(t, n)
+        assert t.dim() == 2 and t.dtype == q.dtype
+    _chk(cu_q, "cu_q", torch.int32), _chk(cu_k, "cu_k", torch.int32), _chk(map_off, "map_off", torch.int64)
+    _chk(lse, "lse", torch.float32), _chk(head_w, "head_w", torch.float32), _chk(out, "out", torch.float32)
+    B = cu_q.numel() - 1
+    assert cu_k.numel() == B + 1 and map_off.numel() == B and map_off.is_contiguous()
+    assert lse.is_contiguous() and lse.numel() == H * q.shape[0], "lse must be the [H][total_q] buffer of the same q"
+    assert head_w.is_contiguous() and head_w.numel() == H and out.is_contiguous() and out.dim() == 1
+    assert q.shape[1] >= H * dh and k.shape[1] >= H * dh
+    _lib.check(_lib.lib().acai_attn_probs_mean(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), cu_q.data_ptr(), cu_k.data_ptr(), B, H, dh,
+                                               int(max_q), int(max_k), _dt(q), lse.data_ptr(), q.shape[0], head_w.data_ptr(), map_off.data_ptr(),
+                                               out.data_ptr(), 1 if accumulate else 0, _st()), "acai_attn_probs_mean")
+    return out
+
+
+def attn_map_locate(maps, map_off, cu_q, cu_k, grid_w, max_q, total_q):
+    """Every row of the maps of attn_probs_mean -> (patch [total_q] int32, loc [total_q, 6] fp32: row sum, peak, centroid x, y, spread x, y
+    in patch units) in one launch (acai_attn_map_locate).  grid_w: the images' patches per row, a host list of ints."""
+    _chk(maps, "maps", torch.float32), _chk(map_off, "map_off", torch.int64), _chk(cu_q, "cu_q", torch.int32), _chk(cu_k, "cu_k", torch.int32)
+    B = cu_q.numel() - 1
+    assert maps.is_contiguous() and maps.dim() == 1 and map_off.numel() == B and cu_k.numel() == B + 1 and len(grid_w) == B
+    gw = (ctypes.c_int32 * B)(*[int(w) for w in grid_w])
+    patch = torch.empty(total_q, dtype=torch.int32, device=maps.device)
+    loc = torch.empty(total_q, 6, dtype=torch.float32, device=maps.device)
+    _lib.check(_lib.lib().acai_attn_map_locate(maps.data_ptr(), map_off.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), gw, B, int(max_q),
+                                               patch.data_ptr(), loc.data_ptr(), _st()), "acai_attn_map_locate")
+    return patch, loc
 
 
 def cross_kv_prefill(mem, w_kv, b_kv, row_seq, row_pos, seq_off, seq_len, k_out, v_out, H, dh, dhp, round_bf16=False):

@@ -185,6 +185,26 @@ int acai_colsum(const void *x, int ld, float *out, int rows, int cols, int dtype
  * shared_row >= 0: the caller guarantees that only that index occurs more than once (the MAE mask token) - the other rows are then
  * updated without atomics; shared_row < 0: every row through fp32 atomics. */
 int acai_scatter_add_rows(const float *src, const int32_t *idx, float *dst, int rows, int dim, int shared_row, void *stream);
+/* Token-to-image alignment (an extension; no reference counterpart): the attention probabilities that acai_attn_varlen_fwd never
+ * materialises, as a weighted mean over heads.  q / k / cu_q / cu_k / H / dh / dtype as there (packed, ragged, any row stride >= H*dh; no
+ * causal mask: cross-attention); max_q / max_k bound the sequence lengths.  lse [H][total_q]: the log2-domain log-sum-exp that
+ * acai_attn_varlen_fwd wrote for the SAME q and k; head_w [H] fp32 and map_off [B] int64 (element offsets into out) live on the device.
+ * Image b owns the dense fp32 block [T_b][S_b] at out + map_off[b], row pitch S_b:
+ *   out[t][s] = (accumulate ? out[t][s] : 0) + sum_h head_w[h] * exp2(q_h[t] . k_h[s] * log2(e) / sqrt(dh) - lse[h][t])
+ * summed in head order (the same bits every run; a head of weight 0 is skipped); nothing outside the blocks is written.  bf16 with dh 32 /
+ * 64 and 16-byte aligned rows runs on the matrix cores, everything else as plain fp32 FMAs (fp32 operands are never rounded to bf16).
+ * Enqueues one kernel: no allocation, no host synchronisation.  Errors: null operand, dh > 64, H < 1, unknown dtype. */
+int acai_attn_probs_mean(const void *q, int ldq, const void *k, int ldk, const int32_t *cu_q, const int32_t *cu_k, int B, int H, int dh,
+                         int max_q, int max_k, int dtype, const float *lse, int total_q, const float *head_w, const int64_t *map_off,
+                         float *out, int accumulate, void *stream);
+/* One launch reduces every row of such maps to a location.  grid_w [B] int32 on the HOST (checked here, carried as kernel arguments;
+ * B <= 512): patches per image row - patch s of image b sits at x = s % grid_w[b], y = s / grid_w[b] (the encoder's row-major order).
+ * patch [total_q] int32: arg-max patch, the lower index on ties.  loc [total_q][6] fp32: row sum m, peak probability, centroid
+ * (sum p (x + 1/2) / m, sum p (y + 1/2) / m), standard deviations around it (sx, sy).  fp32 accumulation in a fixed order; a row with
+ * m == 0 gives centroid and spread 0 and patch 0.  Errors: null operand, grid_w[b] < 1, B > 512. */
+int acai_attn_map_locate(const float *map, const int64_t *map_off, const int32_t *cu_q, const int32_t *cu_k, const int32_t *grid_w,
+                         int B, int max_q, int32_t *patch, float *loc, void *stream);
+
 /* nn.Dropout on a projection output followed by the residual add (torch TransformerEncoderLayer dropout1/dropout2, decoder dropout1-3,
  * transition head M:658): out = residual + keep * x / (1 - p); residual may be NULL (plain dropout, and its own backward on dy).
  * keep mask = counter-based hash of (seed, row, col). */
