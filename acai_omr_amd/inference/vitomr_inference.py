@@ -69,17 +69,11 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
             return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, prefix=prefix, grammar=grammar)
 
 
-def aligned_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, layers=None, head_weights=None, return_maps=False, **decode_kwargs):
-    """inference() plus token-to-image alignment (an extension) -> (seqs, log_probs, seq_mask, TokenAlignment).  The images are encoded once;
-    the decode is inference()'s own (decode_kwargs - beam_width, length_penalty, speculative, ngram, prefix, grammar - are passed on, and
-    its errors stay its errors); then one teacher-forced pass over the produced tokens on the same packed memory, with the decode's
-    positions, writes each token's cross-attention map over the image's patches and reduces it to a location
-    (ViTOMR.locate_tokens; the grids come from the image sizes).  layers / head_weights select and weight the decoder layers and heads
-    that are averaged (OMRDecoder.cross_attention_maps_packed; default all, uniform): which of them align best on trained checkpoints has
-    not been measured.  return_maps keeps the per-token maps in the result."""
+def _check_decode_kwargs(who, decode_kwargs):
+    """The decode arguments that aligned_inference / confident_inference pass on to inference()'s decode, refused as inference() refuses them."""
     unknown = set(decode_kwargs) - {"beam_width", "length_penalty", "speculative", "ngram", "prefix", "grammar"}
     if unknown:
-        raise TypeError(f"aligned_inference() got unexpected decode arguments {sorted(unknown)}")
+        raise TypeError(f"{who}() got unexpected decode arguments {sorted(unknown)}")
     beam_width, speculative = decode_kwargs.get("beam_width", 1), decode_kwargs.get("speculative", 0)
     prefix, grammar = decode_kwargs.get("prefix"), decode_kwargs.get("grammar")
     if grammar is not None:
@@ -91,6 +85,28 @@ def aligned_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, layer
         raise ValueError("speculative decoding cannot be combined with beam search (beam_width > 1)")
     if prefix is not None and beam_width != 1:
         raise ValueError("prefix (prompted decoding) cannot be combined with beam search (beam_width > 1): out of scope here")
+
+
+def _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs):
+    """inference()'s decode of packed memories with checked decode_kwargs -> (seqs, log_probs, seq_mask)."""
+    beam_width, speculative = decode_kwargs.get("beam_width", 1), decode_kwargs.get("speculative", 0)
+    prefix, grammar = decode_kwargs.get("prefix"), decode_kwargs.get("grammar")
+    if speculative:
+        return vitomr._speculative_packed(mem32, memb, lens, max_inference_len, speculative, decode_kwargs.get("ngram", 3), prefix=prefix)
+    if beam_width != 1:
+        return vitomr._beam_packed(mem32, memb, lens, beam_width, max_inference_len, decode_kwargs.get("length_penalty", 1.0))
+    return vitomr._greedy_packed(mem32, memb, lens, max_inference_len, prefix=prefix, grammar=grammar)
+
+
+def aligned_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, layers=None, head_weights=None, return_maps=False, **decode_kwargs):
+    """inference() plus token-to-image alignment (an extension) -> (seqs, log_probs, seq_mask, TokenAlignment).  The images are encoded once;
+    the decode is inference()'s own (decode_kwargs - beam_width, length_penalty, speculative, ngram, prefix, grammar - are passed on, and
+    its errors stay its errors); then one teacher-forced pass over the produced tokens on the same packed memory, with the decode's
+    positions, writes each token's cross-attention map over the image's patches and reduces it to a location
+    (ViTOMR.locate_tokens; the grids come from the image sizes).  layers / head_weights select and weight the decoder layers and heads
+    that are averaged (OMRDecoder.cross_attention_maps_packed; default all, uniform): which of them align best on trained checkpoints has
+    not been measured.  return_maps keeps the per-token maps in the result."""
+    _check_decode_kwargs("aligned_inference", decode_kwargs)
     vitomr.decoder._alignment_selection(layers, head_weights)
     vitomr.eval()
     with torch.no_grad():
@@ -100,16 +116,43 @@ def aligned_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, layer
             mem = vitomr.transition_head.forward_packed(lat32)
             bf = mem.dtype == torch.bfloat16
             mem32, memb = (None, mem) if bf else (mem, None)
-            if speculative:
-                seqs, lps, mask = vitomr._speculative_packed(mem32, memb, lens, max_inference_len, speculative, decode_kwargs.get("ngram", 3),
-                                                             prefix=prefix)
-            elif beam_width != 1:
-                seqs, lps, mask = vitomr._beam_packed(mem32, memb, lens, beam_width, max_inference_len, decode_kwargs.get("length_penalty", 1.0))
-            else:
-                seqs, lps, mask = vitomr._greedy_packed(mem32, memb, lens, max_inference_len, prefix=prefix, grammar=grammar)
+            seqs, lps, mask = _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs)
             grids = vitomr._check_grids(dims, lens)
             align = vitomr._align_packed(mem32, memb, lens, seqs, mask, layers, head_weights, True, grids, vitomr.encoder.patch_size, return_maps)
     return seqs, lps, mask, align
+
+
+def confident_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, top_k=5, temperature=1.0, uncertainty=None, layers=None,
+                        head_weights=None, **decode_kwargs):
+    """inference() plus per-token confidence (an extension) -> (seqs, log_probs, seq_mask, TokenConfidence).  The images are encoded once
+    and the decode is inference()'s own (decode_kwargs as in aligned_inference; its errors stay its errors); then one teacher-forced pass
+    over the produced tokens on the same packed memory, with the decode's positions, scores every token under softmax(logits / temperature):
+    log-probability, entropy, rank and the top_k best tokens (ViTOMR.token_confidence).  uncertainty=None runs the logits-only pass;
+    "entropy", "surprisal" or "error" runs the combined pass instead, which also writes the tokens' cross-attention maps (layers /
+    head_weights as in aligned_inference), and fills TokenConfidence.uncertainty - a heat map per image over its patch grid, the maps summed
+    with that per-token weight (ViTOMR.uncertainty_maps) - and TokenConfidence.alignment, what aligned_inference returns.  After a
+    grammar-constrained decode the scores are the unconstrained model's: rank > 0 marks a token the grammar forced.  How well the scores
+    mark real errors on trained checkpoints has not been measured."""
+    _check_decode_kwargs("confident_inference", decode_kwargs)
+    vitomr._check_confidence_args(top_k, temperature)
+    if uncertainty is not None:
+        if not isinstance(uncertainty, str):
+            raise ValueError(f"uncertainty must be None or a weight name, got {type(uncertainty).__name__}")
+        vitomr._check_uncertainty_weight(uncertainty, None)
+        vitomr.decoder._alignment_selection(layers, head_weights)
+    vitomr.eval()
+    with torch.no_grad():
+        dims = list(img.dims) if hasattr(img, "dims") else [vitomr.encoder._grid(t) for t in img]
+        lat32, _, lens = _encode(vitomr, img)
+        with autocast(device_type=device, dtype=torch.bfloat16):
+            mem = vitomr.transition_head.forward_packed(lat32)
+            bf = mem.dtype == torch.bfloat16
+            mem32, memb = (None, mem) if bf else (mem, None)
+            seqs, lps, mask = _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs)
+            grids = vitomr._check_grids(dims, lens) if uncertainty is not None else None
+            conf = vitomr._confidence_packed(mem32, memb, lens, seqs, mask, top_k, temperature, True, uncertainty, layers, head_weights, grids,
+                                             vitomr.encoder.patch_size, uncertainty is not None)
+    return seqs, lps, mask, conf
 
 
 def _encode_chunks(vitomr, imgs, device):

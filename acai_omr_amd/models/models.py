@@ -12,6 +12,7 @@ Precision: as in the reference, modules compute in fp32 unless called under `tor
 (vitomr_inference.py:81-84 runs the encoder outside and the head + decoder inside autocast); the cached decoder
 follows its cache dtype (vitomr_inference.py:94).
 """
+import math
 import re
 
 import torch
@@ -482,10 +483,8 @@ class OMRDecoder(nn.Module):
         views = [out[o:o + int(t) * int(s)].view(int(t), int(s)) for o, t, s in zip(offs, lens_t, lens_s)]
         return (views, logits) if return_logits else views
 
-    def _cross_attention_maps_flat(self, tokens, lens_t, mem32, memb, lens_s, layers, head_weights, position_offset, prec, return_logits):
-        """cross_attention_maps_packed's work: (flat fp32 map buffer, the images' element offsets as a list and as an int64 device tensor,
-        logits or None)."""
-        sel, w = self._alignment_selection(layers, head_weights)
+    def _check_pass_lengths(self, tokens, lens_t, lens_s, position_offset):
+        """The lengths and positions of a teacher-forced pass over packed token ids, checked on the host (ValueError) and as ints."""
         lens_t, lens_s = [int(t) for t in lens_t], [int(s) for s in lens_s]
         if len(lens_t) != len(lens_s) or not lens_t or min(lens_t) < 1 or min(lens_s) < 1:
             raise ValueError(f"lens_t {lens_t} and lens_s {lens_s} must be equally many positive lengths")
@@ -494,6 +493,21 @@ class OMRDecoder(nn.Module):
             raise ValueError(f"positions {position_offset} .. {max(lens_t) + position_offset - 1} lie outside the {self.max_lmx_seq_len} learned ones")
         if int(tokens.numel()) != sum(lens_t):
             raise ValueError(f"tokens holds {int(tokens.numel())} ids for lens_t summing to {sum(lens_t)}")
+        return lens_t, lens_s, position_offset
+
+    def logits_packed(self, tokens, lens_t, mem32, memb, lens_s, position_offset=0, prec=None):
+        """forward_packed over packed token ids whose positions start at position_offset: with 1 the KV-cached decode's positions (quirk Q1,
+        cross_attention_maps_packed), so row j of a decoded sequence holds the logits the decode chose index j + 1 from.  All layers, no
+        maps.  Returns packed logits (sum T, V) fp32."""
+        lens_t, lens_s, position_offset = self._check_pass_lengths(tokens, lens_t, lens_s, position_offset)
+        prec = prec or _autocast_prec()
+        return self._layers_packed(self._embed_packed(tokens.reshape(-1), lens_t, True, position_offset), lens_t, mem32, memb, lens_s, prec)
+
+    def _cross_attention_maps_flat(self, tokens, lens_t, mem32, memb, lens_s, layers, head_weights, position_offset, prec, return_logits):
+        """cross_attention_maps_packed's work: (flat fp32 map buffer, the images' element offsets as a list and as an int64 device tensor,
+        logits or None)."""
+        sel, w = self._alignment_selection(layers, head_weights)
+        lens_t, lens_s, position_offset = self._check_pass_lengths(tokens, lens_t, lens_s, position_offset)
         prec = prec or _autocast_prec()
         dev = self.pos_embedding.device
         offs, total = ops.attn_map_layout(lens_t, lens_s)
@@ -620,6 +634,45 @@ class TokenAlignment:
         return f"TokenAlignment(patch={tuple(self.patch.shape)}, grids={self.grids}, maps={'yes' if self.maps is not None else None})"
 
 
+class TokenConfidence:
+    """How sure the model was about each output token, and what else it could have been (ViTOMR.token_confidence / uncertainty_maps; an
+    extension).  For a batch of B sequences clipped to T' indices, from softmax(logits / temperature) of the step that chose each index:
+    log_prob (B, T') fp32 - the token's log-probability; entropy (B, T') fp32 - the distribution's entropy in nats; rank (B, T') int64 - how
+    many tokens the model ordered before it (raw logit descending, then id ascending; 0 = it was the arg-max); top_tokens (B, T', K) int64
+    and top_log_probs (B, T', K) fp32 - the first K tokens of that order and their log-probabilities.  Where no token is scored - index 0,
+    <bos>, and every position after the row's end - the floats are NaN and the integers -1.  uncertainty: None, or one (h_p, w_p) fp32 heat
+    map per image, the tokens' cross-attention maps summed with a per-token weight; alignment: None or the TokenAlignment of the same
+    pass."""
+
+    __slots__ = ("log_prob", "entropy", "rank", "top_tokens", "top_log_probs", "uncertainty", "alignment")
+
+    def __init__(self, log_prob, entropy, rank, top_tokens, top_log_probs, uncertainty=None, alignment=None):
+        self.log_prob, self.entropy, self.rank, self.top_tokens, self.top_log_probs = log_prob, entropy, rank, top_tokens, top_log_probs
+        self.uncertainty, self.alignment = uncertainty, alignment
+
+    @property
+    def margin(self):
+        """(B, T') fp32: log-probability of the best token minus the runner-up's; NaN where nothing is scored and when K = 1."""
+        if self.top_log_probs.shape[-1] < 2:
+            return torch.full_like(self.log_prob, float("nan"))
+        return self.top_log_probs[..., 0] - self.top_log_probs[..., 1]
+
+    @property
+    def mean_log_prob(self):
+        """(B,) fp32: the mean of log_prob over the row's scored tokens (NaN for a row without one).  The reference UI's per-page figure
+        (ui/routes.py, avg_log_prob -> avgConfidence) is log_probs.sum() / seq_mask.sum(): the same sum - <bos> carries log-probability 0 -
+        divided by one more, because its mask counts <bos>: for a row of L tokens it is (L - 1) / L of this mean."""
+        scored = ~torch.isnan(self.log_prob)
+        return torch.where(scored, self.log_prob, torch.zeros_like(self.log_prob)).sum(-1) / scored.sum(-1)
+
+    def __repr__(self):
+        return (f"TokenConfidence(log_prob={tuple(self.log_prob.shape)}, top_k={self.top_tokens.shape[-1]}, "
+                f"uncertainty={'yes' if self.uncertainty is not None else None}, alignment={'yes' if self.alignment is not None else None})")
+
+
+UNCERTAINTY_WEIGHTS = ("entropy", "surprisal", "error")
+
+
 class ViTOMR(nn.Module):
     def __init__(self, encoder, transition_head, decoder):
         super().__init__()
@@ -668,44 +721,59 @@ class ViTOMR(nn.Module):
                 raise ValueError(f"grids[{i}] = {(h, w)} does not cover the image's {s} patches")
         return out
 
-    def _align_packed(self, mem32, memb, lens_s, seqs, seq_mask, layers, head_weights, as_decoded, grids=None, patch_size=None, return_maps=True):
-        """The alignment pass on packed memories: the maps list of cross_attention_maps, and with grids a TokenAlignment."""
-        dec = self.decoder
-        dec._alignment_selection(layers, head_weights)   # argument errors before any work
+    def _scored_rows(self, mem32, memb, lens_s, seqs, seq_mask):
+        """The teacher-forced pass's inputs for decoded sequences: (L_i of every row, rows with L_i >= 2, their input lengths L_i - 1, their
+        memory lengths, mem32 and memb cut down to those rows, packed input tokens seqs[i, :L_i - 1] - None without such a row, (bi, ti) -
+        for every packed token the (row, output index) of a (B, T') tensor that it scores)."""
         Ls = self._alignment_lengths(seqs, seq_mask)
-        B, Tp = seqs.shape
-        if len(lens_s) != B:
-            raise ValueError(f"{B} sequences for {len(lens_s)} images")
-        dev = dec.pos_embedding.device
+        if len(lens_s) != seqs.shape[0]:
+            raise ValueError(f"{seqs.shape[0]} sequences for {len(lens_s)} images")
+        dev = self.decoder.pos_embedding.device
         rows = [i for i, L in enumerate(Ls) if L >= 2]
-        empty = lambda i: torch.zeros(0, lens_s[i], dtype=torch.float32, device=dev)   # noqa: E731
-        maps = [None] * B
+        lens_t = [Ls[i] - 1 for i in rows]
+        sub_s = [lens_s[i] for i in rows]
+        if not rows:
+            return Ls, rows, lens_t, sub_s, mem32, memb, None, None
+        if len(rows) < len(Ls):   # rows without a scored token leave the batch: their memory rows are cut out
+            starts = [sum(lens_s[:i]) for i in rows]
+            cut = lambda m: None if m is None else torch.cat([m[o:o + s] for o, s in zip(starts, sub_s)]).contiguous()   # noqa: E731
+            mem32, memb = cut(mem32), cut(memb)
+        tokens = torch.cat([seqs[i, :Ls[i] - 1] for i in rows])
+        bi = torch.cat([torch.full((t,), i, dtype=torch.int64) for i, t in zip(rows, lens_t)]).to(dev)
+        ti = torch.cat([torch.arange(1, t + 1, dtype=torch.int64) for t in lens_t]).to(dev)
+        return Ls, rows, lens_t, sub_s, mem32, memb, tokens, (bi, ti)
+
+    def _located(self, shape, lens_s, rows, lens_t, sub_s, at, out, offs, map_off, grids, patch_size, return_maps):
+        """The maps list of cross_attention_maps from the flat buffer of a pass over `rows` (out None: no row had a map), and with grids the
+        TokenAlignment of those maps."""
+        dev = self.decoder.pos_embedding.device
+        B, Tp = shape
+        maps = [torch.zeros(0, s, dtype=torch.float32, device=dev) for s in lens_s]
         patch = torch.full((B, Tp), -1, dtype=torch.int64, device=dev)
         loc_full = torch.full((B, Tp, 6), float("nan"), dtype=torch.float32, device=dev)
-        if rows:
-            lens_t = [Ls[i] - 1 for i in rows]
-            sub_s = [lens_s[i] for i in rows]
-            if len(rows) < B:   # rows without a map leave the batch: their memory rows are cut out
-                starts = [sum(lens_s[:i]) for i in rows]
-                cut = lambda m: None if m is None else torch.cat([m[o:o + s] for o, s in zip(starts, sub_s)]).contiguous()   # noqa: E731
-                mem32, memb = cut(mem32), cut(memb)
-            tokens = torch.cat([seqs[i, :Ls[i] - 1] for i in rows])
-            out, offs, map_off, _ = dec._cross_attention_maps_flat(tokens, lens_t, mem32, memb, sub_s, layers, head_weights, 1 if as_decoded else 0,
-                                                                   None, False)
+        if out is not None:
             for i, o, t, s in zip(rows, offs, lens_t, sub_s):
                 maps[i] = out[o:o + t * s].view(t, s)
             if grids is not None:
                 cu_t, cu_s = EG.cu_from_lens(lens_t, dev), EG.cu_from_lens(sub_s, dev)
                 p, loc = ops.attn_map_locate(out, map_off, cu_t, cu_s, [grids[i][1] for i in rows], max(lens_t), sum(lens_t))
-                bi = torch.cat([torch.full((t,), i, dtype=torch.int64) for i, t in zip(rows, lens_t)]).to(dev)
-                ti = torch.cat([torch.arange(1, t + 1, dtype=torch.int64) for t in lens_t]).to(dev)
-                patch[bi, ti] = p.long()
-                loc_full[bi, ti] = loc
-        maps = [m if m is not None else empty(i) for i, m in enumerate(maps)]
+                patch[at] = p.long()
+                loc_full[at] = loc
         if grids is None:
             return maps
         P = float(patch_size)
         return TokenAlignment(patch, loc_full[..., 2:4] * P, loc_full[..., 4:6] * P, loc_full[..., 1].clone(), list(grids), maps if return_maps else None)
+
+    def _align_packed(self, mem32, memb, lens_s, seqs, seq_mask, layers, head_weights, as_decoded, grids=None, patch_size=None, return_maps=True):
+        """The alignment pass on packed memories: the maps list of cross_attention_maps, and with grids a TokenAlignment."""
+        dec = self.decoder
+        dec._alignment_selection(layers, head_weights)   # argument errors before any work
+        _, rows, lens_t, sub_s, mem32, memb, tokens, at = self._scored_rows(mem32, memb, lens_s, seqs, seq_mask)
+        out = offs = map_off = None
+        if rows:
+            out, offs, map_off, _ = dec._cross_attention_maps_flat(tokens, lens_t, mem32, memb, sub_s, layers, head_weights, 1 if as_decoded else 0,
+                                                                   None, False)
+        return self._located(seqs.shape, lens_s, rows, lens_t, sub_s, at, out, offs, map_off, grids, patch_size, return_maps)
 
     def cross_attention_maps(self, img_latent, latent_attention_mask, seqs, seq_mask=None, layers=None, head_weights=None, as_decoded=True):
         """Token-to-image alignment (an extension): for decoded (or any) sequences `seqs` (B, T) over the memories img_latent (B, S_max, E) /
@@ -742,6 +810,119 @@ class ViTOMR(nn.Module):
         mem32, lens_s = EG.unpad_rows(img_latent.to(self.decoder.pos_embedding.device), latent_attention_mask)
         with torch.no_grad():
             return self._align_packed(mem32, None, lens_s, seqs, seq_mask, layers, head_weights, as_decoded, grids, patch_size, return_maps)
+
+    # ---- per-token confidence (an extension) --------------------------------------------------------------------------------
+    def _check_confidence_args(self, top_k, temperature):
+        """top_k and temperature of token_confidence / uncertainty_maps, checked on the host: (int, float).  ValueError."""
+        V = self.decoder.vocab_size
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= min(ops.CONFIDENCE_MAX_K, V):
+            raise ValueError(f"top_k must be an int with 1 <= top_k <= min({ops.CONFIDENCE_MAX_K}, V={V}), got {top_k!r}")
+        try:
+            tau = float(temperature)
+        except (TypeError, ValueError):
+            raise ValueError(f"temperature must be a positive number, got {temperature!r}") from None
+        if not (tau > 0 and math.isfinite(tau)):
+            raise ValueError(f"temperature must be positive and finite, got {temperature!r}")
+        return top_k, tau
+
+    @staticmethod
+    def _check_uncertainty_weight(weight, shape):
+        """uncertainty_maps' `weight`: one of UNCERTAINTY_WEIGHTS, or a (B, T') real tensor of the caller's.  ValueError."""
+        if isinstance(weight, str):
+            if weight not in UNCERTAINTY_WEIGHTS:
+                raise ValueError(f"weight must be one of {UNCERTAINTY_WEIGHTS} or a (B, T') tensor, got {weight!r}")
+        elif not torch.is_tensor(weight) or tuple(weight.shape) != tuple(shape) or weight.dtype.is_complex or weight.dtype == torch.bool:
+            what = f"a {tuple(weight.shape)} {weight.dtype} tensor" if torch.is_tensor(weight) else repr(weight)
+            raise ValueError(f"weight must be one of {UNCERTAINTY_WEIGHTS} or a real tensor of seqs' shape {tuple(shape)}, got {what}")
+        return weight
+
+    def _confidence_packed(self, mem32, memb, lens_s, seqs, seq_mask, top_k, temperature, as_decoded, weight=None, layers=None,
+                           head_weights=None, grids=None, patch_size=None, return_alignment=False):
+        """The confidence pass on packed memories -> TokenConfidence.  weight None: the logits-only pass; otherwise the combined pass (maps and
+        logits from one teacher-forced pass), the heat maps over `grids`, and with return_alignment the TokenAlignment of the same maps."""
+        dec = self.decoder
+        top_k, tau = self._check_confidence_args(top_k, temperature)
+        B, Tp = seqs.shape
+        dev = dec.pos_embedding.device
+        if weight is not None:
+            dec._alignment_selection(layers, head_weights)
+            weight = self._check_uncertainty_weight(weight, seqs.shape)
+        Ls, rows, lens_t, sub_s, mem32, memb, tokens, at = self._scored_rows(mem32, memb, lens_s, seqs, seq_mask)
+        nan = lambda *sh: torch.full(sh, float("nan"), dtype=torch.float32, device=dev)   # noqa: E731
+        none = lambda *sh: torch.full(sh, -1, dtype=torch.int64, device=dev)   # noqa: E731
+        conf = TokenConfidence(nan(B, Tp), nan(B, Tp), none(B, Tp), none(B, Tp, top_k), nan(B, Tp, top_k))
+        out = offs = map_off = heat = None
+        if rows:
+            if weight is None:
+                logits = dec.logits_packed(tokens, lens_t, mem32, memb, sub_s, 1 if as_decoded else 0)
+            else:
+                out, offs, map_off, logits = dec._cross_attention_maps_flat(tokens, lens_t, mem32, memb, sub_s, layers, head_weights,
+                                                                            1 if as_decoded else 0, None, True)
+            chosen = torch.cat([seqs[i, 1:Ls[i]] for i in rows]).to(dev)
+            lp, ent, rank, ids, top_lp = ops.token_confidence(logits, chosen, top_k, tau)
+            conf.log_prob[at], conf.entropy[at], conf.rank[at] = lp, ent, rank.long()
+            conf.top_tokens[at], conf.top_log_probs[at] = ids.long(), top_lp
+            if weight is not None:
+                if isinstance(weight, str):
+                    w = ent if weight == "entropy" else -lp if weight == "surprisal" else 1.0 - torch.exp(lp)
+                else:
+                    w = weight.to(device=dev, dtype=torch.float32)[at]
+                cu_t, cu_s = EG.cu_from_lens(lens_t, dev), EG.cu_from_lens(sub_s, dev)
+                heat = ops.attn_map_weighted_sum(out, map_off, cu_t, cu_s, w.contiguous(), max(lens_t), layout=(lens_t, sub_s, offs))
+        if weight is not None:
+            conf.uncertainty = [torch.zeros(h, w, dtype=torch.float32, device=dev) for h, w in grids]
+            o = 0
+            for i, s in zip(rows, sub_s):
+                conf.uncertainty[i] = heat[o:o + s].view(*grids[i])
+                o += s
+            if return_alignment:
+                conf.alignment = self._located(seqs.shape, lens_s, rows, lens_t, sub_s, at, out, offs, map_off, grids, patch_size, False)
+        return conf
+
+    def token_confidence(self, img_latent, latent_attention_mask, seqs, seq_mask=None, top_k=5, temperature=1.0, as_decoded=True):
+        """Per-token confidence of decoded (or any) sequences (an extension) -> TokenConfidence.  For seqs (B, T) over the memories
+        img_latent (B, S_max, E) / latent_attention_mask: one teacher-forced pass over input indices 0 .. L_i - 2 (L_i as in
+        cross_attention_maps; all layers, no maps), with the KV-cached decode's positions when as_decoded (default), so that row j holds the
+        logits the decode chose index j + 1 from; then one launch (ops.token_confidence) scores the token actually at each index,
+        seqs[i, 1:L_i], under softmax(logits / temperature): its log-probability, the entropy, its rank and the top_k (1 .. 8) best tokens.
+        Works after every decode mode - greedy, beam, speculative, prompted, constrained, FP8 memory cache - because it reads the memory
+        itself, not the KV caches: engine state, graphs and caches stay untouched, and a decode after it is bitwise the decode before it.
+        Runs under the caller's autocast, as forward does.  For a grammar-constrained decode the scores are the UNCONSTRAINED model's (the
+        decode's own log_probs are renormalised over the allowed tokens): rank > 0 then marks a token the grammar forced.  ValueError for
+        top_k outside 1 .. min(8, V) or a temperature that is not positive and finite."""
+        self._check_confidence_args(top_k, temperature)
+        self._alignment_lengths(seqs, seq_mask)
+        mem32, lens_s = EG.unpad_rows(img_latent.to(self.decoder.pos_embedding.device), latent_attention_mask)
+        with torch.no_grad():
+            return self._confidence_packed(mem32, None, lens_s, seqs, seq_mask, top_k, temperature, as_decoded)
+
+    def uncertainty_maps(self, img_latent, latent_attention_mask, seqs, seq_mask=None, weight="entropy", layers=None, head_weights=None, grids=None,
+                         top_k=5, temperature=1.0, return_alignment=False):
+        """token_confidence plus a page uncertainty map (an extension) -> TokenConfidence with `uncertainty` filled: per image an (h_p, w_p)
+        fp32 heat map over its patch grid, heat[s] = sum_j weight[j] * map[j, s] - every token's cross-attention map (cross_attention_maps;
+        layers / head_weights as there, decode positions) added up with a per-token weight, so that the regions the unsure tokens looked at
+        light up.  One teacher-forced pass gives the maps and the logits.  weight: "entropy" (the step's entropy), "surprisal" (-log_prob),
+        "error" (1 - exp(log_prob)) or a (B, T') tensor of the caller's, of which only the scored entries (index 1 .. L_i - 1) are read;
+        anything else raises ValueError.  grids (required): the images' patch grids [(h_p, w_p), ...] with h_p * w_p = S_i (ValueError
+        otherwise).  return_alignment also fills `alignment` with what locate_tokens returns for the same arguments, from the same maps.  As
+        in token_confidence, the scores after a grammar-constrained decode are the unconstrained model's.  Which weight marks real errors
+        best on trained checkpoints has not been measured, nor which layers and heads to average."""
+        if grids is None:
+            raise ValueError("grids is required: one (h_p, w_p) per image")
+        self._check_confidence_args(top_k, temperature)
+        self.decoder._alignment_selection(layers, head_weights)
+        B, Lm = img_latent.shape[0], img_latent.shape[1]
+        lens_s = [Lm] * B if latent_attention_mask is None else [int(l) for l in (~latent_attention_mask).sum(dim=1).tolist()]
+        grids = self._check_grids(grids, lens_s)
+        self._alignment_lengths(seqs, seq_mask)
+        self._check_uncertainty_weight(weight, seqs.shape)
+        patch_size = getattr(self.encoder, "patch_size", None)
+        if return_alignment and (patch_size is None or float(patch_size) <= 0):
+            raise ValueError("return_alignment needs the encoder's patch_size (the model has no encoder to take it from)")
+        mem32, lens_s = EG.unpad_rows(img_latent.to(self.decoder.pos_embedding.device), latent_attention_mask)
+        with torch.no_grad():
+            return self._confidence_packed(mem32, None, lens_s, seqs, seq_mask, top_k, temperature, True, weight, layers, head_weights, grids,
+                                           patch_size, return_alignment)
 
     def cached_set_up_inference(self, img_latent, max_len):
         self.decoder.prepare_caches(img_latent)

@@ -387,6 +387,91 @@ def attn_map_locate(maps, map_off, cu_q, cu_k, grid_w, max_q, total_q):
     return patch, loc
 
 
+CONFIDENCE_MAX_K = 8
+_WSUM_ROWS = 32   # tokens per split of acai_attn_map_weighted_sum (confidence.hip, WS_ROWS)
+
+
+def token_confidence(logits, chosen, top_k=5, temperature=1.0):
+    """Per-row confidence statistics in one launch (acai_token_confidence).  logits (N, V) fp32 contiguous and chosen (N,) integer ids on the
+    GPU, 1 <= top_k <= min(8, V), temperature > 0 -> (log_prob (N,) fp32, entropy (N,) fp32 in nats, rank (N,) int32, top_ids (N, top_k) int32,
+    top_log_probs (N, top_k) fp32) of softmax(logits / temperature): the chosen token's log-probability, the row's entropy, how many tokens
+    come before the chosen one in the row's order (raw logit descending, then index ascending; 0 = the arg-max) and the first top_k tokens of
+    that order.  -inf logits are allowed (log-probability -inf, ordered last by index); a row without a finite maximum or with a NaN is
+    outside the contract.  Everything is checked on the host before the launch - ValueError (RuntimeError for CPU tensors, as every op); a
+    chosen id outside [0, V) costs one device-to-host read.  N = 0 returns empty tensors without a launch."""
+    _chk(logits, "logits"), _chk(chosen, "chosen")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError(f"logits must be a contiguous (N, V) float32 tensor, got {tuple(logits.shape)} {logits.dtype} strides {logits.stride()}")
+    N, V = logits.shape
+    if chosen.dim() != 1 or chosen.shape[0] != N or chosen.dtype.is_floating_point or chosen.dtype.is_complex or chosen.dtype == torch.bool:
+        raise ValueError(f"chosen must be {N} integer token ids, got {tuple(chosen.shape)} {chosen.dtype}")
+    if chosen.device != logits.device:
+        raise ValueError(f"chosen is on {chosen.device}, logits on {logits.device}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= min(CONFIDENCE_MAX_K, max(V, 1)) or V < 1:
+        raise ValueError(f"top_k must be an int with 1 <= top_k <= min({CONFIDENCE_MAX_K}, V={V}), got {top_k!r}")
+    try:
+        tau = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"temperature must be a positive number, got {temperature!r}") from None
+    if not (tau > 0 and math.isfinite(tau)):
+        raise ValueError(f"temperature must be positive and finite, got {temperature!r}")
+    dev = logits.device
+    log_prob, entropy = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
+    rank = torch.empty(N, dtype=torch.int32, device=dev)
+    top_ids, top_lp = torch.empty(N, top_k, dtype=torch.int32, device=dev), torch.empty(N, top_k, dtype=torch.float32, device=dev)
+    if N == 0:
+        return log_prob, entropy, rank, top_ids, top_lp
+    chosen = chosen.to(torch.int64).contiguous()
+    lo, hi = (int(x) for x in torch.stack([chosen.min(), chosen.max()]).tolist())   # the kernel reads logits[r, chosen[r]]
+    if lo < 0 or hi >= V:
+        raise ValueError(f"chosen holds a token id outside [0, {V}) (smallest {lo}, largest {hi})")
+    _lib.check(_lib.lib().acai_token_confidence(logits.data_ptr(), chosen.data_ptr(), N, V, top_k, tau, log_prob.data_ptr(), entropy.data_ptr(),
+                                                rank.data_ptr(), top_ids.data_ptr(), top_lp.data_ptr(), _st()), "acai_token_confidence")
+    return log_prob, entropy, rank, top_ids, top_lp
+
+
+def attn_map_weighted_sum(maps, map_off, cu_q, cu_k, weights, max_q, layout=None):
+    """The maps of attn_probs_mean summed over the token axis, one weight per token (acai_attn_map_weighted_sum): maps (flat fp32 buffer),
+    map_off [B] int64, cu_q / cu_k [B + 1] int32 as attn_probs_mean takes them, weights (sum T,) fp32 packed like the tokens, max_q >= every
+    T_b -> (sum S,) fp32 packed like the patches, heat_b[s] = sum_t weights_b[t] * map_b[t, s].  The same bits on every run.  The layout
+    is checked on the host (ValueError): every block lies inside `maps`, weights has sum T entries.  layout: the host lists (lens_q, lens_k,
+    offsets) that cu_q, cu_k and map_off were built from, when the caller still has them; without it they are read back from the device once."""
+    _chk(maps, "maps", torch.float32), _chk(map_off, "map_off", torch.int64), _chk(cu_q, "cu_q", torch.int32), _chk(cu_k, "cu_k", torch.int32)
+    _chk(weights, "weights", torch.float32)
+    B = cu_q.numel() - 1
+    if B < 1 or cu_k.numel() != B + 1 or map_off.numel() != B or maps.dim() != 1 or weights.dim() != 1:
+        raise ValueError(f"attn_map_weighted_sum: {B} images need cu_q / cu_k of {B + 1} entries, map_off of {B}, flat maps and weights")
+    if not (maps.is_contiguous() and weights.is_contiguous() and map_off.is_contiguous() and cu_q.is_contiguous() and cu_k.is_contiguous()):
+        raise ValueError("attn_map_weighted_sum: operands must be contiguous")
+    if layout is None:
+        host = torch.cat([cu_q.long(), cu_k.long(), map_off]).tolist()
+        hq, hk, ho = host[:B + 1], host[B + 1:2 * B + 2], host[2 * B + 2:]
+        lens_q, lens_k = [b - a for a, b in zip(hq, hq[1:])], [b - a for a, b in zip(hk, hk[1:])]
+    else:
+        lens_q, lens_k, ho = ([int(v) for v in x] for x in layout)
+        if not len(lens_q) == len(lens_k) == len(ho) == B:
+            raise ValueError(f"attn_map_weighted_sum: layout must hold {B} query lengths, key lengths and offsets")
+        hq, hk = [0], [0]
+        for t, k in zip(lens_q, lens_k):
+            hq.append(hq[-1] + t), hk.append(hk[-1] + k)
+    if hq[0] != 0 or hk[0] != 0 or min(lens_q) < 0 or min(lens_k) < 1:
+        raise ValueError(f"attn_map_weighted_sum: bad cumulative lengths cu_q={hq} cu_k={hk}")
+    if weights.numel() != hq[-1]:
+        raise ValueError(f"attn_map_weighted_sum: weights holds {weights.numel()} entries for {hq[-1]} tokens")
+    if int(max_q) < max(max(lens_q), 1):
+        raise ValueError(f"attn_map_weighted_sum: max_q={max_q} is smaller than the longest sequence ({max(lens_q)})")
+    for b, (o, t, s) in enumerate(zip(ho, lens_q, lens_k)):
+        if o < 0 or o + t * s > maps.numel():
+            raise ValueError(f"attn_map_weighted_sum: image {b}'s [{t}][{s}] block at offset {o} lies outside the {maps.numel()} map elements")
+    total_k, nsplit = hk[-1], -(-int(max_q) // _WSUM_ROWS)
+    out = torch.empty(total_k, dtype=torch.float32, device=maps.device)
+    partial = torch.empty(nsplit * total_k, dtype=torch.float32, device=maps.device) if nsplit > 1 else None
+    _lib.check(_lib.lib().acai_attn_map_weighted_sum(maps.data_ptr(), map_off.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), weights.data_ptr(), B,
+                                                     int(max_q), max(lens_k), total_k, _p(partial), out.data_ptr(), _st()),
+               "acai_attn_map_weighted_sum")
+    return out
+
+
 def cross_kv_prefill(mem, w_kv, b_kv, row_seq, row_pos, seq_off, seq_len, k_out, v_out, H, dh, dhp, round_bf16=False):
     _chk(mem, "mem"), _chk(w_kv, "w_kv")
     M, E = mem.shape

@@ -204,6 +204,26 @@ int acai_attn_probs_mean(const void *q, int ldq, const void *k, int ldk, const i
  * m == 0 gives centroid and spread 0 and patch 0.  Errors: null operand, grid_w[b] < 1, B > 512. */
 int acai_attn_map_locate(const float *map, const int64_t *map_off, const int32_t *cu_q, const int32_t *cu_k, const int32_t *grid_w,
                          int B, int max_q, int32_t *patch, float *loc, void *stream);
+/* Per-token confidence (an extension; no reference counterpart): what a decode step's selection launch knew and threw away.  logits [N][V]
+ * fp32, rows back to back; chosen [N] int64 in [0, V) (the CALLER checks that: the kernel reads logits[r][chosen[r]]); 1 <= top_k <= min(8, V);
+ * temperature > 0.  One launch, one wave per row.  With z = logits[r] / temperature and lse = logsumexp(z):
+ *   log_prob[r] = z[chosen[r]] - lse;   entropy[r] = -sum_i p_i log p_i in nats (p_i = 0 contributes 0);
+ *   rank[r]     = how many tokens come before chosen[r] in the row's order - raw logit descending, then index ascending (0: the arg-max,
+ *                 first index on ties, as the greedy step picks it);
+ *   top_ids[r][0..top_k), top_log_probs[r][0..top_k) = the first top_k tokens of that order and their z - lse.
+ * The order is decided on the raw fp32 logits, so the integer outputs are exact.  -inf logits are allowed: log-probability -inf, ordered
+ * last by index; a row whose maximum is -inf or that holds a NaN is outside the contract.  The same bits on every run.  N == 0 returns
+ * at once.  Errors: null operand, V < 1, top_k or temperature out of range. */
+int acai_token_confidence(const float *logits, const int64_t *chosen, int N, int V, int top_k, float temperature, float *log_prob,
+                          float *entropy, int32_t *rank, int32_t *top_ids, float *top_log_probs, void *stream);
+/* The maps of acai_attn_probs_mean (map / map_off / cu_q / cu_k as there) summed over the token axis with one fp32 weight per token
+ * (weights [total_q], packed like the tokens): out[cu_k[b] + s] = sum_t weights[cu_q[b] + t] * map_b[t][s], fp32 [total_k], packed like the
+ * patches.  max_q / max_k bound the sequence lengths.  The token axis is cut into splits of 32 tokens, one workgroup per split and 256
+ * columns, so that one image fills the device; each split is summed in token order and a second launch adds the splits in order: the same
+ * bits on every run, no atomics.  partial: workspace of ceil(max_q / 32) * total_k floats (may be NULL when max_q <= 32: one launch).  An
+ * image without tokens gets zeros.  Errors: null operand, bad dims, B > 65535. */
+int acai_attn_map_weighted_sum(const float *map, const int64_t *map_off, const int32_t *cu_q, const int32_t *cu_k, const float *weights,
+                               int B, int max_q, int max_k, int64_t total_k, float *partial, float *out, void *stream);
 
 /* nn.Dropout on a projection output followed by the residual add (torch TransformerEncoderLayer dropout1/dropout2, decoder dropout1-3,
  * transition head M:658): out = residual + keep * x / (1 - p); residual may be NULL (plain dropout, and its own backward on dy).
