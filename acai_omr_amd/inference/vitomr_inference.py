@@ -155,6 +155,30 @@ def confident_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, top
     return seqs, lps, mask, conf
 
 
+def diagnosed_inference(vitomr: ViTOMR, img, target_lmx_seqs, device, max_inference_len=1536, **decode_kwargs):
+    """inference() scored against the ground truth (an extension) -> (seqs, log_probs, seq_mask, TokenConfidence, EditAlignment).  The
+    images are encoded once and the decode is inference()'s own (decode_kwargs as in aligned_inference; its errors stay its errors); the
+    decoded rows are then aligned to target_lmx_seqs - a list of 1-D token tensors, one per image, written as the decode writes its rows
+    (<bos> first, <eos> last) - on the device (ops.edit_alignment), and one teacher-forced pass on the same packed memory gives the
+    per-token confidence and, in TokenConfidence.uncertainty, the page heat map of the tokens that are wrong (ViTOMR.error_maps): a
+    substituted or inserted token weighs 1 where it stands, a missing one 1 at the output position where it should have been emitted.
+    TokenConfidence.alignment locates every token.  EditAlignment.pred_op != 0 are the error labels utils.confidence_error_auroc takes."""
+    _check_decode_kwargs("diagnosed_inference", decode_kwargs)
+    vitomr.eval()
+    with torch.no_grad():
+        dims = list(img.dims) if hasattr(img, "dims") else [vitomr.encoder._grid(t) for t in img]
+        lat32, _, lens = _encode(vitomr, img)
+        with autocast(device_type=device, dtype=torch.bfloat16):
+            mem = vitomr.transition_head.forward_packed(lat32)
+            bf = mem.dtype == torch.bfloat16
+            mem32, memb = (None, mem) if bf else (mem, None)
+            seqs, lps, mask = _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs)
+            grids = vitomr._check_grids(dims, lens)
+            al, w = vitomr._error_weights(seqs, mask, target_lmx_seqs, None)
+            conf = vitomr._confidence_packed(mem32, memb, lens, seqs, mask, 5, 1.0, True, w, None, None, grids, vitomr.encoder.patch_size, True)
+    return seqs, lps, mask, conf, al
+
+
 def _encode_chunks(vitomr, imgs, device):
     """Encoder (fp32, outside autocast) and transition head (inside autocast) over chunks of at most max_batch_size images; the packed
     memories of all chunks, concatenated, and their lengths."""

@@ -924,6 +924,39 @@ class ViTOMR(nn.Module):
             return self._confidence_packed(mem32, None, lens_s, seqs, seq_mask, top_k, temperature, True, weight, layers, head_weights, grids,
                                            patch_size, return_alignment)
 
+    # ---- ground-truth error maps (an extension) -----------------------------------------------------------------------------
+    def _error_weights(self, seqs, seq_mask, target_lmx_seqs, pad_idx):
+        """(ops.EditAlignment of seqs at their seq_mask positions - up to and including the first <eos> when seq_mask is None - against the
+        targets, utils.error_token_weights of it): the per-token weight of error_maps.  Device work only."""
+        from ..utils import _pad_targets, error_token_weights
+        dev = self.decoder.pos_embedding.device
+        seqs = seqs.to(dev)
+        keep = self.create_inference_mask(seqs) if seq_mask is None else seq_mask.to(dev).bool()
+        tgt, target_lens = _pad_targets(target_lmx_seqs, pad_idx, dev)
+        if tgt.shape[0] != seqs.shape[0]:
+            raise ValueError(f"{seqs.shape[0]} decoded rows against {tgt.shape[0]} targets")
+        al = ops.edit_alignment(seqs, keep, tgt, target_lens)
+        return al, error_token_weights(al, keep.sum(dim=-1))
+
+    def error_maps(self, img_latent, latent_attention_mask, seqs, seq_mask, target_lmx_seqs, pad_idx=None, grids=None, layers=None,
+                   head_weights=None, return_alignment=False):
+        """Where on the page the REAL errors of decoded rows are (an extension) -> (TokenConfidence, ops.EditAlignment).  seqs / seq_mask
+        (B, T') are aligned to the ground truth on the device (ops.edit_alignment; targets as utils.symbol_error_rate takes them: a list of
+        1-D tensors, or a padded tensor with pad_idx; <bos> / <eos> count where present, so give the targets as the decode writes its
+        rows) and every output token gets the weight utils.error_token_weights states: 1 when it is substituted or inserted, plus the
+        number of target tokens missing in front of it.  That weight goes through uncertainty_maps(weight=<tensor>): the TokenConfidence's
+        `uncertainty` is, per image, the (h_p, w_p) heat map of the cross-attention maps of the tokens in error - all zero for a perfect
+        row - next to the model's own confidence in the same tokens, which utils.confidence_error_auroc relates to pred_op != 0.  grids,
+        layers, head_weights and return_alignment (the TokenAlignment, in `.alignment`) as in uncertainty_maps.  How well the maps point at
+        the faulty symbols on trained checkpoints has not been measured."""
+        if grids is None:
+            raise ValueError("grids is required: one (h_p, w_p) per image")
+        self._alignment_lengths(seqs, seq_mask)   # argument errors before any work
+        al, w = self._error_weights(seqs, seq_mask, target_lmx_seqs, pad_idx)
+        conf = self.uncertainty_maps(img_latent, latent_attention_mask, seqs, seq_mask, weight=w, layers=layers, head_weights=head_weights,
+                                     grids=grids, return_alignment=return_alignment)
+        return conf, al
+
     def cached_set_up_inference(self, img_latent, max_len):
         self.decoder.prepare_caches(img_latent)
         B, dev = img_latent.shape[0], img_latent.device

@@ -8,6 +8,7 @@ import ctypes
 import functools
 
 import math
+from typing import NamedTuple
 
 import torch
 
@@ -833,6 +834,78 @@ def edit_distance(pred, pred_len, tgt, tgt_len, group=1, out=None):
         return out
     _lib.check(_lib.lib().acai_edit_distance(pred.data_ptr(), pred.shape[1], pred_len.data_ptr(), tgt.data_ptr(), tgt.shape[1], tgt_len.data_ptr(),
                                              R, group, out.data_ptr(), _st(pred)), "acai_edit_distance")
+    return out
+
+
+class EditAlignment(NamedTuple):
+    """What edit_alignment returns for R pairs of widths (Lp, Lt).  counts (R, 4) int32: matches, substitutions, insertions, deletions;
+    pred_op (R, Lp) int8: 0 match, 1 substitution, 2 insertion; pred_to_tgt (R, Lp) int32: the aligned target index, -1 for an insertion;
+    tgt_to_pred (R, Lt) int32: the aligned pred index, -1 for a deleted target token; tgt_slot (R, Lt) int32: pred tokens consumed before
+    the target token on the path (for a deleted token: the pred index it is missing in front of, in [0, len]).  -1 past a row's length."""
+    counts: torch.Tensor
+    pred_op: torch.Tensor
+    pred_to_tgt: torch.Tensor
+    tgt_to_pred: torch.Tensor
+    tgt_slot: torch.Tensor
+
+
+EDIT_ALIGNMENT_WORKSPACE_LIMIT = 256 << 20   # bytes of direction words beyond which edit_alignment runs its rows in chunks
+
+
+def edit_alignment_workspace_bytes(ld_pred, ld_tgt, rows=1):
+    """Bytes of workspace that one launch over `rows` pairs of widths (ld_pred, ld_tgt) needs (acai_edit_align_workspace_bytes)."""
+    return int(_lib.lib().acai_edit_align_workspace_bytes(int(ld_pred), int(ld_tgt), int(rows)))
+
+
+def edit_alignment(pred, pred_len, tgt, tgt_len, group=1, out=None, workspace=None):
+    """The canonical optimal edit alignment of each pred[r, :pred_len[r]] to tgt[r // group, :tgt_len[r // group]] (acai_edit_align) ->
+    EditAlignment.  Arguments as edit_distance takes them: pred (R, Lp) and tgt (R // group, Lt) int64, Lp, Lt <= 4096 (ValueError beyond), the
+    lengths int32 vectors or bool prefix masks read on the device (no host sync).  Among the optimal paths the one is returned that, walking
+    back from the ends, prefers the diagonal (match / substitution), then an insertion, then a deletion; counts[:, 1:].sum(1) is
+    edit_distance's result.  out: an EditAlignment (or five tensors) to write into; workspace: a GPU buffer for the direction words
+    (edit_alignment_workspace_bytes; default: allocated here).  When the workspace of all R rows would exceed 256 MiB - or the given one is
+    smaller than that - the rows run in chunks of whole groups, one launch per chunk, with the same results; a workspace too small for one group
+    raises ValueError.  With int32 lengths, out and workspace given and a single chunk, the call is one kernel launch and nothing else."""
+    pred, pred_len = _seq_rows(pred, pred_len, "pred")
+    tgt, tgt_len = _seq_rows(tgt, tgt_len, "tgt")
+    R, group = pred.shape[0], int(group)
+    Lp, Lt = pred.shape[1], tgt.shape[1]
+    if group < 1 or tgt.shape[0] * group != R:
+        raise ValueError(f"edit_alignment: {R} pred rows against {tgt.shape[0]} tgt rows with group {group}")
+    shapes = (((R, 4), torch.int32), ((R, Lp), torch.int8), ((R, Lp), torch.int32), ((R, Lt), torch.int32), ((R, Lt), torch.int32))
+    if out is None:
+        out = EditAlignment(*(torch.empty(s, dtype=d, device=pred.device) for s, d in shapes))
+    else:
+        out = EditAlignment(*out)
+        for t, name, (s, d) in zip(out, EditAlignment._fields, shapes):
+            _chk(t, "out." + name, d)
+            if tuple(t.shape) != s or not t.is_contiguous():
+                raise ValueError(f"out.{name}: expected a contiguous {s} tensor, got {tuple(t.shape)}")
+    if workspace is not None:
+        _chk(workspace, "workspace")
+        if not workspace.is_contiguous():
+            raise ValueError("workspace: expected a contiguous buffer")
+    for t in (pred_len, tgt, tgt_len, workspace) + tuple(out):
+        if t is not None and t.device != pred.device:
+            raise RuntimeError(f"edit_alignment: operands on different devices ({pred.device} and {t.device})")
+    if R == 0:
+        return out
+    per_pair = edit_alignment_workspace_bytes(Lp, Lt, 1)
+    limit = EDIT_ALIGNMENT_WORKSPACE_LIMIT if workspace is None else workspace.numel() * workspace.element_size()
+    if workspace is not None and limit < per_pair * group:
+        raise ValueError(f"workspace: {limit} bytes, one group of {group} pairs needs {per_pair * group}")
+    chunk = R if R * per_pair <= limit else max(limit // (per_pair * group), 1) * group
+    if workspace is None:
+        workspace = torch.empty(min(chunk, R) * per_pair, dtype=torch.uint8, device=pred.device)
+        limit = workspace.numel()
+    L = _lib.lib()
+    for r0 in range(0, R, chunk):
+        r1 = min(r0 + chunk, R)
+        g0, g1 = r0 // group, r1 // group
+        _lib.check(L.acai_edit_align(pred[r0:r1].data_ptr(), Lp, pred_len[r0:r1].data_ptr(), tgt[g0:g1].data_ptr(), Lt, tgt_len[g0:g1].data_ptr(),
+                                     r1 - r0, group, out.counts[r0:r1].data_ptr(), out.pred_op[r0:r1].data_ptr(), out.pred_to_tgt[r0:r1].data_ptr(),
+                                     out.tgt_to_pred[r0:r1].data_ptr(), out.tgt_slot[r0:r1].data_ptr(), workspace.data_ptr(), limit, _st(pred)),
+                   "acai_edit_align")
     return out
 
 

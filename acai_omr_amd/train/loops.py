@@ -254,23 +254,31 @@ def fine_tune_validation(vitomr, dataloader, loss_fn, device):
     return _mean_of(losses)
 
 
-def ser_validation(vitomr, dataloader, device, max_inference_len=MAX_LMX_SEQ_LEN, beam_width=1):
+def ser_validation(vitomr, dataloader, device, max_inference_len=MAX_LMX_SEQ_LEN, beam_width=1, breakdown=False):
     """Corpus symbol error rate of the decoded validation set (utils.symbol_error_rate): `inference()` per batch (greedy, or beam search with
     beam_width > 1), token edit distances and target lengths accumulated on the device, one read at the end.  Targets are the batches' LMX
-    rows as the dataset yields them, so <bos> / <eos> count on both sides.  NaN when the loader holds no target tokens."""
+    rows as the dataset yields them, so <bos> / <eos> count on both sides.  NaN when the loader holds no target tokens.
+    breakdown=True (an extension): the rows are aligned instead (ops.edit_alignment, utils.symbol_error_breakdown's counts) and a dict with
+    `ser`, `sub_rate`, `ins_rate` and `del_rate` over the summed target lengths is returned - `ser` is the float the default returns."""
     from .. import ops
     from ..inference.vitomr_inference import inference
-    from ..utils import _pad_targets
+    from ..utils import _pad_targets, _rates
     vitomr.eval()
     dev_type = torch.device(device).type
     dist_sum = torch.zeros((), dtype=torch.int64, device=device)
     len_sum = torch.zeros((), dtype=torch.int64, device=device)
+    count_sum = torch.zeros(4, dtype=torch.int64, device=device)
     for batch in dataloader:
         imgs, targets = zip(*[(ex[0], ex[1]) for ex in batch])
         seqs, _, seq_mask = inference(vitomr, [img.to(device) for img in imgs], dev_type, max_inference_len=max_inference_len, beam_width=beam_width)
         tgt, target_lens = _pad_targets(list(targets), None, seqs.device)
-        dist_sum += ops.edit_distance(seqs, seq_mask, tgt, target_lens).sum()
+        if breakdown:
+            count_sum += ops.edit_alignment(seqs, seq_mask, tgt, target_lens).counts.sum(dim=0)
+        else:
+            dist_sum += ops.edit_distance(seqs, seq_mask, tgt, target_lens).sum()
         len_sum += target_lens.sum()
+    if breakdown:
+        return dict(zip(("ser", "sub_rate", "ins_rate", "del_rate"), _rates(torch.cat([count_sum, len_sum.reshape(1)]).tolist())))
     total = torch.stack([dist_sum, len_sum]).tolist()
     return total[0] / total[1] if total[1] else float("nan")
 

@@ -3,6 +3,7 @@ the learning-rate schedules of the two training loops.  Pure Python / stock torc
 drive `torch.optim.AdamW` (only `param_groups[i]["lr"]` changes); and the image-side resize transforms (8f-2), whose arithmetic runs in a HIP
 kernel."""
 import math
+from typing import NamedTuple
 
 import torch
 from torch.optim.lr_scheduler import CosineAnnealingLR, LinearLR, SequentialLR
@@ -47,6 +48,130 @@ def symbol_error_rate(seqs, seq_mask, target_lmx_seqs, pad_idx=None):
     distances = ops.edit_distance(seqs, seq_mask, tgt, target_lens)
     total = torch.stack([distances.sum(), target_lens.sum()]).tolist()
     return (total[0] / total[1] if total[1] else float("nan")), distances, target_lens
+
+
+class ErrorBreakdown(NamedTuple):
+    """symbol_error_breakdown's result: ser = sub_rate + ins_rate + del_rate as Python floats over the summed target lengths (NaN when every
+    target is empty), counts int32 (N, 4) - matches, substitutions, insertions, deletions per row -, target_lens int32 (N,) and the
+    ops.EditAlignment the counts come from."""
+    ser: float
+    sub_rate: float
+    ins_rate: float
+    del_rate: float
+    counts: torch.Tensor
+    target_lens: torch.Tensor
+    alignment: tuple
+
+
+def _rates(sums):
+    """(ser, sub_rate, ins_rate, del_rate) from the host list [matches, substitutions, insertions, deletions, summed target lengths]."""
+    _, s, i, d, total = sums
+    if not total:
+        return (float("nan"),) * 4
+    return (s + i + d) / total, s / total, i / total, d / total
+
+
+def symbol_error_breakdown(seqs, seq_mask, target_lmx_seqs, pad_idx=None):
+    """symbol_error_rate split into its kinds of error -> ErrorBreakdown.  Arguments as symbol_error_rate takes them, and the same rule:
+    seqs[i] at its seq_mask positions against target i, both as given, so <bos> / <eos> count where present.  The rows are aligned on the
+    device (ops.edit_alignment: the canonical optimal alignment) and a substitution, an insertion (a decoded symbol the target does not have)
+    and a deletion (a target symbol the decode dropped) are counted apart; `ser` is symbol_error_rate's value on the same inputs.  One host
+    sync, at the end."""
+    from . import ops
+    tgt, target_lens = _pad_targets(target_lmx_seqs, pad_idx, seqs.device)
+    if tgt.shape[0] != seqs.shape[0]:
+        raise ValueError(f"symbol_error_breakdown: {seqs.shape[0]} decoded rows against {tgt.shape[0]} targets")
+    al = ops.edit_alignment(seqs, seq_mask, tgt, target_lens)
+    sums = torch.cat([al.counts.sum(dim=0, dtype=torch.int64), target_lens.sum(dtype=torch.int64).reshape(1)]).tolist()
+    return ErrorBreakdown(*_rates(sums), al.counts, target_lens, al)
+
+
+class TokenConfusions(NamedTuple):
+    """token_confusions' result, each list sorted by falling count (then rising id) and cut to `top` entries with a count above zero:
+    substitutions [(target id, predicted id, count)], deletions [(target id, count)], insertions [(predicted id, count)]."""
+    substitutions: list
+    deletions: list
+    insertions: list
+
+
+def token_confusions(alignment, seqs, targets, vocab_size, top=20):
+    """Which symbols the errors of an alignment involve -> TokenConfusions.  alignment: the ops.EditAlignment of seqs (N, T) against targets -
+    the padded (N, L) tensor the alignment was made with, or the list of 1-D tensors symbol_error_breakdown took (group 1).  The counts are
+    formed on the device (torch.bincount over the alignment's indices) and read once.  Ids must lie in [0, vocab_size): ValueError otherwise
+    (checked on the rows' aligned positions, with the same read); the substitution table has vocab_size^2 bins."""
+    V, top = int(vocab_size), int(top)
+    if V < 1 or top < 1:
+        raise ValueError(f"token_confusions: vocab_size and top must be positive, got {vocab_size!r} and {top!r}")
+    dev = alignment.pred_op.device
+    if not isinstance(targets, torch.Tensor):
+        targets, _ = _pad_targets(targets, None, dev)
+    seqs, targets = seqs.to(dev), targets.to(dev)
+    if alignment.pred_op.shape != seqs.shape or alignment.tgt_to_pred.shape != targets.shape:
+        raise ValueError(f"token_confusions: alignment of widths {tuple(alignment.pred_op.shape)} / {tuple(alignment.tgt_to_pred.shape)} against "
+                         f"seqs {tuple(seqs.shape)} and targets {tuple(targets.shape)}")
+    op = alignment.pred_op
+    sub, ins = op == 1, op == 2
+    dele = (alignment.tgt_to_pred < 0) & (alignment.tgt_slot >= 0)
+    if targets.shape[1]:
+        partner = targets.gather(1, alignment.pred_to_tgt.clamp(min=0).long())
+    else:
+        partner = torch.zeros_like(seqs)
+    bad = ((sub | ins) & ((seqs < 0) | (seqs >= V))).any() | (sub & ((partner < 0) | (partner >= V))).any() | (dele & ((targets < 0) | (targets >= V))).any()
+    p, t, d = seqs.clamp(0, V - 1), partner.clamp(0, V - 1), targets.clamp(0, V - 1)
+    # entries that are not of the kind go to one bin past the table
+    sub_counts = torch.bincount(torch.where(sub, t * V + p, V * V).flatten(), minlength=V * V + 1)[:V * V]
+    ins_counts = torch.bincount(torch.where(ins, p, V).flatten(), minlength=V + 1)[:V]
+    del_counts = torch.bincount(torch.where(dele, d, V).flatten(), minlength=V + 1)[:V]
+    parts = []
+    for counts in (sub_counts, del_counts, ins_counts):
+        c, idx = torch.sort(counts, descending=True, stable=True)   # (stable: equal counts keep the smaller id first)
+        k = min(top, c.shape[0])
+        parts += [c[:k], idx[:k]]
+    host = torch.cat(parts + [bad.reshape(1).to(torch.int64)]).tolist()
+    if host[-1]:
+        raise ValueError(f"token_confusions: a token id outside [0, {V}) takes part in an error")
+    out, o = [], 0
+    for part in parts[::2]:
+        k = part.shape[0]
+        out.append([(i, c) for c, i in zip(host[o:o + k], host[o + k:o + 2 * k]) if c > 0])
+        o += 2 * k
+    return TokenConfusions([(i // V, i % V, c) for i, c in out[0]], out[1], out[2])
+
+
+def error_token_weights(alignment, pred_lens):
+    """The per-token weight of ViTOMR.error_maps from an ops.EditAlignment of decoded rows (B, T') against their targets -> fp32 (B, T'):
+    w[i] = [pred_op[i] != 0] + the number of deleted target tokens whose tgt_slot, clamped to [1, L - 1], is i, with L = pred_lens (B,) the
+    rows' lengths.  A substituted or inserted token is charged where it stands; a missing one to the output position where it should have
+    been emitted - the token it is missing in front of, or the last one (<eos>) when it is missing at the end; never to index 0 (<bos>),
+    which no decode step produced.  Device arithmetic only."""
+    op = alignment.pred_op
+    w = (op > 0).to(torch.float32)
+    if op.shape[1] == 0 or alignment.tgt_slot.shape[1] == 0:
+        return w
+    deleted = (alignment.tgt_to_pred < 0) & (alignment.tgt_slot >= 0)
+    last = (pred_lens.to(op.device).long() - 1)[:, None]
+    pos = torch.minimum(alignment.tgt_slot.long().clamp(min=1), last).clamp(min=0, max=op.shape[1] - 1)
+    return w.scatter_add_(1, pos, deleted.to(torch.float32))
+
+
+def confidence_error_auroc(score, is_error, mask):
+    """How well a per-token score separates the aligned errors from the matches: the area under the ROC curve of `score` (any shape; higher =
+    more suspect: 1 - exp(log_prob), entropy, rank, ...) as a detector of is_error (bool, e.g. EditAlignment.pred_op != 0) over the tokens
+    that `mask` (bool) selects and whose score is not NaN - the probability that a random error scores above a random match, ties counting
+    half.  Rank-based (Mann-Whitney) on the device, tied scores given their average rank, in float64; one host read.  NaN when either class
+    is empty.  0.5 is chance; what trained checkpoints reach has not been measured."""
+    s = score.reshape(-1).to(torch.float64)
+    keep = mask.reshape(-1).to(s.device).bool() & ~torch.isnan(s)
+    pos = is_error.reshape(-1).to(s.device).bool() & keep
+    big = torch.finfo(torch.float64).max
+    s = torch.where(keep, s.clamp(max=big), torch.full_like(s, float("inf")))   # what is left out sorts behind every kept score
+    v, _ = torch.sort(s)
+    lo = torch.searchsorted(v, s, right=False)
+    hi = torch.searchsorted(v, s, right=True)
+    rank = (lo + hi + 1).to(torch.float64) * 0.5   # ranks lo + 1 .. hi share their mean
+    n_pos, n = pos.sum().to(torch.float64), keep.sum().to(torch.float64)
+    u = torch.where(pos, rank, torch.zeros_like(rank)).sum() - n_pos * (n_pos + 1) * 0.5
+    return (u / (n_pos * (n - n_pos))).item()
 
 
 def stepwise_cosine_anneal_with_warmup(optimizer, warmup_steps, total_epochs, final_lr, num_steps_per_epoch):

@@ -266,6 +266,29 @@ int acai_grpo_objective_bwd(const void *logits, int dtype, const int64_t *rollou
 int acai_edit_distance(const int64_t *pred, int ld_pred, const int32_t *pred_len, const int64_t *tgt, int ld_tgt, const int32_t *tgt_len, int R,
                        int group, int32_t *out, void *stream);
 
+/* The edit ALIGNMENT behind that distance (seqalign.hip): which pred tokens match, are substituted or inserted, which target tokens are deleted,
+ * and where.  Rows, lengths, `group`, the clamping of the lengths on the device, the 4096-token limit and the comparison of ids by their low
+ * 32 bits are acai_edit_distance's.  Outputs, all written by the launch (no atomics: the same bits on every run):
+ *   counts      [R][4]       int32: matches, substitutions, insertions, deletions (the last three add up to the distance);
+ *   pred_op     [R][ld_pred] int8:  0 match, 1 substitution, 2 insertion; -1 past the row's length;
+ *   pred_to_tgt [R][ld_pred] int32: the aligned target index; -1 for an insertion and past the length;
+ *   tgt_to_pred [R][ld_tgt]  int32: the aligned pred index; -1 for a deleted target token and past the length;
+ *   tgt_slot    [R][ld_tgt]  int32: pred tokens consumed before target token j on the path (non-decreasing in j; for a deleted token: the pred
+ *                                   index it is missing in front of, in [0, pred_len]); -1 past the length.
+ * The target-side outputs have one row per PRED row (group rows of them per target row).
+ * THE ALIGNMENT IS CANONICAL.  On the table D[i][j] (pred prefix i, target prefix j), start at (pred_len, tgt_len); at (i, j):
+ *   1. if i > 0, j > 0 and D[i-1][j-1] + [pred[i-1] != tgt[j-1]] == D[i][j]: step diagonally (match or substitution);
+ *   2. otherwise, if i > 0 and D[i-1][j] + 1 == D[i][j]: insertion (pred token i-1 is extra), i decreases;
+ *   3. otherwise: deletion (target token j-1 is missing), j decreases.
+ * workspace: device memory, 16-byte aligned, of at least acai_edit_align_workspace_bytes(ld_pred, ld_tgt, R) bytes (the direction words of the
+ * forward sweep: (min(ld) + 63) * ceil(2 W / 32) * 256 bytes per pair, W the strip width of max(ld); 0 for arguments acai_edit_align
+ * refuses).  Every pointer, R % group == 0, the widths and the workspace size are checked BEFORE the launch (-1).  One kernel launch, no host
+ * synchronisation, no allocation: capturable in a hipGraph. */
+size_t acai_edit_align_workspace_bytes(int ld_pred, int ld_tgt, int rows);
+int acai_edit_align(const int64_t *pred, int ld_pred, const int32_t *pred_len, const int64_t *tgt, int ld_tgt, const int32_t *tgt_len, int R,
+                    int group, int32_t *counts, int8_t *pred_op, int32_t *pred_to_tgt, int32_t *tgt_to_pred, int32_t *tgt_slot, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
 /* Fused multi-tensor AdamW: one launch steps every parameter tensor (reference: torch.optim.AdamW in acai_omr/train/pre_train.py:105 and
  * omr_teacher_force_train.py:207 over the param groups of acai_omr/models/models.py:761-781; the cosine/warm-up schedule of
  * acai_omr/utils/utils.py:204-222 only changes `lr`).  All tables live in DEVICE memory.  tensors[i]: fp32 parameter, gradient and the two
