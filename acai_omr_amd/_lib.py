@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip"]
+SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -80,6 +80,14 @@ class AcaiAugImage(Structure):
         (n, c_float) for n in ("noise_sigma", "fb", "fc", "pad_")] + [("w", c_float * AUG_MAX_TAPS)]
 
 
+PAGE_LANE_PIXELS, PAGE_WAVES, PAGE_MAX_W, PAGE_MAX_H = 4, 4, 16384, 65535   # acai_page_profile's layout (ACAI_PAGE_*): 4 pixels per lane, 4 waves per row
+
+
+class AcaiCropResize(Structure):
+    _fields_ = [("page", c_void_p), ("tmp_off", c_int64)] + [
+        (n, c_int32) for n in ("page_h", "page_w", "pitch", "in_u8", "x0", "y0", "w", "h", "OH", "OW", "top", "left", "ch", "cw", "row0", "pad_")]
+
+
 _SIGNATURES = {
     "acai_version": (c_int, []),
     "acai_last_error": (c_char_p, []),
@@ -99,6 +107,11 @@ _SIGNATURES = {
     "acai_augment_blur_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "acai_augment_warp": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "acai_augment_jitter_out": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "acai_page_profile": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "acai_page_systems": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p]),
+    "acai_crop_resize_to_patches": (c_int, [c_void_p, POINTER(AcaiCropResize), c_int, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_int,
+                                            c_void_p]),
     "acai_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "acai_attn_varlen_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_uint32, c_int, c_void_p]),

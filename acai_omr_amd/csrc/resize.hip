@@ -6,45 +6,9 @@
 // with aten's mixed float / double evaluation of the window bounds, so that a tap never falls on the other side of a boundary.
 // HBM-bound and tiny next to the encoder (one 512 x 2048 output reads ~4-40 MB): one thread per output sample, threads along x.
 #include "common.h"
+#include "resize_taps.h"
 
 namespace {
-
-struct Axis {
-    float scale, support, invscale;
-    int in_size, max_taps;
-};
-
-__device__ __forceinline__ float cubic_aa(float x) {
-    const float a = -0.5f;
-    x = fabsf(x);
-    if (x < 1.f) return ((a + 2.f) * x - (a + 3.f)) * x * x + 1.f;
-    if (x < 2.f) return (((x - 5.f) * x + 8.f) * x - 4.f) * a;
-    return 0.f;
-}
-
-__device__ __forceinline__ void window(const Axis &ax, int i, int &xmin, int &xsize, float &center) {
-    center = (float)((double)ax.scale * ((double)i + 0.5));
-    const long long lo = (long long)((double)(center - ax.support) + 0.5);
-    const long long hi = (long long)((double)(center + ax.support) + 0.5);
-    xmin = (int)(lo > 0 ? lo : 0);
-    int n = (int)(hi < ax.in_size ? hi : ax.in_size) - xmin;
-    xsize = n < 0 ? 0 : (n > ax.max_taps ? ax.max_taps : n);
-}
-
-__device__ __forceinline__ float tap_weight(const Axis &ax, int j, int xmin, float center) {
-    return cubic_aa((float)(((double)((float)(j + xmin) - center) + 0.5) * (double)ax.invscale));
-}
-
-// Where the height pass puts its samples when it feeds the encoder directly ("direct packing into the token stream"): the
-// crop window (DynamicResize's centre crop to the positional grid) of the resized image goes out as nn.Unfold(P, P) rows - sample (y, x) of
-// the window -> row row0 + (y / P) (cw / P) + x / P, column (y % P) P + x % P - in fp32 or bf16: no image tensor, no patchify launch, no cast.
-struct PatchOut {
-    void *base;
-    int ld, row0, P, top, left, ch, cw, bf16;
-};
-
-__device__ __forceinline__ float in_sample(const float *p) { return *p; }
-__device__ __forceinline__ float in_sample(const unsigned char *p) { return (float)*p / 255.0f; }   // v2.ToDtype(torch.float32, scale=True) of a uint8 image
 
 // VERTICAL = false: in [rows = C*H][W] -> out [rows][OW] along x;  VERTICAL = true: in [C][H][OW] -> out [C][OH][OW] along y
 template <bool VERTICAL, typename TI = float, bool PATCHES = false>
@@ -85,16 +49,6 @@ __global__ __launch_bounds__(256) void resize_axis_kernel(const TI *__restrict__
         out[((size_t)blockIdx.z * out_size + i) * width + x] = t;
     else
         out[(size_t)blockIdx.y * out_size + x] = t;
-}
-
-Axis make_axis(int in_size, int out_size) {
-    Axis a;
-    a.scale = (float)in_size / (float)out_size;
-    a.support = a.scale >= 1.f ? 2.f * a.scale : 2.f;
-    a.invscale = a.scale >= 1.f ? 1.f / a.scale : 1.f;
-    a.in_size = in_size;
-    a.max_taps = (int)ceilf(a.support) * 2 + 1;
-    return a;
 }
 
 }  // namespace

@@ -11,6 +11,7 @@ from torch.amp import autocast
 from ..config import (ENCODER_FINE_TUNE_DEPTH, LMX_VOCAB_PATH, MAX_LMX_SEQ_LEN, NUM_DECODER_LAYERS, PATCH_SIZE, PE_MAX_HEIGHT, PE_MAX_WIDTH,
                       InferenceEvent)
 from ..models.models import FineTuneOMREncoder, OMRDecoder, ScheduledSamplingViTOMR, ViTOMR
+from ..utils import PackedPatches
 
 logger = logging.getLogger(__name__)
 
@@ -181,11 +182,11 @@ def diagnosed_inference(vitomr: ViTOMR, img, target_lmx_seqs, device, max_infere
 
 def _encode_chunks(vitomr, imgs, device):
     """Encoder (fp32, outside autocast) and transition head (inside autocast) over chunks of at most max_batch_size images; the packed
-    memories of all chunks, concatenated, and their lengths."""
+    memories of all chunks, concatenated, and their lengths.  imgs: a list of image tensors, or a `utils.PackedPatches`."""
     chunk = vitomr.decoder.decoder_blocks.max_batch_size if hasattr(vitomr.decoder.decoder_blocks, "max_batch_size") else len(imgs)
     mems, lens = [], []
     for c0 in range(0, len(imgs), chunk):
-        lat32, _, ln = _encode(vitomr, imgs[c0:c0 + chunk])
+        lat32, _, ln = _encode(vitomr, imgs.slice(c0, c0 + chunk) if isinstance(imgs, PackedPatches) else imgs[c0:c0 + chunk])
         with autocast(device_type=device, dtype=torch.bfloat16):
             mems.append(vitomr.transition_head.forward_packed(lat32))
         lens += ln
@@ -226,6 +227,43 @@ def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, s
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
             return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
+
+
+def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None):
+    """Whole pages in, their systems decoded as one batch (an extension; the reference's service crops hand-drawn boxes with PIL and decodes
+    them one by one, acai_omr/ui/routes.py:93-129) -> a `page.PageResult`.
+    pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1].  boxes: None - the systems are found on the device
+    (page.detect_systems with the `page.DetectConfig` detect; it assumes roughly level staff lines, and how well it does on real scans has
+    not been measured) - or, per page, a list of pixel boxes (x0, y0, x1, y1) or of the UI's fraction boxes (dicts, or tuples holding
+    floats: page.boxes_from_fractions); for one page the list may be given bare.  resize: the `utils.DynamicResize` every box goes through.
+    All systems of all pages are cut out and resized into one packed patch stream by one launch pair (page.split_pages), encoded in chunks
+    of the cache's batch size and decoded by continuous batching: the rows are what continuous_inference returns for the resized crops, in
+    page order and top to bottom.  max_inference_len, slots, grammar: as in continuous_inference.  A page without systems contributes no
+    rows; with no system at all nothing is launched and the result is empty."""
+    from .. import page as pg
+    pages, boxes = pg._page_lists(pages, boxes)
+    if boxes is not None and len(boxes) != len(pages):
+        raise ValueError(f"{len(pages)} pages but boxes for {len(boxes)}")
+    pages = [pg._device_page(p, resize.device) for p in pages]
+    if boxes is None:
+        per_page = [pg.detect_systems(p, detect) for p in pages]
+    else:
+        per_page = [pg.boxes_from_fractions(b, *p.shape) if b and pg._is_fraction_box(b[0]) else [pg._pixel_box(x, *p.shape) for x in b]
+                    for p, b in zip(pages, boxes)]
+    plans = pg.plan_systems([tuple(p.shape) for p in pages], per_page, resize)
+    system_page, sizes, windows = [p for p, *_ in plans], [s for _, _, s, _ in plans], [c for *_, c in plans]
+    dec = vitomr.decoder
+    specials = [getattr(dec, n) for n in ("bos_idx", "eos_idx", "pad_idx") if hasattr(dec, n)]
+    if not plans:
+        return pg.PageResult(per_page, None, None, None, [], [], [], specials)
+    vitomr.eval()
+    with torch.no_grad():
+        packed = pg.split_pages(pages, per_page, resize)
+        mem, lens = _encode_chunks(vitomr, packed, device)
+        bf = mem.dtype == torch.bfloat16
+        with autocast(device_type=device, dtype=torch.bfloat16):
+            seqs, lps, mask = vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
+    return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials)
 
 
 def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None, *, grammar=None):

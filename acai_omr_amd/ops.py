@@ -252,6 +252,89 @@ def resize_to_patches(img, size, P, out, row0, crop=None, clamp01=False):
     return n
 
 
+# ---- whole pages (csrc/page.hip) --------------------------------------------------------------------------------------------------------
+def _page(page):
+    """A page operand: one channel, uint8 or fp32, (H, W) or (1, H, W) on the GPU, rows `pitch` elements apart (a column slice of a wider
+    tensor is taken as it is).  Returns (2-D view, H, W, pitch, in_u8)."""
+    if not torch.is_tensor(page):
+        raise TypeError("page: expected a tensor")
+    _chk(page, "page")
+    if page.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"page: expected uint8 or float32, got {page.dtype}")
+    if page.dim() == 3 and page.shape[0] == 1:
+        page = page[0]
+    if page.dim() != 2 or page.shape[0] < 1 or page.shape[1] < 1:
+        raise ValueError("page: expected one channel, (H, W) or (1, H, W), not empty")
+    H, W = page.shape
+    pitch = page.stride(0) if H > 1 else W
+    if pitch < W:
+        raise ValueError("page: rows overlap (row stride below the width)")
+    return page, H, W, pitch, 1 if page.dtype == torch.uint8 else 0
+
+
+@_on_operand_device
+def page_profile(page, ink_threshold=0.5):
+    """Row profiles of a page -> (ink, run), int32 [H] each: the number of pixels below ink_threshold in each row and the longest run of
+    consecutive such pixels (uint8 pages are read as p / 255).  W <= 16384, H <= 65535."""
+    page, H, W, pitch, u8 = _page(page)
+    out = torch.empty(2, H, dtype=torch.int32, device=page.device)
+    _lib.check(_lib.lib().acai_page_profile(page.data_ptr(), u8, H, W, pitch, float(ink_threshold), out[0].data_ptr(), out[1].data_ptr(), _st(page)),
+               "acai_page_profile")
+    return out[0], out[1]
+
+
+@_on_operand_device
+def page_systems(page, ink, run, ink_threshold, min_ink, merge_gap, min_height, line_len, min_line_rows, margin, max_systems, out=None):
+    """The profiles of `page_profile` -> (count int32 [1], boxes int32 [max_systems, 4]) on the device: bands of inked rows
+    (ink >= min_ink, gaps of at most merge_gap rows bridged) that are at least min_height tall and hold at least min_line_rows rows with
+    run >= line_len, as boxes (x0, y0, x1, y1) around their ink grown by margin and clipped to the page, top to bottom.  count may exceed
+    max_systems; box rows from min(count, max_systems) on are left as they are.  Both are views of one int32 buffer (`out`, 4 + 4
+    max_systems elements, allocated when None), so one copy brings both to the host."""
+    page, H, W, pitch, u8 = _page(page)
+    _chk(ink, "ink", torch.int32), _chk(run, "run", torch.int32)
+    if tuple(ink.shape) != (H,) or tuple(run.shape) != (H,) or ink.device != page.device or run.device != page.device:
+        raise ValueError(f"ink / run: expected int32 [{H}] on the page's device")
+    n = int(max_systems)
+    if out is None:
+        out = torch.empty(4 + 4 * max(n, 0), dtype=torch.int32, device=page.device)
+    _chk(out, "out", torch.int32)
+    if out.dim() != 1 or out.numel() < 4 + 4 * n or out.device != page.device:
+        raise ValueError(f"out: expected at least {4 + 4 * n} int32 on the page's device")
+    count, boxes = out[:1], out[4:4 + 4 * n].view(n, 4)
+    _lib.check(_lib.lib().acai_page_systems(page.data_ptr(), u8, H, W, pitch, float(ink_threshold), ink.data_ptr(), run.data_ptr(), int(min_ink),
+                                            int(merge_gap), int(min_height), int(line_len), int(min_line_rows), int(margin), n, count.data_ptr(),
+                                            boxes.data_ptr(), _st(page)), "acai_page_systems")
+    return count, boxes
+
+
+def crop_resize_entry(page, box, size, crop, row0, tmp_off):
+    """One `_lib.AcaiCropResize`: `box` = (x0, y0, w, h) of `page` (a GPU tensor as `page_profile` takes it) resized to `size` = (OH, OW), of
+    which the window `crop` = (top, left, ch, cw) goes to the patch rows from row0; tmp_off: its offset into the width-pass scratch."""
+    page, H, W, pitch, u8 = _page(page)
+    x0, y0, w, h = (int(v) for v in box)
+    top, left, ch, cw = (int(v) for v in crop)
+    return _lib.AcaiCropResize(page.data_ptr(), int(tmp_off), H, W, pitch, u8, x0, y0, w, h, int(size[0]), int(size[1]), top, left, ch, cw, int(row0), 0)
+
+
+@_on_operand_device
+def crop_resize_to_patches(entries, out, P, clamp01=False):
+    """A list of `crop_resize_entry` -> their nn.Unfold(P, P) rows in the packed patch stream `out` [rows, P*P] (fp32 or bf16) in two
+    launches, whatever the number of entries: every box is cut from its page, resized (bicubic, antialiased, taps clamped to the box) and
+    cropped to its window exactly as `resize_to_patches` does it for a contiguous copy of the box - the same bits.  The pages must stay alive
+    until the call returns (the entries hold raw pointers) and lie on `out`'s device.  One table upload, one scratch allocation."""
+    _chk(out, "out")
+    if out.dim() != 2 or out.shape[1] != P * P or out.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"out: expected [rows, {P * P}] fp32 or bf16, got {tuple(out.shape)} {out.dtype}")
+    if not entries:
+        raise ValueError("crop_resize_to_patches: no entries")
+    host = (_lib.AcaiCropResize * len(entries))(*entries)
+    tmp_elems = max(e.tmp_off + e.h * e.OW for e in entries)
+    table = h2d(torch.frombuffer(memoryview(host).cast("B"), dtype=torch.uint8), out.device)
+    tmp = torch.empty(max(int(tmp_elems), 1), dtype=torch.float32, device=out.device)
+    _lib.check(_lib.lib().acai_crop_resize_to_patches(table.data_ptr(), host, len(entries), tmp.data_ptr(), int(tmp_elems), out.data_ptr(), _ld(out),
+                                                      out.shape[0], int(P), _dt(out), int(bool(clamp01)), _st(out)), "acai_crop_resize_to_patches")
+
+
 # ---- camera augmentation (csrc/augment.hip) ---------------------------------------------------------------------------------------------
 def augment_table(entries, device):
     """A list of `_lib.AcaiAugImage` -> the read-only descriptor table in device memory (a uint8 tensor): the one upload of a call."""

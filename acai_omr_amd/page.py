@@ -1,0 +1,233 @@
+"""Whole-page input (an extension): from a photographed or scanned page to the staff systems the model reads.
+
+The reference's service has its user draw a box around every system of an uploaded page, crops each box with PIL, runs
+`base_img_transform` on each crop, decodes the crops one after another at batch size 1, joins the sequences with " " and reports one
+average confidence (acai_omr/ui/routes.py: `setup_inference` :108-129, `multiple_img_stream_inference_wrapper` :93-104, `prepare_results`
+:172-192).  This module is the host edge of doing the same on the device for all systems of all pages at once:
+
+  * `boxes_from_fractions`  the UI's payload (fractions of the page) -> pixel boxes, rounded as PIL's `Image.crop` rounds them;
+  * `detect_systems`        no boxes drawn: row profiles -> bands of inked rows -> the bands that hold staff lines (ops.page_profile,
+                            ops.page_systems; the reference has no detector);
+  * `split_pages`           every box of every page cut out, resized as `DynamicResize` resizes the crop and written into ONE
+                            `PackedPatches` by one launch pair (ops.crop_resize_to_patches) - no crop copies, no per-system launches;
+  * `PageResult`            the per-system rows of the decode, joined per page as the service joins them.
+
+`inference.vitomr_inference.page_inference` strings them together.  There is no CPU fallback.
+
+The detection rule assumes roughly LEVEL staff lines: a staff line must show up as a long horizontal run within single pixel rows, so a
+page rotated by more than about one line thickness over `line_frac` of its width (a skewed phone photo) loses its line rows and its systems
+with them.  How well the rule does on real scans and photos has not been measured (no such data here); explicit boxes remain the fallback.
+"""
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from .utils import PackedPatches, stringify_lmx_seq
+
+NO_GPU = "acai_omr_amd page input runs on the GPU (HIP page kernels); there is no CPU fallback"
+
+
+@dataclass
+class DetectConfig:
+    """Parameters of `detect_systems`.  A field left at None is sized from the page (H rows, W columns) when the page is seen, in proportion
+    to an engraved A4 / letter page, whose staff is about H / 45 tall with H / 180 between its lines and at least H / 30 of white between
+    systems:
+
+      ink_threshold  a pixel is ink if its value (uint8 / 255) is below this;
+      min_ink        a row is inked if it holds at least this many ink pixels            default max(1, W // 500): a speck of dust is not ink;
+      merge_gap      inked rows at most this many rows apart belong to one band          default max(1, H // 200): under the white between
+                                                                                         systems, over anything inside a staff;
+      min_height     a band must be at least this tall                                   default max(1, H // 90): half a staff;
+      line_frac      a line row holds an ink run of at least ceil(line_frac * W) pixels (a staff line; text and dashes do not reach it);
+      min_line_rows  a band must hold at least this many line rows (five lines of a staff, each at least one row thick);
+      margin         the box is the band's ink grown by this much on every side          default max(1, H // 100);
+      max_systems    capacity of the device-side box list; more kept bands than this is an error."""
+    ink_threshold: float = 0.5
+    min_ink: Optional[int] = None
+    merge_gap: Optional[int] = None
+    min_height: Optional[int] = None
+    line_frac: float = 0.5
+    min_line_rows: int = 5
+    margin: Optional[int] = None
+    max_systems: int = 64
+
+    def resolved(self, H, W):
+        """(min_ink, merge_gap, min_height, line_len, margin) for an H x W page."""
+        pick = lambda v, d: int(d if v is None else v)   # noqa: E731
+        return (pick(self.min_ink, max(1, W // 500)), pick(self.merge_gap, max(1, H // 200)), pick(self.min_height, max(1, H // 90)),
+                int(math.ceil(self.line_frac * W)), pick(self.margin, max(1, H // 100)))
+
+
+def _device_page(page, device=None):
+    """One page -> a (H, W) uint8 / fp32 GPU tensor (a CPU tensor is uploaded once; other float types are widened to fp32)."""
+    if not torch.is_tensor(page) or page.dim() not in (2, 3) or (page.dim() == 3 and page.shape[0] != 1):
+        raise TypeError("expected a page as a (H,W) or (1,H,W) tensor")
+    if not torch.cuda.is_available():
+        raise RuntimeError(NO_GPU)
+    if page.dim() == 3:
+        page = page[0]
+    if not page.is_cuda:
+        page = page.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+    if page.dtype != torch.uint8:
+        page = page.to(torch.float32)
+    return page if page.stride(-1) == 1 and (page.shape[0] == 1 or page.stride(0) >= page.shape[1]) else page.contiguous()
+
+
+def detect_systems(page, cfg=None):
+    """The staff systems of one page -> [(x0, y0, x1, y1), ...] in pixels, top to bottom; an empty page gives [].  Three launches and ONE
+    device-to-host copy (the count and the boxes together).  More than cfg.max_systems systems: ValueError."""
+    from . import ops
+    cfg = cfg or DetectConfig()
+    page = _device_page(page)
+    H, W = page.shape
+    min_ink, merge_gap, min_height, line_len, margin = cfg.resolved(H, W)
+    ink, run = ops.page_profile(page, cfg.ink_threshold)
+    out = torch.empty(4 + 4 * cfg.max_systems, dtype=torch.int32, device=page.device)
+    ops.page_systems(page, ink, run, cfg.ink_threshold, min_ink, merge_gap, min_height, line_len, cfg.min_line_rows, margin, cfg.max_systems, out=out)
+    host = out.cpu()
+    count = int(host[0])
+    if count > cfg.max_systems:
+        raise ValueError(f"the page has {count} systems, more than max_systems = {cfg.max_systems}")
+    return [tuple(int(v) for v in b) for b in host[4:4 + 4 * count].view(count, 4).tolist()]
+
+
+def _pixel_box(box, H, W):
+    x0, y0, x1, y1 = (int(v) for v in box)
+    if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+        raise ValueError(f"box {(x0, y0, x1, y1)} is empty or outside the {H} x {W} page")
+    return x0, y0, x1, y1
+
+
+def boxes_from_fractions(boxes, H, W):
+    """The UI's boxes - dicts with x0, y0, x1, y1 or 4-tuples in that order, as fractions of the page - sorted by y0 (routes.py:122) -> pixel
+    boxes.  Every coordinate is int(round(fraction * size)) with Python's rounding (ties to even), which is what PIL's `Image.crop` makes of
+    the float box routes.py:126 hands it.  A box that comes out empty or outside the page: ValueError."""
+    rows = [tuple(float(b[k]) for k in ("x0", "y0", "x1", "y1")) if isinstance(b, dict) else tuple(float(v) for v in b) for b in boxes]
+    if any(len(r) != 4 for r in rows):
+        raise ValueError("a box is x0, y0, x1, y1")
+    return [_pixel_box((int(round(x0 * W)), int(round(y0 * H)), int(round(x1 * W)), int(round(y1 * H))), H, W)
+            for x0, y0, x1, y1 in sorted(rows, key=lambda r: r[1])]
+
+
+def _is_fraction_box(b):
+    return isinstance(b, dict) or any(isinstance(v, float) for v in b)
+
+
+def _is_box(b):
+    return isinstance(b, dict) or (isinstance(b, (list, tuple)) and len(b) == 4 and not isinstance(b[0], (list, tuple, dict)))
+
+
+def _page_lists(pages, boxes):
+    """One page (with its boxes as one list) or a list of pages (with one list of boxes per page) -> the list form of both."""
+    if torch.is_tensor(pages):
+        pages = [pages]
+        if boxes is not None and (len(boxes) == 0 or _is_box(boxes[0])):
+            boxes = [boxes]
+    return list(pages), boxes
+
+
+def plan_systems(pages_hw, boxes_per_page, resize):
+    """[(page, (x0, y0, x1, y1), (OH, OW), (top, left, ch, cw)), ...] in page order, then in the order given: `resize._plan` of every box."""
+    plans = []
+    for p, ((H, W), boxes) in enumerate(zip(pages_hw, boxes_per_page)):
+        for b in boxes:
+            x0, y0, x1, y1 = _pixel_box(b, H, W)
+            size, crop = resize._plan(y1 - y0, x1 - x0)
+            plans.append((p, (x0, y0, x1, y1), size, crop))
+    return plans
+
+
+def split_pages(pages, boxes_per_page, resize, dtype=torch.float32):
+    """`resize.to_patches` of every box of every page without cutting the boxes out first: pages = one page or a list (uint8, or float in
+    [0, 1]), boxes_per_page = one list of pixel boxes (x0, y0, x1, y1) per page -> a `PackedPatches` with one image per box, in page order
+    and then in the order given; its rows are, bit for bit, those of `resize.to_patches([page[y0:y1, x0:x1], ...])`.  One table upload and
+    one `ops.crop_resize_to_patches` call (two launches) for everything."""
+    from . import ops
+    pages, boxes_per_page = _page_lists(pages, boxes_per_page)
+    if len(pages) != len(boxes_per_page):
+        raise ValueError(f"{len(pages)} pages but boxes for {len(boxes_per_page)}")
+    pages = [_device_page(p, resize.device) for p in pages]
+    plans = plan_systems([tuple(p.shape) for p in pages], boxes_per_page, resize)
+    if not plans:
+        raise ValueError("split_pages: no boxes")
+    P = resize.patch_size
+    dims = [(crop[2] // P, crop[3] // P) for _, _, _, crop in plans]
+    out = torch.empty(sum(h * w for h, w in dims), P * P, dtype=dtype, device=pages[0].device)
+    entries, row0, tmp_off = [], 0, 0
+    for (p, (x0, y0, x1, y1), size, crop), (hp, wp) in zip(plans, dims):
+        entries.append(ops.crop_resize_entry(pages[p], (x0, y0, x1 - x0, y1 - y0), size, crop, row0, tmp_off))
+        row0 += hp * wp
+        tmp_off += (y1 - y0) * size[1]
+    ops.crop_resize_to_patches(entries, out, P, clamp01=True)
+    return PackedPatches(out, dims, P)
+
+
+class PageResult:
+    """What `page_inference` returns.  Rows are systems, in page order and top to bottom within a page:
+
+      boxes        per page, its list of pixel boxes (x0, y0, x1, y1);
+      seqs, log_probs, seq_mask   (N, T') as `continuous_inference` returns them, one row per system (None when there is no system at all);
+      system_page  the page index of every row;
+      sizes, windows   per row, the size (OH, OW) its box was resized to and the window (top, left, ch, cw) of it the model saw."""
+
+    def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=()):
+        self.boxes, self.seqs, self.log_probs, self.seq_mask = boxes, seqs, log_probs, seq_mask
+        self.system_page, self.sizes, self.windows = list(system_page), list(sizes), list(windows)
+        self.specials = tuple(specials)   # the ids of <bos>, <eos>, <pad>: what tokens() leaves out
+        self._flat = [b for page in boxes for b in page]
+
+    def __len__(self):
+        return len(self.system_page)
+
+    def _rows(self, page):
+        return [i for i, p in enumerate(self.system_page) if p == page]
+
+    def tokens(self):
+        """Per page, the tokens of its systems joined in reading order, without <bos>, <eos> and <pad>: a list of 1-D int64 tensors."""
+        out = []
+        for p in range(len(self.boxes)):
+            parts = []
+            for i in self._rows(p):
+                t = self.seqs[i][self.seq_mask[i]]
+                for s in self.specials:
+                    t = t[t != s]
+                parts.append(t)
+            out.append(torch.cat(parts) if parts else torch.empty(0, dtype=torch.int64))
+        return out
+
+    def lmx(self, idxs_to_tokens):
+        """Per page, `stringify_lmx_seq` of every system's row joined with " ", as the service joins them (routes.py:74-80, :179)."""
+        return [" ".join(stringify_lmx_seq(self.seqs[i][self.seq_mask[i]], idxs_to_tokens) for i in self._rows(p)) for p in range(len(self.boxes))]
+
+    @property
+    def avg_log_probs(self):
+        """Per system, sum(log_probs[mask]) / mask.sum(): the service's avgLogProb (routes.py:83).  fp32 (N,)."""
+        if not len(self):
+            return torch.empty(0)
+        m = self.seq_mask
+        return (self.log_probs * m).sum(1) / m.sum(1)
+
+    @property
+    def avg_confidence(self):
+        """Per page, exp(mean of its systems' avg_log_probs): the service's avgConfidence (routes.py:190).  A page without systems: nan."""
+        a = self.avg_log_probs
+        return [math.exp(float(a[rows].mean())) if rows else float("nan") for rows in (self._rows(p) for p in range(len(self.boxes)))]
+
+    def _affine(self, system):
+        x0, y0, x1, y1 = self._flat[system]
+        (OH, OW), (top, left, _, _) = self.sizes[system], self.windows[system]
+        return x0, y0, (x1 - x0) / OW, (y1 - y0) / OH, top, left
+
+    def to_page_xy(self, system, x, y):
+        """Pixel (x, y) of the tensor the model saw of `system` (its box resized, then cropped to the window) -> page pixels (floats): the
+        resize's own map, source = (resized + 0.5) * scale - 0.5 per axis (align_corners = False), shifted by the window and the box.  With
+        it a `TokenAlignment` of the system can be drawn on the page."""
+        x0, y0, sx, sy, top, left = self._affine(system)
+        return x0 + (x + left + 0.5) * sx - 0.5, y0 + (y + top + 0.5) * sy - 0.5
+
+    def from_page_xy(self, system, px, py):
+        """The inverse of `to_page_xy`."""
+        x0, y0, sx, sy, top, left = self._affine(system)
+        return (px - x0 + 0.5) / sx - 0.5 - left, (py - y0 + 0.5) / sy - 0.5 - top

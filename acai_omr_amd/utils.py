@@ -247,6 +247,12 @@ class PackedPatches:
     def __len__(self):
         return len(self.dims)
 
+    def slice(self, i0, i1):
+        """Images i0 .. i1 - 1 as a `PackedPatches` over a view of the same rows (what a chunked encode takes one chunk at a time)."""
+        i0, i1 = max(0, min(int(i0), len(self.dims))), max(0, min(int(i1), len(self.dims)))
+        r0 = sum(h * w for h, w in self.dims[:i0])
+        return PackedPatches(self.patches[r0:r0 + sum(h * w for h, w in self.dims[i0:i1])], self.dims[i0:i1], self.patch_size)
+
 
 class PatchDivisibleResize(torch.nn.Module):
     """`PatchDivisibleResize` (acai_omr/utils/utils.py:309-330): resize to the nearest lower patch-divisible size, bicubic + antialias, on the GPU.

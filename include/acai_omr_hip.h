@@ -676,6 +676,55 @@ int acai_augment_warp(const AcaiAugImage *table, int n_images, int max_h, int ma
 int acai_augment_jitter_out(const AcaiAugImage *table, int n_images, int max_h, int max_w, int in_slot, int do_jitter, void *patches,
                             int ld, int P, int out_dtype, void *stream);
 
+/* ---- whole pages: find the staff systems, cut them out, resize them into the patch stream ----------------------------------------------
+ * The reference's service takes a page and hand-drawn boxes, crops each with PIL and transforms and decodes the crops one by one
+ * (acai_omr/ui/routes.py:93-129, `setup_inference` / `multiple_img_stream_inference_wrapper`).  The three entry points below are the device
+ * side of doing that for all systems of all pages at once, and of finding the boxes when none are drawn (an extension: the reference has no
+ * detector; its tests import a `SystemDetectionDataset` that was never written).  A page is one channel, fp32 in [0, 1] or uint8 (in_u8 = 1,
+ * read as (float)p / 255 like acai_resize_to_patches), [H][pitch] with pitch >= W in elements.  Integer outputs are exact and do not depend
+ * on the launch order: no atomics. */
+#define ACAI_PAGE_LANE_PIXELS 4   /* acai_page_profile: consecutive pixels per lane, 64 lanes = 256 pixels per wave step ... */
+#define ACAI_PAGE_WAVES 4         /* ... and each of a row's 4 waves owns one contiguous span of ceil(ceil(W / 4) / 256) * 256 pixels */
+#define ACAI_PAGE_MAX_W 16384
+#define ACAI_PAGE_MAX_H 65535
+
+/* Row profiles: ink[y] = number of pixels of row y with value < ink_threshold, run[y] = the longest run of consecutive such pixels
+ * (staff lines are the long runs).  One workgroup per row; W <= ACAI_PAGE_MAX_W, H <= ACAI_PAGE_MAX_H. */
+int acai_page_profile(const void *page, int in_u8, int H, int W, int pitch, float ink_threshold, int32_t *ink, int32_t *run, void *stream);
+
+/* The profiles -> system boxes, in two launches with no host step between them.  A row is inked if ink[y] >= min_ink (>= 1).  A band is a
+ * maximal set of inked rows in which consecutive inked rows are separated by at most merge_gap other rows, [y0, y1) from its first inked
+ * row to one past its last.  It is kept if y1 - y0 >= min_height and at least min_line_rows of its rows have run[y] >= line_len.  Of a
+ * kept band, x0 / x1 are the leftmost / one past the rightmost column with a pixel < ink_threshold in rows [y0, y1) (a second read of the
+ * page, of the kept bands only), and its box is (max(x0 - margin, 0), max(y0 - margin, 0), min(x1 + margin, W), min(y1 + margin, H)).
+ * count[0] = the number of kept bands (may exceed max_systems); boxes [max_systems][4] = the first max_systems of them, top to bottom;
+ * rows of `boxes` from min(count, max_systems) on are not written. */
+int acai_page_systems(const void *page, int in_u8, int H, int W, int pitch, float ink_threshold, const int32_t *ink, const int32_t *run,
+                      int min_ink, int merge_gap, int min_height, int line_len, int min_line_rows, int margin, int max_systems,
+                      int32_t *count, int32_t *boxes, void *stream);
+
+/* One box to cut, resize and pack (acai_crop_resize_to_patches). */
+typedef struct AcaiCropResize {
+    const void *page;       /* the page the box lies in, [page_h][pitch] */
+    int64_t tmp_off;        /* where this entry's h x OW width-pass samples start in `tmp`, in floats */
+    int32_t page_h, page_w; /* only read on the host (the box must lie inside the page) */
+    int32_t pitch, in_u8;
+    int32_t x0, y0, w, h;   /* the source box */
+    int32_t OH, OW;         /* the size the box is resized to */
+    int32_t top, left, ch, cw; /* the window of the OH x OW result that is kept (multiples of P) */
+    int32_t row0, pad_;     /* first row of the patch stream */
+} AcaiCropResize;
+
+/* acai_resize_to_patches over a table of n boxes, each cut from its own page, in TWO launches whatever n is: the width pass of every box
+ * into `tmp`, then the height pass of every box into its rows of `patches` [patch_rows][ld >= P*P] (nn.Unfold order, out_dtype, clamp01).
+ * "Crop, then resize": a sample's taps are clamped to the BOX, so entry e gets, bit for bit, what acai_resize_to_patches writes for the
+ * contiguous copy of page[y0 : y0 + h, x0 : x0 + w] (the same window, weights and accumulation order: csrc/resize_taps.h).
+ * `table` is the device copy the kernels read; `host_table` holds the same n entries in host memory and is what is checked here: boxes
+ * inside their pages, windows inside (OH, OW) and multiples of P, rows inside `patches`, samples inside `tmp` (tmp_elems floats), and
+ * n, max h and max OH are grid dimensions (<= 65535). */
+int acai_crop_resize_to_patches(const AcaiCropResize *table, const AcaiCropResize *host_table, int n, float *tmp, int64_t tmp_elems,
+                                void *patches, int ld, int64_t patch_rows, int P, int out_dtype, int clamp01, void *stream);
+
 /* hipGraph helpers (capture on `stream`, replay). */
 int acai_graph_begin(void *stream);
 int acai_graph_end(void *stream, void **graph_exec_out);
