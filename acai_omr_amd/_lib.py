@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip"]
+SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -83,6 +83,12 @@ class AcaiAugImage(Structure):
 PAGE_LANE_PIXELS, PAGE_WAVES, PAGE_MAX_W, PAGE_MAX_H = 4, 4, 16384, 65535   # acai_page_profile's layout (ACAI_PAGE_*): 4 pixels per lane, 4 waves per row
 
 
+# csrc/deskew.hip (ACAI_STRIP_* / ACAI_SKEW_*): the strip kernel's tile (rows, 16-byte units), the row differences per workgroup of the score
+# kernel, the size of a slope table and the largest slope, round(tan(15 deg) * 65536).  The strip profile is uint8 [nS][H].
+STRIP_TILE_ROWS, STRIP_TILE_UNITS, SKEW_CHUNK, SKEW_MAX_SLOPES, SKEW_MAX_SLOPE = 64, 32, 1023, 1024, 17560
+STRIP_WIDTHS = (8, 16, 32, 64)
+
+
 class AcaiCropResize(Structure):
     _fields_ = [("page", c_void_p), ("tmp_off", c_int64)] + [
         (n, c_int32) for n in ("page_h", "page_w", "pitch", "in_u8", "x0", "y0", "w", "h", "OH", "OW", "top", "left", "ch", "cw", "row0", "pad_")]
@@ -112,6 +118,9 @@ _SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p]),
     "acai_crop_resize_to_patches": (c_int, [c_void_p, POINTER(AcaiCropResize), c_int, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_int,
                                             c_void_p]),
+    "acai_page_strips": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+    "acai_page_skew_scores": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_int32), c_int, c_void_p, c_void_p]),
+    "acai_page_rotate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
     "acai_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "acai_attn_varlen_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_uint32, c_int, c_void_p]),

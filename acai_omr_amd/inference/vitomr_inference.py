@@ -229,7 +229,7 @@ def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, s
             return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
 
 
-def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None):
+def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None, deskew=None):
     """Whole pages in, their systems decoded as one batch (an extension; the reference's service crops hand-drawn boxes with PIL and decodes
     them one by one, acai_omr/ui/routes.py:93-129) -> a `page.PageResult`.
     pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1].  boxes: None - the systems are found on the device
@@ -239,12 +239,22 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     All systems of all pages are cut out and resized into one packed patch stream by one launch pair (page.split_pages), encoded in chunks
     of the cache's batch size and decoded by continuous batching: the rows are what continuous_inference returns for the resized crops, in
     page order and top to bottom.  max_inference_len, slots, grammar: as in continuous_inference.  A page without systems contributes no
-    rows; with no system at all nothing is launched and the result is empty."""
+    rows; with no system at all nothing is launched and the result is empty.
+    deskew (an extension, default None = off: the path above, unchanged): True or a `page.SkewConfig` - every page's skew is estimated on
+    the device (page.estimate_skew) - or one angle in degrees, or a list with one per page.  The pages are turned level FIRST
+    (page.deskew_pages); detection then runs on the levelled pages, and boxes the caller supplies refer to the LEVELLED pages too (pixels
+    of, or fractions of, the page after the turn, which has the size of the page before it).  The result's boxes are in the levelled
+    pages, its `angles` says by how much each was turned, and `to_page_xy` / `box_corners` lead back to the pages as they were passed in."""
     from .. import page as pg
     pages, boxes = pg._page_lists(pages, boxes)
     if boxes is not None and len(boxes) != len(pages):
         raise ValueError(f"{len(pages)} pages but boxes for {len(boxes)}")
     pages = [pg._device_page(p, resize.device) for p in pages]
+    angles = None
+    if deskew is not None and deskew is not False:
+        estimate = deskew is True or isinstance(deskew, pg.SkewConfig)
+        pages, angles = pg.deskew_pages(pages, None if estimate else deskew, deskew if isinstance(deskew, pg.SkewConfig) else None)
+    turned = dict(angles=angles, page_sizes=[tuple(p.shape) for p in pages])
     if boxes is None:
         per_page = [pg.detect_systems(p, detect) for p in pages]
     else:
@@ -255,7 +265,7 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     dec = vitomr.decoder
     specials = [getattr(dec, n) for n in ("bos_idx", "eos_idx", "pad_idx") if hasattr(dec, n)]
     if not plans:
-        return pg.PageResult(per_page, None, None, None, [], [], [], specials)
+        return pg.PageResult(per_page, None, None, None, [], [], [], specials, **turned)
     vitomr.eval()
     with torch.no_grad():
         packed = pg.split_pages(pages, per_page, resize)
@@ -263,7 +273,7 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
             seqs, lps, mask = vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
-    return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials)
+    return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, **turned)
 
 
 def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None, *, grammar=None):

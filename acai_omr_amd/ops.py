@@ -335,6 +335,79 @@ def crop_resize_to_patches(entries, out, P, clamp01=False):
                                                       out.shape[0], int(P), _dt(out), int(bool(clamp01)), _st(out)), "acai_crop_resize_to_patches")
 
 
+# ---- page deskew (csrc/deskew.hip) ------------------------------------------------------------------------------------------------------
+def _strip(S):
+    if S not in _lib.STRIP_WIDTHS:
+        raise ValueError(f"strip width {S}: expected one of {_lib.STRIP_WIDTHS}")
+    return int(S)
+
+
+@_on_operand_device
+def page_strips(page, S=16, ink_threshold=0.5):
+    """Strip profile of a page (as `page_profile` takes it) -> uint8 [nS, H], nS = ceil(W / S): the number of pixels below ink_threshold of
+    row y in columns [s S, min((s + 1) S, W)), strip-major so that the rows of a strip are contiguous.  S in {8, 16, 32, 64}."""
+    S = _strip(S)
+    page, H, W, pitch, u8 = _page(page)
+    out = torch.empty(-(-W // S), H, dtype=torch.uint8, device=page.device)
+    _lib.check(_lib.lib().acai_page_strips(page.data_ptr(), u8, H, W, pitch, float(ink_threshold), S, out.data_ptr(), _st(page)), "acai_page_strips")
+    return out
+
+
+def skew_slope_table(slopes, device):
+    """Q16 slopes (Python ints, round(tan(angle) * 65536)) -> (device int32 [K], the ctypes host copy the C ABI checks): the one upload a
+    batch of `page_skew_scores` calls shares."""
+    slopes = [int(m) for m in slopes]
+    if not 1 <= len(slopes) <= _lib.SKEW_MAX_SLOPES or any(abs(m) > _lib.SKEW_MAX_SLOPE for m in slopes):
+        raise ValueError(f"skew slopes: expected 1 .. {_lib.SKEW_MAX_SLOPES} values within +-{_lib.SKEW_MAX_SLOPE} (tan 15 deg in Q16)")
+    return h2d(torch.tensor(slopes, dtype=torch.int32), device), (ctypes.c_int32 * len(slopes))(*slopes)
+
+
+@_on_operand_device
+def page_skew_scores(strips, W, S, slopes, out=None):
+    """`page_strips` of a page of width W at strip width S, and K Q16 slopes (a list of ints, or a `skew_slope_table`) -> int64 [K]: for
+    every slope the strip profile sheared along it, summed over the strips and scored by the sum of its squared row differences
+    (include/acai_omr_hip.h has the integer definition).  `out`: an int64 [K] to write into (a row of a larger tensor)."""
+    _chk(strips, "strips", torch.uint8)
+    S = _strip(S)
+    if strips.dim() != 2 or not strips.is_contiguous() or strips.shape[0] != -(-int(W) // S) or strips.shape[1] < 1:
+        raise ValueError(f"strips: expected a contiguous uint8 [ceil({W} / {S}), H], got {tuple(strips.shape)}")
+    table, host = slopes if isinstance(slopes, tuple) else skew_slope_table(slopes, strips.device)
+    _chk(table, "slopes", torch.int32)
+    K = len(host)
+    if table.dim() != 1 or table.numel() != K or table.device != strips.device:
+        raise ValueError(f"slopes: expected int32 [{K}] on the strips' device")
+    if out is None:
+        out = torch.empty(K, dtype=torch.int64, device=strips.device)
+    _chk(out, "out", torch.int64)
+    if tuple(out.shape) != (K,) or out.device != strips.device:
+        raise ValueError(f"out: expected int64 [{K}] on the strips' device")
+    _lib.check(_lib.lib().acai_page_skew_scores(strips.data_ptr(), strips.shape[1], int(W), S, table.data_ptr(), host, K, out.data_ptr(), _st(strips)),
+               "acai_page_skew_scores")
+    return out
+
+
+def rotation_q16(angle_deg):
+    """(cos_q, sin_q) = (round(cos * 65536), round(sin * 65536)) of an angle in degrees: what `page_rotate` turns by."""
+    a = math.radians(float(angle_deg))
+    return int(round(math.cos(a) * 65536.0)), int(round(math.sin(a) * 65536.0))
+
+
+@_on_operand_device
+def page_rotate(page, angle=None, fill=None, cos_sin_q=None):
+    """The page turned about its centre by `angle` degrees (positive: what is displayed turns counter-clockwise), or by the Q16 pair
+    cos_sin_q = (cos_q, sin_q) -> a new contiguous page of the same size and dtype.  Bilinear with Q16 source coordinates and 8-bit weights
+    (include/acai_omr_hip.h); taps outside the page read `fill` (default: the paper, 255 / 1.0).  uint8 results are exact integers."""
+    page, H, W, pitch, u8 = _page(page)
+    if (angle is None) == (cos_sin_q is None):
+        raise ValueError("page_rotate: give the angle in degrees or cos_sin_q")
+    cos_q, sin_q = rotation_q16(angle) if cos_sin_q is None else (int(v) for v in cos_sin_q)
+    if fill is None:
+        fill = 255 if u8 else 1.0
+    out = torch.empty(H, W, dtype=page.dtype, device=page.device)
+    _lib.check(_lib.lib().acai_page_rotate(page.data_ptr(), u8, H, W, pitch, cos_q, sin_q, float(fill), out.data_ptr(), W, _st(page)), "acai_page_rotate")
+    return out
+
+
 # ---- camera augmentation (csrc/augment.hip) ---------------------------------------------------------------------------------------------
 def augment_table(entries, device):
     """A list of `_lib.AcaiAugImage` -> the read-only descriptor table in device memory (a uint8 tensor): the one upload of a call."""

@@ -8,6 +8,8 @@ average confidence (acai_omr/ui/routes.py: `setup_inference` :108-129, `multiple
   * `boxes_from_fractions`  the UI's payload (fractions of the page) -> pixel boxes, rounded as PIL's `Image.crop` rounds them;
   * `detect_systems`        no boxes drawn: row profiles -> bands of inked rows -> the bands that hold staff lines (ops.page_profile,
                             ops.page_systems; the reference has no detector);
+  * `estimate_skew`, `deskew_pages`   opt-in, in front of the detection: the skew of a page estimated on the device and the page turned level
+                            (ops.page_strips, ops.page_skew_scores, ops.page_rotate; the reference has a person draw the boxes instead);
   * `split_pages`           every box of every page cut out, resized as `DynamicResize` resizes the crop and written into ONE
                             `PackedPatches` by one launch pair (ops.crop_resize_to_patches) - no crop copies, no per-system launches;
   * `PageResult`            the per-system rows of the decode, joined per page as the service joins them.
@@ -16,7 +18,13 @@ average confidence (acai_omr/ui/routes.py: `setup_inference` :108-129, `multiple
 
 The detection rule assumes roughly LEVEL staff lines: a staff line must show up as a long horizontal run within single pixel rows, so a
 page rotated by more than about one line thickness over `line_frac` of its width (a skewed phone photo) loses its line rows and its systems
-with them.  How well the rule does on real scans and photos has not been measured (no such data here); explicit boxes remain the fallback.
+with them.  `deskew_pages` levels such a page first (`page_inference(..., deskew=True)`): the skew is the candidate angle, of a fixed grid
+up to `SkewConfig.max_angle` <= 15 degrees, along which the sheared row profile of the page is sharpest, refined by a parabola through its
+neighbours, and the page is turned by it with bilinear sampling; `PageResult` then reports boxes in the levelled page and maps points back
+to the page that was passed in.  Not handled: perspective and page curl, EXIF or quarter-turn orientation, a coarse-to-fine angle search,
+and cropping straight from the unrotated page (one resampling fewer).  The defaults of `SkewConfig` rest on the proportions of an engraved
+page, not on data: how well the estimate and the rule do on real scans and photos has not been measured (no such data here); explicit
+boxes remain the fallback.
 """
 import math
 from dataclasses import dataclass
@@ -93,6 +101,88 @@ def detect_systems(page, cfg=None):
     return [tuple(int(v) for v in b) for b in host[4:4 + 4 * count].view(count, 4).tolist()]
 
 
+@dataclass
+class SkewConfig:
+    """Parameters of `estimate_skew`, angles in degrees: the candidates are (k - n) step for k = 0 .. 2 n with n = round(max_angle / step)
+    (max_angle <= 15, at most 1024 candidates); the page is cut into vertical strips of `strip` columns (8, 16, 32 or 64: a strip must be
+    narrow enough for a staff line to stay within about a row across it at max_angle); ink_threshold as in `DetectConfig`."""
+    max_angle: float = 10.0
+    step: float = 0.125
+    strip: int = 16
+    ink_threshold: float = 0.5
+
+    def candidates(self):
+        if not (self.step > 0 and 0 <= self.max_angle <= 15):
+            raise ValueError(f"SkewConfig: step = {self.step} must be positive and max_angle = {self.max_angle} within 0 .. 15 degrees")
+        n = int(round(self.max_angle / self.step))
+        if 2 * n + 1 > 1024:
+            raise ValueError(f"SkewConfig: {2 * n + 1} candidate angles, more than 1024")
+        return [(k - n) * self.step for k in range(2 * n + 1)]
+
+    def slopes(self):
+        """The candidates as Q16 slopes, round(tan(angle) * 65536) in float64: the device does no trigonometry."""
+        return [int(round(math.tan(math.radians(a)) * 65536.0)) for a in self.candidates()]
+
+
+def choose_skew(scores, cfg):
+    """The integer scores of cfg's candidates -> the skew in degrees (float64 arithmetic on the host).  The maximum wins; among equal maxima
+    the candidate nearest to 0, the negative one first (a blank page: exactly 0.0).  An interior winner k with den = s[k-1] - 2 s[k] + s[k+1]
+    < 0 is refined by the vertex of the parabola through its neighbours: + step * 0.5 * (s[k-1] - s[k+1]) / den."""
+    s = [int(v) for v in scores]
+    cand = cfg.candidates()
+    if len(s) != len(cand):
+        raise ValueError(f"{len(s)} scores for {len(cand)} candidates")
+    n, best = len(s) // 2, max(s)
+    k = min((i for i, v in enumerate(s) if v == best), key=lambda i: (abs(i - n), i))
+    angle = cand[k]
+    if 0 < k < len(s) - 1:
+        den = s[k - 1] - 2 * s[k] + s[k + 1]
+        if den < 0:
+            angle += cfg.step * 0.5 * (s[k - 1] - s[k + 1]) / den
+    return float(angle)
+
+
+def skew_scores(pages, cfg=None):
+    """int64 [pages, candidates] on the device: per page two launches (ops.page_strips, ops.page_skew_scores) into one tensor; the slope
+    table is uploaded once."""
+    from . import ops
+    cfg = cfg or SkewConfig()
+    pages, _ = _page_lists(pages, None)
+    pages = [_device_page(p) for p in pages]
+    if not pages:
+        raise ValueError("skew_scores: no pages")
+    table = ops.skew_slope_table(cfg.slopes(), pages[0].device)
+    scores = torch.empty(len(pages), len(table[1]), dtype=torch.int64, device=pages[0].device)
+    for i, p in enumerate(pages):
+        ops.page_skew_scores(ops.page_strips(p, cfg.strip, cfg.ink_threshold), p.shape[1], cfg.strip, table, out=scores[i])
+    return scores
+
+
+def estimate_skew(pages, cfg=None):
+    """One page or a list -> per page, the angle in degrees by which `ops.page_rotate` levels it: positive when the staff lines run down to
+    the right.  Two launches per page, and ONE device-to-host copy (the scores of all pages) per call; the angle is chosen on the host
+    (`choose_skew`).  A blank page gives exactly 0.0."""
+    cfg = cfg or SkewConfig()
+    return [choose_skew(row, cfg) for row in skew_scores(pages, cfg).cpu().tolist()]
+
+
+def deskew_pages(pages, angles=None, cfg=None, fill=None):
+    """One page or a list -> (the levelled pages, their angles).  angles: None - `estimate_skew` with cfg - or one float for all pages or a
+    list with one per page.  Every page is turned by its angle (ops.page_rotate; fill: what lies outside the page, default the paper); an
+    angle of exactly 0.0 returns the page itself (on the device), with no launch."""
+    from . import ops
+    pages, _ = _page_lists(pages, None)
+    pages = [_device_page(p) for p in pages]
+    if angles is None:
+        angles = estimate_skew(pages, cfg) if pages else []
+    elif isinstance(angles, (int, float)):
+        angles = [float(angles)] * len(pages)
+    angles = [float(a) for a in angles]
+    if len(angles) != len(pages):
+        raise ValueError(f"{len(pages)} pages but {len(angles)} angles")
+    return [p if a == 0.0 else ops.page_rotate(p, a, fill) for p, a in zip(pages, angles)], angles
+
+
 def _pixel_box(box, H, W):
     x0, y0, x1, y1 = (int(v) for v in box)
     if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
@@ -167,13 +257,19 @@ def split_pages(pages, boxes_per_page, resize, dtype=torch.float32):
 class PageResult:
     """What `page_inference` returns.  Rows are systems, in page order and top to bottom within a page:
 
-      boxes        per page, its list of pixel boxes (x0, y0, x1, y1);
+      boxes        per page, its list of pixel boxes (x0, y0, x1, y1), in the LEVELLED page when the page was deskewed (what was cropped);
+      angles       per page, the angle in degrees it was turned by before anything else (0.0: not deskewed);
+      page_sizes   per page, its (H, W): the turn is about the page's centre (may be None when no page was turned);
       seqs, log_probs, seq_mask   (N, T') as `continuous_inference` returns them, one row per system (None when there is no system at all);
       system_page  the page index of every row;
       sizes, windows   per row, the size (OH, OW) its box was resized to and the window (top, left, ch, cw) of it the model saw."""
 
-    def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=()):
+    def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=(), angles=None, page_sizes=None):
         self.boxes, self.seqs, self.log_probs, self.seq_mask = boxes, seqs, log_probs, seq_mask
+        self.angles = [0.0] * len(boxes) if angles is None else [float(a) for a in angles]
+        self.page_sizes = None if page_sizes is None else [tuple(int(v) for v in hw) for hw in page_sizes]
+        if len(self.angles) != len(boxes) or (any(self.angles) and (self.page_sizes is None or len(self.page_sizes) != len(boxes))):
+            raise ValueError("PageResult: one angle per page, and the page sizes with them when a page was turned")
         self.system_page, self.sizes, self.windows = list(system_page), list(sizes), list(windows)
         self.specials = tuple(specials)   # the ids of <bos>, <eos>, <pad>: what tokens() leaves out
         self._flat = [b for page in boxes for b in page]
@@ -220,14 +316,44 @@ class PageResult:
         (OH, OW), (top, left, _, _) = self.sizes[system], self.windows[system]
         return x0, y0, (x1 - x0) / OW, (y1 - y0) / OH, top, left
 
+    def _rotation(self, page):
+        """(cos, sin, cx, cy) of the turn that levelled `page`, as the kernel applied it (cos_q / 65536, sin_q / 65536 about the centre), or
+        None for a page that was not turned."""
+        if self.angles[page] == 0.0:
+            return None
+        from .ops import rotation_q16
+        cos_q, sin_q = rotation_q16(self.angles[page])
+        H, W = self.page_sizes[page]
+        return cos_q / 65536.0, sin_q / 65536.0, (W - 1) / 2.0, (H - 1) / 2.0
+
+    def _unlevel(self, page, lx, ly):
+        """A point of the levelled page -> the point of the caller's page it was sampled from."""
+        rot = self._rotation(page)
+        if rot is None:
+            return lx, ly
+        c, s, cx, cy = rot
+        return cx + c * (lx - cx) - s * (ly - cy), cy + s * (lx - cx) + c * (ly - cy)
+
     def to_page_xy(self, system, x, y):
-        """Pixel (x, y) of the tensor the model saw of `system` (its box resized, then cropped to the window) -> page pixels (floats): the
-        resize's own map, source = (resized + 0.5) * scale - 0.5 per axis (align_corners = False), shifted by the window and the box.  With
-        it a `TokenAlignment` of the system can be drawn on the page."""
+        """Pixel (x, y) of the tensor the model saw of `system` (its box resized, then cropped to the window) -> pixels (floats) of the page
+        the caller passed in: the resize's own map, source = (resized + 0.5) * scale - 0.5 per axis (align_corners = False), shifted by the
+        window and the box, then - for a page that was deskewed - the turn that levelled it, backwards.  With it a `TokenAlignment` of the
+        system can be drawn on the page."""
         x0, y0, sx, sy, top, left = self._affine(system)
-        return x0 + (x + left + 0.5) * sx - 0.5, y0 + (y + top + 0.5) * sy - 0.5
+        return self._unlevel(self.system_page[system], x0 + (x + left + 0.5) * sx - 0.5, y0 + (y + top + 0.5) * sy - 0.5)
 
     def from_page_xy(self, system, px, py):
         """The inverse of `to_page_xy`."""
         x0, y0, sx, sy, top, left = self._affine(system)
+        rot = self._rotation(self.system_page[system])
+        if rot is not None:   # the exact inverse of the quantised matrix (cos^2 + sin^2 is 1 only to 2^-16)
+            c, s, cx, cy = rot
+            det, dx, dy = c * c + s * s, px - cx, py - cy
+            px, py = cx + (c * dx + s * dy) / det, cy + (c * dy - s * dx) / det
         return (px - x0 + 0.5) / sx - 0.5 - left, (py - y0 + 0.5) / sy - 0.5 - top
+
+    def box_corners(self, system):
+        """The corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of `system`'s box in the page the caller passed in: the box itself for a page
+        that was not deskewed, a tilted quadrilateral otherwise (for a UI to draw)."""
+        x0, y0, x1, y1 = self._flat[system]
+        return [self._unlevel(self.system_page[system], float(x), float(y)) for x, y in ((x0, y0), (x1, y0), (x1, y1), (x0, y1))]

@@ -725,6 +725,43 @@ typedef struct AcaiCropResize {
 int acai_crop_resize_to_patches(const AcaiCropResize *table, const AcaiCropResize *host_table, int n, float *tmp, int64_t tmp_elems,
                                 void *patches, int ld, int64_t patch_rows, int P, int out_dtype, int clamp01, void *stream);
 
+/* ---- page deskew: estimate the skew of a page and turn it level (csrc/deskew.hip) ---------------------------------------------------------
+ * The detection rule of acai_page_systems needs level staff lines; a photographed page is not level.  A page is as acai_page_profile takes
+ * it (uint8 or fp32, pitch >= W, the same ink test in_sample(p) < ink_threshold, the same size limits).  Everything below is defined in
+ * integers, fp32 rotation aside, and the results do not depend on how the launches are scheduled.  Shifts are arithmetic. */
+#define ACAI_STRIP_TILE_ROWS 64    /* acai_page_strips: a workgroup owns 64 rows x 32 units of 16 bytes (16 uint8 or 4 fp32 pixels) ... */
+#define ACAI_STRIP_TILE_UNITS 32   /* ... one unit per lane and step; a strip is a whole number of units or, uint8 at S = 8, half a unit */
+#define ACAI_SKEW_CHUNK 1023       /* acai_page_skew_scores: row differences per workgroup (256 threads x 4 rows, the last row is the halo) */
+#define ACAI_SKEW_MAX_SLOPES 1024
+#define ACAI_SKEW_MAX_SLOPE 17560  /* round(tan(15 deg) * 65536) */
+
+/* Strip profile.  The page is cut into vertical strips of S columns, S in {8, 16, 32, 64}, nS = ceil(W / S); strips[s][y] = the number of
+ * ink pixels of row y in columns [s S, min((s + 1) S, W)).  Columns behind W (the pitch padding) never count.  LAYOUT: uint8 [nS][H] (a
+ * count is at most 64) - the rows of one strip are contiguous, which is the direction acai_page_skew_scores walks.  One read of the page,
+ * 16 bytes per lane where base and pitch are multiples of 16 bytes, element by element where not. */
+int acai_page_strips(const void *page, int in_u8, int H, int W, int pitch, float ink_threshold, int S, uint8_t *strips, void *stream);
+
+/* Skew scores of K candidate slopes m_k in Q16 (m = round(tan(angle) * 65536), |m| <= ACAI_SKEW_MAX_SLOPE, 1 <= K <= ACAI_SKEW_MAX_SLOPES):
+ *   dx(s) = s S + S / 2 - W / 2 (integer divisions),  off(s, k) = (m_k dx(s) + 32768) >> 16,
+ *   Q_k[y] = sum over s of strips[s][y + off(s, k)], rows outside [0, H) contributing 0,
+ *   scores[k] = sum over y in [0, H - 2] of (Q_k[y + 1] - Q_k[y])^2 in 64 bits (H = 1: 0).
+ * `strips` is what acai_page_strips wrote for the same H, W, S.  `slopes` is the device copy of the table, `host_slopes` the same K values
+ * in host memory (what is checked here).  scores [K] is zeroed on the stream, then ONE launch over (slope, chunk of ACAI_SKEW_CHUNK row
+ * differences) adds one 64-bit integer atomic per workgroup: integer sums, so the result is the same whatever the order. */
+int acai_page_skew_scores(const uint8_t *strips, int H, int W, int S, const int32_t *slopes, const int32_t *host_slopes, int K, int64_t *scores,
+                          void *stream);
+
+/* The page turned about its centre by the angle with cos_q = round(cos * 65536), sin_q = round(sin * 65536): a positive angle turns what is
+ * displayed counter-clockwise.  Output pixel (x, y) of `out` [H][out_pitch >= W] (the input's element type, not in place) is sampled at,
+ * in 64-bit integers with dx2 = 2 x - (W - 1), dy2 = 2 y - (H - 1),
+ *   sx = (cos_q dx2 - sin_q dy2 + (W - 1) 65536) >> 1,   sy = (sin_q dx2 + cos_q dy2 + (H - 1) 65536) >> 1,
+ *   ix = sx >> 16, iy = sy >> 16, fx = (sx >> 8) & 255, fy = (sy >> 8) & 255,
+ * bilinear over the taps t00 = (iy, ix), t01 = (iy, ix + 1), t10 = (iy + 1, ix), t11 = (iy + 1, ix + 1); a tap outside the page reads
+ * `fill` (uint8: an integer in 0 .. 255).  uint8: ((256 - fy) ((256 - fx) t00 + fx t01) + fy ((256 - fx) t10 + fx t11) + 32768) >> 16, so
+ * angle 0 is the identity and (cos_q, sin_q) = (0, 65536) a quarter turn of a square page.  fp32: the same weights f / 256 in fp32.
+ * A lane makes 4 consecutive pixels and stores them as one word where `out` and out_pitch are multiples of it (4 bytes; fp32: 16). */
+int acai_page_rotate(const void *page, int in_u8, int H, int W, int pitch, int cos_q, int sin_q, float fill, void *out, int out_pitch, void *stream);
+
 /* hipGraph helpers (capture on `stream`, replay). */
 int acai_graph_begin(void *stream);
 int acai_graph_end(void *stream, void **graph_exec_out);
