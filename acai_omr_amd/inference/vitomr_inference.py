@@ -229,7 +229,7 @@ def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, s
             return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
 
 
-def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None, deskew=None):
+def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None, deskew=None, flatten=None):
     """Whole pages in, their systems decoded as one batch (an extension; the reference's service crops hand-drawn boxes with PIL and decodes
     them one by one, acai_omr/ui/routes.py:93-129) -> a `page.PageResult`.
     pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1].  boxes: None - the systems are found on the device
@@ -244,17 +244,27 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     the device (page.estimate_skew) - or one angle in degrees, or a list with one per page.  The pages are turned level FIRST
     (page.deskew_pages); detection then runs on the levelled pages, and boxes the caller supplies refer to the LEVELLED pages too (pixels
     of, or fractions of, the page after the turn, which has the size of the page before it).  The result's boxes are in the levelled
-    pages, its `angles` says by how much each was turned, and `to_page_xy` / `box_corners` lead back to the pages as they were passed in."""
+    pages, its `angles` says by how much each was turned, and `to_page_xy` / `box_corners` lead back to the pages as they were passed in.
+    flatten (an extension, default None = off, as is False: the path above, unchanged, no launch added): True or a `page.FlattenConfig` -
+    the uneven illumination of every page is divided out FIRST (page.flatten_pages, two launches per page, no copy to the host); deskew
+    (if asked for), detection and the crops the model reads all see the flattened pages.  Geometry does not change: boxes, angles and the
+    maps back to the page are what they are without it.  The result's `flattened` says which pages were.  Chosen on synthetic shading; not
+    measured on real photographs."""
     from .. import page as pg
     pages, boxes = pg._page_lists(pages, boxes)
     if boxes is not None and len(boxes) != len(pages):
         raise ValueError(f"{len(pages)} pages but boxes for {len(boxes)}")
     pages = [pg._device_page(p, resize.device) for p in pages]
-    angles = None
+    angles, flattened = None, None
+    if flatten is not None and flatten is not False:
+        if flatten is not True and not isinstance(flatten, pg.FlattenConfig):
+            raise TypeError("flatten: expected None, a bool or a page.FlattenConfig")
+        pages = pg.flatten_pages(pages, None if flatten is True else flatten)
+        flattened = [True] * len(pages)
     if deskew is not None and deskew is not False:
         estimate = deskew is True or isinstance(deskew, pg.SkewConfig)
         pages, angles = pg.deskew_pages(pages, None if estimate else deskew, deskew if isinstance(deskew, pg.SkewConfig) else None)
-    turned = dict(angles=angles, page_sizes=[tuple(p.shape) for p in pages])
+    turned = dict(angles=angles, page_sizes=[tuple(p.shape) for p in pages], flattened=flattened)
     if boxes is None:
         per_page = [pg.detect_systems(p, detect) for p in pages]
     else:

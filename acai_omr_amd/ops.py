@@ -408,6 +408,53 @@ def page_rotate(page, angle=None, fill=None, cos_sin_q=None):
     return out
 
 
+# ---- page illumination flattening (csrc/flatten.hip) ------------------------------------------------------------------------------------
+def _tile(tile):
+    if tile not in _lib.FLATTEN_TILES:
+        raise ValueError(f"tile {tile}: expected one of {_lib.FLATTEN_TILES}")
+    return int(tile)
+
+
+@_on_operand_device
+def page_tile_levels(page, tile, percent=50):
+    """Tile levels of a page (as `page_profile` takes it) -> uint8 [GH, GW], GH = ceil(H / tile), GW = ceil(W / tile): per tile of tile x
+    tile pixels (cut off at the page's edges) the rank-th smallest level of its n pixels, rank = max(1, (n percent + 99) // 100) - at the
+    default 50 the median, the paper of a tile that is not mostly ink.  A uint8 pixel is its own level, an fp32 pixel v is
+    floor(v * 255 + 0.5) clipped to 0 .. 255.  tile in {16, 32, 64, 128}, percent an integer in 1 .. 100 (ValueError otherwise)."""
+    tile = _tile(tile)
+    if int(percent) != percent or not 1 <= int(percent) <= 100:
+        raise ValueError(f"percent = {percent}: expected an integer in 1 .. 100")
+    page, H, W, pitch, u8 = _page(page)
+    out = torch.empty(-(-H // tile), -(-W // tile), dtype=torch.uint8, device=page.device)
+    _lib.check(_lib.lib().acai_page_tile_levels(page.data_ptr(), u8, H, W, pitch, tile, int(percent), out.data_ptr(), _st(page)), "acai_page_tile_levels")
+    return out
+
+
+@_on_operand_device
+def page_flatten(page, grid, tile, rq=85, floor=32, out=None):
+    """The page divided by its paper level -> a page of the same size and dtype (`out`: a (H, W) view to write into, its padding is left
+    alone; allocated contiguous when None).  grid: `page_tile_levels` of the page at `tile`.  A tile whose level is below rq / 256 of the
+    brightest level among its 3 x 3 neighbours takes that level (it is mostly ink; rq = 0: never), every level is raised to `floor`, the
+    grid is interpolated bilinearly between the tile centres, and a pixel p becomes min(255, p * 255 / background) rounded to nearest -
+    include/acai_omr_hip.h has the integer definition, which the fp32 output follows with one multiply.  One launch.  A grid of another
+    shape, dtype or device, a tile other than 16, 32, 64, 128, rq outside 0 .. 256 or floor outside 1 .. 255: ValueError."""
+    tile = _tile(tile)
+    page, H, W, pitch, u8 = _page(page)
+    want = (-(-H // tile), -(-W // tile))
+    if not torch.is_tensor(grid) or not grid.is_cuda or grid.device != page.device or grid.dtype != torch.uint8 or tuple(grid.shape) != want or not grid.is_contiguous():
+        raise ValueError(f"grid: expected a contiguous uint8 {list(want)} on the page's device (page_tile_levels at tile {tile})")
+    if int(rq) != rq or not 0 <= int(rq) <= 256 or int(floor) != floor or not 1 <= int(floor) <= 255:
+        raise ValueError(f"rq = {rq}, floor = {floor}: expected integers in 0 .. 256 and 1 .. 255")
+    if out is None:
+        out = torch.empty(H, W, dtype=page.dtype, device=page.device)
+    if (not torch.is_tensor(out) or not out.is_cuda or out.device != page.device or out.dtype != page.dtype or tuple(out.shape) != (H, W)
+            or out.stride(1) != 1 or (H > 1 and out.stride(0) < W) or out.data_ptr() == page.data_ptr()):
+        raise ValueError(f"out: expected a {page.dtype} ({H}, {W}) view on the page's device with contiguous, non-overlapping rows, not the page itself")
+    _lib.check(_lib.lib().acai_page_flatten(page.data_ptr(), u8, H, W, pitch, grid.data_ptr(), tile, int(rq), int(floor), out.data_ptr(),
+                                            out.stride(0) if H > 1 else W, _st(page)), "acai_page_flatten")
+    return out
+
+
 # ---- camera augmentation (csrc/augment.hip) ---------------------------------------------------------------------------------------------
 def augment_table(entries, device):
     """A list of `_lib.AcaiAugImage` -> the read-only descriptor table in device memory (a uint8 tensor): the one upload of a call."""

@@ -10,6 +10,8 @@ average confidence (acai_omr/ui/routes.py: `setup_inference` :108-129, `multiple
                             ops.page_systems; the reference has no detector);
   * `estimate_skew`, `deskew_pages`   opt-in, in front of the detection: the skew of a page estimated on the device and the page turned level
                             (ops.page_strips, ops.page_skew_scores, ops.page_rotate; the reference has a person draw the boxes instead);
+  * `flatten_pages`         opt-in, in front of everything else: the paper's brightness estimated per tile on the device and divided out
+                            of the page (ops.page_tile_levels, ops.page_flatten; the reference reads the photo as it comes);
   * `split_pages`           every box of every page cut out, resized as `DynamicResize` resizes the crop and written into ONE
                             `PackedPatches` by one launch pair (ops.crop_resize_to_patches) - no crop copies, no per-system launches;
   * `PageResult`            the per-system rows of the decode, joined per page as the service joins them.
@@ -25,6 +27,16 @@ to the page that was passed in.  Not handled: perspective and page curl, EXIF or
 and cropping straight from the unrotated page (one resampling fewer).  The defaults of `SkewConfig` rest on the proportions of an engraved
 page, not on data: how well the estimate and the rule do on real scans and photos has not been measured (no such data here); explicit
 boxes remain the fallback.
+
+Every stage decides "ink or paper" with ONE threshold for the whole page (`value / 255 < ink_threshold`), so a page lit unevenly - falloff
+towards the far edge, a vignette, the shadow of the hand and the phone - turns to "ink" wherever its paper falls below it, and bands merge
+across systems.  `flatten_pages` (`page_inference(..., flatten=True)`) divides the local paper level out first: the median level of every
+tile (`FlattenConfig.tile` pixels square), a tile that is mostly ink taking its brightest neighbour's instead, interpolated bilinearly
+between the tile centres; a pixel becomes 255 * p / background.  Deskew, detection and the crops the model reads all see the flattened
+page; geometry does not change.  Not handled: using the flattened page for detection only while cropping from the original, binarisation,
+colour input, the dark table around a page, and ink areas more than two tiles wide in both directions (the rescue reaches one tile).  The
+defaults of `FlattenConfig` were chosen on synthetic shading (ramps, a vignette, hard shadow edges): nothing has been measured on real
+photographs (no such data here), nor how a trained checkpoint reads flattened crops.
 """
 import math
 from dataclasses import dataclass
@@ -32,6 +44,7 @@ from typing import Optional
 
 import torch
 
+from ._lib import FLATTEN_TILES
 from .utils import PackedPatches, stringify_lmx_seq
 
 NO_GPU = "acai_omr_amd page input runs on the GPU (HIP page kernels); there is no CPU fallback"
@@ -183,6 +196,62 @@ def deskew_pages(pages, angles=None, cfg=None, fill=None):
     return [p if a == 0.0 else ops.page_rotate(p, a, fill) for p, a in zip(pages, angles)], angles
 
 
+@dataclass
+class FlattenConfig:
+    """Parameters of `flatten_pages`:
+
+      tile       the paper level is estimated per tile of tile x tile pixels: 16, 32, 64 or 128   default (None): the largest of those that
+                                                                                is <= max(16, H // 40) - wider than a staff is tall, so that
+                                                                                the median of a tile over a staff is still paper;
+      percent    a tile's level is the level below or at which this share of its pixels lie: an integer in 1 .. 100 (50: the median);
+      ink_ratio  a tile whose level is below ink_ratio of the brightest level among its 3 x 3 neighbours is mostly ink and takes that
+                 level; on the device rq = round(ink_ratio * 256), 0 <= rq <= 256, and 0 switches the rescue off;
+      floor      no tile level is taken below this level (1 .. 255): what is darker is not lit paper, and dividing by it would only lift
+                 noise.
+
+    Anything else: ValueError, when the config is made and again when it is used."""
+    tile: Optional[int] = None
+    percent: int = 50
+    ink_ratio: float = 1.0 / 3.0
+    floor: int = 32
+
+    def __post_init__(self):
+        self.check()
+
+    def check(self):
+        """(percent, rq, floor) as the device takes them."""
+        if self.tile is not None and (isinstance(self.tile, bool) or not isinstance(self.tile, int) or self.tile not in FLATTEN_TILES):
+            raise ValueError(f"FlattenConfig: tile = {self.tile!r} is not None or one of {FLATTEN_TILES}")
+        for name, lo, hi in (("percent", 1, 100), ("floor", 1, 255)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"FlattenConfig: {name} = {v!r} is not an integer in {lo} .. {hi}")
+        if isinstance(self.ink_ratio, bool) or not isinstance(self.ink_ratio, (int, float)) or not -1.0 < self.ink_ratio < 2.0:
+            raise ValueError(f"FlattenConfig: ink_ratio = {self.ink_ratio!r} is not a number in 0 .. 1")
+        rq = int(round(self.ink_ratio * 256))
+        if not 0 <= rq <= 256:
+            raise ValueError(f"FlattenConfig: ink_ratio = {self.ink_ratio!r} gives rq = {rq}, not in 0 .. 256")
+        return self.percent, rq, self.floor
+
+    def resolved(self, H):
+        """(tile, percent, rq, floor) for a page of H rows."""
+        tile = self.tile if self.tile is not None else max(t for t in FLATTEN_TILES if t <= max(16, H // 40))
+        return (tile,) + self.check()
+
+
+def flatten_pages(pages, cfg=None):
+    """One page or a list -> the list of flattened pages on the device (new contiguous tensors of the pages' sizes and dtypes).  Two launches
+    per page (ops.page_tile_levels, ops.page_flatten), nothing comes back to the host."""
+    from . import ops
+    cfg = cfg or FlattenConfig()
+    pages, _ = _page_lists(pages, None)
+    out = []
+    for p in (_device_page(p) for p in pages):
+        tile, percent, rq, floor = cfg.resolved(p.shape[0])
+        out.append(ops.page_flatten(p, ops.page_tile_levels(p, tile, percent), tile, rq, floor))
+    return out
+
+
 def _pixel_box(box, H, W):
     x0, y0, x1, y1 = (int(v) for v in box)
     if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
@@ -258,14 +327,18 @@ class PageResult:
     """What `page_inference` returns.  Rows are systems, in page order and top to bottom within a page:
 
       boxes        per page, its list of pixel boxes (x0, y0, x1, y1), in the LEVELLED page when the page was deskewed (what was cropped);
+      flattened    per page, whether its illumination was flattened before anything else (what was cropped is then the flattened page);
       angles       per page, the angle in degrees it was turned by before anything else (0.0: not deskewed);
       page_sizes   per page, its (H, W): the turn is about the page's centre (may be None when no page was turned);
       seqs, log_probs, seq_mask   (N, T') as `continuous_inference` returns them, one row per system (None when there is no system at all);
       system_page  the page index of every row;
       sizes, windows   per row, the size (OH, OW) its box was resized to and the window (top, left, ch, cw) of it the model saw."""
 
-    def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=(), angles=None, page_sizes=None):
+    def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=(), angles=None, page_sizes=None, flattened=None):
         self.boxes, self.seqs, self.log_probs, self.seq_mask = boxes, seqs, log_probs, seq_mask
+        self.flattened = [False] * len(boxes) if flattened is None else [bool(f) for f in flattened]
+        if len(self.flattened) != len(boxes):
+            raise ValueError("PageResult: one flattened flag per page")
         self.angles = [0.0] * len(boxes) if angles is None else [float(a) for a in angles]
         self.page_sizes = None if page_sizes is None else [tuple(int(v) for v in hw) for hw in page_sizes]
         if len(self.angles) != len(boxes) or (any(self.angles) and (self.page_sizes is None or len(self.page_sizes) != len(boxes))):

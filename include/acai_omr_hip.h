@@ -762,6 +762,41 @@ int acai_page_skew_scores(const uint8_t *strips, int H, int W, int S, const int3
  * A lane makes 4 consecutive pixels and stores them as one word where `out` and out_pitch are multiples of it (4 bytes; fp32: 16). */
 int acai_page_rotate(const void *page, int in_u8, int H, int W, int pitch, int cos_q, int sin_q, float fill, void *out, int out_pitch, void *stream);
 
+/* ---- page illumination flattening: estimate the paper's brightness locally and divide it out (csrc/flatten.hip) ---------------------------
+ * Every page stage above tells ink from paper by one global threshold; a photographed page is not evenly lit.  A page is as
+ * acai_page_profile takes it (uint8 or fp32 in [0, 1], pitch >= W, the same size limits).  Everything is defined in integers, so no result
+ * depends on how the launches are scheduled; the fp32 output is one correctly rounded fp32 multiply.  Shifts are arithmetic.
+ *
+ * LEVEL of a pixel: a uint8 value itself; of an fp32 value v, min(255, max(0, (int)floorf(v * 255.0f + 0.5f))), the product and the sum
+ * each rounded to fp32 (no FMA).
+ *
+ * Tile levels.  T = tile in {16, 32, 64, 128}, GH = ceil(H / T), GW = ceil(W / T).  Tile (i, j) holds the n pixels of rows
+ * [i T, min((i + 1) T, H)) and columns [j T, min((j + 1) T, W)); rank = max(1, (n percent + 99) / 100), 1 <= percent <= 100;
+ * levels[i][j] = the smallest level L such that at least rank of the tile's pixels have a level <= L (the rank-th smallest level).
+ * LAYOUT: uint8 [GH][GW], contiguous.  One read of the page; a wave per tile builds a 256-bin histogram with integer LDS atomics (sums that
+ * do not depend on their order) and scans it.  Columns behind W (the pitch padding) are never read. */
+int acai_page_tile_levels(const void *page, int in_u8, int H, int W, int pitch, int tile, int percent, uint8_t *levels, void *stream);
+
+/* The page divided by its interpolated paper level, ONE launch.  With g = levels [GH][GW] as acai_page_tile_levels wrote it for the same
+ * H, W, tile:
+ *   rescue and floor   m[i][j] = max of g over the 3 x 3 neighbourhood of (i, j) clipped at the grid's border (the tile itself included);
+ *                      s[i][j] = max(floor, g[i][j] * 256 < m[i][j] * rq ? m[i][j] : g[i][j]),  0 <= rq <= 256 (rq = round(ink_ratio * 256);
+ *                      0: no rescue),  1 <= floor <= 255.  A tile that is mostly ink takes its brightest neighbour's level instead of
+ *                      passing ink off as paper; a shadow, rarely 1 / ink_ratio times darker than the paper beside it, keeps its own.
+ *   background         per axis, with coordinate c, grid size G and D = 2 T:  u = 2 c + 1 - T,  j0 = floor(u / D),  w = u - j0 D (odd, in
+ *                      [1, D)),  the grid indices clamp(j0, 0, G - 1) and clamp(j0 + 1, 0, G - 1): tile centres, the border replicated;
+ *                      bg = ((D - wy) ((D - wx) s00 + wx s01) + wy ((D - wx) s10 + wx s11) + D D / 2) >> log2(D D)   (< 2^24 before the
+ *                      shift; floor <= bg <= 255);
+ *   output             recip[b] = (255 * 65536 + b / 2) / b in integers (b = 1 .. 255; <= 16 711 680, exact in fp32);
+ *                      uint8: out = min(255, (p recip[bg] + 32768) >> 16) in unsigned 32 bits, no float arithmetic;
+ *                      fp32:  out = fminf(1.0f, v * ((float)recip[bg] * 0x1p-16f)).
+ * `out` [H][out_pitch >= W] has the input's element type and is not the input.  Every pixel is read once and written once, 16 bytes per
+ * lane where base and pitch (of the page for loads, of `out` for stores) are multiples of 16 bytes, element by element where not and
+ * across W; nothing behind W is read or written.  A workgroup covers 16 rows of one tile row and stages the five raw grid rows they depend
+ * on (three rows of s, each a 3 x 3 maximum), s and recip in LDS. */
+int acai_page_flatten(const void *page, int in_u8, int H, int W, int pitch, const uint8_t *levels, int tile, int rq, int floor_level, void *out,
+                      int out_pitch, void *stream);
+
 /* hipGraph helpers (capture on `stream`, replay). */
 int acai_graph_begin(void *stream);
 int acai_graph_end(void *stream, void **graph_exec_out);
