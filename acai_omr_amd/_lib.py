@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip"]
+SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -88,6 +88,7 @@ PAGE_LANE_PIXELS, PAGE_WAVES, PAGE_MAX_W, PAGE_MAX_H = 4, 4, 16384, 65535   # ac
 STRIP_TILE_ROWS, STRIP_TILE_UNITS, SKEW_CHUNK, SKEW_MAX_SLOPES, SKEW_MAX_SLOPE = 64, 32, 1023, 1024, 17560
 STRIP_WIDTHS = (8, 16, 32, 64)
 FLATTEN_TILES = (16, 32, 64, 128)   # csrc/flatten.hip: the tile sizes of acai_page_tile_levels / acai_page_flatten
+EXTENTS_MAX_RUN = 256               # csrc/rectify.hip (ACAI_EXTENTS_MAX_RUN): the longest run acai_page_extents can be asked for
 
 
 class AcaiCropResize(Structure):
@@ -124,6 +125,8 @@ _SIGNATURES = {
     "acai_page_rotate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
     "acai_page_tile_levels": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "acai_page_flatten": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "acai_page_extents": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+    "acai_page_warp": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int64), c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     "acai_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "acai_attn_varlen_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_uint32, c_int, c_void_p]),

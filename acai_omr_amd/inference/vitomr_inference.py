@@ -229,7 +229,7 @@ def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, s
             return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
 
 
-def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None, deskew=None, flatten=None):
+def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None, deskew=None, flatten=None, rectify=None):
     """Whole pages in, their systems decoded as one batch (an extension; the reference's service crops hand-drawn boxes with PIL and decodes
     them one by one, acai_omr/ui/routes.py:93-129) -> a `page.PageResult`.
     pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1].  boxes: None - the systems are found on the device
@@ -241,21 +241,39 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     page order and top to bottom.  max_inference_len, slots, grammar: as in continuous_inference.  A page without systems contributes no
     rows; with no system at all nothing is launched and the result is empty.
     deskew (an extension, default None = off: the path above, unchanged): True or a `page.SkewConfig` - every page's skew is estimated on
-    the device (page.estimate_skew) - or one angle in degrees, or a list with one per page.  The pages are turned level FIRST
-    (page.deskew_pages); detection then runs on the levelled pages, and boxes the caller supplies refer to the LEVELLED pages too (pixels
-    of, or fractions of, the page after the turn, which has the size of the page before it).  The result's boxes are in the levelled
+    the device (page.estimate_skew) - or one angle in degrees, or a list with one per page.  The pages are turned level before the
+    detection (page.deskew_pages); detection then runs on the levelled pages, and boxes the caller supplies refer to the LEVELLED pages too
+    (pixels of, or fractions of, the page after the turn, which has the size of the page before it).  The result's boxes are in the levelled
     pages, its `angles` says by how much each was turned, and `to_page_xy` / `box_corners` lead back to the pages as they were passed in.
     flatten (an extension, default None = off, as is False: the path above, unchanged, no launch added): True or a `page.FlattenConfig` -
-    the uneven illumination of every page is divided out FIRST (page.flatten_pages, two launches per page, no copy to the host); deskew
-    (if asked for), detection and the crops the model reads all see the flattened pages.  Geometry does not change: boxes, angles and the
-    maps back to the page are what they are without it.  The result's `flattened` says which pages were.  Chosen on synthetic shading; not
-    measured on real photographs."""
+    the uneven illumination of every page is divided out before deskew (page.flatten_pages, two launches per page, no copy to the host);
+    deskew (if asked for), detection and the crops the model reads all see the flattened pages.  Geometry does not change: boxes, angles and
+    the maps back to the page are what they are without it.  The result's `flattened` says which pages were.  Chosen on synthetic shading;
+    not measured on real photographs.
+    rectify (an extension, default None = off, as is False: the path above, unchanged, no launch added, no copy made): True or a
+    `page.RectifyConfig` - the outline of the sheet is found in every page (page.find_page_quad: two launches and one copy to the host per
+    page) - or the corners themselves, one quad [TL, TR, BR, BL] of (x, y) for all pages or a list with one quad or None per page (a UI
+    lets its user tap them).  The sheet is warped flat FIRST (page.rectify_pages, one launch per page): the order is rectify -> flatten
+    -> deskew -> detect, so that flatten and deskew see the sheet and not the table around it.  A page in which no sheet is found, or
+    which the sheet fills, is left as it is.  Boxes the caller supplies refer to the RECTIFIED page, and then the levelled one.  The
+    result's `quads` and `source_sizes` say what was cut from what, `page_sizes` is the size of the rectified pages, and `to_page_xy` /
+    `from_page_xy` / `box_corners` go the whole way back to the pages as they were passed in.  Not handled: page curl, a sheet lighter
+    than its surroundings or cut off by the frame on more than one side, colour input, EXIF and quarter-turn orientation.  Chosen on
+    synthetic quadrilaterals over a noise table; not measured on real photographs."""
     from .. import page as pg
     pages, boxes = pg._page_lists(pages, boxes)
     if boxes is not None and len(boxes) != len(pages):
         raise ValueError(f"{len(pages)} pages but boxes for {len(boxes)}")
     pages = [pg._device_page(p, resize.device) for p in pages]
-    angles, flattened = None, None
+    angles, flattened, rectified = None, None, {}
+    if rectify is not None and rectify is not False:
+        find = rectify is True or isinstance(rectify, pg.RectifyConfig)
+        if not find and not (pg._is_quad(rectify) or (isinstance(rectify, (list, tuple)) and all(q is None or pg._is_quad(q) for q in rectify))):
+            raise TypeError("rectify: expected None, a bool, a page.RectifyConfig, one quad [TL, TR, BR, BL] or a list of quads (or None) per page")
+        cfg = rectify if isinstance(rectify, pg.RectifyConfig) else pg.RectifyConfig()
+        source_sizes = [tuple(p.shape) for p in pages]
+        pages, quads = pg.rectify_pages(pages, None if find else rectify, cfg)
+        rectified = dict(quads=quads, source_sizes=source_sizes, inset=cfg.inset)
     if flatten is not None and flatten is not False:
         if flatten is not True and not isinstance(flatten, pg.FlattenConfig):
             raise TypeError("flatten: expected None, a bool or a page.FlattenConfig")
@@ -264,7 +282,7 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     if deskew is not None and deskew is not False:
         estimate = deskew is True or isinstance(deskew, pg.SkewConfig)
         pages, angles = pg.deskew_pages(pages, None if estimate else deskew, deskew if isinstance(deskew, pg.SkewConfig) else None)
-    turned = dict(angles=angles, page_sizes=[tuple(p.shape) for p in pages], flattened=flattened)
+    turned = dict(angles=angles, page_sizes=[tuple(p.shape) for p in pages], flattened=flattened, **rectified)
     if boxes is None:
         per_page = [pg.detect_systems(p, detect) for p in pages]
     else:

@@ -455,6 +455,89 @@ def page_flatten(page, grid, tile, rq=85, floor=32, out=None):
     return out
 
 
+# ---- page rectification (csrc/rectify.hip) ----------------------------------------------------------------------------------------------
+def default_min_run(H, W):
+    """The run of paper pixels that counts as the sheet in `page_extents`: max(4, min(H, W) // 100), capped at what the kernel takes."""
+    return min(max(4, min(int(H), int(W)) // 100), _lib.EXTENTS_MAX_RUN)
+
+
+@_on_operand_device
+def page_extents(page, paper_threshold=0.5, min_run=None):
+    """Paper extents of a page (as `page_profile` takes it) -> int32 [2 H + 2 W] = row_lo [H], row_hi [H], col_lo [W], col_hi [W].  A pixel
+    is paper when it is not ink at paper_threshold; with R = min_run (default `default_min_run`; 1 .. 256), row_lo[y] is the smallest x
+    with pixels x .. x + R - 1 of row y all paper (W: none), row_hi[y] the largest x with x - R + 1 .. x all paper (-1: none), col_lo /
+    col_hi the same down the columns (H / -1: none).  Two launches."""
+    page, H, W, pitch, u8 = _page(page)
+    R = default_min_run(H, W) if min_run is None else min_run
+    if isinstance(R, bool) or int(R) != R or not 1 <= int(R) <= _lib.EXTENTS_MAX_RUN:
+        raise ValueError(f"min_run = {min_run!r}: expected an integer in 1 .. {_lib.EXTENTS_MAX_RUN}")
+    out = torch.empty(2 * H + 2 * W, dtype=torch.int32, device=page.device)
+    _lib.check(_lib.lib().acai_page_extents(page.data_ptr(), u8, H, W, pitch, float(paper_threshold), int(R), out.data_ptr(), _st(page)), "acai_page_extents")
+    return out
+
+
+def _solve_square_to_quad(quad):
+    """The unit square's (0, 0), (1, 0), (1, 1), (0, 1) -> the quad's TL, TR, BR, BL: (a, b, c, d, e, f, g, h) of x = (a u + b v + c) / (g u +
+    h v + 1), y = (d u + e v + f) / (g u + h v + 1) in closed form (Heckbert 1989), every operation in float64 and in this order."""
+    (x0, y0), (x1, y1), (x2, y2), (x3, y3) = ((float(x), float(y)) for x, y in quad)
+    dx1, dx2, sx = x1 - x2, x3 - x2, (x0 - x1) + (x2 - x3)
+    dy1, dy2, sy = y1 - y2, y3 - y2, (y0 - y1) + (y2 - y3)
+    det = dx1 * dy2 - dx2 * dy1
+    if det == 0.0:
+        raise ValueError(f"quad {quad}: three corners on a line")
+    g, h = (sx * dy2 - dx2 * sy) / det, (dx1 * sy - sx * dy1) / det
+    return (x1 - x0) + g * x1, (x3 - x0) + h * x3, x0, (y1 - y0) + g * y1, (y3 - y0) + h * y3, y0, g, h
+
+
+def homography_q30(quad, out_size, inset=0):
+    """The nine integers A .. I `page_warp` takes: the homography (float64 on the host, no trigonometry) that takes the corners of the
+    output rectangle grown by `inset` pixels - (-inset, -inset), (OW - 1 + inset, -inset), (OW - 1 + inset, OH - 1 + inset), (-inset,
+    OH - 1 + inset) - to quad = [TL, TR, BR, BL] (x, y) of the page, scaled so that the largest of its denominators at the output pixels
+    (0, 0), (OW - 1, 0), (OW - 1, OH - 1), (0, OH - 1) is 1, every entry int(round(v * 2**30)).  out_size = (OH, OW).  A quad whose
+    denominator is not positive at all four: ValueError."""
+    OH, OW = (int(v) for v in out_size)
+    inset = float(inset)
+    lx, ly = OW - 1 + 2.0 * inset, OH - 1 + 2.0 * inset
+    if OH < 1 or OW < 1 or not (lx > 0 and ly > 0):
+        raise ValueError(f"homography_q30: out_size {out_size} with inset {inset} spans no rectangle")
+    a, b, c, d, e, f, g, h = _solve_square_to_quad(quad)
+    # u = (x + inset) / lx, v = (y + inset) / ly
+    m = [a / lx, b / ly, c + (a * inset) / lx + (b * inset) / ly,
+         d / lx, e / ly, f + (d * inset) / lx + (e * inset) / ly,
+         g / lx, h / ly, 1.0 + (g * inset) / lx + (h * inset) / ly]
+    dens = [m[6] * x + m[7] * y + m[8] for x, y in ((0, 0), (OW - 1, 0), (OW - 1, OH - 1), (0, OH - 1))]
+    if not min(dens) > 0.0:
+        raise ValueError(f"quad {quad}: the output rectangle crosses the horizon of its homography (not a convex quad in TL, TR, BR, BL order?)")
+    top = max(dens)
+    return [int(round(v / top * 2.0 ** 30)) for v in m]
+
+
+@_on_operand_device
+def page_warp(page, coef, out_size, fill=None, out=None):
+    """The page seen through the homography coef = nine integers A .. I (`homography_q30`) -> a new contiguous (OH, OW) page of the same
+    dtype, out_size = (OH, OW) (or written into `out`, a view of that shape with contiguous rows).  Output pixel (x, y) is sampled at
+    floor((A x + B y + C) * 256 / (G x + H y + I)) / 256, floor((D x + E y + F) * 256 / (G x + H y + I)) / 256, bilinear with 8-bit weights
+    as `page_rotate` (include/acai_omr_hip.h); taps outside the page read `fill` (default: the paper, 255 / 1.0).  uint8 results are exact
+    integers.  A denominator that is not positive over the output, or forms beyond 2^62: RuntimeError from the library."""
+    page, H, W, pitch, u8 = _page(page)
+    coef = [int(v) for v in coef]
+    if len(coef) != 9 or any(not -2 ** 63 <= v < 2 ** 63 for v in coef):
+        raise ValueError("page_warp: coef is nine integers A .. I that fit 64 bits")
+    OH, OW = (int(v) for v in out_size)
+    if fill is None:
+        fill = 255 if u8 else 1.0
+    if out is None:
+        if OH < 1 or OW < 1:
+            raise ValueError(f"page_warp: out_size {out_size}")
+        out = torch.empty(OH, OW, dtype=page.dtype, device=page.device)
+    if (not torch.is_tensor(out) or not out.is_cuda or out.device != page.device or out.dtype != page.dtype or tuple(out.shape) != (OH, OW)
+            or out.stride(1) != 1 or (OH > 1 and out.stride(0) < OW)):
+        raise ValueError(f"out: expected a {page.dtype} ({OH}, {OW}) view on the page's device with contiguous, non-overlapping rows")
+    _lib.check(_lib.lib().acai_page_warp(page.data_ptr(), u8, H, W, pitch, (ctypes.c_int64 * 9)(*coef), float(fill), out.data_ptr(), OH, OW,
+                                         out.stride(0) if OH > 1 else OW, _st(page)), "acai_page_warp")
+    return out
+
+
 # ---- camera augmentation (csrc/augment.hip) ---------------------------------------------------------------------------------------------
 def augment_table(entries, device):
     """A list of `_lib.AcaiAugImage` -> the read-only descriptor table in device memory (a uint8 tensor): the one upload of a call."""

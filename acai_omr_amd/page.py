@@ -10,8 +10,11 @@ average confidence (acai_omr/ui/routes.py: `setup_inference` :108-129, `multiple
                             ops.page_systems; the reference has no detector);
   * `estimate_skew`, `deskew_pages`   opt-in, in front of the detection: the skew of a page estimated on the device and the page turned level
                             (ops.page_strips, ops.page_skew_scores, ops.page_rotate; the reference has a person draw the boxes instead);
-  * `flatten_pages`         opt-in, in front of everything else: the paper's brightness estimated per tile on the device and divided out
-                            of the page (ops.page_tile_levels, ops.page_flatten; the reference reads the photo as it comes);
+  * `flatten_pages`         opt-in, in front of deskew and detection: the paper's brightness estimated per tile on the device and divided
+                            out of the page (ops.page_tile_levels, ops.page_flatten; the reference reads the photo as it comes);
+  * `find_page_quad`, `rectify_pages`   opt-in, in front of everything else: the outline of the sheet found in the photo - where the paper
+                            begins and ends in every row and column on the device, four lines fitted through those points on the host -
+                            and the sheet warped flat (ops.page_extents, ops.page_warp);
   * `split_pages`           every box of every page cut out, resized as `DynamicResize` resizes the crop and written into ONE
                             `PackedPatches` by one launch pair (ops.crop_resize_to_patches) - no crop copies, no per-system launches;
   * `PageResult`            the per-system rows of the decode, joined per page as the service joins them.
@@ -23,10 +26,10 @@ page rotated by more than about one line thickness over `line_frac` of its width
 with them.  `deskew_pages` levels such a page first (`page_inference(..., deskew=True)`): the skew is the candidate angle, of a fixed grid
 up to `SkewConfig.max_angle` <= 15 degrees, along which the sheared row profile of the page is sharpest, refined by a parabola through its
 neighbours, and the page is turned by it with bilinear sampling; `PageResult` then reports boxes in the levelled page and maps points back
-to the page that was passed in.  Not handled: perspective and page curl, EXIF or quarter-turn orientation, a coarse-to-fine angle search,
-and cropping straight from the unrotated page (one resampling fewer).  The defaults of `SkewConfig` rest on the proportions of an engraved
-page, not on data: how well the estimate and the rule do on real scans and photos has not been measured (no such data here); explicit
-boxes remain the fallback.
+to the page that was passed in.  Not handled here: perspective (that is `rectify_pages`) and page curl, EXIF or quarter-turn
+orientation, a coarse-to-fine angle search, and cropping straight from the unrotated page (one resampling fewer).  The defaults of
+`SkewConfig` rest on the proportions of an engraved page, not on data: how well the estimate and the rule do on real scans and photos has
+not been measured (no such data here); explicit boxes remain the fallback.
 
 Every stage decides "ink or paper" with ONE threshold for the whole page (`value / 255 < ink_threshold`), so a page lit unevenly - falloff
 towards the far edge, a vignette, the shadow of the hand and the phone - turns to "ink" wherever its paper falls below it, and bands merge
@@ -34,9 +37,22 @@ across systems.  `flatten_pages` (`page_inference(..., flatten=True)`) divides t
 tile (`FlattenConfig.tile` pixels square), a tile that is mostly ink taking its brightest neighbour's instead, interpolated bilinearly
 between the tile centres; a pixel becomes 255 * p / background.  Deskew, detection and the crops the model reads all see the flattened
 page; geometry does not change.  Not handled: using the flattened page for detection only while cropping from the original, binarisation,
-colour input, the dark table around a page, and ink areas more than two tiles wide in both directions (the rescue reaches one tile).  The
-defaults of `FlattenConfig` were chosen on synthetic shading (ramps, a vignette, hard shadow edges): nothing has been measured on real
-photographs (no such data here), nor how a trained checkpoint reads flattened crops.
+colour input, the dark table around a page (that is `rectify_pages`, which runs first), and ink areas more than two tiles wide in both
+directions (the rescue reaches one tile).  The defaults of `FlattenConfig` were chosen on synthetic shading (ramps, a vignette, hard
+shadow edges): nothing has been measured on real photographs (no such data here), nor how a trained checkpoint reads flattened crops.
+
+Every stage above takes the tensor it is given for the sheet.  A phone photo is a sheet seen at an angle, lying on something darker: the
+table counts as ink in every row, the bands merge and the detector finds one "system".  `rectify_pages`
+(`page_inference(..., rectify=True)`) runs FIRST, so that flatten and deskew see the sheet and not the table: `find_page_quad` asks the
+device where the first and the last run of `RectifyConfig.min_run` paper pixels lies in every row and column, fits a line through each of
+the four sets of points on the host (a least-squares line through the central half, three rounds of keeping what lies within `tol` of it,
+a final line) and intersects them; the sheet is then sampled through the homography that takes an output rectangle, grown by `inset`
+pixels so that no fringe of the table comes along, to that quadrilateral, with exact integer arithmetic on the device.  `PageResult` then
+reports boxes in the rectified (and levelled) page and maps points all the way back.  Not handled: page curl; a sheet lighter than
+paper-coloured surroundings (a white sheet on a white desk has no outline), or one cut off by the frame on more than one side; colour
+input; EXIF and quarter-turn orientation; folding the rectification and the turn into one resampling; batching the stage over pages in
+one launch.  The defaults of `RectifyConfig` were chosen on synthetic quadrilaterals over a noise table: nothing has been measured on real
+photographs (no such data here).
 """
 import math
 from dataclasses import dataclass
@@ -44,7 +60,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import FLATTEN_TILES
+from ._lib import EXTENTS_MAX_RUN, FLATTEN_TILES, PAGE_MAX_H, PAGE_MAX_W
 from .utils import PackedPatches, stringify_lmx_seq
 
 NO_GPU = "acai_omr_amd page input runs on the GPU (HIP page kernels); there is no CPU fallback"
@@ -252,6 +268,181 @@ def flatten_pages(pages, cfg=None):
     return out
 
 
+@dataclass
+class RectifyConfig:
+    """Parameters of `find_page_quad` and `rectify_pages`:
+
+      paper_threshold  a pixel is paper if its value (uint8 / 255) is NOT below this (the ink test of the other stages, negated);
+      min_run          a row or column meets the sheet where this many paper pixels follow one another (1 .. 256)
+                                                                                default (None): max(4, min(H, W) // 100) - specks of
+                                                                                light on the table are shorter, a margin is longer;
+      tol              a point belongs to an edge if it lies within this many pixels of the fitted line (> 0);
+      min_points       an edge must keep at least this many points (>= 2);
+      min_area         the quadrilateral must cover at least this share of the frame (0 .. 1);
+      inset            the output rectangle is grown by this many output pixels on every side before it is mapped to the quadrilateral,
+                       so the rim of the sheet - where a pixel is part table - stays outside (>= 0);
+      out_size         (OH, OW) of the rectified page                            default (None): the longer of each pair of opposite
+                                                                                sides of the quadrilateral, rounded, plus one.
+
+    Anything else: ValueError, when the config is made and again when it is used."""
+    paper_threshold: float = 0.5
+    min_run: Optional[int] = None
+    tol: float = 1.5
+    min_points: int = 16
+    min_area: float = 0.25
+    inset: float = 2
+    out_size: Optional[tuple] = None
+
+    def __post_init__(self):
+        self.check()
+
+    def check(self):
+        num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v   # noqa: E731
+        if not num(self.paper_threshold):
+            raise ValueError(f"RectifyConfig: paper_threshold = {self.paper_threshold!r} is not a number")
+        if self.min_run is not None and (isinstance(self.min_run, bool) or not isinstance(self.min_run, int) or not 1 <= self.min_run <= EXTENTS_MAX_RUN):
+            raise ValueError(f"RectifyConfig: min_run = {self.min_run!r} is not None or an integer in 1 .. {EXTENTS_MAX_RUN}")
+        if not num(self.tol) or not self.tol > 0:
+            raise ValueError(f"RectifyConfig: tol = {self.tol!r} is not a positive number")
+        if isinstance(self.min_points, bool) or not isinstance(self.min_points, int) or self.min_points < 2:
+            raise ValueError(f"RectifyConfig: min_points = {self.min_points!r} is not an integer >= 2")
+        if not num(self.min_area) or not 0 <= self.min_area <= 1:
+            raise ValueError(f"RectifyConfig: min_area = {self.min_area!r} is not a share in 0 .. 1")
+        if not num(self.inset) or not 0 <= self.inset <= 1024:
+            raise ValueError(f"RectifyConfig: inset = {self.inset!r} is not a number in 0 .. 1024")
+        if self.out_size is not None:
+            ok = isinstance(self.out_size, (tuple, list)) and len(self.out_size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in self.out_size)
+            if not ok or not (1 <= self.out_size[0] <= PAGE_MAX_H and 1 <= self.out_size[1] <= PAGE_MAX_W):
+                raise ValueError(f"RectifyConfig: out_size = {self.out_size!r} is not None or (OH, OW) within {PAGE_MAX_H} x {PAGE_MAX_W}")
+
+    def resolved(self, H, W):
+        """min_run for an H x W frame."""
+        self.check()
+        return max(4, min(H, W) // 100) if self.min_run is None else self.min_run
+
+
+def _fit_edge(t, v, tol, min_points):
+    """Points (t_k, v_k) of one edge in the order of t (float64 tensors) -> (a, b) of the line v = a t + b, or None.  The central half by
+    index, n // 4 <= k < n - n // 4, gives the first least-squares line; three times the points (of ALL of the edge's) within tol of the
+    line, measured along v, give the next one."""
+    n = t.numel()
+    keep = torch.zeros(n, dtype=torch.bool)
+    keep[n // 4:n - n // 4] = True
+    for rounds_left in (3, 2, 1, 0):
+        tt, vv = t[keep], v[keep]
+        if tt.numel() < 2 or (rounds_left == 0 and tt.numel() < min_points):
+            return None
+        tm, vm = tt.mean(), vv.mean()
+        dt = tt - tm
+        stt = (dt * dt).sum()
+        if float(stt) == 0.0:
+            return None
+        a = (dt * (vv - vm)).sum() / stt
+        b = vm - a * tm
+        if rounds_left:
+            keep = (v - (a * t + b)).abs() <= tol
+    return float(a), float(b)
+
+
+def _quad_ok(quad, H, W, min_area):
+    """Convex, in the order TL, TR, BR, BL (clockwise as displayed, y down), at least min_area of the frame, and not the frame itself."""
+    cross = []
+    for i in range(4):
+        (ax, ay), (bx, by), (cx, cy) = quad[i], quad[(i + 1) % 4], quad[(i + 2) % 4]
+        cross.append((bx - ax) * (cy - by) - (by - ay) * (cx - bx))
+    (tlx, tly), (trx, try_), (brx, bry), (blx, bly) = quad
+    if not (all(c > 0 for c in cross) and tlx < trx and blx < brx and tly < bly and try_ < bry):
+        return False
+    area = 0.5 * abs(sum(quad[i][0] * quad[(i + 1) % 4][1] - quad[(i + 1) % 4][0] * quad[i][1] for i in range(4)))
+    if area < min_area * H * W:
+        return False
+    frame = ((0, 0), (W - 1, 0), (W - 1, H - 1), (0, H - 1))
+    return not all(abs(x - fx) <= 1 and abs(y - fy) <= 1 for (x, y), (fx, fy) in zip(quad, frame))
+
+
+def fit_page_quad(extents, H, W, cfg=None):
+    """`ops.page_extents` of an H x W frame, on the host (a tensor or a list of 2 H + 2 W integers) -> the sheet's corners [TL, TR, BR, BL]
+    as (x, y) floats, or None.  float64 throughout.  The left edge is the points (row_lo[y], y) over the rows with row_hi >= 0, fitted as
+    x = a y + b; the right edge (row_hi[y], y); the top and bottom edges (x, col_lo[x]) and (x, col_hi[x]) over the columns with
+    col_hi >= 0, fitted as y = a x + b (`_fit_edge`); the corners are where the lines meet.  None when an edge keeps fewer than
+    cfg.min_points points, the quadrilateral is not convex or not in that order, covers less than cfg.min_area of the frame, or has all
+    four corners within a pixel of the frame's (the sheet fills the frame: nothing to do)."""
+    cfg = cfg or RectifyConfig()
+    cfg.check()
+    e = torch.as_tensor(extents).to("cpu", torch.float64)
+    if e.numel() != 2 * H + 2 * W:
+        raise ValueError(f"extents: expected {2 * H + 2 * W} values for a {H} x {W} frame, got {e.numel()}")
+    row_lo, row_hi, col_lo, col_hi = e[:H], e[H:2 * H], e[2 * H:2 * H + W], e[2 * H + W:]
+    ys, xs = torch.nonzero(row_hi >= 0).flatten(), torch.nonzero(col_hi >= 0).flatten()
+    yt, xt = ys.to(torch.float64), xs.to(torch.float64)
+    lines = [_fit_edge(t, v, float(cfg.tol), cfg.min_points)
+             for t, v in ((yt, row_lo[ys]), (yt, row_hi[ys]), (xt, col_lo[xs]), (xt, col_hi[xs]))]
+    if any(ln is None for ln in lines):
+        return None
+    left, right, top, bottom = lines
+    quad = []
+    for (a1, b1), (a2, b2) in ((left, top), (right, top), (right, bottom), (left, bottom)):   # x = a1 y + b1 meets y = a2 x + b2
+        d = 1.0 - a1 * a2
+        if d == 0.0:
+            return None
+        x = (a1 * b2 + b1) / d
+        quad.append((x, a2 * x + b2))
+    return quad if _quad_ok(quad, H, W, cfg.min_area) else None
+
+
+def find_page_quad(page, cfg=None):
+    """The outline of the sheet in one photographed page -> [TL, TR, BR, BL] as (x, y) floats in the page's pixels, or None when no sheet
+    is found or the sheet fills the frame (`fit_page_quad` has the rule).  One `ops.page_extents` call (two launches) and ONE device-to-host
+    copy; the fit is float64 on the host."""
+    from . import ops
+    cfg = cfg or RectifyConfig()
+    page = _device_page(page)
+    H, W = page.shape
+    return fit_page_quad(ops.page_extents(page, cfg.paper_threshold, cfg.resolved(H, W)).cpu(), H, W, cfg)
+
+
+def _is_quad(q):
+    return (isinstance(q, (list, tuple)) and len(q) == 4
+            and all(isinstance(c, (list, tuple)) and len(c) == 2 and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in c) for c in q))
+
+
+def rectified_size(quad, cfg=None):
+    """(OH, OW) a quad is rectified to: cfg.out_size, or the longer of each pair of opposite sides, rounded, plus one (pixel centres at both
+    ends), within the page limits."""
+    if cfg is not None and cfg.out_size is not None:
+        return tuple(cfg.out_size)
+    (tl, tr, br, bl), d = quad, lambda p, q: math.hypot(p[0] - q[0], p[1] - q[1])   # noqa: E731
+    return (min(max(int(round(max(d(tl, bl), d(tr, br)))) + 1, 1), PAGE_MAX_H), min(max(int(round(max(d(tl, tr), d(bl, br)))) + 1, 1), PAGE_MAX_W))
+
+
+def rectify_pages(pages, quads=None, cfg=None, fill=None):
+    """One page or a list -> (the rectified pages, their quads).  quads: None - `find_page_quad` of every page with cfg - or one quad
+    [TL, TR, BR, BL] for all pages, or a list with one per page in which an entry may be None (a UI lets its user tap the corners).  A page
+    with a quad is sampled through `ops.homography_q30(quad, size, cfg.inset)` into a new page of `rectified_size(quad, cfg)` (one launch,
+    ops.page_warp; fill: what lies outside the photo, default the paper); a page whose quad is None is returned as it is, with no launch."""
+    from . import ops
+    cfg = cfg or RectifyConfig()
+    cfg.check()
+    pages, _ = _page_lists(pages, None)
+    pages = [_device_page(p) for p in pages]
+    if quads is None:
+        quads = [find_page_quad(p, cfg) for p in pages]
+    elif _is_quad(quads):
+        quads = [quads] * len(pages)
+    quads = list(quads)
+    if len(quads) != len(pages) or not all(q is None or _is_quad(q) for q in quads):
+        raise ValueError(f"{len(pages)} pages but {len(quads)} quads (each None or four (x, y) corners TL, TR, BR, BL)")
+    quads = [None if q is None else [(float(x), float(y)) for x, y in q] for q in quads]
+    out = []
+    for p, q in zip(pages, quads):
+        if q is None:
+            out.append(p)
+        else:
+            size = rectified_size(q, cfg)
+            out.append(ops.page_warp(p, ops.homography_q30(q, size, cfg.inset), size, fill))
+    return out, quads
+
+
 def _pixel_box(box, H, W):
     x0, y0, x1, y1 = (int(v) for v in box)
     if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
@@ -326,16 +517,29 @@ def split_pages(pages, boxes_per_page, resize, dtype=torch.float32):
 class PageResult:
     """What `page_inference` returns.  Rows are systems, in page order and top to bottom within a page:
 
-      boxes        per page, its list of pixel boxes (x0, y0, x1, y1), in the LEVELLED page when the page was deskewed (what was cropped);
-      flattened    per page, whether its illumination was flattened before anything else (what was cropped is then the flattened page);
-      angles       per page, the angle in degrees it was turned by before anything else (0.0: not deskewed);
-      page_sizes   per page, its (H, W): the turn is about the page's centre (may be None when no page was turned);
+      boxes        per page, its list of pixel boxes (x0, y0, x1, y1), in the RECTIFIED and LEVELLED page when the page was rectified or
+                   deskewed (what was cropped);
+      flattened    per page, whether its illumination was flattened (what was cropped is then the flattened page);
+      angles       per page, the angle in degrees it was turned by after rectification and flattening (0.0: not deskewed);
+      page_sizes   per page, the (H, W) of the page that was turned and cropped - the rectified page when it was rectified: the turn is about
+                   its centre (may be None when no page was turned or rectified);
+      quads        per page, the corners [TL, TR, BR, BL] of the sheet in the page as it was passed in, or None: not rectified;
+      source_sizes per page, the (H, W) of the page as it was passed in (page_sizes when not given: nothing was rectified);
+      inset        the `RectifyConfig.inset` the quads were rectified with (the homography is `ops.homography_q30(quad, page_size, inset)`);
       seqs, log_probs, seq_mask   (N, T') as `continuous_inference` returns them, one row per system (None when there is no system at all);
       system_page  the page index of every row;
       sizes, windows   per row, the size (OH, OW) its box was resized to and the window (top, left, ch, cw) of it the model saw."""
 
-    def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=(), angles=None, page_sizes=None, flattened=None):
+    def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=(), angles=None, page_sizes=None, flattened=None,
+                 quads=None, source_sizes=None, inset=2):
         self.boxes, self.seqs, self.log_probs, self.seq_mask = boxes, seqs, log_probs, seq_mask
+        self.quads = [None] * len(boxes) if quads is None else [None if q is None else [(float(x), float(y)) for x, y in q] for q in quads]
+        self.source_sizes = None if source_sizes is None else [tuple(int(v) for v in hw) for hw in source_sizes]
+        self.inset = inset
+        if len(self.quads) != len(boxes) or (self.source_sizes is not None and len(self.source_sizes) != len(boxes)) or (
+                any(q is not None for q in self.quads) and (page_sizes is None or len(page_sizes) != len(boxes))):
+            raise ValueError("PageResult: one quad (or None) and one source size per page, and the page sizes with them when a page was rectified")
+        self._coef = {}
         self.flattened = [False] * len(boxes) if flattened is None else [bool(f) for f in flattened]
         if len(self.flattened) != len(boxes):
             raise ValueError("PageResult: one flattened flag per page")
@@ -343,6 +547,8 @@ class PageResult:
         self.page_sizes = None if page_sizes is None else [tuple(int(v) for v in hw) for hw in page_sizes]
         if len(self.angles) != len(boxes) or (any(self.angles) and (self.page_sizes is None or len(self.page_sizes) != len(boxes))):
             raise ValueError("PageResult: one angle per page, and the page sizes with them when a page was turned")
+        if self.source_sizes is None:   # nothing was rectified: the page that was turned and cropped is the page that was passed in
+            self.source_sizes = self.page_sizes
         self.system_page, self.sizes, self.windows = list(system_page), list(sizes), list(windows)
         self.specials = tuple(specials)   # the ids of <bos>, <eos>, <pad>: what tokens() leaves out
         self._flat = [b for page in boxes for b in page]
@@ -400,24 +606,59 @@ class PageResult:
         return cos_q / 65536.0, sin_q / 65536.0, (W - 1) / 2.0, (H - 1) / 2.0
 
     def _unlevel(self, page, lx, ly):
-        """A point of the levelled page -> the point of the caller's page it was sampled from."""
+        """A point of the levelled page -> the point of the page that was turned (the rectified page, or the caller's) it was sampled from."""
         rot = self._rotation(page)
         if rot is None:
             return lx, ly
         c, s, cx, cy = rot
         return cx + c * (lx - cx) - s * (ly - cy), cy + s * (lx - cx) + c * (ly - cy)
 
+    def _homography(self, page):
+        """The nine integers the kernel rectified `page` with, or None for a page that was not rectified."""
+        if self.quads[page] is None:
+            return None
+        if page not in self._coef:
+            from .ops import homography_q30
+            self._coef[page] = homography_q30(self.quads[page], self.page_sizes[page], self.inset)
+        return self._coef[page]
+
+    def _unrectify(self, page, rx, ry):
+        """A point of the rectified page -> the point of the caller's page it was sampled from: the quantised homography in float64 (the
+        kernel's own source coordinate is this, rounded down to 1 / 256 pixel)."""
+        m = self._homography(page)
+        if m is None:
+            return rx, ry
+        A, B, C, D, E, F, G, H, I = (float(v) for v in m)   # noqa: E741
+        den = G * rx + H * ry + I
+        return (A * rx + B * ry + C) / den, (D * rx + E * ry + F) / den
+
+    def _rectify(self, page, px, py):
+        """The inverse of `_unrectify`: the adjugate of the integer matrix, formed exactly, applied in float64."""
+        m = self._homography(page)
+        if m is None:
+            return px, py
+        A, B, C, D, E, F, G, H, I = m   # noqa: E741
+        adj = [E * I - F * H, C * H - B * I, B * F - C * E, F * G - D * I, A * I - C * G, C * D - A * F, D * H - E * G, B * G - A * H, A * E - B * D]
+        big = max(abs(v) for v in adj) or 1
+        a, b, c, d, e, f, g, h, i = (v / big for v in adj)   # (int / int: correctly rounded whatever the size)
+        den = g * px + h * py + i
+        return (a * px + b * py + c) / den, (d * px + e * py + f) / den
+
+    def _to_source(self, page, lx, ly):
+        return self._unrectify(page, *self._unlevel(page, lx, ly))
+
     def to_page_xy(self, system, x, y):
         """Pixel (x, y) of the tensor the model saw of `system` (its box resized, then cropped to the window) -> pixels (floats) of the page
         the caller passed in: the resize's own map, source = (resized + 0.5) * scale - 0.5 per axis (align_corners = False), shifted by the
-        window and the box, then - for a page that was deskewed - the turn that levelled it, backwards.  With it a `TokenAlignment` of the
-        system can be drawn on the page."""
+        window and the box, then - for a page that was deskewed - the turn that levelled it, backwards, then - for a page that was
+        rectified - the homography it was sampled through.  With it a `TokenAlignment` of the system can be drawn on the page."""
         x0, y0, sx, sy, top, left = self._affine(system)
-        return self._unlevel(self.system_page[system], x0 + (x + left + 0.5) * sx - 0.5, y0 + (y + top + 0.5) * sy - 0.5)
+        return self._to_source(self.system_page[system], x0 + (x + left + 0.5) * sx - 0.5, y0 + (y + top + 0.5) * sy - 0.5)
 
     def from_page_xy(self, system, px, py):
         """The inverse of `to_page_xy`."""
         x0, y0, sx, sy, top, left = self._affine(system)
+        px, py = self._rectify(self.system_page[system], px, py)
         rot = self._rotation(self.system_page[system])
         if rot is not None:   # the exact inverse of the quantised matrix (cos^2 + sin^2 is 1 only to 2^-16)
             c, s, cx, cy = rot
@@ -427,6 +668,6 @@ class PageResult:
 
     def box_corners(self, system):
         """The corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of `system`'s box in the page the caller passed in: the box itself for a page
-        that was not deskewed, a tilted quadrilateral otherwise (for a UI to draw)."""
+        that was neither rectified nor deskewed, a quadrilateral otherwise (for a UI to draw)."""
         x0, y0, x1, y1 = self._flat[system]
-        return [self._unlevel(self.system_page[system], float(x), float(y)) for x, y in ((x0, y0), (x1, y0), (x1, y1), (x0, y1))]
+        return [self._to_source(self.system_page[system], float(x), float(y)) for x, y in ((x0, y0), (x1, y0), (x1, y1), (x0, y1))]

@@ -797,6 +797,41 @@ int acai_page_tile_levels(const void *page, int in_u8, int H, int W, int pitch, 
 int acai_page_flatten(const void *page, int in_u8, int H, int W, int pitch, const uint8_t *levels, int tile, int rq, int floor_level, void *out,
                       int out_pitch, void *stream);
 
+/* ---- page rectification: find the sheet's outline in the photo and warp it flat (csrc/rectify.hip) --------------------------------------
+ * Every page stage above takes the tensor it is given for the sheet; a phone photo is a sheet seen at an angle, lying on something darker.
+ * A page is as acai_page_profile takes it (uint8 or fp32, pitch >= W, the same size limits).  A pixel is PAPER when it is not ink under the
+ * ink test of the stages above at paper_threshold: !(in_sample(p) < paper_threshold).  Everything is defined in integers, the fp32 blend
+ * aside, and no result depends on how the launches are scheduled.  Shifts are arithmetic, divisions marked "floor" round down. */
+#define ACAI_EXTENTS_MAX_RUN 256   /* acai_page_extents: the longest run that can be asked for ... */
+#define ACAI_EXTENTS_TILE_ROWS 64  /* ... and the rows of a column workgroup's chunk (it also reads the min_run - 1 rows above them) */
+
+/* Paper extents, R = min_run in 1 .. ACAI_EXTENTS_MAX_RUN.  out is int32 [2 H + 2 W]:
+ *   out[y]             row_lo[y] = the smallest x with pixels x .. x + R - 1 of row y all paper, W if there is none;
+ *   out[H + y]         row_hi[y] = the largest x with pixels x - R + 1 .. x of row y all paper, -1 if there is none;
+ *   out[2 H + x]       col_lo[x] = the smallest y with pixels y .. y + R - 1 of column x all paper, H if there is none;
+ *   out[2 H + W + x]   col_hi[x] = the largest y with pixels y - R + 1 .. y of column x all paper, -1 if there is none.
+ * Columns behind W (the pitch padding) are never read and end every run.  TWO launches, each reading the page once: a wave per row joins
+ * the run summaries of its lanes' 16-byte units and writes row_lo / row_hi (and the "none" values of the column halves); then workgroups
+ * over (512 bytes of the rows, ACAI_EXTENTS_TILE_ROWS rows) walk their columns down, having also read the R - 1 rows above their chunk (a
+ * run that ends in the chunk may begin there), and lower col_lo / raise col_hi with integer atomic min / max: the same whatever the order.
+ * 16 bytes per lane where base and pitch are multiples of 16 bytes, element by element where not and across W. */
+int acai_page_extents(const void *page, int in_u8, int H, int W, int pitch, float paper_threshold, int min_run, int32_t *out, void *stream);
+
+/* The page seen through the homography coef = {A, B, C, D, E, F, G, H, I} (nine 64-bit integers in host memory, passed by value into the
+ * launch).  Output pixel (x, y) of `out` [OH][out_pitch >= OW] (the input's element type, not the input; OH, OW within the page limits) is
+ * sampled at, all in 64-bit integers,
+ *   den = G x + H y + I,   sxq = floor((A x + B y + C) * 256 / den),   syq = floor((D x + E y + F) * 256 / den),
+ *   ix = sxq >> 8, fx = sxq & 255, iy = syq >> 8, fy = syq & 255,
+ * with the taps and the blend of acai_page_rotate: t00 = (iy, ix), t01 = (iy, ix + 1), t10 = (iy + 1, ix), t11 = (iy + 1, ix + 1), a tap
+ * outside the page reads `fill` (uint8: an integer in 0 .. 255); uint8: ((256 - fy) ((256 - fx) t00 + fx t01) + fy ((256 - fx) t10 + fx t11)
+ * + 32768) >> 16; fp32: the same weights f / 256 in fp32.  So A = E = I = 2^30 and the rest 0 is the identity.  Refused, with an error
+ * that begins "acai_page_warp:": at any of the four output corners (0, 0), (OW - 1, 0), (OW - 1, OH - 1), (0, OH - 1), den <= 0 or
+ * den >= 2^62, or |A x + B y + C| * 256 or |D x + E y + F| * 256 reaching 2^62 (the forms are linear, so the corners bound them over the
+ * whole output); out == page; bad sizes.  The quotients are exact: a double estimate corrected by the integer remainder, the 64-bit
+ * division where the estimate could be off by more than one.  A lane makes 4 consecutive pixels, stepping the forms by A, D, G. */
+int acai_page_warp(const void *page, int in_u8, int H, int W, int pitch, const int64_t coef[9], float fill, void *out, int OH, int OW, int out_pitch,
+                   void *stream);
+
 /* hipGraph helpers (capture on `stream`, replay). */
 int acai_graph_begin(void *stream);
 int acai_graph_end(void *stream, void **graph_exec_out);
