@@ -984,7 +984,7 @@ def gelu_bwd(a, dh):
 def colsum(x, out=None):
     """Column sums of x (fp32).  out: an existing fp32 vector to ADD them to (the kernel accumulates with float atomics)."""
     _chk(x, "x")
-    assert x.dim() == 2
+    assert x.dim() == 2 and x.stride(1) == 1     # the kernel takes a row stride only
     if out is None:
         out = _ZEROS.take(1, x.shape[1], x.device).view(-1)
     else:
@@ -1036,7 +1036,7 @@ def pe_interp_bwd(dout, h_out, w_out, table_shape):
 
 def ce_loss(logits, target, ignore_index, count, want_grad, label_smoothing=0.0):
     _chk(logits, "logits", torch.float32), _chk(target, "target", torch.int64)
-    assert logits.dim() == 2 and target.numel() == logits.shape[0] and target.is_contiguous()
+    assert logits.dim() == 2 and logits.stride(1) == 1 and target.numel() == logits.shape[0] and target.is_contiguous()
     loss = torch.zeros(1, dtype=torch.float32, device=logits.device)
     dl = torch.empty(logits.shape, dtype=torch.float32, device=logits.device) if want_grad else None
     _lib.check(_lib.lib().acai_ce_loss(logits.data_ptr(), logits.stride(0), target.data_ptr(), int(ignore_index), 1.0 / float(count), float(label_smoothing),

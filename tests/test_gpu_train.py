@@ -817,7 +817,9 @@ def test_layernorm_bwd_fused_and_colsum_vec(dev, dim):
 
 def test_fused_adamw_matches_torch(dev):
     """FusedAdamW (one HIP launch for every tensor) against torch.optim.AdamW over several steps: param groups with their own lr / weight decay
-    (the layer-wise LR groups of models.py:761-781), an LR schedule, a frozen parameter, odd sizes and unaligned views, state_dict round trip."""
+    (the layer-wise LR groups of models.py:761-781), an LR schedule, a frozen parameter, odd sizes, state_dict round trip.
+    (Every tensor here is its own, 16-byte aligned allocation; unaligned views, which take the kernel's scalar branch, are in
+    tests/test_gpu_row_kernels.py::test_fused_adamw.)"""
     from acai_omr_amd.optim import FusedAdamW
     g = torch.Generator().manual_seed(4)
     shapes = [(1024, 768), (768,), (3, 5), (17,), (40000,), (1,)]
