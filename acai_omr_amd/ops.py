@@ -76,6 +76,8 @@ def layernorm(x, w, b, eps, want_f32=True, want_bf16=False, out_f32=None):
     y32 = (out_f32 if out_f32 is not None else torch.empty_like(x)) if want_f32 else None
     y16 = torch.empty(rows, dim, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
     assert w.numel() == dim and b.numel() == dim and w.dtype == torch.float32 and b.dtype == torch.float32
+    if rows == 0:       # an empty tensor's data_ptr() is null, which the C entry point refuses before it looks at rows
+        return y32, y16
     _lib.check(_lib.lib().acai_layernorm_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), float(eps), _p(y32), _p(y16), rows, dim, _st()),
                "acai_layernorm_fwd")
     return y32, y16
@@ -202,6 +204,8 @@ def cast_bf16(x):
     _chk(x, "x", torch.float32)
     assert x.is_contiguous()
     y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    if x.numel() == 0:
+        return y
     _lib.check(_lib.lib().acai_cast_f32_bf16(x.data_ptr(), y.data_ptr(), x.numel(), _st()), "acai_cast_f32_bf16")
     return y
 
@@ -601,6 +605,8 @@ def gather_rows(table, idx, add=None, out=None):
     assert out.is_contiguous() and out.shape == (rows, dim)
     if add is not None:
         assert add.shape == (rows, dim) and add.is_contiguous() and add.dtype == torch.float32
+    if rows == 0:
+        return out
     _lib.check(_lib.lib().acai_gather_rows(table.data_ptr(), idx.data_ptr(), _p(add), out.data_ptr(), rows, dim, _st()), "acai_gather_rows")
     return out
 
