@@ -30,6 +30,9 @@ class AcaiAdamWTensor(Structure):
                 ("bias_c1", c_float), ("bias_c2_sqrt", c_float)]
 
 
+GRAD_NORM_TOTAL, GRAD_NORM_COEF, GRAD_NORM_FINITE, GRAD_NORM_WORDS = 0, 1, 2, 4   # the result block of acai_grad_norm (ACAI_GRAD_NORM_*)
+
+
 class AcaiCastEntry(Structure):
     _fields_ = [("src", c_void_p), ("dst16", c_void_p), ("dst16t", c_void_p), ("dst32r", c_void_p), ("rows", c_int32), ("cols", c_int32),
                 ("tile0", c_int32), ("pad_", c_int32)]
@@ -148,6 +151,8 @@ _SIGNATURES = {
     "acai_gelu_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "acai_gelu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "acai_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "acai_grad_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "acai_adamw_step_clipped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     "acai_cast_weights": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "acai_gemm_dw": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "acai_colsum": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -482,9 +482,19 @@ extern "C" int acai_dropout_add(const void *x, const float *residual, void *out,
 // in torch's order of operations:  p *= 1 - lr wd;  m += (g - m)(1 - b1);  v = b2 v + (1 - b2) g g;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).
 // HBM-bound: 28 bytes per parameter.  A workgroup owns one chunk of one tensor (chunk table built by the host once per parameter set).
 namespace {
+// CLIPPED: the gradient multiplier is grad_scale * c with c read from the result block of acai_grad_norm, and every workgroup leaves before its
+// first load of p / m / v when that block says the norm is not finite (skip_nonfinite).  The plain form compiles to what it was before.
+template <bool CLIPPED>
 __global__ __launch_bounds__(256) void adamw_kernel(const AcaiAdamWTensor *__restrict__ tensors, const AcaiAdamWGroup *__restrict__ groups,
                                                     const int32_t *__restrict__ chunk_tensor, const int64_t *__restrict__ chunk_off, int chunk_elems,
-                                                    float grad_scale) {
+                                                    float grad_scale, const float *__restrict__ result, int skip_nonfinite, int32_t *skipped) {
+    if constexpr (CLIPPED) {
+        if (skip_nonfinite && result[ACAI_GRAD_NORM_FINITE] == 0.0f) {   // (uniform over the grid: every workgroup reads the same word)
+            if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(skipped, 1);
+            return;
+        }
+        grad_scale *= result[ACAI_GRAD_NORM_COEF];
+    }
     const AcaiAdamWTensor t = tensors[chunk_tensor[blockIdx.x]];
     const AcaiAdamWGroup h = groups[t.group];
     const int64_t off = chunk_off[blockIdx.x];
@@ -519,6 +529,83 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AcaiAdamWTensor *__res
         for (int64_t i = threadIdx.x; i < n; i += 256) upd(p[i], g[i], m[i], v[i]);
     }
 }
+
+// ---- global gradient norm, two launches ------------------------------------------------------------------------------------------------------
+// (torch.nn.utils.clip_grad_norm_ of omr_grpo_train.py:367 is ~a dozen ATen launches, two reads and a write of every gradient.)  Launch 1:
+// the AdamW chunk table again, one workgroup per chunk, sum of g * g in fp64 from the first add (convert, then fma: one fp64 fma per 4 bytes
+// streamed stays far under the HBM time), one double per chunk, no atomics.  Launch 2: one workgroup adds each tensor's partials and then the
+// tensors, every sum in an order fixed by the indices alone, so the result repeats bit for bit.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const AcaiAdamWTensor *__restrict__ tensors, const int32_t *__restrict__ chunk_tensor,
+                                                         const int64_t *__restrict__ chunk_off, int chunk_elems, double *__restrict__ partial) {
+    __shared__ double sw[4];
+    const AcaiAdamWTensor t = tensors[chunk_tensor[blockIdx.x]];
+    const int64_t off = chunk_off[blockIdx.x];
+    const int64_t n = min((int64_t)chunk_elems, t.n - off);
+    const float *g = t.g + off;
+    double s = 0.0;
+    auto add = [&](float gg) {
+        const double d = (double)gg;
+        s = fma(d, d, s);
+    };
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+        const int64_t n4 = n >> 2;
+#pragma unroll 4
+        for (int64_t i = threadIdx.x; i < n4; i += 256) {
+            const f32x4 gv = reinterpret_cast<const f32x4 *>(g)[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) add(gv[e]);
+        }
+        for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) add(g[i]);
+    } else {
+        for (int64_t i = threadIdx.x; i < n; i += 256) add(g[i]);
+    }
+    s = wave_sum_f64(s);
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((sw[0] + sw[1]) + sw[2]) + sw[3];
+}
+
+// One workgroup of 16 waves.  A wave takes tensors wave, wave + 16, ...; its lanes take that tensor's partials lane, lane + 64, ... in chunk
+// order and a butterfly adds the 64 lane sums; lane 0 keeps the wave's running sum over its tensors; thread 0 adds the 16 wave sums.
+__global__ __launch_bounds__(1024) void grad_norm_finish_kernel(const double *__restrict__ partial, const int32_t *__restrict__ tensor_chunk0,
+                                                                int n_tensors, float grad_scale, float max_norm, float *__restrict__ tensor_norm,
+                                                                float *__restrict__ result) {
+    __shared__ double sw[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double scale = fabs((double)grad_scale);
+    double acc = 0.0;
+    for (int i = wave; i < n_tensors; i += 16) {
+        const int c0 = tensor_chunk0[i], c1 = tensor_chunk0[i + 1];
+        double s = 0.0;
+        for (int c = c0 + lane; c < c1; c += 64) s += partial[c];
+        s = wave_sum_f64(s);
+        if (tensor_norm && lane == 0) tensor_norm[i] = (float)(scale * sqrt(s));
+        acc += s;
+    }
+    if (lane == 0) sw[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int w = 0; w < 16; ++w) tot += sw[w];
+        const float norm = (float)(scale * sqrt(tot));
+        // torch's formula and order in fp32: clamp(max_norm / (norm + 1e-6), max = 1); the comparison keeps a NaN coefficient a NaN, as clamp does
+        float coef = 1.0f;
+        if (max_norm > 0.0f && max_norm < INFINITY) {
+            coef = max_norm / (norm + 1e-6f);
+            coef = coef > 1.0f ? 1.0f : coef;
+        }
+        result[ACAI_GRAD_NORM_TOTAL] = norm;
+        result[ACAI_GRAD_NORM_COEF] = coef;
+        result[ACAI_GRAD_NORM_FINITE] = isfinite(norm) ? 1.0f : 0.0f;
+        result[3] = 0.0f;
+    }
+}
 }  // namespace
 
 extern "C" int acai_adamw_step(const AcaiAdamWTensor *tensors, const AcaiAdamWGroup *groups, const int32_t *chunk_tensor, const int64_t *chunk_off,
@@ -526,8 +613,39 @@ extern "C" int acai_adamw_step(const AcaiAdamWTensor *tensors, const AcaiAdamWGr
     ACAI_CHECK_ARG(tensors && groups && chunk_tensor && chunk_off && n_chunks >= 0 && chunk_elems > 0 && chunk_elems % 4 == 0,
                    "acai_adamw_step: bad arguments");
     if (n_chunks == 0) return 0;
-    hipLaunchKernelGGL(adamw_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, groups, chunk_tensor, chunk_off, chunk_elems, grad_scale);
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, groups, chunk_tensor, chunk_off, chunk_elems,
+                       grad_scale, (const float *)nullptr, 0, (int32_t *)nullptr);
     ACAI_LAUNCH_CHECK("acai_adamw_step");
+    return 0;
+}
+
+extern "C" int acai_grad_norm(const AcaiAdamWTensor *tensors, const int32_t *chunk_tensor, const int64_t *chunk_off, const int32_t *tensor_chunk0,
+                              int n_tensors, int n_chunks, int chunk_elems, float grad_scale, float max_norm, double *workspace, float *tensor_norm,
+                              float *result, void *stream) {
+    ACAI_CHECK_ARG(tensors && chunk_tensor && chunk_off && tensor_chunk0 && result && n_tensors >= 0 && n_chunks >= 0 && (workspace || n_chunks == 0) &&
+                       chunk_elems > 0 && chunk_elems % 4 == 0,
+                   "acai_grad_norm: bad arguments");
+    ACAI_CHECK_ARG((((uintptr_t)workspace) & 7) == 0 && (((uintptr_t)result) & 3) == 0, "acai_grad_norm: workspace / result misaligned");
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunk_tensor, chunk_off, chunk_elems, workspace);
+        ACAI_LAUNCH_CHECK("acai_grad_norm (sums)");
+    }
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const double *)workspace, tensor_chunk0, n_tensors, grad_scale,
+                       max_norm, tensor_norm, result);
+    ACAI_LAUNCH_CHECK("acai_grad_norm");
+    return 0;
+}
+
+extern "C" int acai_adamw_step_clipped(const AcaiAdamWTensor *tensors, const AcaiAdamWGroup *groups, const int32_t *chunk_tensor,
+                                       const int64_t *chunk_off, int n_chunks, int chunk_elems, float grad_scale, const float *result,
+                                       int skip_nonfinite, int32_t *skipped, void *stream) {
+    ACAI_CHECK_ARG(tensors && groups && chunk_tensor && chunk_off && result && n_chunks >= 0 && chunk_elems > 0 && chunk_elems % 4 == 0 &&
+                       (skipped || !skip_nonfinite),
+                   "acai_adamw_step_clipped: bad arguments");
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, groups, chunk_tensor, chunk_off, chunk_elems,
+                       grad_scale, result, skip_nonfinite, skipped);
+    ACAI_LAUNCH_CHECK("acai_adamw_step_clipped");
     return 0;
 }
 

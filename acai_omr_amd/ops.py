@@ -971,6 +971,63 @@ def cast_weights(items):
     return outs
 
 
+GRAD_CHUNK = 16384   # elements per workgroup of the gradient-norm sums (optim.CHUNK: the AdamW step shares its chunk table with them)
+
+
+def chunk_tables(sizes, chunk=GRAD_CHUNK):
+    """The chunk tables of the multi-tensor launches (acai_adamw_step, acai_grad_norm) for tensors of `sizes` elements: per workgroup its tensor
+    and first element, and per tensor its first chunk (n + 1 entries, the last one the chunk count).  Host lists."""
+    ct, co, c0 = [], [], []
+    for i, n in enumerate(sizes):
+        c0.append(len(ct))
+        for off in range(0, n, chunk):
+            ct.append(i)
+            co.append(off)
+    c0.append(len(ct))
+    return ct, co, c0
+
+
+def grad_norm_launch(tensors, chunk_tensor, chunk_off, tensor_chunk0, n_tensors, n_chunks, chunk, grad_scale, max_norm, workspace, want_per_tensor=True):
+    """acai_grad_norm over device tables the caller owns (optim.FusedAdamW: the tables of its step).  workspace: float64 [n_chunks].  Returns
+    (result block fp32 [GRAD_NORM_WORDS], per-tensor norms fp32 [n_tensors] or None), both fresh."""
+    dev = tensors.device
+    assert tensors.dtype == torch.uint8 and tensors.numel() == n_tensors * ctypes.sizeof(_lib.AcaiAdamWTensor)
+    assert chunk_tensor.dtype == torch.int32 and chunk_tensor.numel() == n_chunks and chunk_off.dtype == torch.int64 and chunk_off.numel() == n_chunks
+    assert tensor_chunk0.dtype == torch.int32 and tensor_chunk0.numel() == n_tensors + 1
+    assert workspace.dtype == torch.float64 and workspace.is_contiguous() and workspace.numel() >= n_chunks
+    assert all(t.device == dev for t in (chunk_tensor, chunk_off, tensor_chunk0, workspace))
+    result = torch.empty(_lib.GRAD_NORM_WORDS, dtype=torch.float32, device=dev)
+    norms = torch.empty(n_tensors, dtype=torch.float32, device=dev) if want_per_tensor else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().acai_grad_norm(tensors.data_ptr(), chunk_tensor.data_ptr(), chunk_off.data_ptr(), tensor_chunk0.data_ptr(), n_tensors,
+                                             n_chunks, chunk, float(grad_scale), float(max_norm), workspace.data_ptr(), _p(norms), result.data_ptr(),
+                                             _st()), "acai_grad_norm")
+    return result, norms
+
+
+def grad_norm(tensors, *, grad_scale=1.0, per_tensor=False):
+    """The 2-norm of `grad_scale * t` over all of `tensors` (contiguous fp32 CUDA tensors on one device) as a 0-dim fp32 device tensor, and
+    with per_tensor=True also the fp32 vector of each tensor's own norm.  Two launches, sums in fp64 in a fixed order (bitwise repeatable), no
+    host synchronisation: what `torch.nn.utils.get_total_norm` computes through a foreach norm, a stack and a second norm."""
+    tensors = list(tensors)
+    if not tensors:
+        raise RuntimeError("grad_norm: no tensors")
+    dev = tensors[0].device
+    for t in tensors:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and not t.is_sparse and t.is_contiguous() and t.device == dev):
+            raise RuntimeError("grad_norm: dense contiguous fp32 tensors on one GPU only (the product path has no CPU fallback)")
+    arr = (_lib.AcaiAdamWTensor * len(tensors))()
+    for i, t in enumerate(tensors):
+        arr[i].g, arr[i].n = t.data_ptr(), t.numel()
+    ct, co, c0 = chunk_tables([t.numel() for t in tensors])
+    table = h2d(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8), dev)
+    ctd, cod = h2d(torch.tensor(ct, dtype=torch.int32), dev), h2d(torch.tensor(co, dtype=torch.int64), dev)
+    result, norms = grad_norm_launch(table, ctd, cod, h2d(torch.tensor(c0, dtype=torch.int32), dev), len(tensors), len(ct), GRAD_CHUNK, grad_scale, 0.0,
+                                     torch.empty(len(ct), dtype=torch.float64, device=dev), want_per_tensor=per_tensor)
+    total = result[_lib.GRAD_NORM_TOTAL]
+    return (total, norms) if per_tensor else total
+
+
 def gelu_fwd(a):
     _chk(a, "a")
     assert a.is_contiguous()

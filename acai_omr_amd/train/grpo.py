@@ -15,12 +15,15 @@ Same names and argument orders as the reference, so code written for omr_grpo_tr
     rollouts themselves can be constrained by it (grpo_update(grammar=), validation_loop(grammar=));
   * rollouts may go through continuously refilled decode rows instead of one static batch (grpo_update(rollout_slots=...), and always in
     validation_loop): the same draws per rollout, no B * G <= max batch size limit, and a rollout that never draws <eos> does not hold the
-    finished ones' rows to max_actions."""
+    finished ones' rows to max_actions;
+  * grpo_update(fused_clip=True) clips inside the fused AdamW step (optim.FusedAdamW.step(max_grad_norm=1.0)) instead of through
+    torch.nn.utils.clip_grad_norm_; off by default, the reference's call stays."""
 from dataclasses import dataclass
 
 import torch
 
 from .. import ops
+from ..optim import FusedAdamW
 from . import autograd_path as AP
 
 
@@ -288,14 +291,19 @@ def _rollouts_continuous(old_policy, img_latent, latent_attention_mask, group_si
 
 
 def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOConfig, ce_loss_fn, device, logger=None, counter=None, *, reward_fn,
-                uniforms=None, rollout_slots=None, grammar=None):
+                uniforms=None, rollout_slots=None, grammar=None, fused_clip=False):
     """One GRPO minibatch update.  batch: list of (image, target_lmx_seq, target_musicxml_str).  reward_fn(rollouts, rollout_mask, target_lmx_seqs,
     batch) -> (B, G) raw rewards, or (rewards, RewardComponents).  uniforms (R, max_actions): the rollout draws (cached_forward_rollout_policy).
     rollout_slots: None = one static batch of B * G rollout rows (B * G <= the cache's max batch size); an integer = that many decode rows
     refilled as rollouts finish, for any B * G.  grammar: a grammar.TokenAutomaton that constrains the rollouts
     (cached_forward_rollout_policy(grammar=)): old_policy_log_probs are then the constrained policy's, while the theta logits of the ratio
-    stay unconstrained - pass the same automaton to make_token_reward_fn to reward what it checks.  Returns (avg loss over update epochs, avg CE loss, avg raw reward, avg reward components
+    stay unconstrained - pass the same automaton to make_token_reward_fn to reward what it checks.  fused_clip: clip inside the optimizer's
+    own launches (`optimizer.step(max_grad_norm=1.0)`, optimizer an `optim.FusedAdamW`) instead of `torch.nn.utils.clip_grad_norm_`: one read of
+    the gradients instead of three, a non-finite norm skips the step, and `optimizer.grad_norm` / `clip_coef` / `skipped_steps` report it without
+    a host round trip.  Returns (avg loss over update epochs, avg CE loss, avg raw reward, avg reward components
     or None)."""
+    if fused_clip and not isinstance(optimizer, FusedAdamW):
+        raise ValueError(f"grpo_update: fused_clip needs an optim.FusedAdamW, got {type(optimizer).__name__}")
     rollout_config, reward_config, loss_config, update_config = grpo_config.get_configs()
     dev_type = torch.device(device).type
     pad_idx = old_policy.decoder.pad_idx
@@ -356,8 +364,11 @@ def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOCon
                 logger.log_overall_loss(loss, counter.global_step)
             loss.backward()
             # quirk kept: max_norm is the literal 1.0 of omr_grpo_train.py:367 - UpdateConfig.max_grad_norm is not read
-            torch.nn.utils.clip_grad_norm_(policy_theta.parameters(), max_norm=1.0)
-            optimizer.step()
+            if fused_clip:
+                optimizer.step(max_grad_norm=1.0)
+            else:
+                torch.nn.utils.clip_grad_norm_(policy_theta.parameters(), max_norm=1.0)
+                optimizer.step()
             optimizer.zero_grad()
             if counter is not None:
                 counter.global_step += 1

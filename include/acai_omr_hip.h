@@ -309,6 +309,34 @@ typedef struct AcaiAdamWGroup {
 int acai_adamw_step(const AcaiAdamWTensor *tensors, const AcaiAdamWGroup *groups, const int32_t *chunk_tensor, const int64_t *chunk_off,
                     int n_chunks, int chunk_elems, float grad_scale, void *stream);
 
+/* Global gradient norm over the tensors of an AdamW tensor table, and the AdamW step that clips by it (reference:
+ * torch.nn.utils.clip_grad_norm_(max_norm=1.0) between backward and optimizer.step(), acai_omr/train/omr_grpo_train.py:367).  No host
+ * synchronisation, no write of scaled gradients, no float atomics: the result repeats bit for bit from run to run.
+ *
+ * acai_grad_norm reads only `g` and `n` of tensors[]; chunk_tensor / chunk_off are the tables acai_adamw_step takes, and tensor_chunk0
+ * (n_tensors + 1 int32, device) holds each tensor's first chunk, tensor_chunk0[n_tensors] = n_chunks: the chunks of a tensor are contiguous
+ * and in element order.  workspace: n_chunks doubles (device, 8-byte aligned).  Two launches: per chunk, the sum of g * g in fp64; then one
+ * workgroup adds the chunks of each tensor and the tensors, in fp64 and in a fixed order.  It writes
+ *   tensor_norm[i] (optional, may be NULL)   |grad_scale| * sqrt(sum over tensor i), fp32
+ *   result[ACAI_GRAD_NORM_TOTAL]             N = the norm of grad_scale * g over all tensors, fp32
+ *   result[ACAI_GRAD_NORM_COEF]              c = min(1, max_norm / (N + 1e-6)), in fp32 from the fp32 N (torch's formula and order; a NaN
+ *                                            N gives a NaN c, as torch's clamp does); c = 1 when max_norm is not positive or not finite
+ *   result[ACAI_GRAD_NORM_FINITE]            1.0f if N is finite, 0.0f otherwise
+ * result has ACAI_GRAD_NORM_WORDS floats.
+ *
+ * acai_adamw_step_clipped is acai_adamw_step with the gradient multiplier grad_scale * result[ACAI_GRAD_NORM_COEF].  With skip_nonfinite != 0
+ * and result[ACAI_GRAD_NORM_FINITE] == 0 it leaves parameters and both moments untouched and adds 1 to *skipped (device int32). */
+#define ACAI_GRAD_NORM_TOTAL 0
+#define ACAI_GRAD_NORM_COEF 1
+#define ACAI_GRAD_NORM_FINITE 2
+#define ACAI_GRAD_NORM_WORDS 4
+int acai_grad_norm(const AcaiAdamWTensor *tensors, const int32_t *chunk_tensor, const int64_t *chunk_off, const int32_t *tensor_chunk0,
+                   int n_tensors, int n_chunks, int chunk_elems, float grad_scale, float max_norm, double *workspace, float *tensor_norm,
+                   float *result, void *stream);
+int acai_adamw_step_clipped(const AcaiAdamWTensor *tensors, const AcaiAdamWGroup *groups, const int32_t *chunk_tensor, const int64_t *chunk_off,
+                            int n_chunks, int chunk_elems, float grad_scale, const float *result, int skip_nonfinite, int32_t *skipped,
+                            void *stream);
+
 /* The operand copies autocast makes of the fp32 master weights (torch casts each nn.Linear weight / bias to bf16 on every call under
  * torch.autocast, omr_teacher_force_train.py:112-116; this path caches them per parameter version) for ALL parameters in one launch, after an
  * optimizer step: per entry any of the bf16 copy [rows][cols], the transposed bf16 copy [cols][rows] (the dX GEMM's row-major operand) and
