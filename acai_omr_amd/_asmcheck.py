@@ -2,7 +2,7 @@
 not model.  `_lib.build()` runs them on every (re)compile of the sources concerned and FAILS THE BUILD on a hit; `tools/check_async_regs.py`
 is the command-line form.
 
-1. gemm_nt_pp_kernel / gemm_tn_pp_kernel (gemm.hip): vector-memory loads issued from inline asm (`global_load_dword[x4] vN, ...`: the bias of
+1. gemm_nt_pp_kernel / gemm_tn_pp_kernel (gemm_pp.hip): vector-memory loads issued from inline asm (`global_load_dword[x4] vN, ...`: the bias of
    the tile in flight, the deferred GELU chunks) are invisible to the wait-count pass; their destination registers hold garbage until the
    kernel's own counted `s_waitcnt vmcnt(N)` retires them.  Between such a load and the next `s_waitcnt ... vmcnt(` in layout order no
    instruction may read or write those registers - a register-allocator copy, spill or reuse there reads data that has not landed (the

@@ -11,10 +11,16 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "elementwise.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip"]
+SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
+# AcaiGemmLaunch.kernel (ACAI_GEMM_K_*) and .pp_mode (ACAI_PP_*): what acai_gemm_plan / acai_gemm_last_plan report
+(GEMM_K_REG, GEMM_K_GLDS, GEMM_K_GLDS3, GEMM_K_PERS, GEMM_K_256, GEMM_K_PERS256, GEMM_K_PP, GEMM_K_TN_GLDS, GEMM_K_TN_RING,
+ GEMM_K_TN_PP) = range(10)
+GEMM_KERNEL_NAMES = ("gemm_nt_kernel", "gemm_nt_glds_kernel", "gemm_nt_glds3_kernel", "gemm_nt_pers_kernel", "gemm_nt_256_kernel",
+                     "gemm_nt_pers256_kernel", "gemm_nt_pp_kernel", "gemm_tn_glds_kernel", "gemm_tn_ring_kernel", "gemm_tn_pp_kernel")
+GEMM_PP_OBF, GEMM_PP_GELU, GEMM_PP_AUX1, GEMM_PP_AUX2, GEMM_PP_RES, GEMM_PP_SCALE, GEMM_PP_DEFER, GEMM_PP_AUX3, GEMM_PP_AUX4 = 1, 2, 4, 8, 16, 32, 64, 128, 256
 DEC_CROSS_FP8 = 256   # AcaiDecoder.flags: e4m3fn cross K/V with per-row scales (AcaiDecLayer.k_cross_scale / v_cross_scale)
 
 
@@ -23,6 +29,31 @@ class AcaiDecLayer(Structure):
         "self_in_w", "self_in_b", "self_out_w", "self_out_b", "cross_q_w", "cross_q_b", "cross_out_w", "cross_out_b",
         "lin1_w", "lin1_b", "lin2_w", "lin2_b", "n1_w", "n1_b", "n2_w", "n2_b", "n3_w", "n3_b",
         "k_self", "v_self", "k_cross", "v_cross", "k_cross_scale", "v_cross_scale")]
+
+
+class AcaiGemmQuery(Structure):
+    _fields_ = [(n, c_int) for n in (
+        "elem_size", "epi", "trans_a", "trans_w", "M", "N", "K", "lda", "ldw", "ldc", "ldr", "ldaux",
+        "a_aligned", "w_aligned", "c_aligned", "r_aligned", "aux_aligned", "out_dtype", "flags", "aux_mode",
+        "has_residual", "scale_cols", "want_colsum", "variant", "n_cu")]
+
+
+class AcaiGemmLaunch(Structure):
+    _fields_ = [(n, c_int) for n in ("kernel", "wm", "fast", "pp_mode", "grid", "block", "ksplit", "vec_epi", "row0", "rows", "k0", "k", "colsum")]
+
+
+def gemm_last_plan():
+    """The launches of the calling thread's most recent GEMM entry call (acai_gemm_last_plan), as a list of AcaiGemmLaunch."""
+    out, n = (AcaiGemmLaunch * 2)(), c_int(0)
+    check(lib().acai_gemm_last_plan(out, ctypes.byref(n)), "acai_gemm_last_plan")
+    return [out[i] for i in range(n.value)]
+
+
+def gemm_last_kernels():
+    """gemm_last_plan() as kernel names with the template form that was chosen: "gemm_nt_glds_kernel<wm=2>", "gemm_nt_kernel<fast=0>",
+    "gemm_nt_pp_kernel<mode=33>" (GEMM_PP_* bits); the other kernels by name alone.  What the GPU tests assert after a call."""
+    form = {GEMM_K_GLDS: lambda l: f"<wm={l.wm}>", GEMM_K_REG: lambda l: f"<fast={l.fast}>", GEMM_K_PP: lambda l: f"<mode={l.pp_mode}>"}
+    return [GEMM_KERNEL_NAMES[l.kernel] + form.get(l.kernel, lambda l: "")(l) for l in gemm_last_plan()]
 
 
 class AcaiAdamWTensor(Structure):
@@ -107,6 +138,8 @@ _SIGNATURES = {
                              c_int, c_int, c_int, c_void_p]),
     "acai_gemm_nt_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "acai_gemm_set_variant": (c_int, [c_int]),
+    "acai_gemm_plan": (c_int, [POINTER(AcaiGemmQuery), POINTER(AcaiGemmLaunch), POINTER(c_int)]),
+    "acai_gemm_last_plan": (c_int, [POINTER(AcaiGemmLaunch), POINTER(c_int)]),
     "acai_gemm": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
                           c_int, c_int, c_int, c_void_p]),
     "acai_cross_kv_prefill": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -236,7 +269,7 @@ def build(force=False, verbose=False):
 
     # Sources whose correctness rests on something the compiler does not model (asm loads it cannot see, a counted LDS wait): their generated
     # assembly is checked on every rebuild and a hit FAILS the build (acai_omr_amd/_asmcheck.py; ADVICE r3: the check used to be a manual tool).
-    asm_checks = {"gemm.hip": ["check_untracked_loads"], "attn_fwd64w.hip": ["check_fwd64w_barrier", "check_asm_mfma_operands"],
+    asm_checks = {"gemm_pp.hip": ["check_untracked_loads"], "attn_fwd64w.hip": ["check_fwd64w_barrier", "check_asm_mfma_operands"],
                   "attn_bwd64w.hip": ["check_asm_mfma_operands"], "attn_bwd1p.hip": ["check_asm_mfma_operands"]}
     jobs, to_check = [], []
     for src in srcs:

@@ -89,6 +89,53 @@ int acai_cross_kv_prefill(const void *mem, int ldm, const void *Wkv, int ldw, co
                           const int32_t *row_pos, const int64_t *seq_off, const int32_t *seq_len, void *k_out, void *v_out,
                           int M, int E, int H, int dh, int dhp, int dtype, int flags, void *stream);
 
+/* Which kernels a GEMM call runs.  The selection rule is a pure host function of the query below (csrc/gemm_plan.h): acai_gemm_plan
+ * evaluates it without touching a device, acai_gemm_last_plan reports what the most recent acai_gemm_nt[_ex] / acai_gemm / acai_gemm_dw /
+ * acai_cross_kv_prefill call of the calling thread launched (n = 0 before the first one and after a call with M = 0).  A plan has one
+ * launch, or two: the rows past a multiple of 256 as a second launch (row0 / rows), or the tokens past a multiple of 64 of a weight
+ * gradient as a register-staged second launch (k0 / k).  No reference counterpart. */
+enum {
+    ACAI_GEMM_K_REG = 0,       /* gemm_nt_kernel: register-staged, guarded loads (`fast`: 16-byte chunks) */
+    ACAI_GEMM_K_GLDS = 1,      /* gemm_nt_glds_kernel: two LDS-DMA stages, `wm` = 2 (128x128 tile) or 4 (256x128) */
+    ACAI_GEMM_K_GLDS3 = 2,     /* gemm_nt_glds3_kernel: 256x128, three stages */
+    ACAI_GEMM_K_PERS = 3,      /* gemm_nt_pers_kernel: persistent 256x128 three-stage ring */
+    ACAI_GEMM_K_256 = 4,       /* gemm_nt_256_kernel: 256x256, two stages */
+    ACAI_GEMM_K_PERS256 = 5,   /* gemm_nt_pers256_kernel: persistent 256x256 ring of half-stages */
+    ACAI_GEMM_K_PP = 6,        /* gemm_nt_pp_kernel: ping-pong ring with the register epilogue, instantiation `pp_mode` */
+    ACAI_GEMM_K_TN_GLDS = 7,   /* gemm_tn_glds_kernel: weight gradient, two LDS-DMA stages, whole 64-token tiles only */
+    ACAI_GEMM_K_TN_RING = 8,   /* gemm_tn_ring_kernel: weight gradient, 256x128 three-stage ring */
+    ACAI_GEMM_K_TN_PP = 9      /* gemm_tn_pp_kernel: weight gradient, 256x256 ping-pong, forms the column sums itself */
+};
+/* AcaiGemmLaunch.pp_mode bits (the epilogue form gemm_nt_pp_kernel is instantiated for) */
+enum { ACAI_PP_OBF = 1, ACAI_PP_GELU = 2, ACAI_PP_AUX1 = 4, ACAI_PP_AUX2 = 8, ACAI_PP_RES = 16, ACAI_PP_SCALE = 32,
+       ACAI_PP_DEFER = 64, ACAI_PP_AUX3 = 128, ACAI_PP_AUX4 = 256 };
+typedef struct AcaiGemmQuery {
+    int elem_size;               /* operand element: 2 (bf16) or 4 (fp32) */
+    int epi;                     /* 0: linear epilogue; 1: the cross K/V prefill scatter */
+    int trans_a, trans_w;
+    int M, N, K;
+    int lda, ldw, ldc, ldr, ldaux;
+    int a_aligned, w_aligned, c_aligned, r_aligned, aux_aligned;   /* the operand's base is 16-byte aligned (r / aux: read only when present) */
+    int out_dtype, flags, aux_mode;
+    int has_residual;
+    int scale_cols;
+    int want_colsum;             /* weight gradient: column sums of A are asked for beside it */
+    int variant;                 /* acai_gemm_set_variant */
+    int n_cu;                    /* compute units of the device */
+} AcaiGemmQuery;
+typedef struct AcaiGemmLaunch {
+    int kernel;                  /* ACAI_GEMM_K_* */
+    int wm, fast, pp_mode;       /* template form: K_GLDS / K_REG / K_PP (0 elsewhere) */
+    int grid, block;
+    int ksplit, vec_epi;
+    int row0, rows;              /* output rows [row0, row0 + rows) */
+    int k0, k;                   /* reduction range [k0, k0 + k) */
+    int colsum;                  /* this launch also forms the column sums */
+} AcaiGemmLaunch;
+/* launches_out: room for two launches; *n_out: how many the plan has. */
+int acai_gemm_plan(const AcaiGemmQuery *query, AcaiGemmLaunch *launches_out, int *n_out);
+int acai_gemm_last_plan(AcaiGemmLaunch *launches_out, int *n_out);
+
 /* nn.Unfold(P, stride P) on one (1,H,W) fp32 image, transposed to rows of P*P pixels (M:23,48-52);
  * rows are written starting at out + row0*ld (dtype `out_dtype`). */
 int acai_patchify(const float *img, int H, int W, int P, void *out, int ld, int row0, int out_dtype, void *stream);

@@ -1,5 +1,5 @@
 """acai_cross_kv_prefill (the memory cache every decode mode reads) against a float64 reference, on every GEMM kernel its dispatch
-(`launch<T, 1>` in csrc/gemm.hip) can pick: K/V = mem . Wkv^T + bkv, scattered head-major, ragged per sequence and padded from dh to dhp.
+(epi 1 in csrc/gemm_plan.h) can pick: K/V = mem . Wkv^T + bkv, scattered head-major, ragged per sequence and padded from dh to dhp.
 
 Every case checks the values at the addressed elements, that every other element of both buffers (pad lanes d in [dh, dhp), the gaps
 between the sequences' regions, a guard before the first and after the last region) still holds the sentinel it was filled with, and
@@ -9,15 +9,9 @@ bkv ~ N(0,1)):
   bf16  |out - ref| <= 2^-8 |ref| + 1e-4 sqrt(E) + 1e-4           one bf16 ulp (twice the half-ulp of the final rounding) plus the
                                                                   project's fp32-accumulation term; reference on the bf16-rounded operands
 
-Which kernel a shape reaches (the derivations next to the shapes quote launch(); BKG = 64 bf16 / 32 fp32 elements per K-tile,
-EPC = 8 / 4 elements per 16 bytes, N = 2E, K = E):
-  fast   = lda % EPC == 0 && ldw % EPC == 0 && both pointers 16-byte aligned && K % EPC == 0
-  !fast                      -> gemm_nt_kernel<FAST = false>
-  fast && K % BKG != 0       -> gemm_nt_kernel<FAST = true>
-  fast && K % BKG == 0       -> the LDS-DMA kernels: nwg4 = cdiv(M,256) * cdiv(N,128), nwg256 = cdiv(M,256) * cdiv(N,256), ktiles = K / BKG;
-                                auto: nwg4 >= 512 ? (ktiles <= 24 ? 4 : (bf16 && ktiles >= 64 ? ... : 3)) : 1; the steps to 6 / 7 are
-                                EPI == 0 only; a pinned 5 / 6 / 7 needs nwg256 >= 8 and a pinned 4 nwg4 >= 8, else 1; 6 and 7 run 5's
-                                kernel when EPI != 0.
+Which kernel a shape reaches is not derived here: the comments next to the shapes say why a shape was chosen, and each test asserts the
+kernel its calls ran (acai_gemm_last_plan; the rule itself is csrc/gemm_plan.h, tested without a GPU in test_gemm_plan_cpu.py).  N = 2E,
+K = E; a K-tile is 64 bf16 / 32 fp32 elements, a 16-byte chunk 8 / 4.
 """
 import math
 
@@ -178,9 +172,12 @@ def _check_one(out, ref, mask, E, dtype, what):
         assert bool((err <= bound).all()), f"{what}: max error / bound {float((err / bound).max()):.3f}"
 
 
-def _check(dev, c, what):
+def _check(dev, c, what, ran=None):
+    """ran: the kernel each call must have launched (_lib.gemm_last_kernels)"""
+    from acai_omr_amd import _lib
     for name in ("bias", "nobias"):
         k, v = _run(dev, c, name == "bias")
+        assert ran is None or _lib.gemm_last_kernels() == [ran], (what, name, _lib.gemm_last_kernels())
         k_ref, v_ref = c[name]
         # (K against the K reference in k_out and V against the V reference in v_out: data in the wrong buffer fails both)
         _check_one(k, k_ref, c["mask"], c["E"], c["dtype"], f"{what} {name} K")
@@ -203,26 +200,28 @@ GENERIC = [
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("H,dh,dhp,E,M,lens", GENERIC, ids=lambda p: "-".join(map(str, p)) if isinstance(p, list) else str(p))
 def test_generic_kernels(dev, H, dh, dhp, E, M, lens, dtype):
-    _check(dev, _case(dev, H, dh, dhp, E, M, dtype, lens=lens), f"E={E} M={M} {dtype}")
+    _check(dev, _case(dev, H, dh, dhp, E, M, dtype, lens=lens), f"E={E} M={M} {dtype}", ran=f"gemm_nt_kernel<fast={int(E % 8 == 0)}>")
 
 
-# E = 64, M = 130 (two row tiles, the second with 2 rows; H = 1, one 64-lane head):
-#  contig / aligned_view: fast, K % BKG == 0 (64 % 64, 64 % 32) -> the LDS-DMA branch; nwg4 = cdiv(130,256) * cdiv(128,128) = 1 < 512
-#                         -> variant 1, gemm_nt_glds_kernel<T, 1, 2>
-#  odd_stride:            lda = 77 -> !fast -> gemm_nt_kernel<FAST = false>
+# E = 64, M = 130 (two row tiles, the second with 2 rows; H = 1, one 64-lane head): a whole number of K-tiles in both types, one small
+# problem -> the 128 x 128 two-stage LDS-DMA kernel for contiguous operands and for an aligned view; a row stride of 77 elements allows no
+# 16-byte chunks -> the register-staged kernel with guarded loads.
 # With H = 1 the position h * len + s does not depend on how heads and positions interleave, so the same shape also runs as four heads of 16.
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("view", ["contig", "odd_stride", "aligned_view"])
 @pytest.mark.parametrize("H,dh", [(1, 64), (4, 16)])
 def test_two_stage_tile_and_memory_views(dev, H, dh, view, dtype):
-    _check(dev, _case(dev, H, dh, dh, 64, 130, dtype, lens=[64, 1, 65], view=view), f"E=64 H={H} M=130 {view} {dtype}")
+    _check(dev, _case(dev, H, dh, dh, 64, 130, dtype, lens=[64, 1, 65], view=view), f"E=64 H={H} M=130 {view} {dtype}",
+           ran="gemm_nt_kernel<fast=0>" if view == "odd_stride" else "gemm_nt_glds_kernel<wm=2>")
 
 
 # ---- the LDS-DMA kernels, each pinned --------------------------------------------------------------------------------------------------
-# M is the smallest count of the form 256 n + 5 with nwg256 = cdiv(M,256) * cdiv(2E,256) >= 8 (then nwg4 = cdiv(M,256) * cdiv(2E,128) >= 8
-# too), so that a pinned 4 / 5 / 6 is not sent back to variant 1; the last 256-row tile holds 5 rows.  K-tiles bf16 / fp32 = E/64 / E/32.
-#  pinned 1 -> gemm_nt_glds_kernel<T, 1, 2> (128 x 128), 2 -> gemm_nt_glds_kernel<T, 1, 4> (256 x 128), 3 -> gemm_nt_glds3_kernel,
-#  4 -> gemm_nt_pers_kernel, 5 and 6 -> gemm_nt_256_kernel (its epilogue takes the wave's block as two 64-row halves)
+# M is the smallest count of the form 256 n + 5 with at least eight 256 x 256 tiles (then at least eight 256 x 128 tiles too), so that a
+# pinned 4 / 5 / 6 is not sent back to variant 1; the last 256-row tile holds 5 rows.  K-tiles bf16 / fp32 = E/64 / E/32.
+# The scatter epilogue has no persistent 256 x 256 ring: 6 runs the 256 x 256 kernel of 5 (its epilogue takes the wave's block as two
+# 64-row halves).
+PINNED_KERNEL = {1: "gemm_nt_glds_kernel<wm=2>", 2: "gemm_nt_glds_kernel<wm=4>", 3: "gemm_nt_glds3_kernel", 4: "gemm_nt_pers_kernel",
+                 5: "gemm_nt_256_kernel", 6: "gemm_nt_256_kernel"}
 PINNED = [
     # N = 256: cdiv(N,256) = 1 -> cdiv(M,256) >= 8 -> M > 1792.  2 / 4 K-tiles.
     (128, 8, 16, 16, 1797),
@@ -240,26 +239,22 @@ PINNED = [
 @pytest.mark.parametrize("E,H,dh,dhp,M", PINNED)
 def test_lds_dma_kernels_pinned(dev, E, H, dh, dhp, M, dtype, variant):
     from acai_omr_amd import _lib
-    assert -(-M // 256) * -(-2 * E // 256) >= 8 and E % 64 == 0
     c = _case(dev, H, dh, dhp, E, M, dtype)
     _lib.check(_lib.lib().acai_gemm_set_variant(variant), "acai_gemm_set_variant")
     try:
-        _check(dev, c, f"variant {variant} E={E} H={H} M={M} {dtype}")
+        _check(dev, c, f"variant {variant} E={E} H={H} M={M} {dtype}", ran=PINNED_KERNEL[variant])
     finally:
         _lib.lib().acai_gemm_set_variant(0)
 
 
 # ---- auto dispatch at batch size: what a rollout batch of 64 images by a few hundred memory tokens runs --------------------------------
-# bf16, E = 512: N = 1024, nwg4 = cdiv(M,256) * 8 >= 512 <=> cdiv(M,256) >= 64 <=> M > 16128; M = 16400 -> nwg4 = 65 * 8 = 520.
-#   ktiles = 512 / 64 = 8 <= 24 -> variant 4; the step back to 1 needs ktiles >= 16; the steps to 6 / 7 are EPI == 0 only; nwg4 >= 8
-#   -> gemm_nt_pers_kernel<bf16_t, 1>.
-# fp32, E = 1024: N = 2048, nwg4 = cdiv(M,256) * 16 >= 512 <=> cdiv(M,256) >= 32 <=> M > 7936; M = 8000 -> nwg4 = 32 * 16 = 512.
-#   ktiles = 1024 / 32 = 32 > 24 and not bf16 -> variant 3 -> gemm_nt_glds3_kernel<float, 1>.
+# bf16, E = 512: N = 1024, M = 16400 is 65 x 8 = 520 tiles of 256 x 128 - the smallest row count of a rollout batch past the 512 tiles from
+#   which the auto rule leaves the 128 x 128 kernel; 8 K-tiles -> the persistent three-stage ring.
+# fp32, E = 1024: N = 2048, M = 8000 is 32 x 16 = 512 such tiles; 32 K-tiles of 32 floats -> the three-stage kernel.
 @pytest.mark.parametrize("dtype,E,H,dh,M", [("bf16", 512, 8, 64, 16400), ("fp32", 1024, 16, 64, 8000)])
 def test_auto_dispatch_at_batch_size(dev, dtype, E, H, dh, M):
-    nwg4, ktiles = -(-M // 256) * -(-2 * E // 128), E // (64 if dtype == "bf16" else 32)
-    assert nwg4 >= 512 and (ktiles <= 24 if dtype == "bf16" else ktiles > 24)
-    _check(dev, _case(dev, H, dh, dh, E, M, dtype, on_device=True, lo=100, hi=400), f"auto E={E} M={M} {dtype}")
+    _check(dev, _case(dev, H, dh, dh, E, M, dtype, on_device=True, lo=100, hi=400), f"auto E={E} M={M} {dtype}",
+           ran="gemm_nt_pers_kernel" if dtype == "bf16" else "gemm_nt_glds3_kernel")
 
 
 # ---- the slot refill's call shape (engine._slot_refill): one sequence, row_seq all zero, a one-element seq_off that is not zero ----------

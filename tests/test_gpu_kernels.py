@@ -46,19 +46,31 @@ def test_gemm_nt(dev, M, N, K, dtype):
 def test_gemm_nt_three_stage_tile(dev, K, dtype, variant):
     """The large-tile LDS-DMA kernels, each pinned in turn (256x128 two-stage, three-stage with counted vmcnt waits, persistent ring across
     tiles, 256x256, persistent 256x256 on the ring of half-stages, 7 = the ping-pong ring with the register epilogue - bf16 only, fp32 falls
-    back to 6): every K-tile count modulo 3, one to many tiles, ragged M / N edges."""
+    back to 6, which for fp32 is the 256x256 kernel): every K-tile count modulo 3, one to many tiles, ragged M / N edges.  Each call must
+    have run the kernel named here; GELU + residual is no ping-pong form and keeps the persistent 256x256 ring under 7."""
     from acai_omr_amd import _lib
     if dtype == "fp32":
         K //= 2   # 32 floats per K-tile: same tile counts
+    pinned = {2: "gemm_nt_glds_kernel<wm=4>", 3: "gemm_nt_glds3_kernel", 4: "gemm_nt_pers_kernel", 5: "gemm_nt_256_kernel",
+              6: "gemm_nt_pers256_kernel" if dtype == "bf16" else "gemm_nt_256_kernel"}
+    pinned[7] = pinned[6]
+    want = {form: [pinned[variant]] for form in ("plain", "gelu_res", "bf16_out", "view")}
+    if variant == 7 and dtype == "bf16":
+        want.update(plain=["gemm_nt_pp_kernel<mode=0>"], bf16_out=["gemm_nt_pp_kernel<mode=1>"], view=["gemm_nt_pp_kernel<mode=0>"])
     _lib.check(_lib.lib().acai_gemm_set_variant(variant), "acai_gemm_set_variant")
     try:
-        _check_gemm_nt(dev, 8192 + 40, 2048 + 24, K, dtype)
+        _check_gemm_nt(dev, 8192 + 40, 2048 + 24, K, dtype, want)
     finally:
         _lib.lib().acai_gemm_set_variant(0)
 
 
-def _check_gemm_nt(dev, M, N, K, dtype):
-    from acai_omr_amd import ops
+def _check_gemm_nt(dev, M, N, K, dtype, want=None):
+    """want: per call form, the kernels that must have run (_lib.gemm_last_kernels)"""
+    from acai_omr_amd import _lib, ops
+
+    def ran(form):
+        if want is not None:
+            assert _lib.gemm_last_kernels() == want[form], (form, _lib.gemm_last_kernels())
     g = torch.Generator().manual_seed(M + N + K)
     a, w = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / math.sqrt(K)
     bias, res = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
@@ -72,19 +84,23 @@ def _check_gemm_nt(dev, M, N, K, dtype):
     base = a.double() @ w.double().t() + bias.double()
     # plain
     y = ops.gemm_nt(ad, wd, bias.to(dev))
+    ran("plain")
     assert (y.cpu().double() - base).abs().max() < (tol if dtype == "fp32" else 1e-4 * K ** 0.5 + 1e-4)
     # gelu + residual, fp32 out
     y = ops.gemm_nt(ad, wd, bias.to(dev), residual=res.to(dev), gelu=True)
+    ran("gelu_res")
     ref = torch.nn.functional.gelu(base.float()).double() + res.double()
     assert (y.cpu().double() - ref).abs().max() < (tol if dtype == "fp32" else 1e-3)
     # bf16 output with autocast-style rounding
     y = ops.gemm_nt(ad, wd, bias.to(dev), out_dtype=torch.bfloat16, round_bf16=True)
+    ran("bf16_out")
     err = (y.cpu().float().double() - base).abs() / (base.abs() + 1)
     assert err.max() < 1e-2
     # strided views (columns of a wider buffer), as the QKV split uses them
     wide = torch.zeros(M, K + 24, device=dev, dtype=ad.dtype)
     wide[:, 8:8 + K] = ad
     y2 = ops.gemm_nt(wide[:, 8:8 + K], wd, bias.to(dev))
+    ran("view")
     y1 = ops.gemm_nt(ad, wd, bias.to(dev))
     assert torch.equal(y1, y2)
 
@@ -447,9 +463,13 @@ def test_gemm_nt_col_scale(dev, dtype, shape):
 @pytest.mark.parametrize("shape", [(136, 264, 4096), (768, 2304, 8192 + 64), (512, 8, 640), (40, 1000, 192), (1024, 1024, 8208), (264, 136, 100)])
 def test_gemm_weight_gradient_form(dev, dtype, shape):
     """dW = dY^T X (both operands contraction-major, split-K atomics into an fp32 gradient that may already hold a value): the LDS-DMA
-    transposing-read kernel (bf16, token count % 64 == 0) and the register-staged form (fp32 / other shapes) against fp64."""
-    from acai_omr_amd import ops
+    transposing-read kernels (bf16: the three-stage ring from 16 64-token tiles on, below that the two-stage kernel, which leaves tokens past
+    a multiple of 64 to a second, register-staged launch) and the register-staged form alone (fp32) against fp64."""
+    from acai_omr_amd import _lib, ops
     M, N, K = shape      # dW is [M, N], K = tokens
+    want = {(136, 264, 4096): ["gemm_tn_ring_kernel"], (768, 2304, 8192 + 64): ["gemm_tn_ring_kernel"], (512, 8, 640): ["gemm_tn_glds_kernel"],
+            (40, 1000, 192): ["gemm_tn_glds_kernel"], (1024, 1024, 8208): ["gemm_tn_ring_kernel"],
+            (264, 136, 100): ["gemm_tn_glds_kernel", "gemm_nt_kernel<fast=1>"]}[shape] if dtype == "bf16" else ["gemm_nt_kernel<fast=1>"]
     g = torch.Generator().manual_seed(M + N + K)
     dy, x = torch.randn(K, M, generator=g), torch.randn(K, N, generator=g)
     dt = torch.bfloat16 if dtype == "bf16" else torch.float32
@@ -458,6 +478,7 @@ def test_gemm_weight_gradient_form(dev, dtype, shape):
     seed = torch.randn(M, N, generator=g)
     out = seed.clone().to(dev)
     ops.gemm(dy.to(dev).to(dt), x.to(dev).to(dt), trans_a=True, trans_w=True, out=out)
+    assert _lib.gemm_last_kernels() == want
     ref = seed.double() + dy.double().t() @ x.double()
     tol = 2e-4 * math.sqrt(K)
     assert (out.cpu().double() - ref).abs().max() < tol, float((out.cpu().double() - ref).abs().max())
@@ -466,6 +487,7 @@ def test_gemm_weight_gradient_form(dev, dtype, shape):
     wide[:, 8:8 + M] = dy.to(dev).to(dt)
     out2 = seed.clone().to(dev)
     ops.gemm(wide[:, 8:8 + M], x.to(dev).to(dt), trans_a=True, trans_w=True, out=out2)
+    assert _lib.gemm_last_kernels() == want
     assert (out2.cpu().double() - ref).abs().max() < tol
 
 
@@ -476,9 +498,15 @@ def test_gemm_nt_pingpong_epilogues(dev, K, shape):
     """gemm_nt_pp_kernel (variant 7: ping-pong wave groups, swapped 16x16x32 MFMAs, register epilogue with permlane16 exchanges and raw buffer
     stores) in EVERY epilogue form the training steps use, against the persistent 256x256 kernel it replaces (variant 6: LDS-transposed
     epilogue): several tiles per workgroup, ragged last tiles in both directions, strided outputs.  The two kernels sum the 64 products of a
-    K-tile in different orders, so bf16 results may differ in the last bit here and there; fp32 results to contraction rounding."""
+    K-tile in different orders, so bf16 results may differ in the last bit here and there; fp32 results to contraction rounding.
+    Every call under 7 must have run the ping-pong kernel in the form named beside it - but GELU + residual, which is none of its forms and
+    falls back to the persistent 256x256 kernel - and every call under 6 that kernel."""
     from acai_omr_amd import _lib, ops
+    from acai_omr_amd._lib import (GEMM_PP_OBF as OBF, GEMM_PP_GELU as GELU, GEMM_PP_AUX1 as AUX1, GEMM_PP_AUX2 as AUX2, GEMM_PP_AUX3 as AUX3,
+                                   GEMM_PP_AUX4 as AUX4, GEMM_PP_RES as RES, GEMM_PP_SCALE as SCALE)
     M, N = shape
+    pp_form = {"plain_bf16": OBF, "plain_f32": 0, "nobias_f32": 0, "res_f32": RES, "gelu_res_f32": None, "gelu_bf16": OBF | GELU | AUX1,
+               "dgelu_bf16": OBF | AUX2, "gelu3_bf16": OBF | GELU | AUX3, "times_bf16": OBF | AUX4, "scale_bf16": OBF | SCALE, "strided_bf16": OBF}
     g = torch.Generator().manual_seed(M + N + K)
     bf = torch.bfloat16
     a = torch.randn(M, K, generator=g).to(dev).to(bf)
@@ -492,22 +520,30 @@ def test_gemm_nt_pingpong_epilogues(dev, K, shape):
         _lib.check(_lib.lib().acai_gemm_set_variant(variant), "acai_gemm_set_variant")
         try:
             out = {}
-            out["plain_bf16"] = ops.gemm_nt(a, w, b, out_dtype=bf, round_bf16=True)
-            out["plain_f32"] = ops.gemm_nt(a, w, b)
-            out["nobias_f32"] = ops.gemm_nt(a, w)
-            out["res_f32"] = ops.gemm_nt(a, w, b, residual=res, round_bf16=True)
-            out["gelu_res_f32"] = ops.gemm_nt(a, w, b, residual=res, gelu=True, round_bf16=True)
+
+            def nt(key, *args, **kw):
+                y = ops.gemm_nt(*args, **kw)
+                fell_back = variant == 6 or pp_form[key] is None
+                assert _lib.gemm_last_kernels() == (["gemm_nt_pers256_kernel"] if fell_back else [f"gemm_nt_pp_kernel<mode={pp_form[key]}>"]), \
+                    (variant, key, _lib.gemm_last_kernels())
+                return y
+
+            out["plain_bf16"] = nt("plain_bf16", a, w, b, out_dtype=bf, round_bf16=True)
+            out["plain_f32"] = nt("plain_f32", a, w, b)
+            out["nobias_f32"] = nt("nobias_f32", a, w)
+            out["res_f32"] = nt("res_f32", a, w, b, residual=res, round_bf16=True)
+            out["gelu_res_f32"] = nt("gelu_res_f32", a, w, b, residual=res, gelu=True, round_bf16=True)
             pre = torch.empty(M, N, dtype=bf, device=dev)
-            out["gelu_bf16"] = ops.gemm_nt(a, w, b, out_dtype=bf, gelu=True, round_bf16=True, pre_act=pre)
+            out["gelu_bf16"] = nt("gelu_bf16", a, w, b, out_dtype=bf, gelu=True, round_bf16=True, pre_act=pre)
             out["pre_bf16"] = pre
-            out["dgelu_bf16"] = ops.gemm_nt(a, w, out_dtype=bf, round_bf16=True, gelu_grad_of=saved)
+            out["dgelu_bf16"] = nt("dgelu_bf16", a, w, out_dtype=bf, round_bf16=True, gelu_grad_of=saved)
             dgo = torch.empty(M, N, dtype=bf, device=dev)      # round 4: the forward keeps gelu'(pre-activation), the backward multiplies by it
-            out["gelu3_bf16"] = ops.gemm_nt(a, w, b, out_dtype=bf, gelu=True, round_bf16=True, gelu_grad_out=dgo)
+            out["gelu3_bf16"] = nt("gelu3_bf16", a, w, b, out_dtype=bf, gelu=True, round_bf16=True, gelu_grad_out=dgo)
             out["dgelu_kept_bf16"] = dgo
-            out["times_bf16"] = ops.gemm_nt(a, w, out_dtype=bf, round_bf16=True, times=saved)
-            out["scale_bf16"] = ops.gemm_nt(a, w, b, out_dtype=bf, round_bf16=True, col_scale=(N // 3 // 4 * 4, ops.QSCALE(64)))
+            out["times_bf16"] = nt("times_bf16", a, w, out_dtype=bf, round_bf16=True, times=saved)
+            out["scale_bf16"] = nt("scale_bf16", a, w, b, out_dtype=bf, round_bf16=True, col_scale=(N // 3 // 4 * 4, ops.QSCALE(64)))
             view = wide[:, 8:8 + N]
-            ops.gemm_nt(a, w, b, out=view, round_bf16=True)
+            nt("strided_bf16", a, w, b, out=view, round_bf16=True)
             out["strided_bf16"] = view.clone()
             torch.cuda.synchronize()
             return out
@@ -535,10 +571,19 @@ def test_gemm_nt_pingpong_epilogues(dev, K, shape):
 @pytest.mark.parametrize("shape", [(8208, 1024, 1024), (8208, 4096, 1024), (8208, 1024, 4096), (16416, 1024, 1024), (4096 + 8, 2048, 1024)])
 def test_gemm_nt_remainder_rows_split_off(dev, shape):
     """The auto rule launches the rows past a multiple of 256 separately where the full-tile part alone saves a round of tiles (the decoder stream of
-    the teacher-forced step: 16 x 513 = 8208 rows; gemm.hip `split_rem`): every epilogue form the training steps use must come out as from ONE launch of
-    a pinned kernel (variant 6) - the remainder rows above all: their A / C / residual / kept-tensor pointers are advanced by hand."""
+    the teacher-forced step: 16 x 513 = 8208 rows; gemm_plan.h): every epilogue form the training steps use must come out as from ONE launch of
+    a pinned kernel (variant 6) - the remainder rows above all: their A / C / residual / kept-tensor pointers are advanced per launch.
+    On 256 CUs the plan has two launches at N = 4096 (528 tiles of 256 x 256: three rounds for 2.06 of work) and for the 16416 rows (260
+    tiles): the full-tile part on the ping-pong ring in the call's form, the remainder on the 128x128 two-stage kernel.  The 8208 rows at
+    N = 1024 (132 tiles) and the 4104 rows (136 tiles; the 128 full ones do not fill the chip) stay one ping-pong launch."""
     from acai_omr_amd import _lib, ops
+    from acai_omr_amd._lib import (GEMM_PP_OBF as OBF, GEMM_PP_GELU as GELU, GEMM_PP_AUX3 as AUX3, GEMM_PP_AUX4 as AUX4, GEMM_PP_RES as RES,
+                                   GEMM_PP_SCALE as SCALE)
     M, N, K = shape
+    pp_form = {"plain_bf16": OBF, "res_f32": RES, "gelu3_bf16": OBF | GELU | AUX3, "times_bf16": OBF | AUX4, "scale_bf16": OBF | SCALE}
+    on_256_cus = torch.cuda.get_device_properties(dev).multi_processor_count == 256
+    splits = {(8208, 1024, 1024): False, (8208, 4096, 1024): True, (8208, 1024, 4096): False, (16416, 1024, 1024): True,
+              (4096 + 8, 2048, 1024): False}[shape]
     g = torch.Generator().manual_seed(M + N + K)
     bf = torch.bfloat16
     a = torch.randn(M, K, generator=g).to(dev).to(bf)
@@ -551,13 +596,25 @@ def test_gemm_nt_remainder_rows_split_off(dev, shape):
         _lib.check(_lib.lib().acai_gemm_set_variant(variant), "acai_gemm_set_variant")
         try:
             out = {}
-            out["plain_bf16"] = ops.gemm_nt(a, w, b, out_dtype=bf, round_bf16=True)
-            out["res_f32"] = ops.gemm_nt(a, w, b, residual=res, round_bf16=True)
+
+            def nt(key, *args, **kw):
+                y = ops.gemm_nt(*args, **kw)
+                ran = _lib.gemm_last_kernels()
+                if variant == 6:
+                    assert ran == ["gemm_nt_pers256_kernel"], (key, ran)
+                elif on_256_cus:
+                    assert ran == [f"gemm_nt_pp_kernel<mode={pp_form[key]}>"] + (["gemm_nt_glds_kernel<wm=2>"] if splits else []), (key, ran)
+                    rows = [(l.row0, l.rows) for l in _lib.gemm_last_plan()]
+                    assert rows == ([(0, M - M % 256), (M - M % 256, M % 256)] if splits else [(0, M)]), (key, rows)
+                return y
+
+            out["plain_bf16"] = nt("plain_bf16", a, w, b, out_dtype=bf, round_bf16=True)
+            out["res_f32"] = nt("res_f32", a, w, b, residual=res, round_bf16=True)
             dgo = torch.full((M, N), 9.0, dtype=bf, device=dev)
-            out["gelu3_bf16"] = ops.gemm_nt(a, w, b, out_dtype=bf, gelu=True, round_bf16=True, gelu_grad_out=dgo)
+            out["gelu3_bf16"] = nt("gelu3_bf16", a, w, b, out_dtype=bf, gelu=True, round_bf16=True, gelu_grad_out=dgo)
             out["dgelu_kept_bf16"] = dgo
-            out["times_bf16"] = ops.gemm_nt(a, w, out_dtype=bf, round_bf16=True, times=saved)
-            out["scale_bf16"] = ops.gemm_nt(a, w, b, out_dtype=bf, round_bf16=True, col_scale=(N // 3 // 4 * 4, ops.QSCALE(64)))
+            out["times_bf16"] = nt("times_bf16", a, w, out_dtype=bf, round_bf16=True, times=saved)
+            out["scale_bf16"] = nt("scale_bf16", a, w, b, out_dtype=bf, round_bf16=True, col_scale=(N // 3 // 4 * 4, ops.QSCALE(64)))
             torch.cuda.synchronize()
             return out
         finally:
@@ -593,9 +650,12 @@ def test_gemm_nt_pingpong_deferred_gelu(dev, shape):
     def run(variant):
         _lib.check(_lib.lib().acai_gemm_set_variant(variant), "acai_gemm_set_variant")
         try:
+            defer = _lib.GEMM_PP_DEFER if variant == 8 else 0   # both calls must have run the ping-pong kernel, in the deferred form only under 8
             pre = torch.empty(M, N, dtype=bf, device=dev)
             y = ops.gemm_nt(a, w, b, out_dtype=bf, gelu=True, round_bf16=True, pre_act=pre)
+            assert _lib.gemm_last_kernels() == [f"gemm_nt_pp_kernel<mode={_lib.GEMM_PP_OBF | _lib.GEMM_PP_GELU | _lib.GEMM_PP_AUX1 | defer}>"]
             dy = ops.gemm_nt(a, w, out_dtype=bf, round_bf16=True, gelu_grad_of=saved)
+            assert _lib.gemm_last_kernels() == [f"gemm_nt_pp_kernel<mode={_lib.GEMM_PP_OBF | _lib.GEMM_PP_AUX2 | defer}>"]
             torch.cuda.synchronize()
             return y, pre, dy
         finally:
@@ -611,15 +671,20 @@ def test_gemm_nt_pingpong_deferred_gelu(dev, shape):
                                    # ping-pong (4096 x 1024) kernel - rows beyond the end arrive as zeros through the buffer LDS-DMA
                                    (1024, 1024, 8208), (4096, 1024, 8208), (1024, 4096, 8208 + 63), (2048, 1024, 1024 + 1)])
 def test_gemm_weight_gradient_pingpong(dev, shape):
-    """dW = dY^T X on the ping-pong TN kernel (gemm_tn_pp_kernel: 256 x 256 tiles, transposing fragment reads out of the swizzled natural
-    image, split-K atomics from the 16x16 accumulators), long token counts incl. a ragged last 64-token tile, ragged output edges."""
-    from acai_omr_amd import ops
+    """dW = dY^T X on the two ring kernels for long token counts, incl. a ragged last 64-token tile and ragged output edges.  The ping-pong
+    kernel (gemm_tn_pp_kernel: 256 x 256 tiles, transposing fragment reads out of the swizzled natural image, split-K atomics from the 16x16
+    accumulators) takes a shape when a workgroup's K-slice is at least 24 K-steps long once K is split over ~256 workgroups: 3072 x 512 from
+    16384 tokens, 4096 x 1024 from 8208 and 1024 x 4096 from 8271.  The other five run the three-stage ring (gemm_tn_ring_kernel: 256 x 128
+    tiles), whose smaller tile leaves them longer slices."""
+    from acai_omr_amd import _lib, ops
     M, N, K = shape     # dW is [M, N], K tokens
+    want = ["gemm_tn_pp_kernel" if shape in ((3072, 512, 16384), (4096, 1024, 8208), (1024, 4096, 8208 + 63)) else "gemm_tn_ring_kernel"]
     g = torch.Generator().manual_seed(M + N + K)
     dy = torch.randn(K, M, generator=g).to(torch.bfloat16)
     x = (torch.randn(K, N, generator=g) / math.sqrt(K)).to(torch.bfloat16)
     ref = dy.float().double().t() @ x.float().double()
     out = ops.gemm(dy.to(dev), x.to(dev), trans_a=True, trans_w=True, out_dtype=torch.float32)
+    assert _lib.gemm_last_kernels() == want
     err = (out.cpu().double() - ref).abs().max()
     assert err < 2e-3 * float(ref.abs().max()) + 1e-4, float(err)
     # accumulation into an existing gradient (the arena hands out zeroed views; a second product adds on top)

@@ -1,5 +1,5 @@
 """Command-line form of acai_omr_amd/_asmcheck.py (the build runs the same checks and fails on a hit):
-    hipcc -O3 --offload-arch=gfx950 -std=c++17 --cuda-device-only -S -o gemm.s acai_omr_amd/csrc/gemm.hip && python tools/check_async_regs.py gemm.s
+    hipcc -O3 --offload-arch=gfx950 -std=c++17 --cuda-device-only -S -o gemm.s acai_omr_amd/csrc/gemm_pp.hip && python tools/check_async_regs.py gemm.s
     ... -fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form -S -o w.s acai_omr_amd/csrc/attn_fwd64w.hip && python tools/check_async_regs.py --fwd64w w.s
     ... -S -o b.s acai_omr_amd/csrc/attn_bwd64w.hip && python tools/check_async_regs.py --asm-mfma b.s   (also valid for attn_fwd64w.hip)"""
 import os
