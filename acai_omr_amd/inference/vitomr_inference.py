@@ -229,7 +229,7 @@ def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, s
             return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
 
 
-def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None, deskew=None, flatten=None, rectify=None):
+def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None, orient=None, deskew=None, flatten=None, rectify=None):
     """Whole pages in, their systems decoded as one batch (an extension; the reference's service crops hand-drawn boxes with PIL and decodes
     them one by one, acai_omr/ui/routes.py:93-129) -> a `page.PageResult`.
     pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1].  boxes: None - the systems are found on the device
@@ -258,13 +258,46 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     which the sheet fills, is left as it is.  Boxes the caller supplies refer to the RECTIFIED page, and then the levelled one.  The
     result's `quads` and `source_sizes` say what was cut from what, `page_sizes` is the size of the rectified pages, and `to_page_xy` /
     `from_page_xy` / `box_corners` go the whole way back to the pages as they were passed in.  Not handled: page curl, a sheet lighter
-    than its surroundings or cut off by the frame on more than one side, colour input, EXIF and quarter-turn orientation.  Chosen on
-    synthetic quadrilaterals over a noise table; not measured on real photographs."""
+    than its surroundings or cut off by the frame on more than one side.  Chosen on synthetic quadrilaterals over a noise table; not
+    measured on real photographs.
+    orient (an extension, default None = off, as is False: with single-channel pages the path above, unchanged, no launch added): colour
+    input and EXIF / quarter-turn orientation.  A page may then also be a decoded colour photo, uint8 (H, W, 3), (H, W, 4) or (3, H, W)
+    (page.ingest_pages says how shapes are read) - also with orient=None, where it is only made grey - and orient is the photo's EXIF
+    orientation code 1 .. 8, one for all pages or a list with one per page (anything PIL's `ImageOps.exif_transpose` would apply), or
+    True or a `page.OrientConfig`: the tag is missing, and one of the codes 1, 3, 6, 8 is estimated per photo on the device
+    (page.estimate_orientation: sideways from row against column profiles, upside down from the ink at the two ends of the systems - a
+    heuristic chosen on synthetic pages, not measured on real photographs; the EXIF code remains the primary path).  The photo is uploaded
+    as it is and ONE launch per photo makes the grey, upright page (page.ingest_pages) before everything else: the order is ingest ->
+    rectify -> flatten -> deskew -> detect.  The estimate is a function of the photo alone: it is made on a temporary that went through
+    rectify (when the outline is to be found) and flatten if those were asked for, the photo is then ingested with that code and the path
+    above runs, so orient=True gives, bit for bit, what orient=<the estimated codes> gives.  Boxes and quads the caller supplies refer
+    to the UPRIGHT page.  The result's `orientations` says which code every page was turned by, `source_sizes` is the size of the photos
+    as passed in, and `to_page_xy` / `from_page_xy` / `box_corners` go back through the turn to the photo's own pixels.  Anything else for
+    orient is a TypeError, a code outside 1 .. 8 a ValueError.  Not handled: float colour input, mirrored photos without a tag, reading
+    the tag out of a file (PIL or any decoder gives the number), JPEG decoding, folding the quarter turn into the rectification warp."""
     from .. import page as pg
     pages, boxes = pg._page_lists(pages, boxes)
     if boxes is not None and len(boxes) != len(pages):
         raise ValueError(f"{len(pages)} pages but boxes for {len(boxes)}")
-    pages = [pg._device_page(p, resize.device) for p in pages]
+    oriented = {}
+    if orient is None or orient is False:
+        pages = pg.ingest_pages(pages, None, device=resize.device)      # (single-channel pages: `pg._device_page` of each, nothing else)
+    else:
+        estimate = orient is True or isinstance(orient, pg.OrientConfig)
+        if not estimate and (isinstance(orient, bool) or not isinstance(orient, (int, list, tuple))):
+            raise TypeError("orient: expected None, a bool, a page.OrientConfig, one EXIF orientation code 1 .. 8 or a list with one per page")
+        codes = None if estimate else pg.orientation_codes(orient, len(pages))
+        photos = [pg._device_photo(p, resize.device) for p in pages]
+        if estimate:
+            codes = []
+            for tmp in pg.ingest_pages(photos):
+                if rectify is True or isinstance(rectify, pg.RectifyConfig):
+                    tmp = pg.rectify_pages(tmp, None, rectify if isinstance(rectify, pg.RectifyConfig) else None)[0][0]
+                if flatten is True or isinstance(flatten, pg.FlattenConfig):
+                    tmp = pg.flatten_pages(tmp, None if flatten is True else flatten)[0]
+                codes.append(pg.estimate_orientation(tmp, orient if isinstance(orient, pg.OrientConfig) else None)[0])
+        oriented = dict(orientations=codes, source_sizes=[pg.photo_size(p) for p in photos])
+        pages = pg.ingest_pages(photos, codes)
     angles, flattened, rectified = None, None, {}
     if rectify is not None and rectify is not False:
         find = rectify is True or isinstance(rectify, pg.RectifyConfig)
@@ -282,7 +315,7 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     if deskew is not None and deskew is not False:
         estimate = deskew is True or isinstance(deskew, pg.SkewConfig)
         pages, angles = pg.deskew_pages(pages, None if estimate else deskew, deskew if isinstance(deskew, pg.SkewConfig) else None)
-    turned = dict(angles=angles, page_sizes=[tuple(p.shape) for p in pages], flattened=flattened, **rectified)
+    turned = dict(angles=angles, page_sizes=[tuple(p.shape) for p in pages], flattened=flattened, **{**rectified, **oriented})
     if boxes is None:
         per_page = [pg.detect_systems(p, detect) for p in pages]
     else:

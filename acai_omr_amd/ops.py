@@ -543,6 +543,112 @@ def page_warp(page, coef, out_size, fill=None, out=None):
 
 
 # ---- camera augmentation (csrc/augment.hip) ---------------------------------------------------------------------------------------------
+# ---- page ingest: colour photos and EXIF / quarter-turn orientation (csrc/ingest.hip) ------------------------------------------------------
+EXIF_TRANSPOSED = (5, 6, 7, 8)        # the orientation codes that swap height and width
+EXIF_INVERSE = {1: 1, 2: 2, 3: 3, 4: 4, 5: 5, 6: 8, 7: 7, 8: 6}   # the code that undoes a code: a quarter turn is undone by the opposite one
+
+
+def exif_code(code):
+    """An EXIF orientation code as an int in 1 .. 8: anything that is not an integer is a TypeError, an integer outside 1 .. 8 a ValueError."""
+    if isinstance(code, bool) or not isinstance(code, int):
+        raise TypeError(f"orientation: expected an EXIF code, an integer in 1 .. 8, got {code!r}")
+    if not 1 <= code <= 8:
+        raise ValueError(f"orientation: {code} is not an EXIF code (1 .. 8)")
+    return code
+
+
+def oriented_size(H, W, code):
+    """(H', W') of an H x W photo once orientation `code` is applied."""
+    return (W, H) if code in EXIF_TRANSPOSED else (H, W)
+
+
+def _photo(image, layout=None):
+    """A decoded photo on the GPU -> (H, W, C, pixel stride, row stride, channel stride), strides in elements.  (H, W); or three
+    dimensions with layout "hwc" (interleaved, C = 1, 3 or 4) or "chw" (planar, C = 1 or 3).  layout None decides by the shape: a leading
+    1 is planar, then a trailing 3 or 4 interleaved, then a leading 3 planar, then a trailing 1 interleaved - so a planar photo 3 or 4
+    pixels wide needs layout="chw" said.  uint8, or single-channel float32.  Any strides (a slice of a larger tensor), none of them 0."""
+    if not torch.is_tensor(image):
+        raise TypeError("image: expected a tensor")
+    _chk(image, "image", rows_contig=False)
+    if image.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"image: expected uint8 or float32, got {image.dtype}")
+    if layout not in (None, "hwc", "chw"):
+        raise ValueError(f"layout: expected None, 'hwc' or 'chw', got {layout!r}")
+    if image.dim() == 2:
+        shape, stride = (*image.shape, 1), (*image.stride(), 1)                                    # (H, W, C), (row, pixel, channel)
+    elif image.dim() == 3:
+        if layout is None:
+            layout = ("chw" if image.shape[0] == 1 else "hwc" if image.shape[2] in (3, 4) else "chw" if image.shape[0] == 3
+                      else "hwc" if image.shape[2] == 1 else None)
+        if layout == "hwc":
+            shape, stride = tuple(image.shape), tuple(image.stride())
+        elif layout == "chw":
+            shape, stride = (image.shape[1], image.shape[2], image.shape[0]), (image.stride(1), image.stride(2), image.stride(0))
+        else:
+            raise TypeError(f"image: a {tuple(image.shape)} tensor is neither (H, W, C) with C in 1, 3, 4 nor (C, H, W) with C in 1, 3")
+    else:
+        raise TypeError("image: expected (H, W), (H, W, C) or (C, H, W)")
+    (H, W, C), (rs, ps, cs) = shape, stride
+    if C not in ((1, 3, 4) if layout != "chw" else (1, 3)):
+        raise TypeError(f"image: {C} channels ({'planar' if layout == 'chw' else 'interleaved'})")
+    if C != 1 and image.dtype != torch.uint8:
+        raise TypeError("image: float colour input is not taken (single-channel float32, or uint8)")
+    if H < 1 or W < 1:
+        raise ValueError("image: empty")
+    if (H > 1 and rs < 1) or (W > 1 and ps < 1) or (C > 1 and cs < 1):
+        raise ValueError("image: a stride of 0 (an expanded tensor)")
+    return H, W, C, max(int(ps), 1), max(int(rs), 1), max(int(cs), 1)
+
+
+@_on_operand_device
+def page_ingest(image, orientation=1, layout=None, out=None):
+    """A decoded photo (`_photo`: uint8 (H, W), (H, W, C), (C, H, W), or single-channel float32, any strides) -> the grey, upright page, a new
+    contiguous (H', W') tensor of the photo's dtype (or `out`, a view of that shape with contiguous rows), in ONE launch.  The grey value
+    is PIL's convert("L"): (19595 R + 38470 G + 7471 B + 32768) >> 16, a fourth channel ignored; a single channel is moved as it is, float32
+    bit for bit.  orientation is an EXIF code 1 .. 8, applied as PIL's ImageOps.exif_transpose applies it (include/acai_omr_hip.h has the
+    eight index maps); 5 .. 8 give a (W, H) page."""
+    code = exif_code(orientation)
+    H, W, C, ps, rs, cs = _photo(image, layout)
+    OH, OW = oriented_size(H, W, code)
+    if out is None:
+        out = torch.empty(OH, OW, dtype=image.dtype, device=image.device)
+    if (not torch.is_tensor(out) or not out.is_cuda or out.device != image.device or out.dtype != image.dtype or tuple(out.shape) != (OH, OW)
+            or out.stride(1) != 1 or (OH > 1 and out.stride(0) < OW)):
+        raise ValueError(f"out: expected a {image.dtype} ({OH}, {OW}) view on the image's device with contiguous, non-overlapping rows")
+    _lib.check(_lib.lib().acai_page_ingest(image.data_ptr(), 1 if image.dtype == torch.uint8 else 0, H, W, C, ps, rs, cs, code, out.data_ptr(),
+                                           out.stride(0) if OH > 1 else OW, _st(image)), "acai_page_ingest")
+    return out
+
+
+@_on_operand_device
+def page_col_profile(page, ink_threshold=0.5):
+    """Column profiles of a page (as `page_profile` takes it) -> (ink, run), int32 [W] each: the number of pixels below ink_threshold in
+    each column and the longest run of consecutive such pixels down it - `page_profile` of the transposed page.  Two launches."""
+    page, H, W, pitch, u8 = _page(page)
+    out = torch.empty(2, W, dtype=torch.int32, device=page.device)
+    work = torch.empty(4 * _lib.col_chunks(H)[1] * W, dtype=torch.int32, device=page.device)
+    _lib.check(_lib.lib().acai_page_col_profile(page.data_ptr(), u8, H, W, pitch, float(ink_threshold), out[0].data_ptr(), out[1].data_ptr(), work.data_ptr(),
+                                                work.numel(), _st(page)), "acai_page_col_profile")
+    return out[0], out[1]
+
+
+@_on_operand_device
+def page_box_ink(page, boxes, ink_threshold=0.5):
+    """The ink count of every rectangle of a device table -> int32 [n]: boxes is a contiguous int32 [n, 4] of (x0, y0, x1, y1) on the page's
+    device (clipped to the page; an empty rectangle counts 0).  One launch for the whole table, none for an empty one."""
+    page, H, W, pitch, u8 = _page(page)
+    if not torch.is_tensor(boxes):
+        raise TypeError("boxes: expected a tensor")
+    _chk(boxes, "boxes", torch.int32)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or not boxes.is_contiguous() or boxes.device != page.device or boxes.shape[0] > 65535:
+        raise ValueError("boxes: expected a contiguous int32 [n, 4] on the page's device, n <= 65535")
+    n = boxes.shape[0]
+    out = torch.empty(n, dtype=torch.int32, device=page.device)
+    _lib.check(_lib.lib().acai_page_box_ink(page.data_ptr(), u8, H, W, pitch, float(ink_threshold), boxes.data_ptr() if n else None, n,
+                                            out.data_ptr() if n else None, _st(page)), "acai_page_box_ink")
+    return out
+
+
 def augment_table(entries, device):
     """A list of `_lib.AcaiAugImage` -> the read-only descriptor table in device memory (a uint8 tensor): the one upload of a call."""
     import ctypes

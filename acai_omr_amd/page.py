@@ -15,6 +15,11 @@ average confidence (acai_omr/ui/routes.py: `setup_inference` :108-129, `multiple
   * `find_page_quad`, `rectify_pages`   opt-in, in front of everything else: the outline of the sheet found in the photo - where the paper
                             begins and ends in every row and column on the device, four lines fitted through those points on the host -
                             and the sheet warped flat (ops.page_extents, ops.page_warp);
+  * `ingest_pages`, `estimate_orientation`   opt-in, the very first step: a decoded COLOUR photo, interleaved or planar, in the layout it
+                            arrived in, made grey with PIL's integer formula and turned upright by its EXIF orientation code in one
+                            launch (ops.page_ingest; the reference does both on the host with PIL, ui/routes.py:98-118), and, for a photo
+                            whose tag was stripped, the quarter turn estimated on the device from the staff lines (ops.page_col_profile,
+                            ops.page_box_ink);
   * `split_pages`           every box of every page cut out, resized as `DynamicResize` resizes the crop and written into ONE
                             `PackedPatches` by one launch pair (ops.crop_resize_to_patches) - no crop copies, no per-system launches;
   * `PageResult`            the per-system rows of the decode, joined per page as the service joins them.
@@ -26,10 +31,10 @@ page rotated by more than about one line thickness over `line_frac` of its width
 with them.  `deskew_pages` levels such a page first (`page_inference(..., deskew=True)`): the skew is the candidate angle, of a fixed grid
 up to `SkewConfig.max_angle` <= 15 degrees, along which the sheared row profile of the page is sharpest, refined by a parabola through its
 neighbours, and the page is turned by it with bilinear sampling; `PageResult` then reports boxes in the levelled page and maps points back
-to the page that was passed in.  Not handled here: perspective (that is `rectify_pages`) and page curl, EXIF or quarter-turn
-orientation, a coarse-to-fine angle search, and cropping straight from the unrotated page (one resampling fewer).  The defaults of
-`SkewConfig` rest on the proportions of an engraved page, not on data: how well the estimate and the rule do on real scans and photos has
-not been measured (no such data here); explicit boxes remain the fallback.
+to the page that was passed in.  Not handled here: perspective (that is `rectify_pages`) and page curl, a quarter-turn (that is
+`ingest_pages`: `SkewConfig.max_angle` stops at 15 degrees), a coarse-to-fine angle search, and cropping straight from the unrotated
+page (one resampling fewer).  The defaults of `SkewConfig` rest on the proportions of an engraved page, not on data: how well the
+estimate and the rule do on real scans and photos has not been measured (no such data here); explicit boxes remain the fallback.
 
 Every stage decides "ink or paper" with ONE threshold for the whole page (`value / 255 < ink_threshold`), so a page lit unevenly - falloff
 towards the far edge, a vignette, the shadow of the hand and the phone - turns to "ink" wherever its paper falls below it, and bands merge
@@ -37,9 +42,10 @@ across systems.  `flatten_pages` (`page_inference(..., flatten=True)`) divides t
 tile (`FlattenConfig.tile` pixels square), a tile that is mostly ink taking its brightest neighbour's instead, interpolated bilinearly
 between the tile centres; a pixel becomes 255 * p / background.  Deskew, detection and the crops the model reads all see the flattened
 page; geometry does not change.  Not handled: using the flattened page for detection only while cropping from the original, binarisation,
-colour input, the dark table around a page (that is `rectify_pages`, which runs first), and ink areas more than two tiles wide in both
-directions (the rescue reaches one tile).  The defaults of `FlattenConfig` were chosen on synthetic shading (ramps, a vignette, hard
-shadow edges): nothing has been measured on real photographs (no such data here), nor how a trained checkpoint reads flattened crops.
+the dark table around a page (that is `rectify_pages`, which runs first), and ink areas more than two tiles wide in both directions (the
+rescue reaches one tile); colour input is made grey first (`ingest_pages`), the shading of the three channels is not estimated apart.
+The defaults of `FlattenConfig` were chosen on synthetic shading (ramps, a vignette, hard shadow edges): nothing has been measured on
+real photographs (no such data here), nor how a trained checkpoint reads flattened crops.
 
 Every stage above takes the tensor it is given for the sheet.  A phone photo is a sheet seen at an angle, lying on something darker: the
 table counts as ink in every row, the bands merge and the detector finds one "system".  `rectify_pages`
@@ -49,10 +55,25 @@ the four sets of points on the host (a least-squares line through the central ha
 a final line) and intersects them; the sheet is then sampled through the homography that takes an output rectangle, grown by `inset`
 pixels so that no fringe of the table comes along, to that quadrilateral, with exact integer arithmetic on the device.  `PageResult` then
 reports boxes in the rectified (and levelled) page and maps points all the way back.  Not handled: page curl; a sheet lighter than
-paper-coloured surroundings (a white sheet on a white desk has no outline), or one cut off by the frame on more than one side; colour
-input; EXIF and quarter-turn orientation; folding the rectification and the turn into one resampling; batching the stage over pages in
-one launch.  The defaults of `RectifyConfig` were chosen on synthetic quadrilaterals over a noise table: nothing has been measured on real
-photographs (no such data here).
+paper-coloured surroundings (a white sheet on a white desk has no outline), or one cut off by the frame on more than one side; folding
+the rectification and the turn into one resampling; batching the stage over pages in one launch.  The defaults of `RectifyConfig` were
+chosen on synthetic quadrilaterals over a noise table: nothing has been measured on real photographs (no such data here).
+
+Every stage above takes ONE channel and a page that stands upright.  A decoded phone photo is (H, W, 3) uint8 - (3, H, W) from a torch
+decoder - and a phone held upright stores its sensor rows sideways and says so in the EXIF orientation tag; without the turn the staff
+lines run down the columns and the detection rule finds nothing.  Colour input and EXIF / quarter-turn orientation: that is
+`ingest_pages` (`page_inference(..., orient=code)`), which runs before everything else: the photo is uploaded as it is and one launch
+writes the grey, upright page - L = (19595 R + 38470 G + 7471 B + 32768) >> 16 as PIL's `convert("L")`, a fourth channel ignored, and the
+index map of `ImageOps.exif_transpose` for the codes 1 .. 8, bit for bit; `PageResult` maps points back through the turn to the pixels of
+the photo.  Where the tag is missing (upload pipelines strip it), `estimate_orientation` (`page_inference(..., orient=True)`) guesses one
+of the codes 1, 3, 6, 8 with two integer decisions.  Sideways: the page has at least `OrientConfig.min_line_rows` line columns (columns
+with an ink run of `line_frac` of the height) and more line columns than line rows.  Upside down: on the page turned level (by code 6 if
+it was sideways), the leftmost `end_frac` of every detected system holds less ink than its rightmost `end_frac`, summed over the systems -
+a system begins with clef, key and time signature and usually a brace, and ends with a thin barline.  That second rule is a HEURISTIC
+chosen on synthetic pages, like the defaults of the other configs: nothing has been measured on real photographs (no such data here); the
+EXIF code remains the primary path.  Not handled: float colour input; mirrored photos without a tag (the estimate never answers 2, 4, 5
+or 7); reading the EXIF tag out of a file (the caller passes the number: PIL or any decoder gives it); JPEG decoding itself; folding the
+quarter turn into the rectification warp (two passes over the page where one could do).
 """
 import math
 from dataclasses import dataclass
@@ -443,6 +464,165 @@ def rectify_pages(pages, quads=None, cfg=None, fill=None):
     return out, quads
 
 
+@dataclass
+class OrientConfig:
+    """Parameters of `estimate_orientation`:
+
+      ink_threshold  a pixel is ink if its value (uint8 / 255) is below this;
+      line_frac      a line row holds an ink run of at least ceil(line_frac * W) pixels, a line column one of ceil(line_frac * H);
+      min_line_rows  a page is sideways only if it has at least this many line columns (and more of them than line rows);
+      end_frac       the ends of a system of width w that are compared are its leftmost and rightmost max(1, round(end_frac * w)) columns;
+      detect         the `DetectConfig` the systems are found with on the page turned level (None: its defaults).
+
+    line_frac, min_line_rows as in `DetectConfig`; end_frac was chosen on synthetic pages (the clef, key and time signature of an engraved
+    system fill about its first eighth): nothing has been measured on real photographs.  Anything else: ValueError."""
+    ink_threshold: float = 0.5
+    line_frac: float = 0.5
+    min_line_rows: int = 5
+    end_frac: float = 0.12
+    detect: Optional[DetectConfig] = None
+
+    def __post_init__(self):
+        self.check()
+
+    def check(self):
+        num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v   # noqa: E731
+        if not num(self.ink_threshold):
+            raise ValueError(f"OrientConfig: ink_threshold = {self.ink_threshold!r} is not a number")
+        if not num(self.line_frac) or not 0 < self.line_frac <= 1:
+            raise ValueError(f"OrientConfig: line_frac = {self.line_frac!r} is not a share in 0 .. 1")
+        if isinstance(self.min_line_rows, bool) or not isinstance(self.min_line_rows, int) or self.min_line_rows < 1:
+            raise ValueError(f"OrientConfig: min_line_rows = {self.min_line_rows!r} is not an integer >= 1")
+        if not num(self.end_frac) or not 0 < self.end_frac <= 0.5:
+            raise ValueError(f"OrientConfig: end_frac = {self.end_frac!r} is not a share in 0 .. 0.5")
+        if self.detect is not None and not isinstance(self.detect, DetectConfig):
+            raise ValueError(f"OrientConfig: detect = {self.detect!r} is not None or a DetectConfig")
+
+
+def _is_single_channel(page):
+    return torch.is_tensor(page) and (page.dim() == 2 or (page.dim() == 3 and page.shape[0] == 1))
+
+
+def _device_photo(page, device=None):
+    """One decoded photo -> the same tensor on the GPU, in the layout and with the strides it came in (a CPU tensor is uploaded once, no
+    host conversion); float types other than fp32 are widened to fp32 (single-channel only: `ops.page_ingest` refuses float colour)."""
+    if not torch.is_tensor(page) or page.dim() not in (2, 3):
+        raise TypeError("expected a photo as a (H,W), (H,W,C) or (C,H,W) tensor")
+    if not torch.cuda.is_available():
+        raise RuntimeError(NO_GPU)
+    if not page.is_cuda:
+        page = page.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+    return page if page.dtype == torch.uint8 else page.to(torch.float32)
+
+
+def photo_size(photo):
+    """(H, W) of a photo as `ingest_pages` reads its shape (a tensor on the device)."""
+    from .ops import _photo
+    return _photo(photo)[:2]
+
+
+def orientation_codes(orientation, n):
+    """None, one EXIF code or one code per page -> the list of n codes (None: all 1).  Not an integer: TypeError; outside 1 .. 8 or the wrong
+    number of them: ValueError."""
+    from .ops import exif_code
+    if orientation is None:
+        return [1] * n
+    if isinstance(orientation, (list, tuple)):
+        if len(orientation) != n:
+            raise ValueError(f"{n} pages but {len(orientation)} orientation codes")
+        return [exif_code(c) for c in orientation]
+    return [exif_code(orientation)] * n
+
+
+def ingest_pages(pages, orientation=None, layout=None, device=None):
+    """One decoded photo or a list -> the list of grey, upright (H', W') pages on the device, uint8 (fp32 for single-channel float input).
+    A photo is (H, W), (1, H, W), interleaved (H, W, C) with C = 1, 3, 4 or planar (C, H, W) with C = 1, 3 (`ops._photo` says how the shape
+    is read; layout = "hwc" / "chw" says it outright), uint8 - float colour is a TypeError.  orientation: None or 1 - grey only - or one
+    EXIF code 1 .. 8 for all photos or a list with one per photo, applied as PIL's `ImageOps.exif_transpose` applies it.  A CPU tensor is
+    uploaded once, in the layout it arrived in: the grey value (PIL's `convert("L")`) and the turn are ONE launch per photo on the device
+    (ops.page_ingest).  A single-channel page with code 1 is returned as `_device_page` returns it: no launch, no copy."""
+    from . import ops
+    pages, _ = _page_lists(pages, None)
+    codes = orientation_codes(orientation, len(pages))
+    out = []
+    for p, c in zip(pages, codes):
+        if c == 1 and layout is None and _is_single_channel(p):
+            out.append(_device_page(p, device))
+        else:
+            out.append(ops.page_ingest(_device_photo(p, device), c, layout))
+    return out
+
+
+def orientation_is_sideways(run_rows, run_cols, H, W, cfg=None):
+    """The first decision of `estimate_orientation`, on the host: run_rows [H] and run_cols [W] are the longest ink runs of the rows and of
+    the columns.  A row is a line row if its run >= ceil(line_frac * W), a column a line column if its run >= ceil(line_frac * H); the page
+    is sideways if it has at least min_line_rows line columns and more line columns than line rows."""
+    cfg = cfg or OrientConfig()
+    rows = sum(1 for v in run_rows if int(v) >= int(math.ceil(cfg.line_frac * W)))
+    cols = sum(1 for v in run_cols if int(v) >= int(math.ceil(cfg.line_frac * H)))
+    return cols >= cfg.min_line_rows and cols > rows
+
+
+def orientation_end_boxes(boxes, cfg=None):
+    """Per system box (x0, y0, x1, y1) its two ends, left then right: the leftmost and the rightmost e = max(1, round(end_frac * w)) columns
+    (Python's rounding) over the box's rows -> a list of 2 n rectangles."""
+    cfg = cfg or OrientConfig()
+    out = []
+    for x0, y0, x1, y1 in boxes:
+        e = max(1, int(round(cfg.end_frac * (x1 - x0))))
+        out += [(x0, y0, x0 + e, y1), (x1 - e, y0, x1, y1)]
+    return out
+
+
+def orientation_up_down(counts):
+    """The second decision: the ink counts of `orientation_end_boxes` -> (upside down, confidence).  With L and R the sums over the left and
+    the right ends, upside down iff R > L (no system, or a tie: upright); confidence = |L - R| / max(L + R, 1)."""
+    left, right = sum(int(v) for v in counts[0::2]), sum(int(v) for v in counts[1::2])
+    return right > left, abs(left - right) / max(left + right, 1)
+
+
+def estimate_orientation(page, cfg=None):
+    """One photo whose EXIF tag is missing -> (code, confidence): the orientation code, one of 1, 3, 6, 8 (mirrored pages do not occur in
+    photos), that `ingest_pages` turns it upright with, and how lopsided the evidence for up against down was, 0.0 .. 1.0.  Colour photos
+    are made grey first (one launch).  Two exact-integer decisions (`orientation_is_sideways`, `orientation_up_down`): the row and the
+    column profile (ops.page_profile, ops.page_col_profile) say whether the staff lines run down the columns; if so the page is turned by
+    code 6 into a temporary (ops.page_ingest); on the page whose lines are level the systems are detected (`detect_systems`) and ONE
+    launch counts the ink of both ends of every system (ops.page_box_ink): a system begins with clef, key and time signature and ends with
+    a thin barline, so the page is upside down iff the right ends hold more ink.  Level and upright: 1; level, upside down: 3; sideways and
+    upright after the code-6 turn: 6; sideways and upside down after it: 8.  Four copies to the host (two profiles, the boxes, the counts).
+    The up / down rule is a heuristic chosen on synthetic pages; nothing has been measured on real photographs.  A blank page, a page
+    without systems and a tie give the code of an upright page with confidence 0.0."""
+    from . import ops
+    cfg = cfg or OrientConfig()
+    cfg.check()
+    if not torch.is_tensor(page):
+        raise TypeError("estimate_orientation: expected one photo as a tensor")
+    page = ingest_pages(page)[0]
+    H, W = page.shape
+    run_rows, run_cols = ops.page_profile(page, cfg.ink_threshold)[1].cpu().tolist(), ops.page_col_profile(page, cfg.ink_threshold)[1].cpu().tolist()
+    sideways = orientation_is_sideways(run_rows, run_cols, H, W, cfg)
+    level = ops.page_ingest(page, 6) if sideways else page
+    rects = orientation_end_boxes(detect_systems(level, cfg.detect), cfg)
+    if not rects:
+        return (6 if sideways else 1), 0.0
+    table = ops.h2d(torch.tensor(rects, dtype=torch.int32), level.device)
+    down, confidence = orientation_up_down(ops.page_box_ink(level, table, cfg.ink_threshold).cpu().tolist())
+    return ((8 if down else 6) if sideways else (3 if down else 1)), confidence
+
+
+def orientation_to_photo_xy(code, source_size, x, y):
+    """A point of the upright page -> the point of the (H, W) = source_size photo it was read from under orientation `code`: the index map
+    of `ops.page_ingest` (integer coordinates are pixel centres, as in every other map here), exact for integers."""
+    H, W = source_size
+    return ((x, y), (W - 1 - x, y), (W - 1 - x, H - 1 - y), (x, H - 1 - y), (y, x), (y, H - 1 - x), (W - 1 - y, H - 1 - x), (W - 1 - y, x))[code - 1]
+
+
+def orientation_from_photo_xy(code, source_size, px, py):
+    """The inverse of `orientation_to_photo_xy`."""
+    H, W = source_size
+    return ((px, py), (W - 1 - px, py), (W - 1 - px, H - 1 - py), (px, H - 1 - py), (py, px), (H - 1 - py, px), (H - 1 - py, W - 1 - px), (py, W - 1 - px))[code - 1]
+
+
 def _pixel_box(box, H, W):
     x0, y0, x1, y1 = (int(v) for v in box)
     if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
@@ -524,14 +704,17 @@ class PageResult:
       page_sizes   per page, the (H, W) of the page that was turned and cropped - the rectified page when it was rectified: the turn is about
                    its centre (may be None when no page was turned or rectified);
       quads        per page, the corners [TL, TR, BR, BL] of the sheet in the page as it was passed in, or None: not rectified;
-      source_sizes per page, the (H, W) of the page as it was passed in (page_sizes when not given: nothing was rectified);
+      source_sizes per page, the (H, W) of the page - the photo - as it was passed in (page_sizes when not given: nothing was rectified
+                   or turned upright);
+      orientations per page, the EXIF orientation code it was turned upright by before anything else (1: as it lay); rectification,
+                   the quads and the angles refer to the upright page, of size `ops.oriented_size(*source_size, code)`;
       inset        the `RectifyConfig.inset` the quads were rectified with (the homography is `ops.homography_q30(quad, page_size, inset)`);
       seqs, log_probs, seq_mask   (N, T') as `continuous_inference` returns them, one row per system (None when there is no system at all);
       system_page  the page index of every row;
       sizes, windows   per row, the size (OH, OW) its box was resized to and the window (top, left, ch, cw) of it the model saw."""
 
     def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=(), angles=None, page_sizes=None, flattened=None,
-                 quads=None, source_sizes=None, inset=2):
+                 quads=None, source_sizes=None, inset=2, orientations=None):
         self.boxes, self.seqs, self.log_probs, self.seq_mask = boxes, seqs, log_probs, seq_mask
         self.quads = [None] * len(boxes) if quads is None else [None if q is None else [(float(x), float(y)) for x, y in q] for q in quads]
         self.source_sizes = None if source_sizes is None else [tuple(int(v) for v in hw) for hw in source_sizes]
@@ -547,6 +730,10 @@ class PageResult:
         self.page_sizes = None if page_sizes is None else [tuple(int(v) for v in hw) for hw in page_sizes]
         if len(self.angles) != len(boxes) or (any(self.angles) and (self.page_sizes is None or len(self.page_sizes) != len(boxes))):
             raise ValueError("PageResult: one angle per page, and the page sizes with them when a page was turned")
+        from .ops import exif_code
+        self.orientations = [1] * len(boxes) if orientations is None else [exif_code(c) for c in orientations]
+        if len(self.orientations) != len(boxes) or (any(c != 1 for c in self.orientations) and self.source_sizes is None):
+            raise ValueError("PageResult: one orientation code per page, and the source sizes with them when a page was turned upright")
         if self.source_sizes is None:   # nothing was rectified: the page that was turned and cropped is the page that was passed in
             self.source_sizes = self.page_sizes
         self.system_page, self.sizes, self.windows = list(system_page), list(sizes), list(windows)
@@ -644,20 +831,29 @@ class PageResult:
         den = g * px + h * py + i
         return (a * px + b * py + c) / den, (d * px + e * py + f) / den
 
+    def _unorient(self, page, ux, uy):
+        """A point of the upright page -> the point of the photo it was read from (`orientation_to_photo_xy`)."""
+        code = self.orientations[page]
+        return (ux, uy) if code == 1 else orientation_to_photo_xy(code, self.source_sizes[page], ux, uy)
+
     def _to_source(self, page, lx, ly):
-        return self._unrectify(page, *self._unlevel(page, lx, ly))
+        return self._unorient(page, *self._unrectify(page, *self._unlevel(page, lx, ly)))
 
     def to_page_xy(self, system, x, y):
         """Pixel (x, y) of the tensor the model saw of `system` (its box resized, then cropped to the window) -> pixels (floats) of the page
         the caller passed in: the resize's own map, source = (resized + 0.5) * scale - 0.5 per axis (align_corners = False), shifted by the
         window and the box, then - for a page that was deskewed - the turn that levelled it, backwards, then - for a page that was
-        rectified - the homography it was sampled through.  With it a `TokenAlignment` of the system can be drawn on the page."""
+        rectified - the homography it was sampled through, then - for a photo that was turned upright - its orientation's index map, to
+        the pixels of the photo as it lay.  With it a `TokenAlignment` of the system can be drawn on the page."""
         x0, y0, sx, sy, top, left = self._affine(system)
         return self._to_source(self.system_page[system], x0 + (x + left + 0.5) * sx - 0.5, y0 + (y + top + 0.5) * sy - 0.5)
 
     def from_page_xy(self, system, px, py):
         """The inverse of `to_page_xy`."""
         x0, y0, sx, sy, top, left = self._affine(system)
+        code = self.orientations[self.system_page[system]]
+        if code != 1:
+            px, py = orientation_from_photo_xy(code, self.source_sizes[self.system_page[system]], px, py)
         px, py = self._rectify(self.system_page[system], px, py)
         rot = self._rotation(self.system_page[system])
         if rot is not None:   # the exact inverse of the quantised matrix (cos^2 + sin^2 is 1 only to 2^-16)

@@ -907,6 +907,39 @@ int acai_page_extents(const void *page, int in_u8, int H, int W, int pitch, floa
 int acai_page_warp(const void *page, int in_u8, int H, int W, int pitch, const int64_t coef[9], float fill, void *out, int OH, int OW, int out_pitch,
                    void *stream);
 
+/* ---- page ingest: colour photos and EXIF / quarter-turn orientation (csrc/ingest.hip) ------------------------------------------------------
+ * The reference makes the grey, upright page on the host with PIL: Image.open(...).convert("L") (acai_omr/ui/routes.py:98,115,
+ * train/datasets.py:32,122) and ImageOps.exif_transpose (ui/routes.py:118).  Here the decoded photo is uploaded as it is and one launch
+ * makes the page, with the same bits.  Everything is defined in integers; no atomics. */
+#define ACAI_COL_CHUNK_ROWS 64   /* acai_page_col_profile: a chunk of rows is max(64, ceil(H / 64)) rows ... */
+#define ACAI_COL_MAX_CHUNKS 64   /* ... so there are ceil(H / that) <= 64 chunks, and `work` holds 4 * chunks * W int32 */
+
+/* src is an image of H rows, W columns and C channels whose element (row r, column c, channel k) lies at src[r row_stride + c pix_stride +
+ * k chan_stride], strides in elements: interleaved (H, W, C), planar (C, H, W), a slice of a larger tensor, all the same kernel.  uint8
+ * (in_u8 = 1) with C = 1, 3 or 4, or fp32 with C = 1.  The grey value of a uint8 pixel is PIL's: the channel itself for C = 1, otherwise
+ * (19595 R + 38470 G + 7471 B + 32768) >> 16 of channels 0, 1, 2 (a fourth channel is ignored, as PIL's RGBA -> L ignores it); an fp32
+ * pixel is moved as 32 bits, whatever they hold.  orientation is an EXIF code, applied as ImageOps.exif_transpose applies it: pixel (y, x)
+ * of `out` [OH][out_pitch >= OW] (uint8, or fp32 for fp32 input; not the source) is the grey value of source element
+ *   1: [y, x]          2: [y, W-1-x]      3: [H-1-y, W-1-x]    4: [H-1-y, x]        and OH x OW = H x W,
+ *   5: [x, y]          6: [H-1-x, y]      7: [H-1-x, W-1-y]    8: [x, W-1-y]        and OH x OW = W x H.
+ * OH <= ACAI_PAGE_MAX_H, OW <= ACAI_PAGE_MAX_W.  ONE launch.  A lane makes 4 consecutive output pixels from 4 C source bytes read as
+ * dwords; codes 5 .. 8 pass a 128 x 128 tile of grey values through LDS so that source rows are read and output rows written whole. */
+int acai_page_ingest(const void *src, int in_u8, int H, int W, int C, int64_t pix_stride, int64_t row_stride, int64_t chan_stride, int orientation,
+                     void *out, int out_pitch, void *stream);
+
+/* Column profiles of a page as acai_page_profile takes it: ink[x] = number of pixels of column x with value < ink_threshold, run[x] = the
+ * longest run of consecutive such pixels down the column: acai_page_profile of the transposed page (the reference has no counterpart; a
+ * page that lies on its side has its staff lines in the columns).  TWO launches: lanes own 4 adjacent columns and walk a chunk of rows
+ * down, leaving (leading run, trailing run, best run, ink) per column and chunk in `work` (work_elems int32, at least 4 * chunks * W, see
+ * ACAI_COL_CHUNK_ROWS); one lane per column then joins its chunks from the top down. */
+int acai_page_col_profile(const void *page, int in_u8, int H, int W, int pitch, float ink_threshold, int32_t *ink, int32_t *run, int32_t *work,
+                          int64_t work_elems, void *stream);
+
+/* out[i] = the number of pixels with value < ink_threshold in rows [y0, y1), columns [x0, x1) of the page, for the n rectangles boxes [n][4]
+ * = (x0, y0, x1, y1) in device memory (clipped to the page on the device; an empty one counts 0).  ONE launch, none for n = 0;
+ * n <= 65535.  The reference has no counterpart: it is how the orientation estimate asks which end of a system holds the clef. */
+int acai_page_box_ink(const void *page, int in_u8, int H, int W, int pitch, float ink_threshold, const int32_t *boxes, int n, int32_t *out, void *stream);
+
 /* hipGraph helpers (capture on `stream`, replay). */
 int acai_graph_begin(void *stream);
 int acai_graph_end(void *stream, void **graph_exec_out);
