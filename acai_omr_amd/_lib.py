@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip"]
+SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -54,6 +54,51 @@ def gemm_last_kernels():
     "gemm_nt_pp_kernel<mode=33>" (GEMM_PP_* bits); the other kernels by name alone.  What the GPU tests assert after a call."""
     form = {GEMM_K_GLDS: lambda l: f"<wm={l.wm}>", GEMM_K_REG: lambda l: f"<fast={l.fast}>", GEMM_K_PP: lambda l: f"<mode={l.pp_mode}>"}
     return [GEMM_KERNEL_NAMES[l.kernel] + form.get(l.kernel, lambda l: "")(l) for l in gemm_last_plan()]
+
+
+# AcaiAttnLaunch.kernel (ACAI_ATTN_K_*), the overrides of acai_attn_set_override (ACAI_ATTN_OV_*: default, lowest, highest value) and the
+# values of ATTN_OV_FWD64 (ACAI_ATTN_FWD64_*)
+(ATTN_K_FWD, ATTN_K_FWD64, ATTN_K_FWD64W, ATTN_K_FWD64_TAIL, ATTN_K_BWD_DQ, ATTN_K_BWD_DKV, ATTN_K_BWD_DQ2, ATTN_K_BWD_DKV2, ATTN_K_BWD64W_DQ,
+ ATTN_K_BWD64W_DKV, ATTN_K_BWD1P) = range(11)
+ATTN_KERNEL_NAMES = ("attn_fwd_kernel", "attn_fwd64_kernel", "attn_fwd64w_kernel", "attn_fwd64_tail_kernel", "attn_bwd_dq_kernel", "attn_bwd_dkv_kernel",
+                     "attn_bwd_dq2_kernel", "attn_bwd_dkv2_kernel", "attn_bwd64w_dq_kernel", "attn_bwd64w_dkv_kernel", "attn_bwd1p_kernel")
+ATTN_OV_TWO_BLOCK, ATTN_OV_FWD64, ATTN_OV_BWD64_WIDE, ATTN_OV_BWD_1P, ATTN_OV_XCD_ORDER, ATTN_OV_COUNT = range(6)
+ATTN_OV_RANGE = ((1, 0, 1), (0, 0, 3), (-1, -1, 3), (1, 0, 1), (-1, -1, 1))
+ATTN_FWD64_AUTO, ATTN_FWD64_NW4, ATTN_FWD64_NW8, ATTN_FWD64_GENERIC = range(4)
+ATTN_REFUSE_PRESCALED, ATTN_REFUSE_ACCUM = 1, 2
+
+
+class AcaiAttnQuery(Structure):
+    _fields_ = [(n, c_int) for n in (
+        "backward", "elem_size", "B", "H", "dh", "max_q", "max_k", "total_q", "total_k", "causal", "accum_dkv", "dropout", "q_prescaled",
+        "ldq", "ldk", "ldv", "ldo", "lddo", "lddq", "lddk", "lddv", "aligned", "cu_k_is_cu_q")] + [("ov", c_int * ATTN_OV_COUNT), ("workspace_bytes", c_int64)]
+
+
+class AcaiAttnLaunch(Structure):
+    _fields_ = [(n, c_int) for n in ("kernel", "elem_size", "dhp", "fast", "drop", "pre", "nq", "waves", "grid_x", "grid_y", "grid_z", "block", "lds_bytes",
+                                     "tail", "tail256", "nblk", "partial_blocks", "equal_len", "rows")]
+
+
+def attn_last_plan():
+    """The launches of the calling thread's most recent acai_attn_varlen_fwd / _bwd[_ws] call (acai_attn_last_plan), as a list of AcaiAttnLaunch."""
+    out, n = (AcaiAttnLaunch * 4)(), c_int(0)
+    check(lib().acai_attn_last_plan(out, ctypes.byref(n)), "acai_attn_last_plan")
+    return [out[i] for i in range(n.value)]
+
+
+def attn_kernel_name(l):
+    """An AcaiAttnLaunch as its kernel's name with the template form that was chosen: "attn_fwd_kernel<bf16,32,fast=1,drop=0,pre=1,nq=2>",
+    "attn_bwd_dq_kernel<fp32,64,fast=0,drop=0,pre=0>", "attn_fwd64_kernel<8>"; the other kernels by name alone.  What the GPU tests assert."""
+    name = ATTN_KERNEL_NAMES[l.kernel]
+    if l.kernel in (ATTN_K_FWD, ATTN_K_BWD_DQ, ATTN_K_BWD_DKV):
+        name += f"<{'bf16' if l.elem_size == 2 else 'fp32'},{l.dhp},fast={l.fast},drop={l.drop},pre={l.pre}" + (f",nq={l.nq}>" if l.kernel == ATTN_K_FWD else ">")
+    elif l.kernel == ATTN_K_FWD64:
+        name += f"<{l.waves}>"
+    return name
+
+
+def attn_last_kernels():
+    return [attn_kernel_name(l) for l in attn_last_plan()]
 
 
 class AcaiAdamWTensor(Structure):
@@ -189,6 +234,10 @@ _SIGNATURES = {
                                         c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                         c_int, c_int, c_int, c_int, c_float, c_uint32, c_int, c_void_p, c_size_t, c_void_p]),
     "acai_attn_varlen_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int]),
+    "acai_attn_plan": (c_int, [POINTER(AcaiAttnQuery), POINTER(AcaiAttnLaunch), POINTER(c_int), POINTER(c_int)]),
+    "acai_attn_last_plan": (c_int, [POINTER(AcaiAttnLaunch), POINTER(c_int)]),
+    "acai_attn_set_override": (c_int, [c_int, c_int]),
+    "acai_attn_get_override": (c_int, [c_int, POINTER(c_int)]),
     "acai_dropout_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_uint32, c_int, c_int, c_void_p]),
     "acai_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "acai_gelu_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),

@@ -11,7 +11,7 @@
 //                    S = Q K^T,  P,  dV^T += dO^T P,  dP = dO V^T,  dS = P o (dP - delta),  dK^T += Q^T dS
 // delta[q] = sum_d dO[q,d] O[q,d] is formed in the prologue of attn_bwd_dq (which runs first) and published for attn_bwd_dkv.  S and P are recomputed in both kernels (7 products instead
 // of 5) - the price of having no cross-workgroup reduction.  fp32: v_mfma_f32_32x32x2_f32, bf16: v_mfma_f32_32x32x16_bf16.
-#include "attn_bwd_args.h"
+#include "attn_internal.h"
 #include <type_traits>
 #ifndef ACAI_DKV_STRAIGHT
 #define ACAI_DKV_STRAIGHT 0
@@ -928,149 +928,49 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     }
 }
 
-// the shapes the one-pass kernel takes (beyond bf16 / prescaled / no dropout / aligned operands, which the dispatch checks by its template arguments)
-inline bool bwd1p_enabled() {   // ACAI_ATTN_BWD_1P=0: keep the two-kernel form (read once per process)
-    static const bool on = !(getenv("ACAI_ATTN_BWD_1P") && atoi(getenv("ACAI_ATTN_BWD_1P")) == 0);
-    return on;
-}
-inline bool bwd1p_shape_ok(int dh, int causal, int accum, int B, int H, int max_q, int max_k, int total_q, int total_k) {
-    // long sequences only (short ones keep the two-kernel form: a workgroup's prologue weighs more); 32-bit byte offsets into one sequence's
-    // [max_q][H][32] fp32 rows
-    (void)B; (void)total_q; (void)total_k;
-    return dh == 32 && !causal && !accum && max_k >= 512 && max_q >= 512 && (long long)(max_q + 64) * H * 128 < 0x7FFFFF00ll;
+static_assert(TT == ATTN_BWD_TT, "attn_plan.h sizes the dynamic LDS from this tile");
+
+// the dQ or dK / dV kernel of one instantiation; one latch per instantiation and device
+template <typename T, int DHP, bool F, bool D, bool P>
+void launch_one_block(const AcaiAttnLaunch &l, const BwdArgs &a, hipStream_t st) {
+    static_assert(TileLayout<sizeof(T), DHP>::PITCH == attn_tile_pitch(sizeof(T), DHP), "attn_plan.h sizes the dynamic LDS from this pitch");
+    static bool attr[ACAI_MAX_DEV] = {};
+    if (acai_first_on_device(attr)) {
+        hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv_kernel<T, DHP, F, D, P>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dq_kernel<T, DHP, F, D, P>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    }
+    if (l.kernel == ACAI_ATTN_K_BWD_DQ) hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DHP, F, D, P>), acai_attn_grid(l), dim3(l.block), l.lds_bytes, st, a);
+    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, DHP, F, D, P>), acai_attn_grid(l), dim3(l.block), l.lds_bytes, st, a);
 }
 
+// the instantiations that exist: prescaled implies 16-byte loads
 template <typename T, int DHP>
-int launch_bwd(const BwdArgs &a, int B, int max_q, int max_k, bool pre, void *ws, size_t ws_bytes, int total_k, hipStream_t st) {
-    constexpr int ES = sizeof(T), EPC = 16 / ES;
-    const bool fast = (a.dh % EPC == 0) && (a.ldq % EPC == 0) && (a.ldk % EPC == 0) && (a.ldv % EPC == 0) && (a.lddo % EPC == 0) && (a.ldo % EPC == 0) &&
-                      aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && aligned16(a.dout) && aligned16(a.o) &&
-                      (a.lddq % EPC == 0) && (a.lddk % EPC == 0) && (a.lddv % EPC == 0) && aligned16(a.dq) && aligned16(a.dk) && aligned16(a.dv) &&   // vector stores of the gradients too
-                      (size_t)max_q * (size_t)(a.ldq > a.lddo ? a.ldq : a.lddo) * ES < 0x7FFFFF00ull && (size_t)max_k * (size_t)(a.ldk > a.ldv ? a.ldk : a.ldv) * ES < 0x7FFFFF00ull;   // the staging's 32-bit buffer resources
-    constexpr int RP = TileLayout<ES, DHP>::PITCH;
-    const size_t lds_dq = 2 * (2 * TT * RP), lds_dkv = 2 * (2 * TT * RP + 2 * TT * sizeof(float));   // two stages each
-    if (pre && !fast) return acai_set_err(-1, "acai_attn_varlen_bwd: q_prescaled needs 16-byte aligned operands and d_h %% %d == 0", EPC);
-    if (a.accum_dkv && !(ES == 2 && fast)) return acai_set_err(-1, "acai_attn_varlen_bwd: accumulating dk / dv needs bf16 and 16-byte aligned operands");
-    auto launch_pair = [&](auto drop, auto fst, auto pr) {
-        constexpr bool D = decltype(drop)::value, F = decltype(fst)::value, P = decltype(pr)::value;
-        static bool attr[ACAI_MAX_DEV] = {};  // one latch per instantiation and device
-        if (acai_first_on_device(attr)) {
-            hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv_kernel<T, DHP, F, D, P>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dq_kernel<T, DHP, F, D, P>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        }
-        dim3 gq(cdiv(max_q, OB), a.H, B), gk(cdiv(max_k, OB), a.H, B);
-        if constexpr (sizeof(T) == 2 && DHP == 32 && F && !D && P) {
-            // the training steps' form on long sequences: two lane-owned blocks per wave (ACAI_ATTN_NQ=1: the one-block kernels, A/B aid)
-            static const int nq_env = getenv("ACAI_ATTN_NQ") ? atoi(getenv("ACAI_ATTN_NQ")) : 2;
-            static bool attr2[ACAI_MAX_DEV] = {};
-            if (acai_first_on_device(attr2)) {
-                hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-                hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dq2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            }
-            // one pass over the scores (attn_bwd1p.hip) when the caller lent a workspace and the sequences are long (ACAI_ATTN_BWD_1P=0: keep the two kernels below, whose dQ is bit-reproducible - the one-pass form adds the key
-            // blocks' contributions to a query's gradient in arrival order)
-            if (bwd1p_enabled() && bwd1p_shape_ok(a.dh, a.causal, a.accum_dkv, B, a.H, max_q, max_k, a.total_q, total_k) && ws && ws_bytes >= acai_attn_bwd1p_workspace(a.total_q, a.H)) {
-                // (when the host can tell that every sequence is max_k keys long, a multiple of 512, the partial-block launch is left out)
-                const bool eq = total_k > 0 && (long long)B * max_k == (long long)total_k && (long long)B * max_q == (long long)a.total_q;
-                acai_attn_bwd1p_launch(a, B, max_k, eq && max_k % 512 == 0 ? 0 : 1, eq ? 1 : 0, ws, st);
-                return;
-            }
-            if (nq_env == 2 && !a.causal && !a.accum_dkv && max_q >= 512 && max_k >= 512) {
-                hipLaunchKernelGGL(attn_bwd_dq2_kernel, dim3(cdiv(max_q, 2 * OB), a.H, B), dim3(256), lds_dq, st, a);
-                hipLaunchKernelGGL(attn_bwd_dkv2_kernel, dim3(cdiv(max_k, 2 * OB), a.H, B), dim3(256), lds_dkv, st, a);
-                return;
-            }
-        }
-        if constexpr (sizeof(T) == 2 && DHP == 64 && F && !D && P) {
-            // the training steps' d_h = 64 form: one wave per SIMD, two lane-owned blocks per wave (attn_bwd64w.hip) over every sequence's full
-            // 256-row blocks; the rows past them (none for the encoder's 256-multiples, one for the decoder's 513 tokens) stay with the
-            // one-block kernels below, offset by tail256.  ACAI_ATTN64_BWD_WIDE: 0 off, 1 dQ only, 2 dK/dV only, 3 both; unset = auto.
-            // Measured (tools/bench_cross_train_attn.py, 16 x 16 heads, same box): the wide dQ form is 1-5 % faster than the one-block kernel
-            // (encoder 4096 x 4096: 1533 against 1561 us; decoder cross 512 x 4096: 184 against 210 us).  The wide dK/dV form is 10 % faster on the
-            // encoder (1886 against 2091 us; 16 x 12 heads: backward 2.51 against 2.63 ms) once its K / V fragments were pinned to the accumulator
-            // half (before that it spilt to scratch and ran 2894 us), but SLOWER where the streamed query loop is short (decoder cross attention,
-            // 513 queries: 9 tiles per workgroup, 663 against 607 us for the pair - one wave per SIMD has nobody to cover a workgroup's prologue):
-            // auto takes it from 2048 streamed queries on.  Why the gains are small: every d_h = 64 attention kernel executes ~1 PFLOP/s of MFMA
-            // work, the rate this chip sustains at its loaded clock.
-            static const int wide_env = getenv("ACAI_ATTN64_BWD_WIDE") ? atoi(getenv("ACAI_ATTN64_BWD_WIDE")) : -1;
-            if (wide_env && !a.causal && a.dh == 64) {
-                const bool wq = (wide_env & 1) && max_q >= 256, wk = (wide_env & 2) && max_k >= 256 && !a.accum_dkv && (wide_env > 0 || max_q >= 2048);
-                // when every sequence is max_q long (B * max_q rows in all) the host knows whether a tail exists; keys: only for self-attention
-                const bool eq_q = (long long)B * max_q == (long long)a.total_q, eq_k = eq_q && a.cu_k == a.cu_q && max_k == max_q;
-                BwdArgs t = a;
-                if (wq) acai_attn_bwd64w_dq_launch(a, B, max_q, st);
-                if (!wq || !eq_q || max_q % 256) {
-                    t.tail256 = wq ? 1 : 0;
-                    const int rows = wq ? (eq_q ? max_q % 256 : 255) : max_q;
-                    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DHP, F, D, P>), dim3(cdiv(rows, OB), a.H, B), dim3(256), lds_dq, st, t);
-                }
-                if (wk) acai_attn_bwd64w_dkv_launch(a, B, max_k, eq_k ? 1 : 0, st);
-                if (!wk || !eq_k || max_k % 256) {
-                    t.tail256 = wk ? 2 : 0;
-                    const int rows = wk ? (eq_k ? max_k % 256 : 255) : max_k;
-                    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, DHP, F, D, P>), dim3(cdiv(rows, OB), a.H, B), dim3(256), lds_dkv, st, t);
-                }
-                return;
-            }
-        }
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DHP, F, D, P>), gq, dim3(256), lds_dq, st, a);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, DHP, F, D, P>), gk, dim3(256), lds_dkv, st, a);
-    };
-    if (pre) {
-        if (a.drop_thr) launch_pair(std::true_type{}, std::true_type{}, std::true_type{});
-        else launch_pair(std::false_type{}, std::true_type{}, std::true_type{});
-    } else if (a.drop_thr) {
-        if (fast) launch_pair(std::true_type{}, std::true_type{}, std::false_type{});
-        else launch_pair(std::true_type{}, std::false_type{}, std::false_type{});
+void launch_form(const AcaiAttnLaunch &l, const BwdArgs &a, hipStream_t st) {
+    if (l.pre) {
+        if (l.drop) launch_one_block<T, DHP, true, true, true>(l, a, st);
+        else launch_one_block<T, DHP, true, false, true>(l, a, st);
+    } else if (l.drop) {
+        if (l.fast) launch_one_block<T, DHP, true, true, false>(l, a, st);
+        else launch_one_block<T, DHP, false, true, false>(l, a, st);
     } else {
-        if (fast) launch_pair(std::false_type{}, std::true_type{}, std::false_type{});
-        else launch_pair(std::false_type{}, std::false_type{}, std::false_type{});
+        if (l.fast) launch_one_block<T, DHP, true, false, false>(l, a, st);
+        else launch_one_block<T, DHP, false, false, false>(l, a, st);
     }
-    ACAI_LAUNCH_CHECK("acai_attn_varlen_bwd");
-    return 0;
 }
 
 }  // namespace
 
-extern "C" int acai_attn_varlen_bwd_ws(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const void *o, int ldo,
-                                       const void *dout, int lddo, void *dq, int lddq, void *dk, int lddk, void *dv, int lddv, const float *lse,
-                                       float *delta, const int32_t *cu_q, const int32_t *cu_k, int B, int H, int dh, int max_q, int max_k,
-                                       int total_q, int total_k, int causal, int dtype, float dropout_p, uint32_t dropout_seed, int q_prescaled,
-                                       void *workspace, size_t workspace_bytes, void *stream) {
-    ACAI_CHECK_ARG(q && k && v && o && dout && dq && dk && dv && lse && delta && cu_q && cu_k, "acai_attn_varlen_bwd: null operand");
-    ACAI_CHECK_ARG(B > 0 && H > 0 && dh > 0 && dh <= 64 && max_q > 0 && max_k > 0 && total_q > 0 && B <= 65535 && H <= 65535,
-                   "acai_attn_varlen_bwd: bad dims");
-    ACAI_CHECK_ARG(total_k >= 0 && (workspace || !workspace_bytes), "acai_attn_varlen_bwd_ws: bad workspace / total_k");
-    BwdArgs a{};
-    a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout; a.dq = dq; a.dk = dk; a.dv = dv; a.lse = lse; a.delta = delta; a.cu_q = cu_q; a.cu_k = cu_k;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    ACAI_CHECK_ARG((causal & ~3) == 0, "acai_attn_varlen_bwd: causal takes bit 0 (causal mask) and bit 1 (accumulate dk / dv)");
-    a.H = H; a.dh = dh; a.causal = causal & 1; a.accum_dkv = (causal >> 1) & 1; a.total_q = total_q;
-    ACAI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "acai_attn_varlen_bwd: dropout_p out of range");
-    a.drop_thr = (uint32_t)((double)dropout_p * 4294967296.0); a.drop_seed = dropout_seed; a.drop_scale = 1.0f / (1.0f - dropout_p);
-    a.scale = 1.0f / sqrtf((float)dh);
-    a.scale_log2e = 1.4426950408889634f * a.scale;
-    hipStream_t st = (hipStream_t)stream;
-    const bool pre = q_prescaled != 0;
-    if (dtype == ACAI_BF16)
-        return dh <= 32 ? launch_bwd<bf16_t, 32>(a, B, max_q, max_k, pre, workspace, workspace_bytes, total_k, st)
-                        : launch_bwd<bf16_t, 64>(a, B, max_q, max_k, pre, nullptr, 0, total_k, st);
-    if (dtype == ACAI_F32)
-        return dh <= 32 ? launch_bwd<float, 32>(a, B, max_q, max_k, pre, nullptr, 0, total_k, st) : launch_bwd<float, 64>(a, B, max_q, max_k, pre, nullptr, 0, total_k, st);
-    return acai_set_err(-1, "acai_attn_varlen_bwd: bad dtype %d", dtype);
-}
-
-extern "C" size_t acai_attn_varlen_bwd_workspace_bytes(int B, int H, int dh, int max_q, int max_k, int total_q, int total_k, int causal, int dtype,
-                                                       float dropout_p, int q_prescaled) {
-    if (dtype != ACAI_BF16 || !q_prescaled || dropout_p != 0.f || B <= 0 || H <= 0 || total_q <= 0) return 0;
-    if (!bwd1p_enabled()) return 0;
-    return bwd1p_shape_ok(dh, causal & 1, (causal >> 1) & 1, B, H, max_q, max_k, total_q, total_k) ? acai_attn_bwd1p_workspace(total_q, H) : 0;
-}
-
-extern "C" int acai_attn_varlen_bwd(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const void *o, int ldo,
-                                    const void *dout, int lddo, void *dq, int lddq, void *dk, int lddk, void *dv, int lddv, const float *lse,
-                                    float *delta, const int32_t *cu_q, const int32_t *cu_k, int B, int H, int dh, int max_q, int max_k,
-                                    int total_q, int causal, int dtype, float dropout_p, uint32_t dropout_seed, int q_prescaled, void *stream) {
-    return acai_attn_varlen_bwd_ws(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, dq, lddq, dk, lddk, dv, lddv, lse, delta, cu_q, cu_k, B, H, dh, max_q, max_k,
-                                   total_q, 0, causal, dtype, dropout_p, dropout_seed, q_prescaled, nullptr, 0, stream);
+void acai_attn_launch_bwd(const AcaiAttnLaunch &l, const BwdArgs &a, hipStream_t st) {
+    if (l.kernel == ACAI_ATTN_K_BWD_DQ2 || l.kernel == ACAI_ATTN_K_BWD_DKV2) {
+        static bool attr2[ACAI_MAX_DEV] = {};
+        if (acai_first_on_device(attr2)) {
+            hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dq2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        }
+        if (l.kernel == ACAI_ATTN_K_BWD_DQ2) hipLaunchKernelGGL(attn_bwd_dq2_kernel, acai_attn_grid(l), dim3(l.block), l.lds_bytes, st, a);
+        else hipLaunchKernelGGL(attn_bwd_dkv2_kernel, acai_attn_grid(l), dim3(l.block), l.lds_bytes, st, a);
+        return;
+    }
+    if (l.elem_size == 2) l.dhp == 32 ? launch_form<bf16_t, 32>(l, a, st) : launch_form<bf16_t, 64>(l, a, st);
+    else l.dhp == 32 ? launch_form<float, 32>(l, a, st) : launch_form<float, 64>(l, a, st);
 }

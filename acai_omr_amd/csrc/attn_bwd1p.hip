@@ -11,7 +11,7 @@
 // partial tiles in LDS and the workgroup adds the result to an fp32 buffer with no-return float atomics, 128 contiguous bytes per query row and 32
 // lanes (measured 1.35 TB/s chip-wide, profiles/r04_atomic_rate.txt; 4096 keys / 512 = 8 adds per element: 2.15 GB per MAE decoder layer = 1.58 ms of
 // atomic-unit time, inside the kernel's 2.9 ms).  A first small kernel forms delta and zeroes that buffer, a last one scales it into the bf16 gradient.
-// The sum over key blocks is in arrival order: dQ is reproducible to fp32 rounding, not bit for bit (ACAI_ATTN_BWD_1P=0 keeps the two-pass kernels,
+// The sum over key blocks is in arrival order: dQ is reproducible to fp32 rounding, not bit for bit (the override ACAI_ATTN_OV_BWD_1P = 0 keeps the two-pass kernels,
 // which are).  Measured: 32 x 16 heads x 4096^2 3.00 ms against 3.78 for the two kernels; DESIGN.md section 5 has the counters and ablations.
 //
 // One wave per SIMD, four lane-owned 32-key blocks per wave: dK / dV 128 accumulator registers, the K / V fragments (B operands of S and dP) 64 and the
@@ -22,7 +22,7 @@
 // scratch round trips at every region boundary (hundreds of spills - what sank the first version of this kernel).  And since with one wave per SIMD
 // nothing issues beside the wave's own stream - every instruction of any kind is a four-cycle issue turn (profiles/r04_valu_issue.txt) - the steady
 // state carries no padding s_nop, no register copies and no address arithmetic that a rotating offset or a scalar operand can replace.
-#include "attn_bwd_args.h"
+#include "attn_internal.h"
 
 #include <type_traits>
 
@@ -588,22 +588,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 }  // namespace
 
-// (64 rows more than the gradient: a workgroup's first two tiles "add" the zero-filled partial sets to the sequence's first 64 rows without a range
-// check - for a sequence shorter than that, or the last one, those adds of 0.0 land in the next sequence's rows or in the padding)
-size_t acai_attn_bwd1p_workspace(int total_q, int H) { return ((size_t)total_q + 64) * H * 32 * sizeof(float); }
+static_assert(LDS_TOTAL == ATTN_BWD1P_LDS, "attn_plan.h states this kernel's LDS size");
 
-// partial_blocks: 0 = the host knows every sequence is a whole number of 512-key blocks (no slot for the keys past the last full block);
-// equal_len: the host knows all sequences have max_q queries and max_k keys (the XCD-aware block order)
-void acai_attn_bwd1p_launch(const BwdArgs &a, int B, int max_k, int partial_blocks, int equal_len, void *workspace, hipStream_t st) {
-    BwdArgs w = a;
-    w.nblk = max_k / KBG + (partial_blocks ? 1 : 0);
-    w.tail256 = equal_len ? 1 : 0;   // (this kernel's use of the field: the XCD-aware block order, for batches known to be equal-length)
+// The delta pass (which also zeroes the workspace), the main kernel over the launch's grid, and the pass that scales the fp32 query gradient
+// into dq.  workspace: attn_bwd1p_workspace(total_q, H) bytes.
+void acai_attn_launch_bwd1p(const AcaiAttnLaunch &l, const BwdArgs &a, void *workspace, hipStream_t st) {
     float *dq32 = reinterpret_cast<float *>(workspace);
     static bool attr[ACAI_MAX_DEV] = {};
     if (acai_first_on_device(attr))
-        hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd1p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+        hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd1p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, l.lds_bytes);
     const int pairs4 = (a.total_q + 64) * a.H * 4;
-    hipLaunchKernelGGL(bwd1p_delta_kernel, dim3(cdiv(pairs4, 256)), dim3(256), 0, st, w, dq32, a.total_q);
-    hipLaunchKernelGGL(attn_bwd1p_kernel, dim3(w.nblk * a.H * B), dim3(NT), LDS_TOTAL, st, w, dq32);
-    hipLaunchKernelGGL(bwd1p_scale_kernel, dim3(cdiv(a.total_q * a.H * 4, 256)), dim3(256), 0, st, w, dq32, a.total_q);
+    hipLaunchKernelGGL(bwd1p_delta_kernel, dim3(cdiv(pairs4, 256)), dim3(256), 0, st, a, dq32, a.total_q);
+    hipLaunchKernelGGL(attn_bwd1p_kernel, acai_attn_grid(l), dim3(l.block), l.lds_bytes, st, a, dq32);
+    hipLaunchKernelGGL(bwd1p_scale_kernel, dim3(cdiv(a.total_q * a.H * 4, 256)), dim3(256), 0, st, a, dq32, a.total_q);
 }

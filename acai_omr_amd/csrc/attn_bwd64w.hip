@@ -26,7 +26,7 @@
 // Register halves: the dK / dV kernel needs 128 (gradients) + 64 (K / V fragments) + 32 (transposed fragments) accumulator-half registers and ~210
 // architectural ones; left to the allocator the K / V fragments ended up partly architectural and the kernel spilt to scratch (2894 us against the
 // one-block kernel's 2142 on 16 x 16 x 4096^2) - its S / dP MFMAs are therefore inline asm with the B operand constrained to "a" (1886 us, no spill).
-#include "attn_bwd_args.h"
+#include "attn_internal.h"
 
 #include <type_traits>
 
@@ -701,18 +701,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 }  // namespace
 
-void acai_attn_bwd64w_dq_launch(const BwdArgs &a, int B, int max_q, hipStream_t st) {
-    BwdArgs w = a;
-    w.nblk = max_q / RBG;
-    const int grid = w.nblk * a.H * B;
-    if (!acai_xcd_order((long long)B * max_q == (long long)a.total_q)) w.nblk = -w.nblk;   // (nblk < 0: plain block order)
-    if (grid > 0) hipLaunchKernelGGL(attn_bwd64w_dq_kernel, dim3(grid), dim3(NT), 0, st, w);
-}
-
-void acai_attn_bwd64w_dkv_launch(const BwdArgs &a, int B, int max_k, int equal_len, hipStream_t st) {
-    BwdArgs w = a;
-    w.nblk = max_k / RBG;
-    const int grid = w.nblk * a.H * B;
-    if (!acai_xcd_order(equal_len != 0)) w.nblk = -w.nblk;
-    if (grid > 0) hipLaunchKernelGGL(attn_bwd64w_dkv_kernel, dim3(grid), dim3(NT), 0, st, w);
+void acai_attn_launch_bwd64w(const AcaiAttnLaunch &l, const BwdArgs &a, hipStream_t st) {
+    if (l.kernel == ACAI_ATTN_K_BWD64W_DQ) hipLaunchKernelGGL(attn_bwd64w_dq_kernel, acai_attn_grid(l), dim3(l.block), 0, st, a);
+    else hipLaunchKernelGGL(attn_bwd64w_dkv_kernel, acai_attn_grid(l), dim3(l.block), 0, st, a);
 }

@@ -16,7 +16,7 @@
 // pointer arithmetic in the loop; the resource is rebuilt per tile in SGPRs because only the VGPR offset is range-checked).
 // Reference "maximum" zero as in the two-block d_h = 32 form: probabilities are 2^score as they stand; a row sum outside (2^-100, 2^100)
 // makes the workgroup take the exact row maxima in a pre-pass and run the same loop again with the score accumulators starting at -m.
-#include "attn_args.h"
+#include "attn_internal.h"
 
 #include <type_traits>
 
@@ -449,38 +449,23 @@ __global__ __launch_bounds__(512) void attn_fwd64_tail_kernel(AttnArgs a) {
 
 }  // namespace
 
-int acai_attn_fwd64_launch(const AttnArgs &a, int B, int max_q, hipStream_t st) {
-    static const int nw_env = getenv("ACAI_ATTN64_NW") ? atoi(getenv("ACAI_ATTN64_NW")) : 4;
+void acai_attn_launch_fwd64(const AcaiAttnLaunch &l, const AttnArgs &a, hipStream_t st) {
+    const dim3 grid = acai_attn_grid(l), block(l.block);
+    if (l.kernel == ACAI_ATTN_K_FWD64_TAIL) {
+        hipLaunchKernelGGL(attn_fwd64_tail_kernel, grid, block, 0, st, a);
+        return;
+    }
 #ifdef ACAI_ATTN64_ABLATE
     const int abl = getenv("ACAI_ATTN64_ABL") ? atoi(getenv("ACAI_ATTN64_ABL")) : 0;
-#define ACAI_ABL_CASE(X) case X: hipLaunchKernelGGL((attn_fwd64_kernel<4, X>), dim3(cdiv(max_q, 128), a.H, B), dim3(256), 0, st, a); return 0;
+#define ACAI_ABL_CASE(X) case X: hipLaunchKernelGGL((attn_fwd64_kernel<4, X>), dim3(cdiv(l.rows, 128), a.H, l.grid_z), dim3(256), 0, st, a); return;
     switch (abl) {
         ACAI_ABL_CASE(1) ACAI_ABL_CASE(3) ACAI_ABL_CASE(4) ACAI_ABL_CASE(8) ACAI_ABL_CASE(12) ACAI_ABL_CASE(16) ACAI_ABL_CASE(32) ACAI_ABL_CASE(48)
         ACAI_ABL_CASE(64) ACAI_ABL_CASE(15) ACAI_ABL_CASE(79) ACAI_ABL_CASE(112) ACAI_ABL_CASE(124) ACAI_ABL_CASE(7)
         default: break;
     }
 #endif
-    // 0: the 32-queries-per-wave kernel everywhere; 1 (default): 64 queries per wave, one wave per SIMD, with a 128-query tail launch
-    static const int wide_env = getenv("ACAI_ATTN64_WIDE") ? atoi(getenv("ACAI_ATTN64_WIDE")) : 1;
-    if (wide_env) {
-        AttnArgs w = a;
-        // A sequence's last 256-query block goes to the tail kernel when it holds <= 32 rows.  When every sequence is max_q long (B * max_q rows
-        // in all) the host knows whether such a tail exists and launches only what is needed; were that reading of the arguments wrong, the
-        // wide kernel (tail = 0) still covers every row.
-        const bool all_equal = (long long)B * max_q == (long long)a.total_q;
-        const int rem = max_q % 256;
-        const bool need_tail = !all_equal || (rem > 0 && rem <= 32);
-        w.tail = need_tail ? 32 : 0;
-        // (equal lengths: the wide grid covers the full blocks only - workgroups that exit at once still wait for a whole free CU each, one
-        // per (sequence, head): 192 against 147 us on the decoder's 513-query cross attention)
-        const int wide_q = (all_equal && need_tail) ? max_q - rem : max_q;
-        if (wide_q > 0) acai_attn_fwd64w_launch(w, B, wide_q, st);
-        if (need_tail) hipLaunchKernelGGL(attn_fwd64_tail_kernel, dim3(1, a.H, B), dim3(512), 0, st, w);
-        return 0;
-    }
-    if (nw_env == 8)
-        hipLaunchKernelGGL((attn_fwd64_kernel<8>), dim3(cdiv(max_q, 256), a.H, B), dim3(512), 0, st, a);
+    if (l.waves == 8)
+        hipLaunchKernelGGL((attn_fwd64_kernel<8>), grid, block, 0, st, a);
     else
-        hipLaunchKernelGGL((attn_fwd64_kernel<4>), dim3(cdiv(max_q, 128), a.H, B), dim3(256), 0, st, a);
-    return 0;
+        hipLaunchKernelGGL((attn_fwd64_kernel<4>), grid, block, 0, st, a);
 }

@@ -19,7 +19,7 @@
 // V(t+1) are resident for the reloads, K(t+3) and V(t+2) are on their way through registers and are written at the tile's end.
 // One barrier per tile.  Probabilities are 2^score against a zero reference; a row sum outside (2^-100, 2^100) sends the workgroup
 // through a plain two-pass loop (exact row maxima, then the products again).
-#include "attn_args.h"
+#include "attn_internal.h"
 
 #include <type_traits>
 
@@ -399,19 +399,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 }  // namespace
 
-void acai_attn_fwd64w_launch(const AttnArgs &a, int B, int max_q, hipStream_t st) {
-    AttnArgs w = a;
-    w.nqb = cdiv(max_q, QBG);
-    const int grid = w.nqb * a.H * B;
-    if (!acai_xcd_order((long long)B * max_q == (long long)a.total_q)) w.nqb = -w.nqb;
+void acai_attn_launch_fwd64w(const AcaiAttnLaunch &l, const AttnArgs &a, hipStream_t st) {
+    const dim3 grid = acai_attn_grid(l), block(l.block);
 #ifdef ACAI_ATTN64_ABLATE
     const int abl = getenv("ACAI_ATTN64_ABL") ? atoi(getenv("ACAI_ATTN64_ABL")) : 0;
-#define ACAI_ABL_CASE(X) case X: hipLaunchKernelGGL(attn_fwd64w_kernel<X>, dim3(grid), dim3(NT), 0, st, w); return;
+#define ACAI_ABL_CASE(X) case X: hipLaunchKernelGGL(attn_fwd64w_kernel<X>, grid, block, 0, st, a); return;
     switch (abl) {
         ACAI_ABL_CASE(1) ACAI_ABL_CASE(3) ACAI_ABL_CASE(4) ACAI_ABL_CASE(8) ACAI_ABL_CASE(12) ACAI_ABL_CASE(16) ACAI_ABL_CASE(32) ACAI_ABL_CASE(48)
         ACAI_ABL_CASE(64) ACAI_ABL_CASE(15) ACAI_ABL_CASE(79) ACAI_ABL_CASE(112) ACAI_ABL_CASE(124) ACAI_ABL_CASE(7) ACAI_ABL_CASE(120) ACAI_ABL_CASE(76) ACAI_ABL_CASE(128) ACAI_ABL_CASE(256) ACAI_ABL_CASE(512) ACAI_ABL_CASE(384) ACAI_ABL_CASE(640) ACAI_ABL_CASE(768) ACAI_ABL_CASE(896)
         default: break;
     }
 #endif
-    hipLaunchKernelGGL(attn_fwd64w_kernel<0>, dim3(grid), dim3(NT), 0, st, w);
+    hipLaunchKernelGGL(attn_fwd64w_kernel<0>, grid, block, 0, st, a);
 }

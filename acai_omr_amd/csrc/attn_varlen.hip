@@ -14,7 +14,7 @@
 // K=2 MFMA with A key (i&3)+8(i>>2)+4h).  bf16 -> v_mfma_f32_32x32x16_bf16, fp32 -> v_mfma_f32_32x32x2_f32.
 // Online softmax in fp32 with exp2 and a finite -1e30 floor; global loads of tile t+1 are issued before
 // the MFMAs of tile t (issue-early / write-late) into the other of two LDS stages: one barrier per tile.
-#include "attn_args.h"
+#include "attn_internal.h"
 
 #ifndef ACAI_ATTN_QK_FIRST
 #define ACAI_ATTN_QK_FIRST 0
@@ -532,70 +532,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACAI_FWD_WA
     }
 }
 
+// the instantiation of a launch's form: fast / dropout / prescaled, and the two-blocks-per-wave form that exists for bf16, d_h <= 32 alone
 template <typename T, int DHP>
-int launch(const AttnArgs &a, int B, int max_q, bool pre, hipStream_t st) {
-    constexpr int EPC = 16 / sizeof(T);
-    const bool fast = (a.dh % EPC == 0) && (a.ldq % EPC == 0) && (a.ldk % EPC == 0) && (a.ldv % EPC == 0) && (a.ldo % EPC == 0) &&
-                      aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && aligned16(a.out);
-    dim3 grid(cdiv(max_q, QB), a.H, B);
-    // train-mode attention dropout is its own instantiation, so the common kernel carries no hash code / registers; the prescaled-q form
-    // (training path) exists for 16-byte-aligned operands only
-    if (pre) {
-        if (!fast) return acai_set_err(-1, "acai_attn_varlen_fwd: q_prescaled needs 16-byte aligned operands and d_h %% %d == 0", EPC);
-        if (a.drop_thr)
-            hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, true, true>), grid, dim3(256), 0, st, a);
-        else if constexpr (sizeof(T) == 2) {
-            // the training steps' form: two query blocks per wave (ACAI_ATTN_NQ=1: one, A/B aid) when the sequences are long enough to fill the chip
-            static const int nq_env = getenv("ACAI_ATTN_NQ") ? atoi(getenv("ACAI_ATTN_NQ")) : 2;
-            // (d_h = 64 keeps one block: two need 256 registers + 55 spilt even with the zero reference, and measured 5 % slower - 0.97 against 0.92 ms)
-            bool two = false;
-            if constexpr (DHP == 64) {
-                // d_h = 64 exactly, no causal mask: the software-pipelined kernel of attn_fwd64.hip (ACAI_ATTN64=0: this file's kernel, A/B aid)
-                static const int f64_env = getenv("ACAI_ATTN64") ? atoi(getenv("ACAI_ATTN64")) : 1;
-                if (f64_env && a.dh == 64 && !a.causal) {
-                    const int rc = acai_attn_fwd64_launch(a, B, max_q, st);
-                    ACAI_LAUNCH_CHECK("acai_attn_varlen_fwd");
-                    return rc;
-                }
+void launch_form(const AcaiAttnLaunch &l, const AttnArgs &a, hipStream_t st) {
+    const dim3 grid = acai_attn_grid(l), block(l.block);
+    if (l.pre) {
+        if (l.drop) {
+            hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, true, true>), grid, block, 0, st, a);
+            return;
+        }
+        if constexpr (sizeof(T) == 2 && DHP == 32) {
+            if (l.nq == 2) {
+                hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, false, true, 2>), grid, block, 0, st, a);
+                return;
             }
-            if constexpr (DHP == 32) {
-                two = nq_env == 2 && max_q >= 512;
-                if (two) hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, false, true, 2>), dim3(cdiv(max_q, 2 * QB), a.H, B), dim3(256), 0, st, a);
-            }
-            if (!two) hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, false, true>), grid, dim3(256), 0, st, a);
-        } else
-            hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, false, true>), grid, dim3(256), 0, st, a);
-    } else if (a.drop_thr) {
-        if (fast)
-            hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, true, false>), grid, dim3(256), 0, st, a);
-        else
-            hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, false, true, false>), grid, dim3(256), 0, st, a);
-    } else if (fast)
-        hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, false, false>), grid, dim3(256), 0, st, a);
+        }
+        hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, false, true>), grid, block, 0, st, a);
+    } else if (l.drop) {
+        if (l.fast) hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, true, false>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, false, true, false>), grid, block, 0, st, a);
+    } else if (l.fast)
+        hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, true, false, false>), grid, block, 0, st, a);
     else
-        hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, false, false, false>), grid, dim3(256), 0, st, a);
-    ACAI_LAUNCH_CHECK("acai_attn_varlen_fwd");
-    return 0;
+        hipLaunchKernelGGL((attn_fwd_kernel<T, DHP, false, false, false>), grid, block, 0, st, a);
 }
 
 }  // namespace
 
-// q_prescaled: q already carries the factor log2(e) / sqrt(dh) (acai_gemm_nt_ex's column scale on the in-projection); the kernel then
-// takes K . Q^T as the score in the log2 domain.  `lse` has the same meaning either way.
-extern "C" int acai_attn_varlen_fwd(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, void *out, int ldo,
-                                    const int32_t *cu_q, const int32_t *cu_k, int B, int H, int dh, int max_q, int causal,
-                                    int dtype, float *lse, int total_q, float dropout_p, uint32_t dropout_seed, int q_prescaled, void *stream) {
-    ACAI_CHECK_ARG(q && k && v && out && cu_q && cu_k, "acai_attn_varlen_fwd: null operand");
-    ACAI_CHECK_ARG(B > 0 && H > 0 && dh > 0 && dh <= 64 && max_q > 0, "acai_attn_varlen_fwd: bad dims B=%d H=%d dh=%d max_q=%d (dh <= 64)", B, H, dh, max_q);
-    ACAI_CHECK_ARG(ldq >= H * dh && ldk >= H * dh && ldv >= H * dh && ldo >= H * dh, "acai_attn_varlen_fwd: row stride smaller than H*dh");
-    ACAI_CHECK_ARG(B <= 65535 && H <= 65535, "acai_attn_varlen_fwd: grid too large");
-    ACAI_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "acai_attn_varlen_fwd: dropout_p out of range");
-    AttnArgs a{q, k, v, out, cu_q, cu_k, ldq, ldk, ldv, ldo, H, dh, causal, 0.f, (uint32_t)((double)dropout_p * 4294967296.0), dropout_seed,
-               1.0f / (1.0f - dropout_p), lse, total_q};
-    a.scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-    hipStream_t st = (hipStream_t)stream;
-    const bool pre = q_prescaled != 0;
-    if (dtype == ACAI_BF16) return dh <= 32 ? launch<bf16_t, 32>(a, B, max_q, pre, st) : launch<bf16_t, 64>(a, B, max_q, pre, st);
-    if (dtype == ACAI_F32) return dh <= 32 ? launch<float, 32>(a, B, max_q, pre, st) : launch<float, 64>(a, B, max_q, pre, st);
-    return acai_set_err(-1, "acai_attn_varlen_fwd: bad dtype %d", dtype);
+void acai_attn_launch_fwd(const AcaiAttnLaunch &l, const AttnArgs &a, hipStream_t st) {
+    if (l.elem_size == 2) l.dhp == 32 ? launch_form<bf16_t, 32>(l, a, st) : launch_form<bf16_t, 64>(l, a, st);
+    else l.dhp == 32 ? launch_form<float, 32>(l, a, st) : launch_form<float, 64>(l, a, st);
 }

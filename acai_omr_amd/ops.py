@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the current stream; every FL
 the HIP library.  Every wrapper checks device / dtype / contiguity on the host before the launch (a
 faulting kernel can take the whole node down) and raises RuntimeError on a non-zero return code.
 """
+import contextlib
 import ctypes
 import functools
 
@@ -720,6 +721,19 @@ def gather_rows(table, idx, add=None, out=None):
 def QSCALE(dh):
     """The factor a prescaled q carries: the softmax scale in the log2 domain."""
     return 1.4426950408889634 / math.sqrt(dh)
+
+
+@contextlib.contextmanager
+def attn_override(which, value):
+    """Sets one process-wide override of the attention selection rule (_lib.ATTN_OV_*, acai_attn_set_override) and puts the previous value
+    back on exit: tests and A/B runs."""
+    L, old = _lib.lib(), ctypes.c_int(0)
+    _lib.check(L.acai_attn_get_override(int(which), ctypes.byref(old)), "acai_attn_get_override")
+    _lib.check(L.acai_attn_set_override(int(which), int(value)), "acai_attn_set_override")
+    try:
+        yield
+    finally:
+        _lib.check(L.acai_attn_set_override(int(which), old.value), "acai_attn_set_override")
 
 
 def attn_varlen(q, k, v, cu_q, cu_k, H, dh, max_q, causal=False, out=None, lse=None, dropout_p=0.0, seed=0, q_prescaled=False):

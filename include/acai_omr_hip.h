@@ -207,8 +207,8 @@ int acai_attn_varlen_bwd(const void *q, int ldq, const void *k, int ldk, const v
 /* The same backward with a caller-lent device workspace (round 4).  With bf16, d_h = 32, q_prescaled, no dropout / mask / accumulation and
  * max_q, max_k >= 512 - the MAE decoder's self-attention (models.py:186-190), ragged batches included - dQ, dK and dV come from ONE pass over
  * the scores (attn_bwd1p.hip): the key blocks add their part of a query's gradient to the fp32 workspace with float atomics, so dQ is
- * reproducible to fp32 rounding, not bit for bit (ACAI_ATTN_BWD_1P=0 in the environment, or no workspace, keeps the two-kernel form, which
- * is).  total_k = the rows of k / v (0 = unknown: when it equals B * max_k with max_k % 512 == 0 the launch for partial key blocks is left out).  acai_attn_varlen_bwd_workspace_bytes: bytes that form needs for a call with these
+ * reproducible to fp32 rounding, not bit for bit (acai_attn_set_override(ACAI_ATTN_OV_BWD_1P, 0), or no workspace, keeps the two-kernel form,
+ * which is).  total_k = the rows of k / v (0 = unknown: when it equals B * max_k with max_k % 512 == 0 the launch for partial key blocks is left out).  acai_attn_varlen_bwd_workspace_bytes: bytes that form needs for a call with these
  * arguments, 0 when it does not apply (then any workspace is ignored).  The workspace is used only inside the call (stream order). */
 size_t acai_attn_varlen_bwd_workspace_bytes(int B, int H, int dh, int max_q, int max_k, int total_q, int total_k, int causal, int dtype,
                                             float dropout_p, int q_prescaled);
@@ -217,6 +217,69 @@ int acai_attn_varlen_bwd_ws(const void *q, int ldq, const void *k, int ldk, cons
                             float *delta, const int32_t *cu_q, const int32_t *cu_k, int B, int H, int dh, int max_q, int max_k,
                             int total_q, int total_k, int causal, int dtype, float dropout_p, uint32_t dropout_seed, int q_prescaled,
                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* Which kernels an acai_attn_varlen_* call runs.  The selection rule is a pure host function of the query below (csrc/attn_plan.h):
+ * acai_attn_plan evaluates it without touching a device, acai_attn_last_plan reports what the most recent acai_attn_varlen_fwd /
+ * acai_attn_varlen_bwd[_ws] call of the calling thread launched (n = 0 before the first one and after a refused call).  A plan has up to
+ * four launches, in stream order: the forward at most two (wide kernel, tail kernel), the d_h = 64 backward at most four (wide dQ, dQ of the
+ * rows past the full 256-row blocks, wide dK / dV, dK / dV of the rows past them); the one-pass backward is ONE entry that stands for its
+ * delta / main / scale launches.  No reference counterpart. */
+enum {
+    ACAI_ATTN_K_FWD = 0,         /* attn_fwd_kernel<elem, dhp, fast, drop, pre, nq> (attn_varlen.hip) */
+    ACAI_ATTN_K_FWD64 = 1,       /* attn_fwd64_kernel<waves> (attn_fwd64.hip): 32 queries per wave, 4 or 8 waves */
+    ACAI_ATTN_K_FWD64W = 2,      /* attn_fwd64w_kernel (attn_fwd64w.hip): 64 queries per wave, one wave per SIMD */
+    ACAI_ATTN_K_FWD64_TAIL = 3,  /* attn_fwd64_tail_kernel: a sequence's last 256-query block of <= `tail` rows, keys split over 8 waves */
+    ACAI_ATTN_K_BWD_DQ = 4,      /* attn_bwd_dq_kernel<elem, dhp, fast, drop, pre> (attn_bwd.hip) */
+    ACAI_ATTN_K_BWD_DKV = 5,     /* attn_bwd_dkv_kernel<elem, dhp, fast, drop, pre> */
+    ACAI_ATTN_K_BWD_DQ2 = 6,     /* attn_bwd_dq2_kernel: bf16, d_h <= 32, two blocks per wave */
+    ACAI_ATTN_K_BWD_DKV2 = 7,    /* attn_bwd_dkv2_kernel */
+    ACAI_ATTN_K_BWD64W_DQ = 8,   /* attn_bwd64w_dq_kernel (attn_bwd64w.hip): the full 256-query blocks */
+    ACAI_ATTN_K_BWD64W_DKV = 9,  /* attn_bwd64w_dkv_kernel: the full 256-key blocks */
+    ACAI_ATTN_K_BWD1P = 10       /* bwd1p_delta_kernel, attn_bwd1p_kernel (whose grid / block / LDS the entry holds), bwd1p_scale_kernel */
+};
+/* Process-wide overrides of the rule (tests and A/B runs; acai_attn_set_override copies them into every query, so the plan stays pure). */
+enum {
+    ACAI_ATTN_OV_TWO_BLOCK = 0,  /* 1 (default) / 0: two blocks per wave at d_h <= 32 on long sequences, forward and backward */
+    ACAI_ATTN_OV_FWD64 = 1,      /* the bf16 prescaled unmasked d_h = 64 forward: ACAI_ATTN_FWD64_* */
+    ACAI_ATTN_OV_BWD64_WIDE = 2, /* its backward: -1 auto (default), 0 one-block kernels, 1 wide dQ, 2 wide dK / dV, 3 both */
+    ACAI_ATTN_OV_BWD_1P = 3,     /* 1 (default) / 0: the one-pass d_h = 32 backward when a workspace is lent */
+    ACAI_ATTN_OV_XCD_ORDER = 4,  /* XCD-aware block order of the d_h = 64 kernels' one-dimensional grids: -1 auto (default: equal-length batches), 0, 1 */
+    ACAI_ATTN_OV_COUNT = 5
+};
+enum { ACAI_ATTN_FWD64_AUTO = 0 /* wide + tail */, ACAI_ATTN_FWD64_NW4 = 1, ACAI_ATTN_FWD64_NW8 = 2 /* attn_fwd64_kernel<4> / <8> */,
+       ACAI_ATTN_FWD64_GENERIC = 3 /* attn_fwd_kernel */ };
+/* why a plan is empty: the entry then fails with its error text */
+enum { ACAI_ATTN_REFUSE_NONE = 0, ACAI_ATTN_REFUSE_PRESCALED = 1 /* q_prescaled without aligned operands */,
+       ACAI_ATTN_REFUSE_ACCUM = 2 /* accumulating dk / dv without bf16 and aligned operands */ };
+typedef struct AcaiAttnQuery {
+    int backward;                /* 0: acai_attn_varlen_fwd, 1: acai_attn_varlen_bwd[_ws] */
+    int elem_size;               /* 2 (bf16) or 4 (fp32) */
+    int B, H, dh, max_q, max_k, total_q, total_k;   /* forward: max_k, total_k unused; total_k = 0: unknown */
+    int causal, accum_dkv, dropout, q_prescaled;
+    int ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv; /* row strides in elements (forward: the first four) */
+    int aligned;                 /* every operand's base (backward: the gradients' too) is 16-byte aligned */
+    int cu_k_is_cu_q;            /* self-attention: the keys' offsets are the queries' */
+    int ov[ACAI_ATTN_OV_COUNT];  /* acai_attn_set_override */
+    long long workspace_bytes;   /* backward: bytes of workspace lent (0: none) */
+} AcaiAttnQuery;
+typedef struct AcaiAttnLaunch {
+    int kernel;                  /* ACAI_ATTN_K_* */
+    int elem_size, dhp, fast, drop, pre, nq, waves;   /* template form: element, head-size class 32 / 64, 16-byte loads, dropout, prescaled q,
+                                                         blocks per wave, K_FWD64's waves (forms a kernel does not have: 0) */
+    int grid_x, grid_y, grid_z, block, lds_bytes;     /* lds_bytes: dynamic LDS */
+    /* host-decided kernel arguments */
+    int tail;                    /* AttnArgs::tail: K_FWD64W leaves, K_FWD64_TAIL takes, last blocks of <= tail rows */
+    int tail256;                 /* BwdArgs::tail256.  K_BWD_DQ / K_BWD_DKV: 1 / 2 = only the rows past each sequence's last full 256-row
+                                    block (dQ / dK, dV).  K_BWD1P: 1 = XCD-aware block order */
+    int nblk;                    /* AttnArgs::nqb / BwdArgs::nblk: blocks per (sequence, head) of a one-dimensional grid; < 0: plain block order */
+    int partial_blocks, equal_len;   /* K_BWD1P: a slot for the keys past the last full 512-key block; batch known to be equal-length */
+    int rows;                    /* rows per sequence that the grid covers */
+} AcaiAttnLaunch;
+/* launches_out: room for four launches; *n_out: how many the plan has; *refusal_out (may be NULL): ACAI_ATTN_REFUSE_*. */
+int acai_attn_plan(const AcaiAttnQuery *query, AcaiAttnLaunch *launches_out, int *n_out, int *refusal_out);
+int acai_attn_last_plan(AcaiAttnLaunch *launches_out, int *n_out);
+int acai_attn_set_override(int which, int value);
+int acai_attn_get_override(int which, int *value_out);
 
 /* Backward of nn.LayerNorm: dx (fp32) from x, w, dy; dw/db (both or neither NULL) are ACCUMULATED with fp32 atomics (zero or seed
  * them); dx_bf16 (may be NULL; needs dim % 256 == 0, dim <= 1024): bf16 copy of dx for the GEMM that consumes it; dxsum (may be NULL, same

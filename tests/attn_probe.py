@@ -240,8 +240,8 @@ FWD_TWO_BLOCK = [                               # bf16, prescaled, d_h <= 32, ma
 ]
 FWD_64 = [                                      # bf16, prescaled, d_h = 64, no mask: attn_fwd64.hip, wide + tail
     (2, 64, [513, 130], [1100, 64], False),
-    (1, 64, [40, 129, 192], [40, 65, 191], False),
-    (1, 64, [256], [1], False),
+    (1, 64, [40, 129, 192], [40, 65, 191], False),          # (the tail kernel is launched and finds no last block of <= 32 rows)
+    (1, 64, [256], [1], False),                             # (equal lengths, a multiple of 256: the wide kernel alone)
     (2, 64, [288, 289, 20], [700, 64, 1], False),
     (1, 64, [513] * 3, [1100] * 3, False),
 ]
@@ -264,7 +264,7 @@ BWD_ONE_PASS_EQUAL = [                          # attn_bwd1p.hip with equal leng
 BWD_64 = [                                      # bf16, prescaled, d_h = 64, max_q >= 256: attn_bwd64w.hip + the one-block tails
     (2, 64, [513, 700], None, False),
     (2, 64, [600, 256, 40], [1000, 577, 300], False),
-    (2, 64, [768], [129], False),
+    (2, 64, [768], [129], False),                           # (no rows past the full query blocks, no full key block: never the wide dK / dV)
 ]
 BWD_ACCUMULATE = [(2, 64, [300], [513], False)]
 FWD_CASES = FWD_GENERIC + FWD_TWO_BLOCK + FWD_64

@@ -14,10 +14,10 @@ Worst error / tolerance seen on an MI355X, per form - the margin the kernels lea
   backward, two blocks per wave  dq 0.06, dk 0.06, dv 0.08
   backward, one pass             dq 0.07, dk 0.08, dv 0.07
   backward, attn_bwd64w          dq 0.06, dk 0.06, dv 0.07, with the wide dK / dV form as without it
-  backward, accumulating         dq 0.06, dk 0.07, dv 0.07"""
-import os
-import subprocess
-import sys
+  backward, accumulating         dq 0.06, dk 0.07, dv 0.07
+
+Every test also asserts, through acai_attn_last_plan, the kernels and forms that its forward and its backward call ran."""
+import contextlib
 
 import pytest
 import torch
@@ -64,10 +64,18 @@ def _reference(case, dtype, prescaled, backward):
     return have
 
 
-def launch(dev, case, dtype, prescaled, backward=False, lend_workspace=True, calls=1, accumulate=None):
-    """Runs the forward (and the backward, `calls` times into the same outputs) on guarded views.  Returns the WHOLE allocations of the
-    outputs, guards included, on the CPU.  accumulate = (dk0, dv0): what dk / dv hold before a backward call that adds to them."""
-    from acai_omr_amd import engine, ops
+def launch(dev, case, dtype, prescaled, backward=False, lend_workspace=True, calls=1, accumulate=None, overrides=()):
+    """Runs the forward (and the backward, `calls` times into the same outputs) on guarded views, under the given (override, value) pairs.
+    Returns the WHOLE allocations of the outputs, guards included, on the CPU, and what ran: {"fwd": [AcaiAttnLaunch, ...], "bwd": ...}.
+    accumulate = (dk0, dv0): what dk / dv hold before a backward call that adds to them."""
+    from acai_omr_amd import _lib, engine, ops
+    with contextlib.ExitStack() as stack:
+        for which, value in overrides:
+            stack.enter_context(ops.attn_override(which, value))
+        return _launch(_lib, engine, ops, dev, case, dtype, prescaled, backward, lend_workspace, calls, accumulate)
+
+
+def _launch(_lib, engine, ops, dev, case, dtype, prescaled, backward, lend_workspace, calls, accumulate):
     H, dh, lens_q, lens_k, causal = case
     lens_k = lens_k or lens_q
     E = H * dh
@@ -79,7 +87,7 @@ def launch(dev, case, dtype, prescaled, backward=False, lend_workspace=True, cal
     lse = P.guarded(torch.empty(H * sum(lens_q), device=dev), ROWS)
     o = ops.attn_varlen(qd, kd, vd, cu_q, cu_k, H, dh, max(lens_q), causal=causal, out=out, lse=lse, q_prescaled=prescaled)
     assert o.data_ptr() == out.data_ptr()
-    got = {"out": out, "lse": lse}
+    got, ran = {"out": out, "lse": lse}, {"fwd": _lib.attn_last_plan()}
     if backward:
         dd = P.guarded(dout.to(dev).to(dtype), ROWS, kind="dout")
         dq, dk, dv = P.guarded(torch.empty_like(qd), ROWS), P.guarded(torch.empty_like(kd), ROWS), P.guarded(torch.empty_like(vd), ROWS)
@@ -89,9 +97,33 @@ def launch(dev, case, dtype, prescaled, backward=False, lend_workspace=True, cal
         for _ in range(calls):
             ops.attn_varlen_bwd(qd, kd, vd, out, dd, lse, cu_q, cu_k, H, dh, max(lens_q), max(lens_k), causal, dq, dk, dv, q_prescaled=prescaled,
                                 accumulate_dkv=accumulate is not None, lend_workspace=lend_workspace)
+            ran["bwd"] = _lib.attn_last_plan()
         got.update(dq=dq, dk=dk, dv=dv)
     torch.cuda.synchronize()
-    return {n: t._base.cpu() for n, t in got.items()}
+    return {n: t._base.cpu() for n, t in got.items()}, ran
+
+
+def kernels(launches):
+    from acai_omr_amd import _lib
+    return [_lib.attn_kernel_name(l) for l in launches]
+
+
+def _form(kernel, case, dtype, prescaled):
+    """The name of an instantiated kernel in the form a case reaches: 16-byte loads where the head size allows them, no dropout."""
+    dh = case[1]
+    fast = int(dh % (8 if dtype == BF else 4) == 0)
+    return (f"{kernel}<{'bf16' if dtype == BF else 'fp32'},{32 if dh <= 32 else 64},fast={fast},drop=0,pre={int(prescaled)}"
+            + (",nq=1>" if kernel == "attn_fwd_kernel" else ">"))
+
+
+def _ragged(lens):
+    return len(set(lens)) > 1
+
+
+def _dq_past_full_blocks(case):
+    """The one-block dQ launch over the rows past each sequence's last full 256-row block (tail256 = 1): present unless the host can tell
+    from equal lengths that there are no such rows."""
+    return _ragged(case[2]) or max(case[2]) % 256 != 0
 
 
 def check(form, case, dtype, prescaled, whole, accumulate=None):
@@ -139,65 +171,102 @@ def _typed(cases):
 def test_forward_generic(dev, case, dtype, prescaled):
     """attn_fwd_kernel, one query block per wave: fast and unaligned (bf16 d_h = 12) loads, prescaled or not, causal or not.  (bf16 prescaled
     d_h = 64 without a mask is attn_fwd64.hip's.)"""
-    check("fwd generic", case, dtype, prescaled, launch(dev, case, dtype, prescaled))
+    whole, ran = launch(dev, case, dtype, prescaled)
+    assert kernels(ran["fwd"]) == [_form("attn_fwd_kernel", case, dtype, prescaled)]
+    check("fwd generic", case, dtype, prescaled, whole)
 
 
 @pytest.mark.parametrize("case", P.FWD_TWO_BLOCK, ids=P.case_id)
 def test_forward_two_blocks_per_wave(dev, case):
     """bf16, prescaled, d_h <= 32, >= 512 queries: two query blocks per wave against a zero reference."""
-    check("fwd two-block", case, BF, True, launch(dev, case, BF, True))
+    whole, ran = launch(dev, case, BF, True)
+    assert kernels(ran["fwd"]) == ["attn_fwd_kernel<bf16,32,fast=1,drop=0,pre=1,nq=2>"]
+    check("fwd two-block", case, BF, True, whole)
 
 
 @pytest.mark.parametrize("case", P.FWD_64, ids=P.case_id)
 def test_forward_dh64_pipelined(dev, case):
-    """attn_fwd64.hip (bf16, prescaled, d_h = 64, no mask): the wide kernel over the full 256-row blocks and the tail kernel."""
-    check("fwd64", case, BF, True, launch(dev, case, BF, True))
+    """attn_fwd64.hip (bf16, prescaled, d_h = 64, no mask): the wide kernel, which leaves a sequence's last 256-row block to the tail kernel
+    when it holds <= 32 rows.  The tail kernel is launched for every ragged batch (in [40, 129, 192] it finds no such block and exits) and
+    for an equal-length one with such a block; [256] runs the wide kernel alone."""
+    whole, ran = launch(dev, case, BF, True)
+    lens_q = case[2]
+    tail = _ragged(lens_q) or 0 < max(lens_q) % 256 <= 32
+    assert kernels(ran["fwd"]) == ["attn_fwd64w_kernel"] + (["attn_fwd64_tail_kernel"] if tail else [])
+    assert [l.tail for l in ran["fwd"]] == [32 if tail else 0] * len(ran["fwd"])
+    check("fwd64", case, BF, True, whole)
+
+
+@pytest.mark.parametrize("waves,form", [(4, 1), (8, 2)], ids=["four-wave", "eight-wave"])
+@pytest.mark.parametrize("case", P.FWD_64, ids=P.case_id)
+def test_forward_dh64_narrow_forms(dev, case, waves, form):
+    """attn_fwd64_kernel<4> and <8> (32 queries per wave; the override ACAI_ATTN_OV_FWD64 is the only way to them): one launch covers
+    every row, tails included."""
+    from acai_omr_amd import _lib
+    assert form == (_lib.ATTN_FWD64_NW4 if waves == 4 else _lib.ATTN_FWD64_NW8)
+    whole, ran = launch(dev, case, BF, True, overrides=[(_lib.ATTN_OV_FWD64, form)])
+    assert kernels(ran["fwd"]) == [f"attn_fwd64_kernel<{waves}>"]
+    assert ran["fwd"][0].grid_x == -(-max(case[2]) // (32 * waves)) and ran["fwd"][0].block == 64 * waves
+    check(f"fwd64 {waves} waves", case, BF, True, whole)
 
 
 @pytest.mark.parametrize("case,dtype,prescaled", _typed(P.BWD_GENERIC))
 def test_backward_one_block(dev, case, dtype, prescaled):
     """attn_bwd.hip's one-block dQ and dK / dV kernels.  (bf16 prescaled d_h = 64 with 256 queries: the wide dQ form of attn_bwd64w.hip.)"""
-    check("bwd one-block", case, dtype, prescaled, launch(dev, case, dtype, prescaled, backward=True))
+    whole, ran = launch(dev, case, dtype, prescaled, backward=True)
+    dq, dkv = _form("attn_bwd_dq_kernel", case, dtype, prescaled), _form("attn_bwd_dkv_kernel", case, dtype, prescaled)
+    wide_dq = dtype == BF and prescaled and case[1] == 64 and not case[4] and max(case[2]) >= 256   # [256] x [400]: no rows past the full block
+    assert kernels(ran["bwd"]) == (["attn_bwd64w_dq_kernel", dkv] if wide_dq else [dq, dkv])
+    assert [l.tail256 for l in ran["bwd"]] == [0, 0]
+    check("bwd one-block", case, dtype, prescaled, whole)
 
 
 @pytest.mark.parametrize("case", P.BWD_TWO_BLOCK, ids=P.case_id)
 def test_backward_two_blocks_per_wave(dev, case):
     """bf16, prescaled, d_h <= 32, >= 512 queries and keys, no workspace lent: the two-blocks-per-wave dQ and dK / dV kernels."""
-    check("bwd two-block", case, BF, True, launch(dev, case, BF, True, backward=True, lend_workspace=False))
+    whole, ran = launch(dev, case, BF, True, backward=True, lend_workspace=False)
+    assert kernels(ran["bwd"]) == ["attn_bwd_dq2_kernel", "attn_bwd_dkv2_kernel"]
+    check("bwd two-block", case, BF, True, whole)
 
 
 @pytest.mark.parametrize("case", P.BWD_TWO_BLOCK + P.BWD_ONE_PASS_EQUAL, ids=P.case_id)
 def test_backward_one_pass(dev, case):
     """attn_bwd1p.hip (d_h = 32, a workspace lent; d_h = 24 stays with the two-block kernels): ragged and equal-length launches, called twice
     over the same workspace, which the call itself must zero again."""
-    check("bwd one-pass", case, BF, True, launch(dev, case, BF, True, backward=True, lend_workspace=True, calls=2))
+    whole, ran = launch(dev, case, BF, True, backward=True, lend_workspace=True, calls=2)
+    if case[1] == 32:
+        equal = case in P.BWD_ONE_PASS_EQUAL   # (their key counts are multiples of 512: no slot for partial key blocks)
+        assert kernels(ran["bwd"]) == ["attn_bwd1p_kernel"]
+        assert (ran["bwd"][0].equal_len, ran["bwd"][0].partial_blocks, ran["bwd"][0].tail256) == ((1, 0, 1) if equal else (0, 1, 0))
+    else:
+        assert kernels(ran["bwd"]) == ["attn_bwd_dq2_kernel", "attn_bwd_dkv2_kernel"]
+    check("bwd one-pass", case, BF, True, whole)
 
 
 @pytest.mark.parametrize("case", P.BWD_64, ids=P.case_id)
 def test_backward_dh64_wide_dq(dev, case):
     """bf16, prescaled, d_h = 64, >= 256 queries, as dispatched by default: attn_bwd64w.hip's wide dQ over the full 256-row blocks, the
-    one-block kernels over the rows past them and over dK / dV."""
-    check("bwd64w dQ", case, BF, True, launch(dev, case, BF, True, backward=True))
+    one-block kernels over the rows past them (none in [768], an equal-length multiple of 256) and over dK / dV."""
+    whole, ran = launch(dev, case, BF, True, backward=True)
+    dq, dkv = _form("attn_bwd_dq_kernel", case, BF, True), _form("attn_bwd_dkv_kernel", case, BF, True)
+    assert kernels(ran["bwd"]) == ["attn_bwd64w_dq_kernel"] + ([dq] if _dq_past_full_blocks(case) else []) + [dkv]
+    assert [l.tail256 for l in ran["bwd"]] == [0] + ([1] if _dq_past_full_blocks(case) else []) + [0]
+    check("bwd64w dQ", case, BF, True, whole)
 
 
-_WIDE_DKV_SNIPPET = r"""
-import sys, torch
-import attn_probe as P, test_gpu_attn_edges as T
-torch.save({P.case_id(c): T.launch(torch.device("cuda:0"), c, torch.bfloat16, True, backward=True) for c in P.BWD_64}, sys.argv[1])
-"""
-
-
-def test_backward_dh64_wide_dkv(dev, tmp_path):
-    """attn_bwd64w.hip's wide dK / dV form next to its wide dQ.  The form is chosen once per process (ACAI_ATTN64_BWD_WIDE=3): one child
-    process runs the three cases, this one checks what it wrote."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    f = tmp_path / "wide.pt"
-    env = dict(os.environ, ACAI_ATTN64_BWD_WIDE="3", PYTHONPATH=os.pathsep.join([os.path.dirname(here), here, os.environ.get("PYTHONPATH", "")]))
-    r = subprocess.run([sys.executable, "-c", _WIDE_DKV_SNIPPET, str(f)], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    wholes = torch.load(f)
+def test_backward_dh64_wide_dkv(dev):
+    """attn_bwd64w.hip's wide dK / dV form next to its wide dQ (ACAI_ATTN_OV_BWD64_WIDE = 3; by default only sequences of >= 2048 queries
+    take it): the wide kernel over the full 256-key blocks, the one-block kernel over the keys past them.  [768] x [129] has no full key
+    block and keeps the one-block dK / dV kernel alone: two of the three cases reach the wide form."""
+    from acai_omr_amd import _lib
     for case in P.BWD_64:
-        check("bwd64w dQ + dK/dV", case, BF, True, wholes[P.case_id(case)])
+        whole, ran = launch(dev, case, BF, True, backward=True, overrides=[(_lib.ATTN_OV_BWD64_WIDE, 3)])
+        dq, dkv = _form("attn_bwd_dq_kernel", case, BF, True), _form("attn_bwd_dkv_kernel", case, BF, True)
+        wide = max(case[3] or case[2]) >= 256
+        assert wide == (case != P.BWD_64[2])
+        assert kernels(ran["bwd"]) == ["attn_bwd64w_dq_kernel"] + ([dq] if _dq_past_full_blocks(case) else []) + (["attn_bwd64w_dkv_kernel"] if wide else []) + [dkv]
+        assert ran["bwd"][-1].tail256 == (2 if wide else 0)
+        check("bwd64w dQ + dK/dV", case, BF, True, whole)
 
 
 @pytest.mark.parametrize("case", P.BWD_ACCUMULATE, ids=P.case_id)
@@ -206,4 +275,8 @@ def test_backward_accumulates_into_dk_dv(dev, case):
     g = torch.Generator().manual_seed(9)
     H, dh, lens_q, lens_k, causal = case
     before = tuple(torch.randn(sum(lens_k), H * dh, generator=g).to(BF) for _ in range(2))
-    check("bwd accumulate", case, BF, True, launch(dev, case, BF, True, backward=True, accumulate=before), accumulate=before)
+    whole, ran = launch(dev, case, BF, True, backward=True, accumulate=before)
+    # (d_h = 64 with 300 queries: the wide dQ and the one-block dQ over the 44 rows past its block; accumulation keeps the one-block dK / dV)
+    assert kernels(ran["bwd"]) == ["attn_bwd64w_dq_kernel", _form("attn_bwd_dq_kernel", case, BF, True), _form("attn_bwd_dkv_kernel", case, BF, True)]
+    assert [l.tail256 for l in ran["bwd"]] == [0, 1, 0]
+    check("bwd accumulate", case, BF, True, whole, accumulate=before)

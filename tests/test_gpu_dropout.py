@@ -126,8 +126,8 @@ def ref_attn_dropout(q, k, v, dout, lens_q, lens_k, H, dh, causal, p, seed):
     return o, lse, qr.grad, kr.grad, vr.grad
 
 
-# The dropout instantiations (attn_varlen.hip launch<>: attn_fwd_kernel<T, DHP, FAST, DROP = true, PRE>; attn_bwd.hip launch_pair(D = true, F, P):
-# attn_bwd_dq_kernel / attn_bwd_dkv_kernel<T, DHP, F, D, P>).  "slow": d_h not a multiple of 16 bytes' elements (fp32 4, bf16 8);
+# The dropout instantiations (attn_varlen.hip launch_form<>: attn_fwd_kernel<T, DHP, FAST, DROP = true, PRE>; attn_bwd.hip launch_form<>:
+# attn_bwd_dq_kernel / attn_bwd_dkv_kernel<T, DHP, F, D = true, P>).  "slow": d_h not a multiple of 16 bytes' elements (fp32 4, bf16 8);
 # "fast": aligned, q unscaled; "pre": aligned, q prescaled (the training path).  Each instantiation is reached by the cases marked:
 #
 #   T     DHP | slow                     | fast                            | pre

@@ -120,96 +120,93 @@ def test_attn_backward(dev, H, dh, lens_q, lens_k, causal, dtype, prescaled):
         assert err < tol, (name, float(err))
 
 
-_BWD64W_SNIPPET = r"""
-import sys, torch
-from acai_omr_amd import engine, ops
-dev, bf, dh, H = "cuda", torch.bfloat16, 64, 2
-lens_q, lens_k = [600, 300, 256], [1000, 577, 256]
-E = H * dh
-g = torch.Generator().manual_seed(11)
-q = (torch.randn(sum(lens_q), E, generator=g) * ops.QSCALE(dh)).to(dev).to(bf)
-k = torch.randn(sum(lens_k), E, generator=g).to(dev).to(bf)
-v = torch.randn(sum(lens_k), E, generator=g).to(dev).to(bf)
-do = torch.randn(sum(lens_q), E, generator=g).to(dev).to(bf)
-cu_q, cu_k = engine.cu_from_lens(lens_q, dev), engine.cu_from_lens(lens_k, dev)
-lse = torch.empty(H * sum(lens_q), device=dev)
-o = ops.attn_varlen(q, k, v, cu_q, cu_k, H, dh, max(lens_q), lse=lse, q_prescaled=True)
-dq, dk, dv = torch.full_like(q, 7.0), torch.full_like(k, 7.0), torch.full_like(v, 7.0)
-ops.attn_varlen_bwd(q, k, v, o, do, lse, cu_q, cu_k, H, dh, max(lens_q), max(lens_k), False, dq, dk, dv, q_prescaled=True)
-torch.cuda.synchronize()
-torch.save({"dq": dq.cpu(), "dk": dk.cpu(), "dv": dv.cpu()}, sys.argv[1])
-"""
+def _bwd64w_gradients():
+    """dq, dk, dv of one ragged d_h = 64 batch under the process-wide overrides as they stand, and the kernels that ran."""
+    from acai_omr_amd import _lib, engine, ops
+    dev, bf, dh, H = "cuda", torch.bfloat16, 64, 2
+    lens_q, lens_k = [600, 300, 256], [1000, 577, 256]
+    E = H * dh
+    g = torch.Generator().manual_seed(11)
+    q = (torch.randn(sum(lens_q), E, generator=g) * ops.QSCALE(dh)).to(dev).to(bf)
+    k = torch.randn(sum(lens_k), E, generator=g).to(dev).to(bf)
+    v = torch.randn(sum(lens_k), E, generator=g).to(dev).to(bf)
+    do = torch.randn(sum(lens_q), E, generator=g).to(dev).to(bf)
+    cu_q, cu_k = engine.cu_from_lens(lens_q, dev), engine.cu_from_lens(lens_k, dev)
+    lse = torch.empty(H * sum(lens_q), device=dev)
+    o = ops.attn_varlen(q, k, v, cu_q, cu_k, H, dh, max(lens_q), lse=lse, q_prescaled=True)
+    dq, dk, dv = torch.full_like(q, 7.0), torch.full_like(k, 7.0), torch.full_like(v, 7.0)
+    ops.attn_varlen_bwd(q, k, v, o, do, lse, cu_q, cu_k, H, dh, max(lens_q), max(lens_k), False, dq, dk, dv, q_prescaled=True)
+    ran = _lib.attn_last_kernels()
+    torch.cuda.synchronize()
+    return {"dq": dq.cpu(), "dk": dk.cpu(), "dv": dv.cpu()}, ran
 
 
-def test_attn_backward_wide_dh64_forms_equal_the_one_block_kernels(dev, tmp_path):
+def test_attn_backward_wide_dh64_forms_equal_the_one_block_kernels(dev):
     """attn_bwd64w.hip (one wave per SIMD, two lane-owned blocks per wave): dQ is on by default, dK / dV is off (measured slower); both are
     the same arithmetic in the same summation order as attn_bwd.hip's one-block kernels, so every form must give the same gradients to the
-    last place - ragged batch, tails past the last full 256-row block, a sequence of exactly one block, a ragged last streamed tile.  The form is chosen once
-    per process (ACAI_ATTN64_BWD_WIDE), hence the child processes, one after the other."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    last place - ragged batch, tails past the last full 256-row block, a sequence of exactly one block, a ragged last streamed tile.  The form is pinned
+    by the override ACAI_ATTN_OV_BWD64_WIDE, and each run asserts the kernels it ran."""
+    from acai_omr_amd import _lib, ops
+    dq, dkv = "attn_bwd_dq_kernel<bf16,64,fast=1,drop=0,pre=1>", "attn_bwd_dkv_kernel<bf16,64,fast=1,drop=0,pre=1>"
+    expected = {0: [dq, dkv], 1: ["attn_bwd64w_dq_kernel", dq, dkv], 2: [dq, "attn_bwd64w_dkv_kernel", dkv],
+                3: ["attn_bwd64w_dq_kernel", dq, "attn_bwd64w_dkv_kernel", dkv]}
     outs = {}
-    for mode in ("0", "1", "2", "3"):
-        f = tmp_path / f"w{mode}.pt"
-        env = dict(os.environ, ACAI_ATTN64_BWD_WIDE=mode, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-        r = subprocess.run([sys.executable, "-c", _BWD64W_SNIPPET, str(f)], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs[mode] = torch.load(f)
-    for mode in ("1", "2", "3"):
+    for mode in (0, 1, 2, 3):
+        with ops.attn_override(_lib.ATTN_OV_BWD64_WIDE, mode):
+            outs[mode], ran = _bwd64w_gradients()
+        assert ran == expected[mode], (mode, ran)
+    for mode in (1, 2, 3):
         for n in ("dq", "dk", "dv"):
-            a, b = outs["0"][n].float(), outs[mode][n].float()
+            a, b = outs[0][n].float(), outs[mode][n].float()
             # full streamed tiles give the same bits (tools/dbg_bwd64w.py); in a ragged last tile the one-block kernels' general loop forms
             # 2^(c s - lse) from a zero-started accumulator where these start the accumulator at -lse: a last-place difference in a few elements
             d = (a - b).abs()
             assert float(d.max()) <= 2.0 ** -7 * float(a.abs().max()) and float((d > 0).float().mean()) < 2e-3, (mode, n, float(d.max()), float((d > 0).float().mean()))
-    assert float(outs["0"]["dq"].float().abs().max()) < 6.0   # (every row was written: the 7.0 fill is gone)
+    assert float(outs[0]["dq"].float().abs().max()) < 6.0   # (every row was written: the 7.0 fill is gone)
 
 
-_BWD1P_SNIPPET = r"""
-import sys, torch
-from acai_omr_amd import engine, ops
-dev, bf, dh = "cuda", torch.bfloat16, 32
-out = {}
-for name, H, lens_q, lens_k in (("square", 3, [1024] * 3, [1024] * 3), ("ragged_last_tile", 2, [1000] * 2, [1536] * 2), ("smallest", 1, [512], [512]),
-                               # ragged batches: keys past the last full 512-key block (the second launch), a sequence shorter than one block / one tile,
-                               # a one-key tail, a sequence whose keys are all tail, fewer than 64 queries in the LAST sequence (the workspace's padding rows)
-                               ("ragged", 2, [700, 40, 1300, 513], [1100, 300, 1025, 512]), ("ragged_short_last", 1, [600, 33], [640, 511])):
-    E = H * dh
-    B, lq, lk = len(lens_q), max(lens_q), max(lens_k)
-    g = torch.Generator().manual_seed(sum(lens_q) + sum(lens_k))
-    qkv = torch.randn(sum(lens_k), 3 * E, generator=g).to(dev).to(bf)     # k, v: strided views of one buffer, like the in-projection's output
-    q = (torch.randn(sum(lens_q), E, generator=g) * ops.QSCALE(dh)).to(dev).to(bf)
-    k, v = qkv[:, E:2 * E], qkv[:, 2 * E:]
-    do = torch.randn(sum(lens_q), E, generator=g).to(dev).to(bf)
-    cu_q, cu_k = engine.cu_from_lens(lens_q, dev), engine.cu_from_lens(lens_k, dev)
-    lse = torch.empty(H * sum(lens_q), device=dev)
-    o = ops.attn_varlen(q, k, v, cu_q, cu_k, H, dh, lq, lse=lse, q_prescaled=True)
-    dq, dkv = torch.full_like(q, 7.0), torch.full_like(qkv, 7.0)
-    for rep in range(2):   # (twice: the workspace is reused and must be re-zeroed by the call itself)
-        ops.attn_varlen_bwd(q, k, v, o, do, lse, cu_q, cu_k, H, dh, lq, lk, False, dq, dkv[:, E:2 * E], dkv[:, 2 * E:], q_prescaled=True)
-    torch.cuda.synchronize()
-    out[name] = {"dq": dq.cpu(), "dk": dkv[:, E:2 * E].cpu(), "dv": dkv[:, 2 * E:].cpu(), "untouched": dkv[:, :E].cpu()}
-torch.save(out, sys.argv[1])
-"""
+def _bwd1p_gradients():
+    """The gradients of five d_h = 32 batches under the process-wide overrides as they stand, and the kernels each backward call ran."""
+    from acai_omr_amd import _lib, engine, ops
+    dev, bf, dh = "cuda", torch.bfloat16, 32
+    out, ran = {}, {}
+    for name, H, lens_q, lens_k in (("square", 3, [1024] * 3, [1024] * 3), ("ragged_last_tile", 2, [1000] * 2, [1536] * 2), ("smallest", 1, [512], [512]),
+                                   # ragged batches: keys past the last full 512-key block (the second launch), a sequence shorter than one block / one tile,
+                                   # a one-key tail, a sequence whose keys are all tail, fewer than 64 queries in the LAST sequence (the workspace's padding rows)
+                                   ("ragged", 2, [700, 40, 1300, 513], [1100, 300, 1025, 512]), ("ragged_short_last", 1, [600, 33], [640, 511])):
+        E = H * dh
+        B, lq, lk = len(lens_q), max(lens_q), max(lens_k)
+        g = torch.Generator().manual_seed(sum(lens_q) + sum(lens_k))
+        qkv = torch.randn(sum(lens_k), 3 * E, generator=g).to(dev).to(bf)     # k, v: strided views of one buffer, like the in-projection's output
+        q = (torch.randn(sum(lens_q), E, generator=g) * ops.QSCALE(dh)).to(dev).to(bf)
+        k, v = qkv[:, E:2 * E], qkv[:, 2 * E:]
+        do = torch.randn(sum(lens_q), E, generator=g).to(dev).to(bf)
+        cu_q, cu_k = engine.cu_from_lens(lens_q, dev), engine.cu_from_lens(lens_k, dev)
+        lse = torch.empty(H * sum(lens_q), device=dev)
+        o = ops.attn_varlen(q, k, v, cu_q, cu_k, H, dh, lq, lse=lse, q_prescaled=True)
+        dq, dkv = torch.full_like(q, 7.0), torch.full_like(qkv, 7.0)
+        for rep in range(2):   # (twice: the workspace is reused and must be re-zeroed by the call itself)
+            ops.attn_varlen_bwd(q, k, v, o, do, lse, cu_q, cu_k, H, dh, lq, lk, False, dq, dkv[:, E:2 * E], dkv[:, 2 * E:], q_prescaled=True)
+        ran[name] = _lib.attn_last_kernels()
+        torch.cuda.synchronize()
+        out[name] = {"dq": dq.cpu(), "dk": dkv[:, E:2 * E].cpu(), "dv": dkv[:, 2 * E:].cpu(), "untouched": dkv[:, :E].cpu()}
+    return out, ran
 
 
-def test_attn_backward_one_pass_dh32_equals_the_two_kernel_form(dev, tmp_path):
+def test_attn_backward_one_pass_dh32_equals_the_two_kernel_form(dev):
     """attn_bwd1p.hip (bf16, d_h = 32, prescaled q, no mask, long sequences): P and dS are formed once per score and dQ is summed over the
-    key blocks with fp32 atomics, so against the two-kernel form (ACAI_ATTN_BWD_1P=0) dK / dV agree to the last place and dQ to the rounding
+    key blocks with fp32 atomics, so against the two-kernel form (ACAI_ATTN_OV_BWD_1P = 0) dK / dV agree to the last place and dQ to the rounding
     of an fp32 sum taken in another order.  Query counts that end inside a 64-row tile, strided k / v / dk / dv views, the smallest shape
-    the form takes, ragged batches (partial key blocks, short sequences), and a second call over the same workspace.  The form is chosen
-    once per process: child processes."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    the form takes, ragged batches (partial key blocks, short sequences), and a second call over the same workspace.  The form is pinned by
+    the override, and each run asserts the kernels it ran."""
+    from acai_omr_amd import _lib, ops
     outs = {}
-    for mode in ("0", "1"):
-        f = tmp_path / f"p{mode}.pt"
-        env = dict(os.environ, ACAI_ATTN_BWD_1P=mode, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-        r = subprocess.run([sys.executable, "-c", _BWD1P_SNIPPET, str(f)], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs[mode] = torch.load(f)
-    for case in outs["0"]:
-        two, one = outs["0"][case], outs["1"][case]
+    for mode, expected in ((0, ["attn_bwd_dq2_kernel", "attn_bwd_dkv2_kernel"]), (1, ["attn_bwd1p_kernel"])):
+        with ops.attn_override(_lib.ATTN_OV_BWD_1P, mode):
+            outs[mode], ran = _bwd1p_gradients()
+        assert all(r == expected for r in ran.values()), (mode, ran)
+    for case in outs[0]:
+        two, one = outs[0][case], outs[1][case]
         assert float((one["untouched"].float() - 7.0).abs().max()) == 0.0, case
         for n in ("dq", "dk", "dv"):
             a, b = two[n].float(), one[n].float()

@@ -1,10 +1,15 @@
 """Timing ablations of attn_fwd64_kernel (results are wrong in these modes): needs the -DACAI_ATTN64_ABLATE build
 (bash tools/build_variant.sh abl64 "-fno-slp-vectorize -DACAI_ATTN64_ABLATE" attn_fwd64.hip; ACAI_OMR_LIB=.../variants/abl64.so).
+The four-wave attn_fwd64_kernel is pinned through the override (the default form, attn_fwd64w_kernel, has ablations of its own under the same
+switch: --attn fwd64=0, tools/attn_overrides.py).
 Bits: 1 no exp2, 2 no pack, 4 no LDS fragment reads, 8 no staging / barrier, 16 no S MFMAs, 32 no P V MFMAs, 64 no row-sum MFMAs."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from acai_omr_amd import engine, ops
+from acai_omr_amd import _lib, engine, ops
+import attn_overrides
+_lib.check(_lib.lib().acai_attn_set_override(_lib.ATTN_OV_FWD64, _lib.ATTN_FWD64_NW4), "acai_attn_set_override")
+attn_overrides.apply(sys.argv)
 dev, bf = "cuda", torch.bfloat16
 B, H, S, dh = 16, 12, 4096, 64
 E = H * dh

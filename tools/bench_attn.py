@@ -1,10 +1,12 @@
-"""Varlen flash attention fwd / bwd timing on the path's shapes: python tools/bench_attn.py [iters]
-(run under `rocprofv3 --kernel-trace --stats` for the per-kernel split)."""
+"""Varlen flash attention fwd / bwd timing on the path's shapes: python tools/bench_attn.py [iters] [--attn NAME=VALUE ...]
+(run under `rocprofv3 --kernel-trace --stats` for the per-kernel split; --attn: tools/attn_overrides.py)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from acai_omr_amd import engine, ops
+import attn_overrides
 
+attn_overrides.apply(sys.argv)
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 dev = torch.device("cuda", 0)
 only = os.environ.get("ACAI_BENCH_ATTN_ONLY")

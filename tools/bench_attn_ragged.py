@@ -1,11 +1,14 @@
 """Attention forward / backward on a RAGGED batch shaped like config 5's streams (images 256x1024 ... 768x3072 -> 1024 ... 9216 tokens):
-python tools/bench_attn_ragged.py [H dh]   (default 16 32: the MAE decoder; 12 64: the encoder.  ACAI_ATTN_BWD_1P=0: the two-kernel d_h = 32
-backward; ACAI_XCD_ORDER=0 / 1: the XCD-aware block order of the one-dimensional grids forced off / on)"""
+python tools/bench_attn_ragged.py [H dh] [--attn NAME=VALUE ...]   (default 16 32: the MAE decoder; 12 64: the encoder.  --attn bwd_1p=0: the
+two-kernel d_h = 32 backward; --attn xcd_order=0 / 1: the XCD-aware block order of the d_h = 64 kernels' one-dimensional grids forced off / on;
+tools/attn_overrides.py)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from acai_omr_amd import engine, ops
+import attn_overrides
 
+overrides = attn_overrides.apply(sys.argv)
 dev, bf = torch.device("cuda", 0), torch.bfloat16
 H, dh = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (16, 32)
 E = H * dh
@@ -35,4 +38,4 @@ for name, fn in (("fwd", fwd), ("bwd", bwd)):
     res[name] = (time.perf_counter() - t0) / 10 * 1e3
 scores = H * sum(l * l for l in lens)
 print(f"ragged batch of {len(lens)} sequences ({min(lens)}..{max(lens)} tokens, {tot} in all), {H} heads of {dh}: fwd {res['fwd']:.3f} ms  bwd {res['bwd']:.3f} ms "
-      f"({scores / res['bwd'] / 1e9:.2f} T scores/s)  [ACAI_ATTN_BWD_1P={os.environ.get('ACAI_ATTN_BWD_1P', '1')} ACAI_XCD_ORDER={os.environ.get('ACAI_XCD_ORDER', 'auto')} ACAI_RAGGED_SORT={os.environ.get('ACAI_RAGGED_SORT', '0')}]")
+      f"({scores / res['bwd'] / 1e9:.2f} T scores/s)  [{overrides}; ACAI_RAGGED_SORT={os.environ.get('ACAI_RAGGED_SORT', '0')}]")

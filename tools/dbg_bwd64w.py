@@ -1,10 +1,12 @@
-"""Debug aid: dq / dk / dv of the d_h = 64 backward through the wide kernels (ACAI_ATTN64_BWD_WIDE as set) saved to a file, or two saved files compared.
-python tools/dbg_bwd64w.py run out.pt [lq lk H] | python tools/dbg_bwd64w.py cmp a.pt b.pt"""
+"""Debug aid: dq / dk / dv of the d_h = 64 backward through the wide kernels (--attn bwd64_wide=0..3, tools/attn_overrides.py) saved to a file, or two saved files compared.
+python tools/dbg_bwd64w.py run out.pt [lq lk H [dh]] [--attn NAME=VALUE ...] | python tools/dbg_bwd64w.py cmp a.pt b.pt"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 if sys.argv[1] == "run":
     from acai_omr_amd import engine, ops
+    import attn_overrides
+    attn_overrides.apply(sys.argv)
     lq, lk, H = (int(x) for x in sys.argv[3:6]) if len(sys.argv) > 5 else (256, 400, 1)
     dev, bf, dh = "cuda", torch.bfloat16, int(sys.argv[6]) if len(sys.argv) > 6 else 64
     E = H * dh

@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/dbg}
 mkdir -p $out
 for shape in "512 512 1" "1024 1024 2" "1000 1024 1" "4096 4096 16"; do
-  ACAI_ATTN_BWD_1P=0 timeout -k 10 120 python tools/dbg_bwd64w.py run $out/a.pt $shape 32 &&
-  ACAI_ATTN_BWD_1P=1 timeout -k 10 120 python tools/dbg_bwd64w.py run $out/b.pt $shape 32 &&
+  timeout -k 10 120 python tools/dbg_bwd64w.py run $out/a.pt $shape 32 --attn bwd_1p=0 &&
+  timeout -k 10 120 python tools/dbg_bwd64w.py run $out/b.pt $shape 32 --attn bwd_1p=1 &&
   echo "== $shape" && timeout -k 10 60 python tools/dbg_bwd64w.py cmp $out/a.pt $out/b.pt | grep -v "^ \|tensor\|\[" || exit 1
 done
