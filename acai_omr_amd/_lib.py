@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip"]
+SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip", "prune.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -171,6 +171,10 @@ EXTENTS_MAX_RUN = 256               # csrc/rectify.hip (ACAI_EXTENTS_MAX_RUN): t
 COL_CHUNK_ROWS, COL_MAX_CHUNKS = 64, 64   # csrc/ingest.hip (ACAI_COL_*): acai_page_col_profile walks chunks of max(64, ceil(H / 64)) rows
 
 
+# csrc/prune.hip (ACAI_PRUNE_*): the columns of the device table, the largest halo, grid (patches of one image) and number of images
+PRUNE_TABLE_COLS, PRUNE_MAX_HALO, PRUNE_MAX_GRID, PRUNE_MAX_IMAGES = 8, 3, 1 << 20, 65535
+
+
 def col_chunks(H):
     """(rows per chunk, chunks) of acai_page_col_profile for a page of H rows: its `work` holds 4 * chunks * W int32."""
     rows = max(COL_CHUNK_ROWS, -(-int(H) // COL_MAX_CHUNKS))
@@ -218,6 +222,10 @@ _SIGNATURES = {
     "acai_page_ingest": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p]),
     "acai_page_col_profile": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "acai_page_box_ink": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
+    "acai_patch_ink": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_float, c_void_p, c_void_p]),
+    "acai_patch_keep": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "acai_patch_compact": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "acai_attn_map_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "acai_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "acai_attn_varlen_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_uint32, c_int, c_void_p]),

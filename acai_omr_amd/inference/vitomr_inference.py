@@ -27,14 +27,24 @@ def set_up_omr_inference(lmx_vocab_path=LMX_VOCAB_PATH, max_batch_size=32, cache
     return vitomr.to(device), device
 
 
-def _encode(vitomr, img):
+def _encode(vitomr, img, prune=None, return_pruned=False):
     # encoder outside autocast, as the reference (its eval fast path is not autocastable, vitomr_inference.py:63)
     with autocast(device_type="cuda", enabled=False):
-        return vitomr.encoder.forward_packed(img)
+        if prune is None and not return_pruned:
+            return vitomr.encoder.forward_packed(img)
+        return vitomr.encoder.forward_packed(img, prune=prune, return_pruned=return_pruned)
+
+
+def _full_grid(dims, lens, pruned):
+    """(the lengths `_check_grids` compares the grids with, the packed kept indices or None): with a pruned memory the grids are the FULL
+    grids, not the kept counts, and the maps are expanded to them (ViTOMR._align_packed)."""
+    if pruned is None:
+        return lens, None
+    return [h * w for h, w in dims], pruned.kept
 
 
 def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1, length_penalty=1.0, speculative=0, ngram=3, prefix=None, *,
-              grammar=None):
+              grammar=None, prune=None):
     """img: one (1,H,W) tensor or a list of them -> (seqs int64 (B,T'), log_probs fp32 (B,T'), seq_mask bool (B,T')).
     beam_width > 1 (extension): beam search with that many hypotheses per image, scored by cum / len^length_penalty
     (ViTOMR.cached_beam_generate); beam_width = 1 is the reference's greedy decode.
@@ -46,7 +56,13 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
     here).
     grammar (extension, default None = off): a grammar.TokenAutomaton - greedy decoding in which every token is one the automaton allows
     after the tokens before it (ViTOMR.cached_greedy_generate); with beam_width > 1, speculative or prefix it raises ValueError (out of
-    scope here).  What a learned automaton does to the output of a trained checkpoint has not been measured."""
+    scope here).  What a learned automaton does to the output of a trained checkpoint has not been measured.
+    prune (an extension, default None = off: the path above, bit for bit, no launch added): True or a `prune.PruneConfig` - the patches that
+    are blank paper are dropped from the packed stream before the encoder's projection (prune.prune_patches: three launches and one copy
+    of the kept counts to the host per batch), so the encoder, the cross K/V prefill and every decode step see a shorter memory; img may
+    also be an already pruned `utils.PackedPatches`.  It combines with every decode mode above and with the FP8 memory cache.  The
+    thresholds are chosen on synthetic pages; the blank share of real systems and what dropping paper does to the output of a trained
+    checkpoint have not been measured."""
     if grammar is not None:
         for other, on in (("beam search (beam_width > 1)", beam_width != 1), ("speculative decoding (speculative)", bool(speculative)),
                           ("prompted decoding (prefix)", prefix is not None)):
@@ -58,7 +74,7 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
         raise ValueError("prefix (prompted decoding) cannot be combined with beam search (beam_width > 1): out of scope here")
     vitomr.eval()
     with torch.no_grad():
-        lat32, _, lens = _encode(vitomr, img)
+        lat32, _, lens = _encode(vitomr, img, prune)
         with autocast(device_type=device, dtype=torch.bfloat16):
             mem = vitomr.transition_head.forward_packed(lat32)
             bf = mem.dtype == torch.bfloat16
@@ -99,32 +115,37 @@ def _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs):
     return vitomr._greedy_packed(mem32, memb, lens, max_inference_len, prefix=prefix, grammar=grammar)
 
 
-def aligned_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, layers=None, head_weights=None, return_maps=False, **decode_kwargs):
+def aligned_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, layers=None, head_weights=None, return_maps=False, *, prune=None,
+                      **decode_kwargs):
     """inference() plus token-to-image alignment (an extension) -> (seqs, log_probs, seq_mask, TokenAlignment).  The images are encoded once;
     the decode is inference()'s own (decode_kwargs - beam_width, length_penalty, speculative, ngram, prefix, grammar - are passed on, and
     its errors stay its errors); then one teacher-forced pass over the produced tokens on the same packed memory, with the decode's
     positions, writes each token's cross-attention map over the image's patches and reduces it to a location
     (ViTOMR.locate_tokens; the grids come from the image sizes).  layers / head_weights select and weight the decoder layers and heads
     that are averaged (OMRDecoder.cross_attention_maps_packed; default all, uniform): which of them align best on trained checkpoints has
-    not been measured.  return_maps keeps the per-token maps in the result."""
+    not been measured.  return_maps keeps the per-token maps in the result.  prune: as in inference(); the alignment still speaks of the
+    FULL patch grid - `patch` indexes it, centroids and spreads are pixels of the input, `maps[i]` is (L_i - 1, h_p * w_p) with zeros at the
+    dropped patches (ops.attn_map_expand)."""
     _check_decode_kwargs("aligned_inference", decode_kwargs)
     vitomr.decoder._alignment_selection(layers, head_weights)
     vitomr.eval()
     with torch.no_grad():
         dims = list(img.dims) if hasattr(img, "dims") else [vitomr.encoder._grid(t) for t in img]
-        lat32, _, lens = _encode(vitomr, img)
+        lat32, _, lens, pruned = _encode(vitomr, img, prune, True)
         with autocast(device_type=device, dtype=torch.bfloat16):
             mem = vitomr.transition_head.forward_packed(lat32)
             bf = mem.dtype == torch.bfloat16
             mem32, memb = (None, mem) if bf else (mem, None)
             seqs, lps, mask = _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs)
-            grids = vitomr._check_grids(dims, lens)
-            align = vitomr._align_packed(mem32, memb, lens, seqs, mask, layers, head_weights, True, grids, vitomr.encoder.patch_size, return_maps)
+            full, kept = _full_grid(dims, lens, pruned)
+            grids = vitomr._check_grids(dims, full)
+            align = vitomr._align_packed(mem32, memb, lens, seqs, mask, layers, head_weights, True, grids, vitomr.encoder.patch_size, return_maps,
+                                         kept=kept)
     return seqs, lps, mask, align
 
 
 def confident_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, top_k=5, temperature=1.0, uncertainty=None, layers=None,
-                        head_weights=None, **decode_kwargs):
+                        head_weights=None, *, prune=None, **decode_kwargs):
     """inference() plus per-token confidence (an extension) -> (seqs, log_probs, seq_mask, TokenConfidence).  The images are encoded once
     and the decode is inference()'s own (decode_kwargs as in aligned_inference; its errors stay its errors); then one teacher-forced pass
     over the produced tokens on the same packed memory, with the decode's positions, scores every token under softmax(logits / temperature):
@@ -133,7 +154,8 @@ def confident_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, top
     head_weights as in aligned_inference), and fills TokenConfidence.uncertainty - a heat map per image over its patch grid, the maps summed
     with that per-token weight (ViTOMR.uncertainty_maps) - and TokenConfidence.alignment, what aligned_inference returns.  After a
     grammar-constrained decode the scores are the unconstrained model's: rank > 0 marks a token the grammar forced.  How well the scores
-    mark real errors on trained checkpoints has not been measured."""
+    mark real errors on trained checkpoints has not been measured.  prune: as in inference(); heat maps and alignment cover the FULL patch
+    grid, as in aligned_inference."""
     _check_decode_kwargs("confident_inference", decode_kwargs)
     vitomr._check_confidence_args(top_k, temperature)
     if uncertainty is not None:
@@ -144,65 +166,73 @@ def confident_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, top
     vitomr.eval()
     with torch.no_grad():
         dims = list(img.dims) if hasattr(img, "dims") else [vitomr.encoder._grid(t) for t in img]
-        lat32, _, lens = _encode(vitomr, img)
+        lat32, _, lens, pruned = _encode(vitomr, img, prune, True)
         with autocast(device_type=device, dtype=torch.bfloat16):
             mem = vitomr.transition_head.forward_packed(lat32)
             bf = mem.dtype == torch.bfloat16
             mem32, memb = (None, mem) if bf else (mem, None)
             seqs, lps, mask = _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs)
-            grids = vitomr._check_grids(dims, lens) if uncertainty is not None else None
+            full, kept = _full_grid(dims, lens, pruned)
+            grids = vitomr._check_grids(dims, full) if uncertainty is not None else None
             conf = vitomr._confidence_packed(mem32, memb, lens, seqs, mask, top_k, temperature, True, uncertainty, layers, head_weights, grids,
-                                             vitomr.encoder.patch_size, uncertainty is not None)
+                                             vitomr.encoder.patch_size, uncertainty is not None, kept=kept)
     return seqs, lps, mask, conf
 
 
-def diagnosed_inference(vitomr: ViTOMR, img, target_lmx_seqs, device, max_inference_len=1536, **decode_kwargs):
+def diagnosed_inference(vitomr: ViTOMR, img, target_lmx_seqs, device, max_inference_len=1536, *, prune=None, **decode_kwargs):
     """inference() scored against the ground truth (an extension) -> (seqs, log_probs, seq_mask, TokenConfidence, EditAlignment).  The
     images are encoded once and the decode is inference()'s own (decode_kwargs as in aligned_inference; its errors stay its errors); the
     decoded rows are then aligned to target_lmx_seqs - a list of 1-D token tensors, one per image, written as the decode writes its rows
     (<bos> first, <eos> last) - on the device (ops.edit_alignment), and one teacher-forced pass on the same packed memory gives the
     per-token confidence and, in TokenConfidence.uncertainty, the page heat map of the tokens that are wrong (ViTOMR.error_maps): a
     substituted or inserted token weighs 1 where it stands, a missing one 1 at the output position where it should have been emitted.
-    TokenConfidence.alignment locates every token.  EditAlignment.pred_op != 0 are the error labels utils.confidence_error_auroc takes."""
+    TokenConfidence.alignment locates every token.  EditAlignment.pred_op != 0 are the error labels utils.confidence_error_auroc takes.
+    prune: as in inference(); the error map and the alignment cover the FULL patch grid, as in aligned_inference."""
     _check_decode_kwargs("diagnosed_inference", decode_kwargs)
     vitomr.eval()
     with torch.no_grad():
         dims = list(img.dims) if hasattr(img, "dims") else [vitomr.encoder._grid(t) for t in img]
-        lat32, _, lens = _encode(vitomr, img)
+        lat32, _, lens, pruned = _encode(vitomr, img, prune, True)
         with autocast(device_type=device, dtype=torch.bfloat16):
             mem = vitomr.transition_head.forward_packed(lat32)
             bf = mem.dtype == torch.bfloat16
             mem32, memb = (None, mem) if bf else (mem, None)
             seqs, lps, mask = _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs)
-            grids = vitomr._check_grids(dims, lens)
+            full, kept = _full_grid(dims, lens, pruned)
+            grids = vitomr._check_grids(dims, full)
             al, w = vitomr._error_weights(seqs, mask, target_lmx_seqs, None)
-            conf = vitomr._confidence_packed(mem32, memb, lens, seqs, mask, 5, 1.0, True, w, None, None, grids, vitomr.encoder.patch_size, True)
+            conf = vitomr._confidence_packed(mem32, memb, lens, seqs, mask, 5, 1.0, True, w, None, None, grids, vitomr.encoder.patch_size, True,
+                                             kept=kept)
     return seqs, lps, mask, conf, al
 
 
-def _encode_chunks(vitomr, imgs, device):
+def _encode_chunks(vitomr, imgs, device, prune=None):
     """Encoder (fp32, outside autocast) and transition head (inside autocast) over chunks of at most max_batch_size images; the packed
-    memories of all chunks, concatenated, and their lengths.  imgs: a list of image tensors, or a `utils.PackedPatches`."""
+    memories of all chunks, concatenated, and their lengths.  imgs: a list of image tensors, or a `utils.PackedPatches`.  prune: as in
+    inference() - a `PackedPatches` is pruned whole, once (three launches for all chunks), image lists chunk by chunk."""
     chunk = vitomr.decoder.decoder_blocks.max_batch_size if hasattr(vitomr.decoder.decoder_blocks, "max_batch_size") else len(imgs)
+    if prune is not None and prune is not False and isinstance(imgs, PackedPatches) and not imgs.pruned:
+        imgs, prune = vitomr.encoder.prune_packed(imgs, None if prune is True else prune), None
     mems, lens = [], []
     for c0 in range(0, len(imgs), chunk):
-        lat32, _, ln = _encode(vitomr, imgs.slice(c0, c0 + chunk) if isinstance(imgs, PackedPatches) else imgs[c0:c0 + chunk])
+        lat32, _, ln = _encode(vitomr, imgs.slice(c0, c0 + chunk) if isinstance(imgs, PackedPatches) else imgs[c0:c0 + chunk], prune)
         with autocast(device_type=device, dtype=torch.bfloat16):
             mems.append(vitomr.transition_head.forward_packed(lat32))
         lens += ln
     return (mems[0] if len(mems) == 1 else torch.cat(mems)), lens
 
 
-def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None):
+def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None, prune=None):
     """Continuous-batching greedy inference (an extension) as a generator: yields (index, seqs (1,T'), log_probs (1,T'), mask (1,T')) for
     each image as soon as it finishes, in completion order; each is what inference(vitomr, [imgs[index]]) returns.  max_inference_len: one
     cap or a list of per-image caps; slots: decode rows (default: the cache's max batch size).  prefix (prompted decoding, inference())
-    is not supported here: anything but None raises ValueError.  grammar: constrained decoding as in inference()."""
+    is not supported here: anything but None raises ValueError.  grammar: constrained decoding as in inference().  prune: blank-patch
+    pruning as in inference(); imgs may then also be a `utils.PackedPatches`, pruned or not."""
     vitomr._no_prefix(prefix, "continuous batching")
     vitomr.eval()
-    imgs = list(imgs)
+    imgs = imgs if isinstance(imgs, PackedPatches) else list(imgs)
     with torch.no_grad():
-        mem, lens = _encode_chunks(vitomr, imgs, device)
+        mem, lens = _encode_chunks(vitomr, imgs, device, prune)
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
             run = vitomr._continuous_packed_iter(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
@@ -213,23 +243,23 @@ def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=15
     return images()
 
 
-def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None):
+def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None, prune=None):
     """inference() over a list of any length through continuous batching (an extension): `slots` decode rows work through the images in
     input order and a finished row is refilled with the next image at once.  Returns exactly what inference(vitomr, imgs, ...) returns
     (seqs (N,T'), log_probs (N,T'), mask (N,T'), clipped to the longest row); max_inference_len may be a list of per-image caps.  prefix
     (prompted decoding, inference()) is not supported here: anything but None raises ValueError.  grammar: constrained decoding as in
-    inference()."""
+    inference().  prune: blank-patch pruning as in inference(); imgs may then also be a `utils.PackedPatches`, pruned or not."""
     vitomr._no_prefix(prefix, "continuous batching")
     vitomr.eval()
-    imgs = list(imgs)
+    imgs = imgs if isinstance(imgs, PackedPatches) else list(imgs)
     with torch.no_grad():
-        mem, lens = _encode_chunks(vitomr, imgs, device)
+        mem, lens = _encode_chunks(vitomr, imgs, device, prune)
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
             return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
 
 
-def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, grammar=None, orient=None, deskew=None, flatten=None, rectify=None):
+def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, prune=None, grammar=None, orient=None, deskew=None, flatten=None, rectify=None):
     """Whole pages in, their systems decoded as one batch (an extension; the reference's service crops hand-drawn boxes with PIL and decodes
     them one by one, acai_omr/ui/routes.py:93-129) -> a `page.PageResult`.
     pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1].  boxes: None - the systems are found on the device
@@ -274,8 +304,15 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     to the UPRIGHT page.  The result's `orientations` says which code every page was turned by, `source_sizes` is the size of the photos
     as passed in, and `to_page_xy` / `from_page_xy` / `box_corners` go back through the turn to the photo's own pixels.  Anything else for
     orient is a TypeError, a code outside 1 .. 8 a ValueError.  Not handled: float colour input, mirrored photos without a tag, reading
-    the tag out of a file (PIL or any decoder gives the number), JPEG decoding, folding the quarter turn into the rectification warp."""
+    the tag out of a file (PIL or any decoder gives the number), JPEG decoding, folding the quarter turn into the rectification warp.
+    prune (an extension, default None = off, as is False: the path above, unchanged, no launch added): True or a `prune.PruneConfig` - the
+    blank patches of all systems are dropped from the packed stream at once (prune.prune_patches: three launches and one copy of the kept
+    counts to the host for the whole call) before it is encoded; the rows are then what continuous_inference returns for the pruned stream.
+    The result's `patches_kept` / `patches_total` say per system how many patches the model read.  Chosen on synthetic pages; the blank
+    share of real systems and the effect on a trained checkpoint's output have not been measured."""
     from .. import page as pg
+    from ..prune import as_config
+    prune = as_config(prune)
     pages, boxes = pg._page_lists(pages, boxes)
     if boxes is not None and len(boxes) != len(pages):
         raise ValueError(f"{len(pages)} pages but boxes for {len(boxes)}")
@@ -330,11 +367,14 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     vitomr.eval()
     with torch.no_grad():
         packed = pg.split_pages(pages, per_page, resize)
+        total = packed.lens
+        if prune is not None:
+            packed = vitomr.encoder.prune_packed(packed, prune)
         mem, lens = _encode_chunks(vitomr, packed, device)
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
             seqs, lps, mask = vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
-    return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, **turned)
+    return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, patches_kept=packed.lens, patches_total=total, **turned)
 
 
 def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None, *, grammar=None):

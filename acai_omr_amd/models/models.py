@@ -82,11 +82,17 @@ class Encoder(nn.Module):
             raise ValueError(f"{h_p} x {w_p} image is too large for max positional embedding grid of shape {self.pe_max_height} x {self.pe_max_width}")
         return h_p, w_p
 
-    def _pe_packed(self, dims, select=None):
+    def _pe_packed(self, dims, select=None, index=None):
         """pos_embedding[:h_p,:w_p].reshape(-1,E) of every image, concatenated (M:50); `select[i]` optionally picks rows
-        (MAE keeps ids_keep only, M:123).  One row-gather launch; grids beyond the table are interpolated (OMREncoder)."""
+        (MAE keeps ids_keep only, M:123).  One row-gather launch; grids beyond the table are interpolated (OMREncoder).
+        index (a pruned stream's `pe_index`): the rows to gather, already on the device - no host index lists are built."""
         dev, E = self._device(), self.hidden_dim
         table = self.pos_embedding.detach().reshape(-1, E)
+        if index is not None:
+            extra = [self.interpolate_pe(h_p, w_p).detach().reshape(-1, E) for h_p, w_p in dims if h_p > self.pe_max_height or w_p > self.pe_max_width]
+            if extra:
+                table = torch.cat([table] + extra, 0).contiguous()
+            return ops.gather_rows(table, index.contiguous())
         idx, extra = [], []
         base = table.shape[0]
         for i, (h_p, w_p) in enumerate(dims):
@@ -111,14 +117,38 @@ class Encoder(nn.Module):
     def _prec(self):
         return _autocast_prec()
 
-    def embed_packed(self, x):
+    def _check_prune(self, prune, encoding=True):
+        """The `prune` argument as a PruneConfig or None; refused (ValueError) where pruning is out of scope: the MAE encoder, and encoding
+        in training mode."""
+        from ..prune import as_config
+        cfg = as_config(prune)
+        if cfg is not None:
+            if isinstance(self, MAEEncoder):
+                raise ValueError("prune: the MAE encoder masks its own patches; pruning it is out of scope")
+            if encoding and _training_path_needed(self):
+                raise ValueError("prune: training through a pruned patch stream is out of scope (call under torch.no_grad(), or freeze the encoder)")
+        return cfg
+
+    def prune_packed(self, packed, cfg=None):
+        """`prune.prune_patches` of a `utils.PackedPatches` for THIS encoder's positional table (an extension)."""
+        from ..prune import prune_patches
+        return prune_patches(packed, self._check_prune(True if cfg is None else cfg, encoding=False), (self.pe_max_height, self.pe_max_width))
+
+    def embed_packed(self, x, prune=None, return_pruned=False):
         """Packed batchify: returns x32 (M,E), xb (bf16 copy or None), lens, dims.  x: images, or a `utils.PackedPatches` (patch rows written by
-        the resize kernel: no Unfold / cast here)."""
+        the resize kernel: no Unfold / cast here).
+        prune (an extension, default None = off: the path above, unchanged, no launch added): True or a `prune.PruneConfig` - the patch rows
+        are formed as always and the paper patches dropped (prune.prune_patches) in whatever dtype the rows are in, before any cast; `lens`
+        are then the kept counts, `dims` stay the full grids, and the positional rows are gathered through the device index.  A
+        `PackedPatches` that is already pruned is taken as it is (and then prune must be None).  return_pruned appends the pruned
+        `PackedPatches` (its `kept`, `kept_lens`; None without pruning) to the result.  ValueError in training mode and for the MAE encoder."""
         dev = self._device()
         prec = self._prec()
         bf = prec == "bf16"
         P = self.patch_size
         from ..utils import PackedPatches
+        cfg = self._check_prune(prune)
+        pruned = None
         if isinstance(x, PackedPatches):
             if x.patch_size != P or x.patches.shape[1] != NUM_CHANNELS * P * P:
                 raise ValueError(f"patch rows of size {x.patch_size} for an encoder with patch size {P}")
@@ -126,7 +156,19 @@ class Encoder(nn.Module):
             for h_p, w_p in dims:
                 if not self._allow_pe_interpolation and (h_p > self.pe_max_height or w_p > self.pe_max_width):
                     raise ValueError(f"{h_p} x {w_p} image is too large for max positional embedding grid of shape {self.pe_max_height} x {self.pe_max_width}")
-            lens = [h * w for h, w in dims]
+            if x.pruned:
+                if cfg is not None:
+                    raise ValueError("prune: the patch stream is already pruned")
+                self._check_prune(True)
+                if x.pe_grid != (self.pe_max_height, self.pe_max_width):
+                    raise ValueError(f"the stream was pruned for a positional table of {x.pe_grid}, this encoder's is "
+                                     f"{(self.pe_max_height, self.pe_max_width)}: prune it with Encoder.prune_packed")
+                pruned = x
+            elif cfg is not None:
+                if x.patches.device != dev:
+                    x = PackedPatches(x.patches.to(device=dev), x.dims, x.patch_size)
+                pruned = x = self.prune_packed(x, cfg)
+            lens = x.lens
             patches = x.patches.to(device=dev)
             want = torch.bfloat16 if bf else torch.float32
             if patches.dtype != want:
@@ -140,25 +182,35 @@ class Encoder(nn.Module):
             r0 = 0
             for t in imgs:
                 r0 += ops.patchify(t, P, patches, r0)
-        pe = self._pe_packed(dims)
+            if cfg is not None:
+                pruned = self.prune_packed(PackedPatches(patches, dims, P), cfg)
+                lens, patches = pruned.lens, pruned.patches
+        pe = self._pe_packed(dims) if pruned is None else self._pe_packed(dims, index=pruned.pe_index)
+        more = (pruned,) if return_pruned else ()
         wc = _wc(self)
         if not isinstance(self.projection, nn.Linear):     # a swapped-in module (the reference's tests use nn.Identity, tests/test_mae.py:12)
             x32 = (self.projection(patches.float()) + pe).contiguous()
-            return x32, (ops.cast_bf16(x32) if bf else None), lens, dims
+            return (x32, (ops.cast_bf16(x32) if bf else None), lens, dims) + more
         x32 = ops.gemm_nt(patches, wc.w(self.projection.weight, prec), wc.b(self.projection.bias, prec), residual=pe,
                           out_dtype=torch.float32, round_bf16=bf)
-        return x32, (ops.cast_bf16(x32) if bf else None), lens, dims
+        return (x32, (ops.cast_bf16(x32) if bf else None), lens, dims) + more
 
-    def forward_packed(self, x):
-        """Encoder on the packed token stream: (x32 (M,E), xb, lens).  This is what the inference entry points use."""
+    def forward_packed(self, x, prune=None, return_pruned=False):
+        """Encoder on the packed token stream: (x32 (M,E), xb, lens).  This is what the inference entry points use.  prune / return_pruned
+        (an extension): as in embed_packed - the stacks then run on the short stream, nothing in them changes, and with return_pruned the
+        pruned `utils.PackedPatches` (or None) is appended to the result."""
+        pruning = self._check_prune(prune) is not None or bool(getattr(x, "pruned", False))
         if _training_path_needed(self):
+            if pruning:
+                self._check_prune(True)   # raises
             from ..train import autograd_path
-            return autograd_path.encoder_forward_packed(self, x)
-        x32, xb, lens, _ = self.embed_packed(x)
+            out = autograd_path.encoder_forward_packed(self, x)
+            return tuple(out) + (None,) if return_pruned else out
+        x32, xb, lens, _, pruned = self.embed_packed(x, prune, True)
         cu = EG.cu_from_lens(lens, x32.device)
         for st in self._stacks():
             x32, xb = EG.encoder_stack(st, x32, xb, cu, max(lens), self._num_heads(), self._prec(), _wc(self))
-        return x32, xb, lens
+        return (x32, xb, lens, pruned) if return_pruned else (x32, xb, lens)
 
     def _pad_fill(self):
         # eval + even head count: torch takes the nested-tensor fast path and padded rows leave the stack as zeros, i.e.
@@ -261,13 +313,17 @@ class MAE(nn.Module):
         from ..train import autograd_path
         return autograd_path.mae_prepare_for_decoder(self, latent, kept_seq_lens, unmasked_seq_lens, batch_ids_restore, patchified_dims)
 
-    def forward(self, batch, noises=None):
+    def forward(self, batch, noises=None, prune=None):
         """`noises`: optional list of per-image noise vectors (injected masking noise for parity runs; the reference draws
-        torch.rand on the model's device, M:110)."""
+        torch.rand on the model's device, M:110).  prune: refused (ValueError) - blank-patch pruning of the MAE is out of scope."""
+        if prune is not None and prune is not False:
+            raise ValueError("prune: the MAE masks its own patches; pruning it is out of scope")
         from ..train import autograd_path
         return autograd_path.mae_forward(self, batch, noises)
 
-    def forward_packed(self, batch, noises=None):
+    def forward_packed(self, batch, noises=None, prune=None):
+        if prune is not None and prune is not False:
+            raise ValueError("prune: the MAE masks its own patches; pruning it is out of scope")
         from ..train import autograd_path
         return autograd_path.mae_forward(self, batch, noises, packed=True)
 
@@ -764,8 +820,23 @@ class ViTOMR(nn.Module):
         P = float(patch_size)
         return TokenAlignment(patch, loc_full[..., 2:4] * P, loc_full[..., 4:6] * P, loc_full[..., 1].clone(), list(grids), maps if return_maps else None)
 
-    def _align_packed(self, mem32, memb, lens_s, seqs, seq_mask, layers, head_weights, as_decoded, grids=None, patch_size=None, return_maps=True):
-        """The alignment pass on packed memories: the maps list of cross_attention_maps, and with grids a TokenAlignment."""
+    @staticmethod
+    def _expand_maps(out, offs, rows, lens_t, sub_s, lens_s, kept, grids):
+        """The flat map buffer of a pass over the pruned memories of `rows` (sub_s columns each) taken to the columns of the full grids
+        (ops.attn_map_expand): (buffer, offsets list, offsets on the device, the rows' full lengths).  kept: the packed kept indices of ALL
+        images (lens_s of them each), as `utils.PackedPatches.kept` holds them."""
+        if len(rows) < len(lens_s):
+            starts = [sum(lens_s[:i]) for i in rows]
+            kept = torch.cat([kept[o:o + k] for o, k in zip(starts, sub_s)])
+        full = [grids[i][0] * grids[i][1] for i in rows]
+        out, offs, map_off = ops.attn_map_expand(out, lens_t, sub_s, full, kept.contiguous(), offs)
+        return out, offs, map_off, full
+
+    def _align_packed(self, mem32, memb, lens_s, seqs, seq_mask, layers, head_weights, as_decoded, grids=None, patch_size=None, return_maps=True,
+                      kept=None):
+        """The alignment pass on packed memories: the maps list of cross_attention_maps, and with grids a TokenAlignment.  kept (with grids:
+        the FULL grids): the memories are those of a pruned patch stream and lens_s its kept counts; the maps are expanded to the full grids
+        before anything reads them, so patches, centroids and maps are in full-grid coordinates."""
         dec = self.decoder
         dec._alignment_selection(layers, head_weights)   # argument errors before any work
         _, rows, lens_t, sub_s, mem32, memb, tokens, at = self._scored_rows(mem32, memb, lens_s, seqs, seq_mask)
@@ -773,6 +844,10 @@ class ViTOMR(nn.Module):
         if rows:
             out, offs, map_off, _ = dec._cross_attention_maps_flat(tokens, lens_t, mem32, memb, sub_s, layers, head_weights, 1 if as_decoded else 0,
                                                                    None, False)
+        if kept is not None:
+            if rows:
+                out, offs, map_off, sub_s = self._expand_maps(out, offs, rows, lens_t, sub_s, lens_s, kept, grids)
+            lens_s = [h * w for h, w in grids]
         return self._located(seqs.shape, lens_s, rows, lens_t, sub_s, at, out, offs, map_off, grids, patch_size, return_maps)
 
     def cross_attention_maps(self, img_latent, latent_attention_mask, seqs, seq_mask=None, layers=None, head_weights=None, as_decoded=True):
@@ -837,9 +912,10 @@ class ViTOMR(nn.Module):
         return weight
 
     def _confidence_packed(self, mem32, memb, lens_s, seqs, seq_mask, top_k, temperature, as_decoded, weight=None, layers=None,
-                           head_weights=None, grids=None, patch_size=None, return_alignment=False):
+                           head_weights=None, grids=None, patch_size=None, return_alignment=False, kept=None):
         """The confidence pass on packed memories -> TokenConfidence.  weight None: the logits-only pass; otherwise the combined pass (maps and
-        logits from one teacher-forced pass), the heat maps over `grids`, and with return_alignment the TokenAlignment of the same maps."""
+        logits from one teacher-forced pass), the heat maps over `grids`, and with return_alignment the TokenAlignment of the same maps.
+        kept: as in _align_packed - the maps of a pruned memory are expanded to the full `grids` before the sums and the locations."""
         dec = self.decoder
         top_k, tau = self._check_confidence_args(top_k, temperature)
         B, Tp = seqs.shape
@@ -858,6 +934,8 @@ class ViTOMR(nn.Module):
             else:
                 out, offs, map_off, logits = dec._cross_attention_maps_flat(tokens, lens_t, mem32, memb, sub_s, layers, head_weights,
                                                                             1 if as_decoded else 0, None, True)
+                if kept is not None:
+                    out, offs, map_off, sub_s = self._expand_maps(out, offs, rows, lens_t, sub_s, lens_s, kept, grids)
             chosen = torch.cat([seqs[i, 1:Ls[i]] for i in rows]).to(dev)
             lp, ent, rank, ids, top_lp = ops.token_confidence(logits, chosen, top_k, tau)
             conf.log_prob[at], conf.entropy[at], conf.rank[at] = lp, ent, rank.long()
@@ -870,6 +948,8 @@ class ViTOMR(nn.Module):
                 cu_t, cu_s = EG.cu_from_lens(lens_t, dev), EG.cu_from_lens(sub_s, dev)
                 heat = ops.attn_map_weighted_sum(out, map_off, cu_t, cu_s, w.contiguous(), max(lens_t), layout=(lens_t, sub_s, offs))
         if weight is not None:
+            if kept is not None:
+                lens_s = [h * w for h, w in grids]
             conf.uncertainty = [torch.zeros(h, w, dtype=torch.float32, device=dev) for h, w in grids]
             o = 0
             for i, s in zip(rows, sub_s):

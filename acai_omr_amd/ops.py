@@ -7,6 +7,7 @@ faulting kernel can take the whole node down) and raises RuntimeError on a non-z
 import contextlib
 import ctypes
 import functools
+import itertools
 
 import math
 from typing import NamedTuple
@@ -883,6 +884,144 @@ def attn_map_weighted_sum(maps, map_off, cu_q, cu_k, weights, max_q, layout=None
                                                      int(max_q), max(lens_k), total_k, _p(partial), out.data_ptr(), _st()),
                "acai_attn_map_weighted_sum")
     return out
+
+
+PRUNE_MAX_HALO, PRUNE_MAX_GRID, PRUNE_MAX_IMAGES = _lib.PRUNE_MAX_HALO, _lib.PRUNE_MAX_GRID, _lib.PRUNE_MAX_IMAGES
+
+
+def _patch_stream(patches, name):
+    """A packed patch stream [M, L]: fp32 or bf16 on the GPU, rows contiguous, any row pitch and any base (a view of a larger stream)."""
+    _chk(patches, name)
+    if patches.dim() != 2 or patches.shape[1] < 1 or patches.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{name}: expected a [M, L] float32 or bfloat16 tensor with L >= 1, got {tuple(patches.shape)} {patches.dtype}")
+    return patches
+
+
+def prune_table(dims, pe_grid, device):
+    """The device table of patch_keep / patch_compact for images of patch grids dims = [(h_p, w_p), ...] that lie back to back in a patch
+    stream, with the positional table of pe_grid = (pe_max_height, pe_max_width) rows by columns: int32 [B, 8] (include/acai_omr_hip.h).
+    An image whose grid exceeds the table gathers from its own (h_p, w_p) grid appended behind the table, in image order, as
+    Encoder._pe_packed appends the interpolated grids.  -> (table, rows of the stream, the largest grid).  ValueError beyond the limits."""
+    dims = [(int(h), int(w)) for h, w in dims]
+    pe_h, pe_w = (int(v) for v in pe_grid)
+    if len(dims) > PRUNE_MAX_IMAGES:
+        raise ValueError(f"{len(dims)} images in one pruning call (at most {PRUNE_MAX_IMAGES})")
+    rows, off, base = [], 0, pe_h * pe_w
+    for h, w in dims:
+        if h < 1 or w < 1 or h * w > PRUNE_MAX_GRID:
+            raise ValueError(f"a grid of {h} x {w} patches: both sides must be at least 1 and the grid at most {PRUNE_MAX_GRID} patches")
+        if h > pe_h or w > pe_w:
+            rows.append((h, w, off, base, w, 0, 0, 0))
+            base += h * w
+        else:
+            rows.append((h, w, off, 0, pe_w, 0, 0, 0))
+        off += h * w
+    if off >= 2 ** 31 or base >= 2 ** 31:
+        raise ValueError(f"{off} patch rows do not fit 32-bit row indices")
+    table = h2d(torch.tensor(rows, dtype=torch.int32).reshape(len(dims), _lib.PRUNE_TABLE_COLS), device)
+    return table, off, max((h * w for h, w in dims), default=0)
+
+
+@_on_operand_device
+def patch_ink(patches, ink_level=0.5, out=None):
+    """ink [M] int32: per row of the packed patch stream, the number of elements strictly below ink_level, compared on the stored value
+    widened to fp32 (acai_patch_ink; one launch, none for M = 0)."""
+    _patch_stream(patches, "patches")
+    level = float(ink_level)
+    if level != level:
+        raise ValueError("ink_level is NaN")
+    M, L = patches.shape
+    if out is None:
+        out = torch.empty(M, dtype=torch.int32, device=patches.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == M and out.device == patches.device
+    _lib.check(_lib.lib().acai_patch_ink(patches.data_ptr(), _dt(patches), M, L, _ld(patches), level, out.data_ptr(), _st()), "acai_patch_ink")
+    return out
+
+
+@_on_operand_device
+def patch_keep(ink, table, max_grid, max_ink=0, halo=1):
+    """The keep rule on the ink counts of a stream of images (acai_patch_keep; one launch, one workgroup per image): a patch is inked when
+    its count exceeds max_ink, and kept when an inked patch of its own image lies within Chebyshev distance halo; an image without an
+    inked patch keeps all.  table: prune_table's.  -> (kept_local [M] int32 - image i's kept local indices r * w_p + c, ascending, from its
+    first row on; the rest of its slot is not written -, count [B] int32), both on the device."""
+    _chk(ink, "ink", torch.int32), _chk(table, "table", torch.int32)
+    if isinstance(halo, bool) or not isinstance(halo, int) or not 0 <= halo <= PRUNE_MAX_HALO:
+        raise ValueError(f"halo must be an int in 0 .. {PRUNE_MAX_HALO}, got {halo!r}")
+    if isinstance(max_ink, bool) or not isinstance(max_ink, int) or max_ink < 0:
+        raise ValueError(f"max_ink must be a non-negative int, got {max_ink!r}")
+    if table.dim() != 2 or table.shape[1] != _lib.PRUNE_TABLE_COLS or not table.is_contiguous() or ink.dim() != 1 or not ink.is_contiguous():
+        raise ValueError(f"patch_keep: ink must be a contiguous [M] tensor and table a contiguous [B, {_lib.PRUNE_TABLE_COLS}] one")
+    B = table.shape[0]
+    if B > PRUNE_MAX_IMAGES or not 0 <= int(max_grid) <= PRUNE_MAX_GRID:
+        raise ValueError(f"patch_keep: {B} images (at most {PRUNE_MAX_IMAGES}), largest grid {max_grid} (at most {PRUNE_MAX_GRID})")
+    kept_local = torch.empty(ink.numel(), dtype=torch.int32, device=ink.device)
+    count = torch.empty(B, dtype=torch.int32, device=ink.device)
+    _lib.check(_lib.lib().acai_patch_keep(ink.data_ptr(), table.data_ptr(), B, int(max_grid), max_ink, halo, kept_local.data_ptr(), count.data_ptr(),
+                                          _st()), "acai_patch_keep")
+    return kept_local, count
+
+
+@_on_operand_device
+def patch_compact(patches, table, kept_local, counts):
+    """The kept rows as a stream of their own (acai_patch_compact; one launch, none when nothing is kept).  counts: patch_keep's count as a
+    HOST list - reading it is the one device-to-host copy of the stage.  -> (out [sum counts, L] in the input's dtype, the kept rows bit
+    for bit; kept [sum counts] int32, the packed local indices; pe_idx [sum counts] int32, the rows of the positional table)."""
+    _patch_stream(patches, "patches"), _chk(table, "table", torch.int32), _chk(kept_local, "kept_local", torch.int32)
+    counts = [int(c) for c in counts]
+    B, (M, L) = table.shape[0], patches.shape
+    if len(counts) != B or kept_local.numel() != M or not kept_local.is_contiguous() or not table.is_contiguous() or min(counts, default=0) < 0:
+        raise ValueError(f"patch_compact: {len(counts)} counts for {B} images, {kept_local.numel()} kept slots for {M} rows")
+    total = sum(counts)
+    if total > M:
+        raise ValueError(f"patch_compact: {total} kept rows of a stream of {M}")
+    dev = patches.device
+    out = torch.empty(total, L, dtype=patches.dtype, device=dev)
+    kept, pe_idx = torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, dtype=torch.int32, device=dev)
+    if total == 0:
+        return out, kept, pe_idx
+    cu = [0]
+    for c in counts:
+        cu.append(cu[-1] + c)
+    cu_out = h2d(torch.tensor(cu, dtype=torch.int32), dev)
+    _lib.check(_lib.lib().acai_patch_compact(patches.data_ptr(), _dt(patches), L, _ld(patches), table.data_ptr(), kept_local.data_ptr(),
+                                             cu_out.data_ptr(), B, total, out.data_ptr(), kept.data_ptr(), pe_idx.data_ptr(), _st()),
+               "acai_patch_compact")
+    return out, kept, pe_idx
+
+
+@_on_operand_device
+def attn_map_expand(maps, lens_q, kept_lens, full_lens, kept, offs=None):
+    """Per-token maps over kept patches -> over the full grids (acai_attn_map_expand; one launch plus the zero fill).  maps: the flat fp32
+    buffer of attn_probs_mean with image b's [T_b][K_b] block at offs[b] (default: attn_map_layout(lens_q, kept_lens)); kept: the packed
+    int32 local indices of the kept patches, K_b per image, each below S_b = full_lens[b].  -> (out, offsets list, offsets as an int64 device
+    tensor) with image b's [T_b][S_b] block at the offsets of attn_map_layout(lens_q, full_lens): out_b[t, kept_b[j]] = maps_b[t, j], every
+    other element 0."""
+    _chk(maps, "maps", torch.float32), _chk(kept, "kept", torch.int32)
+    lens_q, kept_lens, full_lens = ([int(v) for v in x] for x in (lens_q, kept_lens, full_lens))
+    B = len(lens_q)
+    if not (len(kept_lens) == len(full_lens) == B) or B > PRUNE_MAX_IMAGES or maps.dim() != 1 or kept.dim() != 1:
+        raise ValueError(f"attn_map_expand: {B} token lengths, {len(kept_lens)} kept and {len(full_lens)} full lengths; flat maps and kept")
+    if not (maps.is_contiguous() and kept.is_contiguous()) or kept.numel() != sum(kept_lens):
+        raise ValueError(f"attn_map_expand: kept holds {kept.numel()} indices for kept lengths summing to {sum(kept_lens)}")
+    if any(t < 0 or k < 0 or k > s for t, k, s in zip(lens_q, kept_lens, full_lens)) or max(lens_q, default=0) > 65535:
+        raise ValueError(f"attn_map_expand: bad lengths lens_q={lens_q} kept_lens={kept_lens} full_lens={full_lens}")
+    in_offs = attn_map_layout(lens_q, kept_lens)[0] if offs is None else [int(o) for o in offs]
+    for o, t, k in zip(in_offs, lens_q, kept_lens):
+        if o < 0 or o + t * k > maps.numel():
+            raise ValueError(f"attn_map_expand: a [{t}][{k}] block at offset {o} lies outside the {maps.numel()} map elements")
+    out_offs, total = attn_map_layout(lens_q, full_lens)
+    dev = maps.device
+    out = torch.zeros(total, dtype=torch.float32, device=dev)
+    out_off = h2d(torch.tensor(out_offs, dtype=torch.int64), dev)
+    if B and max(lens_q) and max(kept_lens):
+        # (the three cumulative length tables, [B + 1] each, go up as one tensor)
+        cus = [[0] + list(itertools.accumulate(lens)) for lens in (lens_q, kept_lens, full_lens)]
+        cu = h2d(torch.tensor(cus, dtype=torch.int32), dev)
+        in_off = h2d(torch.tensor(in_offs, dtype=torch.int64), dev)
+        _lib.check(_lib.lib().acai_attn_map_expand(maps.data_ptr(), in_off.data_ptr(), out.data_ptr(), out_off.data_ptr(), cu[0].data_ptr(),
+                                                   cu[1].data_ptr(), cu[2].data_ptr(), kept.data_ptr(), B, max(lens_q), max(kept_lens), _st()),
+                   "acai_attn_map_expand")
+    return out, out_offs, out_off
 
 
 def cross_kv_prefill(mem, w_kv, b_kv, row_seq, row_pos, seq_off, seq_len, k_out, v_out, H, dh, dhp, round_bf16=False):

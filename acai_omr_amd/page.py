@@ -711,11 +711,18 @@ class PageResult:
       inset        the `RectifyConfig.inset` the quads were rectified with (the homography is `ops.homography_q30(quad, page_size, inset)`);
       seqs, log_probs, seq_mask   (N, T') as `continuous_inference` returns them, one row per system (None when there is no system at all);
       system_page  the page index of every row;
-      sizes, windows   per row, the size (OH, OW) its box was resized to and the window (top, left, ch, cw) of it the model saw."""
+      sizes, windows   per row, the size (OH, OW) its box was resized to and the window (top, left, ch, cw) of it the model saw;
+      patches_kept, patches_total   per row, the patches the encoder read and the patches of the window's grid: equal unless the call pruned
+                   blank patches (page_inference(prune=), `prune.prune_patches`)."""
 
     def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=(), angles=None, page_sizes=None, flattened=None,
-                 quads=None, source_sizes=None, inset=2, orientations=None):
+                 quads=None, source_sizes=None, inset=2, orientations=None, patches_kept=None, patches_total=None):
         self.boxes, self.seqs, self.log_probs, self.seq_mask = boxes, seqs, log_probs, seq_mask
+        system_page = list(system_page)
+        self.patches_total = [None] * len(system_page) if patches_total is None else [int(n) for n in patches_total]   # (None: not recorded)
+        self.patches_kept = list(self.patches_total) if patches_kept is None else [int(n) for n in patches_kept]
+        if len(self.patches_total) != len(system_page) or len(self.patches_kept) != len(system_page):
+            raise ValueError("PageResult: one patches_kept and one patches_total per system")
         self.quads = [None] * len(boxes) if quads is None else [None if q is None else [(float(x), float(y)) for x, y in q] for q in quads]
         self.source_sizes = None if source_sizes is None else [tuple(int(v) for v in hw) for hw in source_sizes]
         self.inset = inset

@@ -239,17 +239,45 @@ class PackedPatches:
     """A batch of images as the encoder's projection GEMM wants it: the nn.Unfold(P, P) rows of every image in ONE packed [sum N, P*P] tensor
     (fp32, or bf16 for an autocast encoder) plus the patch grid (h_p, w_p) of each image.  `DynamicResize.to_patches` / `resize_batch_to_patches`
     produce it straight from the resize kernel; `Encoder` / `OMREncoder` / `FineTuneOMREncoder` (`forward`, `forward_packed`) and the
-    `inference()` entry point accept it wherever they accept a list of image tensors."""
+    `inference()` entry point accept it wherever they accept a list of image tensors.
+    A PRUNED stream (`prune.prune_patches`, an extension) holds only the rows of the patches that were kept: `dims` stay the FULL grids,
+    `kept_lens` is the host list of rows per image, `kept` the packed int32 device tensor of their local indices r * w_p + c (ascending within
+    an image), and `pe_index` the int32 device tensor of the rows they gather from a positional table of `pe_grid` = (rows, columns) with the
+    grids of images beyond it appended in image order (Encoder._pe_packed).  All four are None on a stream that was not pruned."""
 
-    def __init__(self, patches, dims, patch_size):
+    def __init__(self, patches, dims, patch_size, kept=None, kept_lens=None, pe_index=None, pe_grid=None):
         self.patches, self.dims, self.patch_size = patches, [tuple(d) for d in dims], patch_size
+        self.kept, self.kept_lens, self.pe_index = kept, None if kept_lens is None else [int(n) for n in kept_lens], pe_index
+        self.pe_grid = None if pe_grid is None else (int(pe_grid[0]), int(pe_grid[1]))
+        if self.pruned and (kept_lens is None or pe_index is None or pe_grid is None or len(self.kept_lens) != len(self.dims)):
+            raise ValueError("a pruned PackedPatches needs kept, kept_lens (one per image), pe_index and pe_grid")
 
     def __len__(self):
         return len(self.dims)
 
+    @property
+    def pruned(self):
+        return self.kept is not None
+
+    @property
+    def lens(self):
+        """Rows per image: the kept counts of a pruned stream, h_p * w_p otherwise."""
+        return list(self.kept_lens) if self.pruned else [h * w for h, w in self.dims]
+
+    def _beyond(self, dims):
+        """The rows that the images of `dims` whose grid exceeds pe_grid append to the positional table."""
+        return sum(h * w for h, w in dims if h > self.pe_grid[0] or w > self.pe_grid[1])
+
     def slice(self, i0, i1):
         """Images i0 .. i1 - 1 as a `PackedPatches` over a view of the same rows (what a chunked encode takes one chunk at a time)."""
         i0, i1 = max(0, min(int(i0), len(self.dims))), max(0, min(int(i1), len(self.dims)))
+        if self.pruned:
+            r0, n = sum(self.kept_lens[:i0]), sum(self.kept_lens[i0:i1])
+            pe, skipped = self.pe_index[r0:r0 + n], self._beyond(self.dims[:i0])
+            if skipped:   # the appended grids of the images in front of the slice are no longer there
+                table_rows = self.pe_grid[0] * self.pe_grid[1]
+                pe = torch.where(pe >= table_rows, pe - skipped, pe)
+            return PackedPatches(self.patches[r0:r0 + n], self.dims[i0:i1], self.patch_size, self.kept[r0:r0 + n], self.kept_lens[i0:i1], pe, self.pe_grid)
         r0 = sum(h * w for h, w in self.dims[:i0])
         return PackedPatches(self.patches[r0:r0 + sum(h * w for h, w in self.dims[i0:i1])], self.dims[i0:i1], self.patch_size)
 

@@ -1003,6 +1003,45 @@ int acai_page_col_profile(const void *page, int in_u8, int H, int W, int pitch, 
  * n <= 65535.  The reference has no counterpart: it is how the orientation estimate asks which end of a system holds the clef. */
 int acai_page_box_ink(const void *page, int in_u8, int H, int W, int pitch, float ink_threshold, const int32_t *boxes, int n, int32_t *out, void *stream);
 
+/* ---- blank-patch pruning ahead of the encoder (csrc/prune.hip) -------------------------------------------------------------------------------
+ * An extension; the reference encodes every patch.  The packed patch stream [M][L] (L = P * P elements per row, fp32 or bf16, rows `pitch`
+ * elements apart; the base need not be the start of an allocation) loses the rows that are paper.  THREE launches for a whole batch and one
+ * copy of the per-image kept counts to the host, which sizes the output between the second and the third.  Integers only, no atomics: the
+ * same result on every run, kept patches in ascending order.
+ * The device table is int32 [B][ACAI_PRUNE_TABLE_COLS], per image: h_p, w_p, its first row in the full stream, the first row of its
+ * positional grid in the positional table, that grid's width (the table's own width, or w_p for an interpolated grid appended to it), and
+ * three words that are not read.  The caller guarantees h_p, w_p >= 1 and that the images' row ranges lie inside the M rows. */
+#define ACAI_PRUNE_TABLE_COLS 8
+#define ACAI_PRUNE_MAX_HALO 3
+#define ACAI_PRUNE_MAX_GRID (1 << 20)   /* patches of one image */
+#define ACAI_PRUNE_MAX_IMAGES 65535
+
+/* ink[r] = the number of elements of row r that are strictly below ink_level, compared on the stored value widened to fp32 (a NaN element is
+ * not ink).  One wave per row; 16-byte loads where base and pitch are multiples of 16 bytes, element by element where not and for the
+ * L % (16 / element size) trailing elements.  Any L >= 1. */
+int acai_patch_ink(const void *patches, int dtype, int M, int L, int64_t pitch, float ink_level, int32_t *ink, void *stream);
+
+/* One workgroup per image.  inked[r][c] = ink > max_ink; keep[r][c] = some inked patch (r', c') of the SAME image with max(|r - r'|,
+ * |c - c'|) <= halo; an image without an inked patch keeps all of its patches.  The kept local indices r * w_p + c are written in ascending
+ * order from the image's first row on into kept_local [M] (the rest of its slot is left as it was) and their number into count[i].  The
+ * block-wide exclusive scan of keep is formed from the waves' 64-bit ballots and popcounts, with the wave totals passed through LDS and a
+ * running base across chunks of 256 patches.  max_grid: the largest h_p * w_p of the table, at most ACAI_PRUNE_MAX_GRID;
+ * halo in 0 .. ACAI_PRUNE_MAX_HALO; B <= ACAI_PRUNE_MAX_IMAGES. */
+int acai_patch_keep(const int32_t *ink, const int32_t *table, int B, int max_grid, int max_ink, int halo, int32_t *kept_local, int32_t *count,
+                    void *stream);
+
+/* cu_out int32 [B + 1]: the exclusive prefix sums of count, in device memory; total = cu_out[B].  Row j of `out` [total][L] (the input's
+ * dtype, contiguous, not the input) is the kept patch row it stands for, bit for bit; kept[j] is its local index in its image's grid and
+ * pe_idx[j] = pe_base + (kept / w_p) * pe_w + kept % w_p the row of the positional table that belongs to it.  One wave per row. */
+int acai_patch_compact(const void *patches, int dtype, int L, int64_t pitch, const int32_t *table, const int32_t *kept_local, const int32_t *cu_out,
+                       int B, int total, void *out, int32_t *kept, int32_t *pe_idx, void *stream);
+
+/* Per-token maps over kept patches -> over the full grid.  Image b holds T_b = cu_q[b + 1] - cu_q[b] rows of K_b = cu_kept[b + 1] - cu_kept[b]
+ * columns at in + in_off[b] and gets T_b rows of S_b = cu_full[b + 1] - cu_full[b] columns at out + out_off[b]:
+ * out_b[t][kept[cu_kept[b] + j]] = in_b[t][j].  `out` is zeroed by the caller; a kept index outside [0, S_b) is skipped.  max_q <= 65535. */
+int acai_attn_map_expand(const float *in, const int64_t *in_off, float *out, const int64_t *out_off, const int32_t *cu_q, const int32_t *cu_kept,
+                         const int32_t *cu_full, const int32_t *kept, int B, int max_q, int max_kept, void *stream);
+
 /* hipGraph helpers (capture on `stream`, replay). */
 int acai_graph_begin(void *stream);
 int acai_graph_end(void *stream, void **graph_exec_out);
