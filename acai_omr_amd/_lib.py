@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip", "prune.hip"]
+SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip", "prune.hip", "assess.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -169,6 +169,8 @@ STRIP_WIDTHS = (8, 16, 32, 64)
 FLATTEN_TILES = (16, 32, 64, 128)   # csrc/flatten.hip: the tile sizes of acai_page_tile_levels / acai_page_flatten
 EXTENTS_MAX_RUN = 256               # csrc/rectify.hip (ACAI_EXTENTS_MAX_RUN): the longest run acai_page_extents can be asked for
 COL_CHUNK_ROWS, COL_MAX_CHUNKS = 64, 64   # csrc/ingest.hip (ACAI_COL_*): acai_page_col_profile walks chunks of max(64, ceil(H / 64)) rows
+# csrc/assess.hip (ACAI_RUNS_CHUNK_ROWS, ACAI_SHARP_CHUNK_ROWS): the rows a wave of acai_page_runs / acai_page_sharpness walks; the words of their outputs
+RUNS_CHUNK_ROWS, SHARP_CHUNK_ROWS, RUNS_WORDS, SHARP_WORDS = 32, 32, 3 * 256, 3 + 256
 
 
 # csrc/prune.hip (ACAI_PRUNE_*): the columns of the device table, the largest halo, grid (patches of one image) and number of images
@@ -222,6 +224,8 @@ _SIGNATURES = {
     "acai_page_ingest": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p]),
     "acai_page_col_profile": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "acai_page_box_ink": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
+    "acai_page_runs": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    "acai_page_sharpness": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "acai_patch_ink": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_float, c_void_p, c_void_p]),
     "acai_patch_keep": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "acai_patch_compact": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

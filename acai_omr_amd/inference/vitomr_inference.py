@@ -259,7 +259,7 @@ def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, s
             return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
 
 
-def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, prune=None, grammar=None, orient=None, deskew=None, flatten=None, rectify=None):
+def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, assess=None, prune=None, grammar=None, orient=None, deskew=None, flatten=None, rectify=None):
     """Whole pages in, their systems decoded as one batch (an extension; the reference's service crops hand-drawn boxes with PIL and decodes
     them one by one, acai_omr/ui/routes.py:93-129) -> a `page.PageResult`.
     pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1].  boxes: None - the systems are found on the device
@@ -309,10 +309,28 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     blank patches of all systems are dropped from the packed stream at once (prune.prune_patches: three launches and one copy of the kept
     counts to the host for the whole call) before it is encoded; the rows are then what continuous_inference returns for the pruned stream.
     The result's `patches_kept` / `patches_total` say per system how many patches the model read.  Chosen on synthetic pages; the blank
-    share of real systems and the effect on a trained checkpoint's output have not been measured."""
+    share of real systems and the effect on a trained checkpoint's output have not been measured.
+    assess (an extension, default None = off, as is False: the path above, unchanged, no launch added, no copy made): True or a
+    `page.AssessConfig` - every page is assessed (page.assess_pages: three launches per page and ONE copy to the host for all pages) on
+    the page detection sees, that is after ingest, rectify, flatten and deskew where those are on; flatten comes first so that one ink
+    threshold holds for the whole page.  The result's `quality` holds per page its `page.PageQuality`: the staff scale (line thickness and
+    the distance from staff line to staff line, from vertical run lengths), sharpness, contrast, focus.  Where the scale was found and
+    boxes is None, detection is sized from it - `detect.resolved(H, W, staff_space=scale.pitch_bin)`: the fields of `detect` left at None
+    come from 180 staff spaces in place of the page height, the fields the caller set win as before - so a dense page of small staves,
+    a half-empty page or a sheet that fills half the frame keeps its systems; a page in engraved A4 proportion resolves to what it
+    resolved to anyway.  `system_staff_space` gives per system the staff space in MODEL pixels.  A page that fails a bound the caller set
+    in the `AssessConfig` (all default to None) has `quality[i].ok` False and the reasons in words, and is decoded all the same: this call
+    reports and never drops rows - refusing the photo is the caller's to do, with the reasons in hand.  Rectify and deskew resample
+    bilinearly, which lowers `sharpness` a little, and flatten stretches the levels: values compare only under the same stage settings,
+    and `page.assess_pages` on the raw page judges the photo itself.  Not handled: sizing flatten, deskew or rectify from the scale
+    (they run before it can be measured), horizontal runs, a scale per system, any default threshold; nothing has been measured on real
+    photographs."""
     from .. import page as pg
     from ..prune import as_config
     prune = as_config(prune)
+    if assess is not None and assess is not False and assess is not True and not isinstance(assess, pg.AssessConfig):
+        raise TypeError("assess: expected None, a bool or a page.AssessConfig")
+    assess = None if assess is None or assess is False else (pg.AssessConfig() if assess is True else assess)
     pages, boxes = pg._page_lists(pages, boxes)
     if boxes is not None and len(boxes) != len(pages):
         raise ValueError(f"{len(pages)} pages but boxes for {len(boxes)}")
@@ -353,8 +371,13 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
         estimate = deskew is True or isinstance(deskew, pg.SkewConfig)
         pages, angles = pg.deskew_pages(pages, None if estimate else deskew, deskew if isinstance(deskew, pg.SkewConfig) else None)
     turned = dict(angles=angles, page_sizes=[tuple(p.shape) for p in pages], flattened=flattened, **{**rectified, **oriented})
+    scales = None
+    if assess is not None and pages:
+        measured = pg.assess_counts(pages, assess)          # the launches and the one copy; the gate waits for the systems' sizes
+        scales = [pg.choose_staff_scale(hists, assess) for hists, _, _ in measured]
     if boxes is None:
-        per_page = [pg.detect_systems(p, detect) for p in pages]
+        per_page = [pg.detect_systems(p, detect) if scales is None or scales[i] is None else pg.detect_systems(p, detect, scales[i].pitch_bin)
+                    for i, p in enumerate(pages)]
     else:
         per_page = [pg.boxes_from_fractions(b, *p.shape) if b and pg._is_fraction_box(b[0]) else [pg._pixel_box(x, *p.shape) for x in b]
                     for p, b in zip(pages, boxes)]
@@ -362,6 +385,10 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     system_page, sizes, windows = [p for p, *_ in plans], [s for _, _, s, _ in plans], [c for *_, c in plans]
     dec = vitomr.decoder
     specials = [getattr(dec, n) for n in ("bos_idx", "eos_idx", "pad_idx") if hasattr(dec, n)]
+    if scales is not None:
+        spaces = pg.system_staff_spaces(scales, plans)
+        smallest = [min((v for v, (p, *_) in zip(spaces, plans) if p == i and v is not None), default=None) for i in range(len(pages))]
+        turned.update(quality=[pg.page_quality(*m, assess, small) for m, small in zip(measured, smallest)], system_staff_space=spaces)
     if not plans:
         return pg.PageResult(per_page, None, None, None, [], [], [], specials, **turned)
     vitomr.eval()

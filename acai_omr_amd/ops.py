@@ -651,6 +651,46 @@ def page_box_ink(page, boxes, ink_threshold=0.5):
     return out
 
 
+# ---- page assessment (csrc/assess.hip) --------------------------------------------------------------------------------------------------
+def _assess_out(out, words, page, name):
+    """The int64 words a page assessment kernel adds into: fresh zeros, or the caller's (a contiguous view on the page's device that it has
+    zeroed - one fill then serves every page of a call)."""
+    if out is None:
+        return torch.zeros(words, dtype=torch.int64, device=page.device)
+    if not torch.is_tensor(out):
+        raise TypeError(f"{name}: out: expected a tensor")
+    _chk(out, "out", torch.int64)
+    if out.numel() != words or not out.is_contiguous() or out.device != page.device:
+        raise ValueError(f"{name}: out: expected {words} contiguous int64 on the page's device")
+    return out
+
+
+@_on_operand_device
+def page_runs(page, ink_threshold=0.5, out=None):
+    """Vertical run-length histograms of a page (as `page_profile` takes it) -> int64 [3, 256]: in every column, the closed runs of ink
+    (row 0) and of paper (row 1) by their length, and every closed ink run together with the closed paper run directly under it by the
+    sum of the two (row 2), lengths clamped to 255; a run that touches the first or the last row of the page is open and not counted.
+    Two launches.  out: 768 zeroed int64 that the counts are ADDED to (default: fresh zeros)."""
+    page, H, W, pitch, u8 = _page(page)
+    hist = _assess_out(out, _lib.RUNS_WORDS, page, "page_runs")
+    work = torch.empty(-(-H // _lib.RUNS_CHUNK_ROWS) * W, dtype=torch.int32, device=page.device)
+    _lib.check(_lib.lib().acai_page_runs(page.data_ptr(), u8, H, W, pitch, float(ink_threshold), hist.data_ptr(), work.data_ptr(), work.numel(), _st(page)),
+               "acai_page_runs")
+    return hist.view(3, 256)
+
+
+@_on_operand_device
+def page_sharpness(page, out=None):
+    """One read of a page (as `page_profile` takes it) -> (stats int64 [3], levels int64 [256]), two views of one buffer: the sum and the
+    sum of squares of the Laplacian L = 4 p - up - down - left - right of the levels over the interior pixels with their number, and the
+    histogram of the levels of all pixels (a uint8 value as it is, a float one as floor(v * 255 + 0.5), clamped).  One launch.  out: 259
+    zeroed int64 that everything is ADDED to (default: fresh zeros)."""
+    page, H, W, pitch, u8 = _page(page)
+    buf = _assess_out(out, _lib.SHARP_WORDS, page, "page_sharpness")
+    _lib.check(_lib.lib().acai_page_sharpness(page.data_ptr(), u8, H, W, pitch, buf.data_ptr(), _st(page)), "acai_page_sharpness")
+    return buf[:3], buf[3:]
+
+
 def augment_table(entries, device):
     """A list of `_lib.AcaiAugImage` -> the read-only descriptor table in device memory (a uint8 tensor): the one upload of a call."""
     import ctypes

@@ -20,6 +20,10 @@ average confidence (acai_omr/ui/routes.py: `setup_inference` :108-129, `multiple
                             launch (ops.page_ingest; the reference does both on the host with PIL, ui/routes.py:98-118), and, for a photo
                             whose tag was stripped, the quarter turn estimated on the device from the staff lines (ops.page_col_profile,
                             ops.page_box_ink);
+  * `estimate_staff_scale`, `assess_pages`   opt-in, on the page detection sees: the thickness of a staff line and the distance from line
+                            to line from the histograms of vertical run lengths, sharpness and contrast from the levels and their
+                            Laplacian (ops.page_runs, ops.page_sharpness; the reference measures nothing) - detection is then sized
+                            from the music instead of the canvas, and a caller can refuse a photo that cannot be read;
   * `split_pages`           every box of every page cut out, resized as `DynamicResize` resizes the crop and written into ONE
                             `PackedPatches` by one launch pair (ops.crop_resize_to_patches) - no crop copies, no per-system launches;
   * `PageResult`            the per-system rows of the decode, joined per page as the service joins them.
@@ -74,6 +78,19 @@ chosen on synthetic pages, like the defaults of the other configs: nothing has b
 EXIF code remains the primary path.  Not handled: float colour input; mirrored photos without a tag (the estimate never answers 2, 4, 5
 or 7); reading the EXIF tag out of a file (the caller passes the number: PIL or any decoder gives it); JPEG decoding itself; folding the
 quarter turn into the rectification warp (two passes over the page where one could do).
+
+Every default of `DetectConfig` is a share of the canvas: right for a full engraved A4 page, wrong for a dense page of small staves (parts,
+hymnals, pocket scores), for a last page that ends half way down and for a sheet that fills half the frame.  And nothing above says
+whether a photo can be read at all: a blurred, washed-out or too-small one decodes to confident-looking tokens.  Both lack one
+measurement, the size of the music in pixels.  `assess_pages` (`page_inference(..., assess=True)`) makes it the way classical OMR front
+ends do: in every column the vertical runs of ink and of paper are histogrammed by length on the device (ops.page_runs); the most frequent
+closed ink run is the staff-line thickness, the most frequent sum of an ink run and the paper run under it the distance from line to line
+(`choose_staff_scale`, integers on the host).  `DetectConfig.resolved(H, W, staff_space)` then sizes merge_gap, min_height and margin from
+180 staff spaces in place of H.  One more read of the page gives the level histogram and the variance of the Laplacian
+(ops.page_sharpness): contrast, sharpness and their quotient, focus.  `AssessConfig` carries a gate over these numbers whose bounds all
+default to None: no threshold is invented here, because nothing in this repository can calibrate one.  Not handled: sizing flatten,
+deskew or rectify from the scale (they run before it can be measured), horizontal runs, a scale per system, any default threshold.
+Nothing has been measured on real photographs (no such data here).
 """
 import math
 from dataclasses import dataclass
@@ -111,9 +128,18 @@ class DetectConfig:
     margin: Optional[int] = None
     max_systems: int = 64
 
-    def resolved(self, H, W):
-        """(min_ink, merge_gap, min_height, line_len, margin) for an H x W page."""
+    def resolved(self, H, W, staff_space=None):
+        """(min_ink, merge_gap, min_height, line_len, margin) for an H x W page.  staff_space (None: as above, from H): the distance from
+        staff line to staff line in pixels as it was measured on the page (`estimate_staff_scale`: `StaffScale.pitch_bin`); merge_gap,
+        min_height and margin, where left at None, are then sized from Hs = floor(180 * staff_space) in place of H - the height of the
+        engraved page on which this music would have that distance, the class's own proportion - so a dense page of small staves, a
+        last page that ends half way down and a sheet that fills half the frame are judged by their music and not by the canvas.
+        min_ink and line_len are shares of the width and stay so."""
         pick = lambda v, d: int(d if v is None else v)   # noqa: E731
+        if staff_space is not None:
+            if isinstance(staff_space, bool) or not isinstance(staff_space, (int, float)) or not 0 < staff_space <= PAGE_MAX_H:
+                raise ValueError(f"DetectConfig: staff_space = {staff_space!r} is not None or a positive number of pixels")
+            H = int(math.floor(180 * staff_space))
         return (pick(self.min_ink, max(1, W // 500)), pick(self.merge_gap, max(1, H // 200)), pick(self.min_height, max(1, H // 90)),
                 int(math.ceil(self.line_frac * W)), pick(self.margin, max(1, H // 100)))
 
@@ -133,14 +159,15 @@ def _device_page(page, device=None):
     return page if page.stride(-1) == 1 and (page.shape[0] == 1 or page.stride(0) >= page.shape[1]) else page.contiguous()
 
 
-def detect_systems(page, cfg=None):
+def detect_systems(page, cfg=None, staff_space=None):
     """The staff systems of one page -> [(x0, y0, x1, y1), ...] in pixels, top to bottom; an empty page gives [].  Three launches and ONE
-    device-to-host copy (the count and the boxes together).  More than cfg.max_systems systems: ValueError."""
+    device-to-host copy (the count and the boxes together).  More than cfg.max_systems systems: ValueError.  staff_space: passed on to
+    `DetectConfig.resolved` (None: the defaults are sized from the page, as ever)."""
     from . import ops
     cfg = cfg or DetectConfig()
     page = _device_page(page)
     H, W = page.shape
-    min_ink, merge_gap, min_height, line_len, margin = cfg.resolved(H, W)
+    min_ink, merge_gap, min_height, line_len, margin = cfg.resolved(H, W) if staff_space is None else cfg.resolved(H, W, staff_space)
     ink, run = ops.page_profile(page, cfg.ink_threshold)
     out = torch.empty(4 + 4 * cfg.max_systems, dtype=torch.int32, device=page.device)
     ops.page_systems(page, ink, run, cfg.ink_threshold, min_ink, merge_gap, min_height, line_len, cfg.min_line_rows, margin, cfg.max_systems, out=out)
@@ -499,6 +526,227 @@ class OrientConfig:
             raise ValueError(f"OrientConfig: detect = {self.detect!r} is not None or a DetectConfig")
 
 
+@dataclass
+class StaffScale:
+    """What `choose_staff_scale` reads off the run-length histograms of a page, in pixels of that page:
+
+      line        the thickness of a staff line: the most frequent closed vertical ink run shorter than pitch_bin;
+      space       the white between two staff lines, pitch_bin - line (also `staff_space`);
+      pitch_bin   the distance from staff line to staff line: the most frequent sum of a closed ink run and the closed paper run under it;
+      pitch       the same as a float: the count-weighted mean of the bins pitch_bin - 1 .. pitch_bin + 1;
+      confidence  the share of all (ink run, paper run) pairs of the page that lie in those three bins, 0 .. 1."""
+    line: int
+    space: int
+    pitch_bin: int
+    pitch: float
+    confidence: float
+
+    @property
+    def staff_space(self):
+        return self.space
+
+
+_GATES = ("min_staff_space", "min_model_staff_space", "min_sharpness", "min_focus", "min_contrast", "min_scale_confidence")
+
+
+@dataclass
+class AssessConfig:
+    """Parameters of `estimate_staff_scale` and `assess_pages`:
+
+      ink_threshold   a pixel is ink if its value (uint8 / 255) is below this, as in `DetectConfig`;
+      paper_percent   `PageQuality.paper_level` is the level at or below which this share of the page's pixels lie (1 .. 100; 50: the
+                      median, paper on any page that is mostly paper);
+      ink_percent     `PageQuality.ink_level` likewise (1 .. 100; 2: darker than nearly everything, yet not one stray pixel);
+
+    and the gate, six lower bounds that ALL default to None - no bound, `PageQuality.ok` is True and `reasons` is empty:
+
+      min_staff_space        on `StaffScale.pitch`, pixels of the page from staff line to staff line (a page without a scale fails it);
+      min_model_staff_space  on `PageResult.system_staff_space`, the same in pixels of what the model reads (`page_inference` only);
+      min_sharpness          on `PageQuality.sharpness`;
+      min_focus              on `PageQuality.focus`;
+      min_contrast           on `PageQuality.contrast`, levels;
+      min_scale_confidence   on `StaffScale.confidence` (a page without a scale fails it).
+
+    No threshold is invented here: nothing in this repository can calibrate one (there are no real photographs in it, and no trained
+    checkpoint whose error rate could be set against these numbers).  A caller who has both sets the bounds.  Anything else: ValueError,
+    when the config is made and again when it is used."""
+    ink_threshold: float = 0.5
+    paper_percent: int = 50
+    ink_percent: int = 2
+    min_staff_space: Optional[float] = None
+    min_model_staff_space: Optional[float] = None
+    min_sharpness: Optional[float] = None
+    min_focus: Optional[float] = None
+    min_contrast: Optional[float] = None
+    min_scale_confidence: Optional[float] = None
+
+    def __post_init__(self):
+        self.check()
+
+    def check(self):
+        num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v   # noqa: E731
+        if not num(self.ink_threshold):
+            raise ValueError(f"AssessConfig: ink_threshold = {self.ink_threshold!r} is not a number")
+        for name in ("paper_percent", "ink_percent"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 100:
+                raise ValueError(f"AssessConfig: {name} = {v!r} is not an integer in 1 .. 100")
+        for name in _GATES:
+            v = getattr(self, name)
+            if v is not None and (not num(v) or v < 0 or v == float("inf")):
+                raise ValueError(f"AssessConfig: {name} = {v!r} is not None or a finite number >= 0")
+        if self.min_scale_confidence is not None and self.min_scale_confidence > 1:
+            raise ValueError(f"AssessConfig: min_scale_confidence = {self.min_scale_confidence!r} is not a share in 0 .. 1")
+
+    def failures(self, scale, sharpness, focus, contrast, model_staff_space=None):
+        """The gate: one reason string per bound that is set and missed (model_staff_space: the smallest of the page's systems, None when
+        it is not known - `assess_pages` - or the page has no system; the bound on it then does not apply)."""
+        self.check()
+        out = []
+
+        def bound(name, value, what):
+            lim = getattr(self, name)
+            if lim is not None and (value is None or value < lim):
+                out.append(f"{what} {'unknown' if value is None else format(value, '.6g')} is below {name} = {lim:g}")
+
+        bound("min_staff_space", None if scale is None else scale.pitch, "staff space (pixels from line to line)")
+        if model_staff_space is not None:
+            bound("min_model_staff_space", model_staff_space, "staff space in model pixels")
+        bound("min_sharpness", sharpness, "sharpness")
+        bound("min_focus", focus, "focus")
+        bound("min_contrast", contrast, "contrast")
+        bound("min_scale_confidence", None if scale is None else scale.confidence, "staff scale confidence")
+        return out
+
+
+@dataclass
+class PageQuality:
+    """What `assess_pages` measures on one page:
+
+      scale        its `StaffScale`, or None (a page without a closed ink run over a closed paper run: blank, or all ink);
+      sharpness    the variance of the 4-neighbour Laplacian L = 4 p - up - down - left - right of the levels over the interior pixels: the
+                   exact rational (n sum L^2 - (sum L)^2) / n^2 of the device's integer sums, converted to float once; 0.0 for a page
+                   without interior pixels;
+      paper_level, ink_level   the levels at `AssessConfig.paper_percent` and `ink_percent` of the level histogram;
+      contrast     paper_level - ink_level;
+      ink_share    the share of pixels whose level l counts as ink, float32(l) / 255 < ink_threshold;
+      focus        sharpness / max(contrast, 1)^2, dimensionless: sharpness falls with the square of the contrast as well as with blur;
+      ok, reasons  the gate of the `AssessConfig` (`AssessConfig.failures`): True and [] unless the caller set a bound that the page misses.
+
+    sharpness and focus depend on what the page went through: bilinear resampling (rectify, deskew) lowers them a little and flattening
+    stretches the levels, so values compare only under the same stage settings; `assess_pages` on the raw page judges the photo itself."""
+    scale: Optional[StaffScale]
+    sharpness: float
+    paper_level: int
+    ink_level: int
+    contrast: int
+    ink_share: float
+    focus: float
+    ok: bool = True
+    reasons: tuple = ()
+
+
+def choose_staff_scale(hists, cfg=None):
+    """`ops.page_runs` of a page, on the host (a tensor or nested lists, [3][256] integers) -> its `StaffScale`, or None.  Integers, and
+    float64 for the two quotients.  pitch_bin is the fullest of bins 2 .. 254 of row 2 (the lowest on ties; every bin empty: None - a
+    blank page); line the fullest of bins 1 .. pitch_bin - 1 of row 0 (the lowest on ties); space = pitch_bin - line; pitch the
+    count-weighted mean of bins pitch_bin - 1 .. pitch_bin + 1 of row 2; confidence the share of row 2's total in those three bins.
+    cfg (an `AssessConfig`) is checked and otherwise unused: the rule has no parameter."""
+    if cfg is not None:
+        cfg.check()
+    rows = hists.tolist() if torch.is_tensor(hists) else [list(r) for r in hists]
+    if len(rows) != 3 or any(len(r) != 256 for r in rows):
+        raise ValueError("choose_staff_scale: expected [3][256] run-length counts")
+    ink, pair = [int(v) for v in rows[0]], [int(v) for v in rows[2]]
+    pitch_bin = max(range(2, 255), key=lambda b: (pair[b], -b))
+    if pair[pitch_bin] == 0:
+        return None
+    line = max(range(1, pitch_bin), key=lambda b: (ink[b], -b))
+    near = range(pitch_bin - 1, pitch_bin + 2)
+    n = sum(pair[b] for b in near)
+    return StaffScale(line, pitch_bin - line, pitch_bin, sum(b * pair[b] for b in near) / n, n / sum(pair))
+
+
+def _level_at(levels, percent):
+    """The smallest level at or below which at least max(1, ceil(n * percent / 100)) of the n pixels lie (`ops.page_tile_levels`' rank)."""
+    rank, acc = max(1, -(-sum(levels) * percent // 100)), 0
+    for level, c in enumerate(levels):
+        acc += c
+        if acc >= rank:
+            return level
+    return 255
+
+
+def page_quality(hists, stats, levels, cfg=None, model_staff_space=None):
+    """The integers of `ops.page_runs` and `ops.page_sharpness`, on the host -> the `PageQuality` (`assess_pages` without the device)."""
+    from fractions import Fraction
+    cfg = cfg or AssessConfig()
+    cfg.check()
+    scale = choose_staff_scale(hists, cfg)
+    s1, s2, n = (int(v) for v in stats)
+    levels = [int(v) for v in levels]
+    sharpness = float(Fraction(n * s2 - s1 * s1, n * n)) if n else 0.0
+    paper, ink = _level_at(levels, cfg.paper_percent), _level_at(levels, cfg.ink_percent)
+    thr = torch.tensor(float(cfg.ink_threshold), dtype=torch.float32)
+    inked = (torch.arange(256, dtype=torch.float32) / torch.tensor(255.0, dtype=torch.float32) < thr).tolist()
+    ink_share = sum(c for c, on in zip(levels, inked) if on) / max(sum(levels), 1)
+    contrast = paper - ink
+    focus = sharpness / max(contrast, 1) ** 2
+    reasons = cfg.failures(scale, sharpness, focus, contrast, model_staff_space)
+    return PageQuality(scale, sharpness, paper, ink, contrast, ink_share, focus, not reasons, tuple(reasons))
+
+
+def _assess_launch(pages, cfg, sharp):
+    """int64 [pages, 768 (+ 259)] on the device: one fill for all pages, then per page the launch pair of `ops.page_runs` and, with
+    `sharp`, the launch of `ops.page_sharpness`."""
+    from . import ops
+    from ._lib import RUNS_WORDS, SHARP_WORDS
+    pages, _ = _page_lists(pages, None)
+    pages = [_device_page(p) for p in pages]
+    if not pages:
+        raise ValueError("no pages")
+    buf = torch.zeros(len(pages), RUNS_WORDS + (SHARP_WORDS if sharp else 0), dtype=torch.int64, device=pages[0].device)
+    for p, row in zip(pages, buf):
+        ops.page_runs(p, cfg.ink_threshold, out=row[:RUNS_WORDS])
+        if sharp:
+            ops.page_sharpness(p, out=row[RUNS_WORDS:])
+    return buf
+
+
+def assess_counts(pages, cfg=None):
+    """The device half of `assess_pages`: per page (hists [3][256], stats [3], levels [256]) as lists of integers on the host, after the
+    launches and the ONE copy of the call."""
+    from ._lib import RUNS_WORDS
+    cfg = cfg or AssessConfig()
+    cfg.check()
+    return [([r[0:256], r[256:512], r[512:RUNS_WORDS]], r[RUNS_WORDS:RUNS_WORDS + 3], r[RUNS_WORDS + 3:]) for r in _assess_launch(pages, cfg, True).cpu().tolist()]
+
+
+def estimate_staff_scale(pages, cfg=None):
+    """One page or a list -> per page its `StaffScale` or None (`choose_staff_scale`).  One launch pair per page (ops.page_runs) into one
+    tensor, and ONE device-to-host copy for all pages."""
+    from ._lib import RUNS_WORDS
+    cfg = cfg or AssessConfig()
+    cfg.check()
+    return [choose_staff_scale([row[0:256], row[256:512], row[512:RUNS_WORDS]], cfg) for row in _assess_launch(pages, cfg, False).cpu().tolist()]
+
+
+def assess_pages(pages, cfg=None, model_staff_space=None):
+    """One page or a list -> per page its `PageQuality`: the staff scale from vertical run lengths, sharpness, contrast and focus from
+    one more read of the page.  Three launches per page (ops.page_runs, ops.page_sharpness) after one fill, and ONE device-to-host copy
+    per call; everything after the copy is integers and float64 on the host (`page_quality`).  The pages are judged as they are passed
+    in: what `page_inference(assess=)` reports was measured behind its other stages (see `PageQuality`).  model_staff_space: per page
+    the number `AssessConfig.min_model_staff_space` is held against, or None (the bound does not apply: it needs the resize).
+    Out of scope: sizing flatten, deskew or rectify from the scale (they run before it can be measured), horizontal runs, a scale per
+    system, any default threshold, and anything measured on real photographs (there are none here)."""
+    cfg = cfg or AssessConfig()
+    rows = assess_counts(pages, cfg)
+    model = [None] * len(rows) if model_staff_space is None else list(model_staff_space)
+    if len(model) != len(rows):
+        raise ValueError(f"{len(rows)} pages but {len(model)} model staff spaces")
+    return [page_quality(*r, cfg, m) for r, m in zip(rows, model)]
+
+
 def _is_single_channel(page):
     return torch.is_tensor(page) and (page.dim() == 2 or (page.dim() == 3 and page.shape[0] == 1))
 
@@ -623,6 +871,12 @@ def orientation_from_photo_xy(code, source_size, px, py):
     return ((px, py), (W - 1 - px, py), (W - 1 - px, H - 1 - py), (px, H - 1 - py), (py, px), (H - 1 - py, px), (H - 1 - py, W - 1 - px), (py, W - 1 - px))[code - 1]
 
 
+def system_staff_spaces(scales, plans):
+    """Per system of `plan_systems`, the pitch of its page's `StaffScale` in MODEL pixels: pitch * resized height / box height (the resize
+    scales both axes alike up to rounding; the height is the axis the pitch was measured along).  None where the page has no scale."""
+    return [None if scales[p] is None else scales[p].pitch * size[0] / (y1 - y0) for p, (_, y0, _, y1), size, _ in plans]
+
+
 def _pixel_box(box, H, W):
     x0, y0, x1, y1 = (int(v) for v in box)
     if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
@@ -713,12 +967,22 @@ class PageResult:
       system_page  the page index of every row;
       sizes, windows   per row, the size (OH, OW) its box was resized to and the window (top, left, ch, cw) of it the model saw;
       patches_kept, patches_total   per row, the patches the encoder read and the patches of the window's grid: equal unless the call pruned
-                   blank patches (page_inference(prune=), `prune.prune_patches`)."""
+                   blank patches (page_inference(prune=), `prune.prune_patches`);
+      quality      per page its `PageQuality`, measured on the page that detection saw, or None: the call did not assess
+                   (page_inference(assess=));
+      system_staff_space   per row, the distance from staff line to staff line in MODEL pixels - the page's `StaffScale.pitch` times the
+                   resized height of the row's box over the box's height - or None: not assessed, or the page has no scale.  What
+                   `AssessConfig.min_model_staff_space` is held against, and the number a UI needs to say "move closer"."""
 
     def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=(), angles=None, page_sizes=None, flattened=None,
-                 quads=None, source_sizes=None, inset=2, orientations=None, patches_kept=None, patches_total=None):
+                 quads=None, source_sizes=None, inset=2, orientations=None, patches_kept=None, patches_total=None, quality=None,
+                 system_staff_space=None):
         self.boxes, self.seqs, self.log_probs, self.seq_mask = boxes, seqs, log_probs, seq_mask
         system_page = list(system_page)
+        self.quality = [None] * len(boxes) if quality is None else list(quality)
+        self.system_staff_space = [None] * len(system_page) if system_staff_space is None else [None if v is None else float(v) for v in system_staff_space]
+        if len(self.quality) != len(boxes) or len(self.system_staff_space) != len(system_page):
+            raise ValueError("PageResult: one quality (or None) per page and one staff space (or None) per system")
         self.patches_total = [None] * len(system_page) if patches_total is None else [int(n) for n in patches_total]   # (None: not recorded)
         self.patches_kept = list(self.patches_total) if patches_kept is None else [int(n) for n in patches_kept]
         if len(self.patches_total) != len(system_page) or len(self.patches_kept) != len(system_page):

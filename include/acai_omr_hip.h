@@ -1003,6 +1003,38 @@ int acai_page_col_profile(const void *page, int in_u8, int H, int W, int pitch, 
  * n <= 65535.  The reference has no counterpart: it is how the orientation estimate asks which end of a system holds the clef. */
 int acai_page_box_ink(const void *page, int in_u8, int H, int W, int pitch, float ink_threshold, const int32_t *boxes, int n, int32_t *out, void *stream);
 
+/* ---- page assessment: staff scale from run lengths, focus and contrast (csrc/assess.hip) ------------------------------------------------------
+ * An extension; the reference decodes whatever photo it is handed.  A page is as acai_page_profile takes it (uint8 or fp32, pitch >= W, the
+ * same size limits).  Integers only: the only atomics are integer adds, so the results are the same bits on every run and for every
+ * launch geometry.  Both entry points ADD to their output: the caller zeroes it (one fill serves all pages of a call). */
+#define ACAI_RUNS_CHUNK_ROWS 32    /* acai_page_runs: a wave walks 32 rows of 256 columns; `work` holds ceil(H / 32) * W int32 */
+#define ACAI_SHARP_CHUNK_ROWS 32   /* acai_page_sharpness: likewise, plus the row above and the row below */
+
+/* Vertical run-length histograms, hist int64 [3][256].  A pixel is ink exactly as in acai_page_profile: in_sample(p) < ink_threshold.  In
+ * every column take the maximal vertical runs of equal colour.  A run that touches row 0 or row H - 1 is OPEN - its true length is not
+ * known - and is never counted; every other run is closed.
+ *   hist[0][min(n, 255)] += 1  for every closed ink run of n rows,
+ *   hist[1][min(n, 255)] += 1  for every closed paper run of n rows,
+ *   hist[2][min(b + w, 255)] += 1  for every closed ink run of b rows that is directly followed, downwards, by a closed paper run of w rows.
+ * Bin 0 of every row stays as it was.  (The most frequent closed ink run of an engraved page is the thickness of a staff line, the most
+ * frequent pair the distance from staff line to staff line.)  TWO launches: a wave owns 256 columns (a lane 4 adjacent ones, so a wave reads
+ * 256 consecutive pixels of a row) of a chunk of ACAI_RUNS_CHUNK_ROWS rows and walks them down; runs that begin and end inside the chunk, and
+ * pairs of two such runs, are counted there - in LDS, then one global add per non-empty bin and workgroup - and the first and last run of
+ * every (column, chunk), with the run next to each, are left in `work` (work_elems int32, at least ceil(H / ACAI_RUNS_CHUNK_ROWS) * W); one
+ * lane per column then joins its chunks from the top down and counts the runs and pairs that cross or touch a chunk's edge. */
+int acai_page_runs(const void *page, int in_u8, int H, int W, int pitch, float ink_threshold, int64_t *hist, int32_t *work, int64_t work_elems,
+                   void *stream);
+
+/* Levels and their Laplacian in one read of the page, out int64 [3 + 256].  The level of a pixel is acai_page_tile_levels': a uint8 value as
+ * it is, an fp32 value v as floor(v * 255 + 0.5) (the product and the sum rounded one after the other) clamped to 0 .. 255.
+ *   out[3 + l] += the number of pixels of level l, over the whole page,
+ *   out[0] += sum L, out[1] += sum L * L, out[2] += count over the interior pixels (rows 1 .. H - 2, columns 1 .. W - 2), where
+ *   L = 4 p - up - down - left - right on levels, and count = (H - 2) (W - 2), or 0 when H < 3 or W < 3.
+ * |L| <= 1020, so the sums fit 64 bits for every page within the size limits.  ONE launch: the waves and lanes of acai_page_runs, three
+ * rows of levels in registers; per-lane sums are added up over the wave by shuffles and over the workgroup in LDS, then one global add
+ * per workgroup and sum, and one per non-empty level. */
+int acai_page_sharpness(const void *page, int in_u8, int H, int W, int pitch, int64_t *out, void *stream);
+
 /* ---- blank-patch pruning ahead of the encoder (csrc/prune.hip) -------------------------------------------------------------------------------
  * An extension; the reference encodes every patch.  The packed patch stream [M][L] (L = P * P elements per row, fp32 or bf16, rows `pitch`
  * elements apart; the base need not be the start of an allocation) loses the rows that are paper.  THREE launches for a whole batch and one
