@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip", "prune.hip", "assess.hip"]
+SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "decode_prefill.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip", "prune.hip", "assess.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -298,6 +298,8 @@ _SIGNATURES = {
     "acai_decode_prompt_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiPrompt), c_void_p]),
     "acai_decode_spec_prompt_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), POINTER(AcaiPrompt), c_void_p]),
     "acai_decode_spec_prompt_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), POINTER(AcaiPrompt), c_void_p]),
+    "acai_decode_prefill_self_kv": (c_int, [POINTER(AcaiDecoder), c_int, c_void_p, c_int, c_int, c_void_p]),
+    "acai_decode_prefill_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiPrompt), c_void_p, c_int, c_void_p]),
     "acai_decode_grammar_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiGrammar), c_void_p]),
     "acai_decode_grammar_sample_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiGrammar), c_void_p, c_int, c_float, c_void_p]),
     "acai_decode_slot_grammar_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), POINTER(AcaiGrammar), c_void_p]),

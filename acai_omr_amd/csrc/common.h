@@ -166,6 +166,45 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---- shared by the token-selection kernels (decode_select.hip) and the prompt prefill (decode_prefill.hip) -------------------------------
+// One wave over a logit row: the row maximum `best` at its first index `bi` (torch.argmax on CPU) and sum_i exp(lg[i] - best), returned
+// wave-uniform.  The greedy step and the beam step share it, so that a beam of width 1 reproduces greedy's log-probabilities bit for bit.
+__device__ __forceinline__ float row_argmax_sumexp(const float *lg, int V, int lane, float &best, int &bi) {
+    best = -INFINITY;
+    bi = 0x7fffffff;
+    for (int i = lane; i < V; i += 64) {
+        const float v = lg[i];
+        if (v > best) {  // strided scan keeps the lowest index per lane on ties
+            best = v;
+            bi = i;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {  // argmax, first index on ties (torch.argmax on CPU)
+        const float ov = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bi, o);
+        if (ov > best || (ov == best && oi < bi)) {
+            best = ov;
+            bi = oi;
+        }
+    }
+    float se = 0.f;
+    for (int i = lane; i < V; i += 64) se += expf(lg[i] - best);
+    return wave_sum(se);
+}
+
+// The prompt length of table row `row` (AcaiPrompt), clamped so that every index 1 .. len is a column of the table and of seqs.
+__device__ __forceinline__ int prompt_len(const int32_t *plen, int row, int ppitch, int max_len) {
+    return min(max(plen[row], 0), min(ppitch, max_len) - 1);
+}
+
+// The prompt's token of output index p of table row `row`, or -1 where the prompt gives none (p outside 1 .. len, an id outside [0, V)).
+__device__ __forceinline__ int prompt_token(const int32_t *ptok, int row, int ppitch, int p, int len, int V) {
+    if (p < 1 || p > len) return -1;
+    const int v = ptok[(size_t)row * ppitch + p];
+    return (v >= 0 && v < V) ? v : -1;
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // Once-per-DEVICE latch for hipFuncSetAttribute and the like (function attributes are per device; a per-process `static bool` skipped the
 // call for every device after the first when one process drives several GPUs).  Usage: static bool seen[ACAI_MAX_DEV]; if (acai_first_on_device(seen)) ...

@@ -9,7 +9,8 @@
 // streaming kernel with 16-byte loads, fp32 accumulation and no host involvement: positions, lengths and
 // the finished flags live in device memory, so one captured hipGraph replays for every token.
 // The step driver lives here; its kernels are in decode_gemv.hip (skinny_gemm / skinny_mfma / skinny_chain), decode_attn.hip
-// (decode_attn, attn_combine, the FP8 memory cache) and decode_select.hip (embedding and token selection), behind decode_internal.h.
+// (decode_attn, attn_combine, the FP8 memory cache), decode_select.hip (embedding and token selection) and decode_prefill.hip (prompt
+// prefill), behind decode_internal.h.
 #include "decode_internal.h"
 
 #include <mutex>
@@ -426,6 +427,37 @@ extern "C" int acai_decode_spec_prompt_step(const AcaiDecoder *d, const AcaiSpec
     rc = decode(d, nullptr, st, false, true, nullptr, nullptr, sp);
     if (rc) return rc;
     return launch_spec_prompt_accept(d, sp, prompt, 0, st);
+}
+
+// Prologue of the two prompt-prefill entry points: the descriptor and the common depth C of the prompts.
+static int check_prefill(const AcaiDecoder *d, int C, const char *fn) {
+    int rc = check_decoder(d);
+    if (rc) return rc;
+    ACAI_CHECK_ARG(d->max_len > 1 && d->max_len <= d->Tmax, "%s: max_len outside [2, Tmax] (max_len=%d Tmax=%d)", fn, d->max_len, d->Tmax);
+    ACAI_CHECK_ARG(C >= 1 && C <= d->max_len - 1, "%s: prefill depth C = %d outside [1, max_len - 1 = %d]", fn, C, d->max_len - 1);
+    return 0;
+}
+
+extern "C" int acai_decode_prefill_self_kv(const AcaiDecoder *d, int layer, const void *qkv, int ld, int C, void *stream) {
+    int rc = check_prefill(d, C, "acai_decode_prefill_self_kv");
+    if (rc) return rc;
+    ACAI_CHECK_ARG(qkv, "acai_decode_prefill_self_kv: null qkv");
+    ACAI_CHECK_ARG(layer >= 0 && layer < d->L, "acai_decode_prefill_self_kv: layer %d outside [0, L = %d)", layer, d->L);
+    ACAI_CHECK_ARG(ld >= 3 * d->E, "acai_decode_prefill_self_kv: ld = %d below 3E = %d", ld, 3 * d->E);
+    ACAI_CHECK_ARG(d->layers[layer].k_self && d->layers[layer].v_self, "acai_decode_prefill_self_kv: null self K/V cache of layer %d", layer);
+    return launch_prefill_self_kv(d, layer, qkv, ld, C, (hipStream_t)stream);
+}
+
+extern "C" int acai_decode_prefill_arm(const AcaiDecoder *d, const AcaiPrompt *prompt, const float *logits, int C, void *stream) {
+    int rc = check_prefill(d, C, "acai_decode_prefill_arm");
+    if (rc) return rc;
+    ACAI_CHECK_ARG(logits, "acai_decode_prefill_arm: null logits");
+    ACAI_CHECK_ARG(d->emb && d->pos && d->seqs && d->logprobs && d->finished, "acai_decode_prefill_arm: decoder has no embedding / sequence state");
+    if ((rc = check_prompt(d, prompt, d->B, "acai_decode_prefill_arm"))) return rc;
+    ACAI_CHECK_ARG(d->V <= 512, "acai_decode_prefill_arm: vocabulary %d above 512", d->V);
+    if ((rc = launch_prefill_arm(d, prompt, logits, C, (hipStream_t)stream))) return rc;
+    x_valid_set(d, true);   // x holds the input of step C + 1
+    return 0;
 }
 
 // Prologue of the grammar-constrained steps, after the counterpart's own checks.

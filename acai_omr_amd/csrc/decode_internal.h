@@ -1,4 +1,4 @@
-// Internal interface between the decode sources (decode.hip, decode_gemv.hip, decode_attn.hip, decode_select.hip).  Not installed and
+// Internal interface between the decode sources (decode.hip, decode_gemv.hip, decode_attn.hip, decode_select.hip, decode_prefill.hip).  Not installed and
 // not part of the C ABI (include/acai_omr_hip.h).  No __device__ helper lives here: what the decode kernels share is in common.h.
 #pragma once
 #include <stdlib.h>
@@ -104,3 +104,7 @@ int launch_grammar_sample(const AcaiDecoder *d, const AcaiGrammar *gr, const flo
 int launch_slot_grammar_argmax(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *gr, hipStream_t st);
 int launch_slot_grammar_sample(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *gr, const float *uniforms, int ld_uniforms,
                                const int32_t *urow, int top_k, float temperature, hipStream_t st);
+
+// ---- decode_prefill.hip: the prompt's self K/V rows and the state its steps would leave, from one teacher-forced pass ------------------
+int launch_prefill_self_kv(const AcaiDecoder *d, int layer, const void *qkv, int ld, int C, hipStream_t st);
+int launch_prefill_arm(const AcaiDecoder *d, const AcaiPrompt *pr, const float *logits, int C, hipStream_t st);

@@ -14,32 +14,7 @@ __global__ __launch_bounds__(256) void embed_kernel(const float *emb, const floa
 
 __global__ void set_step_kernel(int32_t *step, int t) { step[0] = t; }
 
-// One wave over a logit row: the row maximum `best` at its first index `bi` (torch.argmax on CPU) and sum_i exp(lg[i] - best), returned
-// wave-uniform.  The greedy step and the beam step share it, so that a beam of width 1 reproduces greedy's log-probabilities bit for bit.
-__device__ __forceinline__ float row_argmax_sumexp(const float *lg, int V, int lane, float &best, int &bi) {
-    best = -INFINITY;
-    bi = 0x7fffffff;
-    for (int i = lane; i < V; i += 64) {
-        const float v = lg[i];
-        if (v > best) {  // strided scan keeps the lowest index per lane on ties
-            best = v;
-            bi = i;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {  // argmax, first index on ties (torch.argmax on CPU)
-        const float ov = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ov > best || (ov == best && oi < bi)) {
-            best = ov;
-            bi = oi;
-        }
-    }
-    float se = 0.f;
-    for (int i = lane; i < V; i += 64) se += expf(lg[i] - best);
-    return wave_sum(se);
-}
-
+// (row_argmax_sumexp, the row maximum / arg-max / sum of exponentials all selection kernels start from, is in common.h)
 // cached_get_next_token (M:579-581) + loop bookkeeping (M:606-611).  One workgroup, wave w takes rows w, w+4, ...
 // With `emb`: the wave that chose row b's token also writes the NEXT step's input x[b] = vocab_embedding[token] + pos_embedding[t + 1]
 // (quirk Q1: the token at index t is embedded with position t + 1, M:576), so a token step needs no embed launch of its own.
@@ -89,18 +64,7 @@ __global__ __launch_bounds__(1024) void argmax_logprob_kernel(const float *logit
 }
 
 // ---- prompted decoding (an extension: the reference starts every sequence from <bos> alone) -----------------------------------------------
-// The prompt length of table row `row`, clamped so that every index 1 .. len is a column of the table and of seqs.
-__device__ __forceinline__ int prompt_len(const int32_t *plen, int row, int ppitch, int max_len) {
-    return min(max(plen[row], 0), min(ppitch, max_len) - 1);
-}
-
-// The prompt's token of output index p of table row `row`, or -1 where the prompt gives none (p outside 1 .. len, an id outside [0, V)).
-__device__ __forceinline__ int prompt_token(const int32_t *ptok, int row, int ppitch, int p, int len, int V) {
-    if (p < 1 || p > len) return -1;
-    const int v = ptok[(size_t)row * ppitch + p];
-    return (v >= 0 && v < V) ? v : -1;
-}
-
+// (prompt_len / prompt_token, the clamped reads of the prompt tables, are in common.h: decode_prefill.hip shares them)
 // argmax_logprob_kernel (with its bookkeeping) whose token at index t <= len[b] is the prompt's.  The log-prob of token k is
 // -(logf(se) - (logit[k] - max)): for the arg-max the inner difference is exactly 0 and the value is argmax_logprob_kernel's -logf(se) bit for
 // bit (beam_select_kernel's form).  A row inside its prompt (t < len[b]) counts as unfinished.

@@ -292,6 +292,8 @@ class DecodeEngine:
         self.slot_uniforms = None
         self.spec_t = None      # speculative decoding: per-image state (t, cap, steps, key table, next inputs, injected drafts), allocated on first use
         self.prompt_tok = None  # prompted decoding: (Bmax, Tmax) int32 tokens by output index and (Bmax,) int32 lengths, allocated on first use
+        self._mem = None        # the packed memories of the last prepare() (mem32, memb): a prompt prefill's pass reads them again
+        self.prefilled_tokens = 0   # prompt tokens (rows x depth) that prefilled runs took in their pass instead of in prompt steps, so far
         self.gram_next = None   # grammar-constrained decoding: engine-owned copies of the automaton's tables and the rows' states (_set_grammar)
         self._per_row_cross = False
         self.cache_len = 0
@@ -341,6 +343,7 @@ class DecodeEngine:
                 ops.cross_kv_prefill(mem, w, b, row_seq, row_pos, pre_off, pre_len, self.k_cross[i], self.v_cross[i],
                                      H, self.dh, dhp, round_bf16=self.bf)
         self.B, self.lens, self.group = B, [l for l in lens for _ in range(G)], G
+        self._mem = (mem32, memb)
         self.reset_self_cache()
         self._build_desc()
 
@@ -486,13 +489,15 @@ class DecodeEngine:
         cur.wait_stream(self.stream)
 
     # ---- ViTOMR.cached_greedy_generate (models.py:600-615) ----------------------------------------------------------
-    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None, prompt=None, *, grammar=None):
+    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None, prompt=None, *, grammar=None, prefill=False):
         """Runs up to max_len-1 greedy steps; returns views seqs (B,max_len) int64 and logprobs (B,max_len) fp32.
         Early exit when every row has produced <eos> (checked every `poll` steps; overshoot is masked later).
         prompt (an extension; None = off): one token list / 1-D tensor per row, the row's tokens of indices 1 .. P (_set_prompt); the row
         takes them whatever the model prefers, records the model's log-prob of each, and decodes greedily from index P + 1.
         grammar (an extension; None = off): a grammar.TokenAutomaton - every row takes the best token its automaton state allows and
-        logprobs holds the log-softmax over the allowed tokens (_set_grammar); not combinable with prompt."""
+        logprobs holds the log-softmax over the allowed tokens (_set_grammar); not combinable with prompt.
+        prefill (an extension; False = off): with a prompt, the C = min P tokens every row has are computed in one teacher-forced pass
+        (_prefill) and the prompt steps start at index C + 1; without a prompt, or with an empty one in the batch, it changes nothing."""
         if grammar is not None:
             if prompt is not None:
                 raise ValueError("grammar (constrained decoding) cannot be combined with prompt (prompted decoding): out of scope here")
@@ -502,9 +507,10 @@ class DecodeEngine:
         if prompt is None:
             with self._run(max_len, ("greedy",)):
                 return self._decode_loop(max_len, poll, use_graph, on_chunk)
+        plan = self._prefill_plan(prompt, max_len) if prefill else None
         with self._run(max_len, ("prompt",)):
             self._set_prompt(prompt, self.B, max_len)
-            return self._decode_loop(max_len, poll, use_graph, on_chunk)
+            return self._decode_loop(max_len, poll, use_graph, on_chunk, prefill=plan)
 
     # ---- prompted decoding (an extension: the reference starts every sequence from <bos> alone) -------------------------------------------
     def _set_prompt(self, prompt, n, max_len):
@@ -529,6 +535,56 @@ class DecodeEngine:
             lens[i] = p.numel()
         self.prompt_tok[:n].copy_(ops.h2d(tab, self.device))
         self.prompt_len[:n].copy_(ops.h2d(lens, self.device))
+
+    # ---- prompt prefill (an extension): the prompt's common part in one teacher-forced pass instead of one step per token -----------------
+    def _prefill_plan(self, prompt, max_len):
+        """(C, live) of a prefilled prompt run - the depth C = min_b P_b every row's prompt reaches and whether a row goes on after index C
+        (not when every prompt ends there with <eos>: the prompt step's finishing rule at t = C) - checked on the host before anything is
+        launched (ValueError for what a prefilled run cannot do); None = nothing to prefill: the run is the plain prompt run.  A wrong
+        number of prompts or a too long one is left to _set_prompt."""
+        if self.cross_fp8:
+            raise ValueError("prefill (prompt prefill) does not support an FP8 memory cache: the pass reads the unquantised memory; use "
+                             "memory_cache_dtype=None")
+        rows = [torch.as_tensor(p).reshape(-1) for p in prompt]
+        if len(rows) != self.B or not rows or max(r.numel() for r in rows) > max_len - 1 or min(r.numel() for r in rows) < 1:
+            return None
+        if self.group != 1 or self.omr is None or self._mem is None:
+            raise ValueError(f"prefill (prompt prefill) needs an OMRDecoder's engine prepared with one memory per row (prepared: group_size="
+                             f"{self.group})")
+        if self.V > 512:
+            raise ValueError(f"prefill (prompt prefill) needs a vocabulary of at most 512 tokens, got {self.V}")
+        C = min(r.numel() for r in rows)
+        # every id is used as an index where a prompt step would fall back to its arg-max: position j + 1 would then depend on position j
+        for i, r in enumerate(rows):
+            if r.numel() and (int(r.min()) < 0 or int(r.max()) >= self.V):
+                raise ValueError(f"prompt {i} holds a token id outside [0, {self.V}): a prefilled run (prefill) cannot take it")
+        eos = self.omr.eos_idx
+        return C, any(not (r.numel() == C and int(r[-1]) == eos) for r in rows)
+
+    def _prefill(self, C):
+        """The armed engine (arm(), prompt tables set) -> the state after C prompt steps, C = the depth every row's prompt reaches: one
+        packed pass over B sequences of C tokens (row b's tokens of indices 0 .. C - 1 at positions 1 .. C, quirk Q1) over the prepared
+        memories at the engine's precision - OMRDecoder._layers_packed, eagerly, on the current stream; it projects the cross K/V again -
+        whose per-layer qkv goes into the self K/V caches (acai_decode_prefill_self_kv) and whose logits become seqs / logprobs / finished /
+        step / x (acai_decode_prefill_arm)."""
+        B, own, L, d = self.B, self.omr, _lib.lib(), ctypes.byref(self._desc)
+        st = ops._st()
+        tok = self.prompt_tok[:B, :C].clone()          # column 0 is not a prompt column: it becomes <bos>
+        tok[:, 0] = own.bos_idx
+        mem32, memb = self._mem
+
+        def sink(layer, qkv):
+            assert qkv.dtype == self.cdt and qkv.shape == (B * C, 3 * self.E) and qkv.stride(1) == 1
+            _lib.check(L.acai_decode_prefill_self_kv(d, layer, qkv.data_ptr(), qkv.stride(0), C, st), "acai_decode_prefill_self_kv")
+
+        with torch.no_grad():
+            logits = own._layers_packed(own._embed_packed(tok.reshape(-1), [C] * B, True, 1), [C] * B, mem32, memb, self.lens, self.prec,
+                                        kv_sink=sink)
+        assert logits.dtype == torch.float32 and logits.shape == (B * C, self.V) and logits.is_contiguous()
+        _lib.check(L.acai_decode_prefill_arm(d, ctypes.byref(self._prompt_desc), logits.data_ptr(), C, st), "acai_decode_prefill_arm")
+        self._x_valid = True
+        self.cache_len = C
+        self.prefilled_tokens += B * C
 
     # ---- grammar-constrained decoding (an extension: the reference knows no grammar) -----------------------------------------------------------
     GRAMMAR_MODES = ("grammar", "grammar_sample", "slot_grammar", "slot_grammar_sample")
@@ -590,15 +646,18 @@ class DecodeEngine:
             self.uniforms[:B, :max_actions] = uniforms.to(device=self.device, dtype=torch.float32)
             return self._decode_loop(max_actions, poll, use_graph)
 
-    def greedy_chunks(self, max_len, chunk, prompt=None, *, grammar=None):
+    def greedy_chunks(self, max_len, chunk, prompt=None, *, grammar=None, prefill=False):
         """Generator over the greedy loop in chunks of `chunk` tokens (streamed inference): yields (tokens_done, all_finished)
         after each chunk; the decode graph is replayed on the engine's stream, the caller's stream waits for it.
         prompt / grammar: as in greedy(); the mode is ("prompt",) / ("grammar",) while the generator runs and goes back to greedy when it
-        ends or is closed."""
+        ends or is closed.
+        prefill: as in greedy().  The C prefilled tokens are there at once: every multiple of `chunk` up to C is yielded without a step in
+        between, and the first chunk of steps ends at the next multiple, so tokens_done takes the values it takes without prefill."""
         if max_len > self.Tmax:
             raise RuntimeError(f"{max_len} decoding steps is too long for max sequence length of {self.Tmax}")
         if grammar is not None and prompt is not None:
             raise ValueError("grammar (constrained decoding) cannot be combined with prompt (prompted decoding): out of scope here")
+        plan = self._prefill_plan(prompt, max_len) if prefill and prompt is not None else None
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         if prompt is not None:
@@ -612,9 +671,21 @@ class DecodeEngine:
                 if grammar is not None:
                     self._set_grammar(grammar)
                 self._arm_and_capture(self.B)
+                if plan is not None:
+                    self._prefill(plan[0])
             done, total = 0, max_len - 1
+            if plan is not None:
+                C, live = plan
+                cur.wait_stream(self.stream)
+                for done in range(chunk, C, chunk):
+                    yield done, False
+                done = C
+                if not live or C % chunk == 0:
+                    yield done, not live
+                if not live:
+                    return
             while done < total:
-                n = min(chunk, total - done)
+                n = min(chunk - done % chunk, total - done)
                 with torch.cuda.stream(self.stream):
                     self.launch_steps(n)
                     fin = int(self.finished[self.B].item()) == 0
@@ -856,11 +927,19 @@ class DecodeEngine:
             self.ensure_graph(self.STEPS_PER_GRAPH)
             self.arm(B)
 
-    def _decode_loop(self, max_len, poll, use_graph, on_chunk=None):
+    def _decode_loop(self, max_len, poll, use_graph, on_chunk=None, prefill=None):
+        """prefill: _prefill_plan's (C, live) - the loop starts behind the C prefilled indices, and runs no step when no row is live."""
         B = self.B
         self._arm_and_capture(B, use_graph)
         done = 0
         total = max_len - 1
+        if prefill is not None:
+            done, live = prefill
+            self._prefill(done)
+            if on_chunk is not None:
+                on_chunk(done)
+            if not live:
+                total = done
         while done < total:
             n = min(poll, total - done)
             self.launch_steps(n, use_graph)

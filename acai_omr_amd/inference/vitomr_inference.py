@@ -44,7 +44,7 @@ def _full_grid(dims, lens, pruned):
 
 
 def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1, length_penalty=1.0, speculative=0, ngram=3, prefix=None, *,
-              grammar=None, prune=None):
+              grammar=None, prune=None, prefill=False):
     """img: one (1,H,W) tensor or a list of them -> (seqs int64 (B,T'), log_probs fp32 (B,T'), seq_mask bool (B,T')).
     beam_width > 1 (extension): beam search with that many hypotheses per image, scored by cum / len^length_penalty
     (ViTOMR.cached_beam_generate); beam_width = 1 is the reference's greedy decode.
@@ -62,7 +62,10 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
     of the kept counts to the host per batch), so the encoder, the cross K/V prefill and every decode step see a shorter memory; img may
     also be an already pruned `utils.PackedPatches`.  It combines with every decode mode above and with the FP8 memory cache.  The
     thresholds are chosen on synthetic pages; the blank share of real systems and what dropping paper does to the output of a trained
-    checkpoint have not been measured."""
+    checkpoint have not been measured.
+    prefill (an extension, default False = off: the paths above, bit for bit, no launch added): prompt prefill of greedy prompted decoding
+    (ViTOMR.cached_greedy_generate) - the prompt tokens all images have in one teacher-forced pass instead of one decode step each.  With
+    speculative, beam_width > 1, grammar or an FP8 memory cache it raises ValueError (out of scope here)."""
     if grammar is not None:
         for other, on in (("beam search (beam_width > 1)", beam_width != 1), ("speculative decoding (speculative)", bool(speculative)),
                           ("prompted decoding (prefix)", prefix is not None)):
@@ -72,6 +75,7 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
         raise ValueError("speculative decoding cannot be combined with beam search (beam_width > 1)")
     if prefix is not None and beam_width != 1:
         raise ValueError("prefix (prompted decoding) cannot be combined with beam search (beam_width > 1): out of scope here")
+    _check_prefill(prefill, beam_width, speculative, grammar)
     vitomr.eval()
     with torch.no_grad():
         lat32, _, lens = _encode(vitomr, img, prune)
@@ -83,12 +87,23 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
                                                   prefix=prefix)
             if beam_width != 1:
                 return vitomr._beam_packed(None if bf else mem, mem if bf else None, lens, beam_width, max_inference_len, length_penalty)
-            return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, prefix=prefix, grammar=grammar)
+            return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, prefix=prefix, grammar=grammar,
+                                         prefill=prefill)
+
+
+def _check_prefill(prefill, beam_width, speculative, grammar):
+    """prefill (prompt prefill) belongs to greedy prompted decoding alone: the modes it cannot be combined with, refused by name."""
+    if not prefill:
+        return
+    for other, on in (("speculative decoding (speculative)", bool(speculative)), ("beam search (beam_width > 1)", beam_width != 1),
+                      ("grammar (constrained decoding)", grammar is not None)):
+        if on:
+            raise ValueError(f"prefill (prompt prefill) cannot be combined with {other}: out of scope here")
 
 
 def _check_decode_kwargs(who, decode_kwargs):
     """The decode arguments that aligned_inference / confident_inference pass on to inference()'s decode, refused as inference() refuses them."""
-    unknown = set(decode_kwargs) - {"beam_width", "length_penalty", "speculative", "ngram", "prefix", "grammar"}
+    unknown = set(decode_kwargs) - {"beam_width", "length_penalty", "speculative", "ngram", "prefix", "grammar", "prefill"}
     if unknown:
         raise TypeError(f"{who}() got unexpected decode arguments {sorted(unknown)}")
     beam_width, speculative = decode_kwargs.get("beam_width", 1), decode_kwargs.get("speculative", 0)
@@ -102,6 +117,7 @@ def _check_decode_kwargs(who, decode_kwargs):
         raise ValueError("speculative decoding cannot be combined with beam search (beam_width > 1)")
     if prefix is not None and beam_width != 1:
         raise ValueError("prefix (prompted decoding) cannot be combined with beam search (beam_width > 1): out of scope here")
+    _check_prefill(decode_kwargs.get("prefill", False), beam_width, speculative, grammar)
 
 
 def _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs):
@@ -112,13 +128,13 @@ def _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs):
         return vitomr._speculative_packed(mem32, memb, lens, max_inference_len, speculative, decode_kwargs.get("ngram", 3), prefix=prefix)
     if beam_width != 1:
         return vitomr._beam_packed(mem32, memb, lens, beam_width, max_inference_len, decode_kwargs.get("length_penalty", 1.0))
-    return vitomr._greedy_packed(mem32, memb, lens, max_inference_len, prefix=prefix, grammar=grammar)
+    return vitomr._greedy_packed(mem32, memb, lens, max_inference_len, prefix=prefix, grammar=grammar, prefill=decode_kwargs.get("prefill", False))
 
 
 def aligned_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, layers=None, head_weights=None, return_maps=False, *, prune=None,
                       **decode_kwargs):
     """inference() plus token-to-image alignment (an extension) -> (seqs, log_probs, seq_mask, TokenAlignment).  The images are encoded once;
-    the decode is inference()'s own (decode_kwargs - beam_width, length_penalty, speculative, ngram, prefix, grammar - are passed on, and
+    the decode is inference()'s own (decode_kwargs - beam_width, length_penalty, speculative, ngram, prefix, grammar, prefill - are passed on, and
     its errors stay its errors); then one teacher-forced pass over the produced tokens on the same packed memory, with the decode's
     positions, writes each token's cross-attention map over the image's patches and reduces it to a location
     (ViTOMR.locate_tokens; the grids come from the image sizes).  layers / head_weights select and weight the decoder layers and heads
@@ -404,9 +420,10 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, patches_kept=packed.lens, patches_total=total, **turned)
 
 
-def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None, *, grammar=None):
+def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None, *, grammar=None, prefill=False):
     """prefix (extension, default None = off): prompted decoding of the one image, as in inference(); the forced tokens arrive in the
-    STEP events like any others.  grammar (extension, default None = off): constrained decoding as in inference(), not with prefix."""
+    STEP events like any others.  grammar (extension, default None = off): constrained decoding as in inference(), not with prefix.
+    prefill (extension, default False = off): prompt prefill as in inference(); not with grammar."""
     vitomr.eval()
     with torch.no_grad():
         yield {"type": InferenceEvent.ENCODING_START.value, "payload": None}
@@ -415,5 +432,6 @@ def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flus
             img_latent = vitomr.transition_head(img_latent)
             yield {"type": InferenceEvent.ENCODING_FINISH.value, "payload": None}
             for event in vitomr.streamed_cached_greedy_generate(img_latent, latent_attention_mask, max_len=max_inference_len,
-                                                                flush_interval=flush_interval, prefix=prefix, grammar=grammar):
+                                                                flush_interval=flush_interval, prefix=prefix, grammar=grammar,
+                                                                prefill=prefill):
                 yield event

@@ -429,11 +429,13 @@ class OMRDecoder(nn.Module):
             return ops.gather_rows(self.vocab_embedding.weight.detach(), inputs.to(device=dev, dtype=torch.int32).contiguous(), add=x32)
         return x32 + inputs.to(dev).float()
 
-    def _layers_packed(self, x32, lens_t, mem32, memb, lens_s, prec, maps=None):
+    def _layers_packed(self, x32, lens_t, mem32, memb, lens_s, prec, maps=None, kv_sink=None):
         """The decoder layers, final norm and unembed on a packed stream: forward_packed's body, shared with cross_attention_maps_packed.
         maps (None = plain forward): {"weights": {layer index: [H] fp32 device tensor}, "out", "map_off", "logits"} - in those layers the
         cross-attention also saves its log-sum-exp and ops.attn_probs_mean adds the layer's weighted head mean to maps["out"]; unless
-        maps["logits"], the pass ends after the last such layer's cross-attention and returns None."""
+        maps["logits"], the pass ends after the last such layer's cross-attention and returns None.
+        kv_sink (None = off): called as kv_sink(layer index, qkv) with every layer's self-attention in-projection (sum T, 3E) in the compute
+        dtype while it is alive - columns E:3E are the layer's self K and V (DecodeEngine._prefill copies them into the decode's caches)."""
         bf = prec == "bf16"
         dev, E, H = self.pos_embedding.device, self.hidden_dim, self.num_heads
         wc = _wc(self)
@@ -448,6 +450,8 @@ class OMRDecoder(nn.Module):
         for i, ly in enumerate(self.decoder_blocks.layers):
             sa, ca = ly.self_attn, ly.multihead_attn
             qkv = EG.linear(x32, xb, sa.in_proj_weight, sa.in_proj_bias, prec, wc)
+            if kv_sink is not None:
+                kv_sink(i, qkv)
             a = ops.attn_varlen(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], cu_t, cu_t, H, dh, mt, causal=True)
             y = ops.gemm_nt(a, wc.w(sa.out_proj.weight, prec), wc.b(sa.out_proj.bias, prec), residual=x32, round_bf16=bf)
             x32, xb = ops.layernorm(y, ly.norm1.weight.detach(), ly.norm1.bias.detach(), ly.norm1.eps, want_bf16=bf)
@@ -1102,19 +1106,26 @@ class ViTOMR(nn.Module):
         if prefix is not None:
             raise ValueError("grammar (constrained decoding) cannot be combined with prefix (prompted decoding): out of scope here")
 
-    def _greedy_packed(self, mem32, memb, lens, max_len, on_chunk=None, prefix=None, grammar=None):
+    @staticmethod
+    def _check_prefill(prefill, grammar):
+        if prefill and grammar is not None:
+            raise ValueError("prefill (prompt prefill) cannot be combined with grammar (constrained decoding): out of scope here")
+
+    def _greedy_packed(self, mem32, memb, lens, max_len, on_chunk=None, prefix=None, grammar=None, *, prefill=False):
         blocks = self.decoder._cached_blocks()
         self._check_grammar(grammar, prefix)
+        self._check_prefill(prefill, grammar)
         prompt = self._check_prefix(prefix, len(lens), max_len)
         blocks.prepare_caches_packed(mem32, memb, lens)
         eng = blocks.engine(self.decoder.pos_embedding.device)
         if grammar is not None:
             seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk, grammar=grammar)
         else:
-            seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk) if prompt is None else eng.greedy(max_len, on_chunk=on_chunk, prompt=prompt)
+            kw = {"prefill": True} if prefill else {}
+            seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk) if prompt is None else eng.greedy(max_len, on_chunk=on_chunk, prompt=prompt, **kw)
         return self.mask_and_clip_seqs(seqs.clone(), lps.clone())
 
-    def cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, prefix=None, *, grammar=None):
+    def cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, prefix=None, *, grammar=None, prefill=False):
         """Batched greedy decode with KV caching (M:600-615) -> seqs (B,T') int64, log_probs (B,T') fp32, mask (B,T') bool.
         The whole loop runs as replays of one captured hipGraph; the host only polls an "all finished" counter.
         prefix (an extension, default None = off): prompted decoding - one entry per image (a 1-D integer tensor or list, possibly empty;
@@ -1125,9 +1136,15 @@ class ViTOMR(nn.Module):
         grammar (an extension, default None = off): a grammar.TokenAutomaton - at every index a row takes the best token its automaton state
         allows, log_probs holds the log-softmax over the allowed tokens (the policy actually run), and the state advances on the device
         inside the replayed graph.  An automaton that allows everything gives the unconstrained result bit for bit.  Not combinable with
-        prefix (ValueError)."""
+        prefix (ValueError).
+        prefill (an extension, default False = off): prompt prefill - the first C = min_i P_i prompt tokens, which every image has, are
+        computed in one teacher-forced pass over the memories instead of C decode steps, and decoding goes on from index C + 1 (images
+        with P_i > C keep taking their forced tokens there).  The tokens of a prompt and the mask are what they are without it; the
+        log-probs of indices 1 .. C come from the pass and, like everything decoded after them, agree with the stepwise run's within the
+        pass-versus-decode bars (1e-4 fp32, 0.07 bf16), so a free token can differ where the model's top two logits are that close.
+        Without a prefix, or with an empty prompt in the batch, it changes nothing.  Not with an FP8 memory cache (ValueError)."""
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
-        return self._greedy_packed(mem32, None, lens, max_len, prefix=prefix, grammar=grammar)
+        return self._greedy_packed(mem32, None, lens, max_len, prefix=prefix, grammar=grammar, prefill=prefill)
 
     def _beam_packed(self, mem32, memb, lens, beam_width, max_len, length_penalty):
         blocks = self.decoder._cached_blocks()
@@ -1231,13 +1248,15 @@ class ViTOMR(nn.Module):
         return self._continuous_packed(mem32, None, lens, max_len, slots, grammar=grammar)
 
     def streamed_cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, flush_interval=25, prefix=None, *,
-                                        grammar=None):
+                                        grammar=None, prefill=False):
         """Generator of {"type", "payload"} events (M:625-647); single image only.
         prefix: prompted decoding as in cached_greedy_generate; STEP events carry the forced tokens like any others.
-        grammar: constrained decoding as in cached_greedy_generate (not with prefix)."""
+        grammar: constrained decoding as in cached_greedy_generate (not with prefix).
+        prefill: prompt prefill as in cached_greedy_generate; the STEP events of the prefilled tokens follow each other at once."""
         if img_latent.shape[0] != 1:
             raise ValueError("Streamed generation only supports single image batches")
         self._check_grammar(grammar, prefix)
+        self._check_prefill(prefill, grammar)
         prompt = self._check_prefix(prefix, 1, max_len)
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         blocks = self.decoder._cached_blocks()
@@ -1247,7 +1266,7 @@ class ViTOMR(nn.Module):
         # (the reference yields STEP at every t % flush_interval == 0 that did not finish the sequence - also at t == max_len - 1, M:641-645)
         kw = {} if grammar is None else {"grammar": grammar}
         for t_done, finished in (eng.greedy_chunks(max_len, flush_interval, **kw) if prompt is None else
-                                 eng.greedy_chunks(max_len, flush_interval, prompt=prompt)):
+                                 eng.greedy_chunks(max_len, flush_interval, prompt=prompt, **({"prefill": True} if prefill else {}))):
             if finished:
                 break
             if t_done % flush_interval == 0:

@@ -675,6 +675,26 @@ int acai_decode_spec_prompt_arm(const AcaiDecoder *d, const AcaiSpec *sp, const 
  * from sp's usual source.  What is written equals acai_decode_prompt_step run token by token.  Same checks as acai_decode_spec_step and
  * acai_decode_spec_prompt_arm. */
 int acai_decode_spec_prompt_step(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *prompt, void *stream);
+/* Prompt prefill (an extension): the C >= 1 prompt tokens that ALL rows have (C <= min_b len[b]) computed in one teacher-forced pass by the
+ * caller instead of C prompt steps.  The pass runs B sequences of C tokens - row b's tokens of output indices 0 .. C - 1, index 0 being
+ * <bos> - at positions 1 .. C (quirk Q1) over the rows' memories, at the decoder's precision, and keeps per layer the self-attention
+ * in-projection `qkv` [(b * C + p)][ld] in the decoder's dtype and at the end the logits [(b * C + j)][V] fp32 (row b * C + j scores output
+ * index j + 1).  Then, on one stream:
+ *   acai_decode_prefill_self_kv per layer: k_self / v_self [b][h][p][d] = qkv[b * C + p][E + h * dh + d] / [2E + h * dh + d] for b < B,
+ *     p < C, d < dh.  Nothing else is written (positions >= C, pad columns d >= dh, rows >= B keep their content).  qkv is read in place,
+ *     16 bytes at a time where dh, ld and the addresses allow.  Errors: null qkv, layer outside [0, L), C outside [1, max_len - 1],
+ *     ld < 3E.
+ *   acai_decode_prefill_arm once: seqs[b][0] = <bos>, seqs[b][1 .. C] = tok[b][1 .. C], logprobs[b][j + 1] = (logit[token] - max) -
+ *     logf(sum expf(logit - max)) with acai_decode_prompt_step's reduction and rounding, finished[b] = (tok[b][C] == <eos>), finished[B] =
+ *     the count acai_decode_prompt_step leaves at t = C (a row with C < len[b] is unfinished), step = {C + 1, C}, x[b] =
+ *     vocab_embedding[tok[b][C]] + pos_embedding[C + 1] when C + 1 < Tmax: the state C calls of acai_decode_prompt_step leave, the
+ *     log-probs up to the difference between the pass's logits and the steps'.  acai_decode_prompt_step goes on from t = C + 1.  The
+ *     caller keeps every tok[b][1 .. C] inside [0, V) and C <= len[b]: an entry that is not falls back to that position's own arg-max
+ *     (memory-safe, but not what the steps would have done - there the later positions would have seen the arg-max).  Errors: null
+ *     prompt tables or logits, C outside [1, max_len - 1], prompt->rows < B, prompt->pitch < max_len, V > 512.
+ * Both enqueue one kernel (capturable) and launch nothing when they return an error. */
+int acai_decode_prefill_self_kv(const AcaiDecoder *d, int layer, const void *qkv, int ld, int C, void *stream);
+int acai_decode_prefill_arm(const AcaiDecoder *d, const AcaiPrompt *prompt, const float *logits, int C, void *stream);
 /* Grammar-constrained decoding (an extension: the reference knows no grammar).  A token automaton is a table next[state][token]: an entry
  * >= 0 is the state after emitting that token, an entry < 0 forbids the token in that state.  All arrays are device memory:
  *   next:   [states][V] int16, every non-negative entry < states;
