@@ -278,116 +278,43 @@ def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, s
 def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, assess=None, prune=None, grammar=None, orient=None, deskew=None, flatten=None, rectify=None):
     """Whole pages in, their systems decoded as one batch (an extension; the reference's service crops hand-drawn boxes with PIL and decodes
     them one by one, acai_omr/ui/routes.py:93-129) -> a `page.PageResult`.
-    pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1].  boxes: None - the systems are found on the device
-    (page.detect_systems with the `page.DetectConfig` detect; it assumes roughly level staff lines, and how well it does on real scans has
-    not been measured) - or, per page, a list of pixel boxes (x0, y0, x1, y1) or of the UI's fraction boxes (dicts, or tuples holding
-    floats: page.boxes_from_fractions); for one page the list may be given bare.  resize: the `utils.DynamicResize` every box goes through.
+    pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1]; a decoded colour photo, uint8 (H, W, 3), (H, W, 4) or
+    (3, H, W), is made grey first (page.ingest_pages; float colour input is a TypeError).  boxes: None - the systems are found on the device (page.detect_systems with the
+    `page.DetectConfig` detect, which assumes roughly level staff lines) - or, per page, a list of pixel boxes (x0, y0, x1, y1) or of the
+    UI's fraction boxes (page.pixel_boxes); for one page the list may be given bare.  Boxes and quads a caller supplies refer to the page
+    as the stages before detection leave it: UPRIGHT, rectified, levelled.  resize: the `utils.DynamicResize` every box goes through.
     All systems of all pages are cut out and resized into one packed patch stream by one launch pair (page.split_pages), encoded in chunks
     of the cache's batch size and decoded by continuous batching: the rows are what continuous_inference returns for the resized crops, in
     page order and top to bottom.  max_inference_len, slots, grammar: as in continuous_inference.  A page without systems contributes no
-    rows; with no system at all nothing is launched and the result is empty.
-    deskew (an extension, default None = off: the path above, unchanged): True or a `page.SkewConfig` - every page's skew is estimated on
-    the device (page.estimate_skew) - or one angle in degrees, or a list with one per page.  The pages are turned level before the
-    detection (page.deskew_pages); detection then runs on the levelled pages, and boxes the caller supplies refer to the LEVELLED pages too
-    (pixels of, or fractions of, the page after the turn, which has the size of the page before it).  The result's boxes are in the levelled
-    pages, its `angles` says by how much each was turned, and `to_page_xy` / `box_corners` lead back to the pages as they were passed in.
-    flatten (an extension, default None = off, as is False: the path above, unchanged, no launch added): True or a `page.FlattenConfig` -
-    the uneven illumination of every page is divided out before deskew (page.flatten_pages, two launches per page, no copy to the host);
-    deskew (if asked for), detection and the crops the model reads all see the flattened pages.  Geometry does not change: boxes, angles and
-    the maps back to the page are what they are without it.  The result's `flattened` says which pages were.  Chosen on synthetic shading;
-    not measured on real photographs.
-    rectify (an extension, default None = off, as is False: the path above, unchanged, no launch added, no copy made): True or a
-    `page.RectifyConfig` - the outline of the sheet is found in every page (page.find_page_quad: two launches and one copy to the host per
-    page) - or the corners themselves, one quad [TL, TR, BR, BL] of (x, y) for all pages or a list with one quad or None per page (a UI
-    lets its user tap them).  The sheet is warped flat FIRST (page.rectify_pages, one launch per page): the order is rectify -> flatten
-    -> deskew -> detect, so that flatten and deskew see the sheet and not the table around it.  A page in which no sheet is found, or
-    which the sheet fills, is left as it is.  Boxes the caller supplies refer to the RECTIFIED page, and then the levelled one.  The
-    result's `quads` and `source_sizes` say what was cut from what, `page_sizes` is the size of the rectified pages, and `to_page_xy` /
-    `from_page_xy` / `box_corners` go the whole way back to the pages as they were passed in.  Not handled: page curl, a sheet lighter
-    than its surroundings or cut off by the frame on more than one side.  Chosen on synthetic quadrilaterals over a noise table; not
-    measured on real photographs.
-    orient (an extension, default None = off, as is False: with single-channel pages the path above, unchanged, no launch added): colour
-    input and EXIF / quarter-turn orientation.  A page may then also be a decoded colour photo, uint8 (H, W, 3), (H, W, 4) or (3, H, W)
-    (page.ingest_pages says how shapes are read) - also with orient=None, where it is only made grey - and orient is the photo's EXIF
-    orientation code 1 .. 8, one for all pages or a list with one per page (anything PIL's `ImageOps.exif_transpose` would apply), or
-    True or a `page.OrientConfig`: the tag is missing, and one of the codes 1, 3, 6, 8 is estimated per photo on the device
-    (page.estimate_orientation: sideways from row against column profiles, upside down from the ink at the two ends of the systems - a
-    heuristic chosen on synthetic pages, not measured on real photographs; the EXIF code remains the primary path).  The photo is uploaded
-    as it is and ONE launch per photo makes the grey, upright page (page.ingest_pages) before everything else: the order is ingest ->
-    rectify -> flatten -> deskew -> detect.  The estimate is a function of the photo alone: it is made on a temporary that went through
-    rectify (when the outline is to be found) and flatten if those were asked for, the photo is then ingested with that code and the path
-    above runs, so orient=True gives, bit for bit, what orient=<the estimated codes> gives.  Boxes and quads the caller supplies refer
-    to the UPRIGHT page.  The result's `orientations` says which code every page was turned by, `source_sizes` is the size of the photos
-    as passed in, and `to_page_xy` / `from_page_xy` / `box_corners` go back through the turn to the photo's own pixels.  Anything else for
-    orient is a TypeError, a code outside 1 .. 8 a ValueError.  Not handled: float colour input, mirrored photos without a tag, reading
-    the tag out of a file (PIL or any decoder gives the number), JPEG decoding, folding the quarter turn into the rectification warp.
-    prune (an extension, default None = off, as is False: the path above, unchanged, no launch added): True or a `prune.PruneConfig` - the
-    blank patches of all systems are dropped from the packed stream at once (prune.prune_patches: three launches and one copy of the kept
-    counts to the host for the whole call) before it is encoded; the rows are then what continuous_inference returns for the pruned stream.
-    The result's `patches_kept` / `patches_total` say per system how many patches the model read.  Chosen on synthetic pages; the blank
-    share of real systems and the effect on a trained checkpoint's output have not been measured.
-    assess (an extension, default None = off, as is False: the path above, unchanged, no launch added, no copy made): True or a
-    `page.AssessConfig` - every page is assessed (page.assess_pages: three launches per page and ONE copy to the host for all pages) on
-    the page detection sees, that is after ingest, rectify, flatten and deskew where those are on; flatten comes first so that one ink
-    threshold holds for the whole page.  The result's `quality` holds per page its `page.PageQuality`: the staff scale (line thickness and
-    the distance from staff line to staff line, from vertical run lengths), sharpness, contrast, focus.  Where the scale was found and
-    boxes is None, detection is sized from it - `detect.resolved(H, W, staff_space=scale.pitch_bin)`: the fields of `detect` left at None
-    come from 180 staff spaces in place of the page height, the fields the caller set win as before - so a dense page of small staves,
-    a half-empty page or a sheet that fills half the frame keeps its systems; a page in engraved A4 proportion resolves to what it
-    resolved to anyway.  `system_staff_space` gives per system the staff space in MODEL pixels.  A page that fails a bound the caller set
-    in the `AssessConfig` (all default to None) has `quality[i].ok` False and the reasons in words, and is decoded all the same: this call
-    reports and never drops rows - refusing the photo is the caller's to do, with the reasons in hand.  Rectify and deskew resample
-    bilinearly, which lowers `sharpness` a little, and flatten stretches the levels: values compare only under the same stage settings,
-    and `page.assess_pages` on the raw page judges the photo itself.  Not handled: sizing flatten, deskew or rectify from the scale
-    (they run before it can be measured), horizontal runs, a scale per system, any default threshold; nothing has been measured on real
-    photographs."""
+    rows; with no system at all nothing is encoded or decoded and the result is empty.
+
+    The stages, every one an extension that is off at None or False (the path above, unchanged: no launch added, no copy made), in the
+    order they run.  True: the stage estimates what it needs on the device with its default config; a config: with that one.  Every
+    keyword is checked before anything is uploaded (page.resolve_stage): anything not listed is a TypeError, a code outside 1 .. 8 a
+    ValueError.  The function named last says what the stage does, what it costs and what it does not handle.
+
+      order  keyword  besides None / False / True             adds to the result                               documented at
+      1      orient   page.OrientConfig; one EXIF code        orientations, source_sizes; the maps back reach  page.ingest_pages,
+                      1 .. 8, or a list with one per page     the photo's own pixels                           page.estimate_orientation
+      2      rectify  page.RectifyConfig; one quad [TL, TR,   quads, source_sizes, inset; page_sizes is the    page.rectify_pages,
+                      BR, BL], or a list of quads or None     size of the rectified pages                      page.find_page_quad
+      3      flatten  page.FlattenConfig                      flattened (geometry does not change)             page.flatten_pages
+      4      deskew   page.SkewConfig; one angle in degrees,  angles; boxes are in the levelled pages          page.deskew_pages,
+                      or a list with one per page                                                              page.estimate_skew
+      5      assess   page.AssessConfig                       quality, system_staff_space; with boxes=None     page.assess_pages,
+                                                              detection is sized from the staff scale          page.DetectConfig.resolved
+      6      prune    prune.PruneConfig                       patches_kept below patches_total                 prune.prune_patches
+
+    Stages 1 - 4 are page.prepare_pages, so the order is ingest -> rectify -> flatten -> deskew -> detect; 5 measures the pages detection sees and never drops a row; 6 acts on the packed patches of all
+    systems at once.  `PageResult.to_page_xy` / `from_page_xy` / `box_corners` go back through 4, 2 and 1 to the pages as they were passed
+    in.  orient=True gives, bit for bit, what orient=<the estimated codes> gives.  The defaults of every config were chosen on synthetic
+    pages and not measured on real photographs (there are none in this repository)."""
     from .. import page as pg
     from ..prune import as_config
-    prune = as_config(prune)
-    if assess is not None and assess is not False and assess is not True and not isinstance(assess, pg.AssessConfig):
-        raise TypeError("assess: expected None, a bool or a page.AssessConfig")
-    assess = None if assess is None or assess is False else (pg.AssessConfig() if assess is True else assess)
-    pages, boxes = pg._page_lists(pages, boxes)
-    if boxes is not None and len(boxes) != len(pages):
-        raise ValueError(f"{len(pages)} pages but boxes for {len(boxes)}")
-    oriented = {}
-    if orient is None or orient is False:
-        pages = pg.ingest_pages(pages, None, device=resize.device)      # (single-channel pages: `pg._device_page` of each, nothing else)
-    else:
-        estimate = orient is True or isinstance(orient, pg.OrientConfig)
-        if not estimate and (isinstance(orient, bool) or not isinstance(orient, (int, list, tuple))):
-            raise TypeError("orient: expected None, a bool, a page.OrientConfig, one EXIF orientation code 1 .. 8 or a list with one per page")
-        codes = None if estimate else pg.orientation_codes(orient, len(pages))
-        photos = [pg._device_photo(p, resize.device) for p in pages]
-        if estimate:
-            codes = []
-            for tmp in pg.ingest_pages(photos):
-                if rectify is True or isinstance(rectify, pg.RectifyConfig):
-                    tmp = pg.rectify_pages(tmp, None, rectify if isinstance(rectify, pg.RectifyConfig) else None)[0][0]
-                if flatten is True or isinstance(flatten, pg.FlattenConfig):
-                    tmp = pg.flatten_pages(tmp, None if flatten is True else flatten)[0]
-                codes.append(pg.estimate_orientation(tmp, orient if isinstance(orient, pg.OrientConfig) else None)[0])
-        oriented = dict(orientations=codes, source_sizes=[pg.photo_size(p) for p in photos])
-        pages = pg.ingest_pages(photos, codes)
-    angles, flattened, rectified = None, None, {}
-    if rectify is not None and rectify is not False:
-        find = rectify is True or isinstance(rectify, pg.RectifyConfig)
-        if not find and not (pg._is_quad(rectify) or (isinstance(rectify, (list, tuple)) and all(q is None or pg._is_quad(q) for q in rectify))):
-            raise TypeError("rectify: expected None, a bool, a page.RectifyConfig, one quad [TL, TR, BR, BL] or a list of quads (or None) per page")
-        cfg = rectify if isinstance(rectify, pg.RectifyConfig) else pg.RectifyConfig()
-        source_sizes = [tuple(p.shape) for p in pages]
-        pages, quads = pg.rectify_pages(pages, None if find else rectify, cfg)
-        rectified = dict(quads=quads, source_sizes=source_sizes, inset=cfg.inset)
-    if flatten is not None and flatten is not False:
-        if flatten is not True and not isinstance(flatten, pg.FlattenConfig):
-            raise TypeError("flatten: expected None, a bool or a page.FlattenConfig")
-        pages = pg.flatten_pages(pages, None if flatten is True else flatten)
-        flattened = [True] * len(pages)
-    if deskew is not None and deskew is not False:
-        estimate = deskew is True or isinstance(deskew, pg.SkewConfig)
-        pages, angles = pg.deskew_pages(pages, None if estimate else deskew, deskew if isinstance(deskew, pg.SkewConfig) else None)
-    turned = dict(angles=angles, page_sizes=[tuple(p.shape) for p in pages], flattened=flattened, **{**rectified, **oriented})
-    scales = None
+    prune, (assess, _) = as_config(prune), pg.resolve_stage("assess", assess)
+    pages, boxes = pg.page_lists(pages, boxes)
+    pages, prepared = pg.prepare_pages(pages, resize.device, orient=orient, rectify=rectify, flatten=flatten, deskew=deskew)
+    extra, scales = dict(vars(prepared)), None
     if assess is not None and pages:
         measured = pg.assess_counts(pages, assess)          # the launches and the one copy; the gate waits for the systems' sizes
         scales = [pg.choose_staff_scale(hists, assess) for hists, _, _ in measured]
@@ -395,18 +322,16 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
         per_page = [pg.detect_systems(p, detect) if scales is None or scales[i] is None else pg.detect_systems(p, detect, scales[i].pitch_bin)
                     for i, p in enumerate(pages)]
     else:
-        per_page = [pg.boxes_from_fractions(b, *p.shape) if b and pg._is_fraction_box(b[0]) else [pg._pixel_box(x, *p.shape) for x in b]
-                    for p, b in zip(pages, boxes)]
+        per_page = [pg.pixel_boxes(b, *p.shape) for p, b in zip(pages, boxes)]
     plans = pg.plan_systems([tuple(p.shape) for p in pages], per_page, resize)
     system_page, sizes, windows = [p for p, *_ in plans], [s for _, _, s, _ in plans], [c for *_, c in plans]
-    dec = vitomr.decoder
-    specials = [getattr(dec, n) for n in ("bos_idx", "eos_idx", "pad_idx") if hasattr(dec, n)]
+    specials = [getattr(vitomr.decoder, n) for n in ("bos_idx", "eos_idx", "pad_idx") if hasattr(vitomr.decoder, n)]
     if scales is not None:
         spaces = pg.system_staff_spaces(scales, plans)
         smallest = [min((v for v, (p, *_) in zip(spaces, plans) if p == i and v is not None), default=None) for i in range(len(pages))]
-        turned.update(quality=[pg.page_quality(*m, assess, small) for m, small in zip(measured, smallest)], system_staff_space=spaces)
+        extra.update(quality=[pg.page_quality(*m, assess, small) for m, small in zip(measured, smallest)], system_staff_space=spaces)
     if not plans:
-        return pg.PageResult(per_page, None, None, None, [], [], [], specials, **turned)
+        return pg.PageResult(per_page, None, None, None, [], [], [], specials, **extra)
     vitomr.eval()
     with torch.no_grad():
         packed = pg.split_pages(pages, per_page, resize)
@@ -417,7 +342,7 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
             seqs, lps, mask = vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
-    return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, patches_kept=packed.lens, patches_total=total, **turned)
+    return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, patches_kept=packed.lens, patches_total=total, **extra)
 
 
 def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None, *, grammar=None, prefill=False):

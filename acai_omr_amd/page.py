@@ -24,9 +24,12 @@ average confidence (acai_omr/ui/routes.py: `setup_inference` :108-129, `multiple
                             to line from the histograms of vertical run lengths, sharpness and contrast from the levels and their
                             Laplacian (ops.page_runs, ops.page_sharpness; the reference measures nothing) - detection is then sized
                             from the music instead of the canvas, and a caller can refuse a photo that cannot be read;
+  * `prepare_pages`         the stages above that change the page, in their one order ingest -> rectify -> flatten -> deskew, each keyword
+                            read by the one rule of `resolve_stage`; returns the pages detection sees and the `Prepared` record;
   * `split_pages`           every box of every page cut out, resized as `DynamicResize` resizes the crop and written into ONE
                             `PackedPatches` by one launch pair (ops.crop_resize_to_patches) - no crop copies, no per-system launches;
-  * `PageResult`            the per-system rows of the decode, joined per page as the service joins them.
+  * `PageResult`            the per-system rows of the decode, joined per page as the service joins them, and per page the chain of
+                            `PointMap`s (turn, homography, orientation) that leads from what was cropped back to the photo.
 
 `inference.vitomr_inference.page_inference` strings them together.  There is no CPU fallback.
 
@@ -92,9 +95,10 @@ default to None: no threshold is invented here, because nothing in this reposito
 deskew or rectify from the scale (they run before it can be measured), horizontal runs, a scale per system, any default threshold.
 Nothing has been measured on real photographs (no such data here).
 """
+import functools
 import math
 from dataclasses import dataclass
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -102,6 +106,11 @@ from ._lib import EXTENTS_MAX_RUN, FLATTEN_TILES, PAGE_MAX_H, PAGE_MAX_W
 from .utils import PackedPatches, stringify_lmx_seq
 
 NO_GPU = "acai_omr_amd page input runs on the GPU (HIP page kernels); there is no CPU fallback"
+
+
+def _num(v):
+    """A real number: an int or a float, not a bool and not NaN."""
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and v == v
 
 
 @dataclass
@@ -224,7 +233,7 @@ def skew_scores(pages, cfg=None):
     table is uploaded once."""
     from . import ops
     cfg = cfg or SkewConfig()
-    pages, _ = _page_lists(pages, None)
+    pages, _ = page_lists(pages, None)
     pages = [_device_page(p) for p in pages]
     if not pages:
         raise ValueError("skew_scores: no pages")
@@ -248,7 +257,7 @@ def deskew_pages(pages, angles=None, cfg=None, fill=None):
     list with one per page.  Every page is turned by its angle (ops.page_rotate; fill: what lies outside the page, default the paper); an
     angle of exactly 0.0 returns the page itself (on the device), with no launch."""
     from . import ops
-    pages, _ = _page_lists(pages, None)
+    pages, _ = page_lists(pages, None)
     pages = [_device_page(p) for p in pages]
     if angles is None:
         angles = estimate_skew(pages, cfg) if pages else []
@@ -308,7 +317,7 @@ def flatten_pages(pages, cfg=None):
     per page (ops.page_tile_levels, ops.page_flatten), nothing comes back to the host."""
     from . import ops
     cfg = cfg or FlattenConfig()
-    pages, _ = _page_lists(pages, None)
+    pages, _ = page_lists(pages, None)
     out = []
     for p in (_device_page(p) for p in pages):
         tile, percent, rq, floor = cfg.resolved(p.shape[0])
@@ -345,18 +354,17 @@ class RectifyConfig:
         self.check()
 
     def check(self):
-        num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v   # noqa: E731
-        if not num(self.paper_threshold):
+        if not _num(self.paper_threshold):
             raise ValueError(f"RectifyConfig: paper_threshold = {self.paper_threshold!r} is not a number")
         if self.min_run is not None and (isinstance(self.min_run, bool) or not isinstance(self.min_run, int) or not 1 <= self.min_run <= EXTENTS_MAX_RUN):
             raise ValueError(f"RectifyConfig: min_run = {self.min_run!r} is not None or an integer in 1 .. {EXTENTS_MAX_RUN}")
-        if not num(self.tol) or not self.tol > 0:
+        if not _num(self.tol) or not self.tol > 0:
             raise ValueError(f"RectifyConfig: tol = {self.tol!r} is not a positive number")
         if isinstance(self.min_points, bool) or not isinstance(self.min_points, int) or self.min_points < 2:
             raise ValueError(f"RectifyConfig: min_points = {self.min_points!r} is not an integer >= 2")
-        if not num(self.min_area) or not 0 <= self.min_area <= 1:
+        if not _num(self.min_area) or not 0 <= self.min_area <= 1:
             raise ValueError(f"RectifyConfig: min_area = {self.min_area!r} is not a share in 0 .. 1")
-        if not num(self.inset) or not 0 <= self.inset <= 1024:
+        if not _num(self.inset) or not 0 <= self.inset <= 1024:
             raise ValueError(f"RectifyConfig: inset = {self.inset!r} is not a number in 0 .. 1024")
         if self.out_size is not None:
             ok = isinstance(self.out_size, (tuple, list)) and len(self.out_size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in self.out_size)
@@ -471,7 +479,7 @@ def rectify_pages(pages, quads=None, cfg=None, fill=None):
     from . import ops
     cfg = cfg or RectifyConfig()
     cfg.check()
-    pages, _ = _page_lists(pages, None)
+    pages, _ = page_lists(pages, None)
     pages = [_device_page(p) for p in pages]
     if quads is None:
         quads = [find_page_quad(p, cfg) for p in pages]
@@ -513,14 +521,13 @@ class OrientConfig:
         self.check()
 
     def check(self):
-        num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v   # noqa: E731
-        if not num(self.ink_threshold):
+        if not _num(self.ink_threshold):
             raise ValueError(f"OrientConfig: ink_threshold = {self.ink_threshold!r} is not a number")
-        if not num(self.line_frac) or not 0 < self.line_frac <= 1:
+        if not _num(self.line_frac) or not 0 < self.line_frac <= 1:
             raise ValueError(f"OrientConfig: line_frac = {self.line_frac!r} is not a share in 0 .. 1")
         if isinstance(self.min_line_rows, bool) or not isinstance(self.min_line_rows, int) or self.min_line_rows < 1:
             raise ValueError(f"OrientConfig: min_line_rows = {self.min_line_rows!r} is not an integer >= 1")
-        if not num(self.end_frac) or not 0 < self.end_frac <= 0.5:
+        if not _num(self.end_frac) or not 0 < self.end_frac <= 0.5:
             raise ValueError(f"OrientConfig: end_frac = {self.end_frac!r} is not a share in 0 .. 0.5")
         if self.detect is not None and not isinstance(self.detect, DetectConfig):
             raise ValueError(f"OrientConfig: detect = {self.detect!r} is not None or a DetectConfig")
@@ -584,8 +591,7 @@ class AssessConfig:
         self.check()
 
     def check(self):
-        num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v   # noqa: E731
-        if not num(self.ink_threshold):
+        if not _num(self.ink_threshold):
             raise ValueError(f"AssessConfig: ink_threshold = {self.ink_threshold!r} is not a number")
         for name in ("paper_percent", "ink_percent"):
             v = getattr(self, name)
@@ -593,7 +599,7 @@ class AssessConfig:
                 raise ValueError(f"AssessConfig: {name} = {v!r} is not an integer in 1 .. 100")
         for name in _GATES:
             v = getattr(self, name)
-            if v is not None and (not num(v) or v < 0 or v == float("inf")):
+            if v is not None and (not _num(v) or v < 0 or v == float("inf")):
                 raise ValueError(f"AssessConfig: {name} = {v!r} is not None or a finite number >= 0")
         if self.min_scale_confidence is not None and self.min_scale_confidence > 1:
             raise ValueError(f"AssessConfig: min_scale_confidence = {self.min_scale_confidence!r} is not a share in 0 .. 1")
@@ -701,7 +707,7 @@ def _assess_launch(pages, cfg, sharp):
     `sharp`, the launch of `ops.page_sharpness`."""
     from . import ops
     from ._lib import RUNS_WORDS, SHARP_WORDS
-    pages, _ = _page_lists(pages, None)
+    pages, _ = page_lists(pages, None)
     pages = [_device_page(p) for p in pages]
     if not pages:
         raise ValueError("no pages")
@@ -790,7 +796,7 @@ def ingest_pages(pages, orientation=None, layout=None, device=None):
     uploaded once, in the layout it arrived in: the grey value (PIL's `convert("L")`) and the turn are ONE launch per photo on the device
     (ops.page_ingest).  A single-channel page with code 1 is returned as `_device_page` returns it: no launch, no copy."""
     from . import ops
-    pages, _ = _page_lists(pages, None)
+    pages, _ = page_lists(pages, None)
     codes = orientation_codes(orientation, len(pages))
     out = []
     for p, c in zip(pages, codes):
@@ -895,21 +901,28 @@ def boxes_from_fractions(boxes, H, W):
             for x0, y0, x1, y1 in sorted(rows, key=lambda r: r[1])]
 
 
-def _is_fraction_box(b):
-    return isinstance(b, dict) or any(isinstance(v, float) for v in b)
+def pixel_boxes(boxes, H, W):
+    """One page's boxes as a caller gives them - the UI's fraction boxes (the first is a dict, or holds a float: `boxes_from_fractions`)
+    or pixel boxes (x0, y0, x1, y1) - -> pixel boxes of the H x W page, each checked to be non-empty and inside it."""
+    fractions = bool(boxes) and (isinstance(boxes[0], dict) or any(isinstance(v, float) for v in boxes[0]))
+    return boxes_from_fractions(boxes, H, W) if fractions else [_pixel_box(b, H, W) for b in boxes]
 
 
 def _is_box(b):
     return isinstance(b, dict) or (isinstance(b, (list, tuple)) and len(b) == 4 and not isinstance(b[0], (list, tuple, dict)))
 
 
-def _page_lists(pages, boxes):
-    """One page (with its boxes as one list) or a list of pages (with one list of boxes per page) -> the list form of both."""
+def page_lists(pages, boxes):
+    """One page (with its boxes as one list) or a list of pages (with one list of boxes per page) -> the list form of both; boxes (where
+    there are any) for another number of pages: ValueError."""
     if torch.is_tensor(pages):
         pages = [pages]
         if boxes is not None and (len(boxes) == 0 or _is_box(boxes[0])):
             boxes = [boxes]
-    return list(pages), boxes
+    pages = list(pages)
+    if boxes is not None and len(boxes) != len(pages):
+        raise ValueError(f"{len(pages)} pages but boxes for {len(boxes)}")
+    return pages, boxes
 
 
 def plan_systems(pages_hw, boxes_per_page, resize):
@@ -929,9 +942,7 @@ def split_pages(pages, boxes_per_page, resize, dtype=torch.float32):
     and then in the order given; its rows are, bit for bit, those of `resize.to_patches([page[y0:y1, x0:x1], ...])`.  One table upload and
     one `ops.crop_resize_to_patches` call (two launches) for everything."""
     from . import ops
-    pages, boxes_per_page = _page_lists(pages, boxes_per_page)
-    if len(pages) != len(boxes_per_page):
-        raise ValueError(f"{len(pages)} pages but boxes for {len(boxes_per_page)}")
+    pages, boxes_per_page = page_lists(pages, boxes_per_page)
     pages = [_device_page(p, resize.device) for p in pages]
     plans = plan_systems([tuple(p.shape) for p in pages], boxes_per_page, resize)
     if not plans:
@@ -946,6 +957,122 @@ def split_pages(pages, boxes_per_page, resize, dtype=torch.float32):
         tmp_off += (y1 - y0) * size[1]
     ops.crop_resize_to_patches(entries, out, P, clamp01=True)
     return PackedPatches(out, dims, P)
+
+
+_STAGES = {   # keyword of `page_inference` -> (its config, the test for values given in place of an estimate, those values in words)
+    "orient": (OrientConfig, lambda v: not isinstance(v, bool) and isinstance(v, (int, list, tuple)), "one EXIF orientation code 1 .. 8 or a list with one per page"),
+    "rectify": (RectifyConfig, lambda v: _is_quad(v) or (isinstance(v, (list, tuple)) and all(q is None or _is_quad(q) for q in v)),
+                "one quad [TL, TR, BR, BL] or a list of quads (or None) per page"),
+    "flatten": (FlattenConfig, None, None),
+    "deskew": (SkewConfig, lambda v: _num(v) or (isinstance(v, (list, tuple)) and all(_num(a) for a in v)), "one angle in degrees or a list with one per page"),
+    "assess": (AssessConfig, None, None)}
+
+
+def resolve_stage(name, value):
+    """The one rule for a stage keyword of `page_inference` -> (cfg, values).  None or False: (None, None), the stage is off.  True or an
+    instance of the stage's config: (that config, None), the stage estimates with it.  What the stage's own test accepts - codes for
+    orient (a bool is not a code), quads for rectify, angles for deskew: (the default config, the value), the stage applies the caller's
+    values.  Anything else: TypeError.  Nothing is uploaded or launched; what is wrong with a number (a code outside 1 .. 8) is a
+    ValueError from where the number is read."""
+    Config, explicit, what = _STAGES[name]
+    if value is None or value is False:
+        return None, None
+    if value is True or isinstance(value, Config):
+        return (Config() if value is True else value), None
+    if explicit is not None and explicit(value):
+        return Config(), value
+    raise TypeError(f"{name}: expected None, a bool{', ' if what else ' or '}a page.{Config.__name__}{', ' + what if what else ''}")
+
+
+@dataclass
+class Prepared:
+    """What `prepare_pages` did to the pages, field for field what `PageResult` takes and documents under the same names
+    (`PageResult(..., **vars(prepared))`).  A stage that was off leaves its field at None."""
+    orientations: Optional[list]
+    source_sizes: list
+    quads: Optional[list]
+    inset: float
+    flattened: Optional[list]
+    angles: Optional[list]
+    page_sizes: list
+
+
+def prepare_pages(pages, device=None, *, orient=None, rectify=None, flatten=None, deskew=None):
+    """One page or a list, as `page_inference` takes them -> (the pages detection sees, on the device; the `Prepared` record).  The opt-in
+    stages in their one order, ingest -> rectify -> flatten -> deskew (`ingest_pages`, `rectify_pages`, `flatten_pages`, `deskew_pages`
+    say what each does and costs), every keyword by `resolve_stage`, all of them before the first upload.  With every stage off this is
+    `ingest_pages(pages, None, device=device)` and nothing else.  orient=True estimates the code of every photo on a temporary
+    (`estimate_orientation`) and then runs as orient=<those codes>: the same result, bit for bit."""
+    (orient, codes), (rectify, quads) = resolve_stage("orient", orient), resolve_stage("rectify", rectify)
+    (flatten, _), (deskew, angles) = resolve_stage("flatten", flatten), resolve_stage("deskew", deskew)
+    pages, _ = page_lists(pages, None)
+    if orient is None:
+        pages = ingest_pages(pages, None, device=device)      # (single-channel pages: `_device_page` of each, nothing else)
+        source_sizes = [tuple(p.shape) for p in pages]
+    else:
+        codes = None if codes is None else orientation_codes(codes, len(pages))
+        photos = [_device_photo(p, device) for p in pages]
+        if codes is None:
+            codes = []
+            for tmp in ingest_pages(photos):
+                if rectify is not None and quads is None:     # a quad the caller gave refers to the upright page: the temporary is not it
+                    tmp = rectify_pages(tmp, None, rectify)[0][0]
+                if flatten is not None:
+                    tmp = flatten_pages(tmp, flatten)[0]
+                codes.append(estimate_orientation(tmp, orient)[0])
+        source_sizes = [photo_size(p) for p in photos]
+        pages = ingest_pages(photos, codes)
+    if rectify is not None:
+        pages, quads = rectify_pages(pages, quads, rectify)
+    if flatten is not None:
+        pages = flatten_pages(pages, flatten)
+    if deskew is not None:
+        pages, angles = deskew_pages(pages, angles, deskew)
+    return pages, Prepared(orientations=codes, source_sizes=source_sizes, quads=quads, inset=2 if rectify is None else rectify.inset,
+                           flattened=None if flatten is None else [True] * len(pages), angles=angles, page_sizes=[tuple(p.shape) for p in pages])
+
+
+class PointMap(NamedTuple):
+    """One link of the way from the page that was cropped back to the photo, a pair of functions of a point: `back(x, y)` leads towards
+    the photo, `forth(x, y)` is its inverse.  `PageResult` keeps a list of them per page; a new stage that moves pixels adds one."""
+    back: Callable
+    forth: Callable
+
+
+def turn_map(angle, size):
+    """The turn that levelled an (H, W) = size page, as the kernel applied it: cos_q / 65536, sin_q / 65536 about the centre.  `back` takes a
+    point of the levelled page to the page that was turned; `forth` is the exact inverse of that matrix (cos^2 + sin^2 is 1 only to 2^-16)."""
+    from .ops import rotation_q16
+    cos_q, sin_q = rotation_q16(angle)
+    c, s, cx, cy = cos_q / 65536.0, sin_q / 65536.0, (size[1] - 1) / 2.0, (size[0] - 1) / 2.0
+    det = c * c + s * s
+    return PointMap(lambda x, y: (cx + c * (x - cx) - s * (y - cy), cy + s * (x - cx) + c * (y - cy)),
+                    lambda x, y: (cx + (c * (x - cx) + s * (y - cy)) / det, cy + (c * (y - cy) - s * (x - cx)) / det))
+
+
+def _project(m, x, y):
+    den = m[6] * x + m[7] * y + m[8]
+    return (m[0] * x + m[1] * y + m[2]) / den, (m[3] * x + m[4] * y + m[5]) / den
+
+
+def homography_map(quad, size, inset):
+    """The homography a page of (OH, OW) = size was rectified through: the nine integers of `ops.homography_q30(quad, size, inset)`, formed
+    when a point is first mapped.  `back` takes a point of the rectified page to the page it was sampled from, in float64 (the kernel's own
+    source coordinate is this, rounded down to 1 / 256 pixel); `forth` applies the adjugate of the integer matrix, formed exactly and
+    scaled by its largest entry, in float64."""
+    @functools.lru_cache(maxsize=None)
+    def matrices():
+        from .ops import homography_q30
+        A, B, C, D, E, F, G, H, I = m = homography_q30(quad, size, inset)   # noqa: E741
+        adj = [E * I - F * H, C * H - B * I, B * F - C * E, F * G - D * I, A * I - C * G, C * D - A * F, D * H - E * G, B * G - A * H, A * E - B * D]
+        big = max(abs(v) for v in adj) or 1
+        return [float(v) for v in m], [v / big for v in adj]   # (int / int: correctly rounded whatever the size)
+    return PointMap(lambda x, y: _project(matrices()[0], x, y), lambda x, y: _project(matrices()[1], x, y))
+
+
+def orientation_map(code, size):
+    """The index map of orientation `code` on an (H, W) = size photo (`orientation_to_photo_xy` and its inverse): integers stay integers."""
+    return PointMap(functools.partial(orientation_to_photo_xy, code, size), functools.partial(orientation_from_photo_xy, code, size))
 
 
 class PageResult:
@@ -993,7 +1120,6 @@ class PageResult:
         if len(self.quads) != len(boxes) or (self.source_sizes is not None and len(self.source_sizes) != len(boxes)) or (
                 any(q is not None for q in self.quads) and (page_sizes is None or len(page_sizes) != len(boxes))):
             raise ValueError("PageResult: one quad (or None) and one source size per page, and the page sizes with them when a page was rectified")
-        self._coef = {}
         self.flattened = [False] * len(boxes) if flattened is None else [bool(f) for f in flattened]
         if len(self.flattened) != len(boxes):
             raise ValueError("PageResult: one flattened flag per page")
@@ -1010,6 +1136,12 @@ class PageResult:
         self.system_page, self.sizes, self.windows = list(system_page), list(sizes), list(windows)
         self.specials = tuple(specials)   # the ids of <bos>, <eos>, <pad>: what tokens() leaves out
         self._flat = [b for page in boxes for b in page]
+        self._maps = []   # per page its `PointMap`s, from the page that was cropped back to the photo; a stage that did nothing has none
+        for p, (a, q, c) in enumerate(zip(self.angles, self.quads, self.orientations)):
+            chain = [turn_map(a, self.page_sizes[p])] if a != 0.0 else []
+            chain += [homography_map(q, self.page_sizes[p], inset)] if q is not None else []
+            chain += [orientation_map(c, self.source_sizes[p])] if c != 1 else []
+            self._maps.append(chain)
 
     def __len__(self):
         return len(self.system_page)
@@ -1053,88 +1185,37 @@ class PageResult:
         (OH, OW), (top, left, _, _) = self.sizes[system], self.windows[system]
         return x0, y0, (x1 - x0) / OW, (y1 - y0) / OH, top, left
 
-    def _rotation(self, page):
-        """(cos, sin, cx, cy) of the turn that levelled `page`, as the kernel applied it (cos_q / 65536, sin_q / 65536 about the centre), or
-        None for a page that was not turned."""
-        if self.angles[page] == 0.0:
-            return None
-        from .ops import rotation_q16
-        cos_q, sin_q = rotation_q16(self.angles[page])
-        H, W = self.page_sizes[page]
-        return cos_q / 65536.0, sin_q / 65536.0, (W - 1) / 2.0, (H - 1) / 2.0
+    def to_source_xy(self, page, x, y):
+        """A point of `page` as it was cropped (where `boxes` lie) -> the point of the page or photo the caller passed in: the page's maps
+        backwards, one after the other - the turn, the homography, the orientation.  A page that only had its orientation changed keeps
+        integers integers (a pixel for a pixel)."""
+        for m in self._maps[page]:
+            x, y = m.back(x, y)
+        return x, y
 
-    def _unlevel(self, page, lx, ly):
-        """A point of the levelled page -> the point of the page that was turned (the rectified page, or the caller's) it was sampled from."""
-        rot = self._rotation(page)
-        if rot is None:
-            return lx, ly
-        c, s, cx, cy = rot
-        return cx + c * (lx - cx) - s * (ly - cy), cy + s * (lx - cx) + c * (ly - cy)
+    _to_source = to_source_xy   # the name this map had while it was private: kept for callers written against it
 
-    def _homography(self, page):
-        """The nine integers the kernel rectified `page` with, or None for a page that was not rectified."""
-        if self.quads[page] is None:
-            return None
-        if page not in self._coef:
-            from .ops import homography_q30
-            self._coef[page] = homography_q30(self.quads[page], self.page_sizes[page], self.inset)
-        return self._coef[page]
-
-    def _unrectify(self, page, rx, ry):
-        """A point of the rectified page -> the point of the caller's page it was sampled from: the quantised homography in float64 (the
-        kernel's own source coordinate is this, rounded down to 1 / 256 pixel)."""
-        m = self._homography(page)
-        if m is None:
-            return rx, ry
-        A, B, C, D, E, F, G, H, I = (float(v) for v in m)   # noqa: E741
-        den = G * rx + H * ry + I
-        return (A * rx + B * ry + C) / den, (D * rx + E * ry + F) / den
-
-    def _rectify(self, page, px, py):
-        """The inverse of `_unrectify`: the adjugate of the integer matrix, formed exactly, applied in float64."""
-        m = self._homography(page)
-        if m is None:
-            return px, py
-        A, B, C, D, E, F, G, H, I = m   # noqa: E741
-        adj = [E * I - F * H, C * H - B * I, B * F - C * E, F * G - D * I, A * I - C * G, C * D - A * F, D * H - E * G, B * G - A * H, A * E - B * D]
-        big = max(abs(v) for v in adj) or 1
-        a, b, c, d, e, f, g, h, i = (v / big for v in adj)   # (int / int: correctly rounded whatever the size)
-        den = g * px + h * py + i
-        return (a * px + b * py + c) / den, (d * px + e * py + f) / den
-
-    def _unorient(self, page, ux, uy):
-        """A point of the upright page -> the point of the photo it was read from (`orientation_to_photo_xy`)."""
-        code = self.orientations[page]
-        return (ux, uy) if code == 1 else orientation_to_photo_xy(code, self.source_sizes[page], ux, uy)
-
-    def _to_source(self, page, lx, ly):
-        return self._unorient(page, *self._unrectify(page, *self._unlevel(page, lx, ly)))
+    def from_source_xy(self, page, x, y):
+        """The inverse of `to_source_xy`: the same maps forwards, last first."""
+        for m in reversed(self._maps[page]):
+            x, y = m.forth(x, y)
+        return x, y
 
     def to_page_xy(self, system, x, y):
         """Pixel (x, y) of the tensor the model saw of `system` (its box resized, then cropped to the window) -> pixels (floats) of the page
         the caller passed in: the resize's own map, source = (resized + 0.5) * scale - 0.5 per axis (align_corners = False), shifted by the
-        window and the box, then - for a page that was deskewed - the turn that levelled it, backwards, then - for a page that was
-        rectified - the homography it was sampled through, then - for a photo that was turned upright - its orientation's index map, to
-        the pixels of the photo as it lay.  With it a `TokenAlignment` of the system can be drawn on the page."""
+        window and the box, then `to_source_xy`.  With it a `TokenAlignment` of the system can be drawn on the page."""
         x0, y0, sx, sy, top, left = self._affine(system)
-        return self._to_source(self.system_page[system], x0 + (x + left + 0.5) * sx - 0.5, y0 + (y + top + 0.5) * sy - 0.5)
+        return self.to_source_xy(self.system_page[system], x0 + (x + left + 0.5) * sx - 0.5, y0 + (y + top + 0.5) * sy - 0.5)
 
     def from_page_xy(self, system, px, py):
         """The inverse of `to_page_xy`."""
         x0, y0, sx, sy, top, left = self._affine(system)
-        code = self.orientations[self.system_page[system]]
-        if code != 1:
-            px, py = orientation_from_photo_xy(code, self.source_sizes[self.system_page[system]], px, py)
-        px, py = self._rectify(self.system_page[system], px, py)
-        rot = self._rotation(self.system_page[system])
-        if rot is not None:   # the exact inverse of the quantised matrix (cos^2 + sin^2 is 1 only to 2^-16)
-            c, s, cx, cy = rot
-            det, dx, dy = c * c + s * s, px - cx, py - cy
-            px, py = cx + (c * dx + s * dy) / det, cy + (c * dy - s * dx) / det
+        px, py = self.from_source_xy(self.system_page[system], px, py)
         return (px - x0 + 0.5) / sx - 0.5 - left, (py - y0 + 0.5) / sy - 0.5 - top
 
     def box_corners(self, system):
         """The corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of `system`'s box in the page the caller passed in: the box itself for a page
         that was neither rectified nor deskewed, a quadrilateral otherwise (for a UI to draw)."""
         x0, y0, x1, y1 = self._flat[system]
-        return [self._to_source(self.system_page[system], float(x), float(y)) for x, y in ((x0, y0), (x1, y0), (x1, y1), (x0, y1))]
+        return [self.to_source_xy(self.system_page[system], float(x), float(y)) for x, y in ((x0, y0), (x1, y0), (x1, y1), (x0, y1))]

@@ -336,9 +336,9 @@ def test_page_inference_orient(dev, e2e, code):
     lum = G.grey(photo_np)
     upright = G.grey(colour)
     for x, y in ((x0, y0), (x1 - 1, y0), (x1 - 1, y1 - 1), (x0, y1 - 1), (14 + G.CLEF_X, 40), (14 + G.CLEF_X + 2, 44)):      # the last two: in the first clef
-        px, py = res._to_source(0, x, y)
+        px, py = res.to_source_xy(0, x, y)
         assert lum[py, px] == upright[y, x]
-    cx, cy = res._to_source(0, 14 + G.CLEF_X, 40)
+    cx, cy = res.to_source_xy(0, 14 + G.CLEF_X, 40)
     assert lum[cy, cx] < 100 and res.from_page_xy(0, *res.to_page_xy(0, 5.0, 3.0)) == pytest.approx((5.0, 3.0), abs=1e-9)
     # the estimate: a pure function photo -> code, so orient=True is orient=<the estimated codes>, bit for bit
     est = page_inference(m, [photo, torch.from_numpy(colour)], "cuda", tr, max_inference_len=12, orient=True)

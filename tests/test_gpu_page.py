@@ -360,6 +360,27 @@ def test_page_inference_detects(dev, e2e):
     assert len(page_inference(m, blank, "cuda", tr, boxes=[], max_inference_len=12)) == 0
 
 
+def test_page_inference_prepares_pages_in_the_order_of_the_stages_run_by_hand(dev, e2e):
+    """Every stage on, on a photo of the sheet on a table that lies on its side: ingest -> rectify -> flatten -> deskew, then assess and
+    detect, is what the public stage functions give when they are called one after the other in that order."""
+    import ingest_reference as G
+    from test_gpu_ingest import _framed_clef_frame
+    from acai_omr_amd.inference.vitomr_inference import page_inference
+    from acai_omr_amd.page import deskew_pages, flatten_pages, ingest_pages, rectify_pages
+    m, tr = e2e[:2]
+    photo = torch.from_numpy(G.orient(_framed_clef_frame(), G.INVERSE[6]))        # the photo that code 6 turns upright
+    want = page_inference(m, photo, "cuda", tr, max_inference_len=12, orient=6, rectify=True, flatten=True, deskew=True, assess=True)
+    rect, quads = rectify_pages(ingest_pages(photo, 6))
+    level, angles = deskew_pages(flatten_pages(rect))
+    hand = page_inference(m, level[0], "cuda", tr, max_inference_len=12, assess=True)
+    print(f"{len(want)} systems, quad {quads[0]}, angle {angles[0]}")
+    assert len(want) > 0 and quads[0] is not None                                  # rows to compare, and a sheet that was found
+    assert torch.equal(want.seqs, hand.seqs) and torch.equal(want.log_probs, hand.log_probs) and torch.equal(want.seq_mask, hand.seq_mask)
+    assert want.boxes == hand.boxes and want.quality == hand.quality and want.system_staff_space == hand.system_staff_space
+    assert want.quads == quads and want.angles == angles and want.page_sizes == [tuple(level[0].shape)] and want.flattened == [True]
+    assert want.source_sizes == [tuple(photo.shape)] and want.orientations == [6]
+
+
 def test_page_inference_with_a_permissive_grammar(dev, e2e):
     from acai_omr_amd.grammar import TokenAutomaton
     from acai_omr_amd.inference.vitomr_inference import page_inference

@@ -140,7 +140,7 @@ def test_page_result_maps_through_an_orientation(code):
     x0, y0, x1, y1 = res.boxes[0][0]
     corners = [(x0, y0), (x1 - 1, y0), (x1 - 1, y1 - 1), (x0, y1 - 1)]       # the four corner PIXELS of the box
     for x, y in corners:
-        px, py = res._to_source(0, x, y)
+        px, py = res.to_source_xy(0, x, y)
         assert (px, py) == G.to_photo_xy(code, H_SRC, W_SRC, x, y) and photo[py, px] == upright[y, x]
     # the model's pixel grid: the box is resized by 1 (32 x 16 from 32 x 16), so model pixel (x, y) is box pixel (x, y)
     for x, y in ((0, 0), (31, 15), (7, 3)):

@@ -222,9 +222,9 @@ def test_page_result_maps_through_quad_and_angle(angle):
     # the rectangle grown by the inset is the quad
     plain = _result(quad, 0.0)
     for (x, y), corner in zip([(-2, -2), (321, -2), (321, 361), (-2, 361)], quad):
-        assert plain._unrectify(0, x, y) == pytest.approx(corner, abs=Q_TOL)
-        assert plain._rectify(0, *corner) == pytest.approx((x, y), abs=Q_TOL)
-    assert _result(quad, 0.0, inset=0)._unrectify(0, 0, 0) == pytest.approx(quad[0], abs=Q_TOL)
+        assert plain.to_source_xy(0, x, y) == pytest.approx(corner, abs=Q_TOL)
+        assert plain.from_source_xy(0, *corner) == pytest.approx((x, y), abs=Q_TOL)
+    assert _result(quad, 0.0, inset=0).to_source_xy(0, 0, 0) == pytest.approx(quad[0], abs=Q_TOL)
     # every construction the tests had keeps working, and a quad needs the page sizes
     old = PageResult([[(10, 20, 110, 60)]], None, None, None, [0], [(32, 64)], [(0, 0, 32, 64)])
     assert old.quads == [None] and old.source_sizes is None and old.to_page_xy(0, -0.5, -0.5) == pytest.approx((9.5, 19.5))
