@@ -273,6 +273,7 @@ _SIGNATURES = {
                                 c_void_p, c_size_t, c_void_p]),
     "acai_debug_stamps": (c_int, [c_void_p, c_int]),
     "acai_debug_lds_dma_oob": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "acai_debug_lane_xor": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "acai_pe_interp_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "acai_pe_interp_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "acai_cast_f32_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -64,6 +64,14 @@ __device__ __forceinline__ uint4 ld_nt16(const void *p) {
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
+// A load the whole wave makes from one address of memory that no kernel writes while this one runs (a length, an offset, the step counter
+// as the previous launch left it): through the constant address space, so that it is a scalar load wherever it stands.  (A plain load
+// behind an asm statement, or behind any store the compiler cannot tell apart, goes through the vector path and a v_readfirstlane.)
+template <typename T>
+__device__ __forceinline__ T ld_uniform(const T *p) {
+    return *reinterpret_cast<const __attribute__((address_space(4))) T *>(reinterpret_cast<uintptr_t>(p));
+}
+
 // LDS image of a [rows][DHP] attention operand tile (K, V, Q, dO) in its natural row-major order.
 //   bf16: unpadded rows (64 / 128 bytes) with an XOR swizzle of the 16-byte chunk index by row bits, chosen so that BOTH access patterns are
 //         bank-conflict free: ds_read_b128 of one chunk column by 16 consecutive rows, and ds_read_b64_tr_b16 of a 4-row x 64-byte block.
@@ -154,6 +162,37 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 #undef ACAI_DPP_ADD
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+
+// The value lane (i ^ O) holds - what __shfl_xor(v, O) returns - without the LDS crossbar (ds_bpermute: ~100 cycles a round trip, and a
+// butterfly is a chain of them).  Offsets 1 and 2 are quad permutes, 8 is a rotation of the 16-lane row by 8 (i + 8 mod 16 = i ^ 8), 16 and
+// 32 exchange rows / halves with v_permlane16_swap / v_permlane32_swap (both operands the same register: one result holds the lower
+// partner's value, the other the upper partner's).  Offset 4 has no exact DPP form on gfx9 and stays a __shfl_xor.  Every lane of the wave
+// (for O < 16: of the lane's row) must be active.  lane_xor_add / lane_xor_max are the butterfly stages v += __shfl_xor(v, O) and
+// v = fmaxf(v, __shfl_xor(v, O)) with the same operands in the same order: bit-identical results.
+template <int O>
+__device__ __forceinline__ float lane_xor(float v) {
+    static_assert(O == 1 || O == 2 || O == 4 || O == 8 || O == 16 || O == 32, "one butterfly stage of a wave of 64");
+    const int x = __builtin_bit_cast(int, v);
+    if constexpr (O == 1) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false));         // quad_perm [1,0,3,2]
+    else if constexpr (O == 2) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
+    else if constexpr (O == 8) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, false));   // row_ror:8
+    else if constexpr (O == 16) {
+        const auto r = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);
+        return __builtin_bit_cast(float, (__lane_id() & 16) ? r[0] : r[1]);
+    } else if constexpr (O == 32) {
+        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false);
+        return __builtin_bit_cast(float, (__lane_id() & 32) ? r[0] : r[1]);
+    } else return __shfl_xor(v, O);
+}
+// Offset 4 where the four lanes of every quad hold the same value (a sum after its stages 1 and 2): row_half_mirror hands lane i the value
+// of lane 7 - i of its group of 8, which sits in the quad of lane i ^ 4.  NOT lane i ^ 4 itself: on any other input the result differs.
+__device__ __forceinline__ float lane_xor4_quad_uniform(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
+}
+template <int O>
+__device__ __forceinline__ float lane_xor_add(float v) { return v + lane_xor<O>(v); }
+template <int O>
+__device__ __forceinline__ float lane_xor_max(float v) { return fmaxf(v, lane_xor<O>(v)); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

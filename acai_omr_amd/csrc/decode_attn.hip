@@ -31,12 +31,71 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kq = lane % LPK, kg = lane / LPK;
     const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    // The launch is a latency chain after a kernel boundary (the self form moves a few KB; the cross form's ramp delays its first K/V byte).
+    // Every argument the form uses comes in by ONE batch of scalar loads and one wait (left alone, the compiler fetched the struct in up to
+    // four dependent stages, each a cold round trip), and PLAIN / RAGGED request what does not depend on the sequence length - q, and the
+    // self form's first key groups - before they wait for the length.
+    constexpr bool PLAIN = !RAGGED && !ANC && !SLOT && !SPEC;
+    asm volatile("" ::"s"(a.q), "s"(a.kc), "s"(a.vc), "s"(a.partial), "s"(a.ldq), "s"(a.H), "s"(a.dh), "s"(a.dhp), "s"(a.Tmax), "s"(a.chunk),
+                 "s"(a.nsplit), "s"(a.scale_log2e), "s"(a.out), "s"(a.ldo), "s"(a.round_out), "s"(a.tickets), "s"(a.out_bf16));
+    if constexpr (RAGGED) asm volatile("" ::"s"(a.seq_off), "s"(a.seq_len));   // (Tmax, above, is not RAGGED's: it keeps ldq .. scale_log2e one load)
+    if constexpr (PLAIN || ANC) asm volatile("" ::"s"(a.step));
+    if constexpr (SLOT || SPEC) asm volatile("" ::"s"(a.seq_len));
+    if constexpr (ANC || SLOT || SPEC) asm volatile("" ::"s"(a.anc), "s"(a.anc_pitch), "s"(a.anc_bstride));
+    if constexpr (F8) asm volatile("" ::"s"(a.k_scale), "s"(a.v_scale));
+    // the length's scalar loads: requested here, used only below the fence that follows the early requests
+    [[maybe_unused]] int len_raw = 0;
+    [[maybe_unused]] int64_t off_raw = 0;
+    if constexpr (RAGGED) {
+        len_raw = ld_uniform(a.seq_len + b);
+        off_raw = ld_uniform(a.seq_off + b);
+    } else if constexpr (PLAIN) len_raw = ld_uniform(a.step + 1);
+
+    // q: EPC floats per lane as 16-byte loads at clamped addresses (a piece past dh re-reads the row's last piece; its lanes are zeroed
+    // below), or - rows that are not 16-byte aligned, dh no multiple of 4 - as dword loads clamped to the row's last element.  No branch
+    // around a load in either form.
+    float qf[EPC];
+    auto request_q = [&]() {
+        const float *qr = a.q + (size_t)b * a.ldq + h * a.dh;
+        if ((((uintptr_t)a.q | (uintptr_t)(unsigned)a.ldq * 4 | (uintptr_t)(unsigned)a.dh * 4) & 15) == 0 && a.dh >= 4) {
+#pragma unroll
+            for (int j = 0; j < EPC / 4; ++j) {
+                const f32x4 v = *reinterpret_cast<const f32x4 *>(qr + min(kq * EPC + 4 * j, a.dh - 4));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) qf[4 * j + e] = v[e];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) qf[e] = qr[min(kq * EPC + e, a.dh - 1)];
+        }
+    };
+    auto zero_q_past_dh = [&]() {
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) qf[e] = kq * EPC + e < a.dh ? qf[e] : 0.f;
+    };
+    if constexpr (!ANC && !SPEC) request_q();   // (the table forms stage their table first: q held across that barrier costs them ~20 VGPRs)
+    uint4 kn[U], vn[U];
+    if constexpr (PLAIN) {
+        // the first U key groups of the wave, requested before step[1] returns: the cache row of (b, h) is [Tmax][dhp] whatever the length,
+        // and a key index clamped to Tmax - 1 stays inside it; the key loop's `key < c1` test discards what lies past the length
+        const TC *K0 = reinterpret_cast<const TC *>(a.kc) + ((size_t)b * a.H + h) * ((size_t)a.Tmax * a.dhp) + kq * EPC;
+        const TC *V0 = reinterpret_cast<const TC *>(a.vc) + ((size_t)b * a.H + h) * ((size_t)a.Tmax * a.dhp) + kq * EPC;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int key = max(min(split * a.chunk + wave * KPW + kg + u * 4 * KPW, a.Tmax - 1), 0);
+            kn[u] = ld_nt16(K0 + (size_t)key * a.dhp);
+            vn[u] = ld_nt16(V0 + (size_t)key * a.dhp);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);   // every request above is in flight before the length is waited for
+    if constexpr (!ANC && !SPEC) zero_q_past_dh();
+
     int len, hstride;
     size_t base;
     if constexpr (RAGGED) {
-        len = a.seq_len[b];
+        len = len_raw;
         hstride = len * a.dhp;
-        base = (size_t)a.seq_off[b] + (size_t)h * hstride;
+        base = (size_t)off_raw + (size_t)h * hstride;
     } else if constexpr (ANC) {
         len = a.step[1] + 1;
         hstride = a.Tmax * a.dhp;
@@ -51,7 +110,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
         hstride = a.Tmax * a.dhp;
         base = ((size_t)img * R * a.H + h) * hstride;   // + (row of the image) * H * hstride per key
     } else {
-        len = a.step[1] + 1;
+        len = len_raw + 1;
         hstride = a.Tmax * a.dhp;
         base = ((size_t)b * a.H + h) * hstride;
     }
@@ -105,11 +164,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
         } else return (size_t)key * a.dhp;
     };
 
-    float qf[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-        const int d = kq * EPC + e;
-        qf[e] = d < a.dh ? a.q[(size_t)b * a.ldq + h * a.dh + d] : 0.f;
+    if constexpr (ANC || SPEC) {
+        request_q();
+        zero_q_past_dh();
     }
     float m = -1.0e30f, l = 0.f, acc[EPC];
 #pragma unroll
@@ -117,7 +174,6 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
 
     // software pipeline: the U key groups of iteration i+1 are requested before iteration i is computed (a wave that computes has no load
     // in flight otherwise: PMC showed the VALU busy a third of the time and the waves waiting on memory for half of it)
-    uint4 kn[U], vn[U];
     [[maybe_unused]] float ksn[U], vsn[U];
     auto request = [&](int key0) {
 #pragma unroll
@@ -136,7 +192,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
             }
         }
     };
-    request(c0 + wave * KPW + kg);
+    if constexpr (!PLAIN) request(c0 + wave * KPW + kg);   // (PLAIN: requested above, ahead of the length)
     for (int key0 = c0 + wave * KPW + kg; key0 < c1; key0 += 4 * KPW * U) {
         uint4 kk[U], vv[U];
         [[maybe_unused]] float ks[U], vs[U];
@@ -189,8 +245,11 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
             float s = 0.f;
 #pragma unroll
             for (int e = 0; e < EPC; ++e) s = fmaf(qf[e], kf[e], s);
-#pragma unroll
-            for (int o = 1; o < LPK; o <<= 1) s += __shfl_xor(s, o);
+            // the LPK lanes of the key: butterfly on the DPP network (after stages 1 and 2 the quads are uniform: the mirror form of stage 4)
+            if constexpr (LPK > 1) s = lane_xor_add<1>(s);
+            if constexpr (LPK > 2) s = lane_xor_add<2>(s);
+            if constexpr (LPK > 4) s += lane_xor4_quad_uniform(s);
+            if constexpr (LPK > 8) s = lane_xor_add<8>(s);
             if (key < c1) {  // uniform inside a lane group
                 if constexpr (F8) s *= ks[u];
                 s *= a.scale_log2e;
@@ -205,19 +264,23 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DAttnArgs a) {
         }
     }
     // merge the KPW lane groups of this wave (lanes with equal kq)
+    // (lane_xor stages; offset 4 - LPK <= 4 - stays a __shfl_xor inside lane_xor<4>: the partner must keep kq, and the quads differ)
     float mw = m;
-#pragma unroll
-    for (int o = LPK; o < 64; o <<= 1) mw = fmaxf(mw, __shfl_xor(mw, o));
+#define ACAI_MERGE_STAGE(O)                                  \
+    if constexpr (LPK <= O) mw = lane_xor_max<O>(mw);
+    ACAI_MERGE_STAGE(1) ACAI_MERGE_STAGE(2) ACAI_MERGE_STAGE(4) ACAI_MERGE_STAGE(8) ACAI_MERGE_STAGE(16) ACAI_MERGE_STAGE(32)
+#undef ACAI_MERGE_STAGE
     const float f = fast_exp2(m - mw);
     l *= f;
 #pragma unroll
     for (int e = 0; e < EPC; ++e) acc[e] *= f;
-#pragma unroll
-    for (int o = LPK; o < 64; o <<= 1) {
-        l += __shfl_xor(l, o);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) acc[e] += __shfl_xor(acc[e], o);
+#define ACAI_MERGE_STAGE(O)                                  \
+    if constexpr (LPK <= O) {                                \
+        l = lane_xor_add<O>(l);                              \
+        _Pragma("unroll") for (int e = 0; e < EPC; ++e) acc[e] = lane_xor_add<O>(acc[e]); \
     }
+    ACAI_MERGE_STAGE(1) ACAI_MERGE_STAGE(2) ACAI_MERGE_STAGE(4) ACAI_MERGE_STAGE(8) ACAI_MERGE_STAGE(16) ACAI_MERGE_STAGE(32)
+#undef ACAI_MERGE_STAGE
     if (kg == 0) {
         if (kq == 0) {
             red[wave][0] = mw;
@@ -526,6 +589,18 @@ __global__ __launch_bounds__(256) void decode_attn_gmfma_kernel(DAttnArgs a, int
     }
 }
 
+// probe of lane_xor_add / lane_xor_max against the __shfl_xor stage they stand for (acai_debug_lane_xor): one wave per row of 64 values
+template <int O, bool MAX>
+__global__ __launch_bounds__(64) void lane_xor_probe_kernel(const float *in, float *out, int rows) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const float v = in[(size_t)r * 64 + lane], w = __shfl_xor(v, O);
+    float got;
+    if constexpr (O == 4) got = MAX ? fmaxf(v, lane_xor4_quad_uniform(v)) : v + lane_xor4_quad_uniform(v);
+    else got = MAX ? lane_xor_max<O>(v) : lane_xor_add<O>(v);
+    out[(size_t)r * 64 + lane] = got;
+    out[((size_t)rows + r) * 64 + lane] = MAX ? fmaxf(v, w) : v + w;
+}
+
 // one wave per (b, h): out[b, h*dh + d] = sum_s o_s[d] 2^(m_s - M) / sum_s l_s 2^(m_s - M)
 __global__ __launch_bounds__(64) void attn_combine_kernel(const float *partial, float *out, int ldo, int H, int dh, int dhp,
                                                           int nsplit, int round_out) {
@@ -757,6 +832,23 @@ extern "C" int acai_decode_attn_fp8(const float *q, int ldq, const void *kc, con
     int rc = launch_dattn_fp8(a, B, st);
     if (rc || !out) return rc;
     return launch_attn_combine(partial, out, ldo, B, H, dh, dhp, nsplit, round_out, st);
+}
+
+extern "C" int acai_debug_lane_xor(const float *in, int rows, int offset, int op, float *out, void *stream) {
+    ACAI_CHECK_ARG(in && out && rows > 0 && (op == 0 || op == 1), "acai_debug_lane_xor: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+#define ACAI_LX(O)                                                                                                  \
+    case O:                                                                                                         \
+        if (op) hipLaunchKernelGGL((lane_xor_probe_kernel<O, true>), dim3(rows), dim3(64), 0, st, in, out, rows);   \
+        else hipLaunchKernelGGL((lane_xor_probe_kernel<O, false>), dim3(rows), dim3(64), 0, st, in, out, rows);     \
+        break;
+    switch (offset) {
+        ACAI_LX(1) ACAI_LX(2) ACAI_LX(4) ACAI_LX(8) ACAI_LX(16) ACAI_LX(32)
+        default: return acai_set_err(-1, "acai_debug_lane_xor: offset %d is no butterfly stage of a wave of 64", offset);
+    }
+#undef ACAI_LX
+    ACAI_LAUNCH_CHECK("acai_debug_lane_xor");
+    return 0;
 }
 
 extern "C" int acai_decode_merge_in_launch(int dtype, int dhp) {

@@ -175,6 +175,12 @@ int acai_debug_stamps(void *buf, int cap_launches);
  * writing ZEROS (observed on gfx950 / ROCm 7.2, not documented): a ROCm change shows up as a red test instead of wrong gradients. */
 int acai_debug_lds_dma_oob(const void *src, int valid_bytes, void *out, void *stream);
 
+/* Probe of the butterfly stages decode attention builds on (tests/test_gpu_lane_xor.py): every row of in[rows][64] is one wave; out[0][r]
+ * receives the stage made by lane_xor_add<offset> (op 0) or lane_xor_max<offset> (op 1) of csrc/common.h - DPP quad permutes and row
+ * rotation, v_permlane16/32_swap - and out[1][r] the same stage made with __shfl_xor.  offset 1, 2, 8, 16, 32: equal bit for bit on any
+ * input.  offset 4 probes the row_half_mirror form, which equals the shuffle only where the four lanes of every quad hold one value. */
+int acai_debug_lane_xor(const float *in, int rows, int offset, int op, float *out, void *stream);
+
 /* autocast's fp32 -> bf16 input cast (round to nearest even) for an activation that feeds a bf16 GEMM. */
 int acai_cast_f32_bf16(const float *x, void *y, int64_t n, void *stream);
 
