@@ -834,6 +834,70 @@ extern "C" int acai_decode_attn_fp8(const float *q, int ldq, const void *kc, con
     return launch_attn_combine(partial, out, ldo, B, H, dh, dhp, nsplit, round_out, st);
 }
 
+// Test entry: the self-attention forms of a decode step on caller-supplied operands.  The DAttnArgs fields are the ones attend() in
+// decode.hip sets for the self case, and the launch goes through launch_dattn, the step's own dispatch.
+extern "C" int acai_debug_decode_self_attn(int form, const float *q, int ldq, const void *k_cache, const void *v_cache, const int32_t *step,
+                                           const int32_t *row_len, const int32_t *table, int table_pitch, int64_t table_stride, float *partial,
+                                           void *out, int ldo, int B, int H, int dh, int dhp, int Tmax, int chunk, int nsplit, int dtype,
+                                           int round_out, int out_bf16, uint32_t *tickets, void *stream) {
+    const char *fn = "acai_debug_decode_self_attn";
+    ACAI_CHECK_ARG(form >= 0 && form <= 3, "%s: form %d is none of 0 plain, 1 ancestor, 2 ring, 3 speculative", fn, form);
+    ACAI_CHECK_ARG(q && k_cache && v_cache && partial, "%s: null operand", fn);
+    ACAI_CHECK_ARG(form >= 2 || step, "%s: the plain and ancestor forms need step", fn);
+    ACAI_CHECK_ARG(form < 2 || row_len, "%s: the ring and speculative forms need row_len", fn);
+    ACAI_CHECK_ARG(form == 0 || table, "%s: form %d needs its table", fn, form);
+    ACAI_CHECK_ARG(dtype == ACAI_F32 || dtype == ACAI_BF16, "%s: bad dtype", fn);
+    ACAI_CHECK_ARG(B > 0 && H > 0 && dh > 0 && dhp >= dh && dhp <= 64 && (dhp & (dhp - 1)) == 0 && dhp * (dtype == ACAI_BF16 ? 2 : 4) >= 16 &&
+                       Tmax > 0 && chunk > 0 && nsplit > 0,
+                   "%s: bad dims B=%d H=%d dh=%d dhp=%d Tmax=%d chunk=%d nsplit=%d", fn, B, H, dh, dhp, Tmax, chunk, nsplit);
+    ACAI_CHECK_ARG((long)chunk * nsplit >= Tmax, "%s: attention split does not cover the cache (chunk %d x nsplit %d < Tmax %d)", fn, chunk,
+                   nsplit, Tmax);
+    ACAI_CHECK_ARG((form != 1 && form != 3) || chunk <= 16384, "%s: chunk %d above 16384 (the table is staged in LDS)", fn, chunk);
+    ACAI_CHECK_ARG((form != 1 && form != 3) || table_pitch > 0, "%s: table_pitch %d", fn, table_pitch);
+    ACAI_CHECK_ARG(form != 1 || table_pitch >= Tmax, "%s: ancestor table pitch %d below Tmax %d", fn, table_pitch, Tmax);
+    ACAI_CHECK_ARG(form != 3 || (table_stride >= 1 && table_stride <= 8 && B % table_stride == 0),
+                   "%s: %lld rows per image (1 .. 8, dividing B=%d)", fn, (long long)table_stride, B);
+    ACAI_CHECK_ARG(!out_bf16 || (out && (nsplit == 1 || tickets)), "%s: bf16 rows are written by the attention launch only (out, and one split or tickets)", fn);
+    DAttnArgs a{};
+    a.q = q; a.kc = k_cache; a.vc = v_cache; a.ldq = ldq; a.H = H; a.dh = dh; a.dhp = dhp; a.Tmax = Tmax;
+    a.partial = partial; a.scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+    a.chunk = chunk; a.nsplit = nsplit;
+    if (form < 2) a.step = step;
+    else a.seq_len = row_len;
+    if (form == 1) { a.anc = table; a.anc_pitch = table_pitch; a.anc_bstride = table_stride; }
+    if (form == 2) a.slot_first = table;
+    if (form == 3) { a.spec_tab = table; a.anc_pitch = table_pitch; a.anc_bstride = table_stride; }
+    hipStream_t st = (hipStream_t)stream;
+    auto launch = [&]() { return dtype == ACAI_BF16 ? launch_dattn<bf16_t>(a, B, form == 3, st) : launch_dattn<float>(a, B, form == 3, st); };
+    if (out && (nsplit == 1 || tickets)) {
+        a.out = (float *)out; a.ldo = ldo; a.round_out = round_out; a.out_bf16 = out_bf16 ? 1 : 0;
+        if (nsplit > 1) a.tickets = tickets;
+        return launch();
+    }
+    int rc = launch();
+    if (rc || !out) return rc;
+    return launch_attn_combine(partial, (float *)out, ldo, B, H, dh, dhp, nsplit, round_out, st);
+}
+
+// Test entry: acai_decode_attn through the rollout-group kernel (launch_dattn_group, as a step with cross_group > 1 launches it).
+extern "C" int acai_debug_decode_attn_group(const float *q, int ldq, const void *kc, const void *vc, const int64_t *seq_off,
+                                            const int32_t *seq_len, float *partial, float *out, int ldo, int B, int H, int dh, int dhp,
+                                            int chunk, int nsplit, int dtype, int round_out, uint32_t *tickets, int group, void *stream) {
+    const char *fn = "acai_debug_decode_attn_group";
+    ACAI_CHECK_ARG(q && kc && vc && seq_off && seq_len && partial && out, "%s: null operand", fn);
+    ACAI_CHECK_ARG(dtype == ACAI_BF16 && dhp == 64, "%s: the group kernel is bf16 with d_h padded to 64 only", fn);
+    ACAI_CHECK_ARG(B > 0 && H > 0 && dh > 0 && dh <= dhp && chunk > 0 && nsplit > 0 && group > 0 && B % group == 0,
+                   "%s: bad dims B=%d H=%d dh=%d chunk=%d nsplit=%d group=%d", fn, B, H, dh, chunk, nsplit, group);
+    ACAI_CHECK_ARG(nsplit == 1 || tickets, "%s: more than one split needs tickets (the kernel merges inside the launch)", fn);
+    DAttnArgs a{};
+    a.q = q; a.kc = kc; a.vc = vc; a.seq_off = seq_off; a.seq_len = seq_len; a.partial = partial;
+    a.ldq = ldq; a.H = H; a.dh = dh; a.dhp = dhp; a.chunk = chunk; a.nsplit = nsplit;
+    a.scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+    a.out = out; a.ldo = ldo; a.round_out = round_out;
+    if (nsplit > 1) a.tickets = tickets;
+    return launch_dattn_group(a, B, group, (hipStream_t)stream);
+}
+
 extern "C" int acai_debug_lane_xor(const float *in, int rows, int offset, int op, float *out, void *stream) {
     ACAI_CHECK_ARG(in && out && rows > 0 && (op == 0 || op == 1), "acai_debug_lane_xor: bad arguments");
     hipStream_t st = (hipStream_t)stream;

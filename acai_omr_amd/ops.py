@@ -1148,6 +1148,53 @@ def decode_attn(q, kc, vc, seq_off, seq_len, H, dh, dhp, max_len, round_out=Fals
     return out
 
 
+DATTN_PLAIN, DATTN_ANCESTOR, DATTN_RING, DATTN_SPEC = 0, 1, 2, 3   # acai_debug_decode_self_attn's `form`
+
+
+def debug_decode_self_attn(form, q, k_cache, v_cache, H, dh, chunk, nsplit, step=None, row_len=None, table=None, table_pitch=0, table_stride=0,
+                           out=None, round_out=False, tickets=None):
+    """Test entry (acai_debug_decode_self_attn, see the header): the step's self-attention kernels on given operands.  q [B, >= H*dh] fp32
+    (any row stride and alignment); k_cache / v_cache [rows, H, Tmax, dhp] fp32 or bf16; step / row_len / table int32 as the form needs.
+    out: [B, >= H*dh] fp32, or bf16 for the bf16 output form (allocated fp32 when None); tickets: B*H zeroed int32 counters for the merge
+    inside the launch, None for the separate combine launch.  Returns out."""
+    _chk(q, "q", torch.float32), _chk(k_cache, "k_cache"), _chk(v_cache, "v_cache", k_cache.dtype)
+    assert k_cache.dim() == 4 and k_cache.is_contiguous() and v_cache.is_contiguous() and v_cache.shape == k_cache.shape and k_cache.shape[1] == H
+    B, Tmax, dhp = q.shape[0], k_cache.shape[2], k_cache.shape[3]
+    for t, name in ((step, "step"), (row_len, "row_len"), (table, "table"), (tickets, "tickets")):
+        if t is not None:
+            assert _chk(t, name, torch.int32).is_contiguous(), name
+    if out is None:
+        out = torch.empty(B, H * dh, dtype=torch.float32, device=q.device)
+    assert out.dtype in (torch.float32, torch.bfloat16) and out.shape[0] == B and out.shape[1] >= H * dh and out.stride(1) == 1
+    assert tickets is None or tickets.numel() >= B * H
+    partial = torch.empty(B * H * nsplit * (dhp + 2), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().acai_debug_decode_self_attn(int(form), q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), _p(step),
+                                                      _p(row_len), _p(table), int(table_pitch), int(table_stride), partial.data_ptr(),
+                                                      out.data_ptr(), out.stride(0), B, H, dh, dhp, Tmax, chunk, nsplit, _dt(k_cache),
+                                                      1 if round_out else 0, 1 if out.dtype == torch.bfloat16 else 0, _p(tickets), _st()),
+               "acai_debug_decode_self_attn")
+    return out
+
+
+def debug_decode_attn_group(q, kc, vc, seq_off, seq_len, H, dh, dhp, group, chunk, nsplit, out=None, round_out=False, tickets=None):
+    """Test entry (acai_debug_decode_attn_group): decode_attn's operands through the matrix-core rollout-group kernel; rows i*group ..
+    i*group + group - 1 share one image's K/V (seq_off / seq_len keep one entry per row).  bf16, dhp 64; nsplit > 1 needs tickets."""
+    _chk(q, "q", torch.float32), _chk(kc, "kc", torch.bfloat16), _chk(vc, "vc", torch.bfloat16)
+    _chk(seq_off, "seq_off", torch.int64), _chk(seq_len, "seq_len", torch.int32)
+    B = q.shape[0]
+    assert seq_off.numel() == B and seq_len.numel() == B
+    if out is None:
+        out = torch.empty(B, H * dh, dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.shape[0] == B and out.shape[1] >= H * dh and out.stride(1) == 1
+    assert tickets is None or (tickets.dtype == torch.int32 and tickets.numel() >= B * H)
+    partial = torch.empty(B * H * nsplit * (dhp + 2), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().acai_debug_decode_attn_group(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), seq_off.data_ptr(),
+                                                       seq_len.data_ptr(), partial.data_ptr(), out.data_ptr(), out.stride(0), B, H, dh, dhp,
+                                                       chunk, nsplit, _dt(kc), 1 if round_out else 0, _p(tickets), int(group), _st()),
+               "acai_debug_decode_attn_group")
+    return out
+
+
 _BWD_WS = {}   # (device, stream) -> the one-pass attention backward's fp32 query-gradient workspace (used only inside a call, in stream order)
 
 

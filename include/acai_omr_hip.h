@@ -786,6 +786,33 @@ int acai_decode_attn_fp8(const float *q, int ldq, const void *kc, const void *vc
                          const int64_t *seq_off, const int32_t *seq_len, float *partial, float *out, int ldo, int B, int H, int dh,
                          int dhp, int chunk, int nsplit, int round_out, uint32_t *tickets, void *stream);
 
+/* TEST ENTRY (tests/test_gpu_decode_self_attn.py): the self-attention forms of a decode step on caller-supplied operands.  It exists for
+ * tests and launches exactly the step's kernels: it fills the kernel's arguments as the step does for its self attention and goes through the
+ * step's own dispatch.  form: 0 plain, 1 ancestor table (beam step), 2 ring (slot step), 3 key table (speculative verify step).
+ *   q [B][ldq] fp32, head h at column h*dh (any alignment, any ldq); k_cache / v_cache [rows][H][Tmax][dhp] in `dtype` (ACAI_F32 / ACAI_BF16).
+ *   Key p of row b, and the row's key count `len`:
+ *     0  k_cache[b][h][p];                                         len = step[1] + 1
+ *     1  k_cache[table[(step[0] & 1) * table_stride + b * table_pitch + p]][h][p];   len = step[1] + 1
+ *        (table: the two parity copies of [rows][table_pitch] int32, table_stride = rows * table_pitch, table_pitch >= Tmax)
+ *     2  k_cache[b][h][(table[b] + p) % Tmax] (table[b] in [0, Tmax));   len = row_len[b] in [1, Tmax]
+ *     3  R = table_stride rows per image (1 .. 8, B % R == 0), i = b / R: e = table[i * table_pitch + p] names cache row i * R + (e & 7),
+ *        position e >> 3 (both clamped into the image's rows and the cache);   len = max(1, min(row_len[i] + b % R, table_pitch, chunk * nsplit))
+ *   partial: B*H*nsplit*(dhp+2) floats; chunk * nsplit >= Tmax; forms 1 and 3 stage chunk table entries in LDS: chunk <= 16384.
+ *   out [B][ldo]: written by the attention launch itself when nsplit == 1 or `tickets` (B*H zeroed counters, re-zeroed by the launch) is
+ *   given, else by the separate combine launch; NULL stops after the partials.  round_out: values rounded to bf16.  out_bf16 (only where the
+ *   attention launch writes out): out holds bf16 rows, ldo in bf16 elements.  A refused call launches nothing. */
+int acai_debug_decode_self_attn(int form, const float *q, int ldq, const void *k_cache, const void *v_cache, const int32_t *step,
+                                const int32_t *row_len, const int32_t *table, int table_pitch, int64_t table_stride, float *partial, void *out,
+                                int ldo, int B, int H, int dh, int dhp, int Tmax, int chunk, int nsplit, int dtype, int round_out, int out_bf16,
+                                uint32_t *tickets, void *stream);
+/* TEST ENTRY: acai_decode_attn's operands through the matrix-core rollout-group kernel, launched exactly as a step with cross_group > 1
+ * launches it: rows b = i*group .. i*group + group - 1 share the ragged K/V of seq_off / seq_len[i*group] (the arrays keep one entry per
+ * row).  bf16 and dhp == 64 only, B % group == 0, out required; nsplit > 1 needs tickets (the kernel merges inside the launch only; one
+ * counter per (first row of a 16-row tile, head), B*H zeroed counters cover them). */
+int acai_debug_decode_attn_group(const float *q, int ldq, const void *kc, const void *vc, const int64_t *seq_off, const int32_t *seq_len,
+                                 float *partial, float *out, int ldo, int B, int H, int dh, int dhp, int chunk, int nsplit, int dtype,
+                                 int round_out, uint32_t *tickets, int group, void *stream);
+
 /* FP8 memory cache prefill: rows row0 .. row0+nrows-1 (dhp = 16, 32 or 64 elements each, at element offset row*dhp) of the bf16 cross K/V
  * written by acai_cross_kv_prefill -> the same rows of k_out / v_out in OCP e4m3fn, and k_scale[row] / v_scale[row].  The scale is 2^e,
  * e the smallest integer with amax(row) 2^-e <= 448 (at least -126; 0 for an all-zero row); q = round-to-nearest-even(x 2^-e).
