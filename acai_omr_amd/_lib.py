@@ -299,6 +299,8 @@ _SIGNATURES = {
     "acai_decode_slot_sample_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p, c_int, c_void_p, c_int, c_float,
                                              c_void_p]),
     "acai_decode_slot_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), c_void_p, c_int, c_void_p]),
+    "acai_decode_slot_flush": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
     "acai_decode_spec_arm": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), c_void_p]),
     "acai_decode_spec_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), c_void_p]),
     "acai_decode_prompt_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiPrompt), c_void_p]),

@@ -18,6 +18,7 @@ LMX_VOCAB_PATH = "lmx_vocab.txt"
 
 class InferenceEvent(Enum):
     ENCODING_START = "encoding_start"
+    SYSTEMS_FOUND = "systems_found"   # (an extension: streamed_page_inference's layout event)
     ENCODING_FINISH = "encoding_finish"
     STEP = "step"
     INFERENCE_FINISH = "inference_finish"

@@ -342,6 +342,29 @@ __global__ __launch_bounds__(256) void slot_arm_kernel(const int32_t *rows, int 
     }
 }
 
+// What every slot wrote since the caller last looked (acai_decode_slot_flush; the steps leave t at the last token of a finished row and
+// past the last token of a running one).  One wave per slot, four to a workgroup: the lanes stride over the slot's n new entries, so the
+// int64 reads and the int32 / fp32 writes of a wave are consecutive addresses; lanes 0 .. 3 write the header as one 16-byte run.  mark[s]
+// has one reader and one writer, this wave, and every lane has read it before lane 0 stores it.  Nothing but mark and the outputs is
+// written.
+__global__ __launch_bounds__(256) void slot_flush_kernel(const int64_t *seqs, const float *logprobs, int max_len, const int32_t *slot_t,
+                                                         const int32_t *finished, int32_t *mark, int B, int ld, int32_t *out_tok,
+                                                         float *out_lp, int32_t *hdr) {
+    const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= B) return;   // wave-uniform
+    const int fin = finished[s] != 0, m = mark[s];
+    const int end = min(slot_t[s] + fin, max_len);               // (never past the row, whatever t holds)
+    const int n = m < 0 ? 0 : min(max(end - m, 0), ld);          // (a mark below 0 is no index of the row: nothing is read)
+    const int64_t *tok = seqs + (size_t)s * max_len + m;
+    const float *lp = logprobs + (size_t)s * max_len + m;
+    for (int i = lane; i < n; i += 64) {
+        out_tok[(size_t)s * ld + i] = (int32_t)tok[i];
+        out_lp[(size_t)s * ld + i] = lp[i];
+    }
+    if (lane < 4) hdr[4 * s + lane] = lane == 0 ? n : lane == 1 ? m : lane == 2 ? fin : 0;
+    if (lane == 0) mark[s] = m + n;
+}
+
 // ---- speculative greedy decoding (an extension: the reference emits one token per step) -------------------------------------------------
 // An image owns R = D + 1 consecutive decode rows.  Before a verify step, next[i][0] is the image's last emitted token (index t - 1) and
 // next[i][1..D] the draft tokens for indices t .. t + D - 1 (-1 = none); row j consumed next[i][j] at position t + j (quirk Q1) and its
@@ -1084,5 +1107,18 @@ int launch_spec_prompt_accept(const AcaiDecoder *d, const AcaiSpec *sp, const Ac
     a.ptok = pr->tok; a.plen = pr->len; a.ppitch = pr->pitch;
     hipLaunchKernelGGL(spec_accept_kernel<SpecPromptArgs>, dim3(1), row_waves(d), sizeof(int) * 2 * (size_t)d->B, st, a);
     ACAI_LAUNCH_CHECK("spec_prompt_accept");
+    return 0;
+}
+
+// (declared and documented in acai_omr_hip.h; it takes the slot state as bare pointers, not through the decoder descriptor, so that it can
+// be driven over any rows laid out as the slot steps lay them out)
+extern "C" int acai_decode_slot_flush(const int64_t *seqs, const float *logprobs, int max_len, const int32_t *slot_t, const int32_t *finished,
+                                      int32_t *mark, int rows, int B, int ld, int32_t *out_tok, float *out_lp, int32_t *hdr, void *stream) {
+    ACAI_CHECK_ARG(seqs && logprobs && slot_t && finished && mark && out_tok && out_lp && hdr, "acai_decode_slot_flush: null operand");
+    ACAI_CHECK_ARG(B >= 1 && rows >= B, "acai_decode_slot_flush: %d slots over state of %d rows (needs 1 <= B <= rows)", B, rows);
+    ACAI_CHECK_ARG(max_len >= 1 && ld >= 1 && ld <= max_len, "acai_decode_slot_flush: ld %d outside [1, max_len = %d]", ld, max_len);
+    hipLaunchKernelGGL(slot_flush_kernel, dim3(cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, seqs, logprobs, max_len, slot_t, finished, mark,
+                       B, ld, out_tok, out_lp, hdr);
+    ACAI_LAUNCH_CHECK("slot_flush");
     return 0;
 }

@@ -288,8 +288,12 @@ class DecodeEngine:
         self.slot_t = None      # slot state [Bmax] x 3 (local time, ring start, cap), allocated on first use
         self.slot_steps = 0     # decode steps of the last continuous-batching run (the ring index wrapped slot_steps // Tmax times)
         self.slot_busy = 0      # busy slots summed over those steps (mean occupancy = slot_busy / slot_steps)
+        self.slot_polls = 0     # polls of that run (host syncs: one per poll, streamed or not)
         self.slot_urow = None   # sampled slot mode: [Bmax] int32 uniforms row of the sequence in each slot, and the (rows, Tmax) table
         self.slot_uniforms = None
+        self.slot_mark = None   # streamed slot mode: [Bmax] int32 first index of each slot not yet sent, the flush buffer and its pinned twin
+        self._flush_dev = self._flush_host = None
+        self._flush_ld = 0      # entries per slot of that buffer while a streamed run is on (its flush interval), else 0
         self.spec_t = None      # speculative decoding: per-image state (t, cap, steps, key table, next inputs, injected drafts), allocated on first use
         self.prompt_tok = None  # prompted decoding: (Bmax, Tmax) int32 tokens by output index and (Bmax,) int32 lengths, allocated on first use
         self._mem = None        # the packed memories of the last prepare() (mem32, memb): a prompt prefill's pass reads them again
@@ -952,7 +956,8 @@ class DecodeEngine:
         return self.seqs[:B, :max_len], self.logprobs[:B, :max_len], done
 
     # ---- continuous batching (an extension: the reference decodes one static batch) ----------------------------------------------------
-    def continuous(self, mem32, memb, lens, caps, slots, poll=16, use_graph=True, sample=None, uniforms=None, group=1, *, grammar=None):
+    def continuous(self, mem32, memb, lens, caps, slots, poll=16, use_graph=True, sample=None, uniforms=None, group=1, *, grammar=None,
+                   flush=None):
         """Decode of len(lens) images through `slots` decode rows that are refilled as they finish: greedy, or with sample=(top_k,
         temperature) sampled as DecodeEngine.sample samples.  mem32 / memb: the images' packed memories (M, E) fp32 / bf16 copy, lens
         their lengths, caps[i] image i's cap (its row ends after token index caps[i] - 1, or at <eos>).  Checks the arguments at the call,
@@ -965,7 +970,15 @@ class DecodeEngine:
         are per sequence (N = len(lens) * G), and each admission prefills its own slot region.
         grammar (None = off): a grammar.TokenAutomaton constraining every sequence as DecodeEngine.greedy / sample(grammar=) constrain it;
         a slot's automaton state is set to the start state when the slot is refilled.  Modes ("slot_grammar",) / ("slot_grammar_sample",
-        top_k, temperature)."""
+        top_k, temperature).
+        flush (None = off: the path, the launches and the copies above): F >= 1 streams the run (greedy and grammar modes; with sample= a
+        ValueError - rollouts have no consumer for a stream).  The run polls every F steps instead of every `poll`, and each poll's read
+        of the finished flags is replaced by one acai_decode_slot_flush launch and one copy of its buffer into pinned memory: per slot the
+        tokens and log-probs written since the last poll, and the flag in the header.  The generator then yields, per poll and after the
+        next steps are in flight, ("step", image, start, tokens, log_probs) for every busy slot with news, in slot order - tokens int32
+        and log_probs fp32, (1, n), on the CPU, the row's indices start .. start + n - 1 - and then ("finish", image) for the slots freed
+        at that poll; images with a cap below 2 are ("finish", image) up front.  An image's steps tile its row from index 1 through its
+        last token.  The same graphs are replayed: streaming adds no graph key."""
         S = int(slots)
         caps = [int(c) for c in caps]
         if max(caps) > self.Tmax:
@@ -994,10 +1007,17 @@ class DecodeEngine:
             if not isinstance(grammar, TokenAutomaton):
                 raise TypeError(f"grammar must be a grammar.TokenAutomaton, got {type(grammar).__name__}")
             mode = ("slot_grammar",) if sample is None else ("slot_grammar_sample",) + mode[1:]
-        return self._continuous(mem32, memb, lens, caps, S, poll, use_graph, mode, uniforms, G, grammar)
+        if flush is not None:
+            if sample is not None:
+                raise ValueError("flush (streaming) cannot be combined with sample: rollouts have no consumer for a stream")
+            if isinstance(flush, bool) or not isinstance(flush, int) or not 1 <= flush <= self.Tmax:
+                raise ValueError(f"flush must be an int in [1, {self.Tmax}] (the cache's max sequence length), got {flush!r}")
+        return self._continuous(mem32, memb, lens, caps, S, poll, use_graph, mode, uniforms, G, grammar, flush)
 
-    def _continuous(self, mem32, memb, lens, caps, S, poll, use_graph, mode=("slot",), uniforms=None, G=1, grammar=None):
+    def _continuous(self, mem32, memb, lens, caps, S, poll, use_graph, mode=("slot",), uniforms=None, G=1, grammar=None, flush=None):
         N, dev, own = len(caps), self.device, self.omr
+        if flush is not None:
+            poll = flush
         self._slot_group = G
         mem = memb if self.bf else mem32
         if mem is None:
@@ -1012,7 +1032,7 @@ class DecodeEngine:
             offs.append(offs[-1] + l)
         cur = torch.cuda.current_stream(dev)
         self.stream.wait_stream(cur)
-        self.slot_steps = self.slot_busy = 0
+        self.slot_steps = self.slot_busy = self.slot_polls = 0
         harvested = torch.cuda.Event()
         try:
             with torch.cuda.stream(self.stream):
@@ -1023,19 +1043,26 @@ class DecodeEngine:
                 if grammar is not None:
                     self._set_grammar(grammar)
                 self._mode = mode
+                if flush is not None:
+                    self._flush_setup(S, flush)   # before arming: _slot_reset parks the marks with the slots
                 self._arm_and_capture(S, use_graph)
             if sched.skipped:
                 harvested.record(self.stream)
                 cur.wait_event(harvested)
-                yield from sched.skipped
+                yield from sched.skipped if flush is None else [("finish", i) for i in sched.skipped]
             with torch.cuda.stream(self.stream):
                 self._slot_refill(sched.admit(), mem, offs, lens_dev, caps)
                 n = sched.chunk(poll)
                 self.launch_steps(n, use_graph)
             while n > 0:
                 with torch.cuda.stream(self.stream):
-                    fin = self.finished[:S].tolist()   # device -> host sync once per poll
+                    if flush is None:
+                        fin = self.finished[:S].tolist()   # device -> host sync once per poll
+                    else:   # the same one sync: the flags ride in the headers; enqueued before the refill below re-arms a row
+                        hdr, busy = self._flush_poll(S), list(sched.image)
+                        fin = [h[2] for h in hdr]
                     self.slot_steps += n
+                    self.slot_polls += 1
                     self.slot_busy += n * sum(i is not None for i in sched.image)
                     freed = sched.advance(n, fin)
                     for s, i in freed:   # harvest: device-side copies of the finished rows, before the refill re-arms them
@@ -1050,13 +1077,45 @@ class DecodeEngine:
                             self._parked.add(s)
                     n = sched.chunk(poll)
                     self.launch_steps(n, use_graph)   # the next steps run while the caller reads this poll's images
+                if flush is not None:   # the pinned buffer is this poll's until the next poll's copy, which follows these yields
+                    _, tok, lp = self._flush_host_views
+                    for s, (k, start, _, _) in enumerate(hdr):
+                        if busy[s] is not None and k > 0:
+                            yield ("step", busy[s], start, tok[s:s + 1, :k].clone(), lp[s:s + 1, :k].clone())
                 if freed:
                     cur.wait_event(harvested)
                     for _, i in freed:
-                        yield i
+                        yield i if flush is None else ("finish", i)
         finally:
             self._mode = ("greedy",)
+            self._flush_ld = 0
             cur.wait_stream(self.stream)
+
+    def _flush_setup(self, S, F):
+        """Streaming state of a slot run of S slots polled every F steps: the marks, and ONE device buffer (S headers, then S x F tokens,
+        then S x F log-probs: ops.slot_flush_views) with its pinned twin, both kept and only ever grown.  A slot gains at most one token
+        per step, so F entries per slot hold everything a poll can bring."""
+        if self.slot_mark is None:
+            self.slot_mark = torch.zeros(self.Bmax, dtype=torch.int32, device=self.device)
+        need = S * (4 + 2 * F)
+        if self._flush_dev is None or self._flush_dev.numel() < need:
+            self._flush_dev = torch.zeros(need, dtype=torch.int32, device=self.device)
+            self._flush_host = torch.zeros(need, dtype=torch.int32).pin_memory()
+        self._flush_ld = F
+        self._flush_host_views = ops.slot_flush_views(self._flush_host, S, F)
+        hdr, tok, lp = ops.slot_flush_views(self._flush_dev, S, F)
+        # (the poll's launch goes straight to the C ABI with these: ops.slot_flush's checks of seven tensors would sit between the sync and
+        # the next chunk's launch, where the GPU waits for the host)
+        self._flush_args = (self.seqs.data_ptr(), self.logprobs.data_ptr(), self.seqs.stride(0), self.slot_t.data_ptr(), self.finished.data_ptr(),
+                            self.slot_mark.data_ptr(), self.Bmax, S, F, tok.data_ptr(), lp.data_ptr(), hdr.data_ptr())
+
+    def _flush_poll(self, S):
+        """One flush launch over the S slots, one copy of its buffer into pinned memory, one sync -> the headers [[n, start, finished, 0]]."""
+        _lib.check(_lib.lib().acai_decode_slot_flush(*self._flush_args, ops._st()), "acai_decode_slot_flush")
+        need = S * (4 + 2 * self._flush_ld)
+        self._flush_host[:need].copy_(self._flush_dev[:need], non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self._flush_host_views[0].tolist()
 
     def _slot_setup(self, Scap, S):
         """Slot mode for S rows over regions of Scap memory rows: the cross K/V layout, the cross split picked once for [Scap] * S (so that
@@ -1102,6 +1161,8 @@ class DecodeEngine:
         self.slot_t.fill_(1)
         self.slot_first.zero_()
         self.slot_cap.fill_(2)
+        if self._flush_ld:   # a streamed run: a parked slot is finished at t = 1, so its end is 2 - nothing to send
+            self.slot_mark.fill_(2)
         self.cross_len[:S].fill_(1)
         self._parked = set(range(S))
         self.cache_len = 0
@@ -1129,6 +1190,8 @@ class DecodeEngine:
                                          lens_dev[i:i + 1], self.k_cross[li], self.v_cross[li], H, dh, dhp, round_bf16=self.bf)
             self.cross_len[s:s + 1].copy_(lens_dev[i:i + 1])
             self._parked.discard(s)
+            if self._flush_ld:   # a streamed run: the new image is sent from index 1 (<bos> never is); after this poll's flush read the row
+                self.slot_mark[s:s + 1].fill_(1)
         table = [[s for s, _ in admitted], [caps[i] for _, i in admitted]]
         sampled = self._mode[0] in ("slot_sample", "slot_grammar_sample")
         if self._mode[0] in ("slot_grammar", "slot_grammar_sample"):   # a refilled row starts in the automaton's start state; rows that stay

@@ -11,6 +11,7 @@ from torch.amp import autocast
 from ..config import (ENCODER_FINE_TUNE_DEPTH, LMX_VOCAB_PATH, MAX_LMX_SEQ_LEN, NUM_DECODER_LAYERS, PATCH_SIZE, PE_MAX_HEIGHT, PE_MAX_WIDTH,
                       InferenceEvent)
 from ..models.models import FineTuneOMREncoder, OMRDecoder, ScheduledSamplingViTOMR, ViTOMR
+from .. import page as pg
 from ..utils import PackedPatches
 
 logger = logging.getLogger(__name__)
@@ -309,7 +310,23 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     systems at once.  `PageResult.to_page_xy` / `from_page_xy` / `box_corners` go back through 4, 2 and 1 to the pages as they were passed
     in.  orient=True gives, bit for bit, what orient=<the estimated codes> gives.  The defaults of every config were chosen on synthetic
     pages and not measured on real photographs (there are none in this repository)."""
-    from .. import page as pg
+    pages, per_page, plans, specials, extra, prune = _page_front(vitomr, pages, resize, boxes, detect, assess, prune, orient, deskew, flatten, rectify)
+    system_page, sizes, windows = [p for p, *_ in plans], [s for _, _, s, _ in plans], [c for *_, c in plans]
+    if not plans:
+        return pg.PageResult(per_page, None, None, None, [], [], [], specials, **extra)
+    vitomr.eval()
+    with torch.no_grad():
+        packed, total, mem, lens = _page_encode(vitomr, pages, per_page, resize, prune, device)
+        bf = mem.dtype == torch.bfloat16
+        with autocast(device_type=device, dtype=torch.bfloat16):
+            seqs, lps, mask = vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
+    return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, patches_kept=packed.lens, patches_total=total, **extra)
+
+
+def _page_front(vitomr, pages, resize, boxes, detect, assess, prune, orient, deskew, flatten, rectify):
+    """page_inference up to the split, shared with streamed_page_inference: the keyword checks, the page stages, assessment, detection (or
+    the caller's boxes) and the crop plans -> (pages as detection saw them, per-page boxes, plans, the special token ids, PageResult's
+    stage keywords, the resolved prune config)."""
     from ..prune import as_config
     prune, (assess, _) = as_config(prune), pg.resolve_stage("assess", assess)
     pages, boxes = pg.page_lists(pages, boxes)
@@ -324,25 +341,97 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     else:
         per_page = [pg.pixel_boxes(b, *p.shape) for p, b in zip(pages, boxes)]
     plans = pg.plan_systems([tuple(p.shape) for p in pages], per_page, resize)
-    system_page, sizes, windows = [p for p, *_ in plans], [s for _, _, s, _ in plans], [c for *_, c in plans]
     specials = [getattr(vitomr.decoder, n) for n in ("bos_idx", "eos_idx", "pad_idx") if hasattr(vitomr.decoder, n)]
     if scales is not None:
         spaces = pg.system_staff_spaces(scales, plans)
         smallest = [min((v for v, (p, *_) in zip(spaces, plans) if p == i and v is not None), default=None) for i in range(len(pages))]
         extra.update(quality=[pg.page_quality(*m, assess, small) for m, small in zip(measured, smallest)], system_staff_space=spaces)
-    if not plans:
-        return pg.PageResult(per_page, None, None, None, [], [], [], specials, **extra)
-    vitomr.eval()
-    with torch.no_grad():
-        packed = pg.split_pages(pages, per_page, resize)
-        total = packed.lens
-        if prune is not None:
-            packed = vitomr.encoder.prune_packed(packed, prune)
-        mem, lens = _encode_chunks(vitomr, packed, device)
-        bf = mem.dtype == torch.bfloat16
-        with autocast(device_type=device, dtype=torch.bfloat16):
-            seqs, lps, mask = vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
-    return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, patches_kept=packed.lens, patches_total=total, **extra)
+    return pages, per_page, plans, specials, extra, prune
+
+
+def _page_encode(vitomr, pages, per_page, resize, prune, device):
+    """All systems of all pages cut out and resized into one packed patch stream, pruned when asked, and encoded in chunks -> (the packed
+    patches, the patch counts before pruning, the packed memories, their lengths).  The caller holds no_grad."""
+    packed = pg.split_pages(pages, per_page, resize)
+    total = packed.lens
+    if prune is not None:
+        packed = vitomr.encoder.prune_packed(packed, prune)
+    mem, lens = _encode_chunks(vitomr, packed, device)
+    return packed, total, mem, lens
+
+
+def streamed_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, flush_interval=25, *, grammar=None, prune=None):
+    """continuous_inference as a generator of {"type", "payload"} events (an extension: the reference's service streams one image at a time,
+    acai_omr/ui/routes.py) - every image's tokens while they are decoded, with continuous batching kept.  imgs: a list of image tensors or
+    a `utils.PackedPatches`; max_inference_len, slots, grammar, prune: as in continuous_inference.  The events, in order:
+      ENCODING_START        None
+      ENCODING_FINISH       {"images": N}, after the chunked encode
+      STEP                  {"image": i, "start": t0, "tokens": int32 (1, n), "log_probs": fp32 (1, n)}, CPU tensors: the row's indices
+                            t0 .. t0 + n - 1; per poll (every flush_interval decode steps, sooner at a cap) one for each image being decoded
+      INFERENCE_FINISH      {"image": i, "sequence", "log_probs", "mask"}: what iter_continuous_inference yields for i; after its last STEP
+      ALL_INFERENCE_FINISH  None
+    An image's STEP events tile its row from index 1 through its last token (ViTOMR.streamed_continuous_generate).  The GPU decodes the
+    next flush_interval steps while the caller consumes a poll's events.  A prefix is not offered, as in continuous batching.
+    flush_interval: an int in [1, the cache's max sequence length] - anything else is a ValueError, raised at the call like grammar's
+    TypeError; what the decode itself refuses (slots, caps) is raised when the decode starts."""
+    vitomr._check_grammar(grammar)
+    vitomr._check_flush_interval(flush_interval)
+    imgs = imgs if isinstance(imgs, PackedPatches) else list(imgs)
+
+    def events():
+        vitomr.eval()
+        yield {"type": InferenceEvent.ENCODING_START.value, "payload": None}
+        with torch.no_grad():
+            mem, lens = _encode_chunks(vitomr, imgs, device, prune)
+            bf = mem.dtype == torch.bfloat16
+            yield {"type": InferenceEvent.ENCODING_FINISH.value, "payload": {"images": len(lens)}}
+            with autocast(device_type=device, dtype=torch.bfloat16):
+                run = vitomr._streamed_continuous_packed_iter(None if bf else mem, mem if bf else None, lens, max_inference_len, slots,
+                                                              flush_interval, grammar=grammar)
+            yield from run
+        yield {"type": InferenceEvent.ALL_INFERENCE_FINISH.value, "payload": None}
+    return events()
+
+
+def streamed_page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, flush_interval=25, *, assess=None, prune=None, grammar=None, orient=None, deskew=None, flatten=None, rectify=None):
+    """page_inference as a generator of {"type", "payload"} events (an extension): the systems of whole pages, decoded by continuous batching,
+    token by token as they come.  Every argument but flush_interval is page_inference's and is checked as there, at the call: the keyword
+    checks and flush_interval (an int in [1, the cache's max sequence length], else ValueError) before anything is uploaded, then the page
+    stages and detection run at the call as well, so that what they refuse is raised there.  The events, in order:
+      ENCODING_START        None: the stages and detection are done, the split is about to start
+      SYSTEMS_FOUND         {"layout": PageResult} with the geometry and the stage reports but no rows yet (seqs None): boxes, angles, quads,
+                            orientations, quality, sizes, windows, to_page_xy, box_corners ... all work - for a UI to draw the boxes while the
+                            encoder runs
+      ENCODING_FINISH       {"images": N}, N the systems of all pages
+      STEP                  streamed_continuous_inference's payload plus "page" and "system": the row's page and its index within that page
+      INFERENCE_FINISH      likewise, {"image", "sequence", "log_probs", "mask", "page", "system"}
+      ALL_INFERENCE_FINISH  {"result": PageResult}, equal to page_inference's on the same arguments
+    A page set without systems yields ENCODING_START, SYSTEMS_FOUND and ALL_INFERENCE_FINISH with the empty result; nothing is encoded."""
+    vitomr._check_grammar(grammar)
+    vitomr._check_flush_interval(flush_interval)
+    pages, per_page, plans, specials, extra, prune = _page_front(vitomr, pages, resize, boxes, detect, assess, prune, orient, deskew, flatten, rectify)
+    system_page, sizes, windows = [p for p, *_ in plans], [s for _, _, s, _ in plans], [c for *_, c in plans]
+    tags = [{"page": p, "system": system_page[:i].count(p)} for i, p in enumerate(system_page)]
+
+    def events():
+        yield {"type": InferenceEvent.ENCODING_START.value, "payload": None}
+        layout = pg.PageResult(per_page, None, None, None, system_page, sizes, windows, specials, **extra)
+        yield {"type": InferenceEvent.SYSTEMS_FOUND.value, "payload": {"layout": layout}}
+        if not plans:
+            yield {"type": InferenceEvent.ALL_INFERENCE_FINISH.value, "payload": {"result": pg.PageResult(per_page, None, None, None, [], [], [], specials, **extra)}}
+            return
+        vitomr.eval()
+        with torch.no_grad():
+            packed, total, mem, lens = _page_encode(vitomr, pages, per_page, resize, prune, device)
+            bf = mem.dtype == torch.bfloat16
+            yield {"type": InferenceEvent.ENCODING_FINISH.value, "payload": {"images": len(lens)}}
+            with autocast(device_type=device, dtype=torch.bfloat16):
+                run = vitomr._streamed_continuous_packed_iter(None if bf else mem, mem if bf else None, lens, max_inference_len, slots,
+                                                              flush_interval, grammar=grammar, tags=tags)
+            seqs, lps, mask = yield from run
+        result = pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, patches_kept=packed.lens, patches_total=total, **extra)
+        yield {"type": InferenceEvent.ALL_INFERENCE_FINISH.value, "payload": {"result": result}}
+    return events()
 
 
 def streamed_inference(img, vitomr: ViTOMR, device, max_inference_len=1536, flush_interval=25, prefix=None, *, grammar=None, prefill=False):

@@ -1247,6 +1247,52 @@ class ViTOMR(nn.Module):
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._continuous_packed(mem32, None, lens, max_len, slots, grammar=grammar)
 
+    def _check_flush_interval(self, flush_interval):
+        """flush_interval of the streamed continuous-batching entry points: an int in [1, the cache's maximum sequence length]."""
+        top = self.decoder._cached_blocks().max_decoder_seq_len
+        if isinstance(flush_interval, bool) or not isinstance(flush_interval, int) or not 1 <= flush_interval <= top:
+            raise ValueError(f"flush_interval must be an int in [1, {top}] (the cache's max sequence length), got {flush_interval!r}")
+        return flush_interval
+
+    def _streamed_continuous_packed_iter(self, mem32, memb, lens, max_len, slots=None, flush_interval=25, use_graph=True, grammar=None,
+                                         tags=None):
+        """Streamed continuous-batching greedy decode of packed memories (DecodeEngine.continuous(flush=)): a generator of STEP and
+        INFERENCE_FINISH events, as streamed_continuous_generate describes them.  tags: None, or per image a dictionary that is merged
+        into the payload of its events (the page entry point names the row's page and system with it).  Argument errors are raised here,
+        at the call.  The generator's return value (`yield from`) is _continuous_packed's triple of all rows."""
+        self._check_grammar(grammar)
+        self._check_flush_interval(flush_interval)
+        eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, 16, use_graph, grammar=grammar, flush=flush_interval)
+        if tags is not None and len(tags) != len(caps):
+            raise ValueError(f"{len(tags)} tags for {len(caps)} images")
+
+        def events():
+            for ev in run:
+                i = ev[1]
+                tag = {} if tags is None else tags[i]
+                if ev[0] == "step":
+                    yield {"type": InferenceEvent.STEP.value, "payload": {"image": i, "start": ev[2], "tokens": ev[3], "log_probs": ev[4], **tag}}
+                else:
+                    seqs, lps, mask = self._mask_and_clip_capped(eng.cont_seqs[i:i + 1, :caps[i]], eng.cont_lps[i:i + 1, :caps[i]], [caps[i]])
+                    yield {"type": InferenceEvent.INFERENCE_FINISH.value,
+                           "payload": {"image": i, "sequence": seqs, "log_probs": lps, "mask": mask, **tag}}
+            return self._mask_and_clip_capped(eng.cont_seqs, eng.cont_lps, caps)   # (the generator's value: all rows, as _continuous_packed)
+        return events()
+
+    def streamed_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None, flush_interval=25, *, grammar=None):
+        """cached_continuous_generate as a generator of {"type", "payload"} events (an extension: the reference streams one image at a
+        time), so that a caller sees every image's tokens while `slots` rows decode the batch.  Every flush_interval decode steps - sooner
+        where a row reaches its cap - each image that is being decoded and has new tokens gives one STEP {"image": i, "start": t0,
+        "tokens": int32 (1, n), "log_probs": fp32 (1, n)}, both on the CPU: the row's indices t0 .. t0 + n - 1.  An image's STEP events tile
+        its row from index 1 (<bos> is never sent) through its last token - its <eos>, or the token at its cap - and all precede its
+        INFERENCE_FINISH {"image": i, "sequence", "log_probs", "mask"}, the three exactly what cached_continuous_generate's row i is when
+        decoded alone (iter_continuous_inference's tuple).  Within a poll the STEP events come in slot order, then the INFERENCE_FINISH of
+        the rows that ended.  An image with a cap below 2 has no STEP and finishes first.  The event list is a function of the inputs,
+        `slots` and flush_interval alone.  max_len, slots, grammar: as in cached_continuous_generate; a prefix is not offered.
+        flush_interval: an int in [1, the cache's max sequence length] (ValueError, at the call)."""
+        mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
+        return self._streamed_continuous_packed_iter(mem32, None, lens, max_len, slots, flush_interval, grammar=grammar)
+
     def streamed_cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, flush_interval=25, prefix=None, *,
                                         grammar=None, prefill=False):
         """Generator of {"type", "payload"} events (M:625-647); single image only.

@@ -1091,6 +1091,46 @@ def cross_kv_quantize_fp8(k_in, v_in, k_out, v_out, k_scale, v_scale, row0, nrow
                                                      v_scale.data_ptr(), int(row0), int(nrows), int(dhp), _st()), "acai_cross_kv_quantize_fp8")
 
 
+def slot_flush_views(buf, B, ld):
+    """(hdr int32 (B, 4), out_tok int32 (B, ld), out_lp fp32 (B, ld)) as views of the first B * (4 + 2 ld) entries of the flat int32 `buf`,
+    device or host: the layout `slot_flush` writes and the engine copies in one piece.  The header leads, so every part starts on a
+    16-byte boundary of the allocation whenever B * ld is a multiple of 4, and on a 4-byte one always (the kernel stores dwords)."""
+    B, ld = int(B), int(ld)
+    if buf.dtype != torch.int32 or buf.dim() != 1 or not buf.is_contiguous() or buf.numel() < B * (4 + 2 * ld):
+        raise ValueError(f"slot_flush: the buffer must be flat contiguous int32 of at least B * (4 + 2 ld) = {B * (4 + 2 * ld)} entries")
+    return (buf[:4 * B].view(B, 4), buf[4 * B:4 * B + B * ld].view(B, ld), buf[4 * B + B * ld:4 * B + 2 * B * ld].view(torch.float32).view(B, ld))
+
+
+@_on_operand_device
+def slot_flush(seqs, logprobs, slot_t, finished, mark, B, ld, buf=None):
+    """What slots 0 .. B-1 of a slot-mode run wrote since `mark` (acai_decode_slot_flush; the numpy statement is
+    tests/stream_reference.flush_reference): per slot, end = t + 1 if finished else t, n = clamp(end - mark, 0, ld), the n tokens (as
+    int32) and log-probs from index mark, the header (n, mark before, finished, 0), then mark += n.  seqs int64 / logprobs fp32
+    (rows, pitch), slot_t / finished / mark int32 (>= B entries; the fewest rows any of the five has is the `rows` the call is checked
+    against).  buf: flat int32 of B * (4 + 2 ld) entries that receives everything (allocated when None; entries past a slot's n keep what
+    they held).  Returns
+    (hdr, out_tok, out_lp), `slot_flush_views` of buf.  The C ABI refuses a null operand (None here), ld < 1, ld > pitch and fewer than B
+    rows (RuntimeError); nothing is launched then."""
+    B, ld = int(B), int(ld)
+    for t, n, dt in ((seqs, "seqs", torch.int64), (logprobs, "logprobs", torch.float32), (slot_t, "slot_t", torch.int32),
+                     (finished, "finished", torch.int32), (mark, "mark", torch.int32)):
+        if t is not None:
+            _chk(t, n, dt)
+            if not t.is_contiguous():
+                raise ValueError(f"{n}: must be contiguous")
+    pitch = 0 if seqs is None else seqs.shape[-1]
+    if seqs is not None and logprobs is not None and (seqs.dim() != 2 or seqs.shape != logprobs.shape):
+        raise ValueError(f"seqs / logprobs: expected two (rows, pitch) tensors of one shape, got {tuple(seqs.shape)} and {tuple(logprobs.shape)}")
+    rows = min((t.shape[0] for t in (seqs, logprobs, slot_t, finished, mark) if t is not None), default=0)
+    if buf is None:
+        buf = torch.zeros(max(B, 1) * (4 + 2 * max(ld, 1)), dtype=torch.int32, device=mark.device if mark is not None else seqs.device)
+    _chk(buf, "buf", torch.int32)
+    hdr, out_tok, out_lp = slot_flush_views(buf, max(B, 1), max(ld, 1))
+    _lib.check(_lib.lib().acai_decode_slot_flush(_p(seqs), _p(logprobs), pitch, _p(slot_t), _p(finished), _p(mark), rows, B, ld,
+                                                 out_tok.data_ptr(), out_lp.data_ptr(), hdr.data_ptr(), _st()), "acai_decode_slot_flush")
+    return hdr, out_tok, out_lp
+
+
 def skinny_gemm(x, w, bias=None, residual=None, gelu=False, round_bf16=False, out=None):
     """x [B,K] fp32, w [N,K] fp32 or bf16 -> y [B,N] fp32."""
     _chk(x, "x", torch.float32), _chk(w, "w")

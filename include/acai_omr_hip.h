@@ -604,6 +604,20 @@ int acai_decode_slot_sample_step(const AcaiDecoder *d, const AcaiSlots *sl, cons
  * pos_embedding[1].  Rows outside [0, B) are ignored.  Marks x valid for acai_decode_slot_step: the caller keeps every row it did not arm
  * either finished or chained from the previous slot step. */
 int acai_decode_slot_arm(const AcaiDecoder *d, const AcaiSlots *sl, const int32_t *rows, int n, void *stream);
+/* Streaming of a slot-mode run (an extension): collects what slots 0 .. B-1 wrote since the caller last looked, so that one small copy
+ * brings a poll's news to the host.  seqs / logprobs: the rows the slot steps write, max_len entries apart; slot_t / finished: AcaiSlots.t
+ * and the decoder's flags; mark: device int32 [rows] the caller owns - the first index of each slot not yet handed out (the caller sets 1
+ * when it arms a slot, so that <bos> is never sent, and 2 for a parked slot, which is finished at t = 1 and must send nothing).  Per slot s:
+ *   end = finished[s] ? t[s] + 1 : t[s]   (the steps leave t at the last token of a finished row and past the last token otherwise),
+ *   n = clamp(end - mark[s], 0, ld);   out_tok[s][0 .. n) = (int32) seqs[s][mark[s] .. mark[s] + n);   out_lp[s][0 .. n) likewise from
+ *   logprobs;   hdr[s] = {n, mark[s] as it was, finished[s] != 0, 0};   then mark[s] += n - what did not fit stays for the next call.
+ * out_tok (int32) and out_lp (fp32) are [B][ld], hdr is int32 [B][4]; entries past n are left as they were.  The three are meant to be
+ * views of ONE allocation, so that a single copy fetches them.  Nothing else is written: seqs, logprobs, t and finished are read only.
+ * One wave per slot, plain vector stores, no atomics.  Enqueues one kernel, ordered on `stream` after the steps whose tokens it reads
+ * and before an acai_decode_slot_arm that re-arms a slot it has not read yet.  Refused (rc < 0, nothing launched): a null pointer, B < 1,
+ * rows < B, ld < 1, ld > max_len.  (end is held to max_len and a negative mark sends nothing, so no index leaves a row.) */
+int acai_decode_slot_flush(const int64_t *seqs, const float *logprobs, int max_len, const int32_t *slot_t, const int32_t *finished,
+                           int32_t *mark, int rows, int B, int ld, int32_t *out_tok, float *out_lp, int32_t *hdr, void *stream);
 /* Speculative greedy decoding state (draft and verify; an extension: the reference emits one token per step).  An image owns R = D + 1
  * consecutive decode rows that share its cross K/V (dec->cross_group = R, dec->B = images * R).  With t the image's next index to write,
  * row j of a verify step consumes the token at index t - 1 + j - row 0 the last emitted token, rows 1..D the draft tokens - at
