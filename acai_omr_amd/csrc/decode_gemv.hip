@@ -406,12 +406,20 @@ __global__ __launch_bounds__(64 * NW) void skinny_mfma_kernel(SkinnyArgs a) {
 //     straight-line code, so the compiler's counted waits are exact - activations first, weights stay in flight across the barrier, epilogue
 //     operands are requested after the barrier and land under the weight wait;
 //   * one wave reduced and finished all 4 x 64 outputs: here wave i finishes accumulator register i of every lane (4 waves in parallel).
+// Every chain form runs four waves.  At K = 4096 (linear2) a wave owns four of the sixteen K slices and keeps sixteen separate accumulator
+// chains, so the bits are those of one wave per slice.  Per-wave stamps of the sixteen-wave form (profiles/decode_ingest_order_lin2_waves.txt)
+// showed all sixteen waves entering within 0.2 us but their 4 KB chunks landing in four groups 0.6 us apart - waves 0-3, 4-7, 8-11, 12-15,
+// one wave per SIMD in each group: a CU takes in the cold 64 KB image at ~27 GB/s whoever asks for it, and twelve waves idle at the barrier
+// meanwhile.  Four waves with sixteen 1 KB requests each get the same image complete 0.2 us sooner and cost less to launch and to
+// synchronise (kernel 4.6 -> 4.2 us).  Starting every workgroup of an XCD at another piece of the image did not change that rate.
 typedef __attribute__((vector_size(16))) unsigned int skm_v4u;
 
-template <bool XBF16, int LN, int NW, bool WFIRST = false>   // LN: 0 = none, 1 = LayerNorm on load, 2 = two LayerNorms in a row (unembed: norm3 of the last layer, then the final norm)
-__global__ __launch_bounds__(64 * NW) void skinny_chain_kernel(SkinnyArgs a) {
+// NW = K slices of 256 (one fp32 accumulator chain each, summed in slice order at the end); WV = waves, each owning NW / WV consecutive slices
+template <bool XBF16, int LN, int NW, bool WFIRST = false, int WV = NW>   // LN: 0 = none, 1 = LayerNorm on load, 2 = two LayerNorms in a row (unembed: norm3 of the last layer, then the final norm)
+__global__ __launch_bounds__(64 * WV) void skinny_chain_kernel(SkinnyArgs a) {
     constexpr bool HAS_LN = LN > 0;
-    constexpr int K = 256 * NW, PITCH = K * 2 + 16;
+    constexpr int K = 256 * NW, PITCH = K * 2 + 16, SPW = NW / WV;
+    static_assert(NW % WV == 0 && WV >= 4, "whole slices per wave; waves 0..3 finish the outputs");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     asm volatile("" ::"s"(a.x), "s"(a.W), "s"(a.bias), "s"(a.residual), "s"(a.y), "s"(a.ldx), "s"(a.ldw), "s"(a.ldr), "s"(a.ldy), "s"(a.B), "s"(a.N),
                  "s"(a.flags), "s"(a.k_cache), "s"(a.v_cache), "s"(a.step));
@@ -430,15 +438,15 @@ __global__ __launch_bounds__(64 * NW) void skinny_chain_kernel(SkinnyArgs a) {
     };
     stamp(0);
 
-    // weight fragments: lane (r, q) of wave w owns 8 x 16 B of row n0 + r at k = 256 w + 8 q + 32 c.  Buffer loads: lanes without a row are
-    // out of range and read zeros - no branch.  Non-temporal: every weight byte is read once per step.
+    // weight fragments: lane (r, q) of wave w owns 8 x 16 B per slice of row n0 + r at k = 256 (SPW w + t) + 8 q + 32 c.  Buffer loads: lanes
+    // without a row are out of range and read zeros - no branch.  Non-temporal: every weight byte is read once per step.
     const bool row_ok = r < R && n0 + r < a.N;
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.W), 0, (int)((size_t)a.N * a.ldw * 2), 0x00020000);
-    const unsigned woff = row_ok ? (unsigned)(((size_t)(n0 + r) * a.ldw + wave * 256 + 8 * q) * 2) : 0xFFF00000u;
-    skm_v4u wf[8];
+    const unsigned woff = row_ok ? (unsigned)(((size_t)(n0 + r) * a.ldw + wave * (256 * SPW) + 8 * q) * 2) : 0xFFF00000u;
+    skm_v4u wf[8 * SPW];
     auto request_weights = [&]() {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) wf[c] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, woff + 64 * c, 0, 2);
+        for (int c = 0; c < 8 * SPW; ++c) wf[c] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, woff + 64 * c, 0, 2);
     };
 
     if constexpr (XBF16 && NW == 4) {
@@ -461,9 +469,36 @@ __global__ __launch_bounds__(64 * NW) void skinny_chain_kernel(SkinnyArgs a) {
         };
         copy(wave, wave + 4, true);
         if (nb > 8) copy(wave + 8, wave + 12, false);
+    } else if constexpr (XBF16 && WV == 4) {
+        // K = 4096 on four waves: a pass of the image (8 rows, 64 KB) is 8 x 8 pieces of 1 KB.  Wave w takes columns w and w + 4 of pieces in
+        // every row: 16 coalesced loads per lane, all requested before the lane's 32 weight fragments.  A piece of a row the tile does not
+        // have is the same column's piece of row 0 again (same bytes to the same place) instead of a branch around a load.
+        static_assert(!(XBF16 && WV == 4) || K == 4096, "eight 1 KB pieces per row");
+        const unsigned va_off = wave * 1024 + lane * 16, vb_off = va_off + 4096;   // byte offsets inside a row, global and LDS alike
+        auto copy = [&](int pass, bool first) {
+            skm_v4u x[16];   // (an array of uint4 went to scratch)
+            int row[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                row[i] = pass * 8 + i < nb ? pass * 8 + i : 0;
+                const unsigned char *xr = reinterpret_cast<const unsigned char *>(a.x) + (size_t)(bt + row[i]) * a.ldx * 2;
+                x[2 * i] = *reinterpret_cast<const skm_v4u *>(xr + va_off);
+                x[2 * i + 1] = *reinterpret_cast<const skm_v4u *>(xr + vb_off);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (first) request_weights();   // behind this wave's pieces: loads return in issue order
+            __builtin_amdgcn_sched_barrier(0);   // all requests, then the first wait
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                *reinterpret_cast<skm_v4u *>(xs + row[i] * PITCH + va_off) = x[2 * i];
+                *reinterpret_cast<skm_v4u *>(xs + row[i] * PITCH + vb_off) = x[2 * i + 1];
+            }
+        };
+        copy(0, true);
+        if (nb > 8) copy(1, false);
     } else if constexpr (XBF16) {
-        // activation rows are bf16 already: the [nb][K] image is copied in half-row chunks (4 KB), wave w takes chunk w (and w + 16 when the
-        // tile has more than 8 rows): every wave has 4 loads in flight, none idles.  A wave without a chunk copies chunk 0 again (same bytes
+        // K = 4096 on sixteen waves (ACAI_SKINNY_INGEST=0, an A/B aid: a step launches the four-wave form above).  The [nb][K] image is
+        // copied in half-row chunks (4 KB), wave w takes chunk w (and w + 16 when the tile has more than 8 rows): 4 loads in flight per wave.  A wave without a chunk copies chunk 0 again (same bytes
         // to the same place) instead of branching around its loads.
         auto copy = [&](int ch, bool first) {
             const int c = ch < 2 * nb ? ch : 0;
@@ -606,15 +641,19 @@ __global__ __launch_bounds__(64 * NW) void skinny_chain_kernel(SkinnyArgs a) {
             rrstd = a.rstats[cb * 2 + 1];
         }
     }
-    // MFMA over this wave's K slice; batch columns >= nb read row 0 (their outputs are never stored)
-    const unsigned char *xfrag = xs + (r < nb ? r : 0) * PITCH + (wave * 256 + 8 * q) * 2;
-    uint4 xf[8];
+    // MFMA over this wave's K slices, one accumulator chain of eight per slice; batch columns >= nb read row 0 (their outputs are never stored)
+    const unsigned char *xfrag = xs + (r < nb ? r : 0) * PITCH + (wave * (256 * SPW) + 8 * q) * 2;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) xf[c] = *reinterpret_cast<const uint4 *>(xfrag + 64 * c);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < SPW; ++t) {
+        uint4 xf[8];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[c]), __builtin_bit_cast(bf16x8, xf[c]), acc, 0, 0, 0);
-    *reinterpret_cast<f32x4 *>(red + wave * 256 + lane * 4) = acc;
+        for (int c = 0; c < 8; ++c) xf[c] = *reinterpret_cast<const uint4 *>(xfrag + 512 * t + 64 * c);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[8 * t + c]), __builtin_bit_cast(bf16x8, xf[c]), acc, 0, 0, 0);
+        *reinterpret_cast<f32x4 *>(red + (wave * SPW + t) * 256 + lane * 4) = acc;
+    }
     stamp(3);
     __syncthreads();
     stamp(4);
@@ -688,15 +727,20 @@ int launch_skinny(const SkinnyArgs &a, hipStream_t st) {
                 if (acai_first_on_device(attr2)) {
                     hipFuncSetAttribute(reinterpret_cast<const void *>(skinny_chain_kernel<true, 0, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
                     hipFuncSetAttribute(reinterpret_cast<const void *>(skinny_chain_kernel<true, 0, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+                    hipFuncSetAttribute(reinterpret_cast<const void *>(skinny_chain_kernel<true, 0, 16, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
                 }
                 const dim3 cgrid(cdiv(a.N, b.rows_per_block), cdiv(a.B, 16));
                 const int nw = a.K == 4096 ? 16 : 4;
                 const size_t clds = (size_t)nw * 1024 + (size_t)rows * (a.K * 2 + 16);
                 static const bool wfirst = getenv("ACAI_LIN2_WFIRST") && atoi(getenv("ACAI_LIN2_WFIRST")) == 1;   // A/B aid
+                // A/B aid: 0 = the K = 4096 form on sixteen waves (one K slice each), unset = on four waves (four slices each); same bits
+                static const bool four_waves = !(getenv("ACAI_SKINNY_INGEST") && atoi(getenv("ACAI_SKINNY_INGEST")) == 0);
                 if (a.x_bf16 && a.K == 1024)
                     hipLaunchKernelGGL((skinny_chain_kernel<true, 0, 4>), cgrid, dim3(256), clds, st, b);
                 else if (a.x_bf16 && wfirst)
                     hipLaunchKernelGGL((skinny_chain_kernel<true, 0, 16, true>), cgrid, dim3(1024), clds, st, b);
+                else if (a.x_bf16 && four_waves)
+                    hipLaunchKernelGGL((skinny_chain_kernel<true, 0, 16, false, 4>), cgrid, dim3(256), clds, st, b);
                 else if (a.x_bf16)
                     hipLaunchKernelGGL((skinny_chain_kernel<true, 0, 16>), cgrid, dim3(1024), clds, st, b);
                 else if (a.ln_w && a.ln2_w)
