@@ -208,11 +208,19 @@ __device__ __forceinline__ float wave_max(float v) {
 // ---- shared by the token-selection kernels (decode_select.hip) and the prompt prefill (decode_prefill.hip) -------------------------------
 // One wave over a logit row: the row maximum `best` at its first index `bi` (torch.argmax on CPU) and sum_i exp(lg[i] - best), returned
 // wave-uniform.  The greedy step and the beam step share it, so that a beam of width 1 reproduces greedy's log-probabilities bit for bit.
-__device__ __forceinline__ float row_argmax_sumexp(const float *lg, int V, int lane, float &best, int &bi) {
+// MASKED (grammar-constrained selection): only over the tokens with allow[i] >= 0 (allow null: every token) - a masked token counts as a
+// -inf logit, its term is expf(-inf) = 0 exactly and the order of every reduction is the unmasked one's.
+template <bool MASKED = false>
+__device__ __forceinline__ float row_argmax_sumexp(const float *lg, int V, int lane, float &best, int &bi, const int16_t *allow = nullptr) {
+    const auto at = [&](int i) -> float {
+        if constexpr (MASKED)
+            if (allow && allow[i] < 0) return -INFINITY;
+        return lg[i];
+    };
     best = -INFINITY;
     bi = 0x7fffffff;
     for (int i = lane; i < V; i += 64) {
-        const float v = lg[i];
+        const float v = at(i);
         if (v > best) {  // strided scan keeps the lowest index per lane on ties
             best = v;
             bi = i;
@@ -228,7 +236,7 @@ __device__ __forceinline__ float row_argmax_sumexp(const float *lg, int V, int l
         }
     }
     float se = 0.f;
-    for (int i = lane; i < V; i += 64) se += expf(lg[i] - best);
+    for (int i = lane; i < V; i += 64) se += expf(at(i) - best);
     return wave_sum(se);
 }
 

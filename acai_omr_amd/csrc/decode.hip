@@ -252,14 +252,31 @@ static int check_unembed(const AcaiDecoder *d, const char *fn) {
     return 0;
 }
 
+// x holds this step's input: `arm` is the entry point that writes it, once the `state` state is set up
+static int check_x_valid(const AcaiDecoder *d, const char *fn, const char *arm, const char *state) {
+    ACAI_CHECK_ARG(x_valid_get(d), "%s: x does not hold this step's input embedding - call %s after setting up the %s state and after every "
+                                   "acai_decode_logits / acai_decode_hidden", fn, arm, state);
+    return 0;
+}
+
 // Prologue of the chained greedy / sampling / beam steps: the operands, the sequence state and, for a chained step, that x holds this
-// step's input (written by the previous step's argmax / sampling / beam-select kernel, or by acai_decode_embed after arming).
+// step's input (written by the previous step's selection kernel, or by acai_decode_embed after arming).
 static int check_step(const AcaiDecoder *d, const char *fn, bool chained) {
     int rc = check_unembed(d, fn);
     if (rc) return rc;
     ACAI_CHECK_ARG(d->seqs && d->logprobs && d->finished && d->max_len > 1, "%s: null sequence state", fn);
-    ACAI_CHECK_ARG(!chained || x_valid_get(d), "%s: x does not hold this step's input embedding - call acai_decode_embed after arming the "
-                                               "sequence state and after every acai_decode_logits / acai_decode_hidden", fn);
+    return chained ? check_x_valid(d, fn, "acai_decode_embed", "sequence") : 0;
+}
+
+// The draw of a sampling step; a slot step (slot != 0) also takes the uniforms' pitch and the slots' rows of it
+static int check_draw(const AcaiDecoder *d, const char *fn, const float *uniforms, int top_k, float temperature, int slot = 0, int ld_uniforms = 0,
+                      const int32_t *urow = nullptr) {
+    ACAI_CHECK_ARG(uniforms, "%s: null uniforms", fn);
+    ACAI_CHECK_ARG(!slot || urow, "%s: null urow", fn);
+    ACAI_CHECK_ARG(!slot || ld_uniforms >= d->max_len, "%s: ld_uniforms %d is below max_len %d", fn, ld_uniforms, d->max_len);
+    ACAI_CHECK_ARG(top_k >= 1 && top_k <= 64, "%s: top_k %d outside [1, 64]", fn, top_k);
+    ACAI_CHECK_ARG(temperature > 0.f, "%s: temperature must be > 0 (got %g)", fn, (double)temperature);
+    ACAI_CHECK_ARG(d->V <= 512, "%s: vocabulary %d above 512", fn, d->V);
     return 0;
 }
 
@@ -278,8 +295,7 @@ extern "C" int acai_decode_sample_step(const AcaiDecoder *d, const float *unifor
     const bool chained = d && d->E % 4 == 0;
     int rc = check_step(d, "acai_decode_sample_step", chained);
     if (rc) return rc;
-    ACAI_CHECK_ARG(uniforms && top_k >= 1 && top_k <= 64 && temperature > 0.f && d->V <= 512,
-                   "acai_decode_sample_step: needs uniforms, 1 <= top_k <= 64, temperature > 0, vocabulary <= 512 (top_k=%d V=%d)", top_k, d->V);
+    if ((rc = check_draw(d, "acai_decode_sample_step", uniforms, top_k, temperature))) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc = decode(d, nullptr, st, !chained);
     if (rc) return rc;
@@ -323,8 +339,7 @@ extern "C" int acai_decode_slot_arm(const AcaiDecoder *d, const AcaiSlots *sl, c
 extern "C" int acai_decode_slot_step(const AcaiDecoder *d, const AcaiSlots *sl, void *stream) {
     int rc = check_slots(d, sl, "acai_decode_slot_step");
     if (rc) return rc;
-    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_slot_step: x does not hold this step's input embedding - call acai_decode_slot_arm after "
-                                   "setting up the slot state and after every acai_decode_logits / acai_decode_hidden");
+    if ((rc = check_x_valid(d, "acai_decode_slot_step", "acai_decode_slot_arm", "slot"))) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc = decode(d, nullptr, st, false, true, nullptr, sl);
     if (rc) return rc;
@@ -335,14 +350,8 @@ extern "C" int acai_decode_slot_sample_step(const AcaiDecoder *d, const AcaiSlot
                                             const int32_t *urow, int top_k, float temperature, void *stream) {
     int rc = check_slots(d, sl, "acai_decode_slot_sample_step");
     if (rc) return rc;
-    ACAI_CHECK_ARG(uniforms, "acai_decode_slot_sample_step: null uniforms");
-    ACAI_CHECK_ARG(urow, "acai_decode_slot_sample_step: null urow");
-    ACAI_CHECK_ARG(ld_uniforms >= d->max_len, "acai_decode_slot_sample_step: ld_uniforms %d is below max_len %d", ld_uniforms, d->max_len);
-    ACAI_CHECK_ARG(top_k >= 1 && top_k <= 64, "acai_decode_slot_sample_step: top_k %d outside [1, 64]", top_k);
-    ACAI_CHECK_ARG(temperature > 0.f, "acai_decode_slot_sample_step: temperature must be > 0 (got %g)", (double)temperature);
-    ACAI_CHECK_ARG(d->V <= 512, "acai_decode_slot_sample_step: vocabulary %d above 512", d->V);
-    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_slot_sample_step: x does not hold this step's input embedding - call acai_decode_slot_arm "
-                                   "after setting up the slot state and after every acai_decode_logits / acai_decode_hidden");
+    if ((rc = check_draw(d, "acai_decode_slot_sample_step", uniforms, top_k, temperature, 1, ld_uniforms, urow))) return rc;
+    if ((rc = check_x_valid(d, "acai_decode_slot_sample_step", "acai_decode_slot_arm", "slot"))) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc = decode(d, nullptr, st, false, true, nullptr, sl);
     if (rc) return rc;
@@ -380,8 +389,7 @@ extern "C" int acai_decode_spec_arm(const AcaiDecoder *d, const AcaiSpec *sp, vo
 extern "C" int acai_decode_spec_step(const AcaiDecoder *d, const AcaiSpec *sp, void *stream) {
     int rc = check_spec(d, sp, "acai_decode_spec_step");
     if (rc) return rc;
-    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_spec_step: x does not hold this step's input embedding - call acai_decode_spec_arm after "
-                                   "setting up the speculative state and after every acai_decode_logits / acai_decode_hidden");
+    if ((rc = check_x_valid(d, "acai_decode_spec_step", "acai_decode_spec_arm", "speculative"))) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc = decode(d, nullptr, st, false, true, nullptr, nullptr, sp);
     if (rc) return rc;
@@ -420,9 +428,7 @@ extern "C" int acai_decode_spec_prompt_step(const AcaiDecoder *d, const AcaiSpec
     int rc = check_spec(d, sp, "acai_decode_spec_prompt_step");
     if (rc) return rc;
     if ((rc = check_prompt(d, prompt, d->B / (sp->D + 1), "acai_decode_spec_prompt_step"))) return rc;
-    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_spec_prompt_step: x does not hold this step's input embedding - call "
-                                   "acai_decode_spec_prompt_arm after setting up the speculative state and after every acai_decode_logits / "
-                                   "acai_decode_hidden");
+    if ((rc = check_x_valid(d, "acai_decode_spec_prompt_step", "acai_decode_spec_prompt_arm", "speculative"))) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc = decode(d, nullptr, st, false, true, nullptr, nullptr, sp);
     if (rc) return rc;
@@ -487,8 +493,7 @@ extern "C" int acai_decode_grammar_sample_step(const AcaiDecoder *d, const AcaiG
     int rc = check_step(d, "acai_decode_grammar_sample_step", chained);
     if (rc) return rc;
     if ((rc = check_grammar(d, g, "acai_decode_grammar_sample_step"))) return rc;
-    ACAI_CHECK_ARG(uniforms && top_k >= 1 && top_k <= 64 && temperature > 0.f,
-                   "acai_decode_grammar_sample_step: needs uniforms, 1 <= top_k <= 64, temperature > 0 (top_k=%d)", top_k);
+    if ((rc = check_draw(d, "acai_decode_grammar_sample_step", uniforms, top_k, temperature))) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc = decode(d, nullptr, st, !chained);
     if (rc) return rc;
@@ -499,8 +504,7 @@ extern "C" int acai_decode_slot_grammar_step(const AcaiDecoder *d, const AcaiSlo
     int rc = check_slots(d, sl, "acai_decode_slot_grammar_step");
     if (rc) return rc;
     if ((rc = check_grammar(d, g, "acai_decode_slot_grammar_step"))) return rc;
-    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_slot_grammar_step: x does not hold this step's input embedding - call acai_decode_slot_arm "
-                                   "after setting up the slot state and after every acai_decode_logits / acai_decode_hidden");
+    if ((rc = check_x_valid(d, "acai_decode_slot_grammar_step", "acai_decode_slot_arm", "slot"))) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc = decode(d, nullptr, st, false, true, nullptr, sl);
     if (rc) return rc;
@@ -512,12 +516,8 @@ extern "C" int acai_decode_slot_grammar_sample_step(const AcaiDecoder *d, const 
     int rc = check_slots(d, sl, "acai_decode_slot_grammar_sample_step");
     if (rc) return rc;
     if ((rc = check_grammar(d, g, "acai_decode_slot_grammar_sample_step"))) return rc;
-    ACAI_CHECK_ARG(uniforms && urow, "acai_decode_slot_grammar_sample_step: null uniforms or urow");
-    ACAI_CHECK_ARG(ld_uniforms >= d->max_len, "acai_decode_slot_grammar_sample_step: ld_uniforms %d is below max_len %d", ld_uniforms, d->max_len);
-    ACAI_CHECK_ARG(top_k >= 1 && top_k <= 64, "acai_decode_slot_grammar_sample_step: top_k %d outside [1, 64]", top_k);
-    ACAI_CHECK_ARG(temperature > 0.f, "acai_decode_slot_grammar_sample_step: temperature must be > 0 (got %g)", (double)temperature);
-    ACAI_CHECK_ARG(x_valid_get(d), "acai_decode_slot_grammar_sample_step: x does not hold this step's input embedding - call "
-                                   "acai_decode_slot_arm after setting up the slot state and after every acai_decode_logits / acai_decode_hidden");
+    if ((rc = check_draw(d, "acai_decode_slot_grammar_sample_step", uniforms, top_k, temperature, 1, ld_uniforms, urow))) return rc;
+    if ((rc = check_x_valid(d, "acai_decode_slot_grammar_sample_step", "acai_decode_slot_arm", "slot"))) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc = decode(d, nullptr, st, false, true, nullptr, sl);
     if (rc) return rc;

@@ -84,7 +84,8 @@ int launch_attn_combine(const float *partial, float *out, int ldo, int B, int H,
 // may the splits of decode_attn_kernel<dtype's cache type, dhp> be merged inside the launch (tickets)?  dtype: ACAI_F32 / ACAI_BF16 / ACAI_FP8_E4M3
 bool dattn_merge_in_launch(int dtype, int dhp);
 
-// ---- decode_select.hip: one launch helper per selection kernel, operands from the descriptors -----------------------------------------
+// ---- decode_select.hip: one launch helper per selection form, operands from the descriptors (the nine greedy / sampled forms are
+// instantiations of greedy_select_kernel / sample_select_kernel) --------------------------------------------------------------------------
 int launch_embed(const AcaiDecoder *d, const int64_t *tokens, hipStream_t st);
 int launch_set_step(const AcaiDecoder *d, int t, hipStream_t st);
 int launch_advance_cache(const AcaiDecoder *d, hipStream_t st);

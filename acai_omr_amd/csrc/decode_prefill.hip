@@ -27,9 +27,9 @@ __global__ __launch_bounds__(256) void prefill_self_kv_kernel(const T *qkv, int 
 }
 
 // The state C prompt steps leave, from the pass's logits [(b * C + j)][V] (row b * C + j scores output index j + 1): one wave per (row,
-// index) writes seqs[b][j + 1] and logprobs[b][j + 1] as prompt_logprob_kernel does (same reduction, same rounding); the wave of index C
+// index) writes seqs[b][j + 1] and logprobs[b][j + 1] as greedy_select_kernel's PROMPT form does (same reduction, same rounding); the wave of index C
 // also writes finished[b] and the next step's input x[b] = emb[token] + pos[C + 1]; wave 0 writes seqs[.][0] = <bos>'s column through its
-// own row, and thread 0 of workgroup 0 the shared words: finished[B] (prompt_logprob_kernel's count at t = C: a row with C < len[b] is
+// own row, and thread 0 of workgroup 0 the shared words: finished[B] (that form's count at t = C: a row with C < len[b] is
 // unfinished) and step.  A table entry that gives no token (index past len[b], id outside [0, V)) falls back to the row's own arg-max, as
 // the prompt step does at that index, so no table content indexes out of bounds - but unlike there the later indices do not see it: the
 // host refuses such a prompt.

@@ -2,6 +2,8 @@
 // bookkeeping, each with the host helper that launches it from the decoder descriptor.
 #include "decode_internal.h"
 
+#include <type_traits>
+
 namespace {
 
 // x[b,:] = vocab_embedding[token_b] + pos_embedding[t]; token from `tokens` or seqs[b, t-1] (quirk Q1: M:576)
@@ -15,100 +17,13 @@ __global__ __launch_bounds__(256) void embed_kernel(const float *emb, const floa
 __global__ void set_step_kernel(int32_t *step, int t) { step[0] = t; }
 
 // (row_argmax_sumexp, the row maximum / arg-max / sum of exponentials all selection kernels start from, is in common.h)
-// cached_get_next_token (M:579-581) + loop bookkeeping (M:606-611).  One workgroup, wave w takes rows w, w+4, ...
-// With `emb`: the wave that chose row b's token also writes the NEXT step's input x[b] = vocab_embedding[token] + pos_embedding[t + 1]
-// (quirk Q1: the token at index t is embedded with position t + 1, M:576), so a token step needs no embed launch of its own.
-__global__ __launch_bounds__(1024) void argmax_logprob_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs,
-                                                             int max_len, int32_t *step, int32_t *finished, int eos, int round_lp,
-                                                             int bookkeeping, const float *emb, const float *pos, float *x, int E, int Tmax) {
-    __shared__ int unfinished[16];   // up to 16 waves: one row per wave for the usual batch sizes (the rows of a wave run back to back)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = step[0];
-    int cnt = 0;
-    const int nw = blockDim.x >> 6;
-    for (int b = wave; b < B; b += nw) {
-        const float *lg = logits + (size_t)b * V;
-        float best;
-        int bi;
-        const float se = row_argmax_sumexp(lg, V, lane, best, bi);
-        float lp = -logf(se);  // logit[argmax] - logsumexp
-        if (round_lp) lp = round_bf16(lp);
-        if (bookkeeping) {
-            int fin = finished[b];
-            if (bi == eos) fin = 1;
-            if (lane == 0) {
-                seqs[(size_t)b * max_len + t] = bi;
-                logprobs[(size_t)b * max_len + t] = lp;
-                finished[b] = fin;
-            }
-            cnt += fin ? 0 : 1;
-            if (emb && t + 1 < Tmax)
-                for (int i = lane * 4; i < E; i += 256) {
-                    const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)bi * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
-                    *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
-                }
-        } else if (lane == 0) {
-            seqs[b] = bi;
-            logprobs[b] = lp;
-        }
-    }
-    if (lane == 0) unfinished[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int w = 0; w < nw; ++w) tot += unfinished[w];
-        if (bookkeeping) finished[B] = tot;
-        step[0] = t + 1;
-        step[1] = step[1] + 1;
-    }
-}
 
-// ---- prompted decoding (an extension: the reference starts every sequence from <bos> alone) -----------------------------------------------
-// (prompt_len / prompt_token, the clamped reads of the prompt tables, are in common.h: decode_prefill.hip shares them)
-// argmax_logprob_kernel (with its bookkeeping) whose token at index t <= len[b] is the prompt's.  The log-prob of token k is
-// -(logf(se) - (logit[k] - max)): for the arg-max the inner difference is exactly 0 and the value is argmax_logprob_kernel's -logf(se) bit for
-// bit (beam_select_kernel's form).  A row inside its prompt (t < len[b]) counts as unfinished.
-__global__ __launch_bounds__(1024) void prompt_logprob_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
-                                                             int32_t *step, int32_t *finished, int eos, int round_lp, const int32_t *ptok,
-                                                             const int32_t *plen, int ppitch, const float *emb, const float *pos, float *x,
-                                                             int E, int Tmax) {
-    __shared__ int unfinished[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = step[0];
-    int cnt = 0;
-    const int nw = blockDim.x >> 6;
-    for (int b = wave; b < B; b += nw) {
-        const float *lg = logits + (size_t)b * V;
-        float best;
-        int bi;
-        const float se = row_argmax_sumexp(lg, V, lane, best, bi);
-        const int P = prompt_len(plen, b, ppitch, max_len);
-        const int forced = prompt_token(ptok, b, ppitch, t, P, V);
-        const int tok = forced >= 0 ? forced : bi;
-        float lp = -(logf(se) - (lg[tok] - best));
-        if (round_lp) lp = round_bf16(lp);
-        int fin = finished[b];
-        if (tok == eos) fin = 1;
-        if (lane == 0) {
-            seqs[(size_t)b * max_len + t] = tok;
-            logprobs[(size_t)b * max_len + t] = lp;
-            finished[b] = fin;
-        }
-        cnt += (fin && t >= P) ? 0 : 1;
-        if (emb && t + 1 < Tmax)   // next step's input (see argmax_logprob_kernel)
-            for (int i = lane * 4; i < E; i += 256) {
-                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
-                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
-            }
-    }
-    if (lane == 0) unfinished[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int w = 0; w < nw; ++w) tot += unfinished[w];
-        finished[B] = tot;
-        step[0] = t + 1;
-        step[1] = step[1] + 1;
+// The NEXT step's input of row b, written by the wave that chose its token: x[b] = vocab_embedding[tok] + pos_embedding[t1], 16 bytes a lane
+// (E % 4 == 0).  Quirk Q1: the token at index t is embedded with position t1 = t + 1 (M:576).  With it a token step needs no embed launch.
+__device__ __forceinline__ void write_next_input(const float *emb, const float *pos, float *x, int E, int b, int tok, int t1, int lane) {
+    for (int i = lane * 4; i < E; i += 256) {
+        const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)t1 * E + i);
+        *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
     }
 }
 
@@ -119,12 +34,19 @@ __global__ __launch_bounds__(1024) void prompt_logprob_kernel(const float *logit
 // (logits, u) that the oracle restates.  One wave per row: k rounds of a wave-wide arg-max build the sorted top-k (k <= 64).
 // The per-row part, shared by the static and the slot sampler so that a sequence draws the same tokens in either: wave-wide, `sv` / `si` are
 // the wave's own 64 LDS entries.  Returns the drawn token; lp = log_softmax(kept)[drawn] (not rounded).
+// MASKED (grammar-constrained selection): only over the tokens with allow[i] >= 0 (allow null: every token).  With fewer than top_k of them
+// the kept set is the allowed set - the trailing rounds find none - and the rounding fallback of the draw is the last entry that holds a token.
+template <bool MASKED = false>
 __device__ __forceinline__ int topk_draw_row(const float *lg, int V, int lane, float *sv, int *si, int top_k, float inv_temperature, float u,
-                                             float &lp) {
+                                             float &lp, const int16_t *allow = nullptr) {
     // lane owns vocabulary entries lane, lane + 64, ... (V <= 512)
     float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (lane + 64 * j < V) ? lg[lane + 64 * j] : -INFINITY;
+    for (int j = 0; j < 8; ++j) {
+        bool keep = lane + 64 * j < V;
+        if constexpr (MASKED) keep = keep && !(allow && allow[lane + 64 * j] < 0);
+        v[j] = keep ? lg[lane + 64 * j] : -INFINITY;
+    }
     const int k = min(top_k, V);
     for (int r = 0; r < k; ++r) {
         float best = -INFINITY;
@@ -169,35 +91,218 @@ __device__ __forceinline__ int topk_draw_row(const float *lg, int V, int lane, f
     }
     const float target = u * sumT;
     const unsigned long long hit = __ballot(in && cdf > target);
-    const int r = hit ? __builtin_ctzll(hit) : k - 1;              // rounding at the top of the CDF: last kept entry
+    int last = k - 1;                                              // rounding at the top of the CDF: last kept entry
+    if constexpr (MASKED) last = max(__popcll(__ballot(in && x > -INFINITY)), 1) - 1;   // (not k - 1: entries past the allowed set hold no token)
+    const int r = hit ? __builtin_ctzll(hit) : last;
     lp = (sv[r] - m) - logf(sum1);
     return si[r];
 }
 
-__global__ __launch_bounds__(256) void sample_logprob_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
-                                                             const int32_t *step, int32_t *finished, int eos, int round_lp,
-                                                             const float *uniforms, int top_k, float inv_temperature, const float *emb,
-                                                             const float *pos, float *xnext, int E, int Tmax) {
+// ---- the selection of a step: greedy_select_kernel / sample_select_kernel ---------------------------------------------------------------
+// Each is ONE template over what a step may add to plain selection, and a feature is an `if constexpr` branch with an argument struct of its
+// own, so that an instantiation without it compiles without it and loads nothing for it (NoArgs in the struct's place):
+//   SLOT    continuous batching (an extension: the reference decodes one static batch).  A row runs at its OWN local time t = slot_t[b] instead
+//           of step[0]; a finished or idle row is skipped and writes nothing; a row finishes on <eos> or when t has reached its cap - 1, else t
+//           advances; the step closes by advancing the shared ring write index step[1] modulo Tmax (step[0] is not used in slot mode).
+//   GRAMMAR grammar-constrained decoding (an extension: the reference knows no grammar).  The row's table row (grammar_row) masks the reduction
+//           - a token the state forbids counts as a -inf logit, so logprobs holds the log-softmax over the allowed tokens - and the state is
+//           updated (grammar_advance).  With a table that allows every token the step computes what the plain one computes, bit for bit.
+//   PROMPT  prompted decoding (an extension: the reference starts every sequence from <bos> alone; greedy only, without SLOT or GRAMMAR).  The
+//           token at index t <= len[b] is the prompt's (prompt_len / prompt_token, the clamped reads of the prompt tables, are in common.h).
+// Only the combinations an entry point launches are instantiated.
+struct SelArgs {   // what every form takes, from AcaiDecoder
+    const float *logits;
+    int V, B, max_len, eos, round_lp, E, Tmax;
+    int64_t *seqs;
+    float *logprobs;
+    int32_t *step, *finished;
+    const float *emb, *pos;   // emb null (static forms only): the kernel does not write the next step's input
+    float *x;
+};
+struct NoArgs {};
+struct SlotArgs {   // AcaiSlots
+    int32_t *t;
+    const int32_t *cap;
+};
+struct PromptArgs {   // AcaiPrompt
+    const int32_t *tok, *len;
+    int pitch;
+};
+struct GrammarArgs {   // AcaiGrammar
+    const int16_t *next, *resync;
+    int32_t *state;
+    int states, start;
+};
+struct DrawArgs {   // a sampling step's draw: row b at time t takes uniforms[(SLOT ? urow[b] : b) * ld + t]
+    const float *uniforms;
+    int ld;
+    const int32_t *urow;   // SLOT: the sequence each slot decodes (set when the slot is armed), so that a sequence draws what it draws alone
+    int top_k;
+    float inv_temperature;
+    unsigned *ticket;      // SLOT with more than one workgroup: the arrival counter (zero between launches)
+};
+template <bool ON, typename T> using part = std::conditional_t<ON, T, NoArgs>;
+
+// Wave-uniform: the table row of decode row b's state (clamped to [0, states)), or null when that state allows no token - the row is then
+// unconstrained at this step (a defensive path: the builders refuse such tables).
+__device__ __forceinline__ const int16_t *grammar_row(const GrammarArgs &g, int b, int V, int lane) {
+    const int s = min(max(g.state[b], 0), g.states - 1);
+    const int16_t *row = g.next + (size_t)s * V;
+    bool any = false;
+    for (int i = lane; i < V; i += 64) any |= row[i] >= 0;
+    return __ballot(any) ? row : nullptr;
+}
+
+// The state after `tok` was emitted from the state of `row` (grammar_row's result): the table's, resync[tok] out of a dead state.  A token
+// outside [0, V) (no finite logit in the row) leads to start, so that no index leaves the tables.
+__device__ __forceinline__ int grammar_advance(const GrammarArgs &g, const int16_t *row, int tok, int V) {
+    if ((unsigned)tok >= (unsigned)V) return g.start;
+    return row ? row[tok] : g.resync[tok];
+}
+
+// slot mode: the shared ring write index after a step
+__device__ __forceinline__ void advance_ring(int32_t *step, int Tmax) {
+    const int nxt = step[1] + 1;
+    step[1] = nxt >= Tmax ? 0 : nxt;
+}
+
+// cached_get_next_token (M:579-581) + loop bookkeeping (M:606-611).  One workgroup, wave w takes rows w, w + nw, ... (up to 16 waves: one row
+// per wave for the usual batch sizes, the rows of a wave run back to back): the arg-max token and its log-prob into seqs / logprobs at index
+// t, the finished flag, the row's next input (write_next_input), then thread 0 publishes the unfinished count finished[B] and advances the
+// step.  PROMPT: the log-prob of token k is -(logf(se) - (logit[k] - max)); for the arg-max the inner difference is exactly 0 and the value is
+// the plain form's -logf(se) bit for bit (beam_select_kernel's form).  A row inside its prompt (t < len[b]) counts as unfinished.
+template <bool SLOT, bool GRAMMAR, bool PROMPT>
+__global__ __launch_bounds__(1024) void greedy_select_kernel(SelArgs a, part<SLOT, SlotArgs> s, part<GRAMMAR, GrammarArgs> g,
+                                                            part<PROMPT, PromptArgs> p) {
+    __shared__ int unfinished[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int t = 0, cnt = 0;
+    if constexpr (!SLOT) t = a.step[0];
+    for (int b = wave; b < a.B; b += nw) {
+        if constexpr (SLOT) {
+            if (a.finished[b]) continue;   // wave-uniform
+            t = s.t[b];
+        }
+        const float *lg = a.logits + (size_t)b * a.V;
+        const int16_t *allow = nullptr;
+        if constexpr (GRAMMAR) allow = grammar_row(g, b, a.V, lane);
+        float best;
+        int tok;
+        const float se = row_argmax_sumexp<GRAMMAR>(lg, a.V, lane, best, tok, allow);
+        float lp = -logf(se);  // logit[argmax] - logsumexp
+        bool in_prompt = false;
+        if constexpr (PROMPT) {
+            const int P = prompt_len(p.len, b, p.pitch, a.max_len);
+            const int forced = prompt_token(p.tok, b, p.pitch, t, P, a.V);
+            if (forced >= 0) tok = forced;
+            lp = -(logf(se) - (lg[tok] - best));
+            in_prompt = t < P;
+        }
+        if (a.round_lp) lp = round_bf16(lp);
+        int fin;
+        if constexpr (SLOT) {
+            fin = tok == a.eos || t >= s.cap[b] - 1;
+        } else {
+            fin = a.finished[b];
+            if (tok == a.eos) fin = 1;
+        }
+        if (lane == 0) {
+            a.seqs[(size_t)b * a.max_len + t] = tok;
+            a.logprobs[(size_t)b * a.max_len + t] = lp;
+            if constexpr (SLOT) {
+                if (fin) a.finished[b] = 1;
+                else s.t[b] = t + 1;
+            } else {
+                a.finished[b] = fin;
+            }
+            if constexpr (GRAMMAR) g.state[b] = grammar_advance(g, allow, tok, a.V);
+        }
+        cnt += (fin && !in_prompt) ? 0 : 1;
+        // SLOT: an unfinished row has t + 1 <= cap - 1 < max_len <= Tmax, and a slot step is always chained
+        if (SLOT ? !fin : (a.emb && t + 1 < a.Tmax)) write_next_input(a.emb, a.pos, a.x, a.E, b, tok, t + 1, lane);
+    }
+    if (lane == 0) unfinished[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < nw; ++w) tot += unfinished[w];
+        a.finished[a.B] = tot;
+        if constexpr (SLOT) {
+            advance_ring(a.step, a.Tmax);
+        } else {
+            a.step[0] = t + 1;
+            a.step[1] = a.step[1] + 1;
+        }
+    }
+}
+
+// The sampling step: the token of row b is topk_draw_row's.  One wave per row over gridDim.x workgroups of four (the k rounds of a row are a
+// serial chain: one workgroup for every row would put them end to end).  A static step is followed by sample_bookkeeping_kernel.  A slot
+// step closes itself: with more than one workgroup the unfinished count and the ring index are written by the workgroup that arrives last
+// at `ticket` (zero between launches, re-armed here) - every workgroup publishes its rows' flags with agent-scope atomic stores before it
+// takes its ticket, and the last one reads all flags the same way.
+template <bool SLOT, bool GRAMMAR>
+__global__ __launch_bounds__(256) void sample_select_kernel(SelArgs a, DrawArgs d, part<SLOT, SlotArgs> s, part<GRAMMAR, GrammarArgs> g) {
     __shared__ float sv[4][64];
     __shared__ int si[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x * 4 + wave;
-    if (b >= B) return;
-    const int t = step[0];
-    float lp;
-    const int tok = topk_draw_row(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
-                                  uniforms[(size_t)b * max_len + t], lp);
-    if (round_lp) lp = round_bf16(lp);
-    if (lane == 0) {
-        seqs[(size_t)b * max_len + t] = tok;
-        logprobs[(size_t)b * max_len + t] = lp;
-        if (tok == eos) finished[b] = 1;
-    }
-    if (emb && t + 1 < Tmax)   // next step's input (see argmax_logprob_kernel)
-        for (int i = lane * 4; i < E; i += 256) {
-            const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
-            *reinterpret_cast<float4 *>(xnext + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
+    const auto select_row = [&](int b) {
+        int t, urow = b;
+        if constexpr (SLOT) {
+            if (a.finished[b]) return;   // wave-uniform
+            t = s.t[b];
+            urow = d.urow[b];
+        } else {
+            t = a.step[0];
         }
+        const int16_t *allow = nullptr;
+        if constexpr (GRAMMAR) allow = grammar_row(g, b, a.V, lane);
+        float lp;
+        const int tok = topk_draw_row<GRAMMAR>(a.logits + (size_t)b * a.V, a.V, lane, sv[wave], si[wave], d.top_k, d.inv_temperature,
+                                               d.uniforms[(size_t)urow * d.ld + t], lp, allow);
+        if (a.round_lp) lp = round_bf16(lp);
+        bool fin = tok == a.eos;
+        if constexpr (SLOT) fin = fin || t >= s.cap[b] - 1;
+        if (lane == 0) {
+            a.seqs[(size_t)b * a.max_len + t] = tok;
+            a.logprobs[(size_t)b * a.max_len + t] = lp;
+            if constexpr (SLOT) {
+                if (fin) __hip_atomic_store(a.finished + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else s.t[b] = t + 1;
+            } else {
+                if (fin) a.finished[b] = 1;
+            }
+            if constexpr (GRAMMAR) g.state[b] = grammar_advance(g, allow, tok, a.V);
+        }
+        if (SLOT ? !fin : (a.emb && t + 1 < a.Tmax)) write_next_input(a.emb, a.pos, a.x, a.E, b, tok, t + 1, lane);
+    };
+    const int b0 = blockIdx.x * 4 + wave;
+    if constexpr (!SLOT) {   // a wave for every row: no row loop - with it the static draw took 2 us longer
+        if (b0 < a.B) select_row(b0);
+    } else {
+        for (int b = b0; b < a.B; b += gridDim.x * 4) select_row(b);
+        __shared__ int is_last;
+        if (gridDim.x > 1) {
+            __threadfence();   // this thread's flag stores are visible device-wide before the workgroup's ticket
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const unsigned n = __hip_atomic_fetch_add(d.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+                is_last = n == gridDim.x - 1;
+                if (is_last) __hip_atomic_store(d.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __syncthreads();
+        if (gridDim.x > 1 && !is_last) return;
+        if (wave == 0) {
+            int cnt = 0;
+            for (int b = lane; b < a.B; b += 64) cnt += __hip_atomic_load(a.finished + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 1;
+            cnt = (int)wave_sum((float)cnt);
+            if (lane == 0) {
+                a.finished[a.B] = cnt;
+                advance_ring(a.step, a.Tmax);
+            }
+        }
+    }
 }
 
 // loop bookkeeping after a sampling step: unfinished count, advance position and cache length
@@ -215,109 +320,6 @@ __global__ __launch_bounds__(64) void sample_bookkeeping_kernel(int B, int32_t *
 __global__ void advance_cache_kernel(int32_t *step) { step[1] = step[1] + 1; }
 
 // ---- continuous batching (slot mode; an extension: the reference decodes one static batch) --------------------------------------------
-// The greedy token of every unfinished row at its OWN local time t = slot_t[b] (argmax_logprob_kernel's reduction, so a row decodes as it
-// would in a greedy batch): seqs / logprobs at index t, then either the row finishes (<eos>, or t has reached its cap - 1) and from then on
-// writes nothing, or t advances and the wave writes the row's next input emb[token] + pos[t + 1] (quirk Q1).  Thread 0 publishes the
-// unfinished count finished[B] and advances the shared ring write index step[1] modulo Tmax.  step[0] is not used in slot mode.
-__global__ __launch_bounds__(1024) void slot_argmax_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
-                                                          int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap, int eos,
-                                                          int round_lp, const float *emb, const float *pos, float *x, int E, int Tmax) {
-    __shared__ int unfinished[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int cnt = 0;
-    const int nw = blockDim.x >> 6;
-    for (int b = wave; b < B; b += nw) {
-        if (finished[b]) continue;   // wave-uniform: a finished or idle row writes nothing
-        const int t = slot_t[b];
-        const float *lg = logits + (size_t)b * V;
-        float best;
-        int bi;
-        const float se = row_argmax_sumexp(lg, V, lane, best, bi);
-        float lp = -logf(se);
-        if (round_lp) lp = round_bf16(lp);
-        const bool fin = bi == eos || t >= slot_cap[b] - 1;
-        if (lane == 0) {
-            seqs[(size_t)b * max_len + t] = bi;
-            logprobs[(size_t)b * max_len + t] = lp;
-            if (fin) finished[b] = 1;
-            else slot_t[b] = t + 1;
-        }
-        if (!fin) {   // t + 1 <= cap - 1 < max_len <= Tmax
-            cnt += 1;
-            for (int i = lane * 4; i < E; i += 256) {
-                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)bi * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
-                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
-            }
-        }
-    }
-    if (lane == 0) unfinished[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int w = 0; w < nw; ++w) tot += unfinished[w];
-        finished[B] = tot;
-        const int nxt = step[1] + 1;
-        step[1] = nxt >= Tmax ? 0 : nxt;
-    }
-}
-
-// The sampling form of slot_argmax_kernel: the token of every unfinished row is topk_draw_row's at the row's local time t = slot_t[b], with
-// the uniform uniforms[urow[b]][t] of the sequence the slot decodes (urow is set when the slot is armed), so a sequence draws what it draws
-// alone in sample_logprob_kernel whichever slot and step it runs in.  One wave per row over gridDim.x workgroups of four (the k rounds of
-// a row are a serial chain: one workgroup for every row would put them end to end).  With more than one workgroup the unfinished count and
-// the ring index are written by the workgroup that arrives last at `ticket` (zero between launches, re-armed here): every workgroup
-// publishes its rows' flags with agent-scope atomic stores before it takes its ticket, and the last one reads all flags the same way.
-__global__ __launch_bounds__(256) void slot_sample_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
-                                                          int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap, int eos,
-                                                          int round_lp, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k,
-                                                          float inv_temperature, const float *emb, const float *pos, float *x, int E, int Tmax,
-                                                          unsigned *ticket) {
-    __shared__ float sv[4][64];
-    __shared__ int si[4][64];
-    __shared__ int is_last;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
-        if (finished[b]) continue;   // wave-uniform: a finished or idle row writes nothing
-        const int t = slot_t[b];
-        float lp;
-        const int tok = topk_draw_row(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
-                                      uniforms[(size_t)urow[b] * ld_uniforms + t], lp);
-        if (round_lp) lp = round_bf16(lp);
-        const bool fin = tok == eos || t >= slot_cap[b] - 1;
-        if (lane == 0) {
-            seqs[(size_t)b * max_len + t] = tok;
-            logprobs[(size_t)b * max_len + t] = lp;
-            if (fin) __hip_atomic_store(finished + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else slot_t[b] = t + 1;
-        }
-        if (!fin)   // t + 1 <= cap - 1 < max_len <= Tmax
-            for (int i = lane * 4; i < E; i += 256) {
-                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
-                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
-            }
-    }
-    if (gridDim.x > 1) {
-        __threadfence();   // this thread's flag stores are visible device-wide before the workgroup's ticket
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned n = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            is_last = n == gridDim.x - 1;
-            if (is_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-    if (gridDim.x > 1 && !is_last) return;
-    if (wave == 0) {
-        int cnt = 0;
-        for (int b = lane; b < B; b += 64) cnt += __hip_atomic_load(finished + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 1;
-        cnt = (int)wave_sum((float)cnt);
-        if (lane == 0) {
-            finished[B] = cnt;
-            const int nxt = step[1] + 1;
-            step[1] = nxt >= Tmax ? 0 : nxt;
-        }
-    }
-}
 
 // Arms row rows[i] (one workgroup each) for a new sequence: <bos> then <pad>, log-probs 0, unfinished, local time 1 starting at the current
 // ring write index step[1], cap rows[n + i] (clamped to [2, max_len]) and the first input emb[<bos>] + pos[1].  Rows outside [0, B) are
@@ -369,7 +371,7 @@ __global__ __launch_bounds__(256) void slot_flush_kernel(const int64_t *seqs, co
 // An image owns R = D + 1 consecutive decode rows.  Before a verify step, next[i][0] is the image's last emitted token (index t - 1) and
 // next[i][1..D] the draft tokens for indices t .. t + D - 1 (-1 = none); row j consumed next[i][j] at position t + j (quirk Q1) and its
 // logits predict index t + j.  One workgroup closes the step (and, with arm set, opens the run):
-//   1. wave w: the greedy token and log-prob of rows w, w + nw, ... (argmax_logprob_kernel's reduction) into LDS;
+//   1. wave w: the greedy token and log-prob of rows w, w + nw, ... (greedy_select_kernel's reduction) into LDS;
 //   2. wave w: images w, w + nw, ...: accept - g_0, then g_j while draft j equals g_{j-1} - written at t .. t + n, cut at the first <eos>
 //      and at cap - 1; t, finished[i], steps[i];
 //   3. the same wave drafts the next step: from the injected table drafts[i][index] when given, else by prompt lookup - for m = ngram .. 1
@@ -390,7 +392,7 @@ struct SpecArgs {
 };
 
 // A prompted run (acai_decode_spec_prompt_step): the verify step with image i's prompt row i.  Row j at write index t emits the prompt's token
-// while t + j <= len[i], with prompt_logprob_kernel's log-prob, and while the new t <= len[i] the next step's drafts are the prompt's tokens
+// while t + j <= len[i], with greedy_select_kernel's PROMPT log-prob, and while the new t <= len[i] the next step's drafts are the prompt's tokens
 // of indices <= len[i] (none beyond), so that they are all accepted.  The kernel is a template over its argument struct: the unprompted
 // instantiation compiles to what it was.
 struct SpecPromptArgs : SpecArgs {
@@ -543,7 +545,7 @@ struct BeamArgs {
 // One workgroup per image (rows r0 .. r0 + K - 1), step t = step[0]; lineage copy (t & 1) is read, copy (t + 1) & 1 written.
 //   1. the K rows' (cum, finished, len) into LDS (this workgroup is their only writer);
 //   2. wave w builds the candidates of rows w, w + 4, ...: a live row its K best tokens by raw logit in K rounds of a wave-wide arg-max (lower
-//      index first on ties, sample_logprob_kernel's pattern), score cum + lp with greedy's row max / sum of exponentials; a finished row the
+//      index first on ties, topk_draw_row's pattern), score cum + lp with greedy's row max / sum of exponentials; a finished row the
 //      single candidate (itself + <pad>, lp 0, score cum); a row at cum = -inf none.  Candidate c = parent * K + rank;
 //   3. thread c ranks its candidate against all K*K (score descending, then c ascending = parent slot, then rank): rank j < K -> slot j;
 //   4. wave w fills new slots w, w + 4, ...: the parent's lineage up to position t - 1 plus (slot, token, lp) at t, cum, finished, len and the
@@ -663,295 +665,10 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
             a.finished[row] = fin;
             a.len[row] = ln;
         }
-        if (t + 1 < a.Tmax)   // next step's input (see argmax_logprob_kernel)
-            for (int i = lane * 4; i < a.E; i += 256) {
-                const float4 ev = *reinterpret_cast<const float4 *>(a.emb + (size_t)tk * a.E + i), pv = *reinterpret_cast<const float4 *>(a.pos + (size_t)(t + 1) * a.E + i);
-                *reinterpret_cast<float4 *>(a.x + (size_t)row * a.E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
-            }
+        if (t + 1 < a.Tmax) write_next_input(a.emb, a.pos, a.x, a.E, row, tk, t + 1, lane);
     }
 }
 
-// ---- grammar-constrained decoding (an extension: the reference knows no grammar) -------------------------------------------------------------
-// The selection kernels above are left exactly as they are; the constrained forms below are their copies with three additions: the row's
-// table row (grammar_row), the masked reductions (row_argmax_sumexp_masked / topk_draw_row_masked: a token the state forbids counts as a -inf
-// logit) and the state update (grammar_advance).  With a table that allows every token each computes what its plain form computes, bit for
-// bit: a masked term is expf(-inf) = 0 exactly and the order of every reduction is the plain one's.
-struct GrammarArgs {   // AcaiGrammar as the kernels take it
-    const int16_t *next, *resync;
-    int32_t *state;
-    int states, start;
-};
-
-// Wave-uniform: the table row of decode row b's state (clamped to [0, states)), or null when that state allows no token - the row is then
-// unconstrained at this step (a defensive path: the builders refuse such tables).
-__device__ __forceinline__ const int16_t *grammar_row(const GrammarArgs &g, int b, int V, int lane) {
-    const int s = min(max(g.state[b], 0), g.states - 1);
-    const int16_t *row = g.next + (size_t)s * V;
-    bool any = false;
-    for (int i = lane; i < V; i += 64) any |= row[i] >= 0;
-    return __ballot(any) ? row : nullptr;
-}
-
-// The state after `tok` was emitted from the state of `row` (grammar_row's result): the table's, resync[tok] out of a dead state.  A token
-// outside [0, V) (no finite logit in the row) leads to start, so that no index leaves the tables.
-__device__ __forceinline__ int grammar_advance(const GrammarArgs &g, const int16_t *row, int tok, int V) {
-    if ((unsigned)tok >= (unsigned)V) return g.start;
-    return row ? row[tok] : g.resync[tok];
-}
-
-// row_argmax_sumexp over the tokens with allow[i] >= 0 (allow null: every token)
-__device__ __forceinline__ float row_argmax_sumexp_masked(const float *lg, int V, int lane, float &best, int &bi, const int16_t *allow) {
-    best = -INFINITY;
-    bi = 0x7fffffff;
-    for (int i = lane; i < V; i += 64) {
-        const float v = (allow && allow[i] < 0) ? -INFINITY : lg[i];
-        if (v > best) {
-            best = v;
-            bi = i;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ov > best || (ov == best && oi < bi)) {
-            best = ov;
-            bi = oi;
-        }
-    }
-    float se = 0.f;
-    for (int i = lane; i < V; i += 64) se += expf(((allow && allow[i] < 0) ? -INFINITY : lg[i]) - best);
-    return wave_sum(se);
-}
-
-// topk_draw_row over the tokens with allow[i] >= 0 (allow null: every token): with fewer than top_k of them the kept set is the allowed set -
-// the trailing rounds find none - and the rounding fallback of the draw is the last entry that holds a token.
-__device__ __forceinline__ int topk_draw_row_masked(const float *lg, int V, int lane, float *sv, int *si, int top_k, float inv_temperature,
-                                                    float u, float &lp, const int16_t *allow) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (lane + 64 * j < V && !(allow && allow[lane + 64 * j] < 0)) ? lg[lane + 64 * j] : -INFINITY;
-    const int k = min(top_k, V);
-    for (int r = 0; r < k; ++r) {
-        float best = -INFINITY;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (v[j] > best) {
-                best = v[j];
-                bi = lane + 64 * j;
-            }
-        if (best == -INFINITY) bi = 0x7fffffff;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o);
-            const int oi = __shfl_xor(bi, o);
-            if (ov > best || (ov == best && oi < bi)) {
-                best = ov;
-                bi = oi;
-            }
-        }
-        if ((bi & 63) == lane) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (bi == lane + 64 * j) v[j] = -INFINITY;
-        }
-        if (lane == 0) {
-            sv[r] = best;
-            si[r] = bi;
-        }
-    }
-    const bool in = lane < k;
-    const float x = in ? sv[lane] : -INFINITY, m = sv[0];
-    const float pT = in ? expf((x - m) * inv_temperature) : 0.f;
-    const float p1 = in ? expf(x - m) : 0.f;
-    const float sumT = wave_sum(pT), sum1 = wave_sum(p1);
-    float cdf = pT;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float up = __shfl_up(cdf, o);
-        if (lane >= o) cdf += up;
-    }
-    const float target = u * sumT;
-    const unsigned long long hit = __ballot(in && cdf > target);
-    const int last = max(__popcll(__ballot(in && x > -INFINITY)), 1) - 1;
-    const int r = hit ? __builtin_ctzll(hit) : last;
-    lp = (sv[r] - m) - logf(sum1);
-    return si[r];
-}
-
-// argmax_logprob_kernel (with its bookkeeping) under the automaton: logprobs holds the log-softmax over the allowed tokens
-__global__ __launch_bounds__(1024) void grammar_argmax_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
-                                                             int32_t *step, int32_t *finished, int eos, int round_lp, const float *emb,
-                                                             const float *pos, float *x, int E, int Tmax, GrammarArgs g) {
-    __shared__ int unfinished[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = step[0];
-    int cnt = 0;
-    const int nw = blockDim.x >> 6;
-    for (int b = wave; b < B; b += nw) {
-        const float *lg = logits + (size_t)b * V;
-        float best;
-        int bi;
-        const int16_t *allow = grammar_row(g, b, V, lane);
-        const float se = row_argmax_sumexp_masked(lg, V, lane, best, bi, allow);
-        float lp = -logf(se);
-        if (round_lp) lp = round_bf16(lp);
-        int fin = finished[b];
-        if (bi == eos) fin = 1;
-        if (lane == 0) {
-            seqs[(size_t)b * max_len + t] = bi;
-            logprobs[(size_t)b * max_len + t] = lp;
-            finished[b] = fin;
-            g.state[b] = grammar_advance(g, allow, bi, V);
-        }
-        cnt += fin ? 0 : 1;
-        if (emb && t + 1 < Tmax)
-            for (int i = lane * 4; i < E; i += 256) {
-                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)bi * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
-                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
-            }
-    }
-    if (lane == 0) unfinished[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int w = 0; w < nw; ++w) tot += unfinished[w];
-        finished[B] = tot;
-        step[0] = t + 1;
-        step[1] = step[1] + 1;
-    }
-}
-
-// sample_logprob_kernel under the automaton
-__global__ __launch_bounds__(256) void grammar_sample_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
-                                                             const int32_t *step, int32_t *finished, int eos, int round_lp,
-                                                             const float *uniforms, int top_k, float inv_temperature, const float *emb,
-                                                             const float *pos, float *xnext, int E, int Tmax, GrammarArgs g) {
-    __shared__ float sv[4][64];
-    __shared__ int si[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x * 4 + wave;
-    if (b >= B) return;
-    const int t = step[0];
-    float lp;
-    const int16_t *allow = grammar_row(g, b, V, lane);
-    const int tok = topk_draw_row_masked(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
-                                         uniforms[(size_t)b * max_len + t], lp, allow);
-    if (round_lp) lp = round_bf16(lp);
-    if (lane == 0) {
-        seqs[(size_t)b * max_len + t] = tok;
-        logprobs[(size_t)b * max_len + t] = lp;
-        if (tok == eos) finished[b] = 1;
-        g.state[b] = grammar_advance(g, allow, tok, V);
-    }
-    if (emb && t + 1 < Tmax)
-        for (int i = lane * 4; i < E; i += 256) {
-            const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
-            *reinterpret_cast<float4 *>(xnext + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
-        }
-}
-
-// slot_argmax_kernel under the automaton: a finished or idle row reads and writes no state
-__global__ __launch_bounds__(1024) void slot_grammar_argmax_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
-                                                                  int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap,
-                                                                  int eos, int round_lp, const float *emb, const float *pos, float *x, int E,
-                                                                  int Tmax, GrammarArgs g) {
-    __shared__ int unfinished[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int cnt = 0;
-    const int nw = blockDim.x >> 6;
-    for (int b = wave; b < B; b += nw) {
-        if (finished[b]) continue;   // wave-uniform
-        const int t = slot_t[b];
-        const float *lg = logits + (size_t)b * V;
-        float best;
-        int bi;
-        const int16_t *allow = grammar_row(g, b, V, lane);
-        const float se = row_argmax_sumexp_masked(lg, V, lane, best, bi, allow);
-        float lp = -logf(se);
-        if (round_lp) lp = round_bf16(lp);
-        const bool fin = bi == eos || t >= slot_cap[b] - 1;
-        if (lane == 0) {
-            seqs[(size_t)b * max_len + t] = bi;
-            logprobs[(size_t)b * max_len + t] = lp;
-            if (fin) finished[b] = 1;
-            else slot_t[b] = t + 1;
-            g.state[b] = grammar_advance(g, allow, bi, V);
-        }
-        if (!fin) {   // t + 1 <= cap - 1 < max_len <= Tmax
-            cnt += 1;
-            for (int i = lane * 4; i < E; i += 256) {
-                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)bi * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
-                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
-            }
-        }
-    }
-    if (lane == 0) unfinished[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int w = 0; w < nw; ++w) tot += unfinished[w];
-        finished[B] = tot;
-        const int nxt = step[1] + 1;
-        step[1] = nxt >= Tmax ? 0 : nxt;
-    }
-}
-
-// slot_sample_kernel under the automaton (the same ticket hand-off closes the step)
-__global__ __launch_bounds__(256) void slot_grammar_sample_kernel(const float *logits, int V, int B, int64_t *seqs, float *logprobs, int max_len,
-                                                                  int32_t *step, int32_t *finished, int32_t *slot_t, const int32_t *slot_cap,
-                                                                  int eos, int round_lp, const float *uniforms, int ld_uniforms,
-                                                                  const int32_t *urow, int top_k, float inv_temperature, const float *emb,
-                                                                  const float *pos, float *x, int E, int Tmax, unsigned *ticket, GrammarArgs g) {
-    __shared__ float sv[4][64];
-    __shared__ int si[4][64];
-    __shared__ int is_last;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
-        if (finished[b]) continue;   // wave-uniform
-        const int t = slot_t[b];
-        float lp;
-        const int16_t *allow = grammar_row(g, b, V, lane);
-        const int tok = topk_draw_row_masked(logits + (size_t)b * V, V, lane, sv[wave], si[wave], top_k, inv_temperature,
-                                             uniforms[(size_t)urow[b] * ld_uniforms + t], lp, allow);
-        if (round_lp) lp = round_bf16(lp);
-        const bool fin = tok == eos || t >= slot_cap[b] - 1;
-        if (lane == 0) {
-            seqs[(size_t)b * max_len + t] = tok;
-            logprobs[(size_t)b * max_len + t] = lp;
-            if (fin) __hip_atomic_store(finished + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else slot_t[b] = t + 1;
-            g.state[b] = grammar_advance(g, allow, tok, V);
-        }
-        if (!fin)
-            for (int i = lane * 4; i < E; i += 256) {
-                const float4 ev = *reinterpret_cast<const float4 *>(emb + (size_t)tok * E + i), pv = *reinterpret_cast<const float4 *>(pos + (size_t)(t + 1) * E + i);
-                *reinterpret_cast<float4 *>(x + (size_t)b * E + i) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
-            }
-    }
-    if (gridDim.x > 1) {
-        __threadfence();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned n = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            is_last = n == gridDim.x - 1;
-            if (is_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-    if (gridDim.x > 1 && !is_last) return;
-    if (wave == 0) {
-        int cnt = 0;
-        for (int b = lane; b < B; b += 64) cnt += __hip_atomic_load(finished + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 1;
-        cnt = (int)wave_sum((float)cnt);
-        if (lane == 0) {
-            finished[B] = cnt;
-            const int nxt = step[1] + 1;
-            step[1] = nxt >= Tmax ? 0 : nxt;
-        }
-    }
-}
 
 }  // namespace
 
@@ -978,70 +695,71 @@ int launch_advance_cache(const AcaiDecoder *d, hipStream_t st) {
     return 0;
 }
 
-// `chained`: the kernel also writes the next step's input x
-int launch_argmax_logprob(const AcaiDecoder *d, bool chained, hipStream_t st) {
-    hipLaunchKernelGGL(argmax_logprob_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
-                       d->finished, d->eos, round_lp(d), 1, chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax);
-    ACAI_LAUNCH_CHECK("argmax_logprob");
-    return 0;
+// ---- the selection launches: the kernels' argument structs from the descriptors, once ---------------------------------------------------
+// `chained`: the kernel also writes the next step's input x (a slot step always does)
+static SelArgs select_args(const AcaiDecoder *d, bool chained) {
+    return SelArgs{d->logits, d->V, d->B, d->max_len, d->eos, round_lp(d), d->E, d->Tmax, d->seqs, d->logprobs, d->step, d->finished,
+                   chained ? d->emb : nullptr, d->pos, d->x};
 }
-
+static SlotArgs slot_args(const AcaiSlots *sl) { return SlotArgs{sl->t, sl->cap}; }
+static PromptArgs prompt_args(const AcaiPrompt *pr) { return PromptArgs{pr->tok, pr->len, pr->pitch}; }
 static GrammarArgs grammar_args(const AcaiGrammar *gr) { return GrammarArgs{gr->next, gr->resync, gr->state, gr->states, gr->start}; }
+// a static step draws row b's uniforms[b][t] (pitch max_len); a slot step uniforms[urow[b]][t]
+static DrawArgs draw_args(const AcaiDecoder *d, const float *uniforms, int ld, const int32_t *urow, int top_k, float temperature) {
+    return DrawArgs{uniforms, ld, urow, top_k, 1.0f / temperature, (unsigned *)d->tickets};
+}
 
-// the grammar-constrained forms of launch_argmax_logprob / launch_sample_logprob / launch_slot_argmax / launch_slot_sample
-int launch_grammar_argmax(const AcaiDecoder *d, const AcaiGrammar *gr, bool chained, hipStream_t st) {
-    hipLaunchKernelGGL(grammar_argmax_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
-                       d->finished, d->eos, round_lp(d), chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax,
-                       grammar_args(gr));
-    ACAI_LAUNCH_CHECK("grammar_argmax");
+template <bool SLOT, bool GRAMMAR, bool PROMPT>
+static int launch_greedy(const AcaiDecoder *d, bool chained, part<SLOT, SlotArgs> s, part<GRAMMAR, GrammarArgs> g, part<PROMPT, PromptArgs> p,
+                         const char *name, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_select_kernel<SLOT, GRAMMAR, PROMPT>), dim3(1), row_waves(d), 0, st, select_args(d, chained), s, g, p);
+    ACAI_LAUNCH_CHECK(name);
     return 0;
 }
 
+// One wave per row.  A static step is followed by the loop bookkeeping; a slot step without arrival counters (d->tickets) is one workgroup
+// that takes every row and closes the step itself.
+template <bool SLOT, bool GRAMMAR>
+static int launch_sample(const AcaiDecoder *d, bool chained, DrawArgs w, part<SLOT, SlotArgs> s, part<GRAMMAR, GrammarArgs> g, const char *name,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(sample_select_kernel<SLOT, GRAMMAR>), dim3(SLOT && !d->tickets ? 1 : cdiv(d->B, 4)), dim3(256), 0, st,
+                       select_args(d, chained), w, s, g);
+    if (!SLOT) hipLaunchKernelGGL(sample_bookkeeping_kernel, dim3(1), dim3(64), 0, st, d->B, d->step, d->finished);
+    ACAI_LAUNCH_CHECK(name);
+    return 0;
+}
+
+int launch_argmax_logprob(const AcaiDecoder *d, bool chained, hipStream_t st) {
+    return launch_greedy<false, false, false>(d, chained, {}, {}, {}, "argmax_logprob", st);
+}
+int launch_prompt_logprob(const AcaiDecoder *d, const AcaiPrompt *pr, bool chained, hipStream_t st) {
+    return launch_greedy<false, false, true>(d, chained, {}, {}, prompt_args(pr), "prompt_logprob", st);
+}
+int launch_grammar_argmax(const AcaiDecoder *d, const AcaiGrammar *gr, bool chained, hipStream_t st) {
+    return launch_greedy<false, true, false>(d, chained, {}, grammar_args(gr), {}, "grammar_argmax", st);
+}
+int launch_slot_argmax(const AcaiDecoder *d, const AcaiSlots *sl, hipStream_t st) {
+    return launch_greedy<true, false, false>(d, true, slot_args(sl), {}, {}, "slot_argmax", st);
+}
+int launch_slot_grammar_argmax(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *gr, hipStream_t st) {
+    return launch_greedy<true, true, false>(d, true, slot_args(sl), grammar_args(gr), {}, "slot_grammar_argmax", st);
+}
+int launch_sample_logprob(const AcaiDecoder *d, const float *uniforms, int top_k, float temperature, bool chained, hipStream_t st) {
+    return launch_sample<false, false>(d, chained, draw_args(d, uniforms, d->max_len, nullptr, top_k, temperature), {}, {}, "sample_logprob", st);
+}
 int launch_grammar_sample(const AcaiDecoder *d, const AcaiGrammar *gr, const float *uniforms, int top_k, float temperature, bool chained,
                           hipStream_t st) {
-    hipLaunchKernelGGL(grammar_sample_kernel, dim3(cdiv(d->B, 4)), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len,
-                       d->step, d->finished, d->eos, round_lp(d), uniforms, top_k, 1.0f / temperature,
-                       chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax, grammar_args(gr));
-    hipLaunchKernelGGL(sample_bookkeeping_kernel, dim3(1), dim3(64), 0, st, d->B, d->step, d->finished);
-    ACAI_LAUNCH_CHECK("grammar_sample");
-    return 0;
+    return launch_sample<false, true>(d, chained, draw_args(d, uniforms, d->max_len, nullptr, top_k, temperature), {}, grammar_args(gr),
+                                      "grammar_sample", st);
 }
-
-int launch_slot_grammar_argmax(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *gr, hipStream_t st) {
-    hipLaunchKernelGGL(slot_grammar_argmax_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
-                       d->finished, sl->t, (const int32_t *)sl->cap, d->eos, round_lp(d), (const float *)d->emb, (const float *)d->pos, d->x,
-                       d->E, d->Tmax, grammar_args(gr));
-    ACAI_LAUNCH_CHECK("slot_grammar_argmax");
-    return 0;
+int launch_slot_sample(const AcaiDecoder *d, const AcaiSlots *sl, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k,
+                       float temperature, hipStream_t st) {
+    return launch_sample<true, false>(d, true, draw_args(d, uniforms, ld_uniforms, urow, top_k, temperature), slot_args(sl), {}, "slot_sample", st);
 }
-
 int launch_slot_grammar_sample(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *gr, const float *uniforms, int ld_uniforms,
                                const int32_t *urow, int top_k, float temperature, hipStream_t st) {
-    hipLaunchKernelGGL(slot_grammar_sample_kernel, dim3(d->tickets ? cdiv(d->B, 4) : 1), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs,
-                       d->logprobs, d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos, round_lp(d), uniforms,
-                       ld_uniforms, urow, top_k, 1.0f / temperature, (const float *)d->emb, (const float *)d->pos, d->x, d->E, d->Tmax,
-                       (unsigned *)d->tickets, grammar_args(gr));
-    ACAI_LAUNCH_CHECK("slot_grammar_sample");
-    return 0;
-}
-
-// the prompted form of launch_argmax_logprob
-int launch_prompt_logprob(const AcaiDecoder *d, const AcaiPrompt *pr, bool chained, hipStream_t st) {
-    hipLaunchKernelGGL(prompt_logprob_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
-                       d->finished, d->eos, round_lp(d), pr->tok, pr->len, pr->pitch, chained ? (const float *)d->emb : nullptr,
-                       (const float *)d->pos, d->x, d->E, d->Tmax);
-    ACAI_LAUNCH_CHECK("prompt_logprob");
-    return 0;
-}
-
-// the sampling kernel, then the loop bookkeeping
-int launch_sample_logprob(const AcaiDecoder *d, const float *uniforms, int top_k, float temperature, bool chained, hipStream_t st) {
-    hipLaunchKernelGGL(sample_logprob_kernel, dim3(cdiv(d->B, 4)), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs, d->max_len, d->step,
-                       d->finished, d->eos, round_lp(d), uniforms, top_k, 1.0f / temperature,
-                       chained ? (const float *)d->emb : nullptr, (const float *)d->pos, d->x, d->E, d->Tmax);
-    hipLaunchKernelGGL(sample_bookkeeping_kernel, dim3(1), dim3(64), 0, st, d->B, d->step, d->finished);
-    ACAI_LAUNCH_CHECK("sample_logprob");
-    return 0;
+    return launch_sample<true, true>(d, true, draw_args(d, uniforms, ld_uniforms, urow, top_k, temperature), slot_args(sl), grammar_args(gr),
+                                     "slot_grammar_sample", st);
 }
 
 // the beam selection, then the loop bookkeeping
@@ -1063,25 +781,6 @@ int launch_slot_arm(const AcaiDecoder *d, const AcaiSlots *sl, const int32_t *ro
                        d->finished, sl->t, sl->first, sl->cap, (const int32_t *)d->step, d->bos, d->pad,
                        (const float *)d->emb, (const float *)d->pos, d->x, d->E);
     ACAI_LAUNCH_CHECK("slot_arm");
-    return 0;
-}
-
-int launch_slot_argmax(const AcaiDecoder *d, const AcaiSlots *sl, hipStream_t st) {
-    hipLaunchKernelGGL(slot_argmax_kernel, dim3(1), row_waves(d), 0, st, d->logits, d->V, d->B, d->seqs,
-                       d->logprobs, d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos,
-                       round_lp(d), (const float *)d->emb, (const float *)d->pos, d->x, d->E, d->Tmax);
-    ACAI_LAUNCH_CHECK("slot_argmax");
-    return 0;
-}
-
-int launch_slot_sample(const AcaiDecoder *d, const AcaiSlots *sl, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k,
-                       float temperature, hipStream_t st) {
-    // one wave per row; without arrival counters (d->tickets) one workgroup takes every row and closes the step itself
-    hipLaunchKernelGGL(slot_sample_kernel, dim3(d->tickets ? cdiv(d->B, 4) : 1), dim3(256), 0, st, d->logits, d->V, d->B, d->seqs, d->logprobs,
-                       d->max_len, d->step, d->finished, sl->t, (const int32_t *)sl->cap, d->eos, round_lp(d),
-                       uniforms, ld_uniforms, urow, top_k, 1.0f / temperature, (const float *)d->emb, (const float *)d->pos, d->x, d->E, d->Tmax,
-                       (unsigned *)d->tickets);
-    ACAI_LAUNCH_CHECK("slot_sample");
     return 0;
 }
 

@@ -839,7 +839,7 @@ class DecodeEngine:
             self._arm_beam(B)
         if self._mode[0] in ("grammar", "grammar_sample"):
             self.gram_state[:B].fill_(self._gram_desc.start)
-        # input of the first step (<bos> at position 1, quirk Q1); each step's argmax / sampling kernel writes the next step's input
+        # input of the first step (<bos> at position 1, quirk Q1); each step's selection kernel (greedy_select_kernel / sample_select_kernel) writes the next step's input
         _lib.check(_lib.lib().acai_decode_embed(ctypes.byref(self._desc), ops._st()), "acai_decode_embed")
         self._x_valid = True
 
@@ -903,7 +903,7 @@ class DecodeEngine:
 
     def launch_steps(self, n, use_graph=True):
         """Enqueue n decode steps on the current stream (graphs of STEPS_PER_GRAPH steps + single-step graphs for the rest).
-        A chained step takes its input embedding from d->x, which the PREVIOUS step's argmax / sampling kernel wrote (acai_decode_step no
+        A chained step takes its input embedding from d->x, which the PREVIOUS step's selection kernel wrote (acai_decode_step no
         longer embeds by itself).  The stepwise entry points (logits_step / hidden_step) overwrite d->x; after one of them the input is
         rebuilt from the device-side sequence state (`acai_decode_embed`: seqs[:, t-1] at position t) before the chain goes on."""
         if n > 0 and not getattr(self, "_x_valid", False):

@@ -30,7 +30,9 @@ Bars:
      result; inference(grammar=) == streamed_inference(grammar=); FP8 memory cache;
   7. the scan kernel against TokenAutomaton.violations, LDS path and global path;
   8. the C ABI's argument checks;
-  9. one grpo_update with constrained rollouts and the automaton's well-formedness term."""
+  9. one grpo_update with constrained rollouts and the automaton's well-formedness term;
+ 10. every selection form (greedy / sampled x static / slot x plain / grammar, prompted greedy) at 18 rows - more than the 16 waves of the
+     workgroup that closes a greedy step, five sampling workgroups - on a one-layer decoder, against the restatements, bar 2's bounds."""
 import ctypes
 import math
 
@@ -742,3 +744,96 @@ def test_grpo_update_with_a_grammar(dev, slots):
                                         grammar=a)
         assert all(math.isfinite(v) for v in (r2, ce2) + c2._vals()) and -rc.gamma <= c2.wellformedness_scores <= 1.0
         assert c2.wellformedness_scores != 0.0
+
+
+# ---- 10. every selection form at more rows than the closing workgroup has waves ---------------------------------------------------------------
+WIDE_B, WIDE_T, WIDE_K = 18, 10, 5
+WIDE_CAPS = [WIDE_T, 3, WIDE_T - 2, 5, 2, WIDE_T, 7, 4, WIDE_T - 1, 6, WIDE_T, 3, 8, 2, WIDE_T, 5, WIDE_T - 3, WIDE_T]
+
+
+def _wide_case(cdt, dev):
+    """A one-layer decoder (E 1024, 16 heads) on 18 memories of 9 .. 60 rows, max_len 10."""
+    key = ("wide", cdt)
+    if key not in _CACHE:
+        dec = _decoder(T=WIDE_T, L=1, E=1024, H=16, Fd=4096)
+        g = torch.Generator().manual_seed(23)
+        lens = [9 + 3 * i for i in range(WIDE_B)]
+        lat = torch.zeros(WIDE_B, max(lens), 1024)
+        mask = torch.ones(WIDE_B, max(lens), dtype=torch.bool)
+        for i, n in enumerate(lens):
+            lat[i, :n] = torch.randn(n, 1024, generator=g).to(torch.bfloat16).float()
+            mask[i, :n] = False
+        _CACHE[key] = (_vit(dec, 24, cdt, dev), lat.to(dev), mask.to(dev))
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("cdt", DTYPES, ids=IDS)
+def test_every_selection_form_at_18_rows(dev, cdt):
+    """The nine selection forms (greedy / sampled x static / slot x plain / grammar, and prompted greedy) at B = 18 - rows 16 and 17 are the
+    second pass of a wave of the one workgroup that closes a greedy step, and the fifth sampling workgroup is half empty - against the
+    float64 restatements on the host-stepped logits at the same B: tests/grammar_reference.py with the case's restrictive automaton for the
+    grammar forms and a table that allows everything for the plain ones, tests/prompt_reference.py's selection rule for the prompted
+    form.  A slot run (18 slots, caps 2 .. 10) must give every row what the restatement gives it up to its cap.  Tokens and masks equal;
+    log-probs within bar 2's bounds (_check_lps)."""
+    import prompt_reference as PR
+    from acai_omr_amd import engine as EG
+    m, lat, mask = _wide_case(cdt, dev)
+    bf = cdt == torch.bfloat16
+    B, T, K, caps = WIDE_B, WIDE_T, WIDE_K, WIDE_CAPS
+    bos, pad = m.decoder.bos_idx, m.decoder.pad_idx
+    free = _permissive(m, False)
+    tight, _ = _restrictive(m, _greedy(m, lat, mask, T, bf))
+    U = torch.rand(B, T, generator=torch.Generator().manual_seed(14))
+    # prompts of seeded random ids without the specials: row 0 none, row 1 max_len - 1, the rest 1 .. max_len - 2 tokens
+    ok = torch.tensor([i for i in range(m.decoder.vocab_size) if i not in _ids(m).values()])
+    g = torch.Generator().manual_seed(33)
+    prompts = [ok[torch.randint(len(ok), (n,), generator=g)] for n in [0, T - 1] + [1 + (4 * i) % (T - 2) for i in range(2, B)]]
+    eng = m.decoder.decoder_blocks.engine(dev)
+    assert eng.tickets is not None     # a slot sampling step is five workgroups closed by the last to arrive
+
+    def restated(a, sampled):
+        with torch.no_grad(), _ctx(bf):
+            fn = _host_logits(m, lat, mask, T)
+            if sampled:
+                return GR.constrained_sample(fn, a, B, T, bos, U, K, TEMPERATURE)[:2]
+            return GR.constrained_greedy(fn, a, B, T, bos)[:2]
+
+    def restated_prompt():
+        rs = torch.full((B, T), bos, dtype=torch.int64)
+        rlp = torch.zeros(B, T, dtype=torch.float64)
+        with torch.no_grad(), _ctx(bf):
+            fn = _host_logits(m, lat, mask, T)
+            for t in range(1, T):
+                lg = fn(rs[:, t - 1], t)
+                for b in range(B):
+                    rs[b, t], rlp[b, t], _ = PR.select(lg[b].tolist(), t, [int(v) for v in prompts[b]])
+        return rs, rlp
+
+    def check(what, out, ref, row_caps):
+        rs, rlp = ref
+        rmask = m.create_inference_mask(rs) & (torch.arange(T) < torch.tensor(row_caps).unsqueeze(1))
+        n = int(rmask.sum(dim=-1).max())
+        seqs, lps, mk = (x.cpu() for x in out)
+        assert seqs.shape[1] == n and torch.equal(mk, rmask[:, :n]), what
+        assert torch.equal(seqs, rs.masked_fill(~rmask, pad)[:, :n]), (what, (seqs != rs.masked_fill(~rmask, pad)[:, :n]).nonzero().tolist())
+        live = rmask[:, :n].clone()
+        live[:, 0] = False
+        print(what, end=": ")
+        _check_lps(lps, rlp[:, :n], live, bf)
+        assert bool((lps[~mk] == 0).all()), what
+
+    def slots(**kw):
+        with torch.no_grad(), _ctx(bf):
+            mem32, lens = EG.unpad_rows(lat, mask)
+            return m._continuous_packed(mem32, None, lens, caps, B, **kw)
+
+    full = [T] * B
+    for a, name in ((free, "plain"), (tight, "grammar")):
+        kw = {} if a is free else {"grammar": a}
+        ref = restated(a, False)
+        check(f"{name} greedy", _greedy(m, lat, mask, T, bf, **kw), ref, full)
+        check(f"{name} slot greedy", slots(**kw), ref, caps)
+        ref = restated(a, True)
+        check(f"{name} sampled", _sample(m, lat, mask, T, bf, U.to(dev), K, **kw), ref, full)
+        check(f"{name} slot sampled", slots(sample=(K, TEMPERATURE), uniforms=U.to(dev), **kw), ref, caps)
+    check("prompted greedy", _greedy(m, lat, mask, T, bf, prefix=prompts), restated_prompt(), full)
