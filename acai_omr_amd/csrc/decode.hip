@@ -268,9 +268,10 @@ static int check_step(const AcaiDecoder *d, const char *fn, bool chained) {
     return chained ? check_x_valid(d, fn, "acai_decode_embed", "sequence") : 0;
 }
 
-// The draw of a sampling step; a slot step (slot != 0) also takes the uniforms' pitch and the slots' rows of it
-static int check_draw(const AcaiDecoder *d, const char *fn, const float *uniforms, int top_k, float temperature, int slot = 0, int ld_uniforms = 0,
-                      const int32_t *urow = nullptr) {
+// The draw of a sampling step; a slot step (slot != 0) also takes the uniforms' pitch and the slots' rows of it (declared in
+// decode_internal.h: acai_debug_decode_select in decode_select.hip applies the same checks)
+int check_draw(const AcaiDecoder *d, const char *fn, const float *uniforms, int top_k, float temperature, int slot, int ld_uniforms,
+               const int32_t *urow) {
     ACAI_CHECK_ARG(uniforms, "%s: null uniforms", fn);
     ACAI_CHECK_ARG(!slot || urow, "%s: null urow", fn);
     ACAI_CHECK_ARG(!slot || ld_uniforms >= d->max_len, "%s: ld_uniforms %d is below max_len %d", fn, ld_uniforms, d->max_len);

@@ -90,9 +90,16 @@ __device__ __forceinline__ int topk_draw_row(const float *lg, int V, int lane, f
         if (lane >= o) cdf += up;
     }
     const float target = u * sumT;
-    const unsigned long long hit = __ballot(in && cdf > target);
+    // MASKED: the entries past the allowed set hold no token and take no part in the draw.  Their prefix sums add zeros to the last real
+    // entry's, but in another order of additions (the scan pairs differently per lane), so one of them can exceed a target near the top of
+    // the CDF that the last real entry's own prefix does not: it must not be hit, and the rounding fallback is not k - 1.
+    // (Unmasked, every one of the k entries holds a token.  Where the tail's expf underflows to 0 - a low temperature - the same rounding, or
+    // the fallback k - 1, can draw a tail entry of fp32 probability 0 at a u within an ulp or so of 1: a valid kept token, accepted.)
+    bool live = in;
+    if constexpr (MASKED) live = in && x > -INFINITY;
+    const unsigned long long hit = __ballot(live && cdf > target);
     int last = k - 1;                                              // rounding at the top of the CDF: last kept entry
-    if constexpr (MASKED) last = max(__popcll(__ballot(in && x > -INFINITY)), 1) - 1;   // (not k - 1: entries past the allowed set hold no token)
+    if constexpr (MASKED) last = max(__popcll(__ballot(live)), 1) - 1;
     const int r = hit ? __builtin_ctzll(hit) : last;
     lp = (sv[r] - m) - logf(sum1);
     return si[r];
@@ -807,6 +814,69 @@ int launch_spec_prompt_accept(const AcaiDecoder *d, const AcaiSpec *sp, const Ac
     hipLaunchKernelGGL(spec_accept_kernel<SpecPromptArgs>, dim3(1), row_waves(d), sizeof(int) * 2 * (size_t)d->B, st, a);
     ACAI_LAUNCH_CHECK("spec_prompt_accept");
     return 0;
+}
+
+// Test entry (declared and documented in acai_omr_hip.h): ONE selection launch on the logits the caller wrote, through the launch helper the
+// step of that form calls.  No layer runs and check_decoder is not applied: the descriptor holds the fields selection reads and nothing else.
+// The time index a kernel reads on the device (step[0], a slot's t) is the caller's to keep inside the rows, as it is for the steps.
+extern "C" int acai_debug_decode_select(int form, const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *g, const AcaiPrompt *pr,
+                                        const AcaiBeam *bs, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k,
+                                        float temperature, int chained, void *stream) {
+    const char *fn = "acai_debug_decode_select";
+    ACAI_CHECK_ARG(form >= ACAI_SELECT_ARGMAX && form <= ACAI_SELECT_BEAM, "%s: form %d outside [0, 9]", fn, form);
+    const bool beam = form == ACAI_SELECT_BEAM;
+    const bool slot = form == ACAI_SELECT_SLOT_ARGMAX || form == ACAI_SELECT_SLOT_GRAMMAR_ARGMAX || form == ACAI_SELECT_SLOT_SAMPLE ||
+                      form == ACAI_SELECT_SLOT_GRAMMAR_SAMPLE;
+    const bool grammar = form == ACAI_SELECT_GRAMMAR_ARGMAX || form == ACAI_SELECT_SLOT_GRAMMAR_ARGMAX || form == ACAI_SELECT_GRAMMAR_SAMPLE ||
+                         form == ACAI_SELECT_SLOT_GRAMMAR_SAMPLE;
+    const bool sampled = form >= ACAI_SELECT_SAMPLE && form <= ACAI_SELECT_SLOT_GRAMMAR_SAMPLE;
+    ACAI_CHECK_ARG(d, "%s: null decoder", fn);
+    ACAI_CHECK_ARG(d->logits && d->step && d->finished, "%s: null logits / step / finished", fn);
+    ACAI_CHECK_ARG(beam || (d->seqs && d->logprobs), "%s: null seqs / logprobs", fn);
+    ACAI_CHECK_ARG(d->B >= 1 && d->V >= 1 && d->E >= 1 && d->Tmax >= 1 && d->max_len > 1, "%s: bad dims B=%d V=%d E=%d Tmax=%d max_len=%d", fn,
+                   d->B, d->V, d->E, d->Tmax, d->max_len);
+    ACAI_CHECK_ARG(chained || !(slot || beam), "%s: a slot or beam selection always writes the next input (chained = 0 with form %d)", fn, form);
+    ACAI_CHECK_ARG(!chained || (d->emb && d->pos && d->x), "%s: a chained selection needs emb, pos and x", fn);
+    ACAI_CHECK_ARG(!chained || d->E % 4 == 0, "%s: a chained selection needs E %% 4 == 0 (E=%d)", fn, d->E);
+    if (slot) {
+        ACAI_CHECK_ARG(sl && sl->t && sl->cap && sl->rows >= d->B, "%s: null slot state or rows < B", fn);
+        ACAI_CHECK_ARG(d->max_len <= d->Tmax, "%s: a slot selection needs max_len <= Tmax (max_len=%d Tmax=%d)", fn, d->max_len, d->Tmax);
+    }
+    if (grammar) {   // (acai_decode_grammar_step's conditions but its vocabulary bound, which is the sampled forms': check_draw below)
+        ACAI_CHECK_ARG(g && g->next && g->resync && g->state, "%s: null grammar tables or state", fn);
+        ACAI_CHECK_ARG(g->states >= 1 && g->states <= 32767, "%s: states %d outside [1, 32767]", fn, g->states);
+        ACAI_CHECK_ARG(g->start >= 0 && g->start < g->states, "%s: start %d outside [0, states = %d)", fn, g->start, g->states);
+        ACAI_CHECK_ARG(g->rows >= d->B, "%s: grammar rows %d below B = %d", fn, g->rows, d->B);
+    }
+    if (form == ACAI_SELECT_PROMPT) {
+        ACAI_CHECK_ARG(pr && pr->tok && pr->len, "%s: null prompt tables", fn);
+        ACAI_CHECK_ARG(pr->pitch >= d->max_len && pr->rows >= d->B, "%s: needs prompt pitch >= max_len and rows >= B (pitch=%d max_len=%d rows=%d)",
+                       fn, pr->pitch, d->max_len, pr->rows);
+    }
+    if (sampled) {
+        int rc = check_draw(d, fn, uniforms, top_k, temperature, slot ? 1 : 0, ld_uniforms, urow);
+        if (rc) return rc;
+    }
+    if (beam) {
+        ACAI_CHECK_ARG(bs && bs->anc && bs->tok && bs->lp && bs->cum && bs->len, "%s: null beam state", fn);
+        ACAI_CHECK_ARG(bs->K >= 1 && bs->K <= BEAM_MAX && d->B % bs->K == 0 && bs->rows >= d->B && bs->pitch >= d->max_len && d->V <= 512,
+                       "%s: needs 1 <= K <= 16 dividing B, rows >= B, pitch >= max_len, vocabulary <= 512 (K=%d B=%d rows=%d pitch=%d V=%d)", fn,
+                       bs->K, d->B, bs->rows, bs->pitch, d->V);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const bool ch = chained != 0;
+    switch (form) {
+        case ACAI_SELECT_ARGMAX: return launch_argmax_logprob(d, ch, st);
+        case ACAI_SELECT_PROMPT: return launch_prompt_logprob(d, pr, ch, st);
+        case ACAI_SELECT_GRAMMAR_ARGMAX: return launch_grammar_argmax(d, g, ch, st);
+        case ACAI_SELECT_SLOT_ARGMAX: return launch_slot_argmax(d, sl, st);
+        case ACAI_SELECT_SLOT_GRAMMAR_ARGMAX: return launch_slot_grammar_argmax(d, sl, g, st);
+        case ACAI_SELECT_SAMPLE: return launch_sample_logprob(d, uniforms, top_k, temperature, ch, st);
+        case ACAI_SELECT_GRAMMAR_SAMPLE: return launch_grammar_sample(d, g, uniforms, top_k, temperature, ch, st);
+        case ACAI_SELECT_SLOT_SAMPLE: return launch_slot_sample(d, sl, uniforms, ld_uniforms, urow, top_k, temperature, st);
+        case ACAI_SELECT_SLOT_GRAMMAR_SAMPLE: return launch_slot_grammar_sample(d, sl, g, uniforms, ld_uniforms, urow, top_k, temperature, st);
+        default: return launch_beam_select(d, bs, st);
+    }
 }
 
 // (declared and documented in acai_omr_hip.h; it takes the slot state as bare pointers, not through the decoder descriptor, so that it can

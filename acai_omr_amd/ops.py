@@ -1235,6 +1235,74 @@ def debug_decode_attn_group(q, kc, vc, seq_off, seq_len, H, dh, dhp, group, chun
     return out
 
 
+(SELECT_ARGMAX, SELECT_PROMPT, SELECT_GRAMMAR_ARGMAX, SELECT_SLOT_ARGMAX, SELECT_SLOT_GRAMMAR_ARGMAX, SELECT_SAMPLE, SELECT_GRAMMAR_SAMPLE,
+ SELECT_SLOT_SAMPLE, SELECT_SLOT_GRAMMAR_SAMPLE, SELECT_BEAM) = range(10)   # acai_debug_decode_select's `form`
+
+
+def debug_decode_select(form, logits, seqs, logprobs, step, finished, *, max_len, Tmax, eos, bos=0, pad=0, emb=None, pos=None, x=None,
+                        tickets=None, round_lp=False, chained=True, slots=None, grammar=None, prompt=None, beam=None, uniforms=None,
+                        ld_uniforms=0, urow=None, top_k=1, temperature=1.0, B=None, V=None, E=None):
+    """Test entry (acai_debug_decode_select, see the header): one token-selection launch on the logits the caller wrote.  logits [B, V] fp32,
+    seqs [B, max_len] int64, logprobs [B, max_len] fp32, step [2] int32, finished [B + 1] int32, emb [V, E] / pos [Tmax, E] / x [B, E] fp32,
+    tickets int32 (one zeroed counter) or None.  slots = dict(t, cap) int32 [B]; grammar = dict(next int16 [S, V], resync int16 [V], state
+    int32 [B], start); prompt = dict(tok int32 [B, pitch], len int32 [B]); beam = dict(K, anc int32 / tok int64 / lp fp32 [2, B, pitch],
+    cum fp32 [B], len int32 [B]).  Any tensor may be None and B / V / E may be overridden: the entry refuses what its form needs and lacks.
+    Everything is written in place."""
+    d = _lib.AcaiDecoder()
+    d.B = int(B if B is not None else logits.shape[0])
+    d.V = int(V if V is not None else logits.shape[1])
+    d.E = int(E if E is not None else (emb.shape[1] if emb is not None else 4))
+    d.max_len, d.Tmax, d.eos, d.bos, d.pad = int(max_len), int(Tmax), int(eos), int(bos), int(pad)
+    d.flags = GEMM_ROUND_BF16 if round_lp else 0
+    for name, t, dt in (("logits", logits, torch.float32), ("seqs", seqs, torch.int64), ("logprobs", logprobs, torch.float32),
+                        ("step", step, torch.int32), ("finished", finished, torch.int32), ("emb", emb, torch.float32),
+                        ("pos", pos, torch.float32), ("x", x, torch.float32), ("tickets", tickets, torch.int32)):
+        if t is not None:
+            assert _chk(t, name, dt).is_contiguous(), name
+            setattr(d, name, t.data_ptr())
+
+    def ptrs(desc, src, fields):
+        for name, dt in fields:
+            t = src.get(name)
+            if t is not None:
+                assert _chk(t, name, dt).is_contiguous(), name
+                setattr(desc, name, t.data_ptr())
+        return desc
+
+    sl = gr = pr = bs = None
+    if slots is not None:
+        sl = ptrs(_lib.AcaiSlots(), slots, (("t", torch.int32), ("cap", torch.int32)))
+        sl.rows = int(slots.get("rows", d.B))
+    if grammar is not None:
+        gr = ptrs(_lib.AcaiGrammar(), grammar, (("next", torch.int16), ("resync", torch.int16), ("state", torch.int32)))
+        nxt = grammar.get("next")
+        gr.states = int(grammar.get("states", nxt.shape[0] if nxt is not None else 0))
+        gr.start, gr.rows = int(grammar.get("start", 0)), int(grammar.get("rows", d.B))
+    if prompt is not None:
+        pr = ptrs(_lib.AcaiPrompt(), prompt, (("tok", torch.int32), ("len", torch.int32)))
+        tk = prompt.get("tok")
+        pr.pitch, pr.rows = int(prompt.get("pitch", tk.shape[1] if tk is not None else 0)), int(prompt.get("rows", d.B))
+    if beam is not None:
+        bs = ptrs(_lib.AcaiBeam(), beam, (("anc", torch.int32), ("tok", torch.int64), ("lp", torch.float32), ("cum", torch.float32),
+                                          ("len", torch.int32)))
+        an = beam.get("anc")
+        bs.K, bs.rows = int(beam["K"]), int(beam.get("rows", an.shape[1] if an is not None else d.B))
+        bs.pitch = int(beam.get("pitch", an.shape[2] if an is not None else 0))
+    if uniforms is not None:
+        assert _chk(uniforms, "uniforms", torch.float32).is_contiguous()
+        if not ld_uniforms:
+            ld_uniforms = uniforms.shape[1]
+    if urow is not None:
+        assert _chk(urow, "urow", torch.int32).is_contiguous()
+
+    def ref(desc):
+        return None if desc is None else ctypes.byref(desc)
+
+    _lib.check(_lib.lib().acai_debug_decode_select(int(form), ref(d), ref(sl), ref(gr), ref(pr), ref(bs), _p(uniforms), int(ld_uniforms),
+                                                   _p(urow), int(top_k), float(temperature), 1 if chained else 0, _st()),
+               "acai_debug_decode_select")
+
+
 _BWD_WS = {}   # (device, stream) -> the one-pass attention backward's fp32 query-gradient workspace (used only inside a call, in stream order)
 
 

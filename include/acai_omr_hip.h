@@ -826,6 +826,40 @@ int acai_debug_decode_self_attn(int form, const float *q, int ldq, const void *k
 int acai_debug_decode_attn_group(const float *q, int ldq, const void *kc, const void *vc, const int64_t *seq_off, const int32_t *seq_len,
                                  float *partial, float *out, int ldo, int B, int H, int dh, int dhp, int chunk, int nsplit, int dtype,
                                  int round_out, uint32_t *tickets, int group, void *stream);
+/* TEST ENTRY (tests/test_gpu_select_kernels.py): ONE token-selection launch of a decode step on logits the caller wrote into dec->logits.  It
+ * exists for tests and calls exactly the launch helper the step of that form calls after its layers; no layer runs, and the descriptor need
+ * hold only what selection reads: logits, V, B, max_len, Tmax, E, eos, bos, pad, flags (ACAI_GEMM_ROUND_BF16: log-probs rounded to bf16),
+ * seqs, logprobs, step, finished, emb, pos, x, tickets.  Every other field is ignored (layers may be NULL).  form:
+ *   ACAI_SELECT_ARGMAX               acai_decode_step's selection              ACAI_SELECT_SAMPLE               acai_decode_sample_step's
+ *   ACAI_SELECT_PROMPT               acai_decode_prompt_step's (prompt)        ACAI_SELECT_GRAMMAR_SAMPLE       acai_decode_grammar_sample_step's
+ *   ACAI_SELECT_GRAMMAR_ARGMAX       acai_decode_grammar_step's (g)            ACAI_SELECT_SLOT_SAMPLE          acai_decode_slot_sample_step's
+ *   ACAI_SELECT_SLOT_ARGMAX          acai_decode_slot_step's (sl)              ACAI_SELECT_SLOT_GRAMMAR_SAMPLE  acai_decode_slot_grammar_sample_step's
+ *   ACAI_SELECT_SLOT_GRAMMAR_ARGMAX  acai_decode_slot_grammar_step's (sl, g)   ACAI_SELECT_BEAM                 acai_decode_beam_step's (bs)
+ * What each writes is what its step documents above.  sl / g / prompt / bs are read by the forms that name them and may be NULL otherwise
+ * (AcaiSlots.first is not read).  The draw (sampled forms): uniforms, top_k, temperature as in acai_decode_sample_step; a static form reads
+ * uniforms[b * max_len + t] and ignores ld_uniforms / urow, a slot form reads uniforms[urow[b] * ld_uniforms + t[b]].  chained != 0: the launch
+ * also writes the next step's input x (what a step does when E % 4 == 0); the slot and beam forms always do and refuse chained == 0.
+ * PRECONDITIONS the entry cannot check, as for the steps: the time index read on the device (step[0], a slot's t[b]) lies inside the rows
+ * (< max_len, < pitch), and every live row has at least one finite logit among the tokens it may choose (decode selection).
+ * Refused (rc < 0, acai_last_error() names acai_debug_decode_select, nothing launched): a form outside [0, 9]; a null decoder or a null
+ * logits / step / finished (seqs / logprobs but for the beam form); B, V, E or Tmax < 1 or max_len < 2; chained with a null emb / pos / x or
+ * E % 4 != 0; a slot form with null t / cap, rows < B or max_len > Tmax; a grammar form with null next / resync / state, states outside
+ * [1, 32767], start outside [0, states) or rows < B; the prompt form with null tok / len, pitch < max_len or rows < B; a sampled form with null
+ * uniforms, (slot) null urow or ld_uniforms < max_len, top_k outside [1, 64], temperature <= 0 or V > 512; the beam form with a null beam
+ * array, K outside [1, 16] or not dividing B, rows < B, pitch < max_len or V > 512.  The greedy forms take any V. */
+#define ACAI_SELECT_ARGMAX 0
+#define ACAI_SELECT_PROMPT 1
+#define ACAI_SELECT_GRAMMAR_ARGMAX 2
+#define ACAI_SELECT_SLOT_ARGMAX 3
+#define ACAI_SELECT_SLOT_GRAMMAR_ARGMAX 4
+#define ACAI_SELECT_SAMPLE 5
+#define ACAI_SELECT_GRAMMAR_SAMPLE 6
+#define ACAI_SELECT_SLOT_SAMPLE 7
+#define ACAI_SELECT_SLOT_GRAMMAR_SAMPLE 8
+#define ACAI_SELECT_BEAM 9
+int acai_debug_decode_select(int form, const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *g, const AcaiPrompt *prompt,
+                             const AcaiBeam *bs, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k, float temperature,
+                             int chained, void *stream);
 
 /* FP8 memory cache prefill: rows row0 .. row0+nrows-1 (dhp = 16, 32 or 64 elements each, at element offset row*dhp) of the bf16 cross K/V
  * written by acai_cross_kv_prefill -> the same rows of k_out / v_out in OCP e4m3fn, and k_scale[row] / v_scale[row].  The scale is 2^e,
