@@ -292,6 +292,7 @@ _SIGNATURES = {
                                              c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "acai_debug_decode_select": (c_int, [c_int, POINTER(AcaiDecoder), POINTER(AcaiSlots), POINTER(AcaiGrammar), POINTER(AcaiPrompt), POINTER(AcaiBeam),
                                          c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_void_p]),
+    "acai_debug_decode_spec_accept": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSpec), POINTER(AcaiPrompt), c_int, c_void_p]),
     "acai_cross_kv_quantize_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "acai_decode_embed": (c_int, [POINTER(AcaiDecoder), c_void_p]),
     "acai_decode_step": (c_int, [POINTER(AcaiDecoder), c_void_p]),

@@ -879,6 +879,33 @@ extern "C" int acai_debug_decode_select(int form, const AcaiDecoder *d, const Ac
     }
 }
 
+// Test entry (declared and documented in acai_omr_hip.h): ONE launch of spec_accept_kernel on the state and logits the caller wrote, through
+// the helper the speculative steps call.  No layer runs; check_decoder, check_unembed and the x-valid contract are not applied: what is
+// checked is what this launch reads - check_spec's conditions on the speculative state and, with a prompt, check_prompt's for one row per image.
+extern "C" int acai_debug_decode_spec_accept(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *pr, int arm, void *stream) {
+    const char *fn = "acai_debug_decode_spec_accept";
+    ACAI_CHECK_ARG(d, "%s: null decoder", fn);
+    ACAI_CHECK_ARG(d->seqs && d->logprobs && d->step && d->finished, "%s: null seqs / logprobs / step / finished", fn);
+    ACAI_CHECK_ARG(d->emb && d->pos && d->x, "%s: null emb / pos / x", fn);
+    ACAI_CHECK_ARG(arm || d->logits, "%s: a verify step (arm = 0) needs logits", fn);
+    ACAI_CHECK_ARG(d->B >= 1 && d->V >= 1 && d->E >= 1, "%s: bad dims B=%d V=%d E=%d", fn, d->B, d->V, d->E);
+    ACAI_CHECK_ARG(d->max_len > 1 && d->max_len <= d->Tmax, "%s: max_len outside [2, Tmax] (max_len=%d Tmax=%d)", fn, d->max_len, d->Tmax);
+    ACAI_CHECK_ARG(sp && sp->t && sp->cap && sp->steps && sp->tab && sp->next, "%s: null speculative state", fn);
+    ACAI_CHECK_ARG(sp->D >= 1 && sp->D <= 7, "%s: draft length %d outside [1, 7]", fn, sp->D);
+    ACAI_CHECK_ARG(d->B % (sp->D + 1) == 0, "%s: needs B %% (D + 1) == 0 (B=%d D=%d)", fn, d->B, sp->D);
+    ACAI_CHECK_ARG(sp->rows >= d->B / (sp->D + 1) && sp->pitch >= d->max_len && sp->pitch <= d->Tmax, "%s: needs rows >= B / (D + 1) and "
+                   "max_len <= pitch <= Tmax (rows=%d pitch=%d)", fn, sp->rows, sp->pitch);
+    ACAI_CHECK_ARG(sp->drafts || (sp->ngram >= 1 && sp->ngram <= 8), "%s: without a drafts table ngram must be in [1, 8] (got %d)", fn, sp->ngram);
+    if (pr) {
+        const int rows = d->B / (sp->D + 1);
+        ACAI_CHECK_ARG(pr->tok && pr->len, "%s: null prompt tables", fn);
+        ACAI_CHECK_ARG(pr->pitch >= d->max_len && pr->rows >= rows, "%s: needs prompt pitch >= max_len and rows >= %d (pitch=%d max_len=%d rows=%d)",
+                       fn, rows, pr->pitch, d->max_len, pr->rows);
+        return launch_spec_prompt_accept(d, sp, pr, arm, (hipStream_t)stream);
+    }
+    return launch_spec_accept(d, sp, arm, (hipStream_t)stream);
+}
+
 // (declared and documented in acai_omr_hip.h; it takes the slot state as bare pointers, not through the decoder descriptor, so that it can
 // be driven over any rows laid out as the slot steps lay them out)
 extern "C" int acai_decode_slot_flush(const int64_t *seqs, const float *logprobs, int max_len, const int32_t *slot_t, const int32_t *finished,

@@ -1303,6 +1303,52 @@ def debug_decode_select(form, logits, seqs, logprobs, step, finished, *, max_len
                "acai_debug_decode_select")
 
 
+def debug_decode_spec_accept(logits, seqs, logprobs, step, finished, *, spec, max_len, Tmax, eos, pad=0, emb=None, pos=None, x=None,
+                             round_lp=False, arm=False, prompt=None, B=None, V=None, E=None):
+    """Test entry (acai_debug_decode_spec_accept, see the header): the one launch that closes a speculative step (arm: that opens the run) on
+    the state the caller wrote.  logits [B, V] fp32 (None with arm: give B and V), seqs [rows, max_len] int64, logprobs [rows, max_len] fp32,
+    step [2] int32, finished [B + 1] int32, emb [V, E] / pos [Tmax, E] / x [B, E] fp32.  spec = dict(D, ngram, t / cap / steps int32 [rows],
+    tab int32 [rows, pitch], next int32 [rows, 8], drafts int32 [rows, pitch] or None; pitch and rows default to tab's shape);
+    prompt = dict(tok int32 [rows, pitch], len int32 [rows]) for the prompted launch.  Any tensor may be None and B / V / E may be
+    overridden: the entry refuses what it needs and lacks.  Everything is written in place."""
+    d = _lib.AcaiDecoder()
+    d.B = int(B if B is not None else logits.shape[0])
+    d.V = int(V if V is not None else logits.shape[1])
+    d.E = int(E if E is not None else (emb.shape[1] if emb is not None else 4))
+    d.max_len, d.Tmax, d.eos, d.pad = int(max_len), int(Tmax), int(eos), int(pad)
+    d.flags = GEMM_ROUND_BF16 if round_lp else 0
+    for name, t, dt in (("logits", logits, torch.float32), ("seqs", seqs, torch.int64), ("logprobs", logprobs, torch.float32),
+                        ("step", step, torch.int32), ("finished", finished, torch.int32), ("emb", emb, torch.float32),
+                        ("pos", pos, torch.float32), ("x", x, torch.float32)):
+        if t is not None:
+            assert _chk(t, name, dt).is_contiguous(), name
+            setattr(d, name, t.data_ptr())
+
+    def ptrs(desc, src, names):
+        for name in names:
+            t = src.get(name)
+            if t is not None:
+                assert _chk(t, name, torch.int32).is_contiguous(), name
+                setattr(desc, name, t.data_ptr())
+        return desc
+
+    sp = pr = None
+    if spec is not None:
+        sp = ptrs(_lib.AcaiSpec(), spec, ("t", "cap", "steps", "tab", "next", "drafts"))
+        tab = spec.get("tab")
+        sp.D, sp.ngram = int(spec["D"]), int(spec.get("ngram", 0))
+        sp.pitch = int(spec.get("pitch", tab.shape[1] if tab is not None else 0))
+        sp.rows = int(spec.get("rows", tab.shape[0] if tab is not None else 0))
+    if prompt is not None:
+        pr = ptrs(_lib.AcaiPrompt(), prompt, ("tok", "len"))
+        tk = prompt.get("tok")
+        pr.pitch = int(prompt.get("pitch", tk.shape[1] if tk is not None else 0))
+        pr.rows = int(prompt.get("rows", tk.shape[0] if tk is not None else 0))
+    _lib.check(_lib.lib().acai_debug_decode_spec_accept(ctypes.byref(d), None if sp is None else ctypes.byref(sp),
+                                                        None if pr is None else ctypes.byref(pr), 1 if arm else 0, _st()),
+               "acai_debug_decode_spec_accept")
+
+
 _BWD_WS = {}   # (device, stream) -> the one-pass attention backward's fp32 query-gradient workspace (used only inside a call, in stream order)
 
 

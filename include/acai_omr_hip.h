@@ -860,6 +860,24 @@ int acai_debug_decode_attn_group(const float *q, int ldq, const void *kc, const 
 int acai_debug_decode_select(int form, const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *g, const AcaiPrompt *prompt,
                              const AcaiBeam *bs, const float *uniforms, int ld_uniforms, const int32_t *urow, int top_k, float temperature,
                              int chained, void *stream);
+/* TEST ENTRY (tests/test_gpu_spec_accept.py): the ONE launch that closes every step of acai_decode_spec_arm / _spec_step / _spec_prompt_arm /
+ * _spec_prompt_step, on the state and the logits the caller wrote.  It exists for tests and goes through the helper those steps call - the
+ * unprompted launch when prompt is NULL, the prompted one otherwise - with `arm` passed through (arm != 0: the launch of the _arm entry points,
+ * which reads no logits and writes no token; arm == 0: the launch after a verify step's layers).  No layer runs, and the descriptor need
+ * hold only what this launch reads: logits (arm == 0), V, B, max_len, Tmax, E, eos, pad, flags (ACAI_GEMM_ROUND_BF16), seqs, logprobs, step,
+ * finished, emb, pos, x; sp and prompt as the steps take them.  cross_group, the layers, the unembed and the x-valid contract are not
+ * looked at.  What it writes is what AcaiSpec and the four entry points document above: per image the accepted tokens and log-probs,
+ * t, steps, finished[i]; for every image that is unfinished afterwards next[i][0 .. D], tab[i][t' - 1 .. t' - 1 + D] (indices below pitch)
+ * and x of its D + 1 rows (any E >= 1); finished[B]; step[1] unless arm.  An image whose flag is already set has nothing of it written; one
+ * whose t lies outside [1, cap - 1] only gets its flag set; one that finishes in this launch gets no next / tab / x.
+ * PRECONDITIONS the entry cannot check, as for acai_debug_decode_select: every row of a live image has at least one finite logit and no NaN;
+ * the time indices read on the device (t[], step[1]) are the caller's to keep inside the rows (t and cap are clamped as stated, step[1] is
+ * clamped to Tmax - 1 where it is used).
+ * Refused (rc < 0, acai_last_error() names acai_debug_decode_spec_accept, nothing launched): a null decoder; a null seqs, logprobs, step,
+ * finished, emb, pos or x; null logits unless arm; B, V or E < 1; max_len outside [2, Tmax]; a null sp or a null t, cap, steps, tab or
+ * next; D outside [1, 7]; B % (D + 1) != 0; rows < B / (D + 1); pitch outside [max_len, Tmax]; ngram outside [1, 8] unless drafts is given;
+ * with a prompt: null tok / len, prompt pitch < max_len or prompt rows < B / (D + 1). */
+int acai_debug_decode_spec_accept(const AcaiDecoder *d, const AcaiSpec *sp, const AcaiPrompt *prompt, int arm, void *stream);
 
 /* FP8 memory cache prefill: rows row0 .. row0+nrows-1 (dhp = 16, 32 or 64 elements each, at element offset row*dhp) of the bf16 cross K/V
  * written by acai_cross_kv_prefill -> the same rows of k_out / v_out in OCP e4m3fn, and k_scale[row] / v_scale[row].  The scale is 2^e,
