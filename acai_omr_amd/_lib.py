@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "decode_prefill.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip", "prune.hip", "assess.hip"]
+SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "measures.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "decode_prefill.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip", "prune.hip", "assess.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -239,6 +239,13 @@ _SIGNATURES = {
     "acai_token_confidence": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "acai_attn_map_weighted_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p,
                                            c_void_p]),
+    "acai_token_segments": (c_int, [c_void_p, c_int, c_void_p, c_int, POINTER(c_int64), c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    "acai_segment_reduce": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    "acai_attn_map_segment_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_void_p, c_void_p]),
+    "acai_attn_map_extent": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_float, c_void_p, c_void_p]),
     "acai_attn_varlen_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                      c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_float, c_uint32, c_int, c_void_p]),

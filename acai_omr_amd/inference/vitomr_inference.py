@@ -223,6 +223,39 @@ def diagnosed_inference(vitomr: ViTOMR, img, target_lmx_seqs, device, max_infere
     return seqs, lps, mask, conf, al
 
 
+def measured_inference(vitomr: ViTOMR, img, device, max_inference_len=1536, measures=None, target_lmx_seqs=None, *, prune=None, **decode_kwargs):
+    """inference() plus per-MEASURE results (an extension) -> (seqs, log_probs, seq_mask, TokenConfidence, measures.MeasureReport).  The first
+    four are bit for bit what confident_inference(uncertainty="entropy") returns for the same arguments: the images are encoded once, the
+    decode is inference()'s own (decode_kwargs as in aligned_inference; its errors stay its errors), and the combined pass on the same packed
+    memory scores every token and writes the cross-attention maps.  Inside that pass the rows are cut at the delimiter tokens of `measures`
+    (a measures.MeasureConfig; None: the default, every `measure` token) and confidence, location, box and - with target_lmx_seqs, written
+    as diagnosed_inference takes them - the edit errors are reduced per measure on the device (ViTOMR.measure_report).  MeasureConfig.return_maps
+    also keeps the per-token maps in TokenConfidence.alignment.maps (views of the pass's buffer, no copy).  prune: as in inference(); boxes
+    and maps cover the FULL patch grid.  Whether cross-attention localises measures on trained checkpoints has not been measured."""
+    from ..measures import MeasureConfig, report_hook
+    _check_decode_kwargs("measured_inference", decode_kwargs)
+    config = MeasureConfig() if measures is None else measures
+    if not isinstance(config, MeasureConfig):
+        raise TypeError(f"measures must be a measures.MeasureConfig or None, got {type(config).__name__}")
+    config.resolve(vitomr.decoder)
+    vitomr.eval()
+    with torch.no_grad():
+        dims = list(img.dims) if hasattr(img, "dims") else [vitomr.encoder._grid(t) for t in img]
+        lat32, _, lens, pruned = _encode(vitomr, img, prune, True)
+        with autocast(device_type=device, dtype=torch.bfloat16):
+            mem = vitomr.transition_head.forward_packed(lat32)
+            bf = mem.dtype == torch.bfloat16
+            mem32, memb = (None, mem) if bf else (mem, None)
+            seqs, lps, mask = _decode_packed(vitomr, mem32, memb, lens, max_inference_len, decode_kwargs)
+            full, kept = _full_grid(dims, lens, pruned)
+            grids = vitomr._check_grids(dims, full)
+            config.resolve(vitomr.decoder, seqs.shape)
+            hook = report_hook(config, None if target_lmx_seqs is None else vitomr._error_weights(seqs, mask, target_lmx_seqs, None)[0])
+            conf = vitomr._confidence_packed(mem32, memb, lens, seqs, mask, 5, 1.0, True, "entropy", None, None, grids, vitomr.encoder.patch_size,
+                                             True, kept=kept, measure=hook, return_maps=config.return_maps)
+    return seqs, lps, mask, conf, hook.report
+
+
 def _encode_chunks(vitomr, imgs, device, prune=None):
     """Encoder (fp32, outside autocast) and transition head (inside autocast) over chunks of at most max_batch_size images; the packed
     memories of all chunks, concatenated, and their lengths.  imgs: a list of image tensors, or a `utils.PackedPatches`.  prune: as in

@@ -916,29 +916,34 @@ class ViTOMR(nn.Module):
         return weight
 
     def _confidence_packed(self, mem32, memb, lens_s, seqs, seq_mask, top_k, temperature, as_decoded, weight=None, layers=None,
-                           head_weights=None, grids=None, patch_size=None, return_alignment=False, kept=None):
+                           head_weights=None, grids=None, patch_size=None, return_alignment=False, kept=None, measure=None, return_maps=False):
         """The confidence pass on packed memories -> TokenConfidence.  weight None: the logits-only pass; otherwise the combined pass (maps and
-        logits from one teacher-forced pass), the heat maps over `grids`, and with return_alignment the TokenAlignment of the same maps.
-        kept: as in _align_packed - the maps of a pruned memory are expanded to the full `grids` before the sums and the locations."""
+        logits from one teacher-forced pass), the heat maps over `grids`, and with return_alignment the TokenAlignment of the same maps
+        (return_maps keeps the per-token maps in it).  kept: as in _align_packed - the maps of a pruned memory are expanded to the full
+        `grids` before the sums and the locations.  measure (default None: nothing is added): a callable that receives the pass's state
+        (measures.build_report: the per-measure results are formed here, where the flat map buffer exists); it forces the combined pass,
+        without the heat maps when weight is None."""
         dec = self.decoder
         top_k, tau = self._check_confidence_args(top_k, temperature)
         B, Tp = seqs.shape
         dev = dec.pos_embedding.device
-        if weight is not None:
+        if weight is not None or measure is not None:
             dec._alignment_selection(layers, head_weights)
+        if weight is not None:
             weight = self._check_uncertainty_weight(weight, seqs.shape)
         Ls, rows, lens_t, sub_s, mem32, memb, tokens, at = self._scored_rows(mem32, memb, lens_s, seqs, seq_mask)
         nan = lambda *sh: torch.full(sh, float("nan"), dtype=torch.float32, device=dev)   # noqa: E731
         none = lambda *sh: torch.full(sh, -1, dtype=torch.int64, device=dev)   # noqa: E731
         conf = TokenConfidence(nan(B, Tp), nan(B, Tp), none(B, Tp), none(B, Tp, top_k), nan(B, Tp, top_k))
-        out = offs = map_off = heat = None
+        out = offs = map_off = heat = own = None
         if rows:
-            if weight is None:
+            if weight is None and measure is None:
                 logits = dec.logits_packed(tokens, lens_t, mem32, memb, sub_s, 1 if as_decoded else 0)
             else:
                 out, offs, map_off, logits = dec._cross_attention_maps_flat(tokens, lens_t, mem32, memb, sub_s, layers, head_weights,
                                                                             1 if as_decoded else 0, None, True)
-                if kept is not None:
+                own = (out, offs, map_off, sub_s)   # the maps over the memory's own patches: what a measure sums before any expansion
+                if kept is not None and (weight is not None or return_alignment):
                     out, offs, map_off, sub_s = self._expand_maps(out, offs, rows, lens_t, sub_s, lens_s, kept, grids)
             chosen = torch.cat([seqs[i, 1:Ls[i]] for i in rows]).to(dev)
             lp, ent, rank, ids, top_lp = ops.token_confidence(logits, chosen, top_k, tau)
@@ -951,16 +956,20 @@ class ViTOMR(nn.Module):
                     w = weight.to(device=dev, dtype=torch.float32)[at]
                 cu_t, cu_s = EG.cu_from_lens(lens_t, dev), EG.cu_from_lens(sub_s, dev)
                 heat = ops.attn_map_weighted_sum(out, map_off, cu_t, cu_s, w.contiguous(), max(lens_t), layout=(lens_t, sub_s, offs))
-        if weight is not None:
+        if measure is not None:
+            measure(self, seqs=seqs, Ls=Ls, rows=rows, lens_t=lens_t, own=own, conf=conf, grids=grids, patch_size=patch_size, lens_s=lens_s,
+                    kept=kept)
+        if weight is not None or (measure is not None and return_alignment):
             if kept is not None:
                 lens_s = [h * w for h, w in grids]
-            conf.uncertainty = [torch.zeros(h, w, dtype=torch.float32, device=dev) for h, w in grids]
-            o = 0
-            for i, s in zip(rows, sub_s):
-                conf.uncertainty[i] = heat[o:o + s].view(*grids[i])
-                o += s
+            if weight is not None:
+                conf.uncertainty = [torch.zeros(h, w, dtype=torch.float32, device=dev) for h, w in grids]
+                o = 0
+                for i, s in zip(rows, sub_s):
+                    conf.uncertainty[i] = heat[o:o + s].view(*grids[i])
+                    o += s
             if return_alignment:
-                conf.alignment = self._located(seqs.shape, lens_s, rows, lens_t, sub_s, at, out, offs, map_off, grids, patch_size, False)
+                conf.alignment = self._located(seqs.shape, lens_s, rows, lens_t, sub_s, at, out, offs, map_off, grids, patch_size, return_maps)
         return conf
 
     def token_confidence(self, img_latent, latent_attention_mask, seqs, seq_mask=None, top_k=5, temperature=1.0, as_decoded=True):
@@ -1007,6 +1016,42 @@ class ViTOMR(nn.Module):
         with torch.no_grad():
             return self._confidence_packed(mem32, None, lens_s, seqs, seq_mask, top_k, temperature, True, weight, layers, head_weights, grids,
                                            patch_size, return_alignment)
+
+    # ---- per-measure results (an extension) ---------------------------------------------------------------------------------
+    def measure_report(self, img_latent, latent_attention_mask, seqs, seq_mask=None, config=None, target_lmx_seqs=None, layers=None,
+                       head_weights=None, grids=None, patch_size=None, as_decoded=True):
+        """Per-MEASURE results of decoded (or any) sequences (an extension) -> measures.MeasureReport: the rows cut at the delimiter tokens
+        of `config` (a measures.MeasureConfig; default: at every `measure` token), and over each span the tokens' confidence (mean and
+        lowest log-probability, the weakest token, mean and highest entropy, tokens that were not the arg-max), where on the page the span
+        looked - the tokens' cross-attention maps summed over the span, reduced to a centre, a spread and a quantile box in pixels - and,
+        with target_lmx_seqs (as error_maps takes them), the substitutions, insertions and deletions that fall into it.  It runs inside the
+        combined confidence + alignment pass of uncertainty_maps, where the flat map buffer exists: the segmentation and the segmented
+        reductions are device work (ops.token_segments, segment_reduce, attn_map_segment_sum, attn_map_extent) and the per-token maps are
+        never copied out; one copy to the host per call, the segment counts.  grids (required), layers, head_weights and as_decoded as in
+        locate_tokens / uncertainty_maps; patch_size defaults to the encoder's.  Whether cross-attention localises measures on trained
+        checkpoints, which layers, heads or weight do it best and what confidence marks a wrong measure have not been measured."""
+        from ..measures import MeasureConfig, report_hook
+        if grids is None:
+            raise ValueError("grids is required: one (h_p, w_p) per image")
+        config = MeasureConfig() if config is None else config
+        if not isinstance(config, MeasureConfig):
+            raise TypeError(f"config must be a measures.MeasureConfig, got {type(config).__name__}")
+        config.resolve(self.decoder, seqs.shape)   # argument errors before any work
+        self.decoder._alignment_selection(layers, head_weights)
+        B, Lm = img_latent.shape[0], img_latent.shape[1]
+        lens_s = [Lm] * B if latent_attention_mask is None else [int(l) for l in (~latent_attention_mask).sum(dim=1).tolist()]
+        grids = self._check_grids(grids, lens_s)
+        if patch_size is None:
+            patch_size = getattr(self.encoder, "patch_size", None)
+        if patch_size is None or float(patch_size) <= 0:
+            raise ValueError("patch_size is needed (the model has no encoder to take it from) and must be positive")
+        self._alignment_lengths(seqs, seq_mask)
+        mem32, lens_s = EG.unpad_rows(img_latent.to(self.decoder.pos_embedding.device), latent_attention_mask)
+        with torch.no_grad():
+            hook = report_hook(config, None if target_lmx_seqs is None else self._error_weights(seqs, seq_mask, target_lmx_seqs, None)[0])
+            self._confidence_packed(mem32, None, lens_s, seqs, seq_mask, 5, 1.0, as_decoded, None, layers, head_weights, grids, patch_size,
+                                    measure=hook)
+        return hook.report
 
     # ---- ground-truth error maps (an extension) -----------------------------------------------------------------------------
     def _error_weights(self, seqs, seq_mask, target_lmx_seqs, pad_idx):

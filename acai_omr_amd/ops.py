@@ -926,6 +926,219 @@ def attn_map_weighted_sum(maps, map_off, cu_q, cu_k, weights, max_q, layout=None
     return out
 
 
+SEGMENT_MAX_DELIMS, SEGMENT_MAX_PLANES = 8, 8     # measures.hip: SEG_MAX_DELIMS, RED_MAX_K
+EXTENT_MAX_IMAGES, EXTENT_MAX_SIDE = 512, 4096    # measures.hip: EXT_MAX_B, EXT_MAX_SIDE
+
+
+class SegmentStats(NamedTuple):
+    """What segment_reduce returns for K planes, R rows and `cap` segment slots, each (K, R, cap): sum, min, max fp32 and argmin, argmax int32
+    (token indices within the row, the lowest on ties); 0 and -1 in the slots past a row's count."""
+    sum: torch.Tensor
+    min: torch.Tensor
+    max: torch.Tensor
+    argmin: torch.Tensor
+    argmax: torch.Tensor
+
+
+def _seg_outputs(who, out, shapes, dev):
+    """The output tensors of a segment op: allocated, or the caller's `out` checked against (shape, dtype) one by one."""
+    if out is None:
+        return tuple(torch.empty(s, dtype=d, device=dev) for s, d in shapes)
+    out = tuple(out)
+    if len(out) != len(shapes):
+        raise ValueError(f"{who}: out must hold {len(shapes)} tensors, got {len(out)}")
+    for i, (t, (s, d)) in enumerate(zip(out, shapes)):
+        _chk(t, f"{who}: out[{i}]", d)
+        if tuple(t.shape) != tuple(s) or not t.is_contiguous():
+            raise ValueError(f"{who}: out[{i}] must be a contiguous {tuple(s)} tensor, got {tuple(t.shape)}")
+        if t.device != dev:
+            raise RuntimeError(f"{who}: operands on different devices ({dev} and {t.device})")
+    return out
+
+
+@_on_operand_device
+def token_segments(tokens, lens, delims, stop=-1, cap=256, out=None):
+    """Token rows cut at delimiter tokens (acai_token_segments; one launch) -> (seg (R, ld) int32, count (R,) int32, bounds (R, cap, 2) int32).
+    tokens (R, ld) int64 on the GPU, ld >= 1; lens: int32 lengths (R,) or a bool prefix mask of tokens' shape, read on the device and clamped
+    to [0, ld] (no host sync); delims: 1 .. 8 token ids; stop: the <eos> id, or -1 for none; cap >= 1 segment slots per row.  A row ends at E,
+    its first `stop` (or its length); seg[r, p] is the number of delimiters at indices <= p minus one for p < E - so -1 before the first
+    delimiter - and -1 from E on; count[r] is the TRUE number of segments, also beyond cap; bounds[r, m] = (index of the m-th delimiter,
+    index of the next one or E) for m < min(count, cap), (-1, -1) beyond.  ValueError for bad shapes or arguments, RuntimeError for CPU
+    tensors.  With int32 lengths and `out` (the three tensors) given, the call is one kernel launch and nothing else."""
+    _chk(tokens, "tokens", torch.int64), _chk(lens, "lens")
+    if tokens.dim() != 2 or tokens.shape[1] < 1:
+        raise ValueError(f"token_segments: tokens must be (rows, ld >= 1), got {tuple(tokens.shape)}")
+    R, ld = tokens.shape
+    if lens.dtype == torch.bool:
+        if lens.shape != tokens.shape:
+            raise ValueError(f"token_segments: a mask must have tokens' shape {tuple(tokens.shape)}, got {tuple(lens.shape)}")
+        lens = lens.sum(dim=-1, dtype=torch.int32)
+    elif lens.dtype != torch.int32:
+        raise TypeError(f"token_segments: expected int32 lengths or a bool mask, got {lens.dtype}")
+    if lens.shape != (R,):
+        raise ValueError(f"token_segments: expected {R} lengths, got {tuple(lens.shape)}")
+    try:
+        ids = [int(d) for d in delims]
+    except (TypeError, ValueError):
+        raise ValueError(f"token_segments: delims must be 1 .. {SEGMENT_MAX_DELIMS} token ids, got {delims!r}") from None
+    if not 1 <= len(ids) <= SEGMENT_MAX_DELIMS or min(ids) < 0:
+        raise ValueError(f"token_segments: delims must be 1 .. {SEGMENT_MAX_DELIMS} non-negative token ids, got {ids}")
+    stop, cap = int(stop), int(cap)
+    if stop < -1 or cap < 1:
+        raise ValueError(f"token_segments: stop={stop} (an id, or -1 for none) and cap={cap} (at least 1)")
+    if lens.device != tokens.device:
+        raise RuntimeError(f"token_segments: operands on different devices ({tokens.device} and {lens.device})")
+    seg, count, bounds = _seg_outputs("token_segments", out, (((R, ld), torch.int32), ((R,), torch.int32), ((R, cap, 2), torch.int32)),
+                                      tokens.device)
+    if R == 0:
+        return seg, count, bounds
+    tokens, lens = tokens.contiguous(), lens.contiguous()
+    _lib.check(_lib.lib().acai_token_segments(tokens.data_ptr(), ld, lens.data_ptr(), R, (ctypes.c_int64 * len(ids))(*ids), len(ids), stop, cap,
+                                              seg.data_ptr(), count.data_ptr(), bounds.data_ptr(), _st(tokens)), "acai_token_segments")
+    return seg, count, bounds
+
+
+@_on_operand_device
+def segment_reduce(values, bounds, count, out=None):
+    """Per-token values reduced over the spans of token_segments (acai_segment_reduce; one launch) -> SegmentStats.  values (K, R, ld) fp32 with
+    1 <= K <= 8 planes, bounds (R, cap, 2) and count (R,) int32 as token_segments returns them, all on the GPU.  Every output is (K, R, cap):
+    sum, min, max, and argmin / argmax as token indices within the row (the lowest on ties); slots past min(count, cap) hold 0 and -1.  Lane
+    j of a wave adds the span's elements j, j + 64, ... in order, then a fixed butterfly: the same bits on every run, and exact for values
+    whose partial sums fp32 holds (0/1 planes).  A NaN inside a span is outside the contract.  ValueError for bad shapes, RuntimeError for
+    CPU tensors.  With `out` (five tensors) given, the call is one kernel launch and nothing else."""
+    _chk(values, "values", torch.float32), _chk(bounds, "bounds", torch.int32), _chk(count, "count", torch.int32)
+    if values.dim() != 3 or not 1 <= values.shape[0] <= SEGMENT_MAX_PLANES or values.shape[2] < 1:
+        raise ValueError(f"segment_reduce: values must be (1 .. {SEGMENT_MAX_PLANES} planes, rows, ld >= 1), got {tuple(values.shape)}")
+    K, R, ld = values.shape
+    if bounds.dim() != 3 or bounds.shape[0] != R or bounds.shape[1] < 1 or bounds.shape[2] != 2 or count.shape != (R,):
+        raise ValueError(f"segment_reduce: {R} rows need bounds ({R}, cap >= 1, 2) and count ({R},), got {tuple(bounds.shape)} and "
+                         f"{tuple(count.shape)}")
+    cap = bounds.shape[1]
+    if K * R * cap >= 2 ** 31:
+        raise ValueError(f"segment_reduce: {K} x {R} x {cap} spans are too many")
+    for t in (bounds, count):
+        if t.device != values.device:
+            raise RuntimeError(f"segment_reduce: operands on different devices ({values.device} and {t.device})")
+    f32, i32 = torch.float32, torch.int32
+    out = SegmentStats(*_seg_outputs("segment_reduce", out, [((K, R, cap), d) for d in (f32, f32, f32, i32, i32)], values.device))
+    if R == 0:
+        return out
+    values, bounds, count = values.contiguous(), bounds.contiguous(), count.contiguous()
+    _lib.check(_lib.lib().acai_segment_reduce(values.data_ptr(), K, R, ld, bounds.data_ptr(), count.data_ptr(), cap, *(t.data_ptr() for t in out),
+                                              _st(values)), "acai_segment_reduce")
+    return out
+
+
+def _map_layout_host(who, maps, map_off, cu_q, cu_k, layout):
+    """(lens_q, lens_k, offsets) of a flat map buffer as host lists, checked: from `layout`, or read back from the device once."""
+    B = cu_q.numel() - 1
+    if B < 1 or cu_k.numel() != B + 1 or map_off.numel() != B or maps.dim() != 1:
+        raise ValueError(f"{who}: {B} images need cu_q / cu_k of {B + 1} entries, map_off of {B} and flat maps")
+    if not (maps.is_contiguous() and map_off.is_contiguous() and cu_q.is_contiguous() and cu_k.is_contiguous()):
+        raise ValueError(f"{who}: operands must be contiguous")
+    if layout is None:
+        host = torch.cat([cu_q.long(), cu_k.long(), map_off]).tolist()
+        hq, hk, ho = host[:B + 1], host[B + 1:2 * B + 2], host[2 * B + 2:]
+        if hq[0] != 0 or hk[0] != 0:
+            raise ValueError(f"{who}: bad cumulative lengths cu_q={hq} cu_k={hk}")
+        lens_q, lens_k = [b - a for a, b in zip(hq, hq[1:])], [b - a for a, b in zip(hk, hk[1:])]
+    else:
+        lens_q, lens_k, ho = ([int(v) for v in x] for x in layout)
+        if not len(lens_q) == len(lens_k) == len(ho) == B:
+            raise ValueError(f"{who}: layout must hold {B} query lengths, key lengths and offsets")
+    if min(lens_q) < 0 or min(lens_k) < 1:
+        raise ValueError(f"{who}: bad lengths lens_q={lens_q} lens_k={lens_k}")
+    for b, (o, t, s) in enumerate(zip(ho, lens_q, lens_k)):
+        if o < 0 or o + t * s > maps.numel():
+            raise ValueError(f"{who}: image {b}'s [{t}][{s}] block at offset {o} lies outside the {maps.numel()} map elements")
+    return lens_q, lens_k, ho
+
+
+@_on_operand_device
+def attn_map_segment_sum(maps, map_off, cu_q, cu_k, weights, ranges, seg_counts, layout=None, check_ranges=True):
+    """The maps of attn_probs_mean summed over ranges of map rows, one map per range (acai_attn_map_segment_sum; one launch): the segmented
+    form of attn_map_weighted_sum.  maps / map_off / cu_q / cu_k / layout as there; weights (sum T,) fp32 packed like the tokens, or None for
+    all ones (the same bits as a tensor of ones); ranges (sum n, 2) int32 on the GPU: per segment the half-open range [t0, t1) of map rows
+    within its image's block, image after image (map row t belongs to token index t + 1: token_segments' bounds minus one); seg_counts: the
+    images' segment counts n_b, a host list.  -> (out, offsets list, offsets as an int64 device tensor, cu_seg int32 device tensor): image b
+    owns the dense [n_b][S_b] block at offsets[b] of the flat fp32 `out` - attn_map_layout(seg_counts, lens_k) - with out_b[m, s] = sum over
+    the range's rows t, ascending, of weights_b[t] * map_b[t, s]; attn_map_locate, attn_map_expand and attn_map_extent take it with cu_seg in
+    the place of cu_q.  The same bits on every run.  check_ranges reads the ranges back once and refuses (ValueError) an empty one or one
+    outside [0, T_b]; without it the kernel clamps them to the block (callers that built them on the device from token_segments)."""
+    who = "attn_map_segment_sum"
+    _chk(maps, "maps", torch.float32), _chk(map_off, "map_off", torch.int64), _chk(cu_q, "cu_q", torch.int32), _chk(cu_k, "cu_k", torch.int32)
+    _chk(ranges, "ranges", torch.int32)
+    if weights is not None:
+        _chk(weights, "weights", torch.float32)
+    lens_q, lens_k, _ = _map_layout_host(who, maps, map_off, cu_q, cu_k, layout)
+    B = len(lens_q)
+    try:
+        counts = [int(n) for n in seg_counts]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: seg_counts must be a list of {B} segment counts, got {seg_counts!r}") from None
+    if len(counts) != B or min(counts) < 0 or max(counts) > 65535 or B > 65535:
+        raise ValueError(f"{who}: seg_counts must hold {B} counts in [0, 65535], got {counts}")
+    if ranges.dim() != 2 or tuple(ranges.shape) != (sum(counts), 2) or not ranges.is_contiguous():
+        raise ValueError(f"{who}: ranges must be a contiguous ({sum(counts)}, 2) tensor for segment counts {counts}, got {tuple(ranges.shape)}")
+    if weights is not None and (weights.dim() != 1 or weights.numel() != sum(lens_q) or not weights.is_contiguous()):
+        raise ValueError(f"{who}: weights holds {weights.numel()} entries for {sum(lens_q)} tokens")
+    for t in (map_off, cu_q, cu_k, ranges, weights):
+        if t is not None and t.device != maps.device:
+            raise RuntimeError(f"{who}: operands on different devices ({maps.device} and {t.device})")
+    if check_ranges and sum(counts):
+        host, g = ranges.tolist(), 0
+        for b, (n, T) in enumerate(zip(counts, lens_q)):
+            for t0, t1 in host[g:g + n]:
+                if not 0 <= t0 < t1 <= T:
+                    raise ValueError(f"{who}: image {b} has the range [{t0}, {t1}) - empty or outside its {T} map rows")
+            g += n
+    dev = maps.device
+    offs, total = attn_map_layout(counts, lens_k)
+    out = torch.empty(total, dtype=torch.float32, device=dev)
+    # (both tables go up as one tensor: the int64 offsets first, viewed as int32 pairs, then the cumulative counts)
+    both = h2d(torch.cat([torch.tensor(offs, dtype=torch.int64).view(torch.int32), torch.tensor([0] + list(itertools.accumulate(counts)), dtype=torch.int32)]),
+               dev)
+    seg_off, tab = both[:2 * B].view(torch.int64), both[2 * B:]
+    if total:
+        _lib.check(_lib.lib().acai_attn_map_segment_sum(maps.data_ptr(), map_off.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), _p(weights),
+                                                        ranges.data_ptr(), tab.data_ptr(), seg_off.data_ptr(), B, max(lens_k), max(counts),
+                                                        out.data_ptr(), _st(maps)), "acai_attn_map_segment_sum")
+    return out, offs, seg_off, tab
+
+
+@_on_operand_device
+def attn_map_extent(maps, map_off, cu_q, cu_k, grid_w, q, layout=None):
+    """A quantile box for every row of the maps of attn_probs_mean or attn_map_segment_sum (acai_attn_map_extent; one launch) -> (sum T, 4)
+    fp32 (x0, y0, x1, y1) in patch units.  maps / map_off / cu_q / cu_k / layout as attn_map_weighted_sum takes them (for segment maps: cu_seg
+    in the place of cu_q); grid_w: the images' patches per row, a host list of ints in 1 .. 4096; 0 <= q < 0.5.  With the row's column
+    marginal a[x], its running sums C and its mass m, x0 is where C crosses q * m and x1 where it crosses (1 - q) * m, interpolated inside
+    the cell (include/acai_omr_hip.h states the rule); y0, y1 the same over the grid rows, of which the last may be partial.  A row without
+    mass gives zeros.  ValueError for a grid side above 4096, more than 512 images, grid_w < 1 or q outside [0, 0.5)."""
+    who = "attn_map_extent"
+    _chk(maps, "maps", torch.float32), _chk(map_off, "map_off", torch.int64), _chk(cu_q, "cu_q", torch.int32), _chk(cu_k, "cu_k", torch.int32)
+    lens_q, lens_k, _ = _map_layout_host(who, maps, map_off, cu_q, cu_k, layout)
+    B = len(lens_q)
+    try:
+        gw, q = [int(w) for w in grid_w], float(q)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: grid_w must be a list of ints and q a number, got {grid_w!r} and {q!r}") from None
+    if len(gw) != B or B > EXTENT_MAX_IMAGES:
+        raise ValueError(f"{who}: {len(gw)} grid widths for {B} images (at most {EXTENT_MAX_IMAGES})")
+    if not 0.0 <= q < 0.5:
+        raise ValueError(f"{who}: q must satisfy 0 <= q < 0.5, got {q}")
+    for b, (w, s) in enumerate(zip(gw, lens_k)):
+        if not 1 <= w <= EXTENT_MAX_SIDE or -(-s // w) > EXTENT_MAX_SIDE:
+            raise ValueError(f"{who}: image {b} has {s} patches in rows of {w}: both grid sides must lie in 1 .. {EXTENT_MAX_SIDE}")
+    for t in (map_off, cu_q, cu_k):
+        if t.device != maps.device:
+            raise RuntimeError(f"{who}: operands on different devices ({maps.device} and {t.device})")
+    ext = torch.empty(sum(lens_q), 4, dtype=torch.float32, device=maps.device)
+    if sum(lens_q):
+        _lib.check(_lib.lib().acai_attn_map_extent(maps.data_ptr(), map_off.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(),
+                                                   (ctypes.c_int32 * B)(*gw), B, max(lens_q), q, ext.data_ptr(), _st(maps)), "acai_attn_map_extent")
+    return ext
+
+
 PRUNE_MAX_HALO, PRUNE_MAX_GRID, PRUNE_MAX_IMAGES = _lib.PRUNE_MAX_HALO, _lib.PRUNE_MAX_GRID, _lib.PRUNE_MAX_IMAGES
 
 

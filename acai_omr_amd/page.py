@@ -1219,3 +1219,24 @@ class PageResult:
         that was neither rectified nor deskewed, a quadrilateral otherwise (for a UI to draw)."""
         x0, y0, x1, y1 = self._flat[system]
         return [self.to_source_xy(self.system_page[system], float(x), float(y)) for x, y in ((x0, y0), (x1, y0), (x1, y1), (x0, y1))]
+
+
+def measure_boxes(page_result, report):
+    """Each system's measure boxes on the page (host glue; an extension): for every row of `page_result` the list of its measures' boxes,
+    each as the four corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of `report.box_px` - a `measures.MeasureReport` of the same rows, whose
+    boxes are pixels of the tensor the model saw - taken to the pixels of the page the caller passed in (`PageResult.to_page_xy`: a
+    quadrilateral when the page was rectified or turned, as `PageResult.box_corners` gives for the system itself).  A measure without a
+    box (no map rows) is None.  One copy of the boxes to the host."""
+    if report.box_px.shape[0] != len(page_result):
+        raise ValueError(f"measure_boxes: a report of {report.box_px.shape[0]} rows for {len(page_result)} systems")
+    boxes, counts = report.box_px.cpu().tolist(), report.count.cpu().tolist()
+    out = []
+    for s, (row, c) in enumerate(zip(boxes, counts)):
+        quads = []
+        for x0, y0, x1, y1 in row[:min(int(c), len(row))]:
+            if math.isnan(x0):
+                quads.append(None)
+            else:
+                quads.append([page_result.to_page_xy(s, x, y) for x, y in ((x0, y0), (x1, y0), (x1, y1), (x0, y1))])
+        out.append(quads)
+    return out

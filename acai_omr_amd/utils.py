@@ -154,6 +154,15 @@ def error_token_weights(alignment, pred_lens):
     return w.scatter_add_(1, pos, deleted.to(torch.float32))
 
 
+def measure_accuracy(seqs, seq_mask, target_lmx_seqs, delimiters, pad_idx=None):
+    """The share of the TARGET's measures that decoded rows reproduce without error -> (accuracy float, reproduced (N,), target measures (N,)).
+    measures.measure_accuracy, where the rule is stated: every edit operation of the canonical alignment is charged to one target measure -
+    a substitution to the measure of the target token it is aligned to, a deleted target token to its own, an inserted token to the measure
+    of the target token the nearest earlier aligned pred token is aligned to - and a measure is reproduced when nothing is charged to it."""
+    from .measures import measure_accuracy as impl
+    return impl(seqs, seq_mask, target_lmx_seqs, delimiters, pad_idx)
+
+
 def confidence_error_auroc(score, is_error, mask):
     """How well a per-token score separates the aligned errors from the matches: the area under the ROC curve of `score` (any shape; higher =
     more suspect: 1 - exp(log_prob), entropy, rank, ...) as a detector of is_error (bool, e.g. EditAlignment.pred_op != 0) over the tokens

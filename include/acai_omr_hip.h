@@ -341,6 +341,57 @@ int acai_token_confidence(const float *logits, const int64_t *chosen, int N, int
 int acai_attn_map_weighted_sum(const float *map, const int64_t *map_off, const int32_t *cu_q, const int32_t *cu_k, const float *weights,
                                int B, int max_q, int max_k, int64_t total_k, float *partial, float *out, void *stream);
 
+/* Per-measure results (measures.hip; an extension, no reference counterpart): token rows cut at delimiter tokens, and per-token results
+ * reduced over the spans between them.  All four entries enqueue kernels only - no allocation, no host synchronisation, capturable in a
+ * hipGraph - use no floating-point atomics (the same bits on every run), check their arguments before the launch (-1, nothing launched) and
+ * return at once for zero rows.  What they read from DEVICE memory to index with (lengths, bounds, counts, ranges) is clamped to the buffers.
+ *
+ * acai_token_segments: tokens [R][ld] int64 (row stride = ld >= 1), lens [R] int32 read on the device and clamped to [0, ld]; delims: 1 .. 8
+ * token ids in a HOST array (carried as kernel arguments); stop: the <eos> id, or -1 for none; cap >= 1.  For row r with clamped length L:
+ *   E        = the first p < L with tokens[r][p] == stop, L without one;   c(p) = the number of delimiter tokens at indices <= p;
+ *   seg      [R][ld]     int32: c(p) - 1 for p < E (so -1 before the first delimiter, <bos> included), -1 for E <= p < ld;
+ *   count    [R]         int32: c(E - 1), 0 when E == 0 - the TRUE count, also when it exceeds cap;
+ *   bounds   [R][cap][2] int32: for m < min(count, cap) (start, end) = (index of the m-th delimiter, index of the next delimiter or E);
+ *                               (-1, -1) for min(count, cap) <= m < cap.
+ * Every element of seg, count and bounds is written.  One wave per row, chunks of 64 tokens, a ballot / popcount scan with a carry.
+ * Errors: null operand, ld < 1, R < 0, n_delims outside 1 .. 8, cap < 1, stop < -1.
+ *
+ * acai_segment_reduce: values [K][R][ld] fp32, 1 <= K <= 8; bounds / count / cap as acai_token_segments wrote them.  Outputs [K][R][cap]: sum,
+ * min, max fp32 and argmin, argmax int32 (token indices within the row; the lowest index on ties) of values[k][r][start .. end) for
+ * m < min(count[r], cap); 0 and -1 beyond (and for a span that is empty after clamping to [0, ld]).  Every element is written.  One wave per
+ * (k, r, m): lane j takes start + j, start + j + 64, ... in ascending order, then a fixed xor butterfly (1, 2, .. 32) - a sum is at most
+ * ceil(len / 64) + 6 additions deep.  A NaN inside a span is outside the contract.  Errors: null operand, K outside 1 .. 8, ld < 1, cap < 1,
+ * R < 0, K * R * cap >= 2^31.
+ *
+ * acai_attn_map_segment_sum: the segmented form of acai_attn_map_weighted_sum.  map / map_off / cu_q / cu_k as there; weights [total_q] fp32
+ * or NULL (all ones; the same bits as a tensor of ones); ranges [total_seg][2] int32: half-open ranges [t0, t1) of MAP ROWS within the
+ * image's block (map row t belongs to token index t + 1: pass token bounds minus one), clamped to [0, T_b] on the device - an empty or
+ * out-of-block range is for the caller to refuse; cu_seg [B + 1] int32; seg_map_off [B] int64, all in device memory.  Image b with n_b
+ * segments owns the dense [n_b][S_b] block at out + seg_map_off[b]:
+ *   out[m][s] = sum over t in range m, ascending, of weights[cu_q[b] + t] * map_b[t][s]          (fmaf into one accumulator per column)
+ * - the layout of per-token maps with cu_seg in the place of cu_q, so acai_attn_map_locate, acai_attn_map_expand and acai_attn_map_extent
+ * apply to it unchanged.  max_k bounds S_b, max_seg bounds n_b (either 0, or B == 0: returns at once).  One workgroup per (segment, 256
+ * columns): coalesced loads, every map element of a range read once.  Errors: null operand, bad dims, B or max_seg > 65535.
+ *
+ * acai_attn_map_extent: a quantile box for every row of such maps (per token or per segment).  grid_w [B] int32 on the HOST, as
+ * acai_attn_map_locate takes it, 1 .. 4096; 0 <= q < 0.5.  For a row p over S_b patches, n_x = min(grid_w, S_b) columns and n_y =
+ * ceil(S_b / grid_w) grid rows (the last may be partial): column marginal a[x] = sum_y p[y * grid_w + x], C[i] = a[0] + .. + a[i] added in
+ * that order (C[-1] = 0), m = C[n - 1];
+ *   pos(target) = i + (target - C[i - 1]) / a[i] for the smallest i with C[i] >= target and a[i] > 0; n without such an i;
+ *   x0 = pos(q m), x1 = pos((1 - q) m);   y0, y1 the same from the row marginal and its own m.
+ * ext [total rows][4] fp32 = (x0, y0, x1, y1) in patch units, row cu_q[b] + t; m == 0 gives zeros (per axis), as does n_y > 4096 (for the
+ * caller to refuse: S_b is device data).  One workgroup per row; marginals in LDS; fixed orders.  max_q == 0 or B == 0 returns at once.
+ * Errors: null operand, B > 512, grid_w outside 1 .. 4096, q outside [0, 0.5). */
+int acai_token_segments(const int64_t *tokens, int ld, const int32_t *lens, int R, const int64_t *delims, int n_delims, int64_t stop, int cap,
+                        int32_t *seg, int32_t *count, int32_t *bounds, void *stream);
+int acai_segment_reduce(const float *values, int K, int R, int ld, const int32_t *bounds, const int32_t *count, int cap, float *sum, float *vmin,
+                        float *vmax, int32_t *argmin, int32_t *argmax, void *stream);
+int acai_attn_map_segment_sum(const float *map, const int64_t *map_off, const int32_t *cu_q, const int32_t *cu_k, const float *weights,
+                              const int32_t *ranges, const int32_t *cu_seg, const int64_t *seg_map_off, int B, int max_k, int max_seg, float *out,
+                              void *stream);
+int acai_attn_map_extent(const float *map, const int64_t *map_off, const int32_t *cu_q, const int32_t *cu_k, const int32_t *grid_w, int B,
+                         int max_q, float q, float *ext, void *stream);
+
 /* nn.Dropout on a projection output followed by the residual add (torch TransformerEncoderLayer dropout1/dropout2, decoder dropout1-3,
  * transition head M:658): out = residual + keep * x / (1 - p); residual may be NULL (plain dropout, and its own backward on dy).
  * keep mask = counter-based hash of (seed, row, col). */
