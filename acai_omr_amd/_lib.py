@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("ACAI_OMR_LIB") or os.path.join(CSRC, "libacai_omr_hip.so")   # (override: A/B builds of the same sources, tools/ab_*.sh)
-SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "measures.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "decode_prefill.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip", "prune.hip", "assess.hip"]
+SOURCES = ["gemm.hip", "gemm_tile.hip", "gemm_ring.hip", "gemm_pp.hip", "elementwise.hip", "attn.hip", "attn_varlen.hip", "attn_probs.hip", "confidence.hip", "measures.hip", "attn_fwd64.hip", "attn_fwd64w.hip", "attn_bwd.hip", "attn_bwd64w.hip", "attn_bwd1p.hip", "train.hip", "grpo.hip", "seqdist.hip", "seqalign.hip", "grammar.hip", "loops.hip", "decode.hip", "decode_gemv.hip", "decode_attn.hip", "decode_select.hip", "decode_prefill.hip", "resize.hip", "augment.hip", "page.hip", "deskew.hip", "flatten.hip", "rectify.hip", "ingest.hip", "prune.hip", "assess.hip"]
 
 ACAI_F32, ACAI_BF16, ACAI_FP8_E4M3 = 0, 1, 2
 GEMM_GELU, GEMM_ROUND_BF16 = 1, 2
@@ -146,6 +146,10 @@ class AcaiPrompt(Structure):
 
 class AcaiGrammar(Structure):
     _fields_ = [("next", c_void_p), ("resync", c_void_p), ("state", c_void_p)] + [(n, c_int32) for n in ("states", "start", "rows", "pad_")]
+
+
+class AcaiLoop(Structure):
+    _fields_ = [(n, c_void_p) for n in ("run", "stop", "period", "start")] + [(n, c_int32) for n in ("rows", "max_period", "min_repeats", "min_tokens")]
 
 
 AUG_MAX_TAPS, AUG_MEAN_PARTS = 32, 128
@@ -325,6 +329,10 @@ _SIGNATURES = {
                                                      c_int, c_float, c_void_p]),
     "acai_grammar_scan": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p]),
+    "acai_decode_loop_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiLoop), c_void_p]),
+    "acai_decode_slot_loop_step": (c_int, [POINTER(AcaiDecoder), POINTER(AcaiSlots), POINTER(AcaiLoop), c_void_p]),
+    "acai_debug_decode_loop_select": (c_int, [c_int, POINTER(AcaiDecoder), POINTER(AcaiSlots), POINTER(AcaiLoop), c_int, c_void_p]),
+    "acai_repeat_scan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "acai_decode_logits": (c_int, [POINTER(AcaiDecoder), c_void_p, c_int, c_void_p]),
     "acai_decode_hidden": (c_int, [POINTER(AcaiDecoder), c_void_p, c_void_p]),
     "acai_decode_merge_in_launch": (c_int, [c_int, c_int]),

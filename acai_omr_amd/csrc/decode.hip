@@ -525,6 +525,39 @@ extern "C" int acai_decode_slot_grammar_sample_step(const AcaiDecoder *d, const 
     return launch_slot_grammar_sample(d, sl, g, uniforms, ld_uniforms, urow, top_k, temperature, st);
 }
 
+// Prologue of the loop-guard steps, after the counterpart's own checks (declared in decode_internal.h: acai_debug_decode_loop_select in
+// decode_select.hip applies the same checks).
+int check_loop(const AcaiDecoder *d, const AcaiLoop *loop, const char *fn) {
+    ACAI_CHECK_ARG(loop && loop->run && loop->stop && loop->period && loop->start, "%s: null loop counters or report", fn);
+    ACAI_CHECK_ARG(loop->rows >= d->B, "%s: loop rows %d below B = %d", fn, loop->rows, d->B);
+    ACAI_CHECK_ARG(loop->max_period >= 1 && loop->max_period <= 64, "%s: max_period %d outside [1, 64]", fn, loop->max_period);
+    ACAI_CHECK_ARG(loop->min_repeats >= 2, "%s: min_repeats %d below 2", fn, loop->min_repeats);
+    ACAI_CHECK_ARG(loop->min_tokens >= 1, "%s: min_tokens %d below 1", fn, loop->min_tokens);
+    return 0;
+}
+
+extern "C" int acai_decode_loop_step(const AcaiDecoder *d, const AcaiLoop *loop, void *stream) {
+    const bool chained = d && d->E % 4 == 0;
+    int rc = check_step(d, "acai_decode_loop_step", chained);
+    if (rc) return rc;
+    if ((rc = check_loop(d, loop, "acai_decode_loop_step"))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, !chained);
+    if (rc) return rc;
+    return launch_loop_argmax(d, loop, chained, st);
+}
+
+extern "C" int acai_decode_slot_loop_step(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiLoop *loop, void *stream) {
+    int rc = check_slots(d, sl, "acai_decode_slot_loop_step");
+    if (rc) return rc;
+    if ((rc = check_loop(d, loop, "acai_decode_slot_loop_step"))) return rc;
+    if ((rc = check_x_valid(d, "acai_decode_slot_loop_step", "acai_decode_slot_arm", "slot"))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode(d, nullptr, st, false, true, nullptr, sl);
+    if (rc) return rc;
+    return launch_slot_loop_argmax(d, sl, loop, st);
+}
+
 extern "C" int acai_decode_logits(const AcaiDecoder *d, const int64_t *tokens, int time_step, void *stream) {
     int rc = check_unembed(d, "acai_decode_logits");
     if (rc) return rc;

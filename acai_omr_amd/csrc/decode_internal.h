@@ -106,9 +106,14 @@ int launch_slot_grammar_argmax(const AcaiDecoder *d, const AcaiSlots *sl, const 
 int launch_slot_grammar_sample(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *gr, const float *uniforms, int ld_uniforms,
                                const int32_t *urow, int top_k, float temperature, hipStream_t st);
 
+int launch_loop_argmax(const AcaiDecoder *d, const AcaiLoop *lp, bool chained, hipStream_t st);
+int launch_slot_loop_argmax(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiLoop *lp, hipStream_t st);
+
 // ---- decode.hip: the checks of a sampling step's draw (`fn` names the entry point in the message), shared with the selection test entry ----
 int check_draw(const AcaiDecoder *d, const char *fn, const float *uniforms, int top_k, float temperature, int slot = 0, int ld_uniforms = 0,
                const int32_t *urow = nullptr);
+// the checks of a loop-guard descriptor, shared with the loop selection test entry
+int check_loop(const AcaiDecoder *d, const AcaiLoop *loop, const char *fn);
 
 // ---- decode_prefill.hip: the prompt's self K/V rows and the state its steps would leave, from one teacher-forced pass ------------------
 int launch_prefill_self_kv(const AcaiDecoder *d, int layer, const void *qkv, int ld, int C, hipStream_t st);

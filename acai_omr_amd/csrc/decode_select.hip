@@ -116,6 +116,10 @@ __device__ __forceinline__ int topk_draw_row(const float *lg, int V, int lane, f
 //           updated (grammar_advance).  With a table that allows every token the step computes what the plain one computes, bit for bit.
 //   PROMPT  prompted decoding (an extension: the reference starts every sequence from <bos> alone; greedy only, without SLOT or GRAMMAR).  The
 //           token at index t <= len[b] is the prompt's (prompt_len / prompt_token, the clamped reads of the prompt tables, are in common.h).
+//   LOOP    the loop guard (an extension: the reference lets a row repeat itself up to its cap; without GRAMMAR or PROMPT).  The wave that
+//           chose the row's token also keeps, in lane p - 1, the length run[b][p - 1] of the run of indices i ending at t with
+//           seq[i] == seq[i - p] (loop_check); the row ends at the first t where a period's run reaches need(p) = max((R - 1) p, M), the
+//           way a cap ends it.  With a guard that cannot fire the step computes what the plain one computes, bit for bit.
 // Only the combinations an entry point launches are instantiated.
 struct SelArgs {   // what every form takes, from AcaiDecoder
     const float *logits;
@@ -148,6 +152,10 @@ struct DrawArgs {   // a sampling step's draw: row b at time t takes uniforms[(S
     float inv_temperature;
     unsigned *ticket;      // SLOT with more than one workgroup: the arrival counter (zero between launches)
 };
+struct LoopArgs {   // AcaiLoop; R and M clamped to max_len + 1 by loop_args (a need above max_len never fires), so need(p) fits an int
+    int32_t *run, *stop, *period, *start;
+    int P, R, M;
+};
 template <bool ON, typename T> using part = std::conditional_t<ON, T, NoArgs>;
 
 // Wave-uniform: the table row of decode row b's state (clamped to [0, states)), or null when that state allows no token - the row is then
@@ -167,6 +175,31 @@ __device__ __forceinline__ int grammar_advance(const GrammarArgs &g, const int16
     return row ? row[tok] : g.resync[tok];
 }
 
+// The loop guard's part of a step, for the wave that chose `tok` for index t of row b (wave-uniform result): lane p - 1 compares the token
+// p indices back (one coalesced read of the row; only indices >= 1 take part, index 0 is <bos>) with the token in its register and counts
+// its run, +1 on a match, 0 otherwise - lanes past P and indices before 1 + p hold 0.  The verdict is one ballot over run >= need(p); the
+// lowest set bit is the smallest period.  Returns that period, or 0; an <eos> never counts as a loop stop (the row ends on it as it does
+// without a guard).  On a hit lane 0 writes the report: stop = t, the period, and start = t - need(p) - p + 1, the first index of the
+// periodic stretch.  O(1) a step: the row is not scanned again.
+__device__ __forceinline__ int loop_check(const LoopArgs &l, const int64_t *row, int b, int t, int tok, int eos, int lane) {
+    const int p = lane + 1;
+    const bool cmp = p <= l.P && t - p >= 1;
+    const int64_t prev = cmp ? row[t - p] : -1;
+    int32_t *run = l.run + (size_t)b * 64 + lane;
+    const int r = (cmp && prev == (int64_t)tok) ? *run + 1 : 0;
+    *run = r;
+    const int need = max((l.R - 1) * p, l.M);
+    const unsigned long long hit = __ballot(p <= l.P && r >= need);
+    if (!hit || tok == eos) return 0;
+    const int per = __builtin_ctzll(hit) + 1;
+    if (lane == 0) {
+        l.stop[b] = t;
+        l.period[b] = per;
+        l.start[b] = t - max((l.R - 1) * per, l.M) - per + 1;
+    }
+    return per;
+}
+
 // slot mode: the shared ring write index after a step
 __device__ __forceinline__ void advance_ring(int32_t *step, int Tmax) {
     const int nxt = step[1] + 1;
@@ -178,9 +211,10 @@ __device__ __forceinline__ void advance_ring(int32_t *step, int Tmax) {
 // t, the finished flag, the row's next input (write_next_input), then thread 0 publishes the unfinished count finished[B] and advances the
 // step.  PROMPT: the log-prob of token k is -(logf(se) - (logit[k] - max)); for the arg-max the inner difference is exactly 0 and the value is
 // the plain form's -logf(se) bit for bit (beam_select_kernel's form).  A row inside its prompt (t < len[b]) counts as unfinished.
-template <bool SLOT, bool GRAMMAR, bool PROMPT>
+// LOOP: a row that is already finished is not examined and its counters stand; a row the guard stops is finished from this step on.
+template <bool SLOT, bool GRAMMAR, bool PROMPT, bool LOOP = false>
 __global__ __launch_bounds__(1024) void greedy_select_kernel(SelArgs a, part<SLOT, SlotArgs> s, part<GRAMMAR, GrammarArgs> g,
-                                                            part<PROMPT, PromptArgs> p) {
+                                                            part<PROMPT, PromptArgs> p, part<LOOP, LoopArgs> l) {
     __shared__ int unfinished[16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     int t = 0, cnt = 0;
@@ -211,7 +245,13 @@ __global__ __launch_bounds__(1024) void greedy_select_kernel(SelArgs a, part<SLO
             fin = tok == a.eos || t >= s.cap[b] - 1;
         } else {
             fin = a.finished[b];
+            if constexpr (LOOP) {
+                if (!fin && loop_check(l, a.seqs + (size_t)b * a.max_len, b, t, tok, a.eos, lane)) fin = 1;   // wave-uniform
+            }
             if (tok == a.eos) fin = 1;
+        }
+        if constexpr (SLOT && LOOP) {
+            if (loop_check(l, a.seqs + (size_t)b * a.max_len, b, t, tok, a.eos, lane)) fin = 1;
         }
         if (lane == 0) {
             a.seqs[(size_t)b * a.max_len + t] = tok;
@@ -716,10 +756,16 @@ static DrawArgs draw_args(const AcaiDecoder *d, const float *uniforms, int ld, c
     return DrawArgs{uniforms, ld, urow, top_k, 1.0f / temperature, (unsigned *)d->tickets};
 }
 
-template <bool SLOT, bool GRAMMAR, bool PROMPT>
+static LoopArgs loop_args(const AcaiDecoder *d, const AcaiLoop *lp) {
+    const int top = d->max_len + 1;
+    return LoopArgs{lp->run, lp->stop, lp->period, lp->start, lp->max_period, min(lp->min_repeats, top), min(lp->min_tokens, top)};
+}
+
+template <bool SLOT, bool GRAMMAR, bool PROMPT, bool LOOP = false>
 static int launch_greedy(const AcaiDecoder *d, bool chained, part<SLOT, SlotArgs> s, part<GRAMMAR, GrammarArgs> g, part<PROMPT, PromptArgs> p,
-                         const char *name, hipStream_t st) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_select_kernel<SLOT, GRAMMAR, PROMPT>), dim3(1), row_waves(d), 0, st, select_args(d, chained), s, g, p);
+                         const char *name, hipStream_t st, part<LOOP, LoopArgs> l = {}) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_select_kernel<SLOT, GRAMMAR, PROMPT, LOOP>), dim3(1), row_waves(d), 0, st, select_args(d, chained), s, g,
+                       p, l);
     ACAI_LAUNCH_CHECK(name);
     return 0;
 }
@@ -750,6 +796,12 @@ int launch_slot_argmax(const AcaiDecoder *d, const AcaiSlots *sl, hipStream_t st
 }
 int launch_slot_grammar_argmax(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiGrammar *gr, hipStream_t st) {
     return launch_greedy<true, true, false>(d, true, slot_args(sl), grammar_args(gr), {}, "slot_grammar_argmax", st);
+}
+int launch_loop_argmax(const AcaiDecoder *d, const AcaiLoop *lp, bool chained, hipStream_t st) {
+    return launch_greedy<false, false, false, true>(d, chained, {}, {}, {}, "loop_argmax", st, loop_args(d, lp));
+}
+int launch_slot_loop_argmax(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiLoop *lp, hipStream_t st) {
+    return launch_greedy<true, false, false, true>(d, true, slot_args(sl), {}, {}, "slot_loop_argmax", st, loop_args(d, lp));
 }
 int launch_sample_logprob(const AcaiDecoder *d, const float *uniforms, int top_k, float temperature, bool chained, hipStream_t st) {
     return launch_sample<false, false>(d, chained, draw_args(d, uniforms, d->max_len, nullptr, top_k, temperature), {}, {}, "sample_logprob", st);
@@ -877,6 +929,26 @@ extern "C" int acai_debug_decode_select(int form, const AcaiDecoder *d, const Ac
         case ACAI_SELECT_SLOT_GRAMMAR_SAMPLE: return launch_slot_grammar_sample(d, sl, g, uniforms, ld_uniforms, urow, top_k, temperature, st);
         default: return launch_beam_select(d, bs, st);
     }
+}
+
+// Test entry (declared and documented in acai_omr_hip.h): acai_debug_decode_select's counterpart for the two loop-guard forms.
+extern "C" int acai_debug_decode_loop_select(int slot, const AcaiDecoder *d, const AcaiSlots *sl, const AcaiLoop *loop, int chained, void *stream) {
+    const char *fn = "acai_debug_decode_loop_select";
+    ACAI_CHECK_ARG(d, "%s: null decoder", fn);
+    ACAI_CHECK_ARG(d->logits && d->step && d->finished && d->seqs && d->logprobs, "%s: null logits / step / finished / seqs / logprobs", fn);
+    ACAI_CHECK_ARG(d->B >= 1 && d->V >= 1 && d->E >= 1 && d->Tmax >= 1 && d->max_len > 1, "%s: bad dims B=%d V=%d E=%d Tmax=%d max_len=%d", fn,
+                   d->B, d->V, d->E, d->Tmax, d->max_len);
+    ACAI_CHECK_ARG(chained || !slot, "%s: a slot selection always writes the next input (chained = 0 with slot = %d)", fn, slot);
+    ACAI_CHECK_ARG(!chained || (d->emb && d->pos && d->x), "%s: a chained selection needs emb, pos and x", fn);
+    ACAI_CHECK_ARG(!chained || d->E % 4 == 0, "%s: a chained selection needs E %% 4 == 0 (E=%d)", fn, d->E);
+    if (slot) {
+        ACAI_CHECK_ARG(sl && sl->t && sl->cap && sl->rows >= d->B, "%s: null slot state or rows < B", fn);
+        ACAI_CHECK_ARG(d->max_len <= d->Tmax, "%s: a slot selection needs max_len <= Tmax (max_len=%d Tmax=%d)", fn, d->max_len, d->Tmax);
+    }
+    int rc = check_loop(d, loop, fn);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return slot ? launch_slot_loop_argmax(d, sl, loop, st) : launch_loop_argmax(d, loop, chained != 0, st);
 }
 
 // Test entry (declared and documented in acai_omr_hip.h): ONE launch of spec_accept_kernel on the state and logits the caller wrote, through

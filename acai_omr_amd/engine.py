@@ -280,7 +280,8 @@ class DecodeEngine:
         # ("slot_sample", top_k, temperature) (continuous batching, sampled), ("spec", D, ngram) (speculative greedy; ngram 0 = drafts from
         # the injected table), ("prompt",) (greedy from given tokens) or ("spec", D, ngram, "prompt") (the two together); a run sets it and
         # restores greedy when it ends.  Grammar-constrained decoding: ("grammar",), ("grammar_sample", top_k, temperature), ("slot_grammar",),
-        # ("slot_grammar_sample", top_k, temperature) - the four forms above with the token choice masked by a token automaton
+        # ("slot_grammar_sample", top_k, temperature) - the four forms above with the token choice masked by a token automaton.  Loop guard:
+        # ("loop", P, R, M) and ("slot_loop", P, R, M) - greedy and slot with the guard's check in the selection launch
         self._mode = ("greedy",)
         self.uniforms = None    # (Bmax, Tmax) uniforms of the sampling step, allocated on first use
         self.beam_anc = None    # beam-search lineage [2][Bmax][Tmax] (anc / tok / lp) and per-row cum / len, allocated on first use
@@ -299,6 +300,8 @@ class DecodeEngine:
         self._mem = None        # the packed memories of the last prepare() (mem32, memb): a prompt prefill's pass reads them again
         self.prefilled_tokens = 0   # prompt tokens (rows x depth) that prefilled runs took in their pass instead of in prompt steps, so far
         self.gram_next = None   # grammar-constrained decoding: engine-owned copies of the automaton's tables and the rows' states (_set_grammar)
+        self.loop_run = None    # loop guard: (Bmax, 64) int32 run counters and the (3, Bmax) int32 report (stop, period, start), allocated on first use (_set_loop)
+        self.cont_loops = None  # the report of the last guarded continuous-batching run, (3, N) int32 per image
         self._per_row_cross = False
         self.cache_len = 0
         self._desc = None
@@ -493,7 +496,7 @@ class DecodeEngine:
         cur.wait_stream(self.stream)
 
     # ---- ViTOMR.cached_greedy_generate (models.py:600-615) ----------------------------------------------------------
-    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None, prompt=None, *, grammar=None, prefill=False):
+    def greedy(self, max_len, poll=16, use_graph=True, on_chunk=None, prompt=None, *, grammar=None, prefill=False, loop_guard=None):
         """Runs up to max_len-1 greedy steps; returns views seqs (B,max_len) int64 and logprobs (B,max_len) fp32.
         Early exit when every row has produced <eos> (checked every `poll` steps; overshoot is masked later).
         prompt (an extension; None = off): one token list / 1-D tensor per row, the row's tokens of indices 1 .. P (_set_prompt); the row
@@ -501,7 +504,18 @@ class DecodeEngine:
         grammar (an extension; None = off): a grammar.TokenAutomaton - every row takes the best token its automaton state allows and
         logprobs holds the log-softmax over the allowed tokens (_set_grammar); not combinable with prompt.
         prefill (an extension; False = off): with a prompt, the C = min P tokens every row has are computed in one teacher-forced pass
-        (_prefill) and the prompt steps start at index C + 1; without a prompt, or with an empty one in the batch, it changes nothing."""
+        (_prefill) and the prompt steps start at index C + 1; without a prompt, or with an empty one in the batch, it changes nothing.
+        loop_guard (an extension; None = off): a loops.LoopGuard - a row whose tail is periodic by the guard's rule is finished at that index
+        inside the replayed graph, like a row that produced <eos> (but no <eos> is written; the caller cuts the row at loop_report()'s
+        stop), so a batch of looping rows ends early; mode ("loop", P, R, M).  Not combinable with prompt, grammar or prefill."""
+        from .loops import check_guard, refuse_guard
+        if check_guard(loop_guard) is not None:
+            for arg, what in ((prompt, "prompt (prompted decoding)"), (grammar, "grammar (constrained decoding)"), (prefill or None, "prefill")):
+                if arg is not None:
+                    refuse_guard(loop_guard, what)
+            with self._run(max_len, ("loop",) + loop_guard.params):
+                self._set_loop(loop_guard)
+                return self._decode_loop(max_len, poll, use_graph, on_chunk)
         if grammar is not None:
             if prompt is not None:
                 raise ValueError("grammar (constrained decoding) cannot be combined with prompt (prompted decoding): out of scope here")
@@ -631,6 +645,25 @@ class DecodeEngine:
             self.gram_resync.copy_(src_resync)
             self._gram_src = automaton
 
+    # ---- the loop guard (an extension: the reference lets a looping row run to its cap) --------------------------------------------------------
+    LOOP_MODES = ("loop", "slot_loop")
+
+    def _set_loop(self, guard):
+        """The guard's state in engine-owned device buffers that keep their address from run to run (_set_grammar's pattern), so the
+        captured loop-mode graphs stay valid.  P, R and M are launch arguments: they are part of the mode, and with it of the graph key."""
+        if self.loop_run is None:
+            self.loop_run = torch.zeros(self.Bmax, 64, dtype=torch.int32, device=self.device)
+            self.loop_rep = torch.zeros(3, self.Bmax, dtype=torch.int32, device=self.device)
+            d = _lib.AcaiLoop()
+            d.run, d.rows = self.loop_run.data_ptr(), self.Bmax
+            d.stop, d.period, d.start = (self.loop_rep[k].data_ptr() for k in range(3))
+            self._loop_desc = d
+        self._loop_desc.max_period, self._loop_desc.min_repeats, self._loop_desc.min_tokens = guard.params
+
+    def loop_report(self):
+        """(stop, period, start) int32 (B,) views of the last guarded static run's report (period 0: the row did not loop)."""
+        return self.loop_rep[0, :self.B], self.loop_rep[1, :self.B], self.loop_rep[2, :self.B]
+
     # ---- GRPOViTOMR.cached_forward_rollout_policy (models.py:988-1049) ---------------------------------------------------------
     def sample(self, max_actions, top_k, temperature, uniforms=None, poll=16, use_graph=True, *, grammar=None):
         """Up to max_actions-1 sampling steps (top-k, temperature, inverse-CDF draw from `uniforms` (B, max_actions) in [0,1) - drawn from
@@ -650,13 +683,19 @@ class DecodeEngine:
             self.uniforms[:B, :max_actions] = uniforms.to(device=self.device, dtype=torch.float32)
             return self._decode_loop(max_actions, poll, use_graph)
 
-    def greedy_chunks(self, max_len, chunk, prompt=None, *, grammar=None, prefill=False):
+    def greedy_chunks(self, max_len, chunk, prompt=None, *, grammar=None, prefill=False, loop_guard=None):
         """Generator over the greedy loop in chunks of `chunk` tokens (streamed inference): yields (tokens_done, all_finished)
         after each chunk; the decode graph is replayed on the engine's stream, the caller's stream waits for it.
         prompt / grammar: as in greedy(); the mode is ("prompt",) / ("grammar",) while the generator runs and goes back to greedy when it
         ends or is closed.
         prefill: as in greedy().  The C prefilled tokens are there at once: every multiple of `chunk` up to C is yielded without a step in
-        between, and the first chunk of steps ends at the next multiple, so tokens_done takes the values it takes without prefill."""
+        between, and the first chunk of steps ends at the next multiple, so tokens_done takes the values it takes without prefill.
+        loop_guard: as in greedy(); the mode is ("loop", P, R, M) while the generator runs."""
+        from .loops import check_guard, refuse_guard
+        if check_guard(loop_guard) is not None:
+            for arg, what in ((prompt, "prompt (prompted decoding)"), (grammar, "grammar (constrained decoding)"), (prefill or None, "prefill")):
+                if arg is not None:
+                    refuse_guard(loop_guard, what)
         if max_len > self.Tmax:
             raise RuntimeError(f"{max_len} decoding steps is too long for max sequence length of {self.Tmax}")
         if grammar is not None and prompt is not None:
@@ -668,12 +707,16 @@ class DecodeEngine:
             self._mode = ("prompt",)
         if grammar is not None:
             self._mode = ("grammar",)
+        if loop_guard is not None:
+            self._mode = ("loop",) + loop_guard.params
         try:
             with torch.cuda.stream(self.stream):
                 if prompt is not None:
                     self._set_prompt(prompt, self.B, max_len)
                 if grammar is not None:
                     self._set_grammar(grammar)
+                if loop_guard is not None:
+                    self._set_loop(loop_guard)
                 self._arm_and_capture(self.B)
                 if plan is not None:
                     self._prefill(plan[0])
@@ -700,7 +743,7 @@ class DecodeEngine:
                 if fin:
                     return
         finally:
-            if prompt is not None or grammar is not None:
+            if prompt is not None or grammar is not None or loop_guard is not None:
                 self._mode = ("greedy",)
 
     # ---- beam search (an extension: the reference decodes greedily) ----------------------------------------------------------------------
@@ -822,7 +865,7 @@ class DecodeEngine:
         self.beam_len[:B].zero_()
 
     def arm(self, B):
-        if self._mode[0] in ("slot", "slot_sample", "slot_grammar", "slot_grammar_sample"):
+        if self._mode[0] in ("slot", "slot_sample", "slot_grammar", "slot_grammar_sample", "slot_loop"):
             self._slot_reset()
             return
         if self._mode[0] == "spec":
@@ -839,6 +882,9 @@ class DecodeEngine:
             self._arm_beam(B)
         if self._mode[0] in ("grammar", "grammar_sample"):
             self.gram_state[:B].fill_(self._gram_desc.start)
+        if self._mode[0] == "loop":
+            self.loop_run[:B].zero_()
+            self.loop_rep[:, :B].zero_()
         # input of the first step (<bos> at position 1, quirk Q1); each step's selection kernel (greedy_select_kernel / sample_select_kernel) writes the next step's input
         _lib.check(_lib.lib().acai_decode_embed(ctypes.byref(self._desc), ops._st()), "acai_decode_embed")
         self._x_valid = True
@@ -873,6 +919,10 @@ class DecodeEngine:
             _lib.check(L.acai_decode_slot_grammar_sample_step(d, ctypes.byref(self._slot_desc), ctypes.byref(self._gram_desc),
                                                               self.slot_uniforms.data_ptr(), self.Tmax, self.slot_urow.data_ptr(), mode[1],
                                                               mode[2], st), "acai_decode_slot_grammar_sample_step")
+        elif mode[0] == "loop":
+            _lib.check(L.acai_decode_loop_step(d, ctypes.byref(self._loop_desc), st), "acai_decode_loop_step")
+        elif mode[0] == "slot_loop":
+            _lib.check(L.acai_decode_slot_loop_step(d, ctypes.byref(self._slot_desc), ctypes.byref(self._loop_desc), st), "acai_decode_slot_loop_step")
         elif mode[0] == "slot_sample":
             _lib.check(L.acai_decode_slot_sample_step(d, ctypes.byref(self._slot_desc), self.slot_uniforms.data_ptr(), self.Tmax,
                                                       self.slot_urow.data_ptr(), mode[1], mode[2], st), "acai_decode_slot_sample_step")
@@ -957,7 +1007,7 @@ class DecodeEngine:
 
     # ---- continuous batching (an extension: the reference decodes one static batch) ----------------------------------------------------
     def continuous(self, mem32, memb, lens, caps, slots, poll=16, use_graph=True, sample=None, uniforms=None, group=1, *, grammar=None,
-                   flush=None):
+                   flush=None, loop_guard=None):
         """Decode of len(lens) images through `slots` decode rows that are refilled as they finish: greedy, or with sample=(top_k,
         temperature) sampled as DecodeEngine.sample samples.  mem32 / memb: the images' packed memories (M, E) fp32 / bf16 copy, lens
         their lengths, caps[i] image i's cap (its row ends after token index caps[i] - 1, or at <eos>).  Checks the arguments at the call,
@@ -978,7 +1028,15 @@ class DecodeEngine:
         next steps are in flight, ("step", image, start, tokens, log_probs) for every busy slot with news, in slot order - tokens int32
         and log_probs fp32, (1, n), on the CPU, the row's indices start .. start + n - 1 - and then ("finish", image) for the slots freed
         at that poll; images with a cap below 2 are ("finish", image) up front.  An image's steps tile its row from index 1 through its
-        last token.  The same graphs are replayed: streaming adds no graph key."""
+        last token.  The same graphs are replayed: streaming adds no graph key.
+        loop_guard (None = off): a loops.LoopGuard - a sequence whose tail is periodic by the guard's rule frees its slot at that index, as a
+        cap would; its row holds the tokens through `stop`, and `cont_loops` (3, N) int32 the images' (stop, period, start), copied with
+        the row.  Mode ("slot_loop", P, R, M).  Greedy runs only: with sample=, grammar= or flush= a ValueError."""
+        from .loops import check_guard, refuse_guard
+        if check_guard(loop_guard) is not None:
+            for arg, what in ((sample, "sample (sampled rollouts)"), (grammar, "grammar (constrained decoding)"), (flush, "flush (streaming)")):
+                if arg is not None:
+                    refuse_guard(loop_guard, what)
         S = int(slots)
         caps = [int(c) for c in caps]
         if max(caps) > self.Tmax:
@@ -1012,9 +1070,12 @@ class DecodeEngine:
                 raise ValueError("flush (streaming) cannot be combined with sample: rollouts have no consumer for a stream")
             if isinstance(flush, bool) or not isinstance(flush, int) or not 1 <= flush <= self.Tmax:
                 raise ValueError(f"flush must be an int in [1, {self.Tmax}] (the cache's max sequence length), got {flush!r}")
-        return self._continuous(mem32, memb, lens, caps, S, poll, use_graph, mode, uniforms, G, grammar, flush)
+        if loop_guard is not None:
+            mode = ("slot_loop",) + loop_guard.params
+        return self._continuous(mem32, memb, lens, caps, S, poll, use_graph, mode, uniforms, G, grammar, flush, loop_guard)
 
-    def _continuous(self, mem32, memb, lens, caps, S, poll, use_graph, mode=("slot",), uniforms=None, G=1, grammar=None, flush=None):
+    def _continuous(self, mem32, memb, lens, caps, S, poll, use_graph, mode=("slot",), uniforms=None, G=1, grammar=None, flush=None,
+                    loop_guard=None):
         N, dev, own = len(caps), self.device, self.omr
         if flush is not None:
             poll = flush
@@ -1026,6 +1087,7 @@ class DecodeEngine:
         self.cont_seqs = torch.full((N, W), own.pad_idx, dtype=torch.int64, device=dev)
         self.cont_seqs[:, 0] = own.bos_idx
         self.cont_lps = torch.zeros(N, W, dtype=torch.float32, device=dev)
+        self.cont_loops = torch.zeros(3, N, dtype=torch.int32, device=dev) if loop_guard is not None else None
         sched = SlotScheduler(caps, S)
         offs = [0]
         for l in lens:
@@ -1042,6 +1104,8 @@ class DecodeEngine:
                     self._slot_uniforms(uniforms)
                 if grammar is not None:
                     self._set_grammar(grammar)
+                if loop_guard is not None:
+                    self._set_loop(loop_guard)
                 self._mode = mode
                 if flush is not None:
                     self._flush_setup(S, flush)   # before arming: _slot_reset parks the marks with the slots
@@ -1069,6 +1133,8 @@ class DecodeEngine:
                         c = caps[i]
                         self.cont_seqs[i, :c].copy_(self.seqs[s, :c])
                         self.cont_lps[i, :c].copy_(self.logprobs[s, :c])
+                        if loop_guard is not None:
+                            self.cont_loops[:, i].copy_(self.loop_rep[:, s])
                     harvested.record(self.stream)
                     self._slot_refill(sched.admit(), mem, offs, lens_dev, caps)
                     for s in sched.idle():
@@ -1164,6 +1230,9 @@ class DecodeEngine:
         if self._flush_ld:   # a streamed run: a parked slot is finished at t = 1, so its end is 2 - nothing to send
             self.slot_mark.fill_(2)
         self.cross_len[:S].fill_(1)
+        if self._mode[0] == "slot_loop":
+            self.loop_run[:S].zero_()
+            self.loop_rep[:, :S].zero_()
         self._parked = set(range(S))
         self.cache_len = 0
         _lib.check(_lib.lib().acai_decode_slot_arm(ctypes.byref(self._desc), ctypes.byref(self._slot_desc), None, 0, ops._st()),
@@ -1197,6 +1266,10 @@ class DecodeEngine:
         if self._mode[0] in ("slot_grammar", "slot_grammar_sample"):   # a refilled row starts in the automaton's start state; rows that stay
             for s, _ in admitted:                                      # idle keep whatever their state holds (it is never read)
                 self.gram_state[s:s + 1].fill_(self._gram_desc.start)
+        if self._mode[0] == "slot_loop":   # a refilled row starts with no run behind it and no report
+            for s, _ in admitted:
+                self.loop_run[s].zero_()
+                self.loop_rep[:, s].zero_()
         if sampled:
             table.append([i for _, i in admitted])   # the slot's uniforms row: the sequence's own, whichever slot it lands in
         rows = ops.h2d(torch.tensor(table, dtype=torch.int32), self.device)

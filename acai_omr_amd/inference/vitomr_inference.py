@@ -45,7 +45,7 @@ def _full_grid(dims, lens, pruned):
 
 
 def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1, length_penalty=1.0, speculative=0, ngram=3, prefix=None, *,
-              grammar=None, prune=None, prefill=False):
+              grammar=None, prune=None, prefill=False, loop_guard=None):
     """img: one (1,H,W) tensor or a list of them -> (seqs int64 (B,T'), log_probs fp32 (B,T'), seq_mask bool (B,T')).
     beam_width > 1 (extension): beam search with that many hypotheses per image, scored by cum / len^length_penalty
     (ViTOMR.cached_beam_generate); beam_width = 1 is the reference's greedy decode.
@@ -66,7 +66,13 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
     checkpoint have not been measured.
     prefill (an extension, default False = off: the paths above, bit for bit, no launch added): prompt prefill of greedy prompted decoding
     (ViTOMR.cached_greedy_generate) - the prompt tokens all images have in one teacher-forced pass instead of one decode step each.  With
-    speculative, beam_width > 1, grammar or an FP8 memory cache it raises ValueError (out of scope here)."""
+    speculative, beam_width > 1, grammar or an FP8 memory cache it raises ValueError (out of scope here).
+    loop_guard (an extension, default None = off: the paths above, bit for bit, no launch added): a `loops.LoopGuard` - greedy decoding in
+    which a row that fell into a repeat cycle ends at the index where the guard's rule fires (ViTOMR.cached_greedy_generate), found on
+    the device inside the replayed graph; the `loops.LoopReport` is appended to the result.  With beam_width > 1, speculative, prefix,
+    prefill or grammar it raises ValueError (out of scope here; `loops.scan_repeats` covers their output after the fact).  How often
+    trained checkpoints loop, and which thresholds separate a runaway row from a genuine ostinato, has not been measured."""
+    _check_loop_guard(loop_guard, beam_width, speculative, prefix, grammar, prefill)
     if grammar is not None:
         for other, on in (("beam search (beam_width > 1)", beam_width != 1), ("speculative decoding (speculative)", bool(speculative)),
                           ("prompted decoding (prefix)", prefix is not None)):
@@ -89,7 +95,20 @@ def inference(vitomr: ViTOMR, img, device, max_inference_len=1536, beam_width=1,
             if beam_width != 1:
                 return vitomr._beam_packed(None if bf else mem, mem if bf else None, lens, beam_width, max_inference_len, length_penalty)
             return vitomr._greedy_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, prefix=prefix, grammar=grammar,
-                                         prefill=prefill)
+                                         prefill=prefill, loop_guard=loop_guard)
+
+
+def _check_loop_guard(loop_guard, beam_width=1, speculative=0, prefix=None, grammar=None, prefill=False):
+    """loop_guard of the entry points: None or a loops.LoopGuard (TypeError), and none of the modes it cannot be combined with (ValueError
+    naming the mode)."""
+    from ..loops import check_guard, refuse_guard
+    if check_guard(loop_guard) is None:
+        return
+    for other, on in (("beam search (beam_width > 1)", beam_width != 1), ("speculative decoding (speculative)", bool(speculative)),
+                      ("prompted decoding (prefix)", prefix is not None), ("prompt prefill (prefill)", bool(prefill)),
+                      ("grammar (constrained decoding)", grammar is not None)):
+        if on:
+            refuse_guard(loop_guard, other)
 
 
 def _check_prefill(prefill, beam_width, speculative, grammar):
@@ -272,20 +291,24 @@ def _encode_chunks(vitomr, imgs, device, prune=None):
     return (mems[0] if len(mems) == 1 else torch.cat(mems)), lens
 
 
-def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None, prune=None):
+def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None, prune=None,
+                              loop_guard=None):
     """Continuous-batching greedy inference (an extension) as a generator: yields (index, seqs (1,T'), log_probs (1,T'), mask (1,T')) for
     each image as soon as it finishes, in completion order; each is what inference(vitomr, [imgs[index]]) returns.  max_inference_len: one
     cap or a list of per-image caps; slots: decode rows (default: the cache's max batch size).  prefix (prompted decoding, inference())
     is not supported here: anything but None raises ValueError.  grammar: constrained decoding as in inference().  prune: blank-patch
-    pruning as in inference(); imgs may then also be a `utils.PackedPatches`, pruned or not."""
+    pruning as in inference(); imgs may then also be a `utils.PackedPatches`, pruned or not.  loop_guard: loop detection as in inference()
+    (not with grammar) - an image that loops frees its row where the rule fires, and each tuple ends with the image's `loops.LoopReport`."""
     vitomr._no_prefix(prefix, "continuous batching")
+    _check_loop_guard(loop_guard, grammar=grammar)
     vitomr.eval()
     imgs = imgs if isinstance(imgs, PackedPatches) else list(imgs)
     with torch.no_grad():
         mem, lens = _encode_chunks(vitomr, imgs, device, prune)
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
-            run = vitomr._continuous_packed_iter(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
+            run = vitomr._continuous_packed_iter(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar,
+                                                 loop_guard=loop_guard)
 
     def images():
         with torch.no_grad():
@@ -293,23 +316,28 @@ def iter_continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=15
     return images()
 
 
-def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None, prune=None):
+def continuous_inference(vitomr: ViTOMR, imgs, device, max_inference_len=1536, slots=None, prefix=None, *, grammar=None, prune=None,
+                         loop_guard=None):
     """inference() over a list of any length through continuous batching (an extension): `slots` decode rows work through the images in
     input order and a finished row is refilled with the next image at once.  Returns exactly what inference(vitomr, imgs, ...) returns
     (seqs (N,T'), log_probs (N,T'), mask (N,T'), clipped to the longest row); max_inference_len may be a list of per-image caps.  prefix
     (prompted decoding, inference()) is not supported here: anything but None raises ValueError.  grammar: constrained decoding as in
-    inference().  prune: blank-patch pruning as in inference(); imgs may then also be a `utils.PackedPatches`, pruned or not."""
+    inference().  prune: blank-patch pruning as in inference(); imgs may then also be a `utils.PackedPatches`, pruned or not.
+    loop_guard: loop detection as in inference() (not with grammar) - a looping image frees its row where the rule fires instead of
+    holding it to its cap, and the `loops.LoopReport` over the N images is appended to the result."""
     vitomr._no_prefix(prefix, "continuous batching")
+    _check_loop_guard(loop_guard, grammar=grammar)
     vitomr.eval()
     imgs = imgs if isinstance(imgs, PackedPatches) else list(imgs)
+    kw = {} if loop_guard is None else {"loop_guard": loop_guard}
     with torch.no_grad():
         mem, lens = _encode_chunks(vitomr, imgs, device, prune)
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
-            return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
+            return vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar, **kw)
 
 
-def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, assess=None, prune=None, grammar=None, orient=None, deskew=None, flatten=None, rectify=None):
+def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_inference_len=1536, slots=None, detect=None, *, assess=None, prune=None, grammar=None, loop_guard=None, orient=None, deskew=None, flatten=None, rectify=None):
     """Whole pages in, their systems decoded as one batch (an extension; the reference's service crops hand-drawn boxes with PIL and decodes
     them one by one, acai_omr/ui/routes.py:93-129) -> a `page.PageResult`.
     pages: one (H,W) / (1,H,W) tensor or a list of them, uint8 or float in [0, 1]; a decoded colour photo, uint8 (H, W, 3), (H, W, 4) or
@@ -319,7 +347,8 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     as the stages before detection leave it: UPRIGHT, rectified, levelled.  resize: the `utils.DynamicResize` every box goes through.
     All systems of all pages are cut out and resized into one packed patch stream by one launch pair (page.split_pages), encoded in chunks
     of the cache's batch size and decoded by continuous batching: the rows are what continuous_inference returns for the resized crops, in
-    page order and top to bottom.  max_inference_len, slots, grammar: as in continuous_inference.  A page without systems contributes no
+    page order and top to bottom.  max_inference_len, slots, grammar, loop_guard: as in continuous_inference; with a loop guard the
+    result's `loops` is the `loops.LoopReport` over the systems.  A page without systems contributes no
     rows; with no system at all nothing is encoded or decoded and the result is empty.
 
     The stages, every one an extension that is off at None or False (the path above, unchanged: no launch added, no copy made), in the
@@ -343,16 +372,20 @@ def page_inference(vitomr: ViTOMR, pages, device, resize, boxes=None, max_infere
     systems at once.  `PageResult.to_page_xy` / `from_page_xy` / `box_corners` go back through 4, 2 and 1 to the pages as they were passed
     in.  orient=True gives, bit for bit, what orient=<the estimated codes> gives.  The defaults of every config were chosen on synthetic
     pages and not measured on real photographs (there are none in this repository)."""
+    _check_loop_guard(loop_guard, grammar=grammar)
     pages, per_page, plans, specials, extra, prune = _page_front(vitomr, pages, resize, boxes, detect, assess, prune, orient, deskew, flatten, rectify)
     system_page, sizes, windows = [p for p, *_ in plans], [s for _, _, s, _ in plans], [c for *_, c in plans]
     if not plans:
         return pg.PageResult(per_page, None, None, None, [], [], [], specials, **extra)
     vitomr.eval()
+    kw = {} if loop_guard is None else {"loop_guard": loop_guard}
     with torch.no_grad():
         packed, total, mem, lens = _page_encode(vitomr, pages, per_page, resize, prune, device)
         bf = mem.dtype == torch.bfloat16
         with autocast(device_type=device, dtype=torch.bfloat16):
-            seqs, lps, mask = vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots, grammar=grammar)
+            seqs, lps, mask, *loops = vitomr._continuous_packed(None if bf else mem, mem if bf else None, lens, max_inference_len, slots,
+                                                                grammar=grammar, **kw)
+    extra = dict(extra, loops=loops[0]) if loops else extra
     return pg.PageResult(per_page, seqs, lps, mask, system_page, sizes, windows, specials, patches_kept=packed.lens, patches_total=total, **extra)
 
 

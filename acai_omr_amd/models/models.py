@@ -1156,13 +1156,36 @@ class ViTOMR(nn.Module):
         if prefill and grammar is not None:
             raise ValueError("prefill (prompt prefill) cannot be combined with grammar (constrained decoding): out of scope here")
 
-    def _greedy_packed(self, mem32, memb, lens, max_len, on_chunk=None, prefix=None, grammar=None, *, prefill=False):
+    @staticmethod
+    def _check_loop_guard(loop_guard, **others):
+        """Loop detection (an extension): `loop_guard` as the entry points take it - None, or a loops.LoopGuard (TypeError otherwise);
+        others: the arguments of the modes it cannot be combined with, by the name the ValueError gives them (None / False = not used)."""
+        from ..loops import check_guard, refuse_guard
+        if check_guard(loop_guard) is not None:
+            for what, arg in others.items():
+                if arg is not None and arg is not False:
+                    refuse_guard(loop_guard, what)
+        return loop_guard
+
+    def _loop_result(self, seqs, lps, caps, stop, period, start, guard):
+        """A guarded run's rows -> (seqs, log_probs, mask, LoopReport): a loop stop is a cap found on the device, so the mask is
+        _mask_and_clip_capped's at the effective caps - stop + 1, or start + period with trim (one copy of the cycle)."""
+        from ..loops import LoopReport
+        report = LoopReport(stop.clone(), period.clone(), start.clone())
+        return self._mask_and_clip_capped(seqs, lps, report.caps(caps, guard.trim)) + (report,)
+
+    def _greedy_packed(self, mem32, memb, lens, max_len, on_chunk=None, prefix=None, grammar=None, *, prefill=False, loop_guard=None):
         blocks = self.decoder._cached_blocks()
         self._check_grammar(grammar, prefix)
         self._check_prefill(prefill, grammar)
+        self._check_loop_guard(loop_guard, **{"prefix (prompted decoding)": prefix, "grammar (constrained decoding)": grammar,
+                                              "prefill (prompt prefill)": prefill})
         prompt = self._check_prefix(prefix, len(lens), max_len)
         blocks.prepare_caches_packed(mem32, memb, lens)
         eng = blocks.engine(self.decoder.pos_embedding.device)
+        if loop_guard is not None:
+            seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk, loop_guard=loop_guard)
+            return self._loop_result(seqs.clone(), lps.clone(), [max_len] * len(lens), *eng.loop_report(), loop_guard)
         if grammar is not None:
             seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk, grammar=grammar)
         else:
@@ -1170,7 +1193,8 @@ class ViTOMR(nn.Module):
             seqs, lps, _ = eng.greedy(max_len, on_chunk=on_chunk) if prompt is None else eng.greedy(max_len, on_chunk=on_chunk, prompt=prompt, **kw)
         return self.mask_and_clip_seqs(seqs.clone(), lps.clone())
 
-    def cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, prefix=None, *, grammar=None, prefill=False):
+    def cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, prefix=None, *, grammar=None, prefill=False,
+                               loop_guard=None):
         """Batched greedy decode with KV caching (M:600-615) -> seqs (B,T') int64, log_probs (B,T') fp32, mask (B,T') bool.
         The whole loop runs as replays of one captured hipGraph; the host only polls an "all finished" counter.
         prefix (an extension, default None = off): prompted decoding - one entry per image (a 1-D integer tensor or list, possibly empty;
@@ -1187,9 +1211,14 @@ class ViTOMR(nn.Module):
         with P_i > C keep taking their forced tokens there).  The tokens of a prompt and the mask are what they are without it; the
         log-probs of indices 1 .. C come from the pass and, like everything decoded after them, agree with the stepwise run's within the
         pass-versus-decode bars (1e-4 fp32, 0.07 bf16), so a free token can differ where the model's top two logits are that close.
-        Without a prefix, or with an empty prompt in the batch, it changes nothing.  Not with an FP8 memory cache (ValueError)."""
+        Without a prefix, or with an empty prompt in the batch, it changes nothing.  Not with an FP8 memory cache (ValueError).
+        loop_guard (an extension, default None = off): a loops.LoopGuard - a row whose tail is periodic by the guard's rule (loops.py) ends at
+        that index, `stop`, inside the replayed graph: it counts as finished from there on, so a batch whose remaining rows all loop ends
+        early.  Up to `stop` tokens, log-probs and mask are bitwise the unguarded call's; the mask ends at `stop` (with trim: after one copy
+        of the cycle) and no <eos> is written.  A fourth value is returned then, the loops.LoopReport (stop, period, start per row; period
+        0 = no loop).  Not combinable with prefix, grammar or prefill (ValueError)."""
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
-        return self._greedy_packed(mem32, None, lens, max_len, prefix=prefix, grammar=grammar, prefill=prefill)
+        return self._greedy_packed(mem32, None, lens, max_len, prefix=prefix, grammar=grammar, prefill=prefill, loop_guard=loop_guard)
 
     def _beam_packed(self, mem32, memb, lens, beam_width, max_len, length_penalty):
         blocks = self.decoder._cached_blocks()
@@ -1204,14 +1233,17 @@ class ViTOMR(nn.Module):
         seqs, lps, _ = eng.beam(max_len, K, length_penalty)
         return self.mask_and_clip_seqs(seqs, lps)
 
-    def cached_beam_generate(self, img_latent, latent_attention_mask=None, beam_width=4, max_len=1536, length_penalty=1.0, prefix=None):
+    def cached_beam_generate(self, img_latent, latent_attention_mask=None, beam_width=4, max_len=1536, length_penalty=1.0, prefix=None, *,
+                             loop_guard=None):
         """Beam-search decode with KV caching (an extension: the reference decodes greedily) -> seqs (B,T') int64, log_probs (B,T') fp32 per
         token, mask (B,T') bool, as cached_greedy_generate.  Each image keeps beam_width hypotheses; a step extends each live one by its
         beam_width best tokens, keeps the beam_width best by cumulative log-probability, and a hypothesis ends at <eos>.  The result per image
         is the hypothesis with the highest cum / len^length_penalty (len: tokens after <bos>, <eos> included).  beam_width = 1 is greedy,
         bit for bit.  The K hypotheses of an image share its cross K/V; a selection moves no self K/V, only an ancestor table.
-        prefix (prompted decoding, cached_greedy_generate) is not supported here: anything but None raises ValueError."""
+        prefix (prompted decoding, cached_greedy_generate) is not supported here: anything but None raises ValueError; so does a
+        loop_guard (loops.scan_repeats covers the result after the fact)."""
         self._no_prefix(prefix, "beam search")
+        self._check_loop_guard(loop_guard, **{"beam search": True})
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._beam_packed(mem32, None, lens, beam_width, max_len, length_penalty)
 
@@ -1232,7 +1264,8 @@ class ViTOMR(nn.Module):
         seqs, lps, _ = eng.speculative(max_len, D, ngram=ngram, drafts=drafts, poll=poll, use_graph=use_graph, **kw)
         return self.mask_and_clip_seqs(seqs.clone(), lps.clone())
 
-    def cached_speculative_generate(self, img_latent, latent_attention_mask=None, max_len=1536, draft_len=4, ngram=3, drafts=None, prefix=None):
+    def cached_speculative_generate(self, img_latent, latent_attention_mask=None, max_len=1536, draft_len=4, ngram=3, drafts=None, prefix=None, *,
+                                    loop_guard=None):
         """Speculative greedy decode with KV caching (an extension: the reference emits one token per step) -> seqs (B,T') int64, log_probs
         (B,T') fp32, mask (B,T') bool: bitwise what cached_greedy_generate returns for the same arguments, in fewer decode steps when drafts
         are accepted.  Each image owns draft_len + 1 decode rows (so B * (draft_len + 1) <= max batch size, 1 <= draft_len <= 7): one step
@@ -1240,7 +1273,9 @@ class ViTOMR(nn.Module):
         n-grams (suffixes of up to `ngram` tokens, 1..8) or taken from `drafts` (B, max_len) - the token proposed for each index, negative =
         none.  An image that ends early idles until the batch does.  Beam search, sampling, continuous batching (slot mode) and an FP8
         memory cache cannot be combined with it (ValueError): out of scope here.
-        prefix: prompted decoding as in cached_greedy_generate, bitwise its result; the prompt is consumed draft_len + 1 tokens per step."""
+        prefix: prompted decoding as in cached_greedy_generate, bitwise its result; the prompt is consumed draft_len + 1 tokens per step.
+        loop_guard: not supported here (ValueError); loops.scan_repeats covers the result after the fact."""
+        self._check_loop_guard(loop_guard, **{"speculative decoding": True})
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._speculative_packed(mem32, None, lens, max_len, draft_len, ngram, drafts, prefix=prefix)
 
@@ -1253,14 +1288,20 @@ class ViTOMR(nn.Module):
         S = blocks.max_batch_size if slots is None else slots
         return eng, caps, eng.continuous(mem32, memb, lens, caps, S, poll=poll, use_graph=use_graph, **sampling)
 
-    def _continuous_packed_iter(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True, grammar=None):
+    def _continuous_packed_iter(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True, grammar=None, loop_guard=None):
         """Continuous-batching greedy decode of packed memories: yields (index, seqs (1,T'), log_probs (1,T'), mask (1,T')) per image in
-        completion order, each what _greedy_packed of that image alone at its cap returns."""
+        completion order, each what _greedy_packed of that image alone at its cap returns (with a loop_guard: and its LoopReport)."""
         self._check_grammar(grammar)
-        eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph, grammar=grammar)
+        self._check_loop_guard(loop_guard, **{"grammar (constrained decoding)": grammar})
+        kw = {} if loop_guard is None else {"loop_guard": loop_guard}
+        eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph, grammar=grammar, **kw)
 
         def images():
             for i in run:
+                if loop_guard is not None:
+                    yield (i,) + self._loop_result(eng.cont_seqs[i:i + 1, :caps[i]], eng.cont_lps[i:i + 1, :caps[i]], [caps[i]],
+                                                   *eng.cont_loops[:, i:i + 1], loop_guard)
+                    continue
                 yield (i,) + self._mask_and_clip_capped(eng.cont_seqs[i:i + 1, :caps[i]], eng.cont_lps[i:i + 1, :caps[i]], [caps[i]])
         return images()
 
@@ -1276,21 +1317,29 @@ class ViTOMR(nn.Module):
 
     def _continuous_packed(self, mem32, memb, lens, max_len, slots=None, poll=16, use_graph=True, **sampling):
         self._check_grammar(sampling.get("grammar"))
+        guard = self._check_loop_guard(sampling.get("loop_guard"), **{"sample (sampled rollouts)": sampling.get("sample"),
+                                                                     "grammar (constrained decoding)": sampling.get("grammar")})
         eng, caps, run = self._continuous_run(mem32, memb, lens, max_len, slots, poll, use_graph, **sampling)
         for _ in run:
             pass
+        if guard is not None:
+            return self._loop_result(eng.cont_seqs, eng.cont_lps, caps, *eng.cont_loops, guard)
         return self._mask_and_clip_capped(eng.cont_seqs, eng.cont_lps, caps)
 
-    def cached_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None, prefix=None, *, grammar=None):
+    def cached_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None, prefix=None, *, grammar=None,
+                                   loop_guard=None):
         """Continuous-batching greedy decode (an extension: the reference decodes one static batch) -> seqs (N,T') int64, log_probs (N,T')
         fp32, mask (N,T') bool, as cached_greedy_generate on the same batch.  `slots` decode rows (default: the cache's max batch size)
         work through the N images in input order; a row that finishes (<eos> or its cap) is refilled with the next image while the others
         go on, so N may exceed the max batch size.  max_len: one cap for every image, or a sequence of N per-image caps (positions at or
         past an image's cap are masked).  prefix (prompted decoding, cached_greedy_generate) is not supported here: anything but None
-        raises ValueError.  grammar: constrained decoding as in cached_greedy_generate; every image gets what it gets there alone."""
+        raises ValueError.  grammar: constrained decoding as in cached_greedy_generate; every image gets what it gets there alone.
+        loop_guard: loop detection as in cached_greedy_generate - an image that loops frees its row at `stop` for the next image in the
+        queue, and a fourth value, the loops.LoopReport over the N images, is returned.  Not combinable with grammar (ValueError)."""
         self._no_prefix(prefix, "continuous batching")
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
-        return self._continuous_packed(mem32, None, lens, max_len, slots, grammar=grammar)
+        kw = {} if loop_guard is None else {"loop_guard": loop_guard}
+        return self._continuous_packed(mem32, None, lens, max_len, slots, grammar=grammar, **kw)
 
     def _check_flush_interval(self, flush_interval):
         """flush_interval of the streamed continuous-batching entry points: an int in [1, the cache's maximum sequence length]."""
@@ -1324,7 +1373,8 @@ class ViTOMR(nn.Module):
             return self._mask_and_clip_capped(eng.cont_seqs, eng.cont_lps, caps)   # (the generator's value: all rows, as _continuous_packed)
         return events()
 
-    def streamed_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None, flush_interval=25, *, grammar=None):
+    def streamed_continuous_generate(self, img_latent, latent_attention_mask=None, max_len=1536, slots=None, flush_interval=25, *, grammar=None,
+                                     loop_guard=None):
         """cached_continuous_generate as a generator of {"type", "payload"} events (an extension: the reference streams one image at a
         time), so that a caller sees every image's tokens while `slots` rows decode the batch.  Every flush_interval decode steps - sooner
         where a row reaches its cap - each image that is being decoded and has new tokens gives one STEP {"image": i, "start": t0,
@@ -1334,16 +1384,20 @@ class ViTOMR(nn.Module):
         decoded alone (iter_continuous_inference's tuple).  Within a poll the STEP events come in slot order, then the INFERENCE_FINISH of
         the rows that ended.  An image with a cap below 2 has no STEP and finishes first.  The event list is a function of the inputs,
         `slots` and flush_interval alone.  max_len, slots, grammar: as in cached_continuous_generate; a prefix is not offered.
-        flush_interval: an int in [1, the cache's max sequence length] (ValueError, at the call)."""
+        flush_interval: an int in [1, the cache's max sequence length] (ValueError, at the call).  loop_guard: not supported in a streamed
+        run (ValueError)."""
+        self._check_loop_guard(loop_guard, **{"streamed continuous batching": True})
         mem32, lens = EG.unpad_rows(img_latent, latent_attention_mask)
         return self._streamed_continuous_packed_iter(mem32, None, lens, max_len, slots, flush_interval, grammar=grammar)
 
     def streamed_cached_greedy_generate(self, img_latent, latent_attention_mask=None, max_len=1536, flush_interval=25, prefix=None, *,
-                                        grammar=None, prefill=False):
+                                        grammar=None, prefill=False, loop_guard=None):
         """Generator of {"type", "payload"} events (M:625-647); single image only.
         prefix: prompted decoding as in cached_greedy_generate; STEP events carry the forced tokens like any others.
         grammar: constrained decoding as in cached_greedy_generate (not with prefix).
-        prefill: prompt prefill as in cached_greedy_generate; the STEP events of the prefilled tokens follow each other at once."""
+        prefill: prompt prefill as in cached_greedy_generate; the STEP events of the prefilled tokens follow each other at once.
+        loop_guard: not supported in a streamed run (ValueError)."""
+        self._check_loop_guard(loop_guard, **{"streamed greedy decoding": True})
         if img_latent.shape[0] != 1:
             raise ValueError("Streamed generation only supports single image batches")
         self._check_grammar(grammar, prefix)
@@ -1456,7 +1510,7 @@ class GRPOViTOMR(ViTOMR):
         return self.cached_forward_rollout_policy(img_latent, latent_attention_mask, max_actions, top_k, temperature)
 
     def cached_forward_rollout_policy(self, img_latent, latent_attention_mask, max_actions=768, top_k=50, temperature=1.2, group_size=None,
-                                      uniforms=None, prefix=None, *, grammar=None):
+                                      uniforms=None, prefix=None, *, grammar=None, loop_guard=None):
         """Sampling rollouts with KV caching (M:988-1049): per step keep the top_k logits, draw from softmax(kept / temperature), record
         log_softmax(kept)[drawn]; rows stop mattering after their first <eos>.  Returns rollouts (R, T') int64, rollout_log_probs (R, T') fp32,
         rollout_mask (R, T') bool with padding / zero log-probs outside the mask.
@@ -1468,9 +1522,11 @@ class GRPOViTOMR(ViTOMR):
         cached_greedy_generate) is not supported here: anything but None raises ValueError.  grammar (an extension, default None = off): a
         grammar.TokenAutomaton - the top-k filter, the draw and the recorded log_softmax(kept) run over the tokens the rollout's automaton
         state allows, so a rollout cannot hold a transition the automaton forbids; rollout_log_probs is then the log-probability under the
-        constrained policy, which is the old policy of the GRPO ratio."""
+        constrained policy, which is the old policy of the GRPO ratio.  loop_guard: not supported in sampled decoding (ValueError);
+        loops.scan_repeats covers the rollouts after the fact (train/grpo.py logs their loop_rate with it)."""
         self._no_prefix(prefix, "sampling")
         self._check_grammar(grammar)
+        self._check_loop_guard(loop_guard, **{"sampling": True})
         blocks = self.decoder._cached_blocks()
         G = 1 if group_size is None else int(group_size)
         if img_latent.shape[0] % G:

@@ -1516,6 +1516,45 @@ def debug_decode_select(form, logits, seqs, logprobs, step, finished, *, max_len
                "acai_debug_decode_select")
 
 
+def debug_decode_loop_select(slot, logits, seqs, logprobs, step, finished, *, loop, max_len, Tmax, eos, bos=0, pad=0, emb=None, pos=None, x=None,
+                             round_lp=False, chained=True, slots=None, B=None, V=None, E=None):
+    """Test entry (acai_debug_decode_loop_select, see the header): one selection launch of the guarded greedy step (slot: of the guarded slot
+    step) on the logits the caller wrote.  Tensors as debug_decode_select takes them; slots = dict(t, cap) int32 [B]; loop = dict(run int32
+    [rows, 64], stop / period / start int32 [rows], max_period, min_repeats, min_tokens).  Everything is written in place."""
+    d = _lib.AcaiDecoder()
+    d.B = int(B if B is not None else logits.shape[0])
+    d.V = int(V if V is not None else logits.shape[1])
+    d.E = int(E if E is not None else (emb.shape[1] if emb is not None else 4))
+    d.max_len, d.Tmax, d.eos, d.bos, d.pad = int(max_len), int(Tmax), int(eos), int(bos), int(pad)
+    d.flags = GEMM_ROUND_BF16 if round_lp else 0
+    for name, t, dt in (("logits", logits, torch.float32), ("seqs", seqs, torch.int64), ("logprobs", logprobs, torch.float32),
+                        ("step", step, torch.int32), ("finished", finished, torch.int32), ("emb", emb, torch.float32),
+                        ("pos", pos, torch.float32), ("x", x, torch.float32)):
+        if t is not None:
+            assert _chk(t, name, dt).is_contiguous(), name
+            setattr(d, name, t.data_ptr())
+    sl = lp = None
+    if slots is not None:
+        sl = _lib.AcaiSlots()
+        for name in ("t", "cap"):
+            if slots.get(name) is not None:
+                assert _chk(slots[name], name, torch.int32).is_contiguous(), name
+                setattr(sl, name, slots[name].data_ptr())
+        sl.rows = int(slots.get("rows", d.B))
+    if loop is not None:
+        lp = _lib.AcaiLoop()
+        for name in ("run", "stop", "period", "start"):
+            if loop.get(name) is not None:
+                assert _chk(loop[name], name, torch.int32).is_contiguous(), name
+                setattr(lp, name, loop[name].data_ptr())
+        run = loop.get("run")
+        lp.rows = int(loop.get("rows", run.shape[0] if run is not None else d.B))
+        lp.max_period, lp.min_repeats, lp.min_tokens = int(loop["max_period"]), int(loop["min_repeats"]), int(loop["min_tokens"])
+    _lib.check(_lib.lib().acai_debug_decode_loop_select(1 if slot else 0, ctypes.byref(d), None if sl is None else ctypes.byref(sl),
+                                                        None if lp is None else ctypes.byref(lp), 1 if chained else 0, _st()),
+               "acai_debug_decode_loop_select")
+
+
 def debug_decode_spec_accept(logits, seqs, logprobs, step, finished, *, spec, max_len, Tmax, eos, pad=0, emb=None, pos=None, x=None,
                              round_lp=False, arm=False, prompt=None, B=None, V=None, E=None):
     """Test entry (acai_debug_decode_spec_accept, see the header): the one launch that closes a speculative step (arm: that opens the run) on
@@ -2003,6 +2042,42 @@ def grammar_scan(rollouts, rollout_mask, automaton):
                                                 nxt.shape[0], automaton.start, nxt.shape[1], automaton.eos_idx, viol.data_ptr(), comp.data_ptr(),
                                                 _st(rollouts)), "acai_grammar_scan")
     return viol, comp != 0
+
+
+def repeat_scan(tokens, max_period, min_repeats, min_tokens, lens=None):
+    """(stop, period, start, end) int32 (N,) of the loop guard's rule over the rows tokens[n, :len_n] (acai_repeat_scan, see the header; the
+    rule is stated in loops.py).  tokens (N, T) int64, a row-strided view included; lens: None (every row holds T tokens), int32 lengths
+    (N,), read on the device (no host sync), or a bool prefix mask of tokens' shape.  period == 0: the row did not fire and the other three
+    are 0; end is the last index up to which the reported period keeps holding."""
+    _chk(tokens, "tokens", torch.int64, rows_contig=False)
+    if tokens.dim() != 2:
+        raise ValueError(f"tokens: expected (rows, tokens), got {tuple(tokens.shape)}")
+    if not 1 <= int(max_period) <= 64 or int(min_repeats) < 2 or int(min_tokens) < 1:
+        raise ValueError(f"repeat_scan: needs 1 <= max_period <= 64, min_repeats >= 2, min_tokens >= 1 (got {max_period}, {min_repeats}, "
+                         f"{min_tokens})")
+    N, T = tokens.shape
+    if T and tokens.stride(1) != 1:
+        tokens = tokens.contiguous()
+    ld = _ld(tokens) if N and T else T
+    if lens is not None:
+        _chk(lens, "lens")
+        if lens.dtype == torch.bool:
+            if lens.shape != tokens.shape:
+                raise ValueError(f"lens: a mask must have tokens' shape {tuple(tokens.shape)}, got {tuple(lens.shape)}")
+            lens = lens.sum(dim=-1, dtype=torch.int32)
+        elif lens.dtype != torch.int32:
+            raise TypeError(f"lens: expected a bool mask or int32 lengths, got {lens.dtype}")
+        if lens.shape != (N,) or lens.device != tokens.device:
+            raise ValueError(f"lens: expected {N} lengths on {tokens.device}, got {tuple(lens.shape)} on {lens.device}")
+        lens = lens.clamp(max=T).contiguous()
+    elif ld != T:   # a view of wider rows: the kernel's bound without lengths is the row stride
+        lens = torch.full((N,), T, dtype=torch.int32, device=tokens.device)
+    out = torch.zeros(4, N, dtype=torch.int32, device=tokens.device)
+    if N and T:
+        _lib.check(_lib.lib().acai_repeat_scan(tokens.data_ptr(), _p(lens), N, ld, int(max_period), min(int(min_repeats), 1 << 24),
+                                               min(int(min_tokens), 1 << 24), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                               out[3].data_ptr(), _st(tokens)), "acai_repeat_scan")
+    return out[0], out[1], out[2], out[3]
 
 
 for _name, _fn in list(globals().items()):

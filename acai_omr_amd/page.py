@@ -1099,12 +1099,15 @@ class PageResult:
                    (page_inference(assess=));
       system_staff_space   per row, the distance from staff line to staff line in MODEL pixels - the page's `StaffScale.pitch` times the
                    resized height of the row's box over the box's height - or None: not assessed, or the page has no scale.  What
-                   `AssessConfig.min_model_staff_space` is held against, and the number a UI needs to say "move closer"."""
+                   `AssessConfig.min_model_staff_space` is held against, and the number a UI needs to say "move closer";
+      loops        one `loops.LoopReport` over the rows (stop, period, start per system; period 0 = the system did not loop), or None: the
+                   call had no loop guard (page_inference(loop_guard=))."""
 
     def __init__(self, boxes, seqs, log_probs, seq_mask, system_page, sizes, windows, specials=(), angles=None, page_sizes=None, flattened=None,
                  quads=None, source_sizes=None, inset=2, orientations=None, patches_kept=None, patches_total=None, quality=None,
-                 system_staff_space=None):
+                 system_staff_space=None, loops=None):
         self.boxes, self.seqs, self.log_probs, self.seq_mask = boxes, seqs, log_probs, seq_mask
+        self.loops = loops
         system_page = list(system_page)
         self.quality = [None] * len(boxes) if quality is None else list(quality)
         self.system_staff_space = [None] * len(system_page) if system_staff_space is None else [None if v is None else float(v) for v in system_staff_space]

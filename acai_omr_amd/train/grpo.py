@@ -290,8 +290,15 @@ def _rollouts_continuous(old_policy, img_latent, latent_attention_mask, group_si
                                                        rollout_config.temperature, slots=slots, group_size=group_size, uniforms=uniforms)
 
 
+def loop_rate(rollouts, rollout_mask, loop_guard):
+    """The share of rollouts a loops.LoopGuard's rule flags (loops.scan_repeats: one launch over the rollouts where they lie), as a 0-dim
+    fp32 tensor on their device - no host sync.  A diagnostic only: rewards do not see it."""
+    from ..loops import scan_repeats
+    return scan_repeats(rollouts, loop_guard, lens=rollout_mask).looped.float().mean()
+
+
 def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOConfig, ce_loss_fn, device, logger=None, counter=None, *, reward_fn,
-                uniforms=None, rollout_slots=None, grammar=None, fused_clip=False):
+                uniforms=None, rollout_slots=None, loop_guard=None, grammar=None, fused_clip=False):
     """One GRPO minibatch update.  batch: list of (image, target_lmx_seq, target_musicxml_str).  reward_fn(rollouts, rollout_mask, target_lmx_seqs,
     batch) -> (B, G) raw rewards, or (rewards, RewardComponents).  uniforms (R, max_actions): the rollout draws (cached_forward_rollout_policy).
     rollout_slots: None = one static batch of B * G rollout rows (B * G <= the cache's max batch size); an integer = that many decode rows
@@ -300,8 +307,11 @@ def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOCon
     stay unconstrained - pass the same automaton to make_token_reward_fn to reward what it checks.  fused_clip: clip inside the optimizer's
     own launches (`optimizer.step(max_grad_norm=1.0)`, optimizer an `optim.FusedAdamW`) instead of `torch.nn.utils.clip_grad_norm_`: one read of
     the gradients instead of three, a non-finite norm skips the step, and `optimizer.grad_norm` / `clip_coef` / `skipped_steps` report it without
-    a host round trip.  Returns (avg loss over update epochs, avg CE loss, avg raw reward, avg reward components
-    or None)."""
+    a host round trip.  loop_guard: a loops.LoopGuard - with a logger, the share of this minibatch's rollouts its rule flags is logged
+    (`logger.log_loop_rate(rate, step)`, loop_rate above); the rollouts are NOT guarded and the rewards are untouched.  Returns (avg loss
+    over update epochs, avg CE loss, avg raw reward, avg reward components or None)."""
+    from ..loops import check_guard
+    check_guard(loop_guard)
     if fused_clip and not isinstance(optimizer, FusedAdamW):
         raise ValueError(f"grpo_update: fused_clip needs an optim.FusedAdamW, got {type(optimizer).__name__}")
     rollout_config, reward_config, loss_config, update_config = grpo_config.get_configs()
@@ -331,6 +341,8 @@ def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOCon
         logger.log_raw_reward_stats(raw_group_rewards, counter.global_step)
         if reward_components is not None:
             logger.log_raw_reward_components(reward_components, counter.global_step)
+        if loop_guard is not None:
+            logger.log_loop_rate(loop_rate(rollouts, rollout_mask, loop_guard), counter.global_step)
     group_advantages = (raw_group_rewards - raw_group_rewards.mean(dim=-1, keepdim=True)) / (raw_group_rewards.std(dim=-1, keepdim=True) + 1e-8)
     advantages = group_advantages.view(-1)
     if logger is not None:
@@ -379,7 +391,7 @@ def grpo_update(old_policy, policy_theta, optimizer, batch, grpo_config: GRPOCon
 
 # ---- validation (omr_grpo_train.py:456-492) -----------------------------------------------------------------------------------------------
 def validation_loop(dataloader, policy_theta, reward_config, rollout_config, ce_loss_fn, pad_idx, device, *, reward_fn=None, slots=None,
-                    uniforms_fn=None, autocast_dtype=torch.bfloat16, grammar=None):
+                    uniforms_fn=None, autocast_dtype=torch.bfloat16, grammar=None, loop_guard=None, logger=None):
     """Mini or full validation, depending on the dataloader: one sampled rollout per image (group size 1) at rollout_config's max_actions /
     top_k / temperature, scored by reward_fn, and the teacher-forced CE loss of each batch.  Returns (mean raw reward, mean RewardComponents,
     mean CE loss), each a mean over batches of per-batch means, as the reference computes them.
@@ -390,7 +402,12 @@ def validation_loop(dataloader, policy_theta, reward_config, rollout_config, ce_
     max_actions.  reward_fn: as grpo_update's (default make_token_reward_fn(reward_config, pad_idx): the token-level edit cost in the place
     of the reference's tree edit cost).  uniforms_fn(batch_index, R, max_actions) -> (R, max_actions) uniforms fixes the draws (default:
     torch's generator).  autocast_dtype: the reference validates under bf16 autocast; None runs without autocast.  grammar: a
-    grammar.TokenAutomaton that constrains the rollouts and, with the default reward_fn, scores their well-formedness."""
+    grammar.TokenAutomaton that constrains the rollouts and, with the default reward_fn, scores their well-formedness.  loop_guard with
+    logger: the share of the rollouts a loops.LoopGuard's rule flags, a mean over batches like the rest, goes to
+    `logger.log_loop_rate(rate, None)`; the rollouts are not guarded and what is returned does not change."""
+    from ..loops import check_guard
+    check_guard(loop_guard)
+    validation_loop_rate = 0
     if reward_fn is None:
         reward_fn = make_token_reward_fn(reward_config, pad_idx, grammar=grammar)
     dev_type = torch.device(device).type
@@ -421,7 +438,11 @@ def validation_loop(dataloader, policy_theta, reward_config, rollout_config, ce_
             validation_reward += raw_rewards.float().mean().item()
             if reward_components is not None:
                 validation_reward_components += reward_components.avg_over_rollouts()
+            if loop_guard is not None and logger is not None:
+                validation_loop_rate = validation_loop_rate + loop_rate(rollouts, rollout_mask, loop_guard)
             validation_ce_loss += calc_teacher_forced_ce_loss(policy_theta, img_latent, latent_attention_mask, target_lmx_seqs, ce_loss_fn).item()
+    if loop_guard is not None and logger is not None:
+        logger.log_loop_rate(validation_loop_rate / num_batches, None)
     return validation_reward / num_batches, validation_reward_components / num_batches, validation_ce_loss / num_batches
 
 

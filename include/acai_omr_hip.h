@@ -810,6 +810,49 @@ int acai_decode_slot_grammar_sample_step(const AcaiDecoder *d, const AcaiSlots *
  * memory otherwise.  One launch, no host synchronisation, no allocation (capturable).  1 <= states <= 32767, 0 <= start < states, V >= 1. */
 int acai_grammar_scan(const int64_t *tokens, int ld, const int32_t *lens, int R, const int16_t *next, const int16_t *resync, int states, int start,
                       int V, int eos, int32_t *violations, int32_t *complete, void *stream);
+/* The loop guard (an extension: the reference lets a row that fell into a repeat cycle run to its cap).  One rule for the steps below,
+ * acai_repeat_scan and the tests.  With P = max_period, R = min_repeats, M = min_tokens and need(p) = max((R - 1) p, M): index 0 is <bos> and
+ * never takes part; run_p(t) is the number of consecutive indices i ending at t with seq[i] == seq[i - p] and i - p >= 1.  A row fires at
+ * the first t at which some p in 1 .. P has run_p(t) >= need(p); the smallest such p wins.  The report is stop = t, period = p and
+ * start = t - need(p) - p + 1, the first index of the periodic stretch; a row that never fires keeps period = 0.  All arrays are device memory:
+ *   run:                  [rows][64] int32, run_p of row b in run[b][p - 1]; entries at and past P hold 0;
+ *   stop, period, start:  [rows] int32, the report.
+ * The caller zeroes a row's 64 counters and three report words before the row's first step (slot mode: when it arms the slot). */
+typedef struct {
+    int32_t *run;
+    int32_t *stop;
+    int32_t *period;
+    int32_t *start;
+    int32_t rows;          /* rows of the four arrays, >= dec->B */
+    int32_t max_period;    /* P, 1 .. 64 */
+    int32_t min_repeats;   /* R >= 2 */
+    int32_t min_tokens;    /* M >= 1 */
+} AcaiLoop;
+/* One GUARDED greedy step: acai_decode_step, whose selection launch also applies the rule to every unfinished row - the wave that chose
+ * the row's token compares it with the row's tokens 1 .. P indices back and updates run[b][] (O(1) a step; the row is not scanned).  A row
+ * that fires keeps the token at t, gets finished[b] = 1 and leaves the unfinished count; no <eos> is written, and the row goes on emitting
+ * like any finished row.  If the token at t is <eos> the row ends as acai_decode_step ends it and no report is written.  A finished row is
+ * not examined and its counters stand.  With a guard that cannot fire the step is acai_decode_step bit for bit.  Same checks and x contract
+ * as acai_decode_step, plus non-null run / stop / period / start, rows >= B, 1 <= max_period <= 64, min_repeats >= 2, min_tokens >= 1.
+ * Enqueues kernels only (capturable); no launch is added to acai_decode_step's. */
+int acai_decode_loop_step(const AcaiDecoder *d, const AcaiLoop *loop, void *stream);
+/* The SLOT-MODE form: acai_decode_slot_step in which a row also finishes when it fires - finished = <eos> or cap or loop, and t[b] is left
+ * at the row's last token as for a cap.  A finished or idle row reads and writes nothing of the guard's.  Checks: the slot step's and
+ * acai_decode_loop_step's. */
+int acai_decode_slot_loop_step(const AcaiDecoder *d, const AcaiSlots *sl, const AcaiLoop *loop, void *stream);
+/* TEST ENTRY (tests/test_gpu_loop_select.py): ONE selection launch of acai_decode_loop_step (slot == 0) or acai_decode_slot_loop_step
+ * (slot != 0; sl as acai_debug_decode_select's slot forms take it) on logits the caller wrote, with acai_debug_decode_select's contract for
+ * the descriptor, `chained` and the preconditions.  Refused (rc < 0, nothing launched): a null decoder, logits, step, finished, seqs or
+ * logprobs; B, V, E or Tmax < 1 or max_len < 2; chained with a null emb / pos / x or E % 4 != 0; slot with chained == 0, null t / cap,
+ * rows < B or max_len > Tmax; and what acai_decode_loop_step refuses of `loop`. */
+int acai_debug_decode_loop_select(int slot, const AcaiDecoder *d, const AcaiSlots *sl, const AcaiLoop *loop, int chained, void *stream);
+/* The same rule over N finished token rows (loops.hip): rows from any decode mode, and metrics.  tokens [N][ld] int64 (row stride = ld);
+ * lens [N] int32, read ON THE DEVICE and clamped to [0, ld], or NULL for rows of ld tokens.  One wave per row sweeps t forward with the
+ * counters in registers.  Row n gets stop[n], period[n], start[n] of its first firing and end[n], the last index below its length up to
+ * which seq[i] == seq[i - period] keeps holding from stop on; a row that never fires gets four zeros.  An <eos> is a token like any other
+ * here: bound a row by lens to leave it out.  One launch, no host synchronisation, no allocation (capturable). */
+int acai_repeat_scan(const int64_t *tokens, const int32_t *lens, int N, int ld, int max_period, int min_repeats, int min_tokens, int32_t *stop,
+                     int32_t *period, int32_t *start, int32_t *end, void *stream);
 /* The same without the token bookkeeping: logits for caller-supplied tokens/time_step (OMRDecoder.cached_generate). */
 int acai_decode_logits(const AcaiDecoder *dec, const int64_t *tokens, int time_step, void *stream);
 
